@@ -120,6 +120,9 @@ def parse():
     ap.add_argument("--profile-iters", type=int, default=8, help="per-launch hipEvent passes (each over the next batch of the scene ring)")
     ap.add_argument("--dump-launches", default="", help="write the per-launch hipEvent table to this file")
     ap.add_argument("--detail", default="", help="where the full record goes (default: bench_detail.json next to bench.py, and gpurun_out/ when it exists)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps of the main configuration, write what its last step handed the caller "
+                    "(rank 0's composites and masks) to DIR/composite.npy and DIR/mask.npy as float32, at most 60 MB in all (a fixed, seeded sample of the streams "
+                    "when the batch is larger) — with the same arguments the inputs are the same bytes every run, so two builds compare output for output")
     ap.add_argument("--selftest-dist", action="store_true", help="CPU plumbing test of the multi-process path (gloo): launch, rendezvous, counter all-reduce, JSON line — no GPU work")
     a = ap.parse_args()
     return a
@@ -402,6 +405,29 @@ def solo_reference(coll, rank, fn):
     return v
 
 
+DUMP_BYTES = 60_000_000    # --dump-outputs: bytes of array data in all (under 64 MB with the .npy headers)
+
+
+def dump_step_outputs(out_dir, d_out, d_masks):
+    """--dump-outputs: the composites [B,H,W,3] and masks [B,H,W] of one step as float32 DIR/composite.npy, DIR/mask.npy.  A batch larger than DUMP_BYTES is
+    cut to whole streams picked by a fixed seed (sorted), or — when one stream alone is too large — to pixels picked the same way: the same sample every run."""
+    import numpy as np
+    import torch
+    B, H, W = d_masks.shape
+    cap = DUMP_BYTES // (4 * (3 + 1))                            # pixels whose composite (3 x f32) and mask (f32) fit
+    rng = np.random.default_rng(0xD5)
+    comp, mask = d_out[:B], d_masks
+    if B * H * W > cap and H * W <= cap:
+        sel = torch.from_numpy(np.sort(rng.choice(B, cap // (H * W), replace=False))).to(d_out.device)
+        comp, mask = comp.index_select(0, sel), mask.index_select(0, sel)
+    elif B * H * W > cap:
+        sel = torch.from_numpy(np.sort(rng.choice(B * H * W, cap, replace=False))).to(d_out.device)
+        comp, mask = comp.reshape(-1, 3).index_select(0, sel), mask.reshape(-1).index_select(0, sel)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "composite.npy"), comp.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "mask.npy"), mask.cpu().numpy().astype(np.float32))
+
+
 # ------------------------------------------------------------------------------------------------------------------------------
 # one measured configuration
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -425,7 +451,7 @@ def scene_ring(base, B, T, W, seed):
 
 
 def measure(model_key, W, H, B, steps, warmup, rank, world, local_rank, per_stream_bg=False, bg_ring=False, bg_source="", profile_iters=8, dump_launches="", ramp_s=0.0, coll=None,
-            profile=True, moving=True, static_leg=False, parity_streams=2, parity_steps=0):
+            profile=True, moving=True, static_leg=False, parity_streams=2, parity_steps=0, dump_outputs=""):
     """Run one configuration on this rank's GPU.  Returns a dict with the timed result and (rank 0) the per-launch profile and
     the samples the parity leg needs.  `coll` (backscrub_amd.dist.Collective) carries the barriers around the timed region and the one
     reduction of the job; None = this rank alone (N = 1, and rank 0's solo reference run at N > 1)."""
@@ -509,6 +535,8 @@ def measure(model_key, W, H, B, steps, warmup, rank, world, local_rank, per_stre
 
     checksum = int(d_out[:, ::16, ::16].to(torch.int64).sum().item())
     total_frames, max_elapsed, checksum_all, rank_fps = finish_counters(coll, B * steps, elapsed, checksum)     # the only collective of the job
+    if dump_outputs and rank == 0:        # the last timed step's results, before anything below steps the context again
+        dump_step_outputs(dump_outputs, d_out, mg.masks()[:B])
     res = {"model_path": model_path, "model_name": model_name, "weights": weights, "B": B, "W": W, "H": H, "photo": photo, "ring": T,
            "fps": total_frames / max_elapsed, "ms_per_step": 1e3 * max_elapsed / steps, "checksum": checksum_all, "mg": mg, "rank_fps": rank_fps,
            "frames_ring": ring, "d_bg": d_bg, "d_out": d_out, "bg_host": bg_host, "steps": steps, "warmup": warmup}
@@ -1086,7 +1114,8 @@ def main():
             return fps
         solo1 = solo_reference(coll, rank, solo_main)
     res = measure(args.model, W, H, B, args.steps, args.warmup, rank, world, local_rank, ramp_s=args.ramp_seconds, per_stream_bg=args.per_stream_bg, bg_ring=args.bg_ring,
-                  profile_iters=args.profile_iters, dump_launches=args.dump_launches, coll=coll, moving=moving, static_leg=side, parity_streams=4)
+                  profile_iters=args.profile_iters, dump_launches=args.dump_launches, coll=coll, moving=moving, static_leg=side, parity_streams=4,
+                  dump_outputs=args.dump_outputs)
     multi = None
     c4_frag = c4_parity_in = None
     if coll is not None:

@@ -1,4 +1,3 @@
-import glob
 import os
 import sys
 
@@ -13,8 +12,11 @@ def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
 
 
+REFERENCE_MODELS = os.path.join(ROOT, "tests", "golden", "reference_models")
+
+
 def _real_models():
-    return sorted(glob.glob(os.path.join(ROOT, "models", "*.tflite")))
+    return sorted(p for p in (reference_model_path(k) for k in MODEL_KEYS) if os.path.exists(p))
 
 
 MODEL_KEYS = {
@@ -25,11 +27,17 @@ MODEL_KEYS = {
 }
 
 
+def reference_model_path(key):
+    """The reference's real .tflite: the test fixture under tests/golden/reference_models (the Meet and MLKit models; DeepLab's
+    2.7 MB file is not kept in the repository), else a copy staged into models/ by tools/stage_models.py from a reference checkout."""
+    fixture = os.path.join(REFERENCE_MODELS, MODEL_KEYS[key])
+    return fixture if os.path.exists(fixture) else os.path.join(ROOT, "models", MODEL_KEYS[key])
+
+
 def model_path(key, prefer_real=True):
-    """Path of a model for tests: the reference's real .tflite when it was staged into
-    models/ (tools/stage_models.py; git-ignored, travels to the GPU box), else the synthetic
+    """Path of a model for tests: the reference's real .tflite (reference_model_path), else the synthetic
     same-architecture model with seeded random weights under tests/golden/models."""
-    real = os.path.join(ROOT, "models", MODEL_KEYS[key])
+    real = reference_model_path(key)
     if prefer_real and os.path.exists(real):
         return real
     return synthetic_model_path(key)

@@ -646,9 +646,12 @@ def test_end_to_end_on_the_photo_fixture(bs, oracle, key):
     mg.close()
 
 
-def test_deeplab_argmax_agreement(bs, oracle):
-    """DeepLab rarely fires 'person' on synthetic frames, so also compare the full 21-way argmax map."""
+def test_deeplab_argmax_agreement(bs, oracle, monkeypatch, debug_switches):
+    """DeepLab rarely fires 'person' on synthetic frames, so also compare the full 21-way argmax map.  The default batched call decodes
+    straight from the 33x33 logits (the final resize is fused with the argmax) and keeps no full-resolution logits; BSX_KEEP_LOGITS
+    (debug library) makes the same call write them."""
     from backscrub_amd import synth
+    monkeypatch.setenv("BSX_KEEP_LOGITS", "1")
     path = model_path("deeplab")
     W, H = VGA
     mg = bs.MaskGen(path, W, H, n_streams=1)

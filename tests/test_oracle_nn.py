@@ -146,11 +146,11 @@ def test_decision_margin_audit(oracle, key):
     the oracle gives the worst-case full-resolution mask after IIR + upscale + blur, and its IoU with the oracle's mask is the floor for "IoU vs the real reference".
     The numbers are recorded in DESIGN.md §2; the assertions keep them from silently degrading."""
     import os
-    from conftest import MODEL_KEYS, ROOT
+    from conftest import reference_model_path
     import f64_graph
-    path = os.path.join(ROOT, "models", MODEL_KEYS[key])
+    path = reference_model_path(key)
     if not os.path.exists(path):
-        pytest.skip("real weights not staged (models/): the audit is about the shipped models")
+        pytest.skip("real weights neither a fixture nor staged into models/: the audit is about the shipped models")
     kind, (W, H) = AUDIT[key]
     report = []
     for name, frame in _scenes(W, H):

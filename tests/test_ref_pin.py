@@ -5,7 +5,15 @@ compiled unmodified (oracle/Makefile `ref-lib`) against API shims whose OpenCV /
 the oracle's restatement.  So every comparison below isolates reference code: bs_maskgen_* glue and geometry, the decode
 loops + IIR, Convolution2DTransposeBias Prepare/Eval, alpha_blend, the YUYV packing loop.  Rows pinned: SURVEY §8 a1, a2,
 a10-a14, a17, a19, a20, f1 (packing).  NOT pinned by this (third-party, absent from the checkout): cv::resize, cvtColor,
-bilateralFilter, blur, convertTo and the TFLite builtin kernels (rows a3-a9, a15, a16, a18)."""
+bilateralFilter, blur, convertTo and the TFLite builtin kernels (rows a3-a9, a15, a16, a18).
+
+Where the reference's object code cannot be had (no oracle/_ref/libbs_ref.so and no reference checkout to build it from),
+the reference side of every comparison is its recording: SHA-256 digests of the reference's results on the very same
+inputs, in tests/golden/ref_pin_digests.json (tools/make_ref_pin.py, run where the library exists).  Where it can be had,
+the reference runs live and is held to the recording as well.  The cases that run a network are recorded under the name of
+the model file they ran (conftest.model_path: the reference's model where the repository has it, else the synthetic one)."""
+import hashlib
+import json
 import os
 import shutil
 import tempfile
@@ -13,13 +21,18 @@ import tempfile
 import numpy as np
 import pytest
 
-from conftest import model_path
+from conftest import ROOT, model_path
 from oracle import oracle_py, ref_py
 
-pytestmark = pytest.mark.skipif(not ref_py.available(), reason="oracle/_ref/libbs_ref.so absent and no reference checkout to build it from")
+RECORDED = os.path.join(ROOT, "tests", "golden", "ref_pin_digests.json")
+_RECORDING = None          # tools/make_ref_pin.py: a dict that collects the live reference results instead of checking them
 
 GEOMS = [("mlkit", 640, 480), ("lite", 640, 480), ("mlkit", 1280, 720), ("full", 1280, 720), ("lite", 1280, 720), ("full", 640, 480),
          ("lite", 322, 242), ("lite", 160, 96)]
+DECODE_KEYS = ["lite", "mlkit", "deeplab"]
+TCONV = [(48, 80, 16, 2, 2, 2, 1), (16, 16, 16, 1, 2, 2, 1), (5, 7, 4, 3, 3, 2, 1), (5, 7, 4, 3, 3, 2, 2),
+         (6, 5, 8, 2, 4, 2, 1), (4, 4, 3, 5, 3, 1, 1), (3, 9, 2, 2, 2, 3, 2), (7, 3, 5, 1, 5, 3, 1)]
+YUYV = [(640, 480), (2, 2), (322, 242), (6, 1)]
 
 
 def _frames(w, h, n, seed):
@@ -27,30 +40,75 @@ def _frames(w, h, n, seed):
     return [synth.frame(w, h, seed, t) for t in range(n)]
 
 
+def _digest(*arrays):
+    d = hashlib.sha256()
+    for a in arrays:
+        a = np.ascontiguousarray(a)
+        d.update(("%s%s;" % (a.dtype.str, a.shape)).encode())
+        d.update(a.tobytes())
+    return d.hexdigest()[:32]
+
+
+def reference(case, live):
+    """→ the digests of the reference object code's results for `case`: live() through oracle/_ref/libbs_ref.so where it can be had (and then held to the
+    recording too), else the recording."""
+    if _RECORDING is not None:
+        _RECORDING[case] = live()
+        return _RECORDING[case]
+    with open(RECORDED) as f:
+        rec = json.load(f).get(case)
+    if not ref_py.available():
+        assert rec is not None, "%s: no recording in tests/golden/ref_pin_digests.json (tools/make_ref_pin.py)" % case
+        return rec
+    got = live()
+    assert rec is None or got == rec, "%s: the reference's object code no longer gives the recorded results (re-run tools/make_ref_pin.py if the inputs changed)" % case
+    return got
+
+
+def _ref_process(path, w, h, frames, forced=None):
+    """bs_maskgen_new + one bs_maskgen_process per frame (forced: logits handed to the decode in place of the network's) → digest of (mask, ofinal) per call"""
+    ref = ref_py.RefMaskGen(path, w, h)
+    assert ref.ok()
+    out = []
+    for i, f in enumerate(frames):
+        with np.errstate(all="ignore"):
+            mask = ref.process(f, forced_output=None if forced is None else forced[i])
+        assert mask is not None
+        out.append(_digest(mask, ref.last_ofinal()))
+    ref.close()
+    return out
+
+
 @pytest.mark.parametrize("key,w,h", GEOMS)
 def test_whole_process_matches_reference_object_code(key, w, h):
     """bs_maskgen_new + 3 x bs_maskgen_process of the reference vs the oracle's Ctx: identical masks (geometry, state,
     decode+IIR, tconv inside the network, call order) on the SURVEY §8 frame x model pairs and two odd sizes."""
     path = model_path(key)
-    ref = ref_py.RefMaskGen(path, w, h)
-    assert ref.ok()
+    frames = _frames(w, h, 3, seed=7)
+    want = reference("whole_process/%s/%dx%d" % (os.path.basename(path), w, h), lambda: _ref_process(path, w, h, frames))
     oc = oracle_py.Ctx(path, w, h)
-    for f in _frames(w, h, 3, seed=7):
-        got, want = ref.process(f), oc.process(f)
-        assert got is not None
-        assert np.array_equal(got, want)
-        q = oc.in_roidim
-        assert np.array_equal(ref.last_ofinal(), oc.ofinal()[q[1]:q[1] + q[3], q[0]:q[0] + q[2]])
-    ref.close(); oc.close()
+    q = oc.in_roidim
+    got = []
+    for f in frames:
+        m = oc.process(f)
+        got.append(_digest(m, oc.ofinal()[q[1]:q[1] + q[3], q[0]:q[0] + q[2]]))
+    oc.close()
+    assert got == want
 
 
 def test_whole_process_deeplab_one_frame():
     path = model_path("deeplab")
-    ref = ref_py.RefMaskGen(path, 640, 480)
-    oc = oracle_py.Ctx(path, 640, 480)
     f = _frames(640, 480, 1, seed=3)[0]
-    assert np.array_equal(ref.process(f), oc.process(f))
-    ref.close(); oc.close()
+
+    def live():
+        ref = ref_py.RefMaskGen(path, 640, 480)
+        m = ref.process(f)
+        ref.close()
+        return [_digest(m)]
+    want = reference("whole_process/%s/640x480/1" % os.path.basename(path), live)
+    oc = oracle_py.Ctx(path, 640, 480)
+    assert [_digest(oc.process(f))] == want
+    oc.close()
 
 
 def _adversarial_logits(modeltype, shape, rng):
@@ -84,34 +142,32 @@ def _adversarial_logits(modeltype, shape, rng):
     return x.reshape(shape)
 
 
-@pytest.mark.parametrize("key", ["lite", "mlkit", "deeplab"])
+@pytest.mark.parametrize("key", DECODE_KEYS)
 def test_decode_and_iir_match_reference_loops(key):
     """lib/libbackscrub.cc:317-357 through the reference's object code on adversarial logits, 5 frames deep (the IIR state
     walks 0x00 → 0xE0 → 0xFC → 0xFF and back), vs oracle decode_iir; and the mask the reference builds from that state
     (ROI placement, persistent 255 border) vs the oracle's post stage."""
     path = model_path(key)
     w, h = 640, 480
-    ref = ref_py.RefMaskGen(path, w, h)
     oc = oracle_py.Ctx(path, w, h)
     rng = np.random.default_rng(11)
     frame = _frames(w, h, 1, seed=1)[0]
+    logits = [_adversarial_logits(oc.modeltype, (oc.outH, oc.outW, oc.outC), rng) for _ in range(5)]
+    want = reference("decode_iir/%s" % os.path.basename(path), lambda: _ref_process(path, w, h, [frame] * 5, forced=logits))
     state = np.zeros((oc.outH, oc.outW), np.uint8)
     q = oc.in_roidim
+    got = []
     for t in range(5):
-        logits = _adversarial_logits(oc.modeltype, (oc.outH, oc.outW, oc.outC), rng)
-        with np.errstate(all="ignore"):
-            mask = ref.process(frame, forced_output=logits)
-        assert mask is not None
-        state = oracle_py.decode_iir(oc.modeltype, logits, state)
-        assert np.array_equal(ref.last_ofinal(), state[q[1]:q[1] + q[3], q[0]:q[0] + q[2]]), "frame %d" % t
-        oc.set_output(logits)
-        assert np.array_equal(mask, oc.post()), "frame %d" % t
+        state = oracle_py.decode_iir(oc.modeltype, logits[t], state)
+        oc.set_output(logits[t])
+        got.append(_digest(oc.post(), state[q[1]:q[1] + q[3], q[0]:q[0] + q[2]]))
         assert np.array_equal(oc.ofinal(), state)
-    ref.close(); oc.close()
+    oc.close()
+    for t in range(5):
+        assert got[t] == want[t], "frame %d" % t
 
 
-@pytest.mark.parametrize("H,W,Ci,Co,k,s,padding", [(48, 80, 16, 2, 2, 2, 1), (16, 16, 16, 1, 2, 2, 1), (5, 7, 4, 3, 3, 2, 1), (5, 7, 4, 3, 3, 2, 2),
-                                                  (6, 5, 8, 2, 4, 2, 1), (4, 4, 3, 5, 3, 1, 1), (3, 9, 2, 2, 2, 3, 2), (7, 3, 5, 1, 5, 3, 1)])
+@pytest.mark.parametrize("H,W,Ci,Co,k,s,padding", TCONV)
 def test_transpose_conv_bias_matches_reference_op(H, W, Ci, Co, k, s, padding):
     """Convolution2DTransposeBias: the reference's registered Prepare (output shape, :118-186) + Eval (padding arithmetic and
     scatter loops, :188-256 → :37-114) vs the oracle restatement — shipped shapes (k = s = 2, SAME) and overlapping /
@@ -120,10 +176,8 @@ def test_transpose_conv_bias_matches_reference_op(H, W, Ci, Co, k, s, padding):
     x = rng.normal(0, 1, (1, H, W, Ci)).astype(np.float32)
     w = rng.normal(0, 0.5, (Co, k, k, Ci)).astype(np.float32)
     b = rng.normal(0, 1, Co).astype(np.float32)
-    got = ref_py.tconv_bias(x, w, b, padding, (s, s))
-    want = oracle_py.tconv_bias(x, w, b, padding, (s, s))
-    assert got.shape == want.shape
-    assert np.array_equal(got, want)
+    want = reference("tconv_bias/%d,%d,%d,%d,%d,%d,%d" % (H, W, Ci, Co, k, s, padding), lambda: [_digest(ref_py.tconv_bias(x, w, b, padding, (s, s)))])
+    assert [_digest(oracle_py.tconv_bias(x, w, b, padding, (s, s)))] == want
 
 
 def test_alpha_blend_all_byte_triples_match_reference():
@@ -133,10 +187,11 @@ def test_alpha_blend_all_byte_triples_match_reference():
     # channel 0 enumerates every (bg=a, frame=b, m); the other channels carry other pairings of the same mask byte
     bg = np.stack([a.reshape(4096, 4096), b.reshape(4096, 4096), (a ^ b).reshape(4096, 4096)], -1)
     fr = np.stack([b.reshape(4096, 4096), a.reshape(4096, 4096), (255 - a).reshape(4096, 4096)], -1)
-    assert np.array_equal(ref_py.alpha_blend(bg, fr, m2), oracle_py.alpha_blend(bg, fr, m2))
+    want = reference("alpha_blend/all_byte_triples", lambda: [_digest(ref_py.alpha_blend(bg, fr, m2))])
+    assert [_digest(oracle_py.alpha_blend(bg, fr, m2))] == want
 
 
-@pytest.mark.parametrize("w,h", [(640, 480), (2, 2), (322, 242), (6, 1)])
+@pytest.mark.parametrize("w,h", YUYV)
 def test_yuyv_packing_matches_reference(w, h):
     """convert_rgb_to_yuyv (app/deepseg.cc:87-106): split + 4:2:2 packing (Y0 V Y1 U, truncating chroma mean) are the
     reference's; the RGB2YUV colour matrix underneath is the oracle's OpenCV restatement on both sides."""
@@ -144,9 +199,11 @@ def test_yuyv_packing_matches_reference(w, h):
     img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
     edge = np.array([[255, 255, 255], [0, 0, 0], [255, 0, 0], [0, 255, 0], [0, 0, 255], [254, 1, 128]], np.uint8)
     img[0, : min(w, 6)] = edge[: min(w, 6)]
-    assert np.array_equal(ref_py.convert_rgb_to_yuyv(img), oracle_py.bgr_to_yuyv(img))
+    want = reference("yuyv/%dx%d" % (w, h), lambda: [_digest(ref_py.convert_rgb_to_yuyv(img))])
+    assert [_digest(oracle_py.bgr_to_yuyv(img))] == want
 
 
+@pytest.mark.skipif(not ref_py.available(), reason="the reference's own behaviour: needs oracle/_ref/libbs_ref.so or a reference checkout to build it from")
 def test_reference_interface_behaviour():
     """Error / callback / aliasing behaviour of the reference itself, which tests/test_shim.py and test_cabi.py assert for
     the product: NULL on a missing file and on an unknown model name, false on a NULL context, callbacks in the order

@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from conftest import MODEL_KEYS, ROOT
+from conftest import MODEL_KEYS, reference_model_path
 from backscrub_amd import tflite_io as T
 from tools import make_synthetic_model as S
 
@@ -24,9 +24,9 @@ def _signature(m):
 
 @pytest.mark.parametrize("key", list(MODEL_KEYS))
 def test_synthetic_matches_reference_architecture(key):
-    real = os.path.join(ROOT, "models", MODEL_KEYS[key])
+    real = reference_model_path(key)
     if not os.path.exists(real):
-        pytest.skip("reference model not staged (only available where /root/reference exists)")
+        pytest.skip("reference model neither a fixture nor staged into models/")
     a, b = _signature(T.load(real)), _signature(T.loads(T.dumps(S.build(key))))
     assert a == b, "missing %s\nextra %s" % (list((a - b).items())[:5], list((b - a).items())[:5])
 
