@@ -57,6 +57,7 @@ SYMBOLS = [
     ("bsx_step_batch_yuyv", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),
     ("bsx_step_batch_ex", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_uint]),
     ("bsx_step_batch_pipelined", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_uint]),
+    ("bsx_step_batch_vcam", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint]),
     ("bsx_resize_bgr", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("bsx_bgr_to_yuyv", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("bsx_yuyv_to_bgr", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -207,6 +208,25 @@ class MaskGen:
         flags = (1 if yuyv else 0) | (2 if flip_h else 0) | (4 if flip_v else 0) | (8 if no_mask else 0) | (16 if yuyv_in else 0) | ((int(bgblur) & 255) << 8)
         _check(lib().bsx_step_batch_ex(self.h, C.c_void_p(frames.data_ptr()), C.c_void_p(bg.data_ptr() if bg is not None else None), stride,
                                        C.c_void_p(out.data_ptr()), n, _stream_ptr(), flags), self.h, "bsx_step_batch_ex")
+        return out
+
+    def step_vcam(self, frames, bg, out, flip_h=False, flip_v=False, yuyv=False, yuyv_in=False, bgblur=0):
+        """one main-loop iteration at the virtual camera's geometry (--vg, app/deepseg.cc:634-681): blend, flip, cv::resize to out's size and optionally the
+        YUYV pack in one pass (bsx_step_batch_vcam).  out: contiguous cuda uint8 [>=n, out_h, out_w, 3], or [.., 2] with yuyv; out_w, out_h come from its shape."""
+        ch = 2 if yuyv else 3
+        if (out.dim() != 4 or out.shape[3] != ch or out.shape[1] <= 0 or out.shape[2] <= 0 or not out.is_contiguous() or not out.is_cuda
+                or out.dtype != _torch().uint8 or (yuyv and out.shape[2] % 2)):
+            raise BsxError("out must be a contiguous cuda uint8 tensor [n,out_h,out_w,%d]%s" % (ch, " with an even out_w" if yuyv else ""))
+        n = self._n(frames, yuyv_in)
+        if out.shape[0] < n:
+            raise BsxError("out holds %d frames, the batch has %d" % (out.shape[0], n))
+        if bg is None and not bgblur:
+            raise BsxError("bg is required unless bgblur is set")
+        stride = 0 if bg is None else self._bg(bg, n)
+        out_h, out_w = int(out.shape[1]), int(out.shape[2])
+        flags = (1 if yuyv else 0) | (2 if flip_h else 0) | (4 if flip_v else 0) | (16 if yuyv_in else 0) | ((int(bgblur) & 255) << 8)
+        _check(lib().bsx_step_batch_vcam(self.h, C.c_void_p(frames.data_ptr()), C.c_void_p(bg.data_ptr() if bg is not None else None), stride,
+                                         C.c_void_p(out.data_ptr()), out_w, out_h, n, _stream_ptr(), flags), self.h, "bsx_step_batch_vcam")
         return out
 
     def step_pipelined(self, frames, bg, out, flip_h=False, flip_v=False, yuyv=False, no_mask=False, yuyv_in=False):

@@ -77,6 +77,12 @@ struct DevResizeTab {
   ResizeTab tab;
   void* mem = nullptr;
 };
+// capture size -> virtual camera size (bsx_step_batch_vcam): always a linear table (the 2x2 area mode expanded to one: kernels.hpp), and whether the tile
+// footprints fit the kernel's LDS staging area
+struct VcamTab {
+  DevResizeTab d;
+  bool direct = false;
+};
 
 }  // namespace
 
@@ -131,11 +137,13 @@ struct bsx_ctx {
   uint8_t* d_tile_class = nullptr;    // [n_streams][mask tiles]: 1 / 2 = the tile's source block is all 0xFF / 0x00 (tile_class_k), read by mask_tile_k
   size_t tiles_per_frame = 0;
   std::map<std::pair<std::pair<int, int>, std::pair<int, int>>, DevResizeTab> bg_tabs;
+  std::map<std::pair<int, int>, VcamTab> vcam_tabs;   // (out_w, out_h) -> the capture -> vcam table of bsx_step_batch_vcam
   std::string last_error, plan_text;
   bool keep_logits = false;            // BSX_KEEP_LOGITS: segmented plans write the logits and run the stand-alone decode (A/B, debugging)
   bool no_mask_blend_fusion = false;   // BSX_NO_MASK_BLEND_FUSION, read once at bsx_new (no getenv on the per-step path)
   bool no_bgblur_fusion = false;       // BSX_NO_BGBLUR_FUSION: BSX_STEP_BGBLUR always as blur pass + step (the A/B switch of the single-pass form)
   bool no_mask_tile = false;           // BSX_NO_MASK_TILE (tests: the generic mask kernel), likewise
+  bool vcam_direct = false;            // BSX_VCAM_DIRECT (tests: bsx_step_batch_vcam's per-tap path on every table), likewise
   bool no_uniform_tiles = false;       // BSX_NO_UNIFORM_TILES (A/B timing, tests: every mask tile on the general path), likewise
   bool tail_generic = false;           // BSX_TAIL_GENERIC (tests: the scalar argmax scan of the DeepLab tail), likewise
   // Lanes (BSX_LANES=k, experiment): the fused step splits its batch into k contiguous groups of streams and runs each group's launch sequence on its own
@@ -511,10 +519,10 @@ int run_mask(bsx_ctx* c, int n, hipStream_t s, int slot = 0) {
                                       c->d_masks + (size_t)slot * c->width * c->height, c->width, c->height, c->roi, n, s));
   return BSX_OK;
 }
-// bs_maskgen_process for n frames whose per-stream state lives in slots [slot, slot + n)
-int process_impl(bsx_ctx* c, const uint8_t* d_frames, int n, int slot, hipStream_t s) {
+// bs_maskgen_process for n frames whose per-stream state lives in slots [slot, slot + n); yuyv_in: YUYV 4:2:2 frames (only where prep_yuyv_fusable)
+int process_impl(bsx_ctx* c, const uint8_t* d_frames, int n, int slot, hipStream_t s, bool yuyv_in = false) {
   int rc;
-  if ((rc = run_prep(c, d_frames, n, s))) return rc;
+  if ((rc = run_prep(c, d_frames, n, s, false, yuyv_in))) return rc;
   if (c->onprep) { BSX_HIP(c, hipStreamSynchronize(s)); c->onprep(c->caller_ctx); }   // :303
   const bool fused_decode = infer_decodes(c);
   if ((rc = run_infer(c, n, s, !fused_decode, slot))) return rc;
@@ -604,6 +612,7 @@ bsx_ctx* bsx_new(const char* model_path, size_t threads, size_t width, size_t he
   c->no_mask_blend_fusion = BSX_DBG_ENV("BSX_NO_MASK_BLEND_FUSION") != nullptr;
   c->no_bgblur_fusion = BSX_DBG_ENV("BSX_NO_BGBLUR_FUSION") != nullptr;
   c->no_mask_tile = BSX_DBG_ENV("BSX_NO_MASK_TILE") != nullptr;
+  c->vcam_direct = BSX_DBG_ENV("BSX_VCAM_DIRECT") != nullptr;
   c->no_uniform_tiles = getenv("BSX_NO_UNIFORM_TILES") != nullptr;
   c->tail_generic = BSX_DBG_ENV("BSX_TAIL_GENERIC") != nullptr;
   c->keep_logits = BSX_DBG_ENV("BSX_KEEP_LOGITS") != nullptr;
@@ -645,6 +654,7 @@ void bsx_delete(bsx_ctx* c) {
   void* ptrs[] = {c->d_arena, c->d_net_in, c->d_net_in_u8, c->d_net_out, c->d_weights, c->d_ofinal, c->d_masks, c->d_host_frame, c->d_bgr_scratch, c->d_bgr_scratch2, c->d_bgblur_scratch, c->d_bgr_in_scratch, c->d_color_lut, c->tab_down.mem, c->tab_up.mem, c->d_program, c->d_weights16, c->d_tile_class};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (auto& kv : c->bg_tabs) if (kv.second.mem) (void)hipFree(kv.second.mem);
+  for (auto& kv : c->vcam_tabs) if (kv.second.d.mem) (void)hipFree(kv.second.d.mem);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   for (int k = 1; k < 4; k++) { if (c->lane_stream[k]) (void)hipStreamDestroy(c->lane_stream[k]); if (c->ev_join[k]) (void)hipEventDestroy(c->ev_join[k]); }
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
@@ -877,6 +887,81 @@ int bsx_step_batch_yuyv(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg
 }
 int bsx_step_batch_ex(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_frame_stride, uint8_t* d_out, int n, void* stream, unsigned flags) {
   return step_impl(c, d_frames, d_bg, bg_frame_stride, d_out, n, stream, flags);
+}
+
+// ---- the main loop at the virtual camera's geometry (--vg, app/deepseg.cc:634-681): blend → flip → resize → YUYV pack with the resize folded in -----------------
+namespace {
+int vcam_einval(bsx_ctx* c, const char* why) {
+  c->last_error = std::string("error: bsx_step_batch_vcam: ") + why + "\n";
+  return BSX_EINVAL;
+}
+// the capture -> (out_w, out_h) table, built once per output size
+int vcam_tab(bsx_ctx* c, int out_w, int out_h, const VcamTab** out) {
+  auto key = std::make_pair(out_w, out_h);
+  auto it = c->vcam_tabs.find(key);
+  if (it == c->vcam_tabs.end()) {
+    HostResizeTab h = make_resize_tab(c->width, c->height, out_w, out_h);
+    if (h.mode == 2) {              // the 2x2 area mean as a linear table: taps 2d and 2d + 1, coefficients 1024 / 1024 (the same integers: kernels_img.hip)
+      h.mode = 0;
+      h.xofs.resize(out_w); h.xa.assign(2 * (size_t)out_w, 1024); h.yofs.resize(out_h); h.ya.assign(2 * (size_t)out_h, 1024);
+      for (int d = 0; d < out_w; d++) h.xofs[d] = 2 * d;
+      for (int d = 0; d < out_h; d++) h.yofs[d] = 2 * d;
+    }
+    VcamTab v;
+    v.direct = !vcam_tile_fits(h.xofs.data(), h.yofs.data(), h.sw, h.sh, h.dw, h.dh);
+    int rc = upload_tab(c, h, &v.d);
+    if (rc) { if (v.d.mem) (void)hipFree(v.d.mem); return rc; }
+    it = c->vcam_tabs.emplace(key, v).first;
+  }
+  *out = &it->second;
+  return BSX_OK;
+}
+int vcam_impl(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_frame_stride, uint8_t* d_out, int out_w, int out_h, int n, void* stream,
+              unsigned flags) {
+  const int bgblur = (int)((flags >> 8) & 255u);
+  if (!c) return BSX_EINVAL;
+  if (!d_frames || (!d_bg && !bgblur) || !d_out || n <= 0 || n > c->n_streams) return vcam_einval(c, "null buffer or batch size out of range");
+  if ((flags & ~(31u | 0xFF00u)) || (flags & BSX_STEP_NO_MASK)) return vcam_einval(c, "unsupported flags (the no-mask step has no vcam form)");
+  if (bgblur && (bgblur > 31 || !(bgblur & 1))) return vcam_einval(c, "background blur size must be odd and <= 31");
+  if (out_w <= 0 || out_h <= 0) return vcam_einval(c, "output size must be positive");
+  if (c->pend.active) { c->last_error = "error: a pipelined composite is pending (flush with bsx_step_batch_pipelined(ctx, NULL, ...) first)\n"; return BSX_EINVAL; }
+  const bool yuyv = (flags & BSX_STEP_YUYV) != 0, yin = (flags & BSX_STEP_YUYV_IN) != 0;
+  if (yuyv && (out_w & 1)) return vcam_einval(c, "YUYV output needs an even width");
+  if (yin && (c->width & 1)) return vcam_einval(c, "YUYV input needs an even capture width");
+  const size_t px = (size_t)c->width * c->height;
+  const uint8_t* o0 = d_out;
+  const uint8_t* o1 = d_out + (size_t)n * out_w * out_h * (yuyv ? 2 : 3);
+  if (o0 < d_frames + (size_t)n * px * (yin ? 2 : 3) && d_frames < o1) return vcam_einval(c, "output overlaps the frames");
+  if (!bgblur && o0 < d_bg + bg_frame_stride * (size_t)(n - 1) + px * 3 && d_bg < o1) return vcam_einval(c, "output overlaps the background");
+  if (out_w == c->width && out_h == c->height) return step_impl(c, d_frames, d_bg, bg_frame_stride, d_out, n, stream, flags);
+  DeviceGuard guard(c->device);
+  hipStream_t s = pick(c, stream);
+  const VcamTab* vt = nullptr;
+  int rc = vcam_tab(c, out_w, out_h, &vt);
+  if (rc) return rc;
+  if (yin && (bgblur || !prep_yuyv_fusable(c->width, c->roi, c->tab_down.tab))) {
+    // frames the fused prep cannot read as YUYV (or that a blur needs as BGR): converted once into the context's scratch, then the BGR form — as bsx_step_batch_ex
+    if (!c->d_bgr_in_scratch) BSX_HIP(c, hipMalloc(&c->d_bgr_in_scratch, (size_t)c->n_streams * px * 3));
+    BSX_HIP(c, launch_yuyv_to_bgr(d_frames, c->d_bgr_in_scratch, c->width, c->height, n, s));
+    return vcam_impl(c, c->d_bgr_in_scratch, d_bg, bg_frame_stride, d_out, out_w, out_h, n, stream, flags & ~BSX_STEP_YUYV_IN);
+  }
+  if (bgblur) {                     // background = GaussianBlur(the stream's own frame): blurred into the context's scratch, one background per stream
+    if (!c->d_bgblur_scratch) BSX_HIP(c, hipMalloc(&c->d_bgblur_scratch, (size_t)c->n_streams * px * 3));
+    BSX_HIP(c, launch_gauss_blur(d_frames, c->d_bgblur_scratch, c->width, c->height, bgblur, n, s));
+    return vcam_impl(c, d_frames, c->d_bgblur_scratch, px * 3, d_out, out_w, out_h, n, stream, flags & 0xFFu);
+  }
+  // the masks exactly as bsx_process_batch makes them (prep → network → decode → up-scale + blur into the persistent masks, callbacks included), then one pass
+  if ((rc = process_impl(c, d_frames, n, 0, s, yin))) return rc;
+  bsx_roctx::Range range("bsx:vcam");
+  BSX_HIP(c, launch_vcam_blend_resize(d_frames, yin, d_bg, bg_frame_stride, c->d_masks, d_out, c->width, c->height, vt->d.tab, vt->direct || c->vcam_direct, n, s,
+                                      flags & 7u));
+  return BSX_OK;
+}
+}  // namespace
+
+int bsx_step_batch_vcam(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_frame_stride, uint8_t* d_out, int out_w, int out_h, int n, void* stream,
+                        unsigned flags) {
+  return vcam_impl(c, d_frames, d_bg, bg_frame_stride, d_out, out_w, out_h, n, stream, flags);
 }
 
 // ---- two-deep pipeline: mask pipeline of batch k  ||  composite of batch k - 1 ------------------------------------------------------------------

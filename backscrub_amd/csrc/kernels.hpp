@@ -124,6 +124,12 @@ bool gauss_coeff_words(int ksize, int shift, uint32_t* c4 /* [4][9] */, uint32_t
 // blur + alpha blend of the frames over their own blur (deepseg.cc:652-661 without -b), the blurred image never stored; fusable = 4-byte aligned images, w % 4 == 0
 bool gauss_blend_fusable(const uint8_t* frames, const uint8_t* masks, const uint8_t* out, int w, int ksize);
 hipError_t launch_gauss_blend(const uint8_t* frames, const uint8_t* masks, uint8_t* out, int w, int h, int ksize, int n, hipStream_t s);
+// composite at the virtual camera's geometry: alpha blend → cv::flip (flags bits 1-2) → cv::resize to (tab.dw, tab.dh) → [YUYV pack (bit 0)] in one pass over
+// frames, background and the persistent masks (deepseg.cc:634-681).  `tab`: a linear table from the capture size (the 2x2 area mode expanded to one);
+// direct = !vcam_tile_fits(tab): every tap blended where it is read instead of the footprint staged in LDS.  yuyv_in: `frames` is YUYV 4:2:2
+bool vcam_tile_fits(const int* xofs, const int* yofs, int sw, int sh, int dw, int dh);
+hipError_t launch_vcam_blend_resize(const uint8_t* frames, bool yuyv_in, const uint8_t* bg, size_t bg_stride, const uint8_t* masks, uint8_t* out, int W, int H,
+                                    ResizeTab tab, bool direct, int n, hipStream_t s, unsigned flags);
 // fill
 hipError_t launch_fill_u8(uint8_t* p, uint8_t v, size_t bytes, hipStream_t s);
 

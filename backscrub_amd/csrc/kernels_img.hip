@@ -940,6 +940,156 @@ __global__ __launch_bounds__(kThreads) void fill_k(uint4* p, uint4 v, long n16) 
   if (i < n16) p[i] = v;
 }
 
+// ---- composite at the virtual camera's geometry (bsx_step_batch_vcam): blend → flip → cv::resize(INTER_LINEAR) → [YUYV pack], deepseg.cc:634-681 ---------
+// The persistent mask holds every pixel (255 outside the ROI), so the composite at any source pixel is a pointwise function of frame, background and mask: the
+// resampling kernel forms its own taps, and neither the capture-size composite nor the full-size resized image exists in memory.  One workgroup per kVW x kVH
+// output tile, two 4-pixel groups per lane:
+//   LDS form (DIRECT = false): the composite of the tile's source footprint — in the UNFLIPPED frame's coordinates, widened to whole 4-pixel groups — is staged in
+//     LDS as one word per pixel (B | G << 8 | R << 16), each source pixel blended once whatever the scale; every output pixel then reads its four taps there.
+//   DIRECT form: tables whose footprints do not fit kVLdsWords (strong down-scales; decided once per table on the host, vcam_tile_fits) blend each tap where it
+//     is read.
+// The resample is sample_linear's fixed point.  The 2x2 area mode (both scales exactly 2) arrives as a linear table with xofs = 2 dx, yofs = 2 dy and coefficients
+// 1024 / 1024, whose integers ARE the area mean: (1024 * (((s0 + s1) * 1024) >> 4)) >> 16 == s0 + s1, then (.. + .. + 2) >> 2.  A flip is evaluated in the flipped
+// frame's coordinates: output column dx takes taps x0 = xofs[dx] and x1 = min(x0 + 1, W - 1) of the flipped image, i.e. columns W-1-x0 and W-1-x1 of the composite
+// (rows likewise, clamped before mirroring) — resize(flip(C)) and flip(resize(C)) differ at ratios such as 640 -> 426.
+constexpr int kVW = 64, kVH = 32, kVLdsWords = 8192;                 // output tile; LDS staging area: 32 KiB = 8192 source pixels
+static_assert(kVW * kVH == 2 * 4 * kThreads, "vcam tile: two 4-pixel groups per lane");
+constexpr int kVcYuyvOut = 1, kVcFlipH = 2, kVcFlipV = 4, kVcWords = 8, kVcOutWords = 16;      // bits of the kernel's `opt` word
+struct __attribute__((packed, aligned(4))) VcW2 { uint32_t x, y; };
+
+// composite of ONE pixel (cx, cy) as B | G << 8 | R << 16: byte loads, any geometry (YIN: U / V from the macropixel of column cx & ~1, yuyv_to_bgr_k's integers)
+template <bool YIN>
+__device__ __forceinline__ uint32_t vcam_px(const uint8_t* __restrict__ fr, const uint8_t* __restrict__ bgp, const uint8_t* __restrict__ mk, int W, int cx, int cy) {
+  const long p = (long)cy * W + cx;
+  const uint8_t* a = bgp + p * 3;
+  const uint32_t aw = (uint32_t)a[0] | ((uint32_t)a[1] << 8) | ((uint32_t)a[2] << 16);
+  uint32_t bw;
+  if constexpr (YIN) {
+    const uint8_t* q = fr + ((long)cy * W + (cx & ~1)) * 2;
+    bw = yuv_tap_to_bgr((uint32_t)q[(cx & 1) * 2] | ((uint32_t)q[1] << 8) | ((uint32_t)q[3] << 16));
+  } else {
+    const uint8_t* b = fr + p * 3;
+    bw = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16);
+  }
+  const uint32_t m = (uint32_t)mk[p] * 0x00010001u;
+  return blend_word(aw, bw, m, m);                                   // byte 3: 0 blended with 0
+}
+// composite of the 4-pixel group (cx .. cx + 3, cy) as four pixel words.  words: W % 4 == 0 and 4-byte aligned images (cx % 4 == 0 here) — 12 B of background,
+// 12 B (YIN: 8 B) of frame and 4 mask bytes, blend_quad; else pixel by pixel, columns past the row's end left 0 (no tap reads them: x1 <= W - 1)
+template <bool YIN>
+__device__ __forceinline__ void vcam_group(const uint8_t* __restrict__ fr, const uint8_t* __restrict__ bgp, const uint8_t* __restrict__ mk, int W, int cx, int cy,
+                                           bool words, uint32_t w[4]) {
+  if (words) {
+    const long p = (long)cy * W + cx;
+    const u3v av = *reinterpret_cast<const u3v*>(bgp + p * 3);
+    uint32_t b3[3];
+    if constexpr (YIN) {
+      const VcW2 y = *reinterpret_cast<const VcW2*>(fr + p * 2);
+      yuyv4_to_bgr3(y.x, y.y, b3);
+    } else {
+      const u3v bv = *reinterpret_cast<const u3v*>(fr + p * 3);
+      b3[0] = bv.x; b3[1] = bv.y; b3[2] = bv.z;
+    }
+    const uint32_t a3[3] = {av.x, av.y, av.z};
+    uint32_t o[3];
+    blend_quad(a3, b3, *reinterpret_cast<const uint32_t*>(mk + p), o);
+    w[0] = o[0] & 0xffffffu;
+    w[1] = (o[0] >> 24) | ((o[1] & 0xffffu) << 8);
+    w[2] = (o[1] >> 16) | ((o[2] & 0xffu) << 16);
+    w[3] = o[2] >> 8;
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < 4; k++) w[k] = cx + k < W ? vcam_px<YIN>(fr, bgp, mk, W, cx + k, cy) : 0u;
+}
+// one output channel from the four tap words: sample_linear's horizontal pass (11-bit coefficients) and vertical pass
+__device__ __forceinline__ uint32_t vcam_lerp(uint32_t t00, uint32_t t01, uint32_t t10, uint32_t t11, int a0, int a1, int b0, int b1, int sh) {
+  const int h0 = (int)((t00 >> sh) & 255u) * a0 + (int)((t01 >> sh) & 255u) * a1;
+  const int h1 = (int)((t10 >> sh) & 255u) * a0 + (int)((t11 >> sh) & 255u) * a1;
+  return (uint32_t)((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2) & 255u;
+}
+template <bool DIRECT, bool YIN>
+__global__ __launch_bounds__(kThreads) void vcam_blend_resize_k(const uint8_t* __restrict__ frames, const uint8_t* __restrict__ bg, long bg_stride,
+                                                               const uint8_t* __restrict__ masks, uint8_t* __restrict__ out, int W, int H, ResizeTab tab, int ntx,
+                                                               int opt) {
+  __shared__ uint32_t s_px[DIRECT ? 1 : kVLdsWords];
+  const int tid = threadIdx.x, ty = (int)blockIdx.x / ntx, tx = (int)blockIdx.x - ty * ntx;
+  const long n = blockIdx.y;
+  const int dw = tab.dw, dh = tab.dh;
+  const int dx0 = tx * kVW, dy0 = ty * kVH, dx1 = min(dx0 + kVW, dw) - 1, dy1 = min(dy0 + kVH, dh) - 1;
+  const bool fh = (opt & kVcFlipH) != 0, fv = (opt & kVcFlipV) != 0;
+  const uint8_t* fr = frames + n * (long)W * H * (YIN ? 2 : 3);
+  const uint8_t* bgp = bg + n * bg_stride;
+  const uint8_t* mk = masks + n * (long)W * H;
+  int gx0 = 0, cy_lo = 0, rw = 0;                                   // LDS image: composite rows cy_lo.., columns gx0.., rw words per row
+  if constexpr (!DIRECT) {
+    const int fx_lo = tab.xofs[dx0], fx_hi = min(tab.xofs[dx1] + 1, W - 1);
+    const int fy_lo = min(max(tab.yofs[dy0], 0), H - 1), fy_hi = min(max(tab.yofs[dy1] + 1, 0), H - 1);
+    const int cx_lo = fh ? W - 1 - fx_hi : fx_lo, cx_hi = fh ? W - 1 - fx_lo : fx_hi;
+    cy_lo = fv ? H - 1 - fy_hi : fy_lo;
+    gx0 = cx_lo & ~3;
+    const int ng = ((cx_hi - gx0) >> 2) + 1, items = (fy_hi - fy_lo + 1) * ng;     // rows * ng * 4 <= kVLdsWords: vcam_tile_fits
+    rw = 4 * ng;
+    const bool words = (opt & kVcWords) != 0;
+    for (int i = tid; i < items; i += kThreads) {
+      const int r = i / ng, g = i - r * ng;
+      uint32_t w[4];
+      vcam_group<YIN>(fr, bgp, mk, W, gx0 + 4 * g, cy_lo + r, words, w);
+      *reinterpret_cast<uint4*>(s_px + r * rw + 4 * g) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    __syncthreads();
+  }
+  const bool yout = (opt & kVcYuyvOut) != 0, owords = (opt & kVcOutWords) != 0;
+#pragma unroll
+  for (int j = 0; j < 2; j++) {
+    const int gi = tid + j * kThreads, ry = gi / (kVW / 4), dy = dy0 + ry, dx = dx0 + 4 * (gi - ry * (kVW / 4));
+    if (dy > dy1 || dx > dx1) continue;
+    const int sy = tab.yofs[dy], b0 = tab.ya[2 * dy], b1 = tab.ya[2 * dy + 1];
+    int y0 = min(max(sy, 0), H - 1), y1 = min(max(sy + 1, 0), H - 1);
+    if (fv) { y0 = H - 1 - y0; y1 = H - 1 - y1; }
+    const int cnt = min(4, dx1 - dx + 1);
+    uint32_t q[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const int d = min(dx + k, dx1);                                // past the tile's last column: the last pixel again (never stored)
+      const int a0 = tab.xa[2 * d], a1 = tab.xa[2 * d + 1];
+      int x0 = tab.xofs[d], x1 = min(x0 + 1, W - 1);
+      if (fh) { x0 = W - 1 - x0; x1 = W - 1 - x1; }
+      uint32_t t00, t01, t10, t11;
+      if constexpr (DIRECT) {
+        t00 = vcam_px<YIN>(fr, bgp, mk, W, x0, y0); t01 = vcam_px<YIN>(fr, bgp, mk, W, x1, y0);
+        t10 = vcam_px<YIN>(fr, bgp, mk, W, x0, y1); t11 = vcam_px<YIN>(fr, bgp, mk, W, x1, y1);
+      } else {
+        const int r0 = (y0 - cy_lo) * rw - gx0, r1 = (y1 - cy_lo) * rw - gx0;
+        t00 = s_px[r0 + x0]; t01 = s_px[r0 + x1]; t10 = s_px[r1 + x0]; t11 = s_px[r1 + x1];
+      }
+      q[k] = vcam_lerp(t00, t01, t10, t11, a0, a1, b0, b1, 0) | (vcam_lerp(t00, t01, t10, t11, a0, a1, b0, b1, 8) << 8) |
+             (vcam_lerp(t00, t01, t10, t11, a0, a1, b0, b1, 16) << 16);
+    }
+    const long o = n * (long)dw * dh + (long)dy * dw + dx;
+    if (yout) {                                                      // dw even: cnt is 2 or 4, whole pairs
+      const uint32_t p0 = yuyv_pair(q[0] & 255u, (q[0] >> 8) & 255u, q[0] >> 16, q[1] & 255u, (q[1] >> 8) & 255u, q[1] >> 16);
+      const uint32_t p1 = yuyv_pair(q[2] & 255u, (q[2] >> 8) & 255u, q[2] >> 16, q[3] & 255u, (q[3] >> 8) & 255u, q[3] >> 16);
+      uint8_t* op = out + o * 2;
+      if (owords && cnt == 4) *reinterpret_cast<VcW2*>(op) = VcW2{p0, p1};
+      else if (owords) *reinterpret_cast<uint32_t*>(op) = p0;
+      else {
+#pragma unroll
+        for (int b = 0; b < 4; b++) { op[b] = (uint8_t)(p0 >> (8 * b)); if (cnt == 4) op[4 + b] = (uint8_t)(p1 >> (8 * b)); }
+      }
+    } else {
+      uint8_t* op = out + o * 3;
+      if (owords && cnt == 4) {
+        *reinterpret_cast<u3v*>(op) = u3v{q[0] | (q[1] << 24), (q[1] >> 8) | (q[2] << 16), (q[2] >> 16) | (q[3] << 8)};
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+          if (k < cnt) { op[3 * k] = (uint8_t)q[k]; op[3 * k + 1] = (uint8_t)(q[k] >> 8); op[3 * k + 2] = (uint8_t)(q[k] >> 16); }
+      }
+    }
+  }
+}
+
 }  // namespace
 
 // resize + bilateral in one launch (prep_fused_k); input (f32 [n][inH][inW][3]) and / or input_u8 (R|G<<8|B<<16 [n][inH][inW]): whichever is non-null is written
@@ -1386,6 +1536,50 @@ hipError_t launch_gauss_blend(const uint8_t* frames, const uint8_t* masks, uint8
   for (int n0 = 0; n0 < n; n0 += kMaxGridY) {
     const int nn = n - n0 < kMaxGridY ? n - n0 : kMaxGridY;
     gauss_launch<2>(dim3((w + kGTW - 1) / kGTW, (h + kGTH - 1) / kGTH, nn), s, frames + (size_t)n0 * w * h * 3, out + (size_t)n0 * w * h * 3, masks + (size_t)n0 * w * h, w, h, gc, opts);
+  }
+  return hipGetLastError();
+}
+
+// ---- composite at the virtual camera's geometry --------------------------------------------------------------------------------
+// Does the source footprint of every output tile (both column orders: the footprint's 4-pixel grid depends on the horizontal flip) fit vcam_blend_resize_k's
+// LDS staging area?  The same arithmetic as the kernel's; every (tile column, tile row) pair exists, so the largest product is the largest width times height.
+bool vcam_tile_fits(const int* xofs, const int* yofs, int sw, int sh, int dw, int dh) {
+  auto clampi = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
+  int max_rows = 0, max_cols = 0;
+  for (int dy0 = 0; dy0 < dh; dy0 += kVH) {
+    const int dy1 = std::min(dy0 + kVH, dh) - 1;
+    max_rows = std::max(max_rows, clampi(yofs[dy1] + 1, 0, sh - 1) - clampi(yofs[dy0], 0, sh - 1) + 1);
+  }
+  for (int dx0 = 0; dx0 < dw; dx0 += kVW) {
+    const int dx1 = std::min(dx0 + kVW, dw) - 1, lo = xofs[dx0], hi = std::min(xofs[dx1] + 1, sw - 1);
+    for (int fh = 0; fh < 2; fh++) {
+      const int c_lo = fh ? sw - 1 - hi : lo, c_hi = fh ? sw - 1 - lo : hi, g0 = c_lo & ~3;
+      max_cols = std::max(max_cols, 4 * (((c_hi - g0) >> 2) + 1));
+    }
+  }
+  return (long)max_rows * max_cols <= kVLdsWords;
+}
+
+hipError_t launch_vcam_blend_resize(const uint8_t* frames, bool yuyv_in, const uint8_t* bg, size_t bg_stride, const uint8_t* masks, uint8_t* out, int W, int H,
+                                    ResizeTab tab, bool direct, int n, hipStream_t s, unsigned flags) {
+  if (tab.mode != 0 || tab.sw != W || tab.sh != H || (yuyv_in && (W & 1)) || ((flags & 1) && (tab.dw & 1))) return hipErrorInvalidValue;
+  const int ntx = (tab.dw + kVW - 1) / kVW, nty = (tab.dh + kVH - 1) / kVH;
+  if ((long)ntx * nty >= (1l << 31)) return hipErrorInvalidValue;
+  const bool words = W % 4 == 0 && bg_stride % 4 == 0 && ((((uintptr_t)frames) | ((uintptr_t)bg) | ((uintptr_t)masks)) & 3) == 0;
+  const bool owords = (((uintptr_t)out) & 3) == 0 && ((flags & 1) || tab.dw % 4 == 0);
+  const int opt = (int)(flags & 7u) | (words ? kVcWords : 0) | (owords ? kVcOutWords : 0);
+  const size_t fb = (size_t)W * H * (yuyv_in ? 2 : 3), ob = (size_t)tab.dw * tab.dh * ((flags & 1) ? 2 : 3);
+  for (int n0 = 0; n0 < n; n0 += kMaxGridY) {
+    const int nn = n - n0 < kMaxGridY ? n - n0 : kMaxGridY;
+    const dim3 grid((unsigned)(ntx * nty), (unsigned)nn);
+    const uint8_t* f = frames + (size_t)n0 * fb;
+    const uint8_t* b = bg + (size_t)n0 * bg_stride;
+    const uint8_t* m = masks + (size_t)n0 * W * H;
+    uint8_t* o = out + (size_t)n0 * ob;
+#define BSX_VC(D, Y) vcam_blend_resize_k<D, Y><<<grid, kThreads, 0, s>>>(f, b, (long)bg_stride, m, o, W, H, tab, ntx, opt)
+    if (direct) { if (yuyv_in) BSX_VC(true, true); else BSX_VC(true, false); }
+    else { if (yuyv_in) BSX_VC(false, true); else BSX_VC(false, false); }
+#undef BSX_VC
   }
   return hipGetLastError();
 }

@@ -19,6 +19,7 @@
  *   bsx_step_batch_yuyv    … with convert_rgb_to_yuyv fused app/deepseg.cc:634-681
  *   bsx_step_batch_ex      … with cv::flip (and YUYV) fused  app/deepseg.cc:667-681; BSX_STEP_YUYV_IN: … and VideoCapture's YUYV->BGR  app/deepseg.cc:553,725
  *   bsx_step_batch_pipelined  … with the CalcMask worker's overlap of segmentation and blending  app/deepseg.cc:159-285, 634-661
+ *   bsx_step_batch_vcam    … with the resize to the virtual camera's geometry (--vg) fused  app/deepseg.cc:634-681 (the resize: :675-679)
  *                          (set_input_frame → mask → alpha_blend), batched
  *   bsx_resize_bgr         grab_background() cv::resize   app/background.cc:178-194
  *   bsx_bgr_to_yuyv        convert_rgb_to_yuyv()          app/deepseg.cc:87-106
@@ -192,6 +193,20 @@ BSX_API int bsx_step_batch_ex(bsx_ctx* ctx, const uint8_t* d_frames, const uint8
  *     that advances the temporal state while a composite is pending (bsx_process_batch / _host, bsx_step_batch*, bsx_profile_batch, bsx_debug_run_stage 1-3). */
 BSX_API int bsx_step_batch_pipelined(bsx_ctx* ctx, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_frame_stride,
                              uint8_t* d_out, int n, void* stream, unsigned flags);
+
+/* One main-loop iteration whose output has the VIRTUAL CAMERA's geometry (--vg differs from the capture size, app/deepseg.cc:675-679).  For every stream, in the
+ * reference's order: C = alpha_blend(bg, frame, mask) at the capture size; F = cv::flip(C) with BSX_STEP_FLIP_H / _V; R = cv::resize(F, Size(out_w, out_h))
+ * with INTER_LINEAR (the 2x2 area mean when both scales are exactly 2 — the integers of bsx_resize_bgr); convert_rgb_to_yuyv(R) with BSX_STEP_YUYV.
+ * d_out is [n][out_h][out_w][3], or [n][out_h][out_w][2] with BSX_STEP_YUYV.  The masks are made as bsx_process_batch makes them (persistent masks, temporal
+ * state and stage callbacks exactly as bsx_step_batch_ex(flags)); then ONE pass reads frame, background and mask taps and writes the output: neither the
+ * capture-size composite nor the full-size resized image is stored.  The flip is applied before the resize (resize(flip(C)) and flip(resize(C)) differ at
+ * ratios such as 640 -> 426).  The table of each (out_w, out_h) is built on its first use and kept by the context.
+ *   - flags: BSX_STEP_YUYV | BSX_STEP_FLIP_H | BSX_STEP_FLIP_V | BSX_STEP_YUYV_IN | BSX_STEP_BGBLUR(k); BSX_STEP_NO_MASK is refused;
+ *   - BSX_EINVAL also for out_w or out_h <= 0, an odd out_w with BSX_STEP_YUYV, an odd capture width with BSX_STEP_YUYV_IN, d_out overlapping d_frames or
+ *     d_bg (no in-place form: each output pixel reads a neighbourhood of input pixels), and a pending pipelined composite — all before any state changes;
+ *   - out_w == width and out_h == height: the call IS bsx_step_batch_ex(flags). */
+BSX_API int bsx_step_batch_vcam(bsx_ctx* ctx, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_frame_stride,
+                                uint8_t* d_out, int out_w, int out_h, int n, void* stream, unsigned flags);
 
 /* cv::resize(src, dst, Size(dw,dh)) with INTER_LINEAR on packed BGR u8 (device pointers, n images). */
 BSX_API int bsx_resize_bgr(bsx_ctx* ctx, const uint8_t* d_src, int sw, int sh, uint8_t* d_dst, int dw, int dh, int n, void* stream);
