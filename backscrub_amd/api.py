@@ -58,6 +58,8 @@ SYMBOLS = [
     ("bsx_step_batch_ex", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_uint]),
     ("bsx_step_batch_pipelined", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_uint]),
     ("bsx_step_batch_vcam", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint]),
+    ("bsx_step_batch_streams", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_uint]),
+    ("bsx_reset_streams", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
     ("bsx_resize_bgr", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("bsx_bgr_to_yuyv", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("bsx_yuyv_to_bgr", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -112,6 +114,12 @@ def lib():
             f.argtypes = args
         _LIB = L
     return _LIB
+
+
+def _ids(ids):
+    """stream ids (any sequence of ints, a numpy array or a CPU tensor) → (ctypes int array, n); the C side validates range and uniqueness"""
+    v = [int(i) for i in (ids.tolist() if hasattr(ids, "tolist") else ids)]
+    return (C.c_int * max(len(v), 1))(*v), len(v)
 
 
 def _check(rc, ctx=None, what=""):
@@ -209,6 +217,32 @@ class MaskGen:
         _check(lib().bsx_step_batch_ex(self.h, C.c_void_p(frames.data_ptr()), C.c_void_p(bg.data_ptr() if bg is not None else None), stride,
                                        C.c_void_p(out.data_ptr()), n, _stream_ptr(), flags), self.h, "bsx_step_batch_ex")
         return out
+
+    def step_streams(self, ids, frames, bg, out, flip_h=False, flip_v=False, yuyv=False, no_mask=False, bgblur=0, yuyv_in=False):
+        """step_ex for the streams named in `ids` (bsx_step_batch_streams): frames[i], bg[i] (per-stream backgrounds) and out[i] belong to stream ids[i], whose
+        temporal state and persistent mask advance in place; every other stream is untouched.  ids: n distinct stream indices (any sequence of ints), n = len(frames)"""
+        arr, n_ids = _ids(ids)
+        if n_ids == 0:
+            _check(lib().bsx_step_batch_streams(self.h, arr, None, None, 0, None, 0, _stream_ptr(), 0), self.h, "bsx_step_batch_streams")
+            return out
+        n = self._n(frames, yuyv_in)
+        if n != n_ids:
+            raise BsxError("%d ids for a batch of %d frames" % (n_ids, n))
+        want = (self.height, self.width, 2 if yuyv else 3)
+        if out.dim() != 4 or tuple(out.shape[1:]) != want or out.shape[0] < n or not out.is_contiguous() or not out.is_cuda or out.dtype != _torch().uint8:
+            raise BsxError("out must be a contiguous cuda uint8 tensor [>=%d,%d,%d,%d]" % ((n,) + want))
+        if bg is None and not bgblur:
+            raise BsxError("bg is required unless bgblur is set")
+        stride = 0 if bg is None else self._bg(bg, n)
+        flags = (1 if yuyv else 0) | (2 if flip_h else 0) | (4 if flip_v else 0) | (8 if no_mask else 0) | (16 if yuyv_in else 0) | ((int(bgblur) & 255) << 8)
+        _check(lib().bsx_step_batch_streams(self.h, arr, C.c_void_p(frames.data_ptr()), C.c_void_p(bg.data_ptr() if bg is not None else None), stride,
+                                            C.c_void_p(out.data_ptr()), n, _stream_ptr(), flags), self.h, "bsx_step_batch_streams")
+        return out
+
+    def reset_streams(self, ids):
+        """reset the temporal state of the listed streams only (ofinal -> 0, mask -> 255; bsx_reset_streams) — a slot reused for a new camera"""
+        arr, n = _ids(ids)
+        _check(lib().bsx_reset_streams(self.h, arr, n, _stream_ptr()), self.h, "bsx_reset_streams")
 
     def step_vcam(self, frames, bg, out, flip_h=False, flip_v=False, yuyv=False, yuyv_in=False, bgblur=0):
         """one main-loop iteration at the virtual camera's geometry (--vg, app/deepseg.cc:634-681): blend, flip, cv::resize to out's size and optionally the

@@ -14,6 +14,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "../../include/bsx.h"
@@ -162,6 +163,16 @@ struct bsx_ctx {
   hipEvent_t wait_before_state = nullptr;   // consumed by the next launch that writes d_ofinal
   int pipe_wgs = 0;                         // BSX_PIPE_WGS (read at bsx_new, experiment): workgroups per CU the pipelined composite may hold (occupancy cap by an LDS pad; 0 = no cap,
                                             // the default: every cap measured slower — the tile kernel needs its waves, profiles/r04l)
+  // Stream ids of bsx_step_batch_streams / bsx_reset_streams: the host array is copied into the next entry of a pinned ring, from there into the same entry of a device
+  // ring that the call's kernels read (slot_of).  An entry is reused only after the event recorded behind the call that used it has completed — with kIdRing entries
+  // the host waits only when it runs more than kIdRing calls ahead of the GPU.  Allocated on the first call (n_streams ints per entry).
+  static constexpr int kIdRing = 4;
+  int* h_ids = nullptr;                     // pinned [kIdRing][n_streams]
+  int* d_ids = nullptr;                     // device [kIdRing][n_streams]
+  hipEvent_t ev_ids[kIdRing] = {};
+  bool ids_used[kIdRing] = {};
+  int ids_next = 0;
+  std::vector<int> ids_seen;                // host scratch of the duplicate check: [n_streams], -1 = not listed
   bool act16 = false;                  // BSX_ACT16=1: 16-bit activation STORAGE for the segmented Meet / MLKit networks (g1) — opt-in, IoU-gated; needs the specialised middle kernel
 
   // stream-0 view of a graph tensor (network input/output have dedicated buffers; intermediates are batch-major in
@@ -461,16 +472,18 @@ hipError_t seg_k3(bsx_ctx* c, int n, hipStream_t s) {
   void* args[] = {&d, &arena, &pf, &w, &nf};
   return seg_launch(c->seg_fn[1], d.tiles_y * d.tiles_x, n, d.lds_floats, s, args);
 }
-hipError_t seg_tail(bsx_ctx* c, uint8_t* ofinal, bool logits, int n, hipStream_t s) {
+hipError_t seg_tail(bsx_ctx* c, uint8_t* ofinal, bool logits, int n, hipStream_t s, const int* ids = nullptr) {
   const SegPlan& sp = c->plan.seg;
   long pf = (long)c->plan.arena_floats_per_stream;
-  if (logits || !c->seg_fn[2]) return launch_seg_tail(sp.tail, c->d_arena, pf, c->d_net_out, ofinal, c->d_weights, logits, n, s, c->act16);
+  if (logits || !c->seg_fn[2]) return launch_seg_tail(sp.tail, c->d_arena, pf, c->d_net_out, ofinal, c->d_weights, logits, n, s, c->act16, ids);
   SegTail d = sp.tail; float* arena = c->d_arena; float* no = c->d_net_out; const float* w = c->d_weights; int nf = n;
-  void* args[] = {&d, &arena, &pf, &no, &ofinal, &w, &nf};
+  const int* slot_of = ids;
+  void* args[] = {&d, &arena, &pf, &no, &ofinal, &w, &nf, &slot_of};
   return seg_launch(c->seg_fn[2], d.tiles_y * d.tiles_x, n, d.lds_floats, s, args);
 }
 
-int run_infer(bsx_ctx* c, int n, hipStream_t s, bool logits = true, int slot = 0) {
+// ids (device, nullable): the id form of a step — frame i's temporal state is slot ids[i] (then slot == 0); nullptr = slots [slot, slot + n)
+int run_infer(bsx_ctx* c, int n, hipStream_t s, bool logits = true, int slot = 0, const int* ids = nullptr) {
   bsx_roctx::Range range("bsx:network");
   if (c->use_program && c->plan.seg.on) {
     const SegPlan& sp = c->plan.seg;
@@ -481,7 +494,7 @@ int run_infer(bsx_ctx* c, int n, hipStream_t s, bool logits = true, int slot = 0
     BSX_HIP(c, seg_k3(c, n, s));
     if (sp.tail.pre_gate_off >= 0) BSX_HIP(c, launch_seg_gate(sp.tail.gate, c->d_arena, pf, c->d_weights, sp.tail.pre_gate_off, n, s));
     if (!logits) { const int frc = state_write_fence(c, s); if (frc) return frc; }       // the decoding tail reads and writes d_ofinal
-    BSX_HIP(c, seg_tail(c, c->d_ofinal + (size_t)slot * c->outW * c->outH, logits, n, s));
+    BSX_HIP(c, seg_tail(c, c->d_ofinal + (size_t)slot * c->outW * c->outH, logits, n, s, ids));
     return BSX_OK;
   }
   if (c->use_program) {
@@ -496,15 +509,15 @@ int run_infer(bsx_ctx* c, int n, hipStream_t s, bool logits = true, int slot = 0
     const Step& last = c->plan.steps.back();
     { const int frc = state_write_fence(c, s); if (frc) return frc; }
     BSX_HIP(c, launch_resize_argmax_iir(last, c->d_arena + (size_t)c->plan.tensor_off[last.in0] * (size_t)c->n_streams,
-                                        c->d_ofinal + (size_t)slot * c->outW * c->outH, n, s, c->tail_generic));
+                                        c->d_ofinal + (size_t)slot * c->outW * c->outH, n, s, c->tail_generic, ids));
   }
   return BSX_OK;
 }
 // `slot` = first state slot (stream index) of the batch: frame i uses ofinal / mask slot `slot + i`
-int run_decode(bsx_ctx* c, int n, hipStream_t s, int slot = 0) {
+int run_decode(bsx_ctx* c, int n, hipStream_t s, int slot = 0, const int* ids = nullptr) {
   bsx_roctx::Range range("bsx:decode");
   { const int frc = state_write_fence(c, s); if (frc) return frc; }
-  BSX_HIP(c, launch_decode(c->model_type, c->tensor_ptr(c->plan.output), c->d_ofinal + (size_t)slot * c->outW * c->outH, c->outW * c->outH, c->outC, n, s));
+  BSX_HIP(c, launch_decode(c->model_type, c->tensor_ptr(c->plan.output), c->d_ofinal + (size_t)slot * c->outW * c->outH, c->outW * c->outH, c->outC, n, s, ids));
   return BSX_OK;
 }
 // the mask up-scale table with its tile-class scratch re-based to stream `slot` (lanes run concurrently on disjoint slot ranges)
@@ -513,23 +526,24 @@ ResizeTab tab_up_at(const bsx_ctx* c, int slot) {
   if (t.tile_class) t.tile_class += (size_t)slot * c->tiles_per_frame;
   return t;
 }
-int run_mask(bsx_ctx* c, int n, hipStream_t s, int slot = 0) {
+int run_mask(bsx_ctx* c, int n, hipStream_t s, int slot = 0, const int* ids = nullptr) {
   bsx_roctx::Range range("bsx:mask");
   BSX_HIP(c, launch_mask_upscale_blur(c->d_ofinal + (size_t)slot * c->outW * c->outH, c->outW, c->outH, c->in_roi, tab_up_at(c, slot),
-                                      c->d_masks + (size_t)slot * c->width * c->height, c->width, c->height, c->roi, n, s));
+                                      c->d_masks + (size_t)slot * c->width * c->height, c->width, c->height, c->roi, n, s, ids));
   return BSX_OK;
 }
-// bs_maskgen_process for n frames whose per-stream state lives in slots [slot, slot + n); yuyv_in: YUYV 4:2:2 frames (only where prep_yuyv_fusable)
-int process_impl(bsx_ctx* c, const uint8_t* d_frames, int n, int slot, hipStream_t s, bool yuyv_in = false) {
+// bs_maskgen_process for n frames whose per-stream state lives in slots [slot, slot + n) — or, with ids (device, slot = 0), in slots ids[0..n);
+// yuyv_in: YUYV 4:2:2 frames (only where prep_yuyv_fusable)
+int process_impl(bsx_ctx* c, const uint8_t* d_frames, int n, int slot, hipStream_t s, bool yuyv_in = false, const int* ids = nullptr) {
   int rc;
   if ((rc = run_prep(c, d_frames, n, s, false, yuyv_in))) return rc;
   if (c->onprep) { BSX_HIP(c, hipStreamSynchronize(s)); c->onprep(c->caller_ctx); }   // :303
   const bool fused_decode = infer_decodes(c);
-  if ((rc = run_infer(c, n, s, !fused_decode, slot))) return rc;
+  if ((rc = run_infer(c, n, s, !fused_decode, slot, ids))) return rc;
   if (c->oninfer) { BSX_HIP(c, hipStreamSynchronize(s)); c->oninfer(c->caller_ctx); } // :311
-  if (!fused_decode && (rc = run_decode(c, n, s, slot))) return rc;
+  if (!fused_decode && (rc = run_decode(c, n, s, slot, ids))) return rc;
   if (c->onmask) { BSX_HIP(c, hipStreamSynchronize(s)); c->onmask(c->caller_ctx); }   // :363
-  return run_mask(c, n, s, slot);
+  return run_mask(c, n, s, slot, ids);
 }
 
 }  // namespace
@@ -661,6 +675,9 @@ void bsx_delete(bsx_ctx* c) {
   if (c->comp_stream) { (void)hipStreamSynchronize(c->comp_stream); (void)hipStreamDestroy(c->comp_stream); }
   if (c->ev_pdone) (void)hipEventDestroy(c->ev_pdone);
   if (c->ev_pcomp) (void)hipEventDestroy(c->ev_pcomp);
+  for (hipEvent_t& e : c->ev_ids) if (e) (void)hipEventDestroy(e);
+  if (c->d_ids) (void)hipFree(c->d_ids);
+  if (c->h_ids) (void)hipHostFree(c->h_ids);
   delete c;
 }
 
@@ -767,15 +784,23 @@ struct LaneView {
 
 // flags (bsx.h): BSX_STEP_YUYV — the composite leaves as YUYV 4:2:2 (2 B/px), convert_rgb_to_yuyv (deepseg.cc:87-106) applied in the blend's epilogue;
 // BSX_STEP_FLIP_H / _V — cv::flip of the composite (deepseg.cc:667-673) folded into the epilogue's store addresses
-int step_impl(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_frame_stride, uint8_t* d_out, int n, void* stream, unsigned flags) {
-  const int bgblur = (int)((flags >> 8) & 255u);                // BSX_STEP_BGBLUR(ksize): background = blur of the stream's own frame, d_bg unused
+// the argument checks of step_impl that need nothing enqueued (bsx_step_batch_streams runs them before it stages its ids)
+int step_args(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, uint8_t* d_out, int n, unsigned flags) {
+  const int bgblur = (int)((flags >> 8) & 255u);
   if (!c || !d_frames || (!d_bg && !bgblur) || !d_out || n <= 0 || n > c->n_streams || (flags & ~(31u | 0xFF00u))) return BSX_EINVAL;
   if (bgblur && (bgblur > 31 || !(bgblur & 1) || d_frames == d_out)) return BSX_EINVAL;
   if (c->pend.active) { c->last_error = "error: a pipelined composite is pending (flush with bsx_step_batch_pipelined(ctx, NULL, ...) first)\n"; return BSX_EINVAL; }
+  if ((flags & (BSX_STEP_YUYV | BSX_STEP_YUYV_IN)) && (c->width & 1)) return BSX_EINVAL;       // 4:2:2 pairs pixels horizontally
+  return BSX_OK;
+}
+// ids (device, nullable): bsx_step_batch_streams — frame i's temporal state and persistent mask are slot ids[i]; everything else stays indexed by position i
+int step_impl(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_frame_stride, uint8_t* d_out, int n, void* stream, unsigned flags,
+              const int* ids = nullptr) {
+  const int bgblur = (int)((flags >> 8) & 255u);                // BSX_STEP_BGBLUR(ksize): background = blur of the stream's own frame, d_bg unused
+  if (const int arc = step_args(c, d_frames, d_bg, d_out, n, flags)) return arc;
   const int yuyv = (int)(flags & BSX_STEP_YUYV);
   const bool yin = (flags & BSX_STEP_YUYV_IN) != 0;             // the camera's raw 4:2:2 frames (cv::COLOR_YUV2BGR_YUYV, app/deepseg.cc:553,725) instead of BGR
   const unsigned flip = flags & (BSX_STEP_FLIP_H | BSX_STEP_FLIP_V);
-  if ((yuyv || yin) && (c->width & 1)) return BSX_EINVAL;       // 4:2:2 pairs pixels horizontally
   DeviceGuard guard(c->device);
   const size_t px_frame = (size_t)c->width * c->height;
   if (yin) {
@@ -789,21 +814,21 @@ int step_impl(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, size_t b
     if (!direct) {
       if (!c->d_bgr_in_scratch) BSX_HIP(c, hipMalloc(&c->d_bgr_in_scratch, (size_t)c->n_streams * px_frame * 3));
       BSX_HIP(c, launch_yuyv_to_bgr(d_frames, c->d_bgr_in_scratch, c->width, c->height, n, pick(c, stream)));
-      return step_impl(c, c->d_bgr_in_scratch, d_bg, bg_frame_stride, d_out, n, stream, flags & ~BSX_STEP_YUYV_IN);
+      return step_impl(c, c->d_bgr_in_scratch, d_bg, bg_frame_stride, d_out, n, stream, flags & ~BSX_STEP_YUYV_IN, ids);
     }
   }
   if (bgblur) {
     if (!(flags & 15u) && !c->no_bgblur_fusion && gauss_blend_fusable(d_frames, c->d_masks, d_out, c->width, bgblur)) {
       // masks as usual (prep → network → decode → upscale + blur), then ONE pass over the frames: blur tile → blend with the frame and the mask → composite
-      int rc = bsx_process_batch(c, d_frames, n, nullptr, stream);
+      int rc = ids ? process_impl(c, d_frames, n, 0, pick(c, stream), false, ids) : bsx_process_batch(c, d_frames, n, nullptr, stream);
       if (rc) return rc;
-      BSX_HIP(c, launch_gauss_blend(d_frames, c->d_masks, d_out, c->width, c->height, bgblur, n, pick(c, stream)));
+      BSX_HIP(c, launch_gauss_blend(d_frames, c->d_masks, d_out, c->width, c->height, bgblur, n, pick(c, stream), ids));
       return BSX_OK;
     }
     const size_t fb = (size_t)c->width * c->height * 3;
     if (!c->d_bgblur_scratch) BSX_HIP(c, hipMalloc(&c->d_bgblur_scratch, (size_t)c->n_streams * fb));
     BSX_HIP(c, launch_gauss_blur(d_frames, c->d_bgblur_scratch, c->width, c->height, bgblur, n, pick(c, stream)));
-    return step_impl(c, d_frames, c->d_bgblur_scratch, fb, d_out, n, stream, flags & 15u);
+    return step_impl(c, d_frames, c->d_bgblur_scratch, fb, d_out, n, stream, flags & 15u, ids);
   }
   // Aliasing (bsx.h): the reference flips `raw` in place (app/deepseg.cc:667-673), so a caller following it passes d_out == d_frames.  The fused tile kernel reads a
   // frame pixel at (x, y) and stores the flipped (or YUYV-packed: 2 B/px) result at ANOTHER address, which a different tile may not have read yet — with overlapping
@@ -816,13 +841,20 @@ int step_impl(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, size_t b
                     mask_blend_fusable(c->width, c->height, c->roi, d_bg, bg_frame_stride, d_frames, yuyv ? d_frames : d_out);
   if (!fuse) {
     if (yin) return BSX_EINVAL;                                   // unreachable: `direct` above implies `fuse`
-    int rc = bsx_process_batch(c, d_frames, n, nullptr, stream);
+    int rc = ids ? process_impl(c, d_frames, n, 0, pick(c, stream), false, ids) : bsx_process_batch(c, d_frames, n, nullptr, stream);
     if (rc) return rc;
-    if (!yuyv && !flip) return bsx_composite_batch(c, d_bg, bg_frame_stride, d_frames, nullptr, d_out, n, stream);
+    // the composite with the persistent masks of the batch's slots (bsx_composite_batch's blend; with ids the masks are read by stream id)
+    auto composite = [&](uint8_t* dst) -> int {
+      if (!ids) return bsx_composite_batch(c, d_bg, bg_frame_stride, d_frames, nullptr, dst, n, stream);
+      bsx_roctx::Range range("bsx:blend");
+      BSX_HIP(c, launch_blend(d_bg, bg_frame_stride, d_frames, c->d_masks, dst, (size_t)c->width * c->height, n, pick(c, stream), ids));
+      return BSX_OK;
+    };
+    if (!yuyv && !flip) return composite(d_out);
     // unfused geometry: composite into a context-owned BGR scratch, then flip and / or pack as separate passes
     const size_t need = (size_t)c->n_streams * c->width * c->height * 3;
     if (!c->d_bgr_scratch) BSX_HIP(c, hipMalloc(&c->d_bgr_scratch, need));
-    rc = bsx_composite_batch(c, d_bg, bg_frame_stride, d_frames, nullptr, c->d_bgr_scratch, n, stream);
+    rc = composite(c->d_bgr_scratch);
     if (rc) return rc;
     const uint8_t* bgr = c->d_bgr_scratch;
     if (flip) {
@@ -851,14 +883,17 @@ int step_impl(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, size_t b
       if (nb <= 0) break;
       hipStream_t ls = k == 0 ? s : c->lane_stream[k];
       if (k > 0 && hipStreamWaitEvent(ls, c->ev_fork, 0) != hipSuccess) { lane_rc = BSX_EDEVICE; break; }
+      const int st0 = ids ? 0 : f0;                               // the lane's state: slots [f0, f0 + nb), or slots ids[f0 .. f0 + nb)
+      const int* lids = ids ? ids + f0 : nullptr;
       {
         LaneView view(c, f0, per);
         lane_rc = run_prep(c, d_frames + (size_t)f0 * fb, nb, ls, false, yin);
-        if (!lane_rc) lane_rc = run_infer(c, nb, ls, !fd, f0);
-        if (!lane_rc && !fd) lane_rc = run_decode(c, nb, ls, f0);
+        if (!lane_rc) lane_rc = run_infer(c, nb, ls, !fd, st0, lids);
+        if (!lane_rc && !fd) lane_rc = run_decode(c, nb, ls, st0, lids);
       }
-      if (!lane_rc && launch_mask_blend(c->d_ofinal + (size_t)f0 * sm, c->outW, c->outH, c->in_roi, tab_up_at(c, f0), c->d_masks + (size_t)f0 * c->width * c->height, c->width, c->height,
-                                        c->roi, d_bg + (size_t)f0 * bg_frame_stride, bg_frame_stride, d_frames + (size_t)f0 * fb, d_out + (size_t)f0 * ob, nb, ls, (int)flags) != hipSuccess)
+      if (!lane_rc && launch_mask_blend(c->d_ofinal + (size_t)st0 * sm, c->outW, c->outH, c->in_roi, tab_up_at(c, f0), c->d_masks + (size_t)st0 * c->width * c->height, c->width, c->height,
+                                        c->roi, d_bg + (size_t)f0 * bg_frame_stride, bg_frame_stride, d_frames + (size_t)f0 * fb, d_out + (size_t)f0 * ob, nb, ls, (int)flags, 0,
+                                        lids) != hipSuccess)
         lane_rc = BSX_EDEVICE;
       // forked lanes are ALWAYS joined, also after an error: the caller's stream must not be left with work in flight on streams it cannot see
       if (k > 0 && (hipEventRecord(c->ev_join[k], ls) != hipSuccess || hipStreamWaitEvent(s, c->ev_join[k], 0) != hipSuccess)) lane_rc = lane_rc ? lane_rc : BSX_EDEVICE;
@@ -869,12 +904,12 @@ int step_impl(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, size_t b
   if ((rc = run_prep(c, d_frames, n, s, false, yin))) return rc;
   if (c->onprep) { BSX_HIP(c, hipStreamSynchronize(s)); c->onprep(c->caller_ctx); }
   const bool fused_decode = infer_decodes(c);
-  if ((rc = run_infer(c, n, s, !fused_decode, 0))) return rc;
+  if ((rc = run_infer(c, n, s, !fused_decode, 0, ids))) return rc;
   if (c->oninfer) { BSX_HIP(c, hipStreamSynchronize(s)); c->oninfer(c->caller_ctx); }
-  if (!fused_decode && (rc = run_decode(c, n, s))) return rc;
+  if (!fused_decode && (rc = run_decode(c, n, s, 0, ids))) return rc;
   bsx_roctx::Range range("bsx:mask+blend");
   BSX_HIP(c, launch_mask_blend(c->d_ofinal, c->outW, c->outH, c->in_roi, c->tab_up.tab, c->d_masks, c->width, c->height, c->roi, d_bg,
-                               bg_frame_stride, d_frames, d_out, n, s, (int)flags));
+                               bg_frame_stride, d_frames, d_out, n, s, (int)flags, 0, ids));
   return BSX_OK;
 }
 }  // namespace
@@ -887,6 +922,97 @@ int bsx_step_batch_yuyv(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg
 }
 int bsx_step_batch_ex(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_frame_stride, uint8_t* d_out, int n, void* stream, unsigned flags) {
   return step_impl(c, d_frames, d_bg, bg_frame_stride, d_out, n, stream, flags);
+}
+
+// ---- a chosen subset of the context's streams, addressed by stream id ------------------------------------------------------------------------------------
+// The reference processes each camera frame once (CalcMask::run waits for a NEW frame, app/deepseg.cc:182-216; the temporal filter advances once per call,
+// lib/libbackscrub.cc:315-356).  Cameras deliver at their own rates and come and go, so a tick of a server has new frames for SOME streams, not for streams
+// 0 .. n-1: frame i of the call belongs to stream ids[i].  The kernels that read or write per-stream state take the ids as a device array (slot_of) and address
+// that state in place — no gather / scatter of state; everything else (frames, backgrounds, outputs, activations, tile classes) stays indexed by position.
+namespace {
+int ids_einval(bsx_ctx* c, const char* fn, const std::string& why) {
+  c->last_error = std::string("error: ") + fn + ": " + why + "\n";
+  return BSX_EINVAL;
+}
+// host-side validation of ids[0..n): nothing is enqueued before it passes
+int ids_check(bsx_ctx* c, const char* fn, const int* ids, int n) {
+  if (n < 0) return ids_einval(c, fn, "n = " + std::to_string(n) + " is negative");
+  if (n > c->n_streams) return ids_einval(c, fn, "n = " + std::to_string(n) + " exceeds the context's " + std::to_string(c->n_streams) + " streams");
+  if (n > 0 && !ids) return ids_einval(c, fn, "ids is NULL");
+  if (c->pend.active) { c->last_error = "error: a pipelined composite is pending (flush with bsx_step_batch_pipelined(ctx, NULL, ...) first)\n"; return BSX_EINVAL; }
+  if (c->ids_seen.size() != (size_t)c->n_streams) c->ids_seen.assign((size_t)c->n_streams, -1);
+  int rc = BSX_OK, i = 0;
+  for (; i < n; i++) {
+    const int v = ids[i];
+    if (v < 0 || v >= c->n_streams) {
+      rc = ids_einval(c, fn, "ids[" + std::to_string(i) + "] = " + std::to_string(v) + " is out of range [0, " + std::to_string(c->n_streams) + ")");
+      break;
+    }
+    if (c->ids_seen[v] >= 0) {
+      rc = ids_einval(c, fn, "ids[" + std::to_string(i) + "] = " + std::to_string(v) + " repeats ids[" + std::to_string(c->ids_seen[v]) + "]");
+      break;
+    }
+    c->ids_seen[v] = i;
+  }
+  for (int j = 0; j < i; j++) c->ids_seen[ids[j]] = -1;
+  return rc;
+}
+// ids[0..n) → the next entry of the context's pinned ring → the same entry of the device ring, on stream s.  *entry: record ev_ids[*entry] on s behind the last
+// launch that reads the device array (ids_release).  The host waits only when the entry's previous use has not completed yet (kIdRing calls ahead of the GPU).
+int ids_stage(bsx_ctx* c, const int* ids, int n, hipStream_t s, const int** d_ids, int* entry) {
+  const size_t N = (size_t)c->n_streams;
+  if (!c->h_ids) BSX_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_ids), bsx_ctx::kIdRing * N * sizeof(int), hipHostMallocDefault));
+  if (!c->d_ids) BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_ids), bsx_ctx::kIdRing * N * sizeof(int)));
+  for (hipEvent_t& e : c->ev_ids) if (!e) BSX_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  const int k = c->ids_next;
+  if (c->ids_used[k]) {
+    hipError_t e;
+    while ((e = hipEventQuery(c->ev_ids[k])) == hipErrorNotReady) std::this_thread::yield();
+    BSX_HIP(c, e);
+  }
+  memcpy(c->h_ids + (size_t)k * N, ids, (size_t)n * sizeof(int));
+  BSX_HIP(c, hipMemcpyAsync(c->d_ids + (size_t)k * N, c->h_ids + (size_t)k * N, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+  c->ids_next = (k + 1) % bsx_ctx::kIdRing;
+  *d_ids = c->d_ids + (size_t)k * N;
+  *entry = k;
+  return BSX_OK;
+}
+// the ring entry is free again once everything enqueued on s so far has run (recorded also after a failed call: whatever it enqueued may read the entry)
+int ids_release(bsx_ctx* c, int entry, hipStream_t s, int rc) {
+  c->ids_used[entry] = true;
+  const hipError_t e = hipEventRecord(c->ev_ids[entry], s);
+  if (rc == BSX_OK && e != hipSuccess) BSX_HIP(c, e);
+  return rc;
+}
+}  // namespace
+
+int bsx_step_batch_streams(bsx_ctx* c, const int* ids, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_frame_stride, uint8_t* d_out, int n, void* stream,
+                           unsigned flags) {
+  if (!c) return BSX_EINVAL;
+  if (const int rc = ids_check(c, "bsx_step_batch_streams", ids, n)) return rc;
+  if (n == 0) return BSX_OK;
+  if (const int rc = step_args(c, d_frames, d_bg, d_out, n, flags)) return rc;
+  DeviceGuard guard(c->device);
+  hipStream_t s = pick(c, stream);
+  const int* d_ids = nullptr;
+  int entry = 0;
+  if (const int rc = ids_stage(c, ids, n, s, &d_ids, &entry)) return rc;
+  return ids_release(c, entry, s, step_impl(c, d_frames, d_bg, bg_frame_stride, d_out, n, stream, flags, d_ids));
+}
+
+int bsx_reset_streams(bsx_ctx* c, const int* ids, int n, void* stream) {
+  if (!c) return BSX_EINVAL;
+  if (const int rc = ids_check(c, "bsx_reset_streams", ids, n)) return rc;
+  if (n == 0) return BSX_OK;
+  DeviceGuard guard(c->device);
+  hipStream_t s = pick(c, stream);
+  const int* d_ids = nullptr;
+  int entry = 0;
+  if (const int rc = ids_stage(c, ids, n, s, &d_ids, &entry)) return rc;
+  const hipError_t e = launch_reset_slots(c->d_ofinal, (size_t)c->outW * c->outH, c->d_masks, (size_t)c->width * c->height, d_ids, n, s);
+  int rc = BSX_OK;
+  if (e != hipSuccess) { report(c, c->ondebug, c->caller_ctx, "error: HIP %s while resetting streams\n", hipGetErrorString(e)); rc = BSX_EDEVICE; }
+  return ids_release(c, entry, s, rc);
 }
 
 // ---- the main loop at the virtual camera's geometry (--vg, app/deepseg.cc:634-681): blend → flip → resize → YUYV pack with the resize folded in -----------------

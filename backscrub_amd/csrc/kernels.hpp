@@ -40,7 +40,7 @@ inline bool chain3_on(const Plan& plan, int mid, int n, const uint16_t* weights1
 // DeepLab tail: the graph's final RESIZE_BILINEAR fused with the 21-way argmax + temporal IIR (the full-resolution logits never exist)
 bool resize_argmax_fusable(const Step& st);
 // generic = the scalar first-maximum scan (what more than 24 classes take; tests force it for the 21-class graph)
-hipError_t launch_resize_argmax_iir(const Step& st, const float* lowres_logits, uint8_t* ofinal, int n, hipStream_t s, bool generic = false);
+hipError_t launch_resize_argmax_iir(const Step& st, const float* lowres_logits, uint8_t* ofinal, int n, hipStream_t s, bool generic = false, const int* slot_of = nullptr);
 
 // Whole-network per-frame program (kernels_frame.hip): one 1024-lane workgroup per stream.
 hipError_t frame_program_prepare(int lds_floats);
@@ -56,9 +56,13 @@ hipError_t launch_seg_k2(const SegK2& d, float* arena, long per_frame, const flo
 hipError_t launch_seg_k3(const SegK3& d, float* arena, long per_frame, const float* weights, int n, hipStream_t s, bool h16 = false);
 // logits = true: write the network output tensor (debug / stage tests); false: decode + temporal IIR straight into `ofinal`
 hipError_t launch_seg_gate(const SegGate& gt, float* arena, long per_frame, const float* weights, long long out_off, int n, hipStream_t s);
-hipError_t launch_seg_tail(const SegTail& d, float* arena, long per_frame, float* net_out, uint8_t* ofinal, const float* weights, bool logits, int n, hipStream_t s, bool h16 = false);
+hipError_t launch_seg_tail(const SegTail& d, float* arena, long per_frame, float* net_out, uint8_t* ofinal, const float* weights, bool logits, int n, hipStream_t s, bool h16 = false,
+                           const int* slot_of = nullptr);
 
 // ---- image path ----------------------------------------------------------------------
+// slot_of (every launch below that reads or writes per-stream state: the model-resolution temporal state `ofinal` and the persistent full-frame masks):
+// nullptr = frame i of the batch owns state slot i (the dense form); else a DEVICE array of n stream ids — frame i's state is slot slot_of[i], while frames,
+// backgrounds, outputs and scratch stay indexed by the frame's position.  Read once per workgroup (a scalar load: the frame index is workgroup-uniform).
 // Fixed-point bilinear tables of cv::resize(INTER_LINEAR, 8u) for one (src,dst) size pair
 // (device arrays; built on the host with the same float/double arithmetic OpenCV uses).
 struct ResizeTab {
@@ -78,7 +82,8 @@ int mask_tile_width();             // the mask tile kernel's tile geometry (kern
 int mask_tile_height();
 // classify the mask tiles of n streams into tab.tile_class (see ResizeTab); launch_mask_upscale_blur / launch_mask_blend run it themselves
 struct Rect4;
-hipError_t launch_tile_class(const uint8_t* ofinal, int outW, int outH, const Rect4& in_roi, const ResizeTab& tab, const Rect4& roi, int n, hipStream_t s);
+hipError_t launch_tile_class(const uint8_t* ofinal, int outW, int outH, const Rect4& in_roi, const ResizeTab& tab, const Rect4& roi, int n, hipStream_t s,
+                             const int* slot_of = nullptr);
 
 struct Rect4 { int x, y, w, h; };
 
@@ -98,18 +103,19 @@ hipError_t launch_prep_fused(const uint8_t* frames, int W, int H, Rect4 roi, flo
                              BilateralParams bp, int n, hipStream_t s, bool yuyv_in = false);
 bool prep_yuyv_fusable(int W, Rect4 roi, const ResizeTab& tab);
 // decode + temporal IIR on the model-resolution mask.  libbackscrub.cc:317-357
-hipError_t launch_decode(int model_type, const float* logits, uint8_t* ofinal, int npix, int nch, int n, hipStream_t s);
+hipError_t launch_decode(int model_type, const float* logits, uint8_t* ofinal, int npix, int nch, int n, hipStream_t s, const int* slot_of = nullptr);
 // ofinal(in_roi) ↑ roi size, 5x5 box blur (REFLECT_101 on the ROI), write into mask(roi).  libbackscrub.cc:367-371
 hipError_t launch_mask_upscale_blur(const uint8_t* ofinal, int outW, int outH, Rect4 in_roi, ResizeTab tab, uint8_t* mask, int W, int H,
-                                    Rect4 roi, int n, hipStream_t s);
+                                    Rect4 roi, int n, hipStream_t s, const int* slot_of = nullptr);
 // mask upscale + blur AND alpha blend of the same tile in one launch (W, roi.x, roi.w multiples of 4, 4-byte aligned images;
 // pixels outside the ROI — mask 255 forever — get the background copied)
 bool mask_blend_fusable(int W, int H, Rect4 roi, const uint8_t* bg, size_t bg_stride, const uint8_t* frames, const uint8_t* out);
 hipError_t launch_mask_blend(const uint8_t* ofinal, int outW, int outH, Rect4 in_roi, ResizeTab tab, uint8_t* mask, int W, int H, Rect4 roi,
-                             const uint8_t* bg, size_t bg_stride, const uint8_t* frames, uint8_t* out, int n, hipStream_t s, int yuyv = 0, int lds_pad = 0);
+                             const uint8_t* bg, size_t bg_stride, const uint8_t* frames, uint8_t* out, int n, hipStream_t s, int yuyv = 0, int lds_pad = 0,
+                             const int* slot_of = nullptr);
 // alpha blend.  deepseg.cc:108-134
 hipError_t launch_blend(const uint8_t* bg, size_t bg_stride, const uint8_t* frames, const uint8_t* masks, uint8_t* out, size_t npix,
-                        int n, hipStream_t s);
+                        int n, hipStream_t s, const int* slot_of = nullptr);
 // generic BGR resize (background → frame size).  background.cc:186,190
 hipError_t launch_resize_bgr(const uint8_t* src, uint8_t* dst, ResizeTab tab, int n, hipStream_t s);
 // BGR → YUYV.  deepseg.cc:87-106
@@ -123,13 +129,15 @@ hipError_t launch_gauss_blur(const uint8_t* src, uint8_t* dst, int w, int h, int
 bool gauss_coeff_words(int ksize, int shift, uint32_t* c4 /* [4][9] */, uint32_t* c2 /* [2][17] */);   // host: the tables launch_gauss_* pass to the kernel
 // blur + alpha blend of the frames over their own blur (deepseg.cc:652-661 without -b), the blurred image never stored; fusable = 4-byte aligned images, w % 4 == 0
 bool gauss_blend_fusable(const uint8_t* frames, const uint8_t* masks, const uint8_t* out, int w, int ksize);
-hipError_t launch_gauss_blend(const uint8_t* frames, const uint8_t* masks, uint8_t* out, int w, int h, int ksize, int n, hipStream_t s);
+hipError_t launch_gauss_blend(const uint8_t* frames, const uint8_t* masks, uint8_t* out, int w, int h, int ksize, int n, hipStream_t s, const int* slot_of = nullptr);
 // composite at the virtual camera's geometry: alpha blend → cv::flip (flags bits 1-2) → cv::resize to (tab.dw, tab.dh) → [YUYV pack (bit 0)] in one pass over
 // frames, background and the persistent masks (deepseg.cc:634-681).  `tab`: a linear table from the capture size (the 2x2 area mode expanded to one);
 // direct = !vcam_tile_fits(tab): every tap blended where it is read instead of the footprint staged in LDS.  yuyv_in: `frames` is YUYV 4:2:2
 bool vcam_tile_fits(const int* xofs, const int* yofs, int sw, int sh, int dw, int dh);
 hipError_t launch_vcam_blend_resize(const uint8_t* frames, bool yuyv_in, const uint8_t* bg, size_t bg_stride, const uint8_t* masks, uint8_t* out, int W, int H,
                                     ResizeTab tab, bool direct, int n, hipStream_t s, unsigned flags);
+// bsx_reset_streams: state slots ids[0..n) (a device array) back to their initial values, ofinal -> 0 and mask -> 255 (what bsx_reset does for every slot)
+hipError_t launch_reset_slots(uint8_t* ofinal, size_t ofinal_bytes, uint8_t* masks, size_t mask_bytes, const int* ids, int n, hipStream_t s);
 // fill
 hipError_t launch_fill_u8(uint8_t* p, uint8_t v, size_t bytes, hipStream_t s);
 

@@ -288,9 +288,14 @@ __global__ __launch_bounds__(kThreads) void prep_fused_k(const uint8_t* __restri
 }
 
 // ---- decode + temporal IIR -------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void decode_k(int type, const float* __restrict__ t, uint8_t* __restrict__ out, long total, int nch) {
+// slot_of (the id form of a step, launch_decode): frame blockIdx.y's temporal state is slot slot_of[blockIdx.y] and `total` counts ONE frame's pixels; the dense form
+// launches one flat grid (blockIdx.y = 0, slot_of = nullptr).  Same for the three kernels below.
+__device__ __forceinline__ long decode_state_frame(const int* __restrict__ slot_of) { return slot_of ? slot_of[blockIdx.y] : (long)blockIdx.y; }
+__global__ __launch_bounds__(kThreads) void decode_k(int type, const float* __restrict__ t, uint8_t* __restrict__ out, long total, int nch, const int* __restrict__ slot_of) {
   long i = (long)blockIdx.x * kThreads + threadIdx.x;
   if (i >= total) return;
+  t += (long)blockIdx.y * total * nch;
+  out += decode_state_frame(slot_of) * total;
   uint8_t val = 255;
   if (type == 1) {  // DeepLab: first maximum wins, start value -10000, "person" = 15
     const float* p = t + i * nch;
@@ -327,9 +332,11 @@ __device__ __forceinline__ uint32_t meet_val(float l0, float l1) {
   const float s = __fadd_rn(e0, e1);
   return __fdiv_rn(e0, s) < __fdiv_rn(e1, s) ? 0u : 255u;
 }
-__global__ __launch_bounds__(kThreads) void decode_meet4_k(const float4* __restrict__ t, uint32_t* __restrict__ out, long quads) {
+__global__ __launch_bounds__(kThreads) void decode_meet4_k(const float4* __restrict__ t, uint32_t* __restrict__ out, long quads, const int* __restrict__ slot_of) {
   const long i = (long)blockIdx.x * kThreads + threadIdx.x;
   if (i >= quads) return;
+  t += (long)blockIdx.y * quads * 2;
+  out += decode_state_frame(slot_of) * quads;
   const float4 a = t[2 * i], b = t[2 * i + 1];               // (l0,l1) of pixels 0,1 | 2,3
   const uint32_t v = meet_val(a.x, a.y) | (meet_val(a.z, a.w) << 8) | (meet_val(b.x, b.y) << 16) | (meet_val(b.z, b.w) << 24);
   const uint32_t o = out[i];
@@ -337,9 +344,11 @@ __global__ __launch_bounds__(kThreads) void decode_meet4_k(const float4* __restr
 }
 
 // MLKit / BodyPix decode, 4 pixels per lane: `p > 0.65` with the float promoted to double (the literal is a double, libbackscrub.cc:338)
-__global__ __launch_bounds__(kThreads) void decode_thresh4_k(const float4* __restrict__ t, uint32_t* __restrict__ out, long quads) {
+__global__ __launch_bounds__(kThreads) void decode_thresh4_k(const float4* __restrict__ t, uint32_t* __restrict__ out, long quads, const int* __restrict__ slot_of) {
   const long i = (long)blockIdx.x * kThreads + threadIdx.x;
   if (i >= quads) return;
+  t += (long)blockIdx.y * quads;
+  out += decode_state_frame(slot_of) * quads;
   const float4 p = t[i];
   const uint32_t v = ((double)p.x > 0.65 ? 0u : 255u) | (((double)p.y > 0.65 ? 0u : 255u) << 8) | (((double)p.z > 0.65 ? 0u : 255u) << 16) |
                      (((double)p.w > 0.65 ? 0u : 255u) << 24);
@@ -351,9 +360,11 @@ __global__ __launch_bounds__(kThreads) void decode_thresh4_k(const float4* __res
 // read it with coalesced 4-byte loads into LDS, then every lane scans its own nch values (stride nch, conflict-free for odd
 // nch).  A lane reading its classes straight from HBM touches 64 cache lines per load instruction.
 constexpr int kArgmaxMaxCh = 32;
-__global__ __launch_bounds__(kThreads) void decode_argmax_k(const float* __restrict__ t, uint8_t* __restrict__ out, long total, int nch) {
+__global__ __launch_bounds__(kThreads) void decode_argmax_k(const float* __restrict__ t, uint8_t* __restrict__ out, long total, int nch, const int* __restrict__ slot_of) {
   __shared__ float tile[kThreads * kArgmaxMaxCh];
   const long p0 = (long)blockIdx.x * kThreads;
+  t += (long)blockIdx.y * total * nch;
+  out += decode_state_frame(slot_of) * total;
   const int valid = (int)min((long)kThreads, total - p0);
   const float* src = t + p0 * nch;
   for (int i = threadIdx.x; i < valid * nch; i += kThreads) tile[i] = src[i];
@@ -520,13 +531,13 @@ __device__ __forceinline__ void reverse4px(uint32_t (&w)[3]) {
 // ((a*255 + b*0)/255 == a for every byte: the exhaustive blend test covers m = 0 and 255)
 template <bool BLEND, bool WHOLE = false>
 __device__ __forceinline__ void tile_vsum5_store(const uint16_t* hs, uint8_t* __restrict__ mask, uint8_t* __restrict__ outp, const TileBlendOperands& o,
-                                                 int n, int W, int H, Rect4 roi, int tx0, int ty0, int tid, int yuyv_flip, int uniform = 0) {
+                                                 int n, int ms, int W, int H, Rect4 roi, int tx0, int ty0, int tid, int yuyv_flip, int uniform = 0) {
   const int ly0 = tid / (kTW / 4), lx = (tid % (kTW / 4)) * 4;
   const int gx = tx0 + lx;
   const int yuyv = yuyv_flip & 1;
   const bool fh = (yuyv_flip & 2) != 0, fv = (yuyv_flip & 4) != 0, yin = (yuyv_flip & 16) != 0;      // bit 4 = BSX_STEP_YUYV_IN: the frame operand arrived as YUYV
   const int obpp = yuyv ? 2 : 3;                                 // composite written as packed BGR or as YUYV 4:2:2 (convert_rgb_to_yuyv fused in)
-  uint8_t* const dst0 = mask + (long)n * W * H + (long)(roi.y + ty0 + ly0) * W + roi.x + gx;
+  uint8_t* const dst0 = mask + (long)ms * W * H + (long)(roi.y + ty0 + ly0) * W + roi.x + gx;      // ms: the frame's state slot (n: its position in the batch)
   const int oy0 = fv ? H - 1 - (roi.y + ty0 + ly0) : roi.y + ty0 + ly0, ox = fh ? W - 4 - (roi.x + gx) : roi.x + gx;
   const long orow = fv ? -(long)W : (long)W;                     // output row step per tile row
   uint8_t* const out0 = BLEND ? outp + ((long)n * W * H + (long)oy0 * W + ox) * obpp : nullptr;
@@ -575,7 +586,7 @@ template <bool BLEND, bool YIN = false>      // YIN (BSX_STEP_YUYV_IN): `frames`
 __global__ __launch_bounds__(kThreads) void mask_upscale_blur_k(const uint8_t* __restrict__ ofinal, int outW, int outH, Rect4 q, ResizeTab tab,
                                                                uint8_t* __restrict__ mask, int W, int H, Rect4 roi,
                                                                const uint8_t* __restrict__ bg, long bg_stride, const uint8_t* __restrict__ frames,
-                                                               uint8_t* __restrict__ outp, int yuyv, int ntx, int nty, int n_frames) {
+                                                               uint8_t* __restrict__ outp, int yuyv, int ntx, int nty, int n_frames, const int* __restrict__ slot_of) {
   // coefficients are 0..2048: kept as 16-bit so that every product below is a full-rate 24-bit multiply
   __shared__ int col_sx[kHW], col_sx1[kHW], row_s0[kHH], row_s1[kHH];
   __shared__ short col_a0[kHW], col_a1[kHW], row_b0[kHH], row_b1[kHH];
@@ -588,8 +599,9 @@ __global__ __launch_bounds__(kThreads) void mask_upscale_blur_k(const uint8_t* _
   unsigned f_, t_;
   xcd_frame_tile((unsigned)(ntx * nty), (unsigned)n_frames, &f_, &t_);
   const int n = (int)f_, tby = (int)t_ / ntx, tbx = (int)t_ - tby * ntx;
+  const int ms = slot_of ? slot_of[n] : n;                                   // the frame's state slot (ofinal, mask): one scalar load per workgroup
   const int tx0 = tbx * kTW, ty0 = tby * kTH;
-  const uint8_t* src = ofinal + (long)n * outW * outH + (long)q.y * outW + q.x;
+  const uint8_t* src = ofinal + (long)ms * outW * outH + (long)q.y * outW + q.x;
   const int tid = threadIdx.x;
   TileBlendOperands ops;
   yuyv = YIN ? (yuyv | 16) : (yuyv & ~16);                                  // the helpers read bit 4: a compile-time constant per instantiation
@@ -655,7 +667,7 @@ __global__ __launch_bounds__(kThreads) void mask_upscale_blur_k(const uint8_t* _
   __syncthreads();
   tile_hsum5(up, hs, tid);                                                                       // 4.
   __syncthreads();
-  tile_vsum5_store<BLEND>(hs, mask, outp, ops, n, W, H, roi, tx0, ty0, tid, yuyv);               // 5.
+  tile_vsum5_store<BLEND>(hs, mask, outp, ops, n, ms, W, H, roi, tx0, ty0, tid, yuyv);           // 5.
 }
 
 // ---- mask tile, single-round-trip form ---------------------------------------------------------------------------------
@@ -674,7 +686,8 @@ template <bool BLEND, bool YIN = false, bool F0 = false, bool WH = false>
 __global__ __launch_bounds__(kThreads) void mask_tile_k(const uint8_t* __restrict__ ofinal, int outW, int outH, Rect4 q, ResizeTab tab,
                                                        uint8_t* __restrict__ mask, int W, int H, Rect4 roi,
                                                        const uint8_t* __restrict__ bg, long bg_stride, const uint8_t* __restrict__ frames,
-                                                       uint8_t* __restrict__ outp, int yuyv, int ntx, int nty, int n_frames, int ty_base, int nty_all) {
+                                                       uint8_t* __restrict__ outp, int yuyv, int ntx, int nty, int n_frames, int ty_base, int nty_all,
+                                                       const int* __restrict__ slot_of) {
   // (ty_base, nty_all: this launch covers tile rows [ty_base, ty_base + nty) of the nty_all rows of a frame — the launcher cuts a frame whose last tile row is partial
   //  into the whole rows, run by the WH instantiation, and that last row)
   __shared__ short col_c0[kHW], col_c1[kHW], col_a0[kHW], col_a1[kHW];     // block-relative tap columns, coefficients
@@ -712,9 +725,13 @@ __global__ __launch_bounds__(kThreads) void mask_tile_k(const uint8_t* __restric
     const uintptr_t ca = (uintptr_t)tab.tile_class + (size_t)n * (size_t)(ntx * nty_all) + (size_t)(tby * ntx + tbx);
     uniform = (int)((*reinterpret_cast<const uint32_t*>(ca & ~(uintptr_t)3) >> (8 * (unsigned)(ca & 3))) & 255u);
   }
+  // The frame's state slot (ofinal, mask; n = its position: frames, output, tile classes): slot_of[n] — one scalar load — or n.  Formed only AFTER the class byte is
+  // requested, on both paths: anything in front of that load lengthens the dependent chain every tile waits on (formed at the top, the dense step's launch measured
+  // 78 -> 82 us at configs[1]).
   if (uniform) {                                           // wave-uniform: nothing of the general path below is even requested
     tile_load_blend_operands<BLEND, WH>(ops, bg, bg_stride, frames, n, W, H, roi, tx0, ty0, tid, uniform, early_bg ? 2 : 3, yin);
-    tile_vsum5_store<BLEND, WH>(hq_hs, mask, outp, ops, n, W, H, roi, tx0, ty0, tid, yuyv, uniform);
+    const int ms = slot_of ? slot_of[n] : n;
+    tile_vsum5_store<BLEND, WH>(hq_hs, mask, outp, ops, n, ms, W, H, roi, tx0, ty0, tid, yuyv, uniform);
     return;
   }
   // extents of the source block: xofs / yofs are monotonic, so the extreme destination rows / columns give them
@@ -725,7 +742,8 @@ __global__ __launch_bounds__(kThreads) void mask_tile_k(const uint8_t* __restric
   const int smin = min(max(tab.yofs[gy_lo], 0), tab.sh - 1), smax = min(max(tab.yofs[gy_hi] + 1, 0), tab.sh - 1);
   const int cmin = tab.xofs[gx_lo], cmax = min(tab.xofs[gx_hi] + 1, tab.sw - 1);
   const int nsr = smax - smin + 1, ncol = cmax - cmin + 1;
-  const uint8_t* const base = ofinal + (long)n * outW * outH + (long)(q.y + smin) * outW + q.x + cmin;
+  const int ms = slot_of ? slot_of[n] : n;
+  const uint8_t* const base = ofinal + (long)ms * outW * outH + (long)(q.y + smin) * outW + q.x + cmin;
   // (a) raw block: 12 rows x 64 columns in three loads per lane cover the usual 5x up-scale; anything larger loops below
   uint32_t raw[3];
   const int br = tid >> 6, bc = tid & 63;
@@ -769,7 +787,7 @@ __global__ __launch_bounds__(kThreads) void mask_tile_k(const uint8_t* __restric
   __syncthreads();
   tile_hsum5(up, hs, tid);                                                                       // 4.
   __syncthreads();
-  tile_vsum5_store<BLEND, WH>(hs, mask, outp, ops, n, W, H, roi, tx0, ty0, tid, yuyv);               // 5.
+  tile_vsum5_store<BLEND, WH>(hs, mask, outp, ops, n, ms, W, H, roi, tx0, ty0, tid, yuyv);           // 5.
 }
 
 // ---- alpha blend (deepseg.cc:108-134), stand-alone: bsx_composite_batch ---------------------------------------------------------------
@@ -779,12 +797,13 @@ __global__ __launch_bounds__(kThreads) void mask_tile_k(const uint8_t* __restric
 // plain streaming kernel with this mix and coalesced accesses moves 5.7-6.2 TB/s through HBM.
 constexpr int kB4 = 4;
 __global__ __launch_bounds__(kThreads) void blend4x4_k(const uint8_t* __restrict__ bg, long bg_stride, const uint8_t* __restrict__ fr,
-                                                      const uint8_t* __restrict__ mask, uint8_t* __restrict__ out, unsigned quads_per_frame, long npix) {
+                                                      const uint8_t* __restrict__ mask, uint8_t* __restrict__ out, unsigned quads_per_frame, long npix,
+                                                      const int* __restrict__ slot_of) {
   const long n = blockIdx.y;
   const unsigned q0 = blockIdx.x * (kThreads * kB4) + threadIdx.x;      // first 4-pixel group of this lane
   const uint8_t* const a0 = bg + (bg_stride ? n * bg_stride : 0);
   const uint8_t* const b0 = fr + n * npix * 3;
-  const uint8_t* const m0 = mask + n * npix;
+  const uint8_t* const m0 = mask + (slot_of ? (long)slot_of[n] : n) * npix;      // the frame's persistent mask: state slot, one scalar load
   uint8_t* const o0 = out + n * npix * 3;
   u3v av[kB4], bv[kB4];
   uint32_t mw[kB4];
@@ -807,11 +826,11 @@ __global__ __launch_bounds__(kThreads) void blend4x4_k(const uint8_t* __restrict
 
 // scalar tail / unaligned fallback: one pixel per lane
 __global__ __launch_bounds__(kThreads) void blend1_k(const uint8_t* __restrict__ bg, long bg_stride, const uint8_t* __restrict__ fr,
-                                                    const uint8_t* __restrict__ mask, uint8_t* __restrict__ out, long npix) {
+                                                    const uint8_t* __restrict__ mask, uint8_t* __restrict__ out, long npix, const int* __restrict__ slot_of) {
   const long p = (long)blockIdx.x * kThreads + threadIdx.x;
   if (p >= npix) return;
   const long n = blockIdx.y;
-  int m = mask[n * npix + p];
+  int m = mask[(slot_of ? (long)slot_of[n] : n) * npix + p];
   const uint8_t* a = bg + (bg_stride ? n * bg_stride : 0) + p * 3;
   const uint8_t* b = fr + (n * npix + p) * 3;
   uint8_t* o = out + (n * npix + p) * 3;
@@ -1130,15 +1149,18 @@ bool bilateral_taps_match(const BilateralParams& bp) {
 }
 
 
-hipError_t launch_decode(int model_type, const float* logits, uint8_t* ofinal, int npix, int nch, int n, hipStream_t s) {
-  long total = (long)n * npix;
+hipError_t launch_decode(int model_type, const float* logits, uint8_t* ofinal, int npix, int nch, int n, hipStream_t s, const int* slot_of) {
+  // dense: one flat grid over the n frames; slot_of: one grid row per frame (a frame's state lives at slot_of[frame], not next to the previous frame's)
+  const long total = slot_of ? (long)npix : (long)n * npix;
+  const unsigned rows = slot_of ? (unsigned)n : 1u;
+  if (rows > (unsigned)kMaxGridY) return hipErrorInvalidValue;
   int type = model_type == 1 ? 1 : (model_type == 3 ? 3 : 2);
   if (type == 3 && nch == 2 && (total & 3) == 0 && ((((uintptr_t)logits) & 15) | (((uintptr_t)ofinal) & 3)) == 0)
-    decode_meet4_k<<<blocks_for(total / 4), kThreads, 0, s>>>(reinterpret_cast<const float4*>(logits), reinterpret_cast<uint32_t*>(ofinal), total / 4);
+    decode_meet4_k<<<dim3(blocks_for(total / 4), rows), kThreads, 0, s>>>(reinterpret_cast<const float4*>(logits), reinterpret_cast<uint32_t*>(ofinal), total / 4, slot_of);
   else if (type == 2 && nch == 1 && (total & 3) == 0 && ((((uintptr_t)logits) & 15) | (((uintptr_t)ofinal) & 3)) == 0)
-    decode_thresh4_k<<<blocks_for(total / 4), kThreads, 0, s>>>(reinterpret_cast<const float4*>(logits), reinterpret_cast<uint32_t*>(ofinal), total / 4);
-  else if (type == 1 && nch <= kArgmaxMaxCh) decode_argmax_k<<<blocks_for(total), kThreads, 0, s>>>(logits, ofinal, total, nch);
-  else decode_k<<<blocks_for(total), kThreads, 0, s>>>(type, logits, ofinal, total, nch);
+    decode_thresh4_k<<<dim3(blocks_for(total / 4), rows), kThreads, 0, s>>>(reinterpret_cast<const float4*>(logits), reinterpret_cast<uint32_t*>(ofinal), total / 4, slot_of);
+  else if (type == 1 && nch <= kArgmaxMaxCh) decode_argmax_k<<<dim3(blocks_for(total), rows), kThreads, 0, s>>>(logits, ofinal, total, nch, slot_of);
+  else decode_k<<<dim3(blocks_for(total), rows), kThreads, 0, s>>>(type, logits, ofinal, total, nch, slot_of);
   return hipGetLastError();
 }
 
@@ -1163,7 +1185,7 @@ bool mask_tile_fits(const int* xofs, const int* yofs, int sw, int sh, int dw, in
 static bool mask_tile_usable(const ResizeTab& tab) { return tab.mode == 0 && tab.tile_ok; }
 
 hipError_t launch_mask_upscale_blur(const uint8_t* ofinal, int outW, int outH, Rect4 in_roi, ResizeTab tab, uint8_t* mask, int W, int H, Rect4 roi,
-                                    int n, hipStream_t s) {
+                                    int n, hipStream_t s, const int* slot_of) {
   const int ntx = (roi.w + kTW - 1) / kTW, nty = (roi.h + kTH - 1) / kTH;
   if ((unsigned long long)ntx * nty * (unsigned long long)n >= (1ull << 31)) return hipErrorInvalidValue;
   static const bool xcd_on = !(BSX_DBG_ENV("BSX_XCD_TILES") && atoi(BSX_DBG_ENV("BSX_XCD_TILES")) == 0);      // A/B timing: 0 = plain frame-major workgroup order
@@ -1172,9 +1194,9 @@ hipError_t launch_mask_upscale_blur(const uint8_t* ofinal, int outW, int outH, R
   const bool shared_lines = ((roi.x * 3) & 127) != 0 || ((W * 3) & 127) != 0;
   const int nf = (xcd_on && shared_lines) ? n : 0;
   dim3 grid((unsigned)(ntx * nty) * (unsigned)n);
-  if (hipError_t e = launch_tile_class(ofinal, outW, outH, in_roi, tab, roi, n, s)) return e;
-  if (mask_tile_usable(tab)) mask_tile_k<false><<<grid, kThreads, 0, s>>>(ofinal, outW, outH, in_roi, tab, mask, W, H, roi, nullptr, 0, nullptr, nullptr, 0, ntx, nty, nf, 0, nty);
-  else mask_upscale_blur_k<false><<<grid, kThreads, 0, s>>>(ofinal, outW, outH, in_roi, tab, mask, W, H, roi, nullptr, 0, nullptr, nullptr, 0, ntx, nty, nf);
+  if (hipError_t e = launch_tile_class(ofinal, outW, outH, in_roi, tab, roi, n, s, slot_of)) return e;
+  if (mask_tile_usable(tab)) mask_tile_k<false><<<grid, kThreads, 0, s>>>(ofinal, outW, outH, in_roi, tab, mask, W, H, roi, nullptr, 0, nullptr, nullptr, 0, ntx, nty, nf, 0, nty, slot_of);
+  else mask_upscale_blur_k<false><<<grid, kThreads, 0, s>>>(ofinal, outW, outH, in_roi, tab, mask, W, H, roi, nullptr, 0, nullptr, nullptr, 0, ntx, nty, nf, slot_of);
   return hipGetLastError();
 }
 
@@ -1184,16 +1206,17 @@ hipError_t launch_mask_upscale_blur(const uint8_t* ofinal, int outW, int outH, R
 // (The first version gave every tile a wave that walked its block row by row, byte by byte: 17 us at 256 lite/VGA streams, 151 us at 1024 DeepLab streams —
 // more than the shortcut saved; profiles/r04g.)
 constexpr int kClsMaxItems = 8192, kClsMaxTx = 16;
-__global__ __launch_bounds__(kThreads) void tile_class_k(const uint8_t* __restrict__ ofinal, int outW, int outH, Rect4 q, ResizeTab tab, Rect4 roi, int ntx, int nty) {
+__global__ __launch_bounds__(kThreads) void tile_class_k(const uint8_t* __restrict__ ofinal, int outW, int outH, Rect4 q, ResizeTab tab, Rect4 roi, int ntx, int nty,
+                                                        const int* __restrict__ slot_of) {
   __shared__ uint8_t f255[kClsMaxItems], f0[kClsMaxItems];
   __shared__ int cmn[kClsMaxTx], cmx[kClsMaxTx];
   const int n = blockIdx.x, tid = threadIdx.x;
-  const uint8_t* const fr = ofinal + (long)n * outW * outH + (long)q.y * outW + q.x;
   if (tid < ntx) {
     const int tx0 = tid * kTW, gx_lo = max(tx0 - 2, 0), gx_hi = min(tx0 + kTW + 1, roi.w - 1);
     cmn[tid] = tab.xofs[gx_lo]; cmx[tid] = min(tab.xofs[gx_hi] + 1, tab.sw - 1);
   }
   __syncthreads();
+  const uint8_t* const fr = ofinal + (long)(slot_of ? slot_of[n] : n) * outW * outH + (long)q.y * outW + q.x;      // state slot; the classes stay per position n
   struct __attribute__((packed, aligned(1))) U4 { uint32_t v; };
   const int items = tab.sh * ntx;
   for (int i = tid; i < items; i += kThreads) {
@@ -1221,11 +1244,11 @@ __global__ __launch_bounds__(kThreads) void tile_class_k(const uint8_t* __restri
   }
 }
 
-hipError_t launch_tile_class(const uint8_t* ofinal, int outW, int outH, const Rect4& in_roi, const ResizeTab& tab, const Rect4& roi, int n, hipStream_t s) {
+hipError_t launch_tile_class(const uint8_t* ofinal, int outW, int outH, const Rect4& in_roi, const ResizeTab& tab, const Rect4& roi, int n, hipStream_t s, const int* slot_of) {
   if (!tab.tile_class || !mask_tile_usable(tab)) return hipSuccess;
   const int ntx = (roi.w + kTW - 1) / kTW, nty = (roi.h + kTH - 1) / kTH;
   if (ntx > kClsMaxTx || (long)tab.sh * ntx > kClsMaxItems) return hipMemsetAsync(tab.tile_class, 0, (size_t)ntx * nty * n, s);      // out of the classifier's range: all general
-  tile_class_k<<<dim3((unsigned)n), kThreads, 0, s>>>(ofinal, outW, outH, in_roi, tab, roi, ntx, nty);
+  tile_class_k<<<dim3((unsigned)n), kThreads, 0, s>>>(ofinal, outW, outH, in_roi, tab, roi, ntx, nty, slot_of);
   return hipGetLastError();
 }
 
@@ -1235,7 +1258,7 @@ bool mask_blend_fusable(int W, int H, Rect4 roi, const uint8_t* bg, size_t bg_st
 }
 
 hipError_t launch_mask_blend(const uint8_t* ofinal, int outW, int outH, Rect4 in_roi, ResizeTab tab, uint8_t* mask, int W, int H, Rect4 roi,
-                             const uint8_t* bg, size_t bg_stride, const uint8_t* frames, uint8_t* out, int n, hipStream_t s, int yuyv, int lds_pad) {
+                             const uint8_t* bg, size_t bg_stride, const uint8_t* frames, uint8_t* out, int n, hipStream_t s, int yuyv, int lds_pad, const int* slot_of) {
   // lds_pad (bytes of dynamic LDS nobody uses): an OCCUPANCY CAP for the two-deep pipeline (bsx_step_batch_pipelined) — left alone this HBM-bound launch takes every wave
   // slot of every CU and the latency-bound network kernels of the other stream run on what is left (seg_head 2.65x slower, profiles/r04k); with the pad only
   // 160 KB / (static + pad) workgroups fit a CU
@@ -1258,7 +1281,7 @@ hipError_t launch_mask_blend(const uint8_t* ofinal, int outW, int outH, Rect4 in
   const bool shared_lines = ((roi.x * 3) & 127) != 0 || ((W * 3) & 127) != 0;
   const int nf = (xcd_on && shared_lines) ? n : 0;
   dim3 grid((unsigned)(ntx * nty) * (unsigned)n);
-  if (hipError_t e = launch_tile_class(ofinal, outW, outH, in_roi, tab, roi, n, s)) return e;
+  if (hipError_t e = launch_tile_class(ofinal, outW, outH, in_roi, tab, roi, n, s, slot_of)) return e;
   static const bool no_early_bg = BSX_DBG_ENV("BSX_NO_EARLY_BG") != nullptr;      // A/B timing: bit 6 of the flag word = request a shared background only after the tile's class is known (rounds 1-4)
   if (no_early_bg) yuyv |= 64;
   static const bool plain_stores = BSX_DBG_ENV("BSX_TILE_PLAIN_STORES") != nullptr;      // A/B timing: bit 7 = the composite leaves with plain instead of nontemporal stores
@@ -1270,7 +1293,7 @@ hipError_t launch_mask_blend(const uint8_t* ofinal, int outW, int outH, Rect4 in
     // partial row as a second launch of the edge-testing instantiation
     const bool whole_x = f0 && roi.w % kTW == 0 && ((uintptr_t)mask & 3) == 0;      // (W, roi.x multiples of 4: mask_blend_fusable)
     const int nty_whole = whole_x ? roi.h / kTH : 0;
-#define BSX_MT(Y, F, WHL, GRID, NTY, TYB) mask_tile_k<true, Y, F, WHL><<<GRID, kThreads, (size_t)lds_pad, s>>>(ofinal, outW, outH, in_roi, tab, mask, W, H, roi, bg, (long)bg_stride, frames, out, yuyv, ntx, NTY, nf, TYB, nty)
+#define BSX_MT(Y, F, WHL, GRID, NTY, TYB) mask_tile_k<true, Y, F, WHL><<<GRID, kThreads, (size_t)lds_pad, s>>>(ofinal, outW, outH, in_roi, tab, mask, W, H, roi, bg, (long)bg_stride, frames, out, yuyv, ntx, NTY, nf, TYB, nty, slot_of)
     if (nty_whole > 0) {
       const dim3 gw((unsigned)(ntx * nty_whole) * (unsigned)n), gr((unsigned)(ntx * (nty - nty_whole)) * (unsigned)n);
       if (yin) { BSX_MT(true, true, true, gw, nty_whole, 0); if (nty > nty_whole) BSX_MT(true, true, false, gr, nty - nty_whole, nty_whole); }
@@ -1278,13 +1301,13 @@ hipError_t launch_mask_blend(const uint8_t* ofinal, int outW, int outH, Rect4 in
     } else if (yin) { if (f0) BSX_MT(true, true, false, grid, nty, 0); else BSX_MT(true, false, false, grid, nty, 0); }
     else { if (f0) BSX_MT(false, true, false, grid, nty, 0); else BSX_MT(false, false, false, grid, nty, 0); }
 #undef BSX_MT
-  } else if (yin) mask_upscale_blur_k<true, true><<<grid, kThreads, 0, s>>>(ofinal, outW, outH, in_roi, tab, mask, W, H, roi, bg, (long)bg_stride, frames, out, yuyv, ntx, nty, nf);
-  else mask_upscale_blur_k<true, false><<<grid, kThreads, 0, s>>>(ofinal, outW, outH, in_roi, tab, mask, W, H, roi, bg, (long)bg_stride, frames, out, yuyv, ntx, nty, nf);
+  } else if (yin) mask_upscale_blur_k<true, true><<<grid, kThreads, 0, s>>>(ofinal, outW, outH, in_roi, tab, mask, W, H, roi, bg, (long)bg_stride, frames, out, yuyv, ntx, nty, nf, slot_of);
+  else mask_upscale_blur_k<true, false><<<grid, kThreads, 0, s>>>(ofinal, outW, outH, in_roi, tab, mask, W, H, roi, bg, (long)bg_stride, frames, out, yuyv, ntx, nty, nf, slot_of);
   return hipGetLastError();
 }
 
 hipError_t launch_blend(const uint8_t* bg, size_t bg_stride, const uint8_t* frames, const uint8_t* masks, uint8_t* out, size_t npix, int n,
-                        hipStream_t s) {
+                        hipStream_t s, const int* slot_of) {
   // lane-coalesced form: 4-byte alignment and whole 4-pixel groups are enough; anything else takes the per-pixel kernel
   const bool quad_ok = (((uintptr_t)bg | (uintptr_t)frames | (uintptr_t)masks | (uintptr_t)out) & 3) == 0 && (npix % 4 == 0) && (bg_stride % 4 == 0) && npix / 4 < (1l << 31);
   const long quads = quad_ok ? (long)(npix / 4) : 0;
@@ -1292,10 +1315,11 @@ hipError_t launch_blend(const uint8_t* bg, size_t bg_stride, const uint8_t* fram
     const int nn = n - n0 < kMaxGridY ? n - n0 : kMaxGridY;
     const uint8_t* bgp = bg + (size_t)n0 * bg_stride;
     const uint8_t* fp = frames + (size_t)n0 * npix * 3;
-    const uint8_t* mp = masks + (size_t)n0 * npix;
+    const uint8_t* mp = slot_of ? masks : masks + (size_t)n0 * npix;        // (with slot_of the masks are addressed by stream id, not by position)
+    const int* sp = slot_of ? slot_of + n0 : nullptr;
     uint8_t* op = out + (size_t)n0 * npix * 3;
-    if (quads) blend4x4_k<<<dim3((unsigned)((quads + kThreads * kB4 - 1) / (kThreads * kB4)), nn), kThreads, 0, s>>>(bgp, (long)bg_stride, fp, mp, op, (unsigned)quads, (long)npix);
-    else blend1_k<<<dim3(blocks_for((long)npix), nn), kThreads, 0, s>>>(bgp, (long)bg_stride, fp, mp, op, (long)npix);
+    if (quads) blend4x4_k<<<dim3((unsigned)((quads + kThreads * kB4 - 1) / (kThreads * kB4)), nn), kThreads, 0, s>>>(bgp, (long)bg_stride, fp, mp, op, (unsigned)quads, (long)npix, sp);
+    else blend1_k<<<dim3(blocks_for((long)npix), nn), kThreads, 0, s>>>(bgp, (long)bg_stride, fp, mp, op, (long)npix, sp);
   }
   return hipGetLastError();
 }
@@ -1349,7 +1373,7 @@ constexpr int kGOStride = 196;                   // bytes per packed output row 
 static_assert(kGTH * (kGTW / 4) == kThreads && kGTH * kGOStride <= 3 * kGSH * kGSrcStride, "one 4-pixel group per lane; the output tile aliases the source planes");
 template <int MODE, int NT>
 __global__ __launch_bounds__(kThreads) void gauss_blur_k(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, const uint8_t* __restrict__ mask, int W, int H, GaussCoef gc,
-                                                         int opts) {
+                                                         int opts, const int* __restrict__ slot_of) {
   __shared__ __attribute__((aligned(16))) uint8_t s_src[3 * kGSH * kGSrcStride];          // [plane][row][col]; MODE >= 1: later the packed output tile [row][kGOStride]
   __shared__ __attribute__((aligned(16))) uint16_t s_h[3 * kGHPlane];                     // [plane][col][row], gh_col()
   const size_t img = (size_t)blockIdx.z * (size_t)W * H * 3;
@@ -1364,7 +1388,8 @@ __global__ __launch_bounds__(kThreads) void gauss_blur_k(const uint8_t* __restri
   if (MODE == 2 && olive) {
     const uint32_t* fp = reinterpret_cast<const uint32_t*>(in + (unsigned)(ogy * W + ogx) * 3u);
     fr[0] = fp[0]; fr[1] = fp[1]; fr[2] = fp[2];
-    mw = *reinterpret_cast<const uint32_t*>(mask + (size_t)blockIdx.z * (size_t)W * H + (unsigned)(ogy * W + ogx));
+    const size_t ms = slot_of ? (size_t)slot_of[blockIdx.z] : (size_t)blockIdx.z;      // the frame's persistent mask: state slot (one scalar load)
+    mw = *reinterpret_cast<const uint32_t*>(mask + ms * (size_t)W * H + (unsigned)(ogy * W + ogx));
   }
   // 1. stage + de-interleave (reflected at the image border)
   //    The planes start at source column x0 - r - sh, sh = (-r) & 3 when 4-pixel staging is on (a multiple of 4 → aligned 12-byte groups), else 0; the horizontal
@@ -1503,9 +1528,10 @@ static int gauss_opts(const void* src, int w) {                                 
   return !off && (w & 3) == 0 && (((uintptr_t)src) & 3) == 0 ? 1 : 0;
 }
 template <int MODE>
-static void gauss_launch(dim3 grid, hipStream_t s, const uint8_t* src, uint8_t* dst, const uint8_t* mask, int w, int h, const GaussCoef& gc, int opts) {
+static void gauss_launch(dim3 grid, hipStream_t s, const uint8_t* src, uint8_t* dst, const uint8_t* mask, int w, int h, const GaussCoef& gc, int opts,
+                         const int* slot_of = nullptr) {
   switch ((gc.n + gc.sh + 6) >> 2) {                      // NT = ceil((ksize + 3 + sh) / 4): 2 .. 9
-#define BSX_G(NT) case NT: gauss_blur_k<MODE, NT><<<grid, kThreads, 0, s>>>(src, dst, mask, w, h, gc, opts); break;
+#define BSX_G(NT) case NT: gauss_blur_k<MODE, NT><<<grid, kThreads, 0, s>>>(src, dst, mask, w, h, gc, opts, slot_of); break;
     BSX_G(2) BSX_G(3) BSX_G(4) BSX_G(5) BSX_G(6) BSX_G(7) BSX_G(8) BSX_G(9)
 #undef BSX_G
     default: break;
@@ -1529,13 +1555,15 @@ hipError_t launch_gauss_blur(const uint8_t* src, uint8_t* dst, int w, int h, int
 bool gauss_blend_fusable(const uint8_t* frames, const uint8_t* masks, const uint8_t* out, int w, int ksize) {
   return ksize >= 3 && ksize <= 2 * kGMaxR + 1 && (ksize & 1) && frames != out && gauss_words(frames, masks, out, w);
 }
-hipError_t launch_gauss_blend(const uint8_t* frames, const uint8_t* masks, uint8_t* out, int w, int h, int ksize, int n, hipStream_t s) {
+hipError_t launch_gauss_blend(const uint8_t* frames, const uint8_t* masks, uint8_t* out, int w, int h, int ksize, int n, hipStream_t s, const int* slot_of) {
   GaussCoef gc;
   const int opts = gauss_opts(frames, w);
   if (!gauss_coefficients(ksize, &gc, (opts & 1) ? (-(ksize / 2)) & 3 : 0) || !gauss_blend_fusable(frames, masks, out, w, ksize)) return hipErrorInvalidValue;
   for (int n0 = 0; n0 < n; n0 += kMaxGridY) {
     const int nn = n - n0 < kMaxGridY ? n - n0 : kMaxGridY;
-    gauss_launch<2>(dim3((w + kGTW - 1) / kGTW, (h + kGTH - 1) / kGTH, nn), s, frames + (size_t)n0 * w * h * 3, out + (size_t)n0 * w * h * 3, masks + (size_t)n0 * w * h, w, h, gc, opts);
+    const uint8_t* mp = slot_of ? masks : masks + (size_t)n0 * w * h;        // (with slot_of the masks are addressed by stream id, not by position)
+    gauss_launch<2>(dim3((w + kGTW - 1) / kGTW, (h + kGTH - 1) / kGTH, nn), s, frames + (size_t)n0 * w * h * 3, out + (size_t)n0 * w * h * 3, mp, w, h, gc, opts,
+                    slot_of ? slot_of + n0 : nullptr);
   }
   return hipGetLastError();
 }
@@ -1601,6 +1629,26 @@ hipError_t launch_bgr_to_yuyv(const uint8_t* bgr, uint8_t* yuyv, int w, int h, i
 hipError_t launch_yuyv_to_bgr(const uint8_t* yuyv, uint8_t* bgr, int w, int h, int n, hipStream_t s) {
   long pairs = (long)n * w * h / 2;
   yuyv_to_bgr_k<<<blocks_for(pairs), kThreads, 0, s>>>(reinterpret_cast<const uint32_t*>(yuyv), bgr, pairs);
+  return hipGetLastError();
+}
+
+// bsx_reset_streams: grid row y = listed slot ids[y]; its ofinal bytes -> 0 (the reference leaves them uninitialised, bsx_reset defines 0) and its mask bytes -> 255
+// (libbackscrub.cc:248).  A slot's bytes start at any offset (outW * outH need not be a multiple of 4): byte stores, grid-stride — a reset is rare and small.
+__global__ __launch_bounds__(kThreads) void reset_slots_k(uint8_t* __restrict__ ofinal, size_t ofinal_bytes, uint8_t* __restrict__ masks, size_t mask_bytes,
+                                                        const int* __restrict__ ids) {
+  const size_t slot = (size_t)ids[blockIdx.y];
+  uint8_t* const o = ofinal + slot * ofinal_bytes;
+  uint8_t* const m = masks + slot * mask_bytes;
+  const size_t step = (size_t)gridDim.x * kThreads;
+  for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < ofinal_bytes; i += step) o[i] = 0;
+  for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < mask_bytes; i += step) m[i] = 255;
+}
+hipError_t launch_reset_slots(uint8_t* ofinal, size_t ofinal_bytes, uint8_t* masks, size_t mask_bytes, const int* ids, int n, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  if (n > kMaxGridY) return hipErrorInvalidValue;
+  const size_t most = ofinal_bytes > mask_bytes ? ofinal_bytes : mask_bytes;
+  const unsigned bx = (unsigned)std::min<size_t>((most + kThreads - 1) / kThreads, 256);
+  reset_slots_k<<<dim3(bx, (unsigned)n), kThreads, 0, s>>>(ofinal, ofinal_bytes, masks, mask_bytes, ids);
   return hipGetLastError();
 }
 

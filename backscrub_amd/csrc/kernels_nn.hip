@@ -1535,7 +1535,8 @@ constexpr int kFusedTW = 64, kFusedTH = 16, kFusedMaxSrc = 160;    // source pix
 template <bool PERSON_ONLY, int CC = 0, int PC = -1>      // PERSON_ONLY: only "is the first maximum the person class?" is formed (two running maxima), not the argmax itself;
                                                           // CC / PC: class count and person class as compile-time constants (the scan then resolves per class: one v_max each)
 __global__ __launch_bounds__(kThreads) void resize_argmax_iir_k(const float* __restrict__ x, uint8_t* __restrict__ ofinal, int H, int W, int C_, int OH, int OW,
-                                                               float hs, float ws, int half_pixel, int person_, int ntx, int nty, int n_frames) {
+                                                               float hs, float ws, int half_pixel, int person_, int ntx, int nty, int n_frames,
+                                                               const int* __restrict__ slot_of) {
   const int C = CC > 0 ? CC : C_;
   int person = CC > 0 ? PC : person_;
   __shared__ float src[kFusedMaxSrc * kResizePxMaxC];
@@ -1557,7 +1558,7 @@ __global__ __launch_bounds__(kThreads) void resize_argmax_iir_k(const float* __r
   // of memory latencies (source window → barrier → arithmetic → old byte → store), not of arithmetic, and this takes one link out of it.
   constexpr int PPL = kFusedTH / 4;
   const int ox = ox0 + tx;
-  uint8_t* obase = ofinal + n * (long)OH * OW + ox;
+  uint8_t* obase = ofinal + (slot_of ? (long)slot_of[n] : n) * (long)OH * OW + ox;      // the frame's state slot (bsx_step_batch_streams; else slot n): one scalar load
   uint8_t old[PPL];
 #pragma unroll
   for (int k = 0; k < PPL; k++) { const int oy = oy0 + ty + 4 * k; old[k] = (ox < OW && oy < OH) ? obase[(long)oy * OW] : (uint8_t)0; }
@@ -1683,7 +1684,7 @@ bool resize_argmax_fusable(const Step& st) {
   const int rows = (kFusedTH * st.H + st.OH - 1) / st.OH + 2, cols = (kFusedTW * st.W + st.OW - 1) / st.OW + 2;
   return rows * cols <= kFusedMaxSrc;
 }
-hipError_t launch_resize_argmax_iir(const Step& st, const float* x, uint8_t* ofinal, int n, hipStream_t s, bool generic) {
+hipError_t launch_resize_argmax_iir(const Step& st, const float* x, uint8_t* ofinal, int n, hipStream_t s, bool generic, const int* slot_of) {
   float hs = (float)st.H / (float)st.OH, ws = (float)st.W / (float)st.OW;
   if (st.align_corners && st.OH > 1) hs = (float)(st.H - 1) / (float)(st.OH - 1);
   if (st.align_corners && st.OW > 1) ws = (float)(st.W - 1) / (float)(st.OW - 1);
@@ -1693,9 +1694,9 @@ hipError_t launch_resize_argmax_iir(const Step& st, const float* x, uint8_t* ofi
   static const bool xcd_on = !(BSX_DBG_ENV("BSX_XCD_TILES") && atoi(BSX_DBG_ENV("BSX_XCD_TILES")) == 0);      // A/B timing: 0 = plain frame-major workgroup order
   const int nf = xcd_on ? n : 0;
   const int person = 15;                                           // lib/libbackscrub.cc:330 (pascal VOC class 15)
-  if (!generic && st.Cin == 21 && person == 15) resize_argmax_iir_k<true, 21, 15><<<grid, kThreads, 0, s>>>(x, ofinal, st.H, st.W, st.Cin, st.OH, st.OW, hs, ws, st.half_pixel, person, ntx, nty, nf);   // DeepLab / PASCAL VOC
-  else if (!generic && st.Cin <= 24 && person < st.Cin) resize_argmax_iir_k<true><<<grid, kThreads, 0, s>>>(x, ofinal, st.H, st.W, st.Cin, st.OH, st.OW, hs, ws, st.half_pixel, person, ntx, nty, nf);
-  else resize_argmax_iir_k<false><<<grid, kThreads, 0, s>>>(x, ofinal, st.H, st.W, st.Cin, st.OH, st.OW, hs, ws, st.half_pixel, generic ? -1 - person : person, ntx, nty, nf);
+  if (!generic && st.Cin == 21 && person == 15) resize_argmax_iir_k<true, 21, 15><<<grid, kThreads, 0, s>>>(x, ofinal, st.H, st.W, st.Cin, st.OH, st.OW, hs, ws, st.half_pixel, person, ntx, nty, nf, slot_of);   // DeepLab / PASCAL VOC
+  else if (!generic && st.Cin <= 24 && person < st.Cin) resize_argmax_iir_k<true><<<grid, kThreads, 0, s>>>(x, ofinal, st.H, st.W, st.Cin, st.OH, st.OW, hs, ws, st.half_pixel, person, ntx, nty, nf, slot_of);
+  else resize_argmax_iir_k<false><<<grid, kThreads, 0, s>>>(x, ofinal, st.H, st.W, st.Cin, st.OH, st.OW, hs, ws, st.half_pixel, generic ? -1 - person : person, ntx, nty, nf, slot_of);
   return hipGetLastError();
 }
 

@@ -764,7 +764,7 @@ template <int CO, bool LOGITS, bool SIGMOID, bool H16>
 __global__ __launch_bounds__(kSegThreads) __attribute__((amdgpu_waves_per_eu(5, 5))) void seg_tail_k(
 #endif
     const SegTail d_rt, float* __restrict__ arena, long per_frame, float* __restrict__ net_out,
-                                                          uint8_t* __restrict__ ofinal, const float* __restrict__ w, int n_frames) {
+                                                          uint8_t* __restrict__ ofinal, const float* __restrict__ w, int n_frames, const int* __restrict__ slot_of) {
   BSX_SEG_D(SegTail, TAIL);
   unsigned f_, t_;
   xcd_frame_tile((unsigned)(d.tiles_y * d.tiles_x), (unsigned)n_frames, &f_, &t_);
@@ -773,7 +773,7 @@ __global__ __launch_bounds__(kSegThreads) __attribute__((amdgpu_waves_per_eu(5, 
   float* fa = arena + (size_t)f * (size_t)per_frame;
   float* z_t = seg_smem + kScrFloats;                               // [ZH][16][16]
   float* l_t = z_t + max(ZH * 256, kGateStageFloats);               // staged window of lo
-  uint8_t* of = ofinal + (size_t)f * (size_t)(d.H0 * d.W0);
+  uint8_t* of = ofinal + (size_t)(slot_of ? slot_of[f] : f) * (size_t)(d.H0 * d.W0);   // temporal state: slot slot_of[f] (bsx_step_batch_streams), else f — one scalar load
   float* no = net_out + (size_t)f * (size_t)(d.H0 * d.W0 * CO);
   // Phase B lanes = the MFMA's: lane (li, g) = (pixel li of the tile row, channel quad g) runs the depthwise on its 4 channels; its t = z + act(dw(z)) is then the B
   // operand of the transpose convolution, computed as ONE 16 x 16 MFMA tile per row (round 5): A = the 2x2xCO filter as 16 rows n = 4 * pos + oc (rows with oc >= CO are
@@ -908,7 +908,8 @@ hipError_t launch_seg_k3(const SegK3& d, float* arena, long per_frame, const flo
   return hipGetLastError();
 }
 template <bool H16>
-static hipError_t launch_seg_tail_t(const SegTail& d, float* arena, long per_frame, float* net_out, uint8_t* ofinal, const float* weights, bool logits, int n, hipStream_t s) {
+static hipError_t launch_seg_tail_t(const SegTail& d, float* arena, long per_frame, float* net_out, uint8_t* ofinal, const float* weights, bool logits, int n, hipStream_t s,
+                                    const int* slot_of) {
   const dim3 grid((unsigned)(d.tiles_y * d.tiles_x) * (unsigned)n);
   // BSX_SEG_TAIL_WGS=<k> (experiment switch, read once): pad the dynamic LDS so that at most k workgroups fit a CU — the A/B of the tail's 5th workgroup (round 5)
   static const int wgs_cap = BSX_DBG_ENV("BSX_SEG_TAIL_WGS") ? atoi(BSX_DBG_ENV("BSX_SEG_TAIL_WGS")) : 0;
@@ -916,14 +917,14 @@ static hipError_t launch_seg_tail_t(const SegTail& d, float* arena, long per_fra
   if (wgs_cap > 0) lds = std::max(lds, (size_t)(160 * 1024 / (wgs_cap + 1) + 256));
   const bool sig = d.act3 == kActSigmoid;
   if (d.Co == 2 && !sig) {
-    if (logits) seg_tail_k<2, true, false, H16><<<grid, kSegThreads, lds, s>>>(d, arena, per_frame, net_out, ofinal, weights, xcd_frames(n));
-    else seg_tail_k<2, false, false, H16><<<grid, kSegThreads, lds, s>>>(d, arena, per_frame, net_out, ofinal, weights, xcd_frames(n));
+    if (logits) seg_tail_k<2, true, false, H16><<<grid, kSegThreads, lds, s>>>(d, arena, per_frame, net_out, ofinal, weights, xcd_frames(n), slot_of);
+    else seg_tail_k<2, false, false, H16><<<grid, kSegThreads, lds, s>>>(d, arena, per_frame, net_out, ofinal, weights, xcd_frames(n), slot_of);
   } else if (d.Co == 1 && sig) {
-    if (logits) seg_tail_k<1, true, true, H16><<<grid, kSegThreads, lds, s>>>(d, arena, per_frame, net_out, ofinal, weights, xcd_frames(n));
-    else seg_tail_k<1, false, true, H16><<<grid, kSegThreads, lds, s>>>(d, arena, per_frame, net_out, ofinal, weights, xcd_frames(n));
+    if (logits) seg_tail_k<1, true, true, H16><<<grid, kSegThreads, lds, s>>>(d, arena, per_frame, net_out, ofinal, weights, xcd_frames(n), slot_of);
+    else seg_tail_k<1, false, true, H16><<<grid, kSegThreads, lds, s>>>(d, arena, per_frame, net_out, ofinal, weights, xcd_frames(n), slot_of);
   } else if (d.Co == 1) {
-    if (logits) seg_tail_k<1, true, false, H16><<<grid, kSegThreads, lds, s>>>(d, arena, per_frame, net_out, ofinal, weights, xcd_frames(n));
-    else seg_tail_k<1, false, false, H16><<<grid, kSegThreads, lds, s>>>(d, arena, per_frame, net_out, ofinal, weights, xcd_frames(n));
+    if (logits) seg_tail_k<1, true, false, H16><<<grid, kSegThreads, lds, s>>>(d, arena, per_frame, net_out, ofinal, weights, xcd_frames(n), slot_of);
+    else seg_tail_k<1, false, false, H16><<<grid, kSegThreads, lds, s>>>(d, arena, per_frame, net_out, ofinal, weights, xcd_frames(n), slot_of);
   } else {
     return hipErrorInvalidValue;
   }
@@ -933,8 +934,10 @@ hipError_t launch_seg_gate(const SegGate& gt, float* arena, long per_frame, cons
   seg_gate_k<<<n, kSegThreads, (size_t)(kSegScratchFloats + kSegGateStageFloats) * sizeof(float), s>>>(gt, arena, per_frame, weights, out_off);
   return hipGetLastError();
 }
-hipError_t launch_seg_tail(const SegTail& d, float* arena, long per_frame, float* net_out, uint8_t* ofinal, const float* weights, bool logits, int n, hipStream_t s, bool h16) {
-  return h16 ? launch_seg_tail_t<true>(d, arena, per_frame, net_out, ofinal, weights, logits, n, s) : launch_seg_tail_t<false>(d, arena, per_frame, net_out, ofinal, weights, logits, n, s);
+hipError_t launch_seg_tail(const SegTail& d, float* arena, long per_frame, float* net_out, uint8_t* ofinal, const float* weights, bool logits, int n, hipStream_t s, bool h16,
+                           const int* slot_of) {
+  return h16 ? launch_seg_tail_t<true>(d, arena, per_frame, net_out, ofinal, weights, logits, n, s, slot_of)
+             : launch_seg_tail_t<false>(d, arena, per_frame, net_out, ofinal, weights, logits, n, s, slot_of);
 }
 
 #endif

@@ -20,6 +20,8 @@
  *   bsx_step_batch_ex      … with cv::flip (and YUYV) fused  app/deepseg.cc:667-681; BSX_STEP_YUYV_IN: … and VideoCapture's YUYV->BGR  app/deepseg.cc:553,725
  *   bsx_step_batch_pipelined  … with the CalcMask worker's overlap of segmentation and blending  app/deepseg.cc:159-285, 634-661
  *   bsx_step_batch_vcam    … with the resize to the virtual camera's geometry (--vg) fused  app/deepseg.cc:634-681 (the resize: :675-679)
+ *   bsx_step_batch_streams … for the streams that HAVE a new frame, addressed by id  app/deepseg.cc:182-216 (one filter step per new frame)
+ *   bsx_reset_streams      bsx_reset for a chosen subset of the streams (a slot reused for a new camera)
  *                          (set_input_frame → mask → alpha_blend), batched
  *   bsx_resize_bgr         grab_background() cv::resize   app/background.cc:178-194
  *   bsx_bgr_to_yuyv        convert_rgb_to_yuyv()          app/deepseg.cc:87-106
@@ -108,7 +110,7 @@ BSX_API int bsx_get_info(const bsx_ctx* ctx, bsx_info* out);
 /* Last error text for this context (or the global one if ctx==NULL); static/ctx storage. */
 BSX_API const char* bsx_last_error(const bsx_ctx* ctx);
 
-/* Reset the per-stream temporal state (`ofinal` → 0, `mask` → 255) of all streams. */
+/* Reset the per-stream temporal state (`ofinal` → 0, `mask` → 255) of all streams.  bsx_reset_streams (below) resets a chosen subset. */
 BSX_API int bsx_reset(bsx_ctx* ctx, void* stream);
 
 /* Drop-in single-frame path.  h_bgr: height rows of width*3 bytes, `bgr_stride` bytes apart
@@ -119,7 +121,7 @@ BSX_API int bsx_process_host(bsx_ctx* ctx, int stream_idx, const uint8_t* h_bgr,
                      uint8_t* h_mask, size_t mask_stride);
 
 /* Batched device path: frames [n][height][width][3] u8 contiguous (n <= n_streams; frame i
- * belongs to stream i).  Updates each stream's temporal state and its persistent full-frame
+ * belongs to stream i — the dense contract; only bsx_step_batch_streams takes stream ids).  Updates each stream's temporal state and its persistent full-frame
  * mask.  If d_masks != NULL the masks are also copied there ([n][height][width]).
  * Asynchronous on `stream` unless callbacks are set (each callback needs a stream sync). */
 BSX_API int bsx_process_batch(bsx_ctx* ctx, const uint8_t* d_frames, int n, uint8_t* d_masks, void* stream);
@@ -178,7 +180,28 @@ BSX_API int bsx_step_batch_yuyv(bsx_ctx* ctx, const uint8_t* d_frames, const uin
 BSX_API int bsx_step_batch_ex(bsx_ctx* ctx, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_frame_stride,
                       uint8_t* d_out, int n, void* stream, unsigned flags);
 
-/* Throughput mode — the same main-loop iteration as a TWO-DEEP PIPELINE.  The reference runs its two halves concurrently: CalcMask::run() segments on a
+/* One main-loop iteration for the streams named in ids[0..n): frame i, background i (bg_frame_stride as in bsx_step_batch_ex) and output i belong to stream
+ * ids[i]; its temporal state and persistent mask are read and advanced in place; every other stream's state is untouched.  Every other batched entry point ties
+ * batch position to state slot (frame i = stream i); a server whose cameras deliver at different rates, or join and leave, steps only the streams with a NEW frame
+ * — the reference filters each frame once (CalcMask::run waits for a new frame, app/deepseg.cc:182-216; lib/libbackscrub.cc:315-356 advances once per call).
+ *   - ids: host array of n distinct values in [0, n_streams), any order; read before the call returns (the caller may reuse it at once).  The library stages it
+ *     through a small context-owned ring (pinned host + device memory, allocated on the first call): the host waits only when it runs several calls ahead of the GPU;
+ *   - n == 0: returns 0 and enqueues nothing.  flags: exactly those of bsx_step_batch_ex (YUYV, FLIP_H / _V, NO_MASK, YUYV_IN, BGBLUR(k)), every route included;
+ *   - result: bit-identical, per stream, to what that stream's frames would produce stepped alone (a one-stream context fed only its own frames); ids = 0 .. n-1
+ *     is bsx_step_batch_ex(flags);
+ *   - BSX_EINVAL, with a bsx_last_error text naming the offending position and value, for a duplicate id, an id out of range, n < 0 or n > n_streams; also for
+ *     a pending pipelined composite and every argument bsx_step_batch_ex refuses.  All checks run on the host before anything is enqueued: a refused call changes
+ *     no state.
+ * bsx_step_batch_pipelined, bsx_step_batch_vcam and bsx_process_batch keep the dense contract (frame i = stream i). */
+BSX_API int bsx_step_batch_streams(bsx_ctx* ctx, const int* ids, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_frame_stride,
+                                   uint8_t* d_out, int n, void* stream, unsigned flags);
+
+/* Reset the temporal state of the listed streams only (ofinal → 0, persistent mask → 255, as bsx_reset does for all) — a slot reused for a new camera.  The
+ * other streams' state is untouched, and a pending pipelined composite is NOT dropped: the call is refused (BSX_EINVAL) while one is pending.  Same ids rules,
+ * errors and staging as bsx_step_batch_streams; asynchronous on `stream`. */
+BSX_API int bsx_reset_streams(bsx_ctx* ctx, const int* ids, int n, void* stream);
+
+/* Throughput mode — the same main-loop iteration as a TWO-DEEP PIPELINE (dense contract: frame i = stream i).  The reference runs its two halves concurrently: CalcMask::run() segments on a
  * worker thread (app/deepseg.cc:182-216) while the capture loop blends and writes (:634-681).  Call k enqueues the mask pipeline (prep → network → decode /
  * temporal filter) of batch k on `stream` and, concurrently on a context-owned low-priority stream, the mask up-scale + blur + composite of batch k - 1 — the
  * HBM-bound half fills the gaps of the latency-bound half instead of waiting behind it.  Every frame is still composited with ITS OWN mask (the reference's
@@ -194,7 +217,7 @@ BSX_API int bsx_step_batch_ex(bsx_ctx* ctx, const uint8_t* d_frames, const uint8
 BSX_API int bsx_step_batch_pipelined(bsx_ctx* ctx, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_frame_stride,
                              uint8_t* d_out, int n, void* stream, unsigned flags);
 
-/* One main-loop iteration whose output has the VIRTUAL CAMERA's geometry (--vg differs from the capture size, app/deepseg.cc:675-679).  For every stream, in the
+/* One main-loop iteration whose output has the VIRTUAL CAMERA's geometry (--vg differs from the capture size, app/deepseg.cc:675-679; dense contract: frame i = stream i).  For every stream, in the
  * reference's order: C = alpha_blend(bg, frame, mask) at the capture size; F = cv::flip(C) with BSX_STEP_FLIP_H / _V; R = cv::resize(F, Size(out_w, out_h))
  * with INTER_LINEAR (the 2x2 area mean when both scales are exactly 2 — the integers of bsx_resize_bgr); convert_rgb_to_yuyv(R) with BSX_STEP_YUYV.
  * d_out is [n][out_h][out_w][3], or [n][out_h][out_w][2] with BSX_STEP_YUYV.  The masks are made as bsx_process_batch makes them (persistent masks, temporal
