@@ -133,6 +133,11 @@ def _torch():
     return torch
 
 
+def _ptr(t):
+    """a tensor's device address for the C ABI (None: NULL)"""
+    return C.c_void_p(t.data_ptr() if t is not None else None)
+
+
 def _stream_ptr():
     torch = _torch()
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -184,6 +189,18 @@ class MaskGen:
             raise BsxError("bg must be a cuda:%d uint8 tensor [%d,%d,3] or [>=%d,%d,%d,3] with contiguous images" % (self.device, self.height, self.width, n, self.height, self.width))
         return 0 if bg.dim() == 3 else int(bg.stride(0))
 
+    def _step_out(self, out, n, yuyv):
+        want = (self.height, self.width, 2 if yuyv else 3)
+        if out.dim() != 4 or tuple(out.shape[1:]) != want or out.shape[0] < n or not out.is_contiguous() or not out.is_cuda or out.dtype != _torch().uint8:
+            raise BsxError("out must be a contiguous cuda uint8 tensor [>=%d,%d,%d,%d]" % ((n,) + want))
+
+    def _step_flags(self, bg, n, flip_h=False, flip_v=False, yuyv=False, no_mask=False, yuyv_in=False, bgblur=0):
+        """the flags word of a step (bsx.h BSX_STEP_*) and bg_frame_stride; bg may be None only with bgblur"""
+        if bg is None and not bgblur:
+            raise BsxError("bg is required unless bgblur is set")
+        flags = (1 if yuyv else 0) | (2 if flip_h else 0) | (4 if flip_v else 0) | (8 if no_mask else 0) | (16 if yuyv_in else 0) | ((int(bgblur) & 255) << 8)
+        return flags, (0 if bg is None else self._bg(bg, n))
+
     def step(self, frames, bg, out):
         n = self._n(frames)
         stride = self._bg(bg, n)
@@ -207,15 +224,9 @@ class MaskGen:
         bgblur=<odd ksize>: the background is GaussianBlur(the stream's own frame) (-p bgblur:<n> without -b, deepseg.cc:652-661), `bg` may be None;
         yuyv_in: `frames` is the camera's raw YUYV 4:2:2 [n,H,W,2] (cv::COLOR_YUV2BGR_YUYV folded into the kernels that read it: BSX_STEP_YUYV_IN)"""
         n = self._n(frames, yuyv_in)
-        want = (self.height, self.width, 2 if yuyv else 3)
-        if out.dim() != 4 or tuple(out.shape[1:]) != want or out.shape[0] < n or not out.is_contiguous() or not out.is_cuda or out.dtype != _torch().uint8:
-            raise BsxError("out must be a contiguous cuda uint8 tensor [>=%d,%d,%d,%d]" % ((n,) + want))
-        if bg is None and not bgblur:
-            raise BsxError("bg is required unless bgblur is set")
-        stride = 0 if bg is None else self._bg(bg, n)
-        flags = (1 if yuyv else 0) | (2 if flip_h else 0) | (4 if flip_v else 0) | (8 if no_mask else 0) | (16 if yuyv_in else 0) | ((int(bgblur) & 255) << 8)
-        _check(lib().bsx_step_batch_ex(self.h, C.c_void_p(frames.data_ptr()), C.c_void_p(bg.data_ptr() if bg is not None else None), stride,
-                                       C.c_void_p(out.data_ptr()), n, _stream_ptr(), flags), self.h, "bsx_step_batch_ex")
+        self._step_out(out, n, yuyv)
+        flags, stride = self._step_flags(bg, n, flip_h, flip_v, yuyv, no_mask, yuyv_in, bgblur)
+        _check(lib().bsx_step_batch_ex(self.h, _ptr(frames), _ptr(bg), stride, _ptr(out), n, _stream_ptr(), flags), self.h, "bsx_step_batch_ex")
         return out
 
     def step_streams(self, ids, frames, bg, out, flip_h=False, flip_v=False, yuyv=False, no_mask=False, bgblur=0, yuyv_in=False):
@@ -228,15 +239,9 @@ class MaskGen:
         n = self._n(frames, yuyv_in)
         if n != n_ids:
             raise BsxError("%d ids for a batch of %d frames" % (n_ids, n))
-        want = (self.height, self.width, 2 if yuyv else 3)
-        if out.dim() != 4 or tuple(out.shape[1:]) != want or out.shape[0] < n or not out.is_contiguous() or not out.is_cuda or out.dtype != _torch().uint8:
-            raise BsxError("out must be a contiguous cuda uint8 tensor [>=%d,%d,%d,%d]" % ((n,) + want))
-        if bg is None and not bgblur:
-            raise BsxError("bg is required unless bgblur is set")
-        stride = 0 if bg is None else self._bg(bg, n)
-        flags = (1 if yuyv else 0) | (2 if flip_h else 0) | (4 if flip_v else 0) | (8 if no_mask else 0) | (16 if yuyv_in else 0) | ((int(bgblur) & 255) << 8)
-        _check(lib().bsx_step_batch_streams(self.h, arr, C.c_void_p(frames.data_ptr()), C.c_void_p(bg.data_ptr() if bg is not None else None), stride,
-                                            C.c_void_p(out.data_ptr()), n, _stream_ptr(), flags), self.h, "bsx_step_batch_streams")
+        self._step_out(out, n, yuyv)
+        flags, stride = self._step_flags(bg, n, flip_h, flip_v, yuyv, no_mask, yuyv_in, bgblur)
+        _check(lib().bsx_step_batch_streams(self.h, arr, _ptr(frames), _ptr(bg), stride, _ptr(out), n, _stream_ptr(), flags), self.h, "bsx_step_batch_streams")
         return out
 
     def reset_streams(self, ids):
@@ -254,13 +259,9 @@ class MaskGen:
         n = self._n(frames, yuyv_in)
         if out.shape[0] < n:
             raise BsxError("out holds %d frames, the batch has %d" % (out.shape[0], n))
-        if bg is None and not bgblur:
-            raise BsxError("bg is required unless bgblur is set")
-        stride = 0 if bg is None else self._bg(bg, n)
-        out_h, out_w = int(out.shape[1]), int(out.shape[2])
-        flags = (1 if yuyv else 0) | (2 if flip_h else 0) | (4 if flip_v else 0) | (16 if yuyv_in else 0) | ((int(bgblur) & 255) << 8)
-        _check(lib().bsx_step_batch_vcam(self.h, C.c_void_p(frames.data_ptr()), C.c_void_p(bg.data_ptr() if bg is not None else None), stride,
-                                         C.c_void_p(out.data_ptr()), out_w, out_h, n, _stream_ptr(), flags), self.h, "bsx_step_batch_vcam")
+        flags, stride = self._step_flags(bg, n, flip_h, flip_v, yuyv, False, yuyv_in, bgblur)
+        _check(lib().bsx_step_batch_vcam(self.h, _ptr(frames), _ptr(bg), stride, _ptr(out), int(out.shape[2]), int(out.shape[1]), n, _stream_ptr(), flags),
+               self.h, "bsx_step_batch_vcam")
         return out
 
     def step_pipelined(self, frames, bg, out, flip_h=False, flip_v=False, yuyv=False, no_mask=False, yuyv_in=False):
@@ -268,13 +269,9 @@ class MaskGen:
         the previous call (the reference's CalcMask worker next to its blend loop, app/deepseg.cc:159-285).  `out` — and masks() — hold THIS batch's results
         once the NEXT call (or flush_pipelined()) has completed; frames / bg / out must stay untouched until then.  Bit-identical to step_ex per batch."""
         n = self._n(frames, yuyv_in)
-        want = (self.height, self.width, 2 if yuyv else 3)
-        if out.dim() != 4 or tuple(out.shape[1:]) != want or out.shape[0] < n or not out.is_contiguous() or not out.is_cuda or out.dtype != _torch().uint8:
-            raise BsxError("out must be a contiguous cuda uint8 tensor [>=%d,%d,%d,%d]" % ((n,) + want))
-        stride = self._bg(bg, n)
-        flags = (1 if yuyv else 0) | (2 if flip_h else 0) | (4 if flip_v else 0) | (8 if no_mask else 0) | (16 if yuyv_in else 0)
-        _check(lib().bsx_step_batch_pipelined(self.h, C.c_void_p(frames.data_ptr()), C.c_void_p(bg.data_ptr()), stride, C.c_void_p(out.data_ptr()), n, _stream_ptr(), flags),
-               self.h, "bsx_step_batch_pipelined")
+        self._step_out(out, n, yuyv)
+        flags, stride = self._step_flags(bg, n, flip_h, flip_v, yuyv, no_mask, yuyv_in)
+        _check(lib().bsx_step_batch_pipelined(self.h, _ptr(frames), _ptr(bg), stride, _ptr(out), n, _stream_ptr(), flags), self.h, "bsx_step_batch_pipelined")
         # the composite of THIS batch is enqueued by the NEXT call, on a stream torch's caching allocator knows nothing about: the three tensors stay referenced
         # here until then (a caller that drops them would otherwise have their memory handed out again under the pending kernel) — and for ONE MORE call: a caller
         # that alternates streams gets composite k joined into the stream of call k + 1, so a block of call k's stream freed right after call k + 1 could be handed

@@ -295,6 +295,8 @@ int init_device_state(bsx_ctx* c) {
   // spill (DeepLab: 33x33x480) run faster as one batch-wide launch per step.  BSX_FORCE_FRAME_PROGRAM / BSX_NO_FRAME_PROGRAM override.
   c->use_program = !c->plan.program.empty() && BSX_DBG_ENV("BSX_NO_FRAME_PROGRAM") == nullptr &&
                    (c->plan.seg.on || c->plan.program_lds_tensors >= c->plan.program_global_tensors || BSX_DBG_ENV("BSX_FORCE_FRAME_PROGRAM") != nullptr);
+  hipDeviceProp_t prop;                       // the architecture the graph-specialised kernels are compiled for (below)
+  const bool have_prop = c->use_program && !BSX_DBG_ENV("BSX_NO_RTC") && hipGetDeviceProperties(&prop, c->device) == hipSuccess;
   if (c->use_program) {
     BSX_HIP(c, hipMalloc(&c->d_program, c->plan.program.size() * sizeof(MicroOp)));
     BSX_HIP(c, hipMemcpy(c->d_program, c->plan.program.data(), c->plan.program.size() * sizeof(MicroOp), hipMemcpyHostToDevice));
@@ -306,9 +308,8 @@ int init_device_state(bsx_ctx* c) {
     const char* a16 = getenv("BSX_ACT16");
     c->act16 = a16 && atoi(a16) != 0 && c->plan.seg.on;
     if (!BSX_DBG_ENV("BSX_NO_RTC")) {
-      hipDeviceProp_t prop;
       MidBuild mb;
-      if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) c->mid_note = "interpreted (no device properties)";
+      if (!have_prop) c->mid_note = "interpreted (no device properties)";
       else {
         const std::string err = build_mid_kernel(c->plan, c->act16, prop.gcnArchName, &mb);
         if (!err.empty()) c->mid_note = err;
@@ -342,10 +343,9 @@ int init_device_state(bsx_ctx* c) {
   if (c->use_program && c->plan.seg.on) {
     if (BSX_DBG_ENV("BSX_NO_RTC")) c->seg_note = "ahead-of-time kernels (BSX_NO_RTC)";
     else {
-      hipDeviceProp_t prop;
       std::vector<char> code;
       bool cached = false;
-      if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) c->seg_note = "ahead-of-time kernels (no device properties)";
+      if (!have_prop) c->seg_note = "ahead-of-time kernels (no device properties)";
       else {
         c->seg_note = build_seg_kernels(c->plan, c->act16, c->in_u8, prop.gcnArchName, &code, &cached);
         if (c->seg_note.empty()) {
@@ -404,12 +404,22 @@ int init_device_state(bsx_ctx* c) {
 // non-blocking stream is only used by the synchronous host path.
 hipStream_t pick(bsx_ctx*, void* s) { return (hipStream_t)s; }
 
+// bsx_profile_batch times launch k of the step from event ev[k - 1] to ev[k] (ev[0]: in front of the first), for as many launches as its table has rows.  The
+// launches of the step take a nullable timer: without one the cost is one null-pointer test per launch.
+struct LaunchTimer { std::vector<hipEvent_t> ev; int k = 0; ~LaunchTimer() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); } };
+int timed(bsx_ctx* c, LaunchTimer* t, hipStream_t s) {
+  if (t->k + 1 >= (int)t->ev.size()) { c->last_error = "error: bsx_profile_batch: the step made more launches than the profile counts\n"; return BSX_EDEVICE; }
+  BSX_HIP(c, hipEventRecord(t->ev[++t->k], s));
+  return BSX_OK;
+}
+#define BSX_LAUNCH(c, t, s, expr) do { BSX_HIP(c, (expr)); if (t) { const int trc_ = timed(c, t, s); if (trc_) return trc_; } } while (0)
+
 // with_f32: also materialise the f32 input tensor when the stem reads the 8-bit form (the stage-debug entry: tests inspect the tensor)
-int run_prep(bsx_ctx* c, const uint8_t* d_frames, int n, hipStream_t s, bool with_f32 = false, bool yuyv_in = false) {
+int run_prep(bsx_ctx* c, const uint8_t* d_frames, int n, hipStream_t s, bool with_f32 = false, bool yuyv_in = false, LaunchTimer* t = nullptr) {
   bsx_roctx::Range range("bsx:prep");
   float* f32 = (!c->in_u8 || with_f32) ? c->tensor_ptr(c->plan.input) : nullptr;
   uint32_t* u8 = c->in_u8 ? c->d_net_in_u8 : nullptr;
-  BSX_HIP(c, launch_prep_fused(d_frames, c->width, c->height, c->roi, f32, u8, c->inW, c->inH, c->in_roi, c->tab_down.tab, c->bilateral, n, s, yuyv_in));
+  BSX_LAUNCH(c, t, s, launch_prep_fused(d_frames, c->width, c->height, c->roi, f32, u8, c->inW, c->inH, c->in_roi, c->tab_down.tab, c->bilateral, n, s, yuyv_in));
   return BSX_OK;
 }
 // logits = true: the network output tensor is written (stage tests, the stand-alone decode follows); false: the tail kernel of a
@@ -456,22 +466,16 @@ hipError_t seg_head(bsx_ctx* c, int n, hipStream_t s) {
   void* args[] = {&d, &arena, &pf, &in, &w, &sc, &of, &nf};
   return seg_launch(c->seg_mod.fn, d.tiles_y * d.tiles_x, n, d.lds_floats, s, args);
 }
-hipError_t seg_k2(bsx_ctx* c, int n, hipStream_t s) {
-  const SegPlan& sp = c->plan.seg;
+// k2 (fn = seg_fn[0], descriptor plan.seg.k2) and k3 (seg_fn[1], plan.seg.k3) take the same arguments
+template <class D> hipError_t seg_mid(bsx_ctx* c, D d, hipFunction_t fn, hipError_t (*aot)(const D&, float*, long, const float*, int, hipStream_t, bool), int n, hipStream_t s) {
   long pf = (long)c->plan.arena_floats_per_stream;
-  if (!c->seg_fn[0]) return launch_seg_k2(sp.k2, c->d_arena, pf, c->d_weights, n, s, c->act16);
-  SegK2 d = sp.k2; float* arena = c->d_arena; const float* w = c->d_weights; int nf = n;
+  if (!fn) return aot(d, c->d_arena, pf, c->d_weights, n, s, c->act16);
+  float* arena = c->d_arena; const float* w = c->d_weights; int nf = n;
   void* args[] = {&d, &arena, &pf, &w, &nf};
-  return seg_launch(c->seg_fn[0], d.tiles_y * d.tiles_x, n, d.lds_floats, s, args);
+  return seg_launch(fn, d.tiles_y * d.tiles_x, n, d.lds_floats, s, args);
 }
-hipError_t seg_k3(bsx_ctx* c, int n, hipStream_t s) {
-  const SegPlan& sp = c->plan.seg;
-  long pf = (long)c->plan.arena_floats_per_stream;
-  if (!c->seg_fn[1]) return launch_seg_k3(sp.k3, c->d_arena, pf, c->d_weights, n, s, c->act16);
-  SegK3 d = sp.k3; float* arena = c->d_arena; const float* w = c->d_weights; int nf = n;
-  void* args[] = {&d, &arena, &pf, &w, &nf};
-  return seg_launch(c->seg_fn[1], d.tiles_y * d.tiles_x, n, d.lds_floats, s, args);
-}
+hipError_t seg_k2(bsx_ctx* c, int n, hipStream_t s) { return seg_mid(c, c->plan.seg.k2, c->seg_fn[0], launch_seg_k2, n, s); }
+hipError_t seg_k3(bsx_ctx* c, int n, hipStream_t s) { return seg_mid(c, c->plan.seg.k3, c->seg_fn[1], launch_seg_k3, n, s); }
 hipError_t seg_tail(bsx_ctx* c, uint8_t* ofinal, bool logits, int n, hipStream_t s, const int* ids = nullptr) {
   const SegPlan& sp = c->plan.seg;
   long pf = (long)c->plan.arena_floats_per_stream;
@@ -483,72 +487,359 @@ hipError_t seg_tail(bsx_ctx* c, uint8_t* ofinal, bool logits, int n, hipStream_t
 }
 
 // ids (device, nullable): the id form of a step — frame i's temporal state is slot ids[i] (then slot == 0); nullptr = slots [slot, slot + n)
-int run_infer(bsx_ctx* c, int n, hipStream_t s, bool logits = true, int slot = 0, const int* ids = nullptr) {
+int run_infer(bsx_ctx* c, int n, hipStream_t s, bool logits = true, int slot = 0, const int* ids = nullptr, LaunchTimer* t = nullptr) {
   bsx_roctx::Range range("bsx:network");
   if (c->use_program && c->plan.seg.on) {
     const SegPlan& sp = c->plan.seg;
     const long pf = (long)c->plan.arena_floats_per_stream;
-    BSX_HIP(c, seg_head(c, n, s));
-    BSX_HIP(c, seg_k2(c, n, s));
-    BSX_HIP(c, launch_program(c, n, s));
-    BSX_HIP(c, seg_k3(c, n, s));
-    if (sp.tail.pre_gate_off >= 0) BSX_HIP(c, launch_seg_gate(sp.tail.gate, c->d_arena, pf, c->d_weights, sp.tail.pre_gate_off, n, s));
+    BSX_LAUNCH(c, t, s, seg_head(c, n, s));
+    BSX_LAUNCH(c, t, s, seg_k2(c, n, s));
+    BSX_LAUNCH(c, t, s, launch_program(c, n, s));
+    BSX_LAUNCH(c, t, s, seg_k3(c, n, s));
+    if (sp.tail.pre_gate_off >= 0) BSX_LAUNCH(c, t, s, launch_seg_gate(sp.tail.gate, c->d_arena, pf, c->d_weights, sp.tail.pre_gate_off, n, s));
     if (!logits) { const int frc = state_write_fence(c, s); if (frc) return frc; }       // the decoding tail reads and writes d_ofinal
-    BSX_HIP(c, seg_tail(c, c->d_ofinal + (size_t)slot * c->outW * c->outH, logits, n, s, ids));
+    BSX_LAUNCH(c, t, s, seg_tail(c, c->d_ofinal + (size_t)slot * c->outW * c->outH, logits, n, s, ids));
     return BSX_OK;
   }
   if (c->use_program) {
-    BSX_HIP(c, launch_program(c, n, s));
+    BSX_LAUNCH(c, t, s, launch_program(c, n, s));
     return BSX_OK;
   }
   const bool fused_tail = !logits && argmax_tail(c);
   const size_t ns = c->plan.steps.size() - (fused_tail ? 1 : 0);
   for (size_t i = 0; i < ns; i++)
-    BSX_HIP(c, launch_step(c->plan.steps[i], c->plan, c->d_arena, c->d_net_in, c->d_net_out, c->d_weights, n, c->n_streams, s, c->d_weights16, c->f16_terms, c->in_u8 ? c->d_net_in_u8 : nullptr, c->norm_scale, c->norm_offset));
+    BSX_LAUNCH(c, t, s, launch_step(c->plan.steps[i], c->plan, c->d_arena, c->d_net_in, c->d_net_out, c->d_weights, n, c->n_streams, s, c->d_weights16, c->f16_terms, c->in_u8 ? c->d_net_in_u8 : nullptr, c->norm_scale, c->norm_offset));
   if (fused_tail) {
     const Step& last = c->plan.steps.back();
     { const int frc = state_write_fence(c, s); if (frc) return frc; }
-    BSX_HIP(c, launch_resize_argmax_iir(last, c->d_arena + (size_t)c->plan.tensor_off[last.in0] * (size_t)c->n_streams,
-                                        c->d_ofinal + (size_t)slot * c->outW * c->outH, n, s, c->tail_generic, ids));
+    BSX_LAUNCH(c, t, s, launch_resize_argmax_iir(last, c->d_arena + (size_t)c->plan.tensor_off[last.in0] * (size_t)c->n_streams,
+                                                 c->d_ofinal + (size_t)slot * c->outW * c->outH, n, s, c->tail_generic, ids));
   }
   return BSX_OK;
 }
 // `slot` = first state slot (stream index) of the batch: frame i uses ofinal / mask slot `slot + i`
-int run_decode(bsx_ctx* c, int n, hipStream_t s, int slot = 0, const int* ids = nullptr) {
+int run_decode(bsx_ctx* c, int n, hipStream_t s, int slot = 0, const int* ids = nullptr, LaunchTimer* t = nullptr) {
   bsx_roctx::Range range("bsx:decode");
   { const int frc = state_write_fence(c, s); if (frc) return frc; }
-  BSX_HIP(c, launch_decode(c->model_type, c->tensor_ptr(c->plan.output), c->d_ofinal + (size_t)slot * c->outW * c->outH, c->outW * c->outH, c->outC, n, s, ids));
+  BSX_LAUNCH(c, t, s, launch_decode(c->model_type, c->tensor_ptr(c->plan.output), c->d_ofinal + (size_t)slot * c->outW * c->outH, c->outW * c->outH, c->outC, n, s, ids));
   return BSX_OK;
 }
 // the mask up-scale table with its tile-class scratch re-based to stream `slot` (lanes run concurrently on disjoint slot ranges)
-ResizeTab tab_up_at(const bsx_ctx* c, int slot) {
-  ResizeTab t = c->tab_up.tab;
-  if (t.tile_class) t.tile_class += (size_t)slot * c->tiles_per_frame;
-  return t;
-}
-int run_mask(bsx_ctx* c, int n, hipStream_t s, int slot = 0, const int* ids = nullptr) {
+ResizeTab tab_up_at(const bsx_ctx* c, int slot) { ResizeTab t = c->tab_up.tab; if (t.tile_class) t.tile_class += (size_t)slot * c->tiles_per_frame; return t; }
+int run_mask(bsx_ctx* c, int n, hipStream_t s, int slot = 0, const int* ids = nullptr, LaunchTimer* t = nullptr) {
   bsx_roctx::Range range("bsx:mask");
-  BSX_HIP(c, launch_mask_upscale_blur(c->d_ofinal + (size_t)slot * c->outW * c->outH, c->outW, c->outH, c->in_roi, tab_up_at(c, slot),
+  BSX_LAUNCH(c, t, s, launch_mask_upscale_blur(c->d_ofinal + (size_t)slot * c->outW * c->outH, c->outW, c->outH, c->in_roi, tab_up_at(c, slot),
                                       c->d_masks + (size_t)slot * c->width * c->height, c->width, c->height, c->roi, n, s, ids));
   return BSX_OK;
 }
-// bs_maskgen_process for n frames whose per-stream state lives in slots [slot, slot + n) — or, with ids (device, slot = 0), in slots ids[0..n);
-// yuyv_in: YUYV 4:2:2 frames (only where prep_yuyv_fusable)
-int process_impl(bsx_ctx* c, const uint8_t* d_frames, int n, int slot, hipStream_t s, bool yuyv_in = false, const int* ids = nullptr) {
-  int rc;
-  if ((rc = run_prep(c, d_frames, n, s, false, yuyv_in))) return rc;
-  if (c->onprep) { BSX_HIP(c, hipStreamSynchronize(s)); c->onprep(c->caller_ctx); }   // :303
+// prep → [onprep] → network → [oninfer] → decode (unless the network decodes) for n frames whose state lives in slots [slot, slot + n) — or, with ids
+// (device, slot = 0), in slots ids[0..n).  yuyv_in: YUYV frames (only where prep_yuyv_fusable).  t: bsx_profile_batch's timer (launches only, no callbacks).
+int enqueue_masks(bsx_ctx* c, const uint8_t* d_frames, int n, hipStream_t s, bool yuyv_in, int slot, const int* ids, LaunchTimer* t = nullptr) {
+  if (const int rc = run_prep(c, d_frames, n, s, false, yuyv_in, t)) return rc;
+  if (c->onprep && !t) { BSX_HIP(c, hipStreamSynchronize(s)); c->onprep(c->caller_ctx); }   // :303
   const bool fused_decode = infer_decodes(c);
-  if ((rc = run_infer(c, n, s, !fused_decode, slot, ids))) return rc;
-  if (c->oninfer) { BSX_HIP(c, hipStreamSynchronize(s)); c->oninfer(c->caller_ctx); } // :311
-  if (!fused_decode && (rc = run_decode(c, n, s, slot, ids))) return rc;
+  if (const int rc = run_infer(c, n, s, !fused_decode, slot, ids, t)) return rc;
+  if (c->oninfer && !t) { BSX_HIP(c, hipStreamSynchronize(s)); c->oninfer(c->caller_ctx); } // :311
+  return fused_decode ? BSX_OK : run_decode(c, n, s, slot, ids, t);
+}
+// bs_maskgen_process: the masks of n frames into the persistent masks of their slots
+int process_impl(bsx_ctx* c, const uint8_t* d_frames, int n, int slot, hipStream_t s, bool yuyv_in = false, const int* ids = nullptr) {
+  if (const int rc = enqueue_masks(c, d_frames, n, s, yuyv_in, slot, ids)) return rc;
   if (c->onmask) { BSX_HIP(c, hipStreamSynchronize(s)); c->onmask(c->caller_ctx); }   // :363
   return run_mask(c, n, s, slot, ids);
 }
 
-}  // namespace
+// ---- the batch step: every step entry point builds a StepReq, check_step refuses it before anything is enqueued, run_step takes the routes route_of picks -----
 
-namespace {
+// A refused call: its own message (never one an earlier call left), built only here; nothing has been enqueued
+int refuse(bsx_ctx* c, const char* fn, const char* fmt, ...) {
+  char buf[256];
+  va_list ap;                                                     // (only here: messages are built only for a refused call)
+  va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
+  c->last_error = std::string("error: ") + fn + ": " + buf + "\n";
+  return BSX_EINVAL;
+}
+// every entry point that advances the temporal state refuses while the two-deep pipeline holds a composite that reads it
+int refuse_pending(bsx_ctx* c, const char* fn) {
+  return c->pend.active ? refuse(c, fn, "a pipelined composite is pending (flush with bsx_step_batch_pipelined(ctx, NULL, ...) first)") : BSX_OK;
+}
+
+// flags (bsx.h): BSX_STEP_YUYV (the composite leaves as YUYV 4:2:2), BSX_STEP_FLIP_H / _V (cv::flip of the composite), BSX_STEP_NO_MASK, BSX_STEP_YUYV_IN (the
+// camera's raw 4:2:2 frames instead of BGR), BSX_STEP_BGBLUR(ksize) (background = blur of the stream's own frame); all folded into the kernels where they apply
+struct StepReq {
+  const uint8_t* frames; const uint8_t* bg; size_t bg_stride; uint8_t* out;
+  int out_w, out_h, n;            // out_w x out_h: the capture size, except for bsx_step_batch_vcam
+  unsigned flags; hipStream_t s;
+  const int* ids;                 // bsx_step_batch_streams: the DEVICE copy of the stream ids (staged after the checks): frame i's state is slot ids[i]
+  bool yuyv() const { return (flags & BSX_STEP_YUYV) != 0; }
+  bool yin() const { return (flags & BSX_STEP_YUYV_IN) != 0; }
+  unsigned flip() const { return flags & (BSX_STEP_FLIP_H | BSX_STEP_FLIP_V); }
+  int bgblur() const { return (int)((flags >> 8) & 255u); }
+  bool resize(const bsx_ctx* c) const { return out_w != c->width || out_h != c->height; }
+  size_t out_bytes() const { return (size_t)n * out_w * out_h * (yuyv() ? 2 : 3); }
+  bool out_overlaps(const uint8_t* p, size_t bytes) const { return out < p + bytes && p < out + out_bytes(); }
+  bool overlap(const bsx_ctx* c) const { return out_overlaps(frames, (size_t)n * c->width * c->height * (yin() ? 2 : 3)); }
+};
+enum class Entry { Step, Streams, Vcam, Pipelined };
+
+// The fused tile kernel — mask up-scale + blur + blend [+ flip][+ YUYV pack] per tile, YUYV input converted on load — takes the request: no onmask callback
+// (the persistent masks are written by the same launch), the kernel's geometry and alignment, and no overlap it would read after writing
+bool tile_fusable(const bsx_ctx* c, const StepReq& r) {
+  return !c->onmask && !c->no_mask_blend_fusion && (!r.yuyv() || ((uintptr_t)r.out & 3) == 0) && !(r.overlap(c) && (r.yin() || r.yuyv() || r.flip())) &&
+         (!r.yin() || prep_yuyv_fusable(c->width, c->roi, c->tab_down.tab)) &&
+         mask_blend_fusable(c->width, c->height, c->roi, r.bg, r.bg_stride, r.frames, r.yuyv() ? r.frames : r.out);
+}
+
+// The rules of every step entry point, with their differences: the virtual camera refuses BSX_STEP_NO_MASK and any overlap, the pipeline refuses the blur, any
+// overlap and every geometry its fused kernel does not take; the plain step runs in place, and with a flip / YUYV flag on any overlap (through a scratch).
+int check_step(bsx_ctx* c, const char* fn, const StepReq& r, Entry kind) {
+  const bool vcam = kind == Entry::Vcam, pipe = kind == Entry::Pipelined, blur = r.bgblur() != 0;
+  if (!r.frames || (!r.bg && !blur) || !r.out || r.n <= 0 || r.n > c->n_streams) return refuse(c, fn, "null buffer or batch size out of range");
+  if ((r.flags & ~(pipe ? 31u : 31u | 0xFF00u)) || (vcam && (r.flags & BSX_STEP_NO_MASK)))
+    return refuse(c, fn, vcam ? "unsupported flags (the no-mask step has no vcam form)" : "unsupported flags 0x%x", r.flags);
+  if (blur && (r.bgblur() > 31 || !(r.bgblur() & 1))) return refuse(c, fn, "background blur size must be odd and <= 31");
+  if (vcam && (r.out_w <= 0 || r.out_h <= 0)) return refuse(c, fn, "output size must be positive");
+  if (blur && !vcam && r.frames == r.out) return refuse(c, fn, "the background blur cannot run in place");
+  if (!pipe) { if (const int rc = refuse_pending(c, fn)) return rc; }
+  if (r.yuyv() && (r.out_w & 1)) return refuse(c, fn, "YUYV output needs an even width");     // 4:2:2 pairs pixels horizontally
+  if (r.yin() && (c->width & 1)) return refuse(c, fn, "YUYV input needs an even capture width");
+  // vcam: each output pixel reads a neighbourhood of input pixels; pipeline: out(k) is written while frames(k + 1) are read
+  const bool overlap = r.overlap(c);
+  if (vcam && overlap) return refuse(c, fn, "output overlaps the frames");
+  if (vcam && !blur && r.out_overlaps(r.bg, r.bg_stride * (size_t)(r.n - 1) + (size_t)c->width * c->height * 3)) return refuse(c, fn, "output overlaps the background");
+  if (pipe && (overlap || c->onprep || c->oninfer || !tile_fusable(c, r)))
+    return refuse(c, fn, "needs the fused mask + blend geometry, no stage callbacks and non-overlapping buffers");
+  // Aliasing (bsx.h): the reference flips `raw` in place (app/deepseg.cc:667-673), so a caller following it passes d_out == d_frames.  A plain composite in place
+  // (same address read, then written, by the same lane) is fine; with a flip or YUYV flag the fused tile kernel would store to addresses another tile has not read
+  // yet, so those take the unfused sequence through the context's scratch (tile_fusable); YUYV input is converted into a scratch first.  Partial overlap is refused.
+  if (overlap && !r.yin() && !r.yuyv() && !r.flip() && r.out != r.frames) return refuse(c, fn, "output partially overlaps the frames");
+  return BSX_OK;
+}
+
+// YuyvToBgr: YUYV frames the fused kernels do not read (or the blur needs as BGR) into the BGR scratch, then the BGR form; BlurToScratch: the blurred frames
+// into a scratch background, then the step with it; BlurBlend: masks, then blur + blend in one pass; Tile: masks, then mask up-scale + blur + blend per tile in
+// ONE launch; Composite: masks, then the plain blend [into a scratch, + flip][+ YUYV pack]; Vcam: masks, then blend + flip + resize [+ pack] in one pass
+enum class Route { YuyvToBgr, BlurToScratch, BlurBlend, Tile, Composite, Vcam };
+Route route_of(const bsx_ctx* c, const StepReq& r) {
+  const bool resize = r.resize(c);
+  if (r.yin() && (r.bgblur() || !(resize ? prep_yuyv_fusable(c->width, c->roi, c->tab_down.tab) : tile_fusable(c, r)))) return Route::YuyvToBgr;
+  if (r.bgblur())
+    return !resize && !(r.flags & 15u) && !c->no_bgblur_fusion && gauss_blend_fusable(r.frames, c->d_masks, r.out, c->width, r.bgblur()) ? Route::BlurBlend
+                                                                                                                                       : Route::BlurToScratch;
+  if (resize) return Route::Vcam;
+  return tile_fusable(c, r) ? Route::Tile : Route::Composite;
+}
+
+// BSX_LANES: the context's batch buffers re-based to streams [f0, f0 + cap) inside the scope; the batch-major arena of the per-launch path becomes a compact one
+struct LaneView {
+  bsx_ctx* c; float* net_in; uint32_t* net_in_u8; float* net_out; float* arena; int n_streams;
+  LaneView(bsx_ctx* ctx, int f0, int cap) : c(ctx), net_in(ctx->d_net_in), net_in_u8(ctx->d_net_in_u8), net_out(ctx->d_net_out), arena(ctx->d_arena), n_streams(ctx->n_streams) {
+    c->d_net_in += (size_t)f0 * c->inW * c->inH * c->inC;
+    c->d_net_in_u8 += (size_t)f0 * c->inW * c->inH;
+    c->d_net_out += (size_t)f0 * c->outW * c->outH * c->outC;
+    c->d_arena += (size_t)f0 * c->plan.arena_floats_per_stream;
+    c->n_streams = cap;
+  }
+  ~LaneView() { c->d_net_in = net_in; c->d_net_in_u8 = net_in_u8; c->d_net_out = net_out; c->d_arena = arena; c->n_streams = n_streams; }
+};
+
+int run_tile(bsx_ctx* c, const StepReq& r) {
+  const size_t fb = (size_t)c->width * c->height * (r.yin() ? 2 : 3), ob = (size_t)c->width * c->height * (r.yuyv() ? 2 : 3), sm = (size_t)c->outW * c->outH;
+  // frames [f0, f0 + nb) on stream ls, their state in slots [f0, f0 + nb) or ids[f0 .. f0 + nb); per > 0: a lane, whose buffers are re-based (LaneView)
+  auto tile = [&](int f0, int nb, int per, hipStream_t ls) -> int {
+    const int st0 = r.ids ? 0 : f0, *lids = r.ids ? r.ids + f0 : nullptr;
+    int rc;
+    if (per) { LaneView view(c, f0, per); rc = enqueue_masks(c, r.frames + (size_t)f0 * fb, nb, ls, r.yin(), st0, lids); }
+    else rc = enqueue_masks(c, r.frames, nb, ls, r.yin(), 0, r.ids);
+    if (rc) return rc;
+    bsx_roctx::Range range("bsx:mask+blend");
+    BSX_HIP(c, launch_mask_blend(c->d_ofinal + (size_t)st0 * sm, c->outW, c->outH, c->in_roi, tab_up_at(c, f0), c->d_masks + (size_t)st0 * c->width * c->height, c->width,
+                                 c->height, c->roi, r.bg + (size_t)f0 * r.bg_stride, r.bg_stride, r.frames + (size_t)f0 * fb, r.out + (size_t)f0 * ob, nb, ls, (int)r.flags, 0, lids));
+    return BSX_OK;
+  };
+  // (the per-launch path's arena is batch-major: a lane's compact arena is laid out for `per` streams starting at stream f0, so the LAST lane ends at
+  //  K * per streams — lanes are only taken when that still fits the allocation, e.g. not for n = n_streams = 66, K = 4: 4 * 17 = 68)
+  const int n = r.n, K = c->lanes, per = (n + K - 1) / std::max(K, 1);
+  if (!(K > 1 && n >= 16 * K && !c->onprep && !c->oninfer && !c->keep_logits && (c->use_program || K * per <= c->n_streams))) return tile(0, n, 0, r.s);
+  BSX_HIP(c, hipEventRecord(c->ev_fork, r.s));
+  int lane_rc = BSX_OK;
+  for (int k = 0; k < K && lane_rc == BSX_OK; k++) {
+    const int f0 = k * per, nb = std::min(per, n - f0);
+    if (nb <= 0) break;
+    hipStream_t ls = k == 0 ? r.s : c->lane_stream[k];
+    if (k > 0 && hipStreamWaitEvent(ls, c->ev_fork, 0) != hipSuccess) { lane_rc = BSX_EDEVICE; break; }
+    lane_rc = tile(f0, nb, per, ls);
+    // forked lanes are ALWAYS joined, also after an error: the caller's stream must not be left with work in flight on streams it cannot see
+    if (k > 0 && (hipEventRecord(c->ev_join[k], ls) != hipSuccess || hipStreamWaitEvent(r.s, c->ev_join[k], 0) != hipSuccess)) lane_rc = lane_rc ? lane_rc : BSX_EDEVICE;
+  }
+  if (lane_rc == BSX_EDEVICE && c->last_error.empty()) c->last_error = "error: HIP failure while enqueuing a lane of the step\n";
+  return lane_rc;
+}
+
+// the unfused geometry: the composite with the persistent masks of the batch's slots, into a context-owned BGR scratch when a flip and / or a pack follows
+int run_composite(bsx_ctx* c, const StepReq& r) {
+  if (const int rc = process_impl(c, r.frames, r.n, 0, r.s, false, r.ids)) return rc;
+  const size_t px = (size_t)c->width * c->height, need = (size_t)c->n_streams * px * 3;
+  if ((r.yuyv() || r.flip()) && !c->d_bgr_scratch) BSX_HIP(c, hipMalloc(&c->d_bgr_scratch, need));
+  uint8_t* dst = (r.yuyv() || r.flip()) ? c->d_bgr_scratch : r.out;
+  { bsx_roctx::Range range("bsx:blend"); BSX_HIP(c, launch_blend(r.bg, r.bg_stride, r.frames, c->d_masks, dst, px, r.n, r.s, r.ids)); }
+  const uint8_t* bgr = dst;
+  if (r.flip()) {
+    const int code = r.flip() == (BSX_STEP_FLIP_H | BSX_STEP_FLIP_V) ? -1 : (r.flip() == BSX_STEP_FLIP_H ? 1 : 0);
+    uint8_t* fdst = r.out;
+    if (r.yuyv()) { if (!c->d_bgr_scratch2) BSX_HIP(c, hipMalloc(&c->d_bgr_scratch2, need)); fdst = c->d_bgr_scratch2; }
+    BSX_HIP(c, launch_flip_bgr(bgr, fdst, c->width, c->height, code, r.n, r.s));
+    bgr = fdst;
+  }
+  if (r.yuyv()) BSX_HIP(c, launch_bgr_to_yuyv(bgr, r.out, c->width, c->height, r.n, r.s));
+  return BSX_OK;
+}
+
+// the capture -> (out_w, out_h) table of bsx_step_batch_vcam, built once per output size
+int vcam_tab(bsx_ctx* c, int out_w, int out_h, const VcamTab** out) {
+  auto key = std::make_pair(out_w, out_h);
+  auto it = c->vcam_tabs.find(key);
+  if (it == c->vcam_tabs.end()) {
+    HostResizeTab h = make_resize_tab(c->width, c->height, out_w, out_h);
+    if (h.mode == 2) {              // the 2x2 area mean as a linear table: taps 2d and 2d + 1, coefficients 1024 / 1024 (the same integers: kernels_img.hip)
+      h.mode = 0;
+      h.xofs.resize(out_w); h.xa.assign(2 * (size_t)out_w, 1024); h.yofs.resize(out_h); h.ya.assign(2 * (size_t)out_h, 1024);
+      for (int d = 0; d < out_w; d++) h.xofs[d] = 2 * d;
+      for (int d = 0; d < out_h; d++) h.yofs[d] = 2 * d;
+    }
+    VcamTab v;
+    v.direct = !vcam_tile_fits(h.xofs.data(), h.yofs.data(), h.sw, h.sh, h.dw, h.dh);
+    int rc = upload_tab(c, h, &v.d);
+    if (rc) { if (v.d.mem) (void)hipFree(v.d.mem); return rc; }
+    it = c->vcam_tabs.emplace(key, v).first;
+  }
+  *out = &it->second;
+  return BSX_OK;
+}
+
+// a checked request, on the context's device: its route, until the batch is composited (the scratch conversions rewrite the request and decide again)
+int run_step(bsx_ctx* c, StepReq r) {
+  const size_t px = (size_t)c->width * c->height;
+  const VcamTab* vt = nullptr;
+  if (r.resize(c)) { if (const int rc = vcam_tab(c, r.out_w, r.out_h, &vt)) return rc; }
+  for (;;) {
+    switch (route_of(c, r)) {
+      case Route::YuyvToBgr:
+        if (!c->d_bgr_in_scratch) BSX_HIP(c, hipMalloc(&c->d_bgr_in_scratch, (size_t)c->n_streams * px * 3));
+        BSX_HIP(c, launch_yuyv_to_bgr(r.frames, c->d_bgr_in_scratch, c->width, c->height, r.n, r.s));
+        r.frames = c->d_bgr_in_scratch; r.flags &= ~BSX_STEP_YUYV_IN;
+        continue;
+      case Route::BlurToScratch:
+        if (!c->d_bgblur_scratch) BSX_HIP(c, hipMalloc(&c->d_bgblur_scratch, (size_t)c->n_streams * px * 3));
+        BSX_HIP(c, launch_gauss_blur(r.frames, c->d_bgblur_scratch, c->width, c->height, r.bgblur(), r.n, r.s));
+        r.bg = c->d_bgblur_scratch; r.bg_stride = px * 3; r.flags &= ~0xFF00u;
+        continue;
+      case Route::BlurBlend:
+        if (const int rc = process_impl(c, r.frames, r.n, 0, r.s, false, r.ids)) return rc;
+        BSX_HIP(c, launch_gauss_blend(r.frames, c->d_masks, r.out, c->width, c->height, r.bgblur(), r.n, r.s, r.ids));
+        return BSX_OK;
+      case Route::Tile: return run_tile(c, r);
+      case Route::Composite: return run_composite(c, r);
+      case Route::Vcam: {
+        if (const int rc = process_impl(c, r.frames, r.n, 0, r.s, r.yin())) return rc;
+        bsx_roctx::Range range("bsx:vcam");
+        BSX_HIP(c, launch_vcam_blend_resize(r.frames, r.yin(), r.bg, r.bg_stride, c->d_masks, r.out, c->width, c->height, vt->d.tab, vt->direct || c->vcam_direct, r.n,
+                                            r.s, r.flags & 7u));
+        return BSX_OK;
+      }
+    }
+  }
+}
+
+// ---- a chosen subset of the context's streams, addressed by stream id (bsx.h): frame i of the call belongs to stream ids[i].  The kernels that read or write
+// per-stream state take the ids as a device array (slot_of) and address that state in place; everything else stays indexed by position.
+
+// host-side validation of ids[0..n): nothing is enqueued before it passes
+int ids_check(bsx_ctx* c, const char* fn, const int* ids, int n) {
+  if (n < 0) return refuse(c, fn, "n = %d is negative", n);
+  if (n > c->n_streams) return refuse(c, fn, "n = %d exceeds the context's %d streams", n, c->n_streams);
+  if (n > 0 && !ids) return refuse(c, fn, "ids is NULL");
+  if (c->ids_seen.size() != (size_t)c->n_streams) c->ids_seen.assign((size_t)c->n_streams, -1);
+  int rc = BSX_OK, i = 0;
+  for (; i < n; i++) {
+    const int v = ids[i];
+    if (v < 0 || v >= c->n_streams) { rc = refuse(c, fn, "ids[%d] = %d is out of range [0, %d)", i, v, c->n_streams); break; }
+    if (c->ids_seen[v] >= 0) { rc = refuse(c, fn, "ids[%d] = %d repeats ids[%d]", i, v, c->ids_seen[v]); break; }
+    c->ids_seen[v] = i;
+  }
+  for (int j = 0; j < i; j++) c->ids_seen[ids[j]] = -1;
+  return rc;
+}
+// ids[0..n) → the next entry of the pinned ring → the same entry of the device ring, on s (bsx_ctx::kIdRing); ids_release guards the entry behind the call
+int ids_stage(bsx_ctx* c, const int* ids, int n, hipStream_t s, const int** d_ids, int* entry) {
+  const size_t N = (size_t)c->n_streams;
+  if (!c->h_ids) BSX_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_ids), bsx_ctx::kIdRing * N * sizeof(int), hipHostMallocDefault));
+  if (!c->d_ids) BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_ids), bsx_ctx::kIdRing * N * sizeof(int)));
+  for (hipEvent_t& e : c->ev_ids) if (!e) BSX_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  const int k = c->ids_next;
+  if (c->ids_used[k]) {
+    hipError_t e;
+    while ((e = hipEventQuery(c->ev_ids[k])) == hipErrorNotReady) std::this_thread::yield();
+    BSX_HIP(c, e);
+  }
+  memcpy(c->h_ids + (size_t)k * N, ids, (size_t)n * sizeof(int));
+  BSX_HIP(c, hipMemcpyAsync(c->d_ids + (size_t)k * N, c->h_ids + (size_t)k * N, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+  c->ids_next = (k + 1) % bsx_ctx::kIdRing;
+  *d_ids = c->d_ids + (size_t)k * N;
+  *entry = k;
+  return BSX_OK;
+}
+// the ring entry is free again once everything enqueued on s so far has run (recorded also after a failed call: whatever it enqueued may read the entry)
+int ids_release(bsx_ctx* c, int entry, hipStream_t s, int rc) {
+  c->ids_used[entry] = true;
+  const hipError_t e = hipEventRecord(c->ev_ids[entry], s);
+  if (rc == BSX_OK && e != hipSuccess) BSX_HIP(c, e);
+  return rc;
+}
+
+// a step entry point: the request checked (ids included) before anything is enqueued, then on the context's device [the ids staged] and run
+int step_call(bsx_ctx* c, const char* fn, Entry kind, StepReq r, const int* host_ids = nullptr) {
+  if (!c) return BSX_EINVAL;
+  if (kind != Entry::Vcam) { r.out_w = c->width; r.out_h = c->height; }
+  if (kind == Entry::Streams) {
+    if (const int rc = ids_check(c, fn, host_ids, r.n)) return rc;
+    if (r.n == 0) return refuse_pending(c, fn);                   // (check_step refuses a pending composite for n > 0)
+  }
+  if (const int rc = check_step(c, fn, r, kind)) return rc;
+  DeviceGuard guard(c->device);
+  if (kind != Entry::Streams) return run_step(c, r);
+  int entry = 0;
+  if (const int rc = ids_stage(c, host_ids, r.n, r.s, &r.ids, &entry)) return rc;
+  return ids_release(c, entry, r.s, run_step(c, r));
+}
+
+// ---- two-deep pipeline: mask pipeline of batch k  ||  composite of batch k - 1 ------------------------------------------------------------------
+// The composite (HBM-bound) of the batch handed over by the previous call goes to comp_stream, the mask pipeline (latency-bound) of this call's batch to the
+// caller's stream (the reference's CalcMask worker next to its blend loop, app/deepseg.cc:182-216, 634-681); the only shared object, the model-resolution
+// temporal state, is protected by ev_pcomp in front of the launch that advances it.  Every frame is composited with ITS OWN mask (bsx.h).
+
+int pipelined_objects(bsx_ctx* c) {
+  if (c->comp_stream) return BSX_OK;
+  // the composite fills the gaps of the network kernels, not the other way round: lowest priority the device offers (BSX_PIPE_PRIO=0: default priority)
+  int lo = 0, hi = 0;
+  const char* pe = BSX_DBG_ENV("BSX_PIPE_PRIO");
+  if (!(pe && atoi(pe) == 0) && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi) BSX_HIP(c, hipStreamCreateWithPriority(&c->comp_stream, hipStreamNonBlocking, lo));
+  else BSX_HIP(c, hipStreamCreateWithFlags(&c->comp_stream, hipStreamNonBlocking));
+  BSX_HIP(c, hipEventCreateWithFlags(&c->ev_pdone, hipEventDisableTiming));
+  BSX_HIP(c, hipEventCreateWithFlags(&c->ev_pcomp, hipEventDisableTiming));
+  return BSX_OK;
+}
+int composite_pending(bsx_ctx* c, hipStream_t s, bool concurrent) {
+  const bsx_ctx::PendingComposite& p = c->pend;
+  // next to the network kernels the composite holds at most pipe_wgs workgroups per CU (an unused LDS pad: static 16.7 KB + pad <= 64 KB, i.e. >= 2 per CU)
+  int pad = 0;
+  if (concurrent && c->pipe_wgs > 0) pad = std::max(0, std::min(47 * 1024, (160 * 1024 / c->pipe_wgs - 17 * 1024) & ~255));
+  bsx_roctx::Range range("bsx:mask+blend");
+  BSX_HIP(c, launch_mask_blend(c->d_ofinal, c->outW, c->outH, c->in_roi, c->tab_up.tab, c->d_masks, c->width, c->height, c->roi, p.bg, p.bg_stride, p.frames, p.out, p.n, s,
+                               (int)p.flags, pad));
+  return BSX_OK;
+}
+
 // workgroup barriers one launch of the specialised middle kernel executes per frame: one in front of every micro-op, the ones inside squeeze-excite ops (pool | FC | FC)
 // and between the channel chunks of staged depthwise ops — counted in the generated source itself (gen_mid.cpp), so the line cannot drift from the kernel
 std::string mid_barrier_line(const Plan& p, bool act16) {
@@ -710,11 +1001,10 @@ uint8_t* bsx_masks_device(bsx_ctx* c) { return c ? c->d_masks : nullptr; }
 
 int bsx_process_batch(bsx_ctx* c, const uint8_t* d_frames, int n, uint8_t* d_masks, void* stream) {
   if (!c || !d_frames || n <= 0 || n > c->n_streams) return BSX_EINVAL;
-  if (c->pend.active) { c->last_error = "error: a pipelined composite is pending (flush with bsx_step_batch_pipelined(ctx, NULL, ...) first)\n"; return BSX_EINVAL; }
+  if (const int rc = refuse_pending(c, "bsx_process_batch")) return rc;
   DeviceGuard guard(c->device);
   hipStream_t s = pick(c, stream);
-  int rc;
-  if ((rc = process_impl(c, d_frames, n, 0, s))) return rc;
+  if (const int rc = process_impl(c, d_frames, n, 0, s)) return rc;
   if (d_masks) BSX_HIP(c, hipMemcpyAsync(d_masks, c->d_masks, (size_t)n * c->width * c->height, hipMemcpyDeviceToDevice, s));
   return BSX_OK;
 }
@@ -722,7 +1012,7 @@ int bsx_process_batch(bsx_ctx* c, const uint8_t* d_frames, int n, uint8_t* d_mas
 int bsx_process_host(bsx_ctx* c, int stream_idx, const uint8_t* h_bgr, size_t bgr_stride, uint8_t* h_mask, size_t mask_stride) {
   if (!c || !h_bgr || !h_mask || stream_idx < 0 || stream_idx >= c->n_streams) return BSX_EINVAL;
   if (bgr_stride < (size_t)c->width * 3 || mask_stride < (size_t)c->width) return BSX_ESIZE;
-  if (c->pend.active) { c->last_error = "error: a pipelined composite is pending (flush with bsx_step_batch_pipelined(ctx, NULL, ...) first)\n"; return BSX_EINVAL; }
+  if (const int rc = refuse_pending(c, "bsx_process_host")) return rc;
   DeviceGuard guard(c->device);
   hipStream_t s = c->own_stream;
   const size_t fbytes = (size_t)c->width * c->height * 3;
@@ -766,243 +1056,25 @@ int bsx_composite_batch(bsx_ctx* c, const uint8_t* d_bg, size_t bg_frame_stride,
   return BSX_OK;
 }
 
-namespace {
-// The context's batch buffers re-based to streams [f0, f0 + cap) for the launches enqueued inside the scope (one host thread enqueues a context's work).
-// Frame-major buffers simply start at stream f0; the batch-major arena of the per-launch path becomes the group's own compact arena laid out for `cap` streams.
-struct LaneView {
-  bsx_ctx* c; float* net_in; uint32_t* net_in_u8; float* net_out; float* arena; int n_streams;
-  LaneView(bsx_ctx* ctx, int f0, int cap) : c(ctx), net_in(ctx->d_net_in), net_in_u8(ctx->d_net_in_u8), net_out(ctx->d_net_out), arena(ctx->d_arena),
-                                            n_streams(ctx->n_streams) {
-    c->d_net_in += (size_t)f0 * c->inW * c->inH * c->inC;
-    c->d_net_in_u8 += (size_t)f0 * c->inW * c->inH;
-    c->d_net_out += (size_t)f0 * c->outW * c->outH * c->outC;
-    c->d_arena += (size_t)f0 * c->plan.arena_floats_per_stream;
-    c->n_streams = cap;
-  }
-  ~LaneView() { c->d_net_in = net_in; c->d_net_in_u8 = net_in_u8; c->d_net_out = net_out; c->d_arena = arena; c->n_streams = n_streams; }
-};
-
-// flags (bsx.h): BSX_STEP_YUYV — the composite leaves as YUYV 4:2:2 (2 B/px), convert_rgb_to_yuyv (deepseg.cc:87-106) applied in the blend's epilogue;
-// BSX_STEP_FLIP_H / _V — cv::flip of the composite (deepseg.cc:667-673) folded into the epilogue's store addresses
-// the argument checks of step_impl that need nothing enqueued (bsx_step_batch_streams runs them before it stages its ids)
-int step_args(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, uint8_t* d_out, int n, unsigned flags) {
-  const int bgblur = (int)((flags >> 8) & 255u);
-  if (!c || !d_frames || (!d_bg && !bgblur) || !d_out || n <= 0 || n > c->n_streams || (flags & ~(31u | 0xFF00u))) return BSX_EINVAL;
-  if (bgblur && (bgblur > 31 || !(bgblur & 1) || d_frames == d_out)) return BSX_EINVAL;
-  if (c->pend.active) { c->last_error = "error: a pipelined composite is pending (flush with bsx_step_batch_pipelined(ctx, NULL, ...) first)\n"; return BSX_EINVAL; }
-  if ((flags & (BSX_STEP_YUYV | BSX_STEP_YUYV_IN)) && (c->width & 1)) return BSX_EINVAL;       // 4:2:2 pairs pixels horizontally
-  return BSX_OK;
-}
-// ids (device, nullable): bsx_step_batch_streams — frame i's temporal state and persistent mask are slot ids[i]; everything else stays indexed by position i
-int step_impl(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_frame_stride, uint8_t* d_out, int n, void* stream, unsigned flags,
-              const int* ids = nullptr) {
-  const int bgblur = (int)((flags >> 8) & 255u);                // BSX_STEP_BGBLUR(ksize): background = blur of the stream's own frame, d_bg unused
-  if (const int arc = step_args(c, d_frames, d_bg, d_out, n, flags)) return arc;
-  const int yuyv = (int)(flags & BSX_STEP_YUYV);
-  const bool yin = (flags & BSX_STEP_YUYV_IN) != 0;             // the camera's raw 4:2:2 frames (cv::COLOR_YUV2BGR_YUYV, app/deepseg.cc:553,725) instead of BGR
-  const unsigned flip = flags & (BSX_STEP_FLIP_H | BSX_STEP_FLIP_V);
-  DeviceGuard guard(c->device);
-  const size_t px_frame = (size_t)c->width * c->height;
-  if (yin) {
-    // fused form: prep_fused_k and the mask tile kernel convert the pixels they read (2 B/px from HBM, no BGR frame in between).  Everything the fused kernels do
-    // not cover — a background blurred from the frame itself, a geometry the tile kernel or the 8-byte tap window does not take, buffers that overlap, stage
-    // callbacks — converts the batch into a context-owned BGR scratch first (bsx_yuyv_to_bgr's kernel) and runs the BGR step on it: same bytes, one more pass.
-    const size_t in_b = (size_t)n * px_frame * 2, out_b = (size_t)n * px_frame * (yuyv ? 2 : 3);
-    const bool ovl = d_out < d_frames + in_b && d_frames < d_out + out_b;
-    const bool direct = !bgblur && !ovl && !c->onmask && !c->no_mask_blend_fusion && (!yuyv || ((uintptr_t)d_out & 3) == 0) && prep_yuyv_fusable(c->width, c->roi, c->tab_down.tab) &&
-                        mask_blend_fusable(c->width, c->height, c->roi, d_bg, bg_frame_stride, d_frames, yuyv ? d_frames : d_out);
-    if (!direct) {
-      if (!c->d_bgr_in_scratch) BSX_HIP(c, hipMalloc(&c->d_bgr_in_scratch, (size_t)c->n_streams * px_frame * 3));
-      BSX_HIP(c, launch_yuyv_to_bgr(d_frames, c->d_bgr_in_scratch, c->width, c->height, n, pick(c, stream)));
-      return step_impl(c, c->d_bgr_in_scratch, d_bg, bg_frame_stride, d_out, n, stream, flags & ~BSX_STEP_YUYV_IN, ids);
-    }
-  }
-  if (bgblur) {
-    if (!(flags & 15u) && !c->no_bgblur_fusion && gauss_blend_fusable(d_frames, c->d_masks, d_out, c->width, bgblur)) {
-      // masks as usual (prep → network → decode → upscale + blur), then ONE pass over the frames: blur tile → blend with the frame and the mask → composite
-      int rc = ids ? process_impl(c, d_frames, n, 0, pick(c, stream), false, ids) : bsx_process_batch(c, d_frames, n, nullptr, stream);
-      if (rc) return rc;
-      BSX_HIP(c, launch_gauss_blend(d_frames, c->d_masks, d_out, c->width, c->height, bgblur, n, pick(c, stream), ids));
-      return BSX_OK;
-    }
-    const size_t fb = (size_t)c->width * c->height * 3;
-    if (!c->d_bgblur_scratch) BSX_HIP(c, hipMalloc(&c->d_bgblur_scratch, (size_t)c->n_streams * fb));
-    BSX_HIP(c, launch_gauss_blur(d_frames, c->d_bgblur_scratch, c->width, c->height, bgblur, n, pick(c, stream)));
-    return step_impl(c, d_frames, c->d_bgblur_scratch, fb, d_out, n, stream, flags & 15u, ids);
-  }
-  // Aliasing (bsx.h): the reference flips `raw` in place (app/deepseg.cc:667-673), so a caller following it passes d_out == d_frames.  The fused tile kernel reads a
-  // frame pixel at (x, y) and stores the flipped (or YUYV-packed: 2 B/px) result at ANOTHER address, which a different tile may not have read yet — with overlapping
-  // buffers those forms take the unfused sequence (composite into the context's scratch first).  A plain composite in place (same address read, then written, by the
-  // same lane) is fine; partially overlapping buffers are refused.
-  const size_t in_bytes = (size_t)n * c->width * c->height * (yin ? 2 : 3), out_bytes = (size_t)n * c->width * c->height * (yuyv ? 2 : 3);
-  const bool overlap = d_out < d_frames + in_bytes && d_frames < d_out + out_bytes;      // (never with yin: overlapping YUYV input took the scratch route above)
-  if (overlap && !yuyv && !flip && d_out != d_frames) return BSX_EINVAL;
-  const bool fuse = !c->onmask && !c->no_mask_blend_fusion && (!yuyv || ((uintptr_t)d_out & 3) == 0) && !(overlap && (yuyv || flip)) &&
-                    mask_blend_fusable(c->width, c->height, c->roi, d_bg, bg_frame_stride, d_frames, yuyv ? d_frames : d_out);
-  if (!fuse) {
-    if (yin) return BSX_EINVAL;                                   // unreachable: `direct` above implies `fuse`
-    int rc = ids ? process_impl(c, d_frames, n, 0, pick(c, stream), false, ids) : bsx_process_batch(c, d_frames, n, nullptr, stream);
-    if (rc) return rc;
-    // the composite with the persistent masks of the batch's slots (bsx_composite_batch's blend; with ids the masks are read by stream id)
-    auto composite = [&](uint8_t* dst) -> int {
-      if (!ids) return bsx_composite_batch(c, d_bg, bg_frame_stride, d_frames, nullptr, dst, n, stream);
-      bsx_roctx::Range range("bsx:blend");
-      BSX_HIP(c, launch_blend(d_bg, bg_frame_stride, d_frames, c->d_masks, dst, (size_t)c->width * c->height, n, pick(c, stream), ids));
-      return BSX_OK;
-    };
-    if (!yuyv && !flip) return composite(d_out);
-    // unfused geometry: composite into a context-owned BGR scratch, then flip and / or pack as separate passes
-    const size_t need = (size_t)c->n_streams * c->width * c->height * 3;
-    if (!c->d_bgr_scratch) BSX_HIP(c, hipMalloc(&c->d_bgr_scratch, need));
-    rc = composite(c->d_bgr_scratch);
-    if (rc) return rc;
-    const uint8_t* bgr = c->d_bgr_scratch;
-    if (flip) {
-      const int code = flip == (BSX_STEP_FLIP_H | BSX_STEP_FLIP_V) ? -1 : (flip == BSX_STEP_FLIP_H ? 1 : 0);
-      uint8_t* dst = d_out;
-      if (yuyv) { if (!c->d_bgr_scratch2) BSX_HIP(c, hipMalloc(&c->d_bgr_scratch2, need)); dst = c->d_bgr_scratch2; }
-      if ((rc = bsx_flip_bgr(c, bgr, dst, c->width, c->height, n, code, stream))) return rc;
-      bgr = dst;
-    }
-    return yuyv ? bsx_bgr_to_yuyv(c, bgr, d_out, c->width, c->height, n, stream) : BSX_OK;
-  }
-  // process (prep → network → decode), then mask-upscale+blur and alpha blend of each tile in ONE launch
-  hipStream_t s = pick(c, stream);
-  int rc;
-  // (the per-launch path's arena is batch-major: a lane's compact arena is laid out for `per` streams starting at stream f0, so the LAST lane ends at
-  //  K * per streams — lanes are only taken when that still fits the allocation, e.g. not for n = n_streams = 66, K = 4: 4 * 17 = 68)
-  const int lane_per = (n + c->lanes - 1) / std::max(c->lanes, 1);
-  if (c->lanes > 1 && n >= 16 * c->lanes && !c->onprep && !c->oninfer && !c->keep_logits && (c->use_program || c->lanes * lane_per <= c->n_streams)) {
-    const int K = c->lanes, per = lane_per;
-    const bool fd = infer_decodes(c);
-    const size_t fb = (size_t)c->width * c->height * (yin ? 2 : 3), ob = (size_t)c->width * c->height * (yuyv ? 2 : 3), sm = (size_t)c->outW * c->outH;
-    BSX_HIP(c, hipEventRecord(c->ev_fork, s));
-    int lane_rc = BSX_OK;
-    for (int k = 0; k < K && lane_rc == BSX_OK; k++) {
-      const int f0 = k * per, nb = std::min(per, n - f0);
-      if (nb <= 0) break;
-      hipStream_t ls = k == 0 ? s : c->lane_stream[k];
-      if (k > 0 && hipStreamWaitEvent(ls, c->ev_fork, 0) != hipSuccess) { lane_rc = BSX_EDEVICE; break; }
-      const int st0 = ids ? 0 : f0;                               // the lane's state: slots [f0, f0 + nb), or slots ids[f0 .. f0 + nb)
-      const int* lids = ids ? ids + f0 : nullptr;
-      {
-        LaneView view(c, f0, per);
-        lane_rc = run_prep(c, d_frames + (size_t)f0 * fb, nb, ls, false, yin);
-        if (!lane_rc) lane_rc = run_infer(c, nb, ls, !fd, st0, lids);
-        if (!lane_rc && !fd) lane_rc = run_decode(c, nb, ls, st0, lids);
-      }
-      if (!lane_rc && launch_mask_blend(c->d_ofinal + (size_t)st0 * sm, c->outW, c->outH, c->in_roi, tab_up_at(c, f0), c->d_masks + (size_t)st0 * c->width * c->height, c->width, c->height,
-                                        c->roi, d_bg + (size_t)f0 * bg_frame_stride, bg_frame_stride, d_frames + (size_t)f0 * fb, d_out + (size_t)f0 * ob, nb, ls, (int)flags, 0,
-                                        lids) != hipSuccess)
-        lane_rc = BSX_EDEVICE;
-      // forked lanes are ALWAYS joined, also after an error: the caller's stream must not be left with work in flight on streams it cannot see
-      if (k > 0 && (hipEventRecord(c->ev_join[k], ls) != hipSuccess || hipStreamWaitEvent(s, c->ev_join[k], 0) != hipSuccess)) lane_rc = lane_rc ? lane_rc : BSX_EDEVICE;
-    }
-    if (lane_rc == BSX_EDEVICE && c->last_error.empty()) c->last_error = "error: HIP failure while enqueuing a lane of the step\n";
-    return lane_rc;
-  }
-  if ((rc = run_prep(c, d_frames, n, s, false, yin))) return rc;
-  if (c->onprep) { BSX_HIP(c, hipStreamSynchronize(s)); c->onprep(c->caller_ctx); }
-  const bool fused_decode = infer_decodes(c);
-  if ((rc = run_infer(c, n, s, !fused_decode, 0, ids))) return rc;
-  if (c->oninfer) { BSX_HIP(c, hipStreamSynchronize(s)); c->oninfer(c->caller_ctx); }
-  if (!fused_decode && (rc = run_decode(c, n, s, 0, ids))) return rc;
-  bsx_roctx::Range range("bsx:mask+blend");
-  BSX_HIP(c, launch_mask_blend(c->d_ofinal, c->outW, c->outH, c->in_roi, c->tab_up.tab, c->d_masks, c->width, c->height, c->roi, d_bg,
-                               bg_frame_stride, d_frames, d_out, n, s, (int)flags, 0, ids));
-  return BSX_OK;
-}
-}  // namespace
-
 int bsx_step_batch(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_frame_stride, uint8_t* d_out, int n, void* stream) {
-  return step_impl(c, d_frames, d_bg, bg_frame_stride, d_out, n, stream, 0u);
+  return step_call(c, "bsx_step_batch", Entry::Step, StepReq{d_frames, d_bg, bg_frame_stride, d_out, 0, 0, n, 0u, (hipStream_t)stream, nullptr});
 }
 int bsx_step_batch_yuyv(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_frame_stride, uint8_t* d_out_yuyv, int n, void* stream) {
-  return step_impl(c, d_frames, d_bg, bg_frame_stride, d_out_yuyv, n, stream, BSX_STEP_YUYV);
+  return step_call(c, "bsx_step_batch_yuyv", Entry::Step, StepReq{d_frames, d_bg, bg_frame_stride, d_out_yuyv, 0, 0, n, BSX_STEP_YUYV, (hipStream_t)stream, nullptr});
 }
 int bsx_step_batch_ex(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_frame_stride, uint8_t* d_out, int n, void* stream, unsigned flags) {
-  return step_impl(c, d_frames, d_bg, bg_frame_stride, d_out, n, stream, flags);
+  return step_call(c, "bsx_step_batch_ex", Entry::Step, StepReq{d_frames, d_bg, bg_frame_stride, d_out, 0, 0, n, flags, (hipStream_t)stream, nullptr});
 }
-
-// ---- a chosen subset of the context's streams, addressed by stream id ------------------------------------------------------------------------------------
-// The reference processes each camera frame once (CalcMask::run waits for a NEW frame, app/deepseg.cc:182-216; the temporal filter advances once per call,
-// lib/libbackscrub.cc:315-356).  Cameras deliver at their own rates and come and go, so a tick of a server has new frames for SOME streams, not for streams
-// 0 .. n-1: frame i of the call belongs to stream ids[i].  The kernels that read or write per-stream state take the ids as a device array (slot_of) and address
-// that state in place — no gather / scatter of state; everything else (frames, backgrounds, outputs, activations, tile classes) stays indexed by position.
-namespace {
-int ids_einval(bsx_ctx* c, const char* fn, const std::string& why) {
-  c->last_error = std::string("error: ") + fn + ": " + why + "\n";
-  return BSX_EINVAL;
-}
-// host-side validation of ids[0..n): nothing is enqueued before it passes
-int ids_check(bsx_ctx* c, const char* fn, const int* ids, int n) {
-  if (n < 0) return ids_einval(c, fn, "n = " + std::to_string(n) + " is negative");
-  if (n > c->n_streams) return ids_einval(c, fn, "n = " + std::to_string(n) + " exceeds the context's " + std::to_string(c->n_streams) + " streams");
-  if (n > 0 && !ids) return ids_einval(c, fn, "ids is NULL");
-  if (c->pend.active) { c->last_error = "error: a pipelined composite is pending (flush with bsx_step_batch_pipelined(ctx, NULL, ...) first)\n"; return BSX_EINVAL; }
-  if (c->ids_seen.size() != (size_t)c->n_streams) c->ids_seen.assign((size_t)c->n_streams, -1);
-  int rc = BSX_OK, i = 0;
-  for (; i < n; i++) {
-    const int v = ids[i];
-    if (v < 0 || v >= c->n_streams) {
-      rc = ids_einval(c, fn, "ids[" + std::to_string(i) + "] = " + std::to_string(v) + " is out of range [0, " + std::to_string(c->n_streams) + ")");
-      break;
-    }
-    if (c->ids_seen[v] >= 0) {
-      rc = ids_einval(c, fn, "ids[" + std::to_string(i) + "] = " + std::to_string(v) + " repeats ids[" + std::to_string(c->ids_seen[v]) + "]");
-      break;
-    }
-    c->ids_seen[v] = i;
-  }
-  for (int j = 0; j < i; j++) c->ids_seen[ids[j]] = -1;
-  return rc;
-}
-// ids[0..n) → the next entry of the context's pinned ring → the same entry of the device ring, on stream s.  *entry: record ev_ids[*entry] on s behind the last
-// launch that reads the device array (ids_release).  The host waits only when the entry's previous use has not completed yet (kIdRing calls ahead of the GPU).
-int ids_stage(bsx_ctx* c, const int* ids, int n, hipStream_t s, const int** d_ids, int* entry) {
-  const size_t N = (size_t)c->n_streams;
-  if (!c->h_ids) BSX_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_ids), bsx_ctx::kIdRing * N * sizeof(int), hipHostMallocDefault));
-  if (!c->d_ids) BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_ids), bsx_ctx::kIdRing * N * sizeof(int)));
-  for (hipEvent_t& e : c->ev_ids) if (!e) BSX_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  const int k = c->ids_next;
-  if (c->ids_used[k]) {
-    hipError_t e;
-    while ((e = hipEventQuery(c->ev_ids[k])) == hipErrorNotReady) std::this_thread::yield();
-    BSX_HIP(c, e);
-  }
-  memcpy(c->h_ids + (size_t)k * N, ids, (size_t)n * sizeof(int));
-  BSX_HIP(c, hipMemcpyAsync(c->d_ids + (size_t)k * N, c->h_ids + (size_t)k * N, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
-  c->ids_next = (k + 1) % bsx_ctx::kIdRing;
-  *d_ids = c->d_ids + (size_t)k * N;
-  *entry = k;
-  return BSX_OK;
-}
-// the ring entry is free again once everything enqueued on s so far has run (recorded also after a failed call: whatever it enqueued may read the entry)
-int ids_release(bsx_ctx* c, int entry, hipStream_t s, int rc) {
-  c->ids_used[entry] = true;
-  const hipError_t e = hipEventRecord(c->ev_ids[entry], s);
-  if (rc == BSX_OK && e != hipSuccess) BSX_HIP(c, e);
-  return rc;
-}
-}  // namespace
-
+// ids (host): frame i's temporal state and persistent mask are slot ids[i]; everything else stays indexed by position i
 int bsx_step_batch_streams(bsx_ctx* c, const int* ids, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_frame_stride, uint8_t* d_out, int n, void* stream,
                            unsigned flags) {
-  if (!c) return BSX_EINVAL;
-  if (const int rc = ids_check(c, "bsx_step_batch_streams", ids, n)) return rc;
-  if (n == 0) return BSX_OK;
-  if (const int rc = step_args(c, d_frames, d_bg, d_out, n, flags)) return rc;
-  DeviceGuard guard(c->device);
-  hipStream_t s = pick(c, stream);
-  const int* d_ids = nullptr;
-  int entry = 0;
-  if (const int rc = ids_stage(c, ids, n, s, &d_ids, &entry)) return rc;
-  return ids_release(c, entry, s, step_impl(c, d_frames, d_bg, bg_frame_stride, d_out, n, stream, flags, d_ids));
+  return step_call(c, "bsx_step_batch_streams", Entry::Streams, StepReq{d_frames, d_bg, bg_frame_stride, d_out, 0, 0, n, flags, (hipStream_t)stream, nullptr}, ids);
 }
 
 int bsx_reset_streams(bsx_ctx* c, const int* ids, int n, void* stream) {
   if (!c) return BSX_EINVAL;
   if (const int rc = ids_check(c, "bsx_reset_streams", ids, n)) return rc;
+  if (const int rc = refuse_pending(c, "bsx_reset_streams")) return rc;
   if (n == 0) return BSX_OK;
   DeviceGuard guard(c->device);
   hipStream_t s = pick(c, stream);
@@ -1016,135 +1088,25 @@ int bsx_reset_streams(bsx_ctx* c, const int* ids, int n, void* stream) {
 }
 
 // ---- the main loop at the virtual camera's geometry (--vg, app/deepseg.cc:634-681): blend → flip → resize → YUYV pack with the resize folded in -----------------
-namespace {
-int vcam_einval(bsx_ctx* c, const char* why) {
-  c->last_error = std::string("error: bsx_step_batch_vcam: ") + why + "\n";
-  return BSX_EINVAL;
-}
-// the capture -> (out_w, out_h) table, built once per output size
-int vcam_tab(bsx_ctx* c, int out_w, int out_h, const VcamTab** out) {
-  auto key = std::make_pair(out_w, out_h);
-  auto it = c->vcam_tabs.find(key);
-  if (it == c->vcam_tabs.end()) {
-    HostResizeTab h = make_resize_tab(c->width, c->height, out_w, out_h);
-    if (h.mode == 2) {              // the 2x2 area mean as a linear table: taps 2d and 2d + 1, coefficients 1024 / 1024 (the same integers: kernels_img.hip)
-      h.mode = 0;
-      h.xofs.resize(out_w); h.xa.assign(2 * (size_t)out_w, 1024); h.yofs.resize(out_h); h.ya.assign(2 * (size_t)out_h, 1024);
-      for (int d = 0; d < out_w; d++) h.xofs[d] = 2 * d;
-      for (int d = 0; d < out_h; d++) h.yofs[d] = 2 * d;
-    }
-    VcamTab v;
-    v.direct = !vcam_tile_fits(h.xofs.data(), h.yofs.data(), h.sw, h.sh, h.dw, h.dh);
-    int rc = upload_tab(c, h, &v.d);
-    if (rc) { if (v.d.mem) (void)hipFree(v.d.mem); return rc; }
-    it = c->vcam_tabs.emplace(key, v).first;
-  }
-  *out = &it->second;
-  return BSX_OK;
-}
-int vcam_impl(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_frame_stride, uint8_t* d_out, int out_w, int out_h, int n, void* stream,
-              unsigned flags) {
-  const int bgblur = (int)((flags >> 8) & 255u);
-  if (!c) return BSX_EINVAL;
-  if (!d_frames || (!d_bg && !bgblur) || !d_out || n <= 0 || n > c->n_streams) return vcam_einval(c, "null buffer or batch size out of range");
-  if ((flags & ~(31u | 0xFF00u)) || (flags & BSX_STEP_NO_MASK)) return vcam_einval(c, "unsupported flags (the no-mask step has no vcam form)");
-  if (bgblur && (bgblur > 31 || !(bgblur & 1))) return vcam_einval(c, "background blur size must be odd and <= 31");
-  if (out_w <= 0 || out_h <= 0) return vcam_einval(c, "output size must be positive");
-  if (c->pend.active) { c->last_error = "error: a pipelined composite is pending (flush with bsx_step_batch_pipelined(ctx, NULL, ...) first)\n"; return BSX_EINVAL; }
-  const bool yuyv = (flags & BSX_STEP_YUYV) != 0, yin = (flags & BSX_STEP_YUYV_IN) != 0;
-  if (yuyv && (out_w & 1)) return vcam_einval(c, "YUYV output needs an even width");
-  if (yin && (c->width & 1)) return vcam_einval(c, "YUYV input needs an even capture width");
-  const size_t px = (size_t)c->width * c->height;
-  const uint8_t* o0 = d_out;
-  const uint8_t* o1 = d_out + (size_t)n * out_w * out_h * (yuyv ? 2 : 3);
-  if (o0 < d_frames + (size_t)n * px * (yin ? 2 : 3) && d_frames < o1) return vcam_einval(c, "output overlaps the frames");
-  if (!bgblur && o0 < d_bg + bg_frame_stride * (size_t)(n - 1) + px * 3 && d_bg < o1) return vcam_einval(c, "output overlaps the background");
-  if (out_w == c->width && out_h == c->height) return step_impl(c, d_frames, d_bg, bg_frame_stride, d_out, n, stream, flags);
-  DeviceGuard guard(c->device);
-  hipStream_t s = pick(c, stream);
-  const VcamTab* vt = nullptr;
-  int rc = vcam_tab(c, out_w, out_h, &vt);
-  if (rc) return rc;
-  if (yin && (bgblur || !prep_yuyv_fusable(c->width, c->roi, c->tab_down.tab))) {
-    // frames the fused prep cannot read as YUYV (or that a blur needs as BGR): converted once into the context's scratch, then the BGR form — as bsx_step_batch_ex
-    if (!c->d_bgr_in_scratch) BSX_HIP(c, hipMalloc(&c->d_bgr_in_scratch, (size_t)c->n_streams * px * 3));
-    BSX_HIP(c, launch_yuyv_to_bgr(d_frames, c->d_bgr_in_scratch, c->width, c->height, n, s));
-    return vcam_impl(c, c->d_bgr_in_scratch, d_bg, bg_frame_stride, d_out, out_w, out_h, n, stream, flags & ~BSX_STEP_YUYV_IN);
-  }
-  if (bgblur) {                     // background = GaussianBlur(the stream's own frame): blurred into the context's scratch, one background per stream
-    if (!c->d_bgblur_scratch) BSX_HIP(c, hipMalloc(&c->d_bgblur_scratch, (size_t)c->n_streams * px * 3));
-    BSX_HIP(c, launch_gauss_blur(d_frames, c->d_bgblur_scratch, c->width, c->height, bgblur, n, s));
-    return vcam_impl(c, d_frames, c->d_bgblur_scratch, px * 3, d_out, out_w, out_h, n, stream, flags & 0xFFu);
-  }
-  // the masks exactly as bsx_process_batch makes them (prep → network → decode → up-scale + blur into the persistent masks, callbacks included), then one pass
-  if ((rc = process_impl(c, d_frames, n, 0, s, yin))) return rc;
-  bsx_roctx::Range range("bsx:vcam");
-  BSX_HIP(c, launch_vcam_blend_resize(d_frames, yin, d_bg, bg_frame_stride, c->d_masks, d_out, c->width, c->height, vt->d.tab, vt->direct || c->vcam_direct, n, s,
-                                      flags & 7u));
-  return BSX_OK;
-}
-}  // namespace
-
 int bsx_step_batch_vcam(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_frame_stride, uint8_t* d_out, int out_w, int out_h, int n, void* stream,
                         unsigned flags) {
-  return vcam_impl(c, d_frames, d_bg, bg_frame_stride, d_out, out_w, out_h, n, stream, flags);
+  return step_call(c, "bsx_step_batch_vcam", Entry::Vcam, StepReq{d_frames, d_bg, bg_frame_stride, d_out, out_w, out_h, n, flags, (hipStream_t)stream, nullptr});
 }
-
-// ---- two-deep pipeline: mask pipeline of batch k  ||  composite of batch k - 1 ------------------------------------------------------------------
-// The reference overlaps exactly these two halves of its main loop: CalcMask::run() segments on a worker thread (app/deepseg.cc:182-216) while the capture loop
-// blends and writes (:634-681).  Here both halves are GPU work of one context: the composite (HBM-bound: mask tiles + alpha blend) of the batch handed over
-// by the previous call goes to comp_stream, the mask pipeline (latency-bound network kernels) of this call's batch to the caller's stream, and the only shared
-// object — the model-resolution temporal state — is protected by ev_pcomp in front of the launch that advances it.  Unlike the reference's loop, which blends a
-// frame with whatever mask is newest, every frame is composited with ITS OWN mask: results are bit-identical to bsx_step_batch_ex, one call later.
-namespace {
-int pipelined_objects(bsx_ctx* c) {
-  if (c->comp_stream) return BSX_OK;
-  // the composite fills the gaps of the network kernels, not the other way round: lowest priority the device offers (BSX_PIPE_PRIO=0: default priority)
-  int lo = 0, hi = 0;
-  const char* pe = BSX_DBG_ENV("BSX_PIPE_PRIO");
-  if (!(pe && atoi(pe) == 0) && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi) {
-    BSX_HIP(c, hipStreamCreateWithPriority(&c->comp_stream, hipStreamNonBlocking, lo));
-  } else {
-    BSX_HIP(c, hipStreamCreateWithFlags(&c->comp_stream, hipStreamNonBlocking));
-  }
-  BSX_HIP(c, hipEventCreateWithFlags(&c->ev_pdone, hipEventDisableTiming));
-  BSX_HIP(c, hipEventCreateWithFlags(&c->ev_pcomp, hipEventDisableTiming));
-  return BSX_OK;
-}
-int composite_pending(bsx_ctx* c, hipStream_t s, bool concurrent) {
-  const bsx_ctx::PendingComposite& p = c->pend;
-  // next to the network kernels the composite holds at most pipe_wgs workgroups per CU (an unused LDS pad: static 16.7 KB + pad <= 64 KB, i.e. >= 2 per CU)
-  int pad = 0;
-  if (concurrent && c->pipe_wgs > 0) pad = std::max(0, std::min(47 * 1024, (160 * 1024 / c->pipe_wgs - 17 * 1024) & ~255));
-  bsx_roctx::Range range("bsx:mask+blend");
-  BSX_HIP(c, launch_mask_blend(c->d_ofinal, c->outW, c->outH, c->in_roi, c->tab_up.tab, c->d_masks, c->width, c->height, c->roi, p.bg, p.bg_stride, p.frames, p.out, p.n, s,
-                               (int)p.flags, pad));
-  return BSX_OK;
-}
-}  // namespace
 
 int bsx_step_batch_pipelined(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_frame_stride, uint8_t* d_out, int n, void* stream, unsigned flags) {
   if (!c) return BSX_EINVAL;
-  DeviceGuard guard(c->device);
   hipStream_t s = pick(c, stream);
   if (!d_frames) {                                                  // flush: the composite of the last batch, on the caller's stream
+    DeviceGuard guard(c->device);
     if (!c->pend.active) return BSX_OK;
     BSX_HIP(c, hipStreamWaitEvent(s, c->ev_pdone, 0));               // the pending batch's network may have run on another stream than this call's
     const int rc = composite_pending(c, s, false);
     c->pend.active = false;
     return rc;
   }
-  if (!d_bg || !d_out || n <= 0 || n > c->n_streams || (flags & ~31u)) return BSX_EINVAL;
-  const int yuyv = (int)(flags & BSX_STEP_YUYV);
-  const bool yin = (flags & BSX_STEP_YUYV_IN) != 0;
-  if ((yuyv || yin) && (c->width & 1)) return BSX_EINVAL;
-  // the pipeline exists for the fused tile kernel only; out(k) is written while frames(k + 1) are read, so the buffers of a call must not overlap at all
-  const size_t in_bytes = (size_t)n * c->width * c->height * (yin ? 2 : 3), out_bytes = (size_t)n * c->width * c->height * (yuyv ? 2 : 3);
-  const bool overlap = d_out < d_frames + in_bytes && d_frames < d_out + out_bytes;
-  const bool fuse = !c->onprep && !c->oninfer && !c->onmask && !c->no_mask_blend_fusion && !overlap && (!yuyv || ((uintptr_t)d_out & 3) == 0) &&
-                    (!yin || prep_yuyv_fusable(c->width, c->roi, c->tab_down.tab)) &&
-                    mask_blend_fusable(c->width, c->height, c->roi, d_bg, bg_frame_stride, d_frames, yuyv ? d_frames : d_out);
-  if (!fuse) { c->last_error = "error: bsx_step_batch_pipelined needs the fused mask + blend geometry, no stage callbacks and non-overlapping buffers\n"; return BSX_EINVAL; }
+  StepReq r = StepReq{d_frames, d_bg, bg_frame_stride, d_out, c->width, c->height, n, flags, s, nullptr};
+  if (const int rc = check_step(c, "bsx_step_batch_pipelined", r, Entry::Pipelined)) return rc;
+  DeviceGuard guard(c->device);
   int rc = pipelined_objects(c);
   if (rc) return rc;
   bool forked = false;
@@ -1158,10 +1120,7 @@ int bsx_step_batch_pipelined(bsx_ctx* c, const uint8_t* d_frames, const uint8_t*
     forked = true;
     if (!rc) c->wait_before_state = c->ev_pcomp;
   }
-  if (!rc) rc = run_prep(c, d_frames, n, s, false, yin);
-  const bool fused_decode = infer_decodes(c);
-  if (!rc) rc = run_infer(c, n, s, !fused_decode, 0);
-  if (!rc && !fused_decode) rc = run_decode(c, n, s);
+  if (!rc) rc = enqueue_masks(c, d_frames, n, s, r.yin(), 0, nullptr);
   if (forked && (c->wait_before_state || rc)) {                     // fence not consumed (error on the way): join here
     c->wait_before_state = nullptr;
     if (hipStreamWaitEvent(s, c->ev_pcomp, 0) != hipSuccess) rc = rc ? rc : BSX_EDEVICE;
@@ -1230,7 +1189,7 @@ int bsx_debug_buffer(bsx_ctx* c, int which, void** d_ptr, size_t* bytes) {
 
 int bsx_debug_run_stage(bsx_ctx* c, int stage, const uint8_t* d_frames, int n, void* stream) {
   if (!c || n <= 0 || n > c->n_streams) return BSX_EINVAL;
-  if (stage >= 1 && stage <= 3 && c->pend.active) { c->last_error = "error: a pipelined composite is pending (flush with bsx_step_batch_pipelined(ctx, NULL, ...) first)\n"; return BSX_EINVAL; }
+  if (stage >= 1 && stage <= 3) { if (const int rc = refuse_pending(c, "bsx_debug_run_stage")) return rc; }
   DeviceGuard guard(c->device);
   hipStream_t s = pick(c, stream);
   switch (stage) {
@@ -1248,66 +1207,36 @@ int bsx_debug_run_stage(bsx_ctx* c, int stage, const uint8_t* d_frames, int n, v
 int bsx_profile_batch(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_stride, uint8_t* d_out, int n, int iters,
                       bsx_launch_stat* out, int cap, void* stream) {
   if (!c || !d_frames || !d_bg || !d_out || !out || n <= 0 || n > c->n_streams || iters <= 0) return BSX_EINVAL;
-  if (c->pend.active) { c->last_error = "error: a pipelined composite is pending (flush with bsx_step_batch_pipelined(ctx, NULL, ...) first)\n"; return BSX_EINVAL; }
+  if (const int rc = refuse_pending(c, "bsx_profile_batch")) return rc;
   DeviceGuard guard(c->device);
   hipStream_t s = pick(c, stream);
   const bool seg = c->use_program && c->plan.seg.on;
   const bool fused_decode = infer_decodes(c);
   const bool atail = argmax_tail(c);
   const int n_net = c->use_program ? (seg ? (c->plan.seg.tail.pre_gate_off >= 0 ? 6 : 5) : 1) : (int)c->plan.steps.size();
-  const bool fuse_tail = !c->onmask && !c->no_mask_blend_fusion &&
-                         mask_blend_fusable(c->width, c->height, c->roi, d_bg, bg_stride, d_frames, d_out);
+  const bool fuse_tail = tile_fusable(c, StepReq{d_frames, d_bg, bg_stride, d_out, c->width, c->height, n, 0u, s, nullptr});
   const int L = 1 + n_net + (fused_decode ? 0 : 1) + (fuse_tail ? 1 : 2) + (fuse_tail ? 1 : 0);   // + a stand-alone blend launch when the step's tail is fused
   if (cap < L) return BSX_EINVAL;
-  // ONE event between consecutive launches (round 6: L + 1 events, not 2 L): launch k is timed from the event behind launch k - 1 to the event behind itself, so
-  // the per-launch figures add up to the pass and carry one event's cost each instead of two (round 5's bracketing pairs read 11 % over the un-instrumented step)
-  std::vector<hipEvent_t> ev((size_t)L + 1);
-  for (auto& e : ev) BSX_HIP(c, hipEventCreate(&e));
+  // ONE event between consecutive launches (L + 1 events, not 2 L): the per-launch figures add up to the pass and carry one event's cost each instead of two
+  LaunchTimer t{std::vector<hipEvent_t>((size_t)L + 1, nullptr)};
+  for (auto& e : t.ev) BSX_HIP(c, hipEventCreate(&e));
   std::vector<double> sum(L, 0.0);
   const double N = n, px = (double)c->width * c->height;
   for (int it = 0; it < iters; it++) {
-    int k = 0;
-    BSX_HIP(c, hipEventRecord(ev[0], s));
-#define BSX_TIMED(call)                                    \
-    do {                                                   \
-      BSX_HIP(c, (call));                                  \
-      BSX_HIP(c, hipEventRecord(ev[k + 1], s));            \
-      k++;                                                 \
-    } while (0)
-    BSX_TIMED(launch_prep_fused(d_frames, c->width, c->height, c->roi, c->in_u8 ? nullptr : c->tensor_ptr(c->plan.input), c->in_u8 ? c->d_net_in_u8 : nullptr, c->inW, c->inH, c->in_roi,
-                                c->tab_down.tab, c->bilateral, n, s));
-    const long pf = (long)c->plan.arena_floats_per_stream;
-    if (seg) {
-      const SegPlan& sp = c->plan.seg;
-      BSX_TIMED(seg_head(c, n, s));
-      BSX_TIMED(seg_k2(c, n, s));
-      BSX_TIMED(launch_program(c, n, s));
-      BSX_TIMED(seg_k3(c, n, s));
-      if (sp.tail.pre_gate_off >= 0) BSX_TIMED(launch_seg_gate(sp.tail.gate, c->d_arena, pf, c->d_weights, sp.tail.pre_gate_off, n, s));
-      BSX_TIMED(seg_tail(c, c->d_ofinal, !fused_decode, n, s));
-    } else if (c->use_program)
-      BSX_TIMED(launch_program(c, n, s));
-    else {
-      for (size_t si = 0; si + (atail ? 1 : 0) < c->plan.steps.size(); si++)
-        BSX_TIMED(launch_step(c->plan.steps[si], c->plan, c->d_arena, c->d_net_in, c->d_net_out, c->d_weights, n, c->n_streams, s, c->d_weights16, c->f16_terms, c->in_u8 ? c->d_net_in_u8 : nullptr, c->norm_scale, c->norm_offset));
-      if (atail) BSX_TIMED(launch_resize_argmax_iir(c->plan.steps.back(), c->d_arena + (size_t)c->plan.tensor_off[c->plan.steps.back().in0] * (size_t)c->n_streams,
-                                                    c->d_ofinal, n, s, c->tail_generic));
-    }
-    if (!fused_decode) BSX_TIMED(launch_decode(c->model_type, c->tensor_ptr(c->plan.output), c->d_ofinal, c->outW * c->outH, c->outC, n, s));
+    t.k = 0;
+    BSX_HIP(c, hipEventRecord(t.ev[0], s));
+    // the step's own launch sequence (bsx_step_batch on the same buffers), an event behind each launch
+    if (const int rc = enqueue_masks(c, d_frames, n, s, false, 0, nullptr, &t)) return rc;
     if (fuse_tail) {
-      BSX_TIMED(launch_mask_blend(c->d_ofinal, c->outW, c->outH, c->in_roi, c->tab_up.tab, c->d_masks, c->width, c->height, c->roi, d_bg, bg_stride,
-                                  d_frames, d_out, n, s));
-      // not part of the step: the plain alpha-blend kernel (bsx_composite_batch) on the same buffers, for its own roofline line
-      BSX_TIMED(launch_blend(d_bg, bg_stride, d_frames, c->d_masks, d_out, (size_t)c->width * c->height, n, s));
-    } else {
-      BSX_TIMED(launch_mask_upscale_blur(c->d_ofinal, c->outW, c->outH, c->in_roi, c->tab_up.tab, c->d_masks, c->width, c->height, c->roi, n, s));
-      BSX_TIMED(launch_blend(d_bg, bg_stride, d_frames, c->d_masks, d_out, (size_t)c->width * c->height, n, s));
-    }
-#undef BSX_TIMED
+      BSX_LAUNCH(c, &t, s, launch_mask_blend(c->d_ofinal, c->outW, c->outH, c->in_roi, c->tab_up.tab, c->d_masks, c->width, c->height, c->roi, d_bg, bg_stride,
+                                             d_frames, d_out, n, s));
+    } else if (const int rc = run_mask(c, n, s, 0, nullptr, &t)) return rc;
+    // not part of a fused step: the plain alpha-blend kernel (bsx_composite_batch) on the same buffers, for its own roofline line
+    BSX_LAUNCH(c, &t, s, launch_blend(d_bg, bg_stride, d_frames, c->d_masks, d_out, (size_t)c->width * c->height, n, s));
     BSX_HIP(c, hipStreamSynchronize(s));
-    for (int j = 0; j < L; j++) { float ms = 0; BSX_HIP(c, hipEventElapsedTime(&ms, ev[j], ev[j + 1])); sum[j] += ms; }
+    if (t.k != L) { c->last_error = "error: bsx_profile_batch: the step made fewer launches than the profile counts\n"; return BSX_EDEVICE; }
+    for (int j = 0; j < L; j++) { float ms = 0; BSX_HIP(c, hipEventElapsedTime(&ms, t.ev[j], t.ev[j + 1])); sum[j] += ms; }
   }
-  for (auto& e : ev) (void)hipEventDestroy(e);
   auto put = [&](int j, const std::string& name, double bytes, double flops) {
     memset(&out[j], 0, sizeof out[j]);
     snprintf(out[j].name, sizeof out[j].name, "%s", name.c_str());
@@ -1520,7 +1449,7 @@ const char* bsx_plan_describe(bsx_ctx* c) { return c ? c->plan_text.c_str() : ""
 // error, so the inspection entry points refuse arena tensors in that mode (network input / output keep their f32 buffers).
 static bool debug_tensor_readable(const bsx_ctx* c, int t) { return !c->act16 || t == c->plan.input || t == c->plan.output; }
 
-long bsx_debug_tensor_of(bsx_ctx* c, int t, int stream_idx, float* h_out, long cap) {
+static long debug_tensor_at(bsx_ctx* c, int t, int stream_idx, float* h_out, long cap) {
   if (!c || t < 0 || t >= (int)c->graph.tensors.size() || c->plan.tensor_off[t] < 0 || stream_idx < 0 || stream_idx >= c->n_streams) return BSX_EINVAL;
   if (h_out && cap < 0) return BSX_EINVAL;
   if (!debug_tensor_readable(c, t)) { c->last_error = "bsx_debug_tensor: arena tensors are stored as f16 under BSX_ACT16 and are not readable through this entry"; return BSX_EINVAL; }
@@ -1535,16 +1464,7 @@ long bsx_debug_tensor_of(bsx_ctx* c, int t, int stream_idx, float* h_out, long c
   return n;
 }
 
-long bsx_debug_tensor(bsx_ctx* c, int t, float* h_out, long cap) {
-  if (!c || t < 0 || t >= (int)c->graph.tensors.size() || c->plan.tensor_off[t] < 0) return BSX_EINVAL;
-  if (h_out && cap < 0) return BSX_EINVAL;
-  if (!debug_tensor_readable(c, t)) { c->last_error = "bsx_debug_tensor: arena tensors are stored as f16 under BSX_ACT16 and are not readable through this entry"; return BSX_EINVAL; }
-  DeviceGuard guard(c->device);
-  long n = (long)c->graph.tensors[t].elems();
-  if (!h_out) return n;
-  if (hipDeviceSynchronize() != hipSuccess) return BSX_EDEVICE;
-  if (hipMemcpy(h_out, c->tensor_ptr(t), sizeof(float) * (size_t)std::min(n, cap), hipMemcpyDeviceToHost) != hipSuccess) return BSX_EDEVICE;
-  return n;
-}
+long bsx_debug_tensor_of(bsx_ctx* c, int t, int stream_idx, float* h_out, long cap) { return debug_tensor_at(c, t, stream_idx, h_out, cap); }
+long bsx_debug_tensor(bsx_ctx* c, int t, float* h_out, long cap) { return debug_tensor_at(c, t, 0, h_out, cap); }
 
 }  // extern "C"
