@@ -19,11 +19,11 @@
 
 #include "../../include/bsx.h"
 #include "gen_mid.hpp"
-#include "gen_seg.hpp"
 #include "kernels.hpp"
 #include "roctx_ranges.hpp"
-#include "rtc.hpp"
 #include "plan.hpp"
+#include "rtc.hpp"
+#include "specialised.hpp"
 #include "tflite_model.hpp"
 
 using namespace bsx;
@@ -128,11 +128,8 @@ struct bsx_ctx {
   float* d_color_lut = nullptr;
   MicroOp* d_program = nullptr;     // per-frame network program (kernels_frame.hip)
   bool use_program = false;
-  RtcKernel mid;                    // the same program as ONE graph-specialised kernel, compiled by hipRTC when the context is created
-  RtcKernel seg_mod;                // the segment kernels specialised to this graph (gen_seg.cpp; one hipRTC module: seg_mod.fn = bsx_seg_head, seg_fn[] = k2, k3, tail)
-  hipFunction_t seg_fn[3] = {nullptr, nullptr, nullptr};
-  std::string seg_note;
-  std::string mid_note;             //   (gen_mid.cpp, mid_prelude.hip); mid.fn == nullptr: the interpreter runs (BSX_NO_RTC=1, or why in mid_note)
+  SpecialisedKernels kern;          // the program as ONE graph-specialised kernel and the segment kernels specialised to this graph (specialised.hpp); null: the
+                                    // interpreter / the ahead-of-time segment kernels run
   BilateralParams bilateral{};
   DevResizeTab tab_down, tab_up;
   uint8_t* d_tile_class = nullptr;    // [n_streams][mask tiles]: 1 / 2 = the tile's source block is all 0xFF / 0x00 (tile_class_k), read by mask_tile_k
@@ -235,41 +232,6 @@ int upload_tab(bsx_ctx* c, const HostResizeTab& h, DevResizeTab* d) {
   return BSX_OK;
 }
 
-// The graph-specialised SEGMENT kernels of `plan` (gen_seg.cpp), compiled or fetched from the cache for `arch`: "" and the code object, or why there is none
-std::string build_seg_kernels(const Plan& plan, bool h16, bool u8in, const std::string& arch, std::vector<char>* code, bool* cached, size_t* src_bytes = nullptr) {
-  std::string why, log;
-  if (BSX_DBG_ENV("BSX_NO_SEG_RTC")) return "ahead-of-time kernels (BSX_NO_SEG_RTC)";
-  const std::string src = generate_seg_source(plan, h16, u8in, &why);
-  if (src.empty()) return "ahead-of-time kernels (" + why + ")";
-  if (src_bytes) *src_bytes = src.size();
-  if (!rtc_build(src, arch, code, &log, cached)) { if (BSX_DBG_ENV("BSX_RTC_DEBUG")) fprintf(stderr, "%s\n", log.c_str()); return "ahead-of-time kernels (hipRTC: " + log.substr(0, 600) + ")"; }
-  return "";
-}
-
-// The graph-specialised middle kernel of `plan`, compiled (or fetched from the cache) for `arch` — in the form that spills least.  The plain form lets the compiler share
-// every lane-derived value between ops; where that pushes the kernel into scratch (MLKit: 352 bytes at 128 registers) the opaque-lane-index form (mid_prelude.hip:
-// tid_now; 92 registers, no scratch) is compiled too and taken if its scratch is smaller — read from the code objects' kernel descriptors, so the choice needs no GPU and
-// bsx_model_precompile makes the same one a context makes later (both code objects sit in the cache).  Returns "" and fills *code, or the reason there is no kernel.
-struct MidBuild { std::vector<char> code; std::string source, note; bool cached = false, opaque_tid = false; long scratch = -1; };
-std::string build_mid_kernel(const Plan& plan, bool act16, const std::string& arch, MidBuild* out) {
-  std::string why, log;
-  int force = -1;                                                 // debug build: BSX_RTC_TID=0 | 1 forces the plain / the opaque form (A/B timing)
-  if (const char* e = BSX_DBG_ENV("BSX_RTC_TID")) force = atoi(e) != 0;
-  auto build = [&](bool opaque, MidBuild* b) -> std::string {
-    b->source = generate_mid_source(plan, &why, act16, opaque);
-    if (b->source.empty()) return "interpreted (" + why + ")";
-    if (!rtc_build(b->source, arch, &b->code, &log, &b->cached)) { if (BSX_DBG_ENV("BSX_RTC_DEBUG")) fprintf(stderr, "%s\n", log.c_str()); return "interpreted (hipRTC: " + log.substr(0, 400) + ")"; }
-    b->opaque_tid = opaque;
-    b->scratch = code_object_scratch_bytes(b->code, "bsx_mid");
-    return "";
-  };
-  std::string err = build(force == 1, out);
-  if (!err.empty() || force >= 0 || out->scratch <= 0) return err;
-  MidBuild alt;
-  if (build(true, &alt).empty() && alt.scratch >= 0 && alt.scratch < out->scratch) *out = std::move(alt);
-  return "";
-}
-
 int model_type_from_name(const std::string& n) {  // lib/libbackscrub.cc:116-130 (same precedence)
   if (n.find("body-pix") != n.npos) return BSX_MODEL_BODYPIX;
   if (n.find("deeplab") != n.npos) return BSX_MODEL_DEEPLAB;
@@ -297,32 +259,24 @@ int init_device_state(bsx_ctx* c) {
                    (c->plan.seg.on || c->plan.program_lds_tensors >= c->plan.program_global_tensors || BSX_DBG_ENV("BSX_FORCE_FRAME_PROGRAM") != nullptr);
   hipDeviceProp_t prop;                       // the architecture the graph-specialised kernels are compiled for (below)
   const bool have_prop = c->use_program && !BSX_DBG_ENV("BSX_NO_RTC") && hipGetDeviceProperties(&prop, c->device) == hipSuccess;
+  const KernelVariant v = kernel_variant(c->plan);
   if (c->use_program) {
     BSX_HIP(c, hipMalloc(&c->d_program, c->plan.program.size() * sizeof(MicroOp)));
     BSX_HIP(c, hipMemcpy(c->d_program, c->plan.program.data(), c->plan.program.size() * sizeof(MicroOp), hipMemcpyHostToDevice));
     BSX_HIP(c, frame_program_prepare(c->plan.program_lds_floats));
     if (c->plan.seg.on) BSX_HIP(c, seg_prepare());
-    // Specialise the program to this graph: straight-line code with compile-time geometry instead of the interpreted micro-op table.
-    // Compiled by hipRTC for this device's architecture (cached on disk; bsx_model_precompile fills the cache without a GPU).
-    // Anything the generator does not cover, or a failed compilation, leaves the interpreter in charge — never an error.
-    const char* a16 = getenv("BSX_ACT16");
-    c->act16 = a16 && atoi(a16) != 0 && c->plan.seg.on;
-    if (!BSX_DBG_ENV("BSX_NO_RTC")) {
-      MidBuild mb;
-      if (!have_prop) c->mid_note = "interpreted (no device properties)";
-      else {
-        const std::string err = build_mid_kernel(c->plan, c->act16, prop.gcnArchName, &mb);
-        if (!err.empty()) c->mid_note = err;
-        else if (rtc_load(mb.code, "bsx_mid", &c->mid) != hipSuccess) { c->mid_note = "interpreted (code object did not load)"; (void)hipGetLastError(); }
-        else c->mid_note = std::string("specialised kernel (hipRTC") + (mb.cached ? ", from the cache" : ", compiled now") + (mb.opaque_tid ? ", lane indices re-derived per op" : "") +
-                           (mb.scratch > 0 ? ", " + std::to_string(mb.scratch) + " B of scratch" : "") + ")";
-      }
-    } else c->mid_note = "interpreted (BSX_NO_RTC)";
-    if (c->act16 && !c->mid.fn) {            // the interpreter has f32 tensors only: the mode needs the generated kernel
-      c->last_error = "BSX_ACT16: the specialised middle kernel is not available (" + c->mid_note + ")";
+    // Specialise the program and the segment kernels to this graph: straight-line code with compile-time geometry instead of the interpreted micro-op table, the
+    // segment kernels' source with this plan's descriptors as compile-time constants.  Compiled by hipRTC for this device's architecture (cached on disk;
+    // bsx_model_precompile fills the cache without a GPU).  Anything that goes wrong leaves the interpreter / the ahead-of-time kernels in charge — never an error.
+    c->act16 = v.act16;
+    if (BSX_DBG_ENV("BSX_NO_RTC")) no_specialised("BSX_NO_RTC", &c->kern);
+    else if (!have_prop) no_specialised("no device properties", &c->kern);
+    else load_specialised(build_specialised(c->plan, v, prop.gcnArchName), &c->kern);
+    if (c->act16 && !c->kern.mid) {          // the interpreter has f32 tensors only: the mode needs the generated kernel
+      c->last_error = "BSX_ACT16: the specialised middle kernel is not available (" + c->kern.mid_note + ")";
       return BSX_EDEVICE;
     }
-    if (c->act16) c->mid_note += ", 16-bit activation storage";
+    if (c->act16) c->kern.mid_note += ", 16-bit activation storage";
   } else {
     BSX_HIP(c, nn_prepare());                 // per-launch path: the fused kernels' dynamic-LDS limits on this device
   }
@@ -337,28 +291,7 @@ int init_device_state(bsx_ctx* c) {
   }
   // stems with a byte path take the 8-bit network input: the segmented Meet / MLKit head and DeepLab's fused head kernel
   if (BSX_DBG_ENV("BSX_NO_GRAPH")) c->graph_state = -1;
-  c->in_u8 = BSX_DBG_ENV("BSX_F32_INPUT") == nullptr && ((c->use_program && c->plan.seg.on) || (!c->use_program && head0_u8_ok(c->plan)));
-  // The segment kernels specialised to this graph (gen_seg.cpp): the same source as the ahead-of-time kernels with this plan's descriptors as compile-time constants,
-  // compiled by hipRTC (cached on disk; bsx_model_precompile fills the cache without a GPU).  Anything that goes wrong leaves the ahead-of-time kernels in charge.
-  if (c->use_program && c->plan.seg.on) {
-    if (BSX_DBG_ENV("BSX_NO_RTC")) c->seg_note = "ahead-of-time kernels (BSX_NO_RTC)";
-    else {
-      std::vector<char> code;
-      bool cached = false;
-      if (!have_prop) c->seg_note = "ahead-of-time kernels (no device properties)";
-      else {
-        c->seg_note = build_seg_kernels(c->plan, c->act16, c->in_u8, prop.gcnArchName, &code, &cached);
-        if (c->seg_note.empty()) {
-          if (rtc_load(code, "bsx_seg_head", &c->seg_mod) != hipSuccess || rtc_function(c->seg_mod, "bsx_seg_k2", &c->seg_fn[0]) != hipSuccess ||
-              rtc_function(c->seg_mod, "bsx_seg_k3", &c->seg_fn[1]) != hipSuccess || rtc_function(c->seg_mod, "bsx_seg_tail", &c->seg_fn[2]) != hipSuccess) {
-            rtc_unload(&c->seg_mod);
-            (void)hipGetLastError();
-            c->seg_note = "ahead-of-time kernels (code object did not load)";
-          } else c->seg_note = std::string("specialised kernels (hipRTC") + (cached ? ", from the cache)" : ", compiled now)");
-        }
-      }
-    }
-  }
+  c->in_u8 = v.u8in && ((c->use_program && c->plan.seg.on) || (!c->use_program && head0_u8_ok(c->plan)));
   BSX_HIP(c, hipMalloc(&c->d_ofinal, N * c->outW * c->outH));
   BSX_HIP(c, hipMalloc(&c->d_masks, N * c->width * c->height));
   BSX_HIP(c, hipMemset(c->d_ofinal, 0, N * c->outW * c->outH));            // :257 leaves it uninitialised; defined as 0
@@ -432,11 +365,11 @@ bool argmax_tail(const bsx_ctx* c) {
 // the middle of a segmented plan / the whole-network program: the specialised kernel when one was built, else the interpreter
 hipError_t launch_program(bsx_ctx* c, int n, hipStream_t s, unsigned long long* timeline = nullptr) {
   long pf = (long)c->plan.arena_floats_per_stream;
-  if (c->mid.fn) {
+  if (c->kern.mid) {
     float* arena = c->d_arena;
     const float* weights = c->d_weights;
     void* args[] = {&arena, &pf, &weights, &timeline};
-    return hipModuleLaunchKernel(c->mid.fn, (unsigned)n, 1, 1, (unsigned)c->plan.mid_lanes, 1, 1, 0, s, args, nullptr);
+    return hipModuleLaunchKernel(c->kern.mid, (unsigned)n, 1, 1, (unsigned)c->plan.mid_lanes, 1, 1, 0, s, args, nullptr);
   }
   return launch_frame_program(c->d_program, (int)c->plan.program.size(), c->plan.program_lds_floats, c->d_arena, pf, c->d_net_in, c->d_net_out, c->d_weights, n, s,
                               timeline);
@@ -451,54 +384,23 @@ int state_write_fence(bsx_ctx* c, hipStream_t s) {
   return BSX_OK;
 }
 bool infer_decodes(const bsx_ctx* c) { return (c->use_program && c->plan.seg.on && !c->keep_logits) || argmax_tail(c); }
-// the four segment launches of a step: the graph-specialised hipRTC kernels when the context has them (the decode-fused tail only: the logits-writing variant of the stage
-// tests stays with the ahead-of-time kernel), else the ahead-of-time kernels.  Same arguments, descriptor included (the specialised kernels ignore it).
-hipError_t seg_launch(hipFunction_t fn, int tiles, int n, int lds_floats, hipStream_t s, void** args) {
-  return hipModuleLaunchKernel(fn, (unsigned)tiles * (unsigned)n, 1, 1, kSegThreads, 1, 1, (unsigned)((size_t)lds_floats * sizeof(float)), s, args, nullptr);
-}
-hipError_t seg_head(bsx_ctx* c, int n, hipStream_t s) {
-  const SegPlan& sp = c->plan.seg;
-  long pf = (long)c->plan.arena_floats_per_stream;
-  if (!c->seg_mod.fn)
-    return launch_seg_head(sp.head, c->d_arena, pf, c->in_u8 ? (const void*)c->d_net_in_u8 : (const void*)c->d_net_in, c->d_weights, n, s, c->act16, c->in_u8, c->norm_scale, c->norm_offset);
-  SegHead d = sp.head; float* arena = c->d_arena; const float* in = c->in_u8 ? reinterpret_cast<const float*>(c->d_net_in_u8) : c->d_net_in; const float* w = c->d_weights;
-  float sc = c->norm_scale, of = c->norm_offset; int nf = n;
-  void* args[] = {&d, &arena, &pf, &in, &w, &sc, &of, &nf};
-  return seg_launch(c->seg_mod.fn, d.tiles_y * d.tiles_x, n, d.lds_floats, s, args);
-}
-// k2 (fn = seg_fn[0], descriptor plan.seg.k2) and k3 (seg_fn[1], plan.seg.k3) take the same arguments
-template <class D> hipError_t seg_mid(bsx_ctx* c, D d, hipFunction_t fn, hipError_t (*aot)(const D&, float*, long, const float*, int, hipStream_t, bool), int n, hipStream_t s) {
-  long pf = (long)c->plan.arena_floats_per_stream;
-  if (!fn) return aot(d, c->d_arena, pf, c->d_weights, n, s, c->act16);
-  float* arena = c->d_arena; const float* w = c->d_weights; int nf = n;
-  void* args[] = {&d, &arena, &pf, &w, &nf};
-  return seg_launch(fn, d.tiles_y * d.tiles_x, n, d.lds_floats, s, args);
-}
-hipError_t seg_k2(bsx_ctx* c, int n, hipStream_t s) { return seg_mid(c, c->plan.seg.k2, c->seg_fn[0], launch_seg_k2, n, s); }
-hipError_t seg_k3(bsx_ctx* c, int n, hipStream_t s) { return seg_mid(c, c->plan.seg.k3, c->seg_fn[1], launch_seg_k3, n, s); }
-hipError_t seg_tail(bsx_ctx* c, uint8_t* ofinal, bool logits, int n, hipStream_t s, const int* ids = nullptr) {
-  const SegPlan& sp = c->plan.seg;
-  long pf = (long)c->plan.arena_floats_per_stream;
-  if (logits || !c->seg_fn[2]) return launch_seg_tail(sp.tail, c->d_arena, pf, c->d_net_out, ofinal, c->d_weights, logits, n, s, c->act16, ids);
-  SegTail d = sp.tail; float* arena = c->d_arena; float* no = c->d_net_out; const float* w = c->d_weights; int nf = n;
-  const int* slot_of = ids;
-  void* args[] = {&d, &arena, &pf, &no, &ofinal, &w, &nf, &slot_of};
-  return seg_launch(c->seg_fn[2], d.tiles_y * d.tiles_x, n, d.lds_floats, s, args);
-}
-
 // ids (device, nullable): the id form of a step — frame i's temporal state is slot ids[i] (then slot == 0); nullptr = slots [slot, slot + n)
 int run_infer(bsx_ctx* c, int n, hipStream_t s, bool logits = true, int slot = 0, const int* ids = nullptr, LaunchTimer* t = nullptr) {
   bsx_roctx::Range range("bsx:network");
   if (c->use_program && c->plan.seg.on) {
+    // the four segment kernels: the graph-specialised ones where the context loaded them (c->kern.seg), else the ahead-of-time instances
     const SegPlan& sp = c->plan.seg;
+    const hipFunction_t* fn = c->kern.seg;
     const long pf = (long)c->plan.arena_floats_per_stream;
-    BSX_LAUNCH(c, t, s, seg_head(c, n, s));
-    BSX_LAUNCH(c, t, s, seg_k2(c, n, s));
+    const void* in = c->in_u8 ? (const void*)c->d_net_in_u8 : (const void*)c->d_net_in;
+    BSX_LAUNCH(c, t, s, launch_seg_head(fn[0], sp.head, c->d_arena, pf, in, c->d_weights, n, s, c->act16, c->in_u8, c->norm_scale, c->norm_offset));
+    BSX_LAUNCH(c, t, s, launch_seg_k2(fn[1], sp.k2, c->d_arena, pf, c->d_weights, n, s, c->act16));
     BSX_LAUNCH(c, t, s, launch_program(c, n, s));
-    BSX_LAUNCH(c, t, s, seg_k3(c, n, s));
+    BSX_LAUNCH(c, t, s, launch_seg_k3(fn[2], sp.k3, c->d_arena, pf, c->d_weights, n, s, c->act16));
     if (sp.tail.pre_gate_off >= 0) BSX_LAUNCH(c, t, s, launch_seg_gate(sp.tail.gate, c->d_arena, pf, c->d_weights, sp.tail.pre_gate_off, n, s));
     if (!logits) { const int frc = state_write_fence(c, s); if (frc) return frc; }       // the decoding tail reads and writes d_ofinal
-    BSX_LAUNCH(c, t, s, seg_tail(c, c->d_ofinal + (size_t)slot * c->outW * c->outH, logits, n, s, ids));
+    BSX_LAUNCH(c, t, s, launch_seg_tail(fn[3], sp.tail, c->d_arena, pf, c->d_net_out, c->d_ofinal + (size_t)slot * c->outW * c->outH, c->d_weights, logits, n, s,
+                                        c->act16, ids));
     return BSX_OK;
   }
   if (c->use_program) {
@@ -933,10 +835,10 @@ bsx_ctx* bsx_new(const char* model_path, size_t threads, size_t width, size_t he
              c->use_program ? "ON" : "off", c->plan.program.size(), c->plan.program_lds_floats, c->plan.program_lds_floats / 256.0,
              c->plan.program_lds_tensors, c->plan.program_global_tensors);
     c->plan_text += line;
-    if (c->use_program) c->plan_text += "program execution: " + c->mid_note + "\n";
+    if (c->use_program) c->plan_text += "program execution: " + c->kern.mid_note + "\n";
     if (c->use_program && c->plan.seg.on) c->plan_text += c->plan.seg_text;
-    if (c->use_program && c->plan.seg.on) c->plan_text += "segment execution: " + c->seg_note + "\n";
-    if (c->use_program && c->mid.fn) c->plan_text += mid_barrier_line(c->plan, c->act16);
+    if (c->use_program && c->plan.seg.on) c->plan_text += "segment execution: " + c->kern.seg_note + "\n";
+    if (c->use_program && c->kern.mid) c->plan_text += mid_barrier_line(c->plan, c->act16);
     for (size_t i = 0; i < c->plan.program_labels.size(); i++) { c->plan_text += "P" + std::to_string(i) + " " + c->plan.program_labels[i] + "\n"; }
   }
   return c.release();
@@ -954,8 +856,7 @@ void bsx_delete(bsx_ctx* c) {
   DeviceGuard guard(c->device);
   if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
   for (auto& kv : c->host_graphs) if (kv.second) (void)hipGraphExecDestroy(kv.second);
-  rtc_unload(&c->mid);
-  rtc_unload(&c->seg_mod);
+  unload_specialised(&c->kern);
   void* ptrs[] = {c->d_arena, c->d_net_in, c->d_net_in_u8, c->d_net_out, c->d_weights, c->d_ofinal, c->d_masks, c->d_host_frame, c->d_bgr_scratch, c->d_bgr_scratch2, c->d_bgblur_scratch, c->d_bgr_in_scratch, c->d_color_lut, c->tab_down.mem, c->tab_up.mem, c->d_program, c->d_weights16, c->d_tile_class};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (auto& kv : c->bg_tabs) if (kv.second.mem) (void)hipFree(kv.second.mem);
@@ -1380,20 +1281,14 @@ long bsx_model_kernel_source(const char* model_path, char* buf, size_t cap) {
   if (!model_path || !buf || !cap) return BSX_EINVAL;
   try {
     Graph g; Plan p;
-    std::string err, why;
+    std::string err;
     if (!load_tflite(model_path, &g, &err) || !build_plan(g, &p, &err)) { snprintf(buf, cap, "%s", err.c_str()); return BSX_EMODEL; }
-    const char* a16 = getenv("BSX_ACT16");
     if (p.program.empty()) { snprintf(buf, cap, "no program"); return 0; }
-    MidBuild mb;                                                    // the source of the kernel a context would RUN (the form build_mid_kernel picks: compiles, no GPU needed)
-    const std::string e = build_mid_kernel(p, a16 && atoi(a16) != 0 && p.seg.on, "gfx950", &mb);
-    if (!e.empty()) {
-      const std::string src = generate_mid_source(p, &why, a16 && atoi(a16) != 0 && p.seg.on);      // a compiler failure still shows the source; a graph without a body shows why
-      if (src.empty()) { snprintf(buf, cap, "%s", why.c_str()); return 0; }
-      snprintf(buf, cap, "%s", src.c_str());
-      return (long)src.size();
-    }
-    snprintf(buf, cap, "%s", mb.source.c_str());
-    return (long)mb.source.size();
+    // the source of the kernel a context would RUN (the form build_specialised picks: compiles, no GPU needed); a compiler failure still shows the source, a graph
+    // without a body shows why
+    const SpecialisedCode m = build_specialised(p, kernel_variant(p), "gfx950", kBuildMid).mid;
+    snprintf(buf, cap, "%s", (m.source.empty() ? m.why : m.source).c_str());
+    return (long)m.source.size();
   } catch (...) { snprintf(buf, cap, "exception while reading the model"); return BSX_EMODEL; }
 }
 
@@ -1401,13 +1296,11 @@ long bsx_model_seg_source(const char* model_path, char* buf, size_t cap) {
   if (!model_path || !buf || !cap) return BSX_EINVAL;
   try {
     Graph g; Plan p;
-    std::string err, why;
+    std::string err;
     if (!load_tflite(model_path, &g, &err) || !build_plan(g, &p, &err)) { snprintf(buf, cap, "%s", err.c_str()); return BSX_EMODEL; }
-    const char* a16 = getenv("BSX_ACT16");
-    const std::string src = generate_seg_source(p, a16 && atoi(a16) != 0 && p.seg.on, BSX_DBG_ENV("BSX_F32_INPUT") == nullptr, &why);
-    if (src.empty()) { snprintf(buf, cap, "%s", why.c_str()); return 0; }
-    snprintf(buf, cap, "%s", src.c_str());
-    return (long)src.size();
+    const SpecialisedCode sc = build_specialised(p, kernel_variant(p), "gfx950", kBuildSeg).seg;
+    snprintf(buf, cap, "%s", (sc.source.empty() ? sc.why : sc.source).c_str());
+    return (long)sc.source.size();
   } catch (...) { snprintf(buf, cap, "exception while reading the model"); return BSX_EMODEL; }
 }
 
@@ -1415,30 +1308,29 @@ int bsx_model_precompile(const char* model_path, const char* arch, char* msg, si
   if (!model_path || !msg || !cap) return BSX_EINVAL;
   try {
     Graph g; Plan p;
-    std::string err, why, log;
+    std::string err;
     if (!load_tflite(model_path, &g, &err) || !build_plan(g, &p, &err)) { snprintf(msg, cap, "%s", err.c_str()); return BSX_EMODEL; }
-    const char* a16 = getenv("BSX_ACT16");                         // the variant a context created under the same environment would ask for
     if (p.program.empty()) { snprintf(msg, cap, "interpreted (no program)"); return BSX_OK; }
-    MidBuild mb;
-    const std::string e = build_mid_kernel(p, a16 && atoi(a16) != 0 && p.seg.on, arch ? arch : "gfx950", &mb);
-    if (!e.empty()) { snprintf(msg, cap, "%s", e.c_str()); return e.compare(0, 19, "interpreted (hipRTC") == 0 ? BSX_EMODEL : BSX_OK; }
-    // the segment kernels of the same graph (gen_seg.cpp), in the variant a context created under this environment would load
+    // the variant a context created under the same environment would ask for
+    const SpecialisedBuild b = build_specialised(p, kernel_variant(p), arch ? arch : "gfx950");
+    const std::string& e = b.mid.fallback;
+    if (b.mid.code.empty()) { snprintf(msg, cap, "%s", e.c_str()); return e.compare(0, 19, "interpreted (hipRTC") == 0 ? BSX_EMODEL : BSX_OK; }
     std::string seg_msg;
     if (p.seg.on) {
-      std::vector<char> scode;
-      bool scached = false;
-      size_t sbytes = 0;
-      const std::string se = build_seg_kernels(p, a16 && atoi(a16) != 0, BSX_DBG_ENV("BSX_F32_INPUT") == nullptr, arch ? arch : "gfx950", &scode, &scached, &sbytes);
-      char sm[256];
-      if (se.empty()) {
+      if (!b.seg.code.empty()) {
         long worst = 0;
-        for (const char* k : {"bsx_seg_head", "bsx_seg_k2", "bsx_seg_k3", "bsx_seg_tail"}) worst = std::max(worst, code_object_scratch_bytes(scode, k));
-        snprintf(sm, sizeof sm, "; segment kernels %s (%zu bytes of source, %zu bytes of code object, %ld B of scratch)", scached ? "cached" : "compiled", sbytes, scode.size(), worst);
+        for (const char* k : {"bsx_seg_head", "bsx_seg_k2", "bsx_seg_k3", "bsx_seg_tail"}) worst = std::max(worst, code_object_scratch_bytes(b.seg.code, k));
+        char sm[256];
+        snprintf(sm, sizeof sm, "; segment kernels %s (%zu bytes of source, %zu bytes of code object, %ld B of scratch)", b.seg.cached ? "cached" : "compiled", b.seg.source.size(),
+                 b.seg.code.size(), worst);
         seg_msg = sm;
-      } else { seg_msg = "; segment kernels: " + se; if (se.find("hipRTC:") != std::string::npos) { snprintf(msg, cap, "%s", seg_msg.c_str()); return BSX_EMODEL; } }
+      } else {
+        seg_msg = "; segment kernels: " + b.seg.fallback;
+        if (b.seg.fallback.find("hipRTC:") != std::string::npos) { snprintf(msg, cap, "%s", seg_msg.c_str()); return BSX_EMODEL; }
+      }
     }
-    snprintf(msg, cap, "%s (%zu bytes of source, %zu bytes of code object, %ld B of scratch%s, cache %s)%s", mb.cached ? "cached" : "compiled", mb.source.size(), mb.code.size(), mb.scratch,
-             mb.opaque_tid ? ", lane indices re-derived per op" : "", rtc_cache_dir().c_str(), seg_msg.c_str());
+    snprintf(msg, cap, "%s (%zu bytes of source, %zu bytes of code object, %ld B of scratch%s, cache %s)%s", b.mid.cached ? "cached" : "compiled", b.mid.source.size(),
+             b.mid.code.size(), b.scratch, b.opaque_tid ? ", lane indices re-derived per op" : "", rtc_cache_dir().c_str(), seg_msg.c_str());
     return BSX_OK;
   } catch (...) { snprintf(msg, cap, "exception while reading the model"); return BSX_EMODEL; }
 }

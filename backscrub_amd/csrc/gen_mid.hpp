@@ -11,7 +11,7 @@ namespace bsx {
 // act16: the 16-bit activation storage mode — every activation tensor of the program that lives in the arena is read / written as packed halves
 // (the segment kernels either side are launched with h16 = true to match).
 // opaque_tid: the form in which no lane-derived value outlives its op (mid_prelude.hip: tid_now) — fewer registers, a few more instructions per op; chosen by
-// build_mid_kernel (bsx_api.hip) where the plain form spills.
+// build_mid (specialised.cpp) where the plain form spills.
 std::string generate_mid_source(const Plan& plan, std::string* why, bool act16 = false, bool opaque_tid = false);
 
 // which ops of plan.program the generator fuses / chunks (shared with the planner's cost model, plan.cpp)

@@ -50,14 +50,15 @@ hipError_t launch_frame_program(const MicroOp* d_ops, int n_ops, int lds_floats,
 // Spatially-parallel segment kernels around the per-frame program (kernels_seg.hip, segments.hpp)
 hipError_t seg_prepare();
 hipError_t nn_prepare();          // dynamic-LDS limits of the fused per-launch kernels (kernels_nn.hip), for the current device
-hipError_t launch_seg_head(const SegHead& d, float* arena, long per_frame, const void* net_in, const float* weights, int n, hipStream_t s, bool h16 = false, bool u8 = false,
-                           float in_scale = 0.f, float in_offset = 0.f);
-hipError_t launch_seg_k2(const SegK2& d, float* arena, long per_frame, const float* weights, int n, hipStream_t s, bool h16 = false);
-hipError_t launch_seg_k3(const SegK3& d, float* arena, long per_frame, const float* weights, int n, hipStream_t s, bool h16 = false);
-// logits = true: write the network output tensor (debug / stage tests); false: decode + temporal IIR straight into `ofinal`
+// fn: the graph-specialised kernel (specialised.hpp) or nullptr for the ahead-of-time instance; grid, block, dynamic LDS and arguments are the same either way
+hipError_t launch_seg_head(hipFunction_t fn, const SegHead& d, float* arena, long per_frame, const void* net_in, const float* weights, int n, hipStream_t s, bool h16, bool u8,
+                           float in_scale, float in_offset);
+hipError_t launch_seg_k2(hipFunction_t fn, const SegK2& d, float* arena, long per_frame, const float* weights, int n, hipStream_t s, bool h16);
+hipError_t launch_seg_k3(hipFunction_t fn, const SegK3& d, float* arena, long per_frame, const float* weights, int n, hipStream_t s, bool h16);
 hipError_t launch_seg_gate(const SegGate& gt, float* arena, long per_frame, const float* weights, long long out_off, int n, hipStream_t s);
-hipError_t launch_seg_tail(const SegTail& d, float* arena, long per_frame, float* net_out, uint8_t* ofinal, const float* weights, bool logits, int n, hipStream_t s, bool h16 = false,
-                           const int* slot_of = nullptr);
+// logits = true: write the network output tensor (debug / stage tests; ahead of time only); false: decode + temporal IIR straight into `ofinal`
+hipError_t launch_seg_tail(hipFunction_t fn, const SegTail& d, float* arena, long per_frame, float* net_out, uint8_t* ofinal, const float* weights, bool logits, int n,
+                           hipStream_t s, bool h16, const int* slot_of);
 
 // ---- image path ----------------------------------------------------------------------
 // slot_of (every launch below that reads or writes per-stream state: the model-resolution temporal state `ofinal` and the persistent full-frame masks):

@@ -28,6 +28,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "kernels.hpp"
 #include "mfma_tile.hpp"
@@ -854,9 +855,32 @@ __global__ __launch_bounds__(kSegThreads) void seg_gate_k(const SegGate gt, floa
   if (threadIdx.x < 16) fa[out_off + threadIdx.x] = seg_smem[kScrGate + threadIdx.x];
 }
 
-template <class K>
-hipError_t allow_lds(K kernel, int lds_bytes) {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+// The ahead-of-time instance of each segment kernel for a variant: run-time flags to template arguments (pick), one function per kernel.  The graph-specialised
+// kernels of gen_seg.cpp are the same code with the descriptor and these arguments as constants.  The nesting and the polarity of the flags fix the order in which
+// the instances are instantiated, and with it their order in the code object: it is the order of the list of instances these functions replaced.
+template <class F> const void* pick(bool b, F f) { return !b ? f(std::false_type{}) : f(std::true_type{}); }
+template <class K> const void* kernel_ptr(K k) { return reinterpret_cast<const void*>(k); }
+const void* seg_head_instance(bool hswish, bool h16, bool u8) {
+  return pick(u8, [&](auto U) { return pick(h16, [&](auto H) { return pick(!hswish, [&](auto PLAIN) { return kernel_ptr(seg_head_k<!PLAIN, H, U>); }); }); });
+}
+const void* seg_k2_instance(bool h16) { return pick(h16, [](auto H) { return kernel_ptr(seg_k2_k<H>); }); }
+const void* seg_k3_instance(bool h16) { return pick(h16, [](auto H) { return kernel_ptr(seg_k3_k<H>); }); }
+// outputs: 2 channels (Meet), 1 channel with or without a sigmoid (MLKit); nullptr for any other
+const void* seg_tail_instance(int co, bool sigmoid, bool logits, bool h16) {
+  if (co != 1 && co != 2) return nullptr;
+  return pick(h16, [&](auto H) { return pick(co == 2, [&](auto C2) { return pick(!sigmoid, [&](auto LINEAR) { return pick(logits, [&](auto L) -> const void* {
+    if constexpr (C2 && !LINEAR) return nullptr;
+    else return kernel_ptr(seg_tail_k<C2 ? 2 : 1, L, !LINEAR, H>);
+  }); }); }); });
+}
+
+// One launch of a segment kernel: the graph-specialised function `fn` when there is one, else the ahead-of-time instance `aot`.  Grid, block, dynamic LDS and the
+// argument list are the same either way.
+hipError_t seg_launch(hipFunction_t fn, const void* aot, int tiles, int n, size_t lds, hipStream_t s, void** args) {
+  const unsigned grid = (unsigned)tiles * (unsigned)n;
+  if (fn) return hipModuleLaunchKernel(fn, grid, 1, 1, kSegThreads, 1, 1, (unsigned)lds, s, args, nullptr);
+  if (!aot) return hipErrorInvalidValue;
+  return hipLaunchKernel(aot, dim3(grid), dim3(kSegThreads), args, lds, s);
 }
 #endif
 
@@ -866,78 +890,54 @@ hipError_t allow_lds(K kernel, int lds_bytes) {
 hipError_t seg_prepare() {
   const int full = 160 * 1024;     // process-global kernel attributes: always the full LDS (cf. frame_program_prepare)
   hipError_t e = hipSuccess;
-  auto one = [&](auto k) { if (e == hipSuccess) e = allow_lds(k, full); };
-  one(seg_head_k<true, false, false>); one(seg_head_k<false, false, false>); one(seg_head_k<true, true, false>); one(seg_head_k<false, true, false>);
-  one(seg_head_k<true, false, true>); one(seg_head_k<false, false, true>); one(seg_head_k<true, true, true>); one(seg_head_k<false, true, true>);
-  one(seg_k2_k<false>); one(seg_k2_k<true>); one(seg_k3_k<false>); one(seg_k3_k<true>);
-  one(seg_tail_k<1, false, true, false>); one(seg_tail_k<1, true, true, false>); one(seg_tail_k<1, false, false, false>); one(seg_tail_k<1, true, false, false>);
-  one(seg_tail_k<2, false, false, false>); one(seg_tail_k<2, true, false, false>);
-  one(seg_tail_k<1, false, true, true>); one(seg_tail_k<1, true, true, true>); one(seg_tail_k<1, false, false, true>); one(seg_tail_k<1, true, false, true>);
-  one(seg_tail_k<2, false, false, true>); one(seg_tail_k<2, true, false, true>);
+  auto one = [&](const void* k) { if (e == hipSuccess && k) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, full); };
+  for (bool h16 : {false, true}) {
+    for (bool hs : {false, true}) for (bool u8 : {false, true}) one(seg_head_instance(hs, h16, u8));
+    one(seg_k2_instance(h16));
+    one(seg_k3_instance(h16));
+    for (int co : {1, 2}) for (bool sig : {false, true}) for (bool logits : {false, true}) one(seg_tail_instance(co, sig, logits, h16));
+  }
   return e;
 }
 
 // n_frames = 0 tells xcd_frame_tile to keep the plain (frame-major) workgroup order: BSX_XCD_TILES=0, read once per process, for A/B timing
 static int xcd_frames(int n) { static const bool on = !(BSX_DBG_ENV("BSX_XCD_TILES") && atoi(BSX_DBG_ENV("BSX_XCD_TILES")) == 0); return on ? n : 0; }
 
+// fn: the graph-specialised kernel (specialised.hpp), or nullptr for the ahead-of-time instance of the variant.
 // h16: the boundary tensors are stored as halves (BSX_ACT16; the middle program must have been generated for the same storage)
 // u8: net_in points at the 8-bit network input ([n][H0][W0] u32 pixels, prep_fused_k<2>) and (scale, offset) is the model's normalisation
-hipError_t launch_seg_head(const SegHead& d, float* arena, long per_frame, const void* net_in, const float* weights, int n, hipStream_t s, bool h16, bool u8, float in_scale,
-                           float in_offset) {
-  const dim3 grid((unsigned)(d.tiles_y * d.tiles_x) * (unsigned)n);
-  const size_t lds = (size_t)d.lds_floats * sizeof(float);
-  const bool hs = d.stem.act == kActHswish;
-  const float* in = static_cast<const float*>(net_in);
+hipError_t launch_seg_head(hipFunction_t fn, const SegHead& d, float* arena, long per_frame, const void* net_in, const float* weights, int n, hipStream_t s, bool h16, bool u8,
+                           float in_scale, float in_offset) {
   if (u8 && 2 * (2 * d.TC + 1) + 1 > 64) return hipErrorInvalidValue;          // one lane per pixel of an input-tile row (the planner's TC <= 15)
-#define BSX_HEAD(HS, H, U) seg_head_k<HS, H, U><<<grid, kSegThreads, lds, s>>>(d, arena, per_frame, in, weights, in_scale, in_offset, xcd_frames(n))
-  if (hs) { if (h16) { if (u8) BSX_HEAD(true, true, true); else BSX_HEAD(true, true, false); } else { if (u8) BSX_HEAD(true, false, true); else BSX_HEAD(true, false, false); } }
-  else { if (h16) { if (u8) BSX_HEAD(false, true, true); else BSX_HEAD(false, true, false); } else { if (u8) BSX_HEAD(false, false, true); else BSX_HEAD(false, false, false); } }
-#undef BSX_HEAD
-  return hipGetLastError();
+  const float* in = static_cast<const float*>(net_in);
+  int nf = xcd_frames(n);
+  void* args[] = {(void*)&d, &arena, &per_frame, &in, &weights, &in_scale, &in_offset, &nf};
+  return seg_launch(fn, seg_head_instance(d.stem.act == kActHswish, h16, u8), d.tiles_y * d.tiles_x, n, (size_t)d.lds_floats * sizeof(float), s, args);
 }
-hipError_t launch_seg_k2(const SegK2& d, float* arena, long per_frame, const float* weights, int n, hipStream_t s, bool h16) {
-  const dim3 grid((unsigned)(d.tiles_y * d.tiles_x) * (unsigned)n);
-  if (h16) seg_k2_k<true><<<grid, kSegThreads, (size_t)d.lds_floats * sizeof(float), s>>>(d, arena, per_frame, weights, xcd_frames(n));
-  else seg_k2_k<false><<<grid, kSegThreads, (size_t)d.lds_floats * sizeof(float), s>>>(d, arena, per_frame, weights, xcd_frames(n));
-  return hipGetLastError();
+hipError_t launch_seg_k2(hipFunction_t fn, const SegK2& d, float* arena, long per_frame, const float* weights, int n, hipStream_t s, bool h16) {
+  int nf = xcd_frames(n);
+  void* args[] = {(void*)&d, &arena, &per_frame, &weights, &nf};
+  return seg_launch(fn, seg_k2_instance(h16), d.tiles_y * d.tiles_x, n, (size_t)d.lds_floats * sizeof(float), s, args);
 }
-hipError_t launch_seg_k3(const SegK3& d, float* arena, long per_frame, const float* weights, int n, hipStream_t s, bool h16) {
-  const dim3 grid((unsigned)(d.tiles_y * d.tiles_x) * (unsigned)n);
-  if (h16) seg_k3_k<true><<<grid, kSegThreads, (size_t)d.lds_floats * sizeof(float), s>>>(d, arena, per_frame, weights, xcd_frames(n));
-  else seg_k3_k<false><<<grid, kSegThreads, (size_t)d.lds_floats * sizeof(float), s>>>(d, arena, per_frame, weights, xcd_frames(n));
-  return hipGetLastError();
+hipError_t launch_seg_k3(hipFunction_t fn, const SegK3& d, float* arena, long per_frame, const float* weights, int n, hipStream_t s, bool h16) {
+  int nf = xcd_frames(n);
+  void* args[] = {(void*)&d, &arena, &per_frame, &weights, &nf};
+  return seg_launch(fn, seg_k3_instance(h16), d.tiles_y * d.tiles_x, n, (size_t)d.lds_floats * sizeof(float), s, args);
 }
-template <bool H16>
-static hipError_t launch_seg_tail_t(const SegTail& d, float* arena, long per_frame, float* net_out, uint8_t* ofinal, const float* weights, bool logits, int n, hipStream_t s,
-                                    const int* slot_of) {
-  const dim3 grid((unsigned)(d.tiles_y * d.tiles_x) * (unsigned)n);
+// logits: the stage-debug variant, ahead of time only (the specialised tail is the decode-fused one)
+hipError_t launch_seg_tail(hipFunction_t fn, const SegTail& d, float* arena, long per_frame, float* net_out, uint8_t* ofinal, const float* weights, bool logits, int n,
+                           hipStream_t s, bool h16, const int* slot_of) {
   // BSX_SEG_TAIL_WGS=<k> (experiment switch, read once): pad the dynamic LDS so that at most k workgroups fit a CU — the A/B of the tail's 5th workgroup (round 5)
   static const int wgs_cap = BSX_DBG_ENV("BSX_SEG_TAIL_WGS") ? atoi(BSX_DBG_ENV("BSX_SEG_TAIL_WGS")) : 0;
   size_t lds = (size_t)d.lds_floats * sizeof(float);
   if (wgs_cap > 0) lds = std::max(lds, (size_t)(160 * 1024 / (wgs_cap + 1) + 256));
-  const bool sig = d.act3 == kActSigmoid;
-  if (d.Co == 2 && !sig) {
-    if (logits) seg_tail_k<2, true, false, H16><<<grid, kSegThreads, lds, s>>>(d, arena, per_frame, net_out, ofinal, weights, xcd_frames(n), slot_of);
-    else seg_tail_k<2, false, false, H16><<<grid, kSegThreads, lds, s>>>(d, arena, per_frame, net_out, ofinal, weights, xcd_frames(n), slot_of);
-  } else if (d.Co == 1 && sig) {
-    if (logits) seg_tail_k<1, true, true, H16><<<grid, kSegThreads, lds, s>>>(d, arena, per_frame, net_out, ofinal, weights, xcd_frames(n), slot_of);
-    else seg_tail_k<1, false, true, H16><<<grid, kSegThreads, lds, s>>>(d, arena, per_frame, net_out, ofinal, weights, xcd_frames(n), slot_of);
-  } else if (d.Co == 1) {
-    if (logits) seg_tail_k<1, true, false, H16><<<grid, kSegThreads, lds, s>>>(d, arena, per_frame, net_out, ofinal, weights, xcd_frames(n), slot_of);
-    else seg_tail_k<1, false, false, H16><<<grid, kSegThreads, lds, s>>>(d, arena, per_frame, net_out, ofinal, weights, xcd_frames(n), slot_of);
-  } else {
-    return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  int nf = xcd_frames(n);
+  void* args[] = {(void*)&d, &arena, &per_frame, &net_out, &ofinal, &weights, &nf, &slot_of};
+  return seg_launch(logits ? nullptr : fn, seg_tail_instance(d.Co, d.act3 == kActSigmoid, logits, h16), d.tiles_y * d.tiles_x, n, lds, s, args);
 }
 hipError_t launch_seg_gate(const SegGate& gt, float* arena, long per_frame, const float* weights, long long out_off, int n, hipStream_t s) {
   seg_gate_k<<<n, kSegThreads, (size_t)(kSegScratchFloats + kSegGateStageFloats) * sizeof(float), s>>>(gt, arena, per_frame, weights, out_off);
   return hipGetLastError();
-}
-hipError_t launch_seg_tail(const SegTail& d, float* arena, long per_frame, float* net_out, uint8_t* ofinal, const float* weights, bool logits, int n, hipStream_t s, bool h16,
-                           const int* slot_of) {
-  return h16 ? launch_seg_tail_t<true>(d, arena, per_frame, net_out, ofinal, weights, logits, n, s, slot_of)
-             : launch_seg_tail_t<false>(d, arena, per_frame, net_out, ofinal, weights, logits, n, s, slot_of);
 }
 
 #endif

@@ -62,7 +62,7 @@ typedef __attribute__((address_space(1))) _Float16 glb_h;
 // whole straight-line kernel by common-subexpression elimination.  Left alone the compiler carries dozens of such values through the 100-register depthwise
 // bodies: MLKit's kernel sat at 128 registers with 352 bytes of scratch, stores in the first ops and loads all the way down; opaque it needs 92 registers and
 // none (round 6: middle kernel -3.5 %).  Where nothing spills the shared values are free and recomputing them only costs issue slots (segm_lite: +6 %), so the
-// choice is made per graph from the scratch size of the compiled code object (bsx_api.hip: build_mid_kernel).
+// choice is made per graph from the scratch size of the compiled code object (specialised.cpp: build_mid).
 #ifdef BSXM_OPAQUE_TID
 __device__ __forceinline__ int tid_now() { int t = (int)threadIdx.x; asm volatile("" : "+v"(t)); return t; }
 #else

@@ -137,34 +137,16 @@ long code_object_scratch_bytes(const std::vector<char>& code, const char* kernel
       const uint64_t name = u32(off + s), value = u64(off + s + 8);
       if (name >= strsize || strsize - name <= want.size()) continue;
       if (memcmp(p + stroff + name, want.c_str(), want.size() + 1) != 0) continue;
-      for (uint64_t j = 0; j < shnum; j++) {                        // the section that holds the descriptor
-        const uint64_t addr = u64(sh(j, 0x10)), so = u64(sh(j, 0x18)), ss = u64(sh(j, 0x20)), st = u32(sh(j, 4));
-        if (st == 8 || value < addr || value - addr + 64 > ss) continue;      // (SHT_NOBITS has no bytes)
-        const uint64_t fo = so + (value - addr);
-        if (fo + 8 > N) return -1;
-        return (long)u32(fo + 4);
+      for (uint64_t j = 0; j < shnum; j++) {                        // the section that holds the descriptor: SHT_PROGBITS with SHF_ALLOC
+        const uint64_t st = u32(sh(j, 4)), flags = u64(sh(j, 8)), addr = u64(sh(j, 0x10)), so = u64(sh(j, 0x18)), ss = u64(sh(j, 0x20));
+        if (st != 1 || !(flags & 2) || value < addr || value - addr + 64 > ss) continue;
+        if (so > N || N - so < 8 || value - addr > N - so - 8) return -1;
+        return (long)u32(so + (value - addr) + 4);
       }
       return -1;
     }
   }
   return -1;
-}
-
-hipError_t rtc_load(const std::vector<char>& code, const char* kernel, RtcKernel* out) {
-  hipError_t e = hipModuleLoadData(&out->mod, code.data());
-  if (e != hipSuccess) return e;
-  e = hipModuleGetFunction(&out->fn, out->mod, kernel);
-  if (e != hipSuccess) { (void)hipModuleUnload(out->mod); out->mod = nullptr; out->fn = nullptr; }
-  return e;
-}
-
-hipError_t rtc_function(const RtcKernel& loaded, const char* kernel, hipFunction_t* fn) {
-  if (!loaded.mod) return hipErrorInvalidValue;
-  return hipModuleGetFunction(fn, loaded.mod, kernel);
-}
-
-void rtc_unload(RtcKernel* k) {
-  if (k && k->mod) { (void)hipModuleUnload(k->mod); k->mod = nullptr; k->fn = nullptr; }
 }
 
 }  // namespace bsx

@@ -125,8 +125,12 @@ void __hipRegisterFunction(void** modules, const void* host_fn, char* device_fn,
 }
 hipError_t hipModuleLoadData(hipModule_t* m, const void*) { *m = (hipModule_t)handle(); own(*m); logf("hipModuleLoadData", "affine"); return hipSuccess; }
 hipError_t hipModuleUnload(hipModule_t m) { use("hipModuleUnload", m); disown(m); free(m); logf("hipModuleUnload", "affine"); return hipSuccess; }
+// BSX_STUB_NO_FUNCTION=<kernel>: that kernel is missing from every module (a code object that lacks one symbol)
 hipError_t hipModuleGetFunction(hipFunction_t* f, hipModule_t m, const char* name) {
-  use("hipModuleGetFunction", m); *f = (hipFunction_t)handle(); own(*f);
+  use("hipModuleGetFunction", m);
+  const char* missing = getenv("BSX_STUB_NO_FUNCTION");
+  if (missing && strcmp(missing, name) == 0) { logf("hipModuleGetFunction", "affine", name); return hipErrorNotFound; }
+  *f = (hipFunction_t)handle(); own(*f);
   { std::lock_guard<std::mutex> l(g_mu); g_kernel[*f] = name; }
   logf("hipModuleGetFunction", "affine");
   return hipSuccess;

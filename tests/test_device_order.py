@@ -85,3 +85,42 @@ def test_the_interposer_catches_a_violation(stub, tmp_path):
     subprocess.check_call([sys.executable, "-c", code], env=dict(os.environ, BSX_STUB_LOG=log))
     txt = open(log).read()
     assert "MISMATCH hipStreamSynchronize 1 owner=0" in txt
+
+
+def test_a_segment_code_object_that_lacks_one_kernel_is_not_used_at_all(stub, tmp_path):
+    """The four specialised segment kernels are loaded all or none (specialised.cpp: load_specialised).  With bsx_seg_k3 missing from the code object the module is
+    unloaded while the context is created, plan() says so, and every segment launch of a step is the ahead-of-time kernel — none goes to a function of the unloaded
+    module."""
+    log = str(tmp_path / "hip.log")
+    code = ("import ctypes as C, json, os, sys\n"
+            "import numpy as np\n"
+            "sys.path.insert(0, %r)\n"
+            "from backscrub_amd import api\n"
+            "L = C.CDLL(api.lib_path())\n"
+            "for name, res, args in api.SYMBOLS:\n"
+            "    f = getattr(L, name); f.restype, f.argtypes = res, args\n"
+            "lines = lambda: sum(1 for _ in open(os.environ['BSX_STUB_LOG']))\n"
+            "W, H, n = 640, 480, 2\n"
+            "ctx = L.bsx_new(%r.encode(), 2, W, H, n, 0, api.DEBUG_FN(), api.STAGE_FN(), api.STAGE_FN(), api.STAGE_FN(), None)\n"
+            "plan = L.bsx_plan_describe(ctx).decode()\n"
+            "frames, bg, out = np.zeros((n, H, W, 3), np.uint8), np.zeros((H, W, 3), np.uint8), np.zeros((n, H, W, 3), np.uint8)\n"
+            "p = lambda a: C.c_void_p(a.ctypes.data)\n"
+            "a = lines()\n"
+            "rc = L.bsx_step_batch(ctx, p(frames), p(bg), 0, p(out), n, None)\n"
+            "b = lines()\n"
+            "L.bsx_delete(ctx)\n"
+            "print(json.dumps({'plan': plan, 'rc': rc, 'step': [a, b]}))\n" % (ROOT, model_path("lite")))
+    env = dict(os.environ, LD_PRELOAD=stub, BSX_STUB_LOG=log, BSX_STUB_NDEV="1", BSX_STUB_NO_FUNCTION="bsx_seg_k3")
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["rc"] == 0
+    assert "segment execution: ahead-of-time kernels (code object did not load)\n" in d["plan"], d["plan"]
+    assert "program execution: specialised kernel" in d["plan"]                   # the middle kernel's module is another one, and loaded
+    lines = [l.split() for l in open(log).read().splitlines() if l.strip()]
+    created = [l[1] for l in lines[:d["step"][0]] if l[0] == "affine"]
+    assert created.count("hipModuleLoadData") == 2 and created.count("hipModuleUnload") == 1     # the segment module, unloaded at once
+    step = [l for l in lines[d["step"][0]:d["step"][1]] if l[0] == "affine" and l[1] in ("hipLaunchKernel", "hipModuleLaunchKernel")]
+    assert [l[3] for l in step if l[1] == "hipModuleLaunchKernel"] == ["bsx_mid"]
+    seg = [k for k in ("seg_head_k", "seg_k2_k", "seg_k3_k", "seg_tail_k") for l in step if l[1] == "hipLaunchKernel" and k in l[3]]
+    assert seg == ["seg_head_k", "seg_k2_k", "seg_k3_k", "seg_tail_k"], step

@@ -20,7 +20,7 @@ def api():
 
 
 # scratch bytes tolerated per architecture: NONE since round 6.  Rounds 3-5 tolerated 512 / 1088 bytes for segm_full / MLKit: their kernels sat
-# at 126-128 registers because the compiler kept every lane-derived value alive across the whole straight-line kernel; build_mid_kernel (bsx_api.hip) now compiles the
+# at 126-128 registers because the compiler kept every lane-derived value alive across the whole straight-line kernel; build_mid (specialised.cpp) now compiles the
 # form in which each op re-derives its lane indices wherever the plain form spills, and takes it if it spills less (MLKit: 352 -> 0 bytes, 128 -> 92 registers).
 SCRATCH_LIMIT = {"lite": 0, "full": 0, "mlkit": 0}
 
@@ -222,7 +222,7 @@ def test_zero_cell_of_the_middle_kernel(api, key, monkeypatch, debug_switches):
 
 
 def test_the_form_of_the_middle_kernel_is_chosen_by_its_scratch_size(api, monkeypatch, debug_switches):
-    """build_mid_kernel (bsx_api.hip): the plain form first; where its code object reports scratch (kernel descriptor bytes 4-7, read from the ELF by
+    """build_mid (specialised.cpp): the plain form first; where its code object reports scratch (kernel descriptor bytes 4-7, read from the ELF by
     rtc.cpp: code_object_scratch_bytes — no GPU), the form with the lane index behind an opaque asm is compiled too and taken if it spills less.  segm_lite and
     segm_full do not spill and keep the plain form (recomputing shared values costs them issue slots: profiles/r06g); MLKit's plain form spills 352 bytes, its
     opaque form none.  The forced forms of the debug build show the parser reads real values."""
@@ -265,3 +265,47 @@ def test_segment_kernels_specialised_to_the_graph_compile_within_their_budgets(a
     msg = api.model_precompile(model_path(key))
     assert re.search(r"segment kernels (compiled|cached) \(\d+ bytes of source, \d+ bytes of code object, 0 B of scratch\)", msg), msg
     assert api.model_seg_source(model_path("deeplab")) == ""                                          # per-launch path: no segment kernels
+
+
+def test_the_specialised_segment_kernels_carry_the_work_skipping_fields(api, monkeypatch, debug_switches):
+    """The specialised segment kernels are the ahead-of-time ones with the descriptor as constants — the debug build's work-skipping fields included (gen_seg.cpp:
+    seg_constants_text).  BSX_SEG_SKIP=head,k2,k3,tail appears as each descriptor's dbg_skip and BSX_SEG_GATE_SKIP as the gates' timing_skip; without them the text
+    has no dbg_skip line at all, as in the release build."""
+    plain = api.model_seg_source(model_path("lite"))
+    assert "t.dbg_skip" not in plain and "timing_skip = 1" not in plain
+    monkeypatch.setenv("BSX_SEG_SKIP", "1,2,4,8")
+    monkeypatch.setenv("BSX_SEG_GATE_SKIP", "1")
+    src = api.model_seg_source(model_path("lite"))
+    for name, v in (("HEAD", 1), ("K2", 2), ("K3", 4), ("TAIL", 8)):
+        block = src[src.index("kSeg%s = [] {" % name):]
+        block = block[:block.index("return t; }();")]
+        assert "  t.dbg_skip = %d;\n" % v in block, name
+    assert src.count("t.gate.timing_skip = 1;") == 2
+
+
+def test_a_kernel_descriptor_outside_the_cached_file_reads_as_unknown_scratch(api, tmp_path, monkeypatch):
+    """rtc.cpp: code_object_scratch_bytes walks a file from a user-writable cache.  A section header whose offset puts the kernel descriptor past the end of the file
+    (here: 4 bytes short of 2**64, so that offset + 8 wraps round to the start of the file) gives -1 bytes of scratch, not a value read from elsewhere in the file."""
+    import struct
+    monkeypatch.setenv("BSX_KERNEL_CACHE", str(tmp_path))
+    assert " 0 B of scratch" in api.model_precompile(model_path("lite"))
+    mid = [f for f in tmp_path.iterdir() if f.suffix == ".hsaco" and b"bsx_mid.kd" in f.read_bytes()]
+    assert len(mid) == 1
+    elf = bytearray(mid[0].read_bytes())
+    shoff, = struct.unpack_from("<Q", elf, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", elf, 0x3A)
+    sh = [struct.unpack_from("<IIQQQQIIQQ", elf, shoff + i * shentsize) for i in range(shnum)]      # name type flags addr offset size link info align entsize
+    value = None
+    for s in sh:
+        if s[1] == 2:                                                                # SHT_SYMTAB
+            strtab = sh[s[6]]
+            for o in range(s[4], s[4] + s[5], 24):
+                name, = struct.unpack_from("<I", elf, o)
+                if elf[strtab[4] + name:].startswith(b"bsx_mid.kd\0"):
+                    value, = struct.unpack_from("<Q", elf, o + 8)
+    assert value is not None
+    j = next(i for i, s in enumerate(sh) if s[1] == 1 and s[2] & 2 and s[3] <= value < s[3] + s[5])
+    struct.pack_into("<Q", elf, shoff + j * shentsize + 0x18, (-(value - sh[j][3]) - 4) % (1 << 64))
+    mid[0].write_bytes(bytes(elf))
+    msg = api.model_precompile(model_path("lite"))
+    assert msg.startswith("cached") and " -1 B of scratch" in msg, msg

@@ -25,7 +25,7 @@ MODELS = {"lite": os.path.join(REF_MODELS, "segm_lite_v681.tflite"), "full": os.
           "mlkit": os.path.join(REF_MODELS, "selfiesegmentation_mlkit-256x256-2021_01_19-v1215.f16.tflite"), "deeplab": None}    # None: the synthetic DeepLab
 GEOMETRIES = [(640, 480), (1280, 720), (642, 480)]          # the last one: width % 4 != 0, the fused tile kernel does not apply
 SWITCHES = ["BSX_NO_MASK_BLEND_FUSION", "BSX_NO_BGBLUR_FUSION", "BSX_NO_MASK_TILE", "BSX_LANES=2", "BSX_LANES=4", "BSX_KEEP_LOGITS", "BSX_NO_RTC",
-            "BSX_NO_SEGMENTS", "BSX_NO_FRAME_PROGRAM", "BSX_VCAM_DIRECT"]
+            "BSX_NO_SEGMENTS", "BSX_NO_FRAME_PROGRAM", "BSX_VCAM_DIRECT", "BSX_NO_SEG_RTC"]
 
 YUYV, FH, FV, NOMASK, YIN = 1, 2, 4, 8, 16
 
