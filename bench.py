@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py — composited frames/s of the backscrub hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full]
+
+A plain run does only what the headline figure needs: it sets up, ramps the clocks, warms up, times the K steps, writes --dump-outputs and prints
+the line.  --full then measures and checks everything else, as described below: per-launch profile and roofline, parity with the CPU oracle, the
+side probes, the CPU baseline, the other BASELINE configurations and opt-in modes (and at N > 1 rank 0 alone, configs[4] and the second device).
 
 With --gpus N > 1 and no WORLD_SIZE in the environment the script re-executes itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` (one rank per GPU, RCCL);
@@ -124,7 +128,13 @@ def parse():
                     "(rank 0's composites and masks) to DIR/composite.npy and DIR/mask.npy as float32, at most 60 MB in all (a fixed, seeded sample of the streams "
                     "when the batch is larger) — with the same arguments the inputs are the same bytes every run, so two builds compare output for output")
     ap.add_argument("--selftest-dist", action="store_true", help="CPU plumbing test of the multi-process path (gloo): launch, rendezvous, counter all-reduce, JSON line — no GPU work")
+    ap.add_argument("--full", action="store_true", help="after the headline figure, measure and check everything else: per-launch profile and roofline, twin-stream and "
+                    "oracle parity checks, the side probes, the CPU baseline, the other BASELINE configurations and opt-in modes, single-stream latency; at N > 1 "
+                    "also rank 0 alone, the configs[4] slice and the second-device check.  Without it a run sets up, warms up, times the steps, writes "
+                    "--dump-outputs and prints the line; the --no-* switches, --cpu-seconds and --profile-iters then have nothing to act on")
     a = ap.parse_args()
+    if a.dump_launches and not a.full:
+        ap.error("--dump-launches writes the per-launch profile, which only a --full run takes")
     return a
 
 
@@ -983,11 +993,11 @@ def selftest_dist(args):
                 "rank_fps": rank_fps, "frames": frames, "elapsed_max": max_elapsed, "checksum": checksum}
     a, b = shard_streams(args.batch * world, world, rank)
     n4 = max(3, args.steps // 4)
-    # the same order of solo runs, barriers and collectives as main()
-    solo1 = solo_reference(coll, rank, lambda: fake(b - a, args.width, args.height, NAMES["lite"], args.steps, 1.0, None)["fps"]) if world > 1 else None
+    # the same order of solo runs, barriers and collectives as main(): a plain run has the main leg alone
+    solo1 = solo_reference(coll, rank, lambda: fake(b - a, args.width, args.height, NAMES["lite"], args.steps, 1.0, None)["fps"]) if world > 1 and args.full else None
     main = fake(b - a, args.width, args.height, NAMES["lite"], args.steps, 1.0, coll)
-    solo4 = solo_reference(coll, rank, lambda: fake(1024, 1280, 720, NAMES["full"], n4, 4.0, None)["fps"]) if world > 1 else None
-    c4 = fake(1024, 1280, 720, NAMES["full"], n4, 4.0, coll)
+    solo4 = solo_reference(coll, rank, lambda: fake(1024, 1280, 720, NAMES["full"], n4, 4.0, None)["fps"]) if world > 1 and args.full else None
+    c4 = fake(1024, 1280, 720, NAMES["full"], n4, 4.0, coll) if args.full else None
     line = None
     if rank == 0:
         line = {"metric": METRIC, "selftest": "dist", "value": main["fps"], "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -996,7 +1006,7 @@ def selftest_dist(args):
         line.update(multi_gpu_sections(coll, main, c4, solo1, solo4, world))
     coll.close()
     if rank == 0:
-        if not args.no_cpu_baseline:                      # kept at world > 1 (rank 0, after the other ranks have left)
+        if args.full and not args.no_cpu_baseline:        # kept at world > 1 (rank 0, after the other ranks have left)
             try:
                 path, _, _ = resolve_model(args.model)
                 line["cpu_baseline"] = cpu_baseline(path, args.width, args.height, args.cpu_seconds, short=True)
@@ -1102,9 +1112,9 @@ def main():
     W, H, B = args.width, args.height, args.batch
     moving = not args.static_scene
     default_job = (args.model, W, H, B) == ("lite", 640, 480, 256) and not args.per_stream_bg and not args.bg_ring
-    side = not args.no_side_probes
+    side = args.full and not args.no_side_probes
     solo1 = solo4 = None
-    if coll is not None:
+    if coll is not None and args.full:
         # rank 0 ALONE first (the others wait at the barrier): the N = 1 reference of this box, minutes — not runs — apart from the N-rank number
         def solo_main():
             r1 = measure(args.model, W, H, B, args.steps, args.warmup, 0, 1, local_rank, ramp_s=args.ramp_seconds, per_stream_bg=args.per_stream_bg, bg_ring=args.bg_ring,
@@ -1114,14 +1124,14 @@ def main():
             return fps
         solo1 = solo_reference(coll, rank, solo_main)
     res = measure(args.model, W, H, B, args.steps, args.warmup, rank, world, local_rank, ramp_s=args.ramp_seconds, per_stream_bg=args.per_stream_bg, bg_ring=args.bg_ring,
-                  profile_iters=args.profile_iters, dump_launches=args.dump_launches, coll=coll, moving=moving, static_leg=side, parity_streams=4,
+                  profile_iters=args.profile_iters, dump_launches=args.dump_launches, coll=coll, profile=args.full, moving=moving, static_leg=side, parity_streams=4,
                   dump_outputs=args.dump_outputs)
     multi = None
     c4_frag = c4_parity_in = None
     if coll is not None:
         main_leg = {k: res[k] for k in ("B", "W", "H", "model_name", "fps", "ms_per_step", "rank_fps")}
         c4 = None
-        if default_job and not args.no_extra_configs:
+        if args.full and default_job and not args.no_extra_configs:
             # the north-star job's per-GPU slice on EVERY rank: BASELINE configs[4] = 8192 x HD segm_full streams / 8 GPUs = 1024 per GPU
             n4 = max(20, args.steps // 4)
             kw4 = dict(model_key="full", W=1280, H=720, B=1024, moving=moving)
@@ -1169,11 +1179,16 @@ def main():
                         "static_scene": "the same batch every step (rounds 1-4's headline protocol): the uniform-tile shortcut's best case",
                         "worst_case": "BSX_NO_UNIFORM_TILES=1 and one random background image per stream, moving scene: every byte from HBM, every tile on the general path"},
     }
-    result.update({k: v for k, v in summarize(res, load_pmc(B, W, H, res["model_name"])).items() if k not in ("value", "unit", "ms_per_step", "steps", "warmup")})
     if multi is not None:
         result.update(multi)
         if shared:
             result["gpu_sharing"] = "%d ranks on %d GPU(s): throughput numbers of this line are a plumbing run, not a scaling measurement" % (world, n_dev)
+    result["detail_file"] = os.path.basename(args.detail) if args.detail else "bench_detail.json"
+    if not args.full:                                   # a plain run: the headline figure is all it measures
+        release(res)
+        emit(result, args.detail)
+        return
+    result.update({k: v for k, v in summarize(res, load_pmc(B, W, H, res["model_name"])).items() if k not in ("value", "unit", "ms_per_step", "steps", "warmup")})
     mg, ring, d_bg, d_out = res["mg"], res["frames_ring"], res["d_bg"], res["d_out"]
     d_frames = ring[0]
 
@@ -1470,7 +1485,6 @@ def main():
                                        "published_context_not_measured_here": "reference README.md:177 ~10 FPS DeepLab on two i5 cores; Meet model card ~120 FPS inference on a laptop CPU"}
         except Exception as e:  # noqa: BLE001
             result["single_stream"] = {"error": repr(e)}
-    result["detail_file"] = os.path.basename(args.detail) if args.detail else "bench_detail.json"
     emit(result, args.detail)
 
 

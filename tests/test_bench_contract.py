@@ -1,6 +1,6 @@
-"""The JSON line bench.py prints is a contract with the driver (task statement, ④).  On a GPU box the test RUNS bench.py (short: 3 steps,
-a 2-second CPU baseline sample, no extra configurations) and validates the fresh line field by field; without a GPU only the argument
-handling and the multi-process plumbing can run (tests/test_dist_gloo.py covers the latter)."""
+"""The JSON line bench.py prints is a contract with the driver (task statement, ④).  On a GPU box the tests RUN bench.py — a plain run, and a --full
+run (short: 3 steps, a 2-second CPU baseline sample, no extra configurations) — and validate the fresh lines field by field; without a GPU only the
+argument handling and the multi-process plumbing can run (tests/test_dist_gloo.py covers the latter)."""
 import json
 import os
 import subprocess
@@ -22,7 +22,7 @@ def test_bench_refuses_to_run_without_a_gpu():
 @pytest.mark.gpu
 def test_a_fresh_bench_line_has_the_contract_fields(tmp_path):
     detail = str(tmp_path / "detail.json")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--ramp-seconds", "0", "--no-extra-configs", "--cpu-seconds", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--ramp-seconds", "0", "--no-extra-configs", "--cpu-seconds", "2",
                         "--profile-iters", "1", "--detail", detail], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -67,6 +67,39 @@ def test_a_fresh_bench_line_has_the_contract_fields(tmp_path):
     assert full["cpu_baseline"]["parity_sample"]["oracle_mask_pixels_between_0_and_255_last_step"] > 0        # the moving scene leaves IIR transients for the comparison
     for t in full["top_launches"] + full["worst_case"]["top_launches"]:
         assert t["GBps"] <= 8000.0
+
+
+def test_dump_launches_needs_a_full_run():
+    """The per-launch table comes from the profile that only `--full` takes: a plain run refuses the option before it touches a GPU."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--dump-launches", os.devnull],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--full" in r.stderr
+
+
+@pytest.mark.gpu
+def test_a_plain_bench_run_times_the_steps_and_nothing_else(tmp_path):
+    """Without --full the run sets up, warms up, times the steps, writes --dump-outputs and prints the line: the contract keys mean what they do in a
+    --full run, and nothing that needs a run of its own (profile, parity, CPU baseline, side probes, other configurations) is in the record."""
+    import numpy as np
+    detail, dump = str(tmp_path / "detail.json"), str(tmp_path / "out")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--ramp-seconds", "0", "--detail", detail,
+                        "--dump-outputs", dump], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, "bench.py must print exactly ONE JSON line"
+    d = json.loads(lines[0])
+    base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
+    assert d["metric"] == base["metric"] and d["dtype"] == "f32 (network) / u8 (image kernels)"
+    assert d["unit"] == "frames/s" and d["higher_is_better"] is True and d["scaling"] == "weak" and d["vs_baseline"] is None
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["data"].startswith("synthetic")
+    assert abs(d["value"] - 256 * 1e3 / d["ms_per_step"]) / d["value"] < 0.01          # value = streams / step time
+    assert "segm_lite_v681" in d["config"]["workload"] and "batch=256" in d["config"]["workload"] and "moving scene" in d["config"]["workload"]
+    full = json.load(open(detail))
+    assert full["value"] == d["value"] and full["ms_per_step"] == d["ms_per_step"]
+    for k in ("roofline", "cpu_baseline", "host_io", "static_scene", "worst_case", "configs", "full_batch_twin_streams", "top_launches", "yuyv_out", "bgblur_step"):
+        assert full.get(k) is None, k
+    comp, mask = np.load(os.path.join(dump, "composite.npy")), np.load(os.path.join(dump, "mask.npy"))
+    assert comp.dtype == mask.dtype == np.float32 and comp.shape[1:] == (480, 640, 3) and mask.shape == comp.shape[:3] and 0 < comp.shape[0] <= 256
 
 
 def test_the_printed_line_stays_small():

@@ -100,7 +100,7 @@ def test_bench_self_launches_its_ranks():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--selftest-dist", "--batch", "8", "--steps", "5", "--cpu-seconds", "2"],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--selftest-dist", "--full", "--batch", "8", "--steps", "5", "--cpu-seconds", "2"],
                        env=env, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -119,6 +119,25 @@ def test_bench_self_launches_its_ranks():
     assert d["cpu_baseline"]["value"] > 0 and d["cpu_baseline"]["host"]["model"] and d["host"]["logical_cpus"] >= 1
 
 
+def test_a_plain_multi_rank_run_has_the_main_leg_alone():
+    """Without --full, N > 1 takes the main leg only: one collective run, its per-rank rates and counter reduction — no rank-0-alone reference, no configs[4]
+    slice, no CPU baseline."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--selftest-dist", "--batch", "8", "--steps", "5"],
+                       env=env, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["frames"] == 80.0 and abs(d["elapsed_max"] - 0.00625) < 1e-9 and d["checksum"] == 2001
+    assert d["ranks_seen"] == 2 and len(d["configs1"]["per_rank_fps"]) == 2 and abs(d["configs1"]["value"] - d["value"]) < 1e-6
+    assert "rank0_alone_fps" not in d["configs1"] and "configs4" not in d and "cpu_baseline" not in d
+
+
 def test_bench_walks_the_north_star_rank_count_world8():
     """BASELINE configs[4] is an 8-rank job (8192 HD streams / 8 GPUs).  No node with more than one GPU existed in any round, so the exact rank count is walked
     here on gloo: `bench.py --gpus 8 --selftest-dist` self-launches 8 ranks through torch.distributed.run on 127.0.0.1, every rank takes the same order of solo
@@ -130,7 +149,7 @@ def test_bench_walks_the_north_star_rank_count_world8():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["OMP_NUM_THREADS"] = "1"
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--selftest-dist", "--batch", "256", "--steps", "4", "--no-cpu-baseline"],
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--selftest-dist", "--full", "--batch", "256", "--steps", "4", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

@@ -7,9 +7,11 @@ for i in $(seq $R); do
   for spec in "$@"; do
     label=${spec%%=*}; rest=${spec#*=}; lib=${rest%%,*}; envs=""
     if [ "$rest" != "$lib" ]; then envs=$(echo ${rest#*,} | tr ',' ' '); fi
-    env $envs BSX_LIBRARY=$PWD/$lib python bench.py --model deeplab --batch 1024 --no-extra-configs --no-cpu-baseline --steps 10 --warmup 3 --dump-launches gpurun_out/launches_$label.txt 2>/dev/null | tail -1 | python -c "
+    launches=$(mktemp)
+    env $envs BSX_LIBRARY=$PWD/$lib python bench.py --full --model deeplab --batch 1024 --no-extra-configs --no-cpu-baseline --steps 10 --warmup 3 --dump-launches $launches 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read())
 print('$label', round(d['value']), d['ms_per_step'], d.get('parity_sample'))"
-    grep -E "${AB_GREP:-conv#64|conv#66-pool|conv#67}" gpurun_out/launches_$label.txt | grep " us " | sed 's/^/    /'
+    grep -E "${AB_GREP:-conv#64|conv#66-pool|conv#67}" $launches | grep " us " | sed 's/^/    /'
+    rm -f $launches
   done
 done
