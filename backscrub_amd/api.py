@@ -36,6 +36,27 @@ class _Info(C.Structure):
                 ("act_bytes_per_stream", C.c_size_t)]
 
 
+class _StreamSetting(C.Structure):          # bsx.h bsx_stream_setting
+    _fields_ = [("d_bg", C.c_void_p), ("flags", C.c_uint)]
+
+
+class StreamSetting:
+    """one stream's settings for MaskGen.step_mixed — what one reference process takes as -b <image> (bg), -H / -V (flip_h / flip_v), -p bgblur:<k> (bgblur)
+    and toggles at run time with the s / h / v keys (filter_off, flip_h, flip_v; app/deepseg.cc:387-437, 624-673, 777-790).  bg: a cuda uint8 [H,W,3] image
+    (any number of streams may share one); unused with bgblur or filter_off."""
+    __slots__ = ("bg", "flip_h", "flip_v", "bgblur", "filter_off")
+
+    def __init__(self, bg=None, flip_h=False, flip_v=False, bgblur=0, filter_off=False):
+        self.bg, self.flip_h, self.flip_v, self.bgblur, self.filter_off = bg, bool(flip_h), bool(flip_v), int(bgblur), bool(filter_off)
+
+    def flags(self):
+        return (2 if self.flip_h else 0) | (4 if self.flip_v else 0) | ((self.bgblur & 255) << 8) | (32 if self.filter_off else 0)
+
+    def __repr__(self):
+        return "StreamSetting(bg=%s, flip_h=%s, flip_v=%s, bgblur=%d, filter_off=%s)" % (
+            "None" if self.bg is None else "<image>", self.flip_h, self.flip_v, self.bgblur, self.filter_off)
+
+
 class LaunchStat(C.Structure):
     _fields_ = [("name", C.c_char * 64), ("avg_ms", C.c_double), ("bytes", C.c_double), ("flops", C.c_double)]
 
@@ -60,6 +81,7 @@ SYMBOLS = [
     ("bsx_step_batch_vcam", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint]),
     ("bsx_step_batch_streams", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_uint]),
     ("bsx_reset_streams", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
+    ("bsx_step_batch_mixed", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(_StreamSetting), C.c_void_p, C.c_int, C.c_void_p, C.c_uint]),
     ("bsx_resize_bgr", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("bsx_bgr_to_yuyv", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("bsx_yuyv_to_bgr", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -242,6 +264,42 @@ class MaskGen:
         self._step_out(out, n, yuyv)
         flags, stride = self._step_flags(bg, n, flip_h, flip_v, yuyv, no_mask, yuyv_in, bgblur)
         _check(lib().bsx_step_batch_streams(self.h, arr, _ptr(frames), _ptr(bg), stride, _ptr(out), n, _stream_ptr(), flags), self.h, "bsx_step_batch_streams")
+        return out
+
+    def _setting_bg(self, bg, i):
+        """a stream's background image: cuda:<device> uint8 [H,W,3], contiguous (the checks of _bg for one image)"""
+        ok = (bg.dtype == _torch().uint8 and bg.is_cuda and bg.dim() == 3 and tuple(bg.shape) == (self.height, self.width, 3)
+              and tuple(bg.stride()) == (self.width * 3, 3, 1) and bg.device.index == self.device)
+        if not ok:
+            raise BsxError("settings[%d].bg must be a contiguous cuda:%d uint8 tensor [%d,%d,3]" % (i, self.device, self.height, self.width))
+        return bg.data_ptr()
+
+    def step_mixed(self, frames, out, settings, ids=None, yuyv=False, no_mask=False, yuyv_in=False):
+        """one main-loop iteration where every stream has its OWN settings (bsx_step_batch_mixed): settings[i] (a StreamSetting) belongs to frames[i] / out[i] —
+        background image, flip, bgblur, filter switch — in one mask pipeline and one tile launch.  ids: None = frame i is stream i, else the stream ids as in
+        step_streams.  yuyv / no_mask / yuyv_in are batch-wide (they define the buffer layouts)."""
+        settings = list(settings)
+        arr, n_ids = _ids(ids) if ids is not None else (None, None)
+        n = self._n(frames, yuyv_in) if (ids is None or n_ids) else 0
+        if ids is not None and n_ids != n:
+            raise BsxError("%d ids for a batch of %d frames" % (n_ids, n))
+        if len(settings) != n:
+            raise BsxError("%d settings for a batch of %d frames" % (len(settings), n))
+        if n == 0:
+            _check(lib().bsx_step_batch_mixed(self.h, arr, None, None, None, 0, _stream_ptr(), 0), self.h, "bsx_step_batch_mixed")
+            return out
+        self._step_out(out, n, yuyv)
+        st = (_StreamSetting * n)()
+        for i, s in enumerate(settings):
+            if not isinstance(s, StreamSetting):
+                raise BsxError("settings[%d] is not a StreamSetting" % i)
+            reads_bg = not s.filter_off and not s.bgblur
+            if reads_bg and s.bg is None:
+                raise BsxError("settings[%d]: bg is required unless bgblur or filter_off is set" % i)
+            st[i].d_bg = self._setting_bg(s.bg, i) if s.bg is not None else None
+            st[i].flags = s.flags()
+        flags = (1 if yuyv else 0) | (8 if no_mask else 0) | (16 if yuyv_in else 0)
+        _check(lib().bsx_step_batch_mixed(self.h, arr, _ptr(frames), st, _ptr(out), n, _stream_ptr(), flags), self.h, "bsx_step_batch_mixed")
         return out
 
     def reset_streams(self, ids):

@@ -170,6 +170,13 @@ struct bsx_ctx {
   bool ids_used[kIdRing] = {};
   int ids_next = 0;
   std::vector<int> ids_seen;                // host scratch of the duplicate check: [n_streams], -1 = not listed
+  // bsx_step_batch_mixed: per ring entry (the same entries and events as the ids) the batch's descriptor table — n MixDesc (kernels.hpp), then the positions of its
+  // blur streams grouped by blur size (ints) — built in the pinned entry, copied to the device entry in one hipMemcpyAsync.  Allocated on the first mixed call.
+  uint8_t* h_mix = nullptr;                 // pinned [kIdRing][n_streams * (16 + 4)]
+  uint8_t* d_mix = nullptr;                 // device, likewise
+  struct MixBlur { int ksize, off, count; };
+  std::vector<MixBlur> mix_blur;            // the staged call's blur groups: ksize, first index into the position list, count
+  size_t mix_entry_bytes() const { return (size_t)n_streams * (sizeof(MixDesc) + sizeof(int)); }
   bool act16 = false;                  // BSX_ACT16=1: 16-bit activation STORAGE for the segmented Meet / MLKit networks (g1) — opt-in, IoU-gated; needs the specialised middle kernel
 
   // stream-0 view of a graph tensor (network input/output have dedicated buffers; intermediates are batch-major in
@@ -473,6 +480,10 @@ struct StepReq {
   int out_w, out_h, n;            // out_w x out_h: the capture size, except for bsx_step_batch_vcam
   unsigned flags; hipStream_t s;
   const int* ids;                 // bsx_step_batch_streams: the DEVICE copy of the stream ids (staged after the checks): frame i's state is slot ids[i]
+  const MixDesc* mix = nullptr;   // bsx_step_batch_mixed: the DEVICE descriptor table (staged after the checks) — position i's background / flip / filter-off
+  const int* mix_pos = nullptr;   // ... followed by the positions of its blur streams, grouped by blur size (bsx_ctx::mix_blur)
+  bool mix_bgr = false;           // ... some position composites over a blur of its frame: a YUYV batch is converted to BGR first
+  bool mix_blur_due = false;      // ... blur groups not yet launched (BlurToScratch)
   bool yuyv() const { return (flags & BSX_STEP_YUYV) != 0; }
   bool yin() const { return (flags & BSX_STEP_YUYV_IN) != 0; }
   unsigned flip() const { return flags & (BSX_STEP_FLIP_H | BSX_STEP_FLIP_V); }
@@ -482,7 +493,7 @@ struct StepReq {
   bool out_overlaps(const uint8_t* p, size_t bytes) const { return out < p + bytes && p < out + out_bytes(); }
   bool overlap(const bsx_ctx* c) const { return out_overlaps(frames, (size_t)n * c->width * c->height * (yin() ? 2 : 3)); }
 };
-enum class Entry { Step, Streams, Vcam, Pipelined };
+enum class Entry { Step, Streams, Vcam, Pipelined, Mixed };
 
 // The fused tile kernel — mask up-scale + blur + blend [+ flip][+ YUYV pack] per tile, YUYV input converted on load — takes the request: no onmask callback
 // (the persistent masks are written by the same launch), the kernel's geometry and alignment, and no overlap it would read after writing
@@ -496,6 +507,18 @@ bool tile_fusable(const bsx_ctx* c, const StepReq& r) {
 // overlap and every geometry its fused kernel does not take; the plain step runs in place, and with a flip / YUYV flag on any overlap (through a scratch).
 int check_step(bsx_ctx* c, const char* fn, const StepReq& r, Entry kind) {
   const bool vcam = kind == Entry::Vcam, pipe = kind == Entry::Pipelined, blur = r.bgblur() != 0;
+  if (kind == Entry::Mixed) {
+    // the batch's own rules (the per-position ones ran in mix_check): layout flags only, no overlap at all, the fused tile route's geometry and buffers
+    if (!r.frames || !r.out || r.n <= 0 || r.n > c->n_streams) return refuse(c, fn, "null buffer or batch size out of range");
+    if (r.flags & ~(BSX_STEP_YUYV | BSX_STEP_NO_MASK | BSX_STEP_YUYV_IN)) return refuse(c, fn, "flags 0x%x has bits outside yuyv / no-mask / yuyv-in", r.flags);
+    if (const int rc = refuse_pending(c, fn)) return rc;
+    if (r.yuyv() && (c->width & 1)) return refuse(c, fn, "YUYV output needs an even width");
+    if (r.yin() && (c->width & 1)) return refuse(c, fn, "YUYV input needs an even capture width");
+    if (r.overlap(c)) return refuse(c, fn, "output overlaps the frames (the mixed step has no in-place form)");
+    if (c->onmask || !mask_blend_fusable(c->width, c->height, c->roi, nullptr, 0, r.frames, r.out))
+      return refuse(c, fn, "needs the fused mask + blend geometry (width, ROI x and width multiples of 4, 4-byte aligned buffers, no onmask callback)");
+    return BSX_OK;
+  }
   if (!r.frames || (!r.bg && !blur) || !r.out || r.n <= 0 || r.n > c->n_streams) return refuse(c, fn, "null buffer or batch size out of range");
   if ((r.flags & ~(pipe ? 31u : 31u | 0xFF00u)) || (vcam && (r.flags & BSX_STEP_NO_MASK)))
     return refuse(c, fn, vcam ? "unsupported flags (the no-mask step has no vcam form)" : "unsupported flags 0x%x", r.flags);
@@ -523,6 +546,10 @@ int check_step(bsx_ctx* c, const char* fn, const StepReq& r, Entry kind) {
 // ONE launch; Composite: masks, then the plain blend [into a scratch, + flip][+ YUYV pack]; Vcam: masks, then blend + flip + resize [+ pack] in one pass
 enum class Route { YuyvToBgr, BlurToScratch, BlurBlend, Tile, Composite, Vcam };
 Route route_of(const bsx_ctx* c, const StepReq& r) {
+  if (r.mix) {                    // bsx_step_batch_mixed: [YUYV -> BGR] -> [blur groups into the scratch] -> ONE tile launch
+    if (r.yin() && (r.mix_bgr || !prep_yuyv_fusable(c->width, c->roi, c->tab_down.tab))) return Route::YuyvToBgr;
+    return r.mix_blur_due ? Route::BlurToScratch : Route::Tile;
+  }
   const bool resize = r.resize(c);
   if (r.yin() && (r.bgblur() || !(resize ? prep_yuyv_fusable(c->width, c->roi, c->tab_down.tab) : tile_fusable(c, r)))) return Route::YuyvToBgr;
   if (r.bgblur())
@@ -555,8 +582,12 @@ int run_tile(bsx_ctx* c, const StepReq& r) {
     else rc = enqueue_masks(c, r.frames, nb, ls, r.yin(), 0, r.ids);
     if (rc) return rc;
     bsx_roctx::Range range("bsx:mask+blend");
-    BSX_HIP(c, launch_mask_blend(c->d_ofinal + (size_t)st0 * sm, c->outW, c->outH, c->in_roi, tab_up_at(c, f0), c->d_masks + (size_t)st0 * c->width * c->height, c->width,
-                                 c->height, c->roi, r.bg + (size_t)f0 * r.bg_stride, r.bg_stride, r.frames + (size_t)f0 * fb, r.out + (size_t)f0 * ob, nb, ls, (int)r.flags, 0, lids));
+    if (r.mix)
+      BSX_HIP(c, launch_mask_blend_mixed(c->d_ofinal + (size_t)st0 * sm, c->outW, c->outH, c->in_roi, tab_up_at(c, f0), c->d_masks + (size_t)st0 * c->width * c->height,
+                                         c->width, c->height, c->roi, r.mix + f0, r.frames + (size_t)f0 * fb, r.out + (size_t)f0 * ob, nb, ls, (int)r.flags, lids));
+    else
+      BSX_HIP(c, launch_mask_blend(c->d_ofinal + (size_t)st0 * sm, c->outW, c->outH, c->in_roi, tab_up_at(c, f0), c->d_masks + (size_t)st0 * c->width * c->height, c->width,
+                                   c->height, c->roi, r.bg + (size_t)f0 * r.bg_stride, r.bg_stride, r.frames + (size_t)f0 * fb, r.out + (size_t)f0 * ob, nb, ls, (int)r.flags, 0, lids));
     return BSX_OK;
   };
   // (the per-launch path's arena is batch-major: a lane's compact arena is laid out for `per` streams starting at stream f0, so the LAST lane ends at
@@ -632,6 +663,12 @@ int run_step(bsx_ctx* c, StepReq r) {
         r.frames = c->d_bgr_in_scratch; r.flags &= ~BSX_STEP_YUYV_IN;
         continue;
       case Route::BlurToScratch:
+        if (r.mix) {              // one launch per blur size over its positions, each blurred frame into the scratch at its position (the descriptors point there)
+          for (const bsx_ctx::MixBlur& g : c->mix_blur)
+            BSX_HIP(c, launch_gauss_blur(r.frames, c->d_bgblur_scratch, c->width, c->height, g.ksize, g.count, r.s, r.mix_pos + g.off));
+          r.mix_blur_due = false;
+          continue;
+        }
         if (!c->d_bgblur_scratch) BSX_HIP(c, hipMalloc(&c->d_bgblur_scratch, (size_t)c->n_streams * px * 3));
         BSX_HIP(c, launch_gauss_blur(r.frames, c->d_bgblur_scratch, c->width, c->height, r.bgblur(), r.n, r.s));
         r.bg = c->d_bgblur_scratch; r.bg_stride = px * 3; r.flags &= ~0xFF00u;
@@ -672,11 +709,8 @@ int ids_check(bsx_ctx* c, const char* fn, const int* ids, int n) {
   for (int j = 0; j < i; j++) c->ids_seen[ids[j]] = -1;
   return rc;
 }
-// ids[0..n) → the next entry of the pinned ring → the same entry of the device ring, on s (bsx_ctx::kIdRing); ids_release guards the entry behind the call
-int ids_stage(bsx_ctx* c, const int* ids, int n, hipStream_t s, const int** d_ids, int* entry) {
-  const size_t N = (size_t)c->n_streams;
-  if (!c->h_ids) BSX_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_ids), bsx_ctx::kIdRing * N * sizeof(int), hipHostMallocDefault));
-  if (!c->d_ids) BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_ids), bsx_ctx::kIdRing * N * sizeof(int)));
+// the next entry of the staging ring (bsx_ctx::kIdRing: the ids, the mixed step's descriptors), once the event recorded behind its previous user has completed
+int ring_acquire(bsx_ctx* c, int* entry) {
   for (hipEvent_t& e : c->ev_ids) if (!e) BSX_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
   const int k = c->ids_next;
   if (c->ids_used[k]) {
@@ -684,12 +718,24 @@ int ids_stage(bsx_ctx* c, const int* ids, int n, hipStream_t s, const int** d_id
     while ((e = hipEventQuery(c->ev_ids[k])) == hipErrorNotReady) std::this_thread::yield();
     BSX_HIP(c, e);
   }
-  memcpy(c->h_ids + (size_t)k * N, ids, (size_t)n * sizeof(int));
-  BSX_HIP(c, hipMemcpyAsync(c->d_ids + (size_t)k * N, c->h_ids + (size_t)k * N, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
   c->ids_next = (k + 1) % bsx_ctx::kIdRing;
-  *d_ids = c->d_ids + (size_t)k * N;
   *entry = k;
   return BSX_OK;
+}
+// ids[0..n) → entry k of the pinned ring → the same entry of the device ring, on s
+int ids_copy(bsx_ctx* c, const int* ids, int n, hipStream_t s, int k, const int** d_ids) {
+  const size_t N = (size_t)c->n_streams;
+  if (!c->h_ids) BSX_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_ids), bsx_ctx::kIdRing * N * sizeof(int), hipHostMallocDefault));
+  if (!c->d_ids) BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_ids), bsx_ctx::kIdRing * N * sizeof(int)));
+  memcpy(c->h_ids + (size_t)k * N, ids, (size_t)n * sizeof(int));
+  BSX_HIP(c, hipMemcpyAsync(c->d_ids + (size_t)k * N, c->h_ids + (size_t)k * N, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+  *d_ids = c->d_ids + (size_t)k * N;
+  return BSX_OK;
+}
+// ids[0..n) → the next ring entry, on s; ids_release guards the entry behind the call
+int ids_stage(bsx_ctx* c, const int* ids, int n, hipStream_t s, const int** d_ids, int* entry) {
+  if (const int rc = ring_acquire(c, entry)) return rc;
+  return ids_copy(c, ids, n, s, *entry, d_ids);
 }
 // the ring entry is free again once everything enqueued on s so far has run (recorded also after a failed call: whatever it enqueued may read the entry)
 int ids_release(bsx_ctx* c, int entry, hipStream_t s, int rc) {
@@ -699,20 +745,87 @@ int ids_release(bsx_ctx* c, int entry, hipStream_t s, int rc) {
   return rc;
 }
 
-// a step entry point: the request checked (ids included) before anything is enqueued, then on the context's device [the ids staged] and run
-int step_call(bsx_ctx* c, const char* fn, Entry kind, StepReq r, const int* host_ids = nullptr) {
+// ---- bsx_step_batch_mixed: every position with its own background, flip and filter switch (bsx.h), in ONE mask pipeline and ONE tile launch --------------------
+
+constexpr unsigned kStreamFlags = BSX_STEP_FLIP_H | BSX_STEP_FLIP_V | 0xFF00u | BSX_STREAM_FILTER_OFF;
+static_assert(BSX_STEP_FLIP_H == kMixFlipH && BSX_STEP_FLIP_V == kMixFlipV && BSX_STREAM_FILTER_OFF == kMixFilterOff, "descriptor flags = the public bits");
+inline int setting_blur(const bsx_stream_setting& st) { return (st.flags & BSX_STREAM_FILTER_OFF) ? 0 : (int)((st.flags >> 8) & 255u); }   // 0: no blur to make
+
+// host-side validation of settings[0..n), next to ids_check: nothing is enqueued before it passes
+int mix_check(bsx_ctx* c, const char* fn, const bsx_stream_setting* st, const StepReq& r) {
+  if (r.n > 0 && !st) return refuse(c, fn, "settings is NULL");
+  const size_t img = (size_t)c->width * c->height * 3;
+  for (int i = 0; i < r.n; i++) {
+    const unsigned f = st[i].flags;
+    const int k = (int)((f >> 8) & 255u);
+    if (f & ~kStreamFlags) return refuse(c, fn, "settings[%d]: flags 0x%x has bits outside flip / blur / filter-off", i, f);
+    if (k && (k > 31 || !(k & 1))) return refuse(c, fn, "settings[%d]: blur size %d must be odd and <= 31", i, k);
+    if ((f & BSX_STREAM_FILTER_OFF) || k) continue;               // reads no background
+    if (!st[i].d_bg) return refuse(c, fn, "settings[%d]: d_bg is NULL", i);
+    if ((uintptr_t)st[i].d_bg & 3) return refuse(c, fn, "settings[%d]: d_bg %p is not 4-byte aligned", i, (const void*)st[i].d_bg);
+    if (r.frames && r.out && r.out_overlaps(st[i].d_bg, img)) return refuse(c, fn, "settings[%d]: output overlaps the background %p", i, (const void*)st[i].d_bg);
+  }
+  return BSX_OK;
+}
+// the descriptor table of settings[0..n) into ring entry k (pinned), the blur positions grouped by size behind it, one copy to the device entry on r.s.  A blur
+// stream's background is its slot of the blur scratch (filled by the BlurToScratch route before the tile launch); blur size 1 is the frame itself.
+int mix_stage(bsx_ctx* c, const bsx_stream_setting* st, StepReq& r, int k) {
+  const size_t eb = c->mix_entry_bytes(), img = (size_t)c->width * c->height * 3;
+  if (!c->h_mix) BSX_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_mix), bsx_ctx::kIdRing * eb, hipHostMallocDefault));
+  if (!c->d_mix) BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_mix), bsx_ctx::kIdRing * eb));
+  int count[32] = {0};
+  for (int i = 0; i < r.n; i++) count[setting_blur(st[i])]++;
+  r.mix_bgr = false;
+  for (int ks = 1; ks < 32; ks++) r.mix_bgr = r.mix_bgr || count[ks] > 0;
+  if (r.mix_bgr && !c->d_bgblur_scratch) BSX_HIP(c, hipMalloc(&c->d_bgblur_scratch, (size_t)c->n_streams * img));
+  if (r.mix_bgr && r.yin() && !c->d_bgr_in_scratch) BSX_HIP(c, hipMalloc(&c->d_bgr_in_scratch, (size_t)c->n_streams * img));
+  const uint8_t* const bgr = r.yin() ? c->d_bgr_in_scratch : r.frames;     // the BGR frames a blur reads (YuyvToBgr converts a YUYV batch first)
+  int next[32] = {0};
+  c->mix_blur.clear();
+  int npos = 0;
+  for (int ks = 3; ks < 32; ks += 2)
+    if (count[ks]) { c->mix_blur.push_back({ks, npos, count[ks]}); next[ks] = npos; npos += count[ks]; }
+  MixDesc* hd = reinterpret_cast<MixDesc*>(c->h_mix + (size_t)k * eb);
+  int* hp = reinterpret_cast<int*>(hd + r.n);
+  for (int i = 0; i < r.n; i++) {
+    const int ks = setting_blur(st[i]);
+    const uint8_t* bg = st[i].d_bg;
+    if (st[i].flags & BSX_STREAM_FILTER_OFF) bg = nullptr;
+    else if (ks == 1) bg = bgr + (size_t)i * img;                  // GaussianBlur(frame, 1) is the frame
+    else if (ks) { bg = c->d_bgblur_scratch + (size_t)i * img; hp[next[ks]++] = i; }
+    hd[i] = MixDesc{bg, st[i].flags & (kMixFlipH | kMixFlipV | kMixFilterOff), 0u};
+  }
+  uint8_t* const dd = c->d_mix + (size_t)k * eb;
+  BSX_HIP(c, hipMemcpyAsync(dd, hd, (size_t)r.n * sizeof(MixDesc) + (size_t)npos * sizeof(int), hipMemcpyHostToDevice, r.s));
+  r.mix = reinterpret_cast<const MixDesc*>(dd);
+  r.mix_pos = reinterpret_cast<const int*>(r.mix + r.n);
+  r.mix_blur_due = npos > 0;
+  return BSX_OK;
+}
+
+// a step entry point: the request checked (ids and settings included) before anything is enqueued, then on the context's device [the ids / descriptors staged]
+// and run
+int step_call(bsx_ctx* c, const char* fn, Entry kind, StepReq r, const int* host_ids = nullptr, const bsx_stream_setting* settings = nullptr) {
   if (!c) return BSX_EINVAL;
   if (kind != Entry::Vcam) { r.out_w = c->width; r.out_h = c->height; }
-  if (kind == Entry::Streams) {
+  const bool mixed = kind == Entry::Mixed;
+  if (kind == Entry::Streams || (mixed && host_ids)) {
     if (const int rc = ids_check(c, fn, host_ids, r.n)) return rc;
-    if (r.n == 0) return refuse_pending(c, fn);                   // (check_step refuses a pending composite for n > 0)
+  } else if (mixed) {                                             // the dense form: the count rules of ids_check
+    if (r.n < 0) return refuse(c, fn, "n = %d is negative", r.n);
+    if (r.n > c->n_streams) return refuse(c, fn, "n = %d exceeds the context's %d streams", r.n, c->n_streams);
   }
+  if ((kind == Entry::Streams || mixed) && r.n == 0) return refuse_pending(c, fn);   // (check_step refuses a pending composite for n > 0)
+  if (mixed) { if (const int rc = mix_check(c, fn, settings, r)) return rc; }
   if (const int rc = check_step(c, fn, r, kind)) return rc;
   DeviceGuard guard(c->device);
-  if (kind != Entry::Streams) return run_step(c, r);
+  if (kind != Entry::Streams && !mixed) return run_step(c, r);
   int entry = 0;
-  if (const int rc = ids_stage(c, host_ids, r.n, r.s, &r.ids, &entry)) return rc;
-  return ids_release(c, entry, r.s, run_step(c, r));
+  if (const int rc = ring_acquire(c, &entry)) return rc;
+  int rc = BSX_OK;
+  if (host_ids) rc = ids_copy(c, host_ids, r.n, r.s, entry, &r.ids);
+  if (!rc && mixed) rc = mix_stage(c, settings, r, entry);
+  return ids_release(c, entry, r.s, rc ? rc : run_step(c, r));
 }
 
 // ---- two-deep pipeline: mask pipeline of batch k  ||  composite of batch k - 1 ------------------------------------------------------------------
@@ -870,6 +983,8 @@ void bsx_delete(bsx_ctx* c) {
   for (hipEvent_t& e : c->ev_ids) if (e) (void)hipEventDestroy(e);
   if (c->d_ids) (void)hipFree(c->d_ids);
   if (c->h_ids) (void)hipHostFree(c->h_ids);
+  if (c->d_mix) (void)hipFree(c->d_mix);
+  if (c->h_mix) (void)hipHostFree(c->h_mix);
   delete c;
 }
 
@@ -970,6 +1085,12 @@ int bsx_step_batch_ex(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, 
 int bsx_step_batch_streams(bsx_ctx* c, const int* ids, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_frame_stride, uint8_t* d_out, int n, void* stream,
                            unsigned flags) {
   return step_call(c, "bsx_step_batch_streams", Entry::Streams, StepReq{d_frames, d_bg, bg_frame_stride, d_out, 0, 0, n, flags, (hipStream_t)stream, nullptr}, ids);
+}
+
+// settings (host): position i's background, flip, blur and filter switch; flags: the batch's layout bits; ids: NULL = frame i is stream i, else as above
+int bsx_step_batch_mixed(bsx_ctx* c, const int* ids, const uint8_t* d_frames, const bsx_stream_setting* settings, uint8_t* d_out, int n, void* stream,
+                         unsigned flags) {
+  return step_call(c, "bsx_step_batch_mixed", Entry::Mixed, StepReq{d_frames, nullptr, 0, d_out, 0, 0, n, flags, (hipStream_t)stream, nullptr}, ids, settings);
 }
 
 int bsx_reset_streams(bsx_ctx* c, const int* ids, int n, void* stream) {

@@ -114,6 +114,16 @@ bool mask_blend_fusable(int W, int H, Rect4 roi, const uint8_t* bg, size_t bg_st
 hipError_t launch_mask_blend(const uint8_t* ofinal, int outW, int outH, Rect4 in_roi, ResizeTab tab, uint8_t* mask, int W, int H, Rect4 roi,
                              const uint8_t* bg, size_t bg_stride, const uint8_t* frames, uint8_t* out, int n, hipStream_t s, int yuyv = 0, int lds_pad = 0,
                              const int* slot_of = nullptr);
+// bsx_step_batch_mixed: one 16-byte descriptor per position of the batch, read by the mixed instantiations of the mask tile kernels and by outside_roi_mixed_k
+// with one uniform load per workgroup.  bg: the position's background (4-byte aligned BGR, any number of positions may share one; unread when the filter is
+// off); flags: kMixFlipH / kMixFlipV (the same bits as the tile kernels' flag word) | kMixFilterOff.
+constexpr unsigned kMixFlipH = 2u, kMixFlipV = 4u, kMixFilterOff = 32u;
+struct alignas(16) MixDesc { const uint8_t* bg; unsigned flags; unsigned pad; };
+static_assert(sizeof(MixDesc) == 16, "one 16-byte uniform load per workgroup");
+// launch_mask_blend with the background and the flip of each position taken from desc[i] (a DEVICE array of n descriptors) and a filter-off position composited
+// from its frame; `flags`: the batch's bits only (bit 0 = YUYV out, bit 3 = no mask store, bit 4 = YUYV frames).  Same geometry as launch_mask_blend.
+hipError_t launch_mask_blend_mixed(const uint8_t* ofinal, int outW, int outH, Rect4 in_roi, ResizeTab tab, uint8_t* mask, int W, int H, Rect4 roi,
+                                   const MixDesc* desc, const uint8_t* frames, uint8_t* out, int n, hipStream_t s, int flags, const int* slot_of = nullptr);
 // alpha blend.  deepseg.cc:108-134
 hipError_t launch_blend(const uint8_t* bg, size_t bg_stride, const uint8_t* frames, const uint8_t* masks, uint8_t* out, size_t npix,
                         int n, hipStream_t s, const int* slot_of = nullptr);
@@ -126,7 +136,8 @@ hipError_t launch_yuyv_to_bgr(const uint8_t* yuyv, uint8_t* bgr, int w, int h, i
 // cv::flip of the composited frame (code as cv::flip: 0 vertical, >0 horizontal, <0 both).  deepseg.cc:667-673
 hipError_t launch_flip_bgr(const uint8_t* src, uint8_t* dst, int w, int h, int code, int n, hipStream_t s);
 // cv::GaussianBlur(Size(ksize, ksize), sigma 0) of packed BGR u8 images (dst != src), ksize odd <= 31.  deepseg.cc:657-658 (-p bgblur:N)
-hipError_t launch_gauss_blur(const uint8_t* src, uint8_t* dst, int w, int h, int ksize, int n, hipStream_t s);
+// positions (DEVICE array of n, nullable): image i of the launch is image positions[i] of src and of dst (bsx_step_batch_mixed: the positions of one blur size)
+hipError_t launch_gauss_blur(const uint8_t* src, uint8_t* dst, int w, int h, int ksize, int n, hipStream_t s, const int* positions = nullptr);
 bool gauss_coeff_words(int ksize, int shift, uint32_t* c4 /* [4][9] */, uint32_t* c2 /* [2][17] */);   // host: the tables launch_gauss_* pass to the kernel
 // blur + alpha blend of the frames over their own blur (deepseg.cc:652-661 without -b), the blurred image never stored; fusable = 4-byte aligned images, w % 4 == 0
 bool gauss_blend_fusable(const uint8_t* frames, const uint8_t* masks, const uint8_t* out, int w, int ksize);

@@ -443,6 +443,13 @@ __device__ __forceinline__ uint32_t yuyv_pair(uint32_t a0, uint32_t a1, uint32_t
 }
 
 // ---- pieces shared by the two mask tile kernels ------------------------------------------------------------------------------
+// MixDesc n of the table a mixed launch passes as `bg` (kernels.hpp): ONE 16-byte uniform load; the background pointer is returned as a global-memory pointer (a
+// pointer read from memory is otherwise a generic one, and the operand loads through it would be flat loads)
+__device__ __forceinline__ const uint8_t* mix_desc(const uint8_t* table, int n, unsigned* flags) {
+  const uint4 v = reinterpret_cast<const uint4*>(table)[n];
+  *flags = v.z;
+  return (const uint8_t*)(const __attribute__((address_space(1))) uint8_t*)(((uint64_t)v.y << 32) | v.x);
+}
 // Composite operands of a lane's kTileItems 4-pixel groups (12 B of background + 12 B of frame each), requested at the very
 // top of the kernel so that their HBM latency hides behind the LDS phases.
 struct TileBlendOperands { uint32_t a[kTileItems][3], b[kTileItems][3]; };
@@ -451,9 +458,13 @@ struct TileBlendOperands { uint32_t a[kTileItems][3], b[kTileItems][3]; };
 // background before it knows the tile's class (parts = 1) and the frame after (parts = 2)
 // `yin` (wave-uniform; BSX_STEP_YUYV_IN): `frames` holds YUYV 4:2:2 — a lane's four pixels are 8 bytes (b[i][0..1]), converted where they are consumed
 // (tile_frame_bgr below); b[i][2] is then unused
-template <bool BLEND, bool WHOLE = false>      // WHOLE: every tile of the launch lies inside the ROI (roi.w % 128 == 0, roi.h % 32 == 0): no per-item edge tests
+// `sel` (wave-uniform, read only with SEL): which operand the composite is, when that is not what `uniform` says — 2 = the frame whatever the mask
+// (bsx_step_batch_mixed: a stream with its filter switched off), -1 = as `uniform`.  A template parameter: the callers without it compile to what they were.
+template <bool BLEND, bool WHOLE = false, bool SEL = false>      // WHOLE: every tile of the launch lies inside the ROI (roi.w % 128 == 0, roi.h % 32 == 0): no per-item edge tests
 __device__ __forceinline__ void tile_load_blend_operands(TileBlendOperands& o, const uint8_t* __restrict__ bg, long bg_stride, const uint8_t* __restrict__ frames,
-                                                         int n, int W, int H, Rect4 roi, int tx0, int ty0, int tid, int uniform = 0, int parts = 3, bool yin = false) {
+                                                         int n, int W, int H, Rect4 roi, int tx0, int ty0, int tid, int uniform = 0, int parts = 3, bool yin = false,
+                                                         int sel = -1) {
+  if constexpr (SEL) { if (sel >= 0) uniform = sel; }
   if constexpr (BLEND) {
     const int ly0 = tid / (kTW / 4), gx = tx0 + (tid % (kTW / 4)) * 4;
     const long pix0 = (long)(roi.y + ty0 + ly0) * W + roi.x + gx;        // frame coordinates of the ROI-relative tile pixel
@@ -529,9 +540,12 @@ __device__ __forceinline__ void reverse4px(uint32_t (&w)[3]) {
 // pixels go to the mirrored column group in reverse order, the row to the mirrored row; the persistent mask is the unflipped frame's and stays put.
 // `uniform` (wave-uniform; see mask_tile_k): 1 / 2 = every mask byte of the tile is 255 / 0 — no sums to form, and the composite IS the background / the frame
 // ((a*255 + b*0)/255 == a for every byte: the exhaustive blend test covers m = 0 and 255)
-template <bool BLEND, bool WHOLE = false>
+// `sel` (SEL): which operand the composite is when that is not what `uniform` says (see tile_load_blend_operands) — the mask is still formed from `uniform`
+template <bool BLEND, bool WHOLE = false, bool SEL = false>
 __device__ __forceinline__ void tile_vsum5_store(const uint16_t* hs, uint8_t* __restrict__ mask, uint8_t* __restrict__ outp, const TileBlendOperands& o,
-                                                 int n, int ms, int W, int H, Rect4 roi, int tx0, int ty0, int tid, int yuyv_flip, int uniform = 0) {
+                                                 int n, int ms, int W, int H, Rect4 roi, int tx0, int ty0, int tid, int yuyv_flip, int uniform = 0, int sel = -1) {
+  int take = uniform;                                            // the composite's operand: 0 = the blend, 1 = the background, 2 = the frame
+  if constexpr (SEL) { if (sel >= 0) take = sel; }
   const int ly0 = tid / (kTW / 4), lx = (tid % (kTW / 4)) * 4;
   const int gx = tx0 + lx;
   const int yuyv = yuyv_flip & 1;
@@ -565,8 +579,8 @@ __device__ __forceinline__ void tile_vsum5_store(const uint16_t* hs, uint8_t* __
     if constexpr (BLEND) {
       uint32_t* op = reinterpret_cast<uint32_t*>(out0 + (long)(8 * i) * orow * obpp);
       uint32_t o3[3];
-      if (uniform == 1) { o3[0] = o.a[i][0]; o3[1] = o.a[i][1]; o3[2] = o.a[i][2]; }
-      else if (uniform == 2) tile_frame_bgr(o, i, yin, o3);
+      if (take == 1) { o3[0] = o.a[i][0]; o3[1] = o.a[i][1]; o3[2] = o.a[i][2]; }
+      else if (take == 2) tile_frame_bgr(o, i, yin, o3);
       else { uint32_t b3[3]; tile_frame_bgr(o, i, yin, b3); blend_quad(o.a[i], b3, packed, o3); }
       if (fh) reverse4px(o3);
       if (yuyv) {                                                  // deepseg.cc:87-106 on the four composited pixels: 8 bytes instead of 12
@@ -582,7 +596,9 @@ __device__ __forceinline__ void tile_vsum5_store(const uint16_t* hs, uint8_t* __
   }
 }
 
-template <bool BLEND, bool YIN = false>      // YIN (BSX_STEP_YUYV_IN): `frames` is YUYV 4:2:2 — a template parameter so that the BGR instantiation carries none of the conversion
+// MIX (bsx_step_batch_mixed): `bg` is the batch's MixDesc table (kernels.hpp) — the background, flip and filter-off bit of position n come from desc[n], one uniform
+// load per workgroup; bg_stride is unused
+template <bool BLEND, bool YIN = false, bool MIX = false>      // YIN (BSX_STEP_YUYV_IN): `frames` is YUYV 4:2:2 — a template parameter so that the BGR instantiation carries none of the conversion
 __global__ __launch_bounds__(kThreads) void mask_upscale_blur_k(const uint8_t* __restrict__ ofinal, int outW, int outH, Rect4 q, ResizeTab tab,
                                                                uint8_t* __restrict__ mask, int W, int H, Rect4 roi,
                                                                const uint8_t* __restrict__ bg, long bg_stride, const uint8_t* __restrict__ frames,
@@ -605,7 +621,14 @@ __global__ __launch_bounds__(kThreads) void mask_upscale_blur_k(const uint8_t* _
   const int tid = threadIdx.x;
   TileBlendOperands ops;
   yuyv = YIN ? (yuyv | 16) : (yuyv & ~16);                                  // the helpers read bit 4: a compile-time constant per instantiation
-  tile_load_blend_operands<BLEND>(ops, bg, bg_stride, frames, n, W, H, roi, tx0, ty0, tid, 0, 3, YIN);
+  int sel = -1;                                                             // MIX: 2 = the filter is off, the composite is the frame
+  if constexpr (MIX) {
+    unsigned fl;
+    bg = mix_desc(bg, n, &fl); bg_stride = 0;
+    yuyv |= (int)(fl & (kMixFlipH | kMixFlipV));
+    if (fl & kMixFilterOff) sel = 2;
+  }
+  tile_load_blend_operands<BLEND, false, MIX>(ops, bg, bg_stride, frames, n, W, H, roi, tx0, ty0, tid, 0, 3, YIN, sel);
   if (tid == 0) { s_min = 1 << 30; s_max = -1; }
   __syncthreads();
   // 1. column / row tables
@@ -667,7 +690,7 @@ __global__ __launch_bounds__(kThreads) void mask_upscale_blur_k(const uint8_t* _
   __syncthreads();
   tile_hsum5(up, hs, tid);                                                                       // 4.
   __syncthreads();
-  tile_vsum5_store<BLEND>(hs, mask, outp, ops, n, ms, W, H, roi, tx0, ty0, tid, yuyv);           // 5.
+  tile_vsum5_store<BLEND, false, MIX>(hs, mask, outp, ops, n, ms, W, H, roi, tx0, ty0, tid, yuyv, 0, sel);   // 5.
 }
 
 // ---- mask tile, single-round-trip form ---------------------------------------------------------------------------------
@@ -682,7 +705,9 @@ constexpr int kSrcBlockBytes = kHH * kHW;        // the raw block lives in `up` 
 // for every wave-uniform branch it carries: with the YUYV-in conversion behind a run-time flag the BGR step's launch was 12-15 % slower (profiles/r06l: 105-111 ->
 // 94-97 us at configs[1], 1064-1114 -> 946-955 us at the configs[4] slice), code that never ran.
 // WH: whole tiles only (see tile_load_blend_operands) and a 4-byte aligned mask — decided by the launcher from the geometry
-template <bool BLEND, bool YIN = false, bool F0 = false, bool WH = false>
+// MIX (bsx_step_batch_mixed): `bg` is the batch's MixDesc table, as in mask_upscale_blur_k — its uniform load goes out next to the tile-class byte's, and the flip
+// and the filter-off bit become wave-uniform run-time branches (a mixed batch has no F0 / WH launch)
+template <bool BLEND, bool YIN = false, bool F0 = false, bool WH = false, bool MIX = false>
 __global__ __launch_bounds__(kThreads) void mask_tile_k(const uint8_t* __restrict__ ofinal, int outW, int outH, Rect4 q, ResizeTab tab,
                                                        uint8_t* __restrict__ mask, int W, int H, Rect4 roi,
                                                        const uint8_t* __restrict__ bg, long bg_stride, const uint8_t* __restrict__ frames,
@@ -717,7 +742,7 @@ __global__ __launch_bounds__(kThreads) void mask_tile_k(const uint8_t* __restric
   // background is HBM traffic a uniform-0 tile must not pay: it keeps the order class -> operands.
   if (F0) yuyv = 0;                                                                                 // flags as compile-time constants: F0 = none, YIN = bit 4 (read again by
   yuyv = YIN ? (yuyv | 16) : (yuyv & ~16);                                                          // tile_vsum5_store)
-  const bool early_bg = BLEND && bg_stride == 0 && tab.tile_class != nullptr && !(yuyv & 64);      // (bit 6: the debug build's A/B switch for this order)
+  const bool early_bg = BLEND && !MIX && bg_stride == 0 && tab.tile_class != nullptr && !(yuyv & 64);      // (bit 6: the debug build's A/B switch for this order)
   constexpr bool yin = YIN;                                                                         // BSX_STEP_YUYV_IN
   TileBlendOperands ops;
   if (early_bg) tile_load_blend_operands<BLEND, WH>(ops, bg, bg_stride, frames, n, W, H, roi, tx0, ty0, tid, 0, 1, yin);
@@ -725,13 +750,20 @@ __global__ __launch_bounds__(kThreads) void mask_tile_k(const uint8_t* __restric
     const uintptr_t ca = (uintptr_t)tab.tile_class + (size_t)n * (size_t)(ntx * nty_all) + (size_t)(tby * ntx + tbx);
     uniform = (int)((*reinterpret_cast<const uint32_t*>(ca & ~(uintptr_t)3) >> (8 * (unsigned)(ca & 3))) & 255u);
   }
+  int sel = -1;                                             // MIX: 2 = the filter is off — the mask is formed as always, the composite is the frame
+  if constexpr (MIX) {
+    unsigned fl;
+    bg = mix_desc(bg, n, &fl); bg_stride = 0;
+    yuyv |= (int)(fl & (kMixFlipH | kMixFlipV));
+    if (fl & kMixFilterOff) sel = 2;
+  }
   // The frame's state slot (ofinal, mask; n = its position: frames, output, tile classes): slot_of[n] — one scalar load — or n.  Formed only AFTER the class byte is
   // requested, on both paths: anything in front of that load lengthens the dependent chain every tile waits on (formed at the top, the dense step's launch measured
   // 78 -> 82 us at configs[1]).
   if (uniform) {                                           // wave-uniform: nothing of the general path below is even requested
-    tile_load_blend_operands<BLEND, WH>(ops, bg, bg_stride, frames, n, W, H, roi, tx0, ty0, tid, uniform, early_bg ? 2 : 3, yin);
+    tile_load_blend_operands<BLEND, WH, MIX>(ops, bg, bg_stride, frames, n, W, H, roi, tx0, ty0, tid, uniform, early_bg ? 2 : 3, yin, sel);
     const int ms = slot_of ? slot_of[n] : n;
-    tile_vsum5_store<BLEND, WH>(hq_hs, mask, outp, ops, n, ms, W, H, roi, tx0, ty0, tid, yuyv, uniform);
+    tile_vsum5_store<BLEND, WH, MIX>(hq_hs, mask, outp, ops, n, ms, W, H, roi, tx0, ty0, tid, yuyv, uniform, sel);
     return;
   }
   // extents of the source block: xofs / yofs are monotonic, so the extreme destination rows / columns give them
@@ -759,7 +791,7 @@ __global__ __launch_bounds__(kThreads) void mask_tile_k(const uint8_t* __restric
     t_s = tab.yofs[gy]; t_a0 = tab.ya[2 * gy]; t_a1 = tab.ya[2 * gy + 1];
   }
   // (c) composite operands (the shared background is already on its way)
-  tile_load_blend_operands<BLEND, WH>(ops, bg, bg_stride, frames, n, W, H, roi, tx0, ty0, tid, 0, early_bg ? 2 : 3, yin);
+  tile_load_blend_operands<BLEND, WH, MIX>(ops, bg, bg_stride, frames, n, W, H, roi, tx0, ty0, tid, 0, early_bg ? 2 : 3, yin, sel);
   // 1. block and tables into LDS
 #pragma unroll
   for (int j = 0; j < 3; j++) if (br + 4 * j < nsr && bc < ncol) blk[(br + 4 * j) * ncol + bc] = (uint8_t)raw[j];
@@ -787,7 +819,7 @@ __global__ __launch_bounds__(kThreads) void mask_tile_k(const uint8_t* __restric
   __syncthreads();
   tile_hsum5(up, hs, tid);                                                                       // 4.
   __syncthreads();
-  tile_vsum5_store<BLEND, WH>(hs, mask, outp, ops, n, ms, W, H, roi, tx0, ty0, tid, yuyv);           // 5.
+  tile_vsum5_store<BLEND, WH, MIX>(hs, mask, outp, ops, n, ms, W, H, roi, tx0, ty0, tid, yuyv, 0, sel);   // 5.
 }
 
 // ---- alpha blend (deepseg.cc:108-134), stand-alone: bsx_composite_batch ---------------------------------------------------------------
@@ -925,6 +957,41 @@ __global__ __launch_bounds__(kThreads) void outside_roi_yuyv_k(const uint8_t* __
   const long n = blockIdx.y;
   const uint8_t* p = bg + (bg_stride ? n * bg_stride : 0) + ((long)row * W + x) * 3;
   out[n * (long)(W / 2) * H + i] = yuyv_pair(p[0], p[1], p[2], p[3], p[4], p[5]);
+}
+// outside the ROI in a mixed batch (bsx_step_batch_mixed): per position its own background and flip from desc[n] (one uniform load), or with the filter off its
+// own frame — converted on load when the batch's frames are YUYV (flags bit 4); BGR or YUYV out (bit 0).  One lane per group of four pixels, as outside_roi_flip_k.
+__global__ __launch_bounds__(kThreads) void outside_roi_mixed_k(const MixDesc* __restrict__ desc, const uint8_t* __restrict__ frames, uint8_t* __restrict__ out, int W,
+                                                               int H, Rect4 roi, int flags) {
+  const unsigned i = blockIdx.x * kThreads + threadIdx.x, gpr = (unsigned)W / 4;
+  if (i >= gpr * (unsigned)H) return;
+  const int row = (int)(i / gpr), x = (int)(i - (unsigned)row * gpr) * 4;
+  if (row >= roi.y && row < roi.y + roi.h && x >= roi.x && x < roi.x + roi.w) return;
+  const long n = blockIdx.y;
+  unsigned fl;
+  const uint8_t* const bgp = mix_desc(reinterpret_cast<const uint8_t*>(desc), (int)n, &fl);
+  const long px = (long)row * W + x;
+  uint32_t w[3];
+  if (!(fl & kMixFilterOff)) {
+    const uint32_t* p = reinterpret_cast<const uint32_t*>(bgp + px * 3);
+    w[0] = p[0]; w[1] = p[1]; w[2] = p[2];
+  } else if (flags & 16) {
+    const uint32_t* p = reinterpret_cast<const uint32_t*>(frames + (n * (long)W * H + px) * 2);
+    yuyv4_to_bgr3(p[0], p[1], w);
+  } else {
+    const uint32_t* p = reinterpret_cast<const uint32_t*>(frames + (n * (long)W * H + px) * 3);
+    w[0] = p[0]; w[1] = p[1]; w[2] = p[2];
+  }
+  const bool fh = (fl & kMixFlipH) != 0, fv = (fl & kMixFlipV) != 0;
+  if (fh) reverse4px(w);
+  const int oy = fv ? H - 1 - row : row, ox = fh ? W - 4 - x : x;
+  if (flags & 1) {
+    uint32_t* o = reinterpret_cast<uint32_t*>(out + (n * (long)W * H + (long)oy * W + ox) * 2);
+    o[0] = yuyv_pair(w[0] & 255u, (w[0] >> 8) & 255u, (w[0] >> 16) & 255u, w[0] >> 24, w[1] & 255u, (w[1] >> 8) & 255u);
+    o[1] = yuyv_pair((w[1] >> 16) & 255u, w[1] >> 24, w[2] & 255u, (w[2] >> 8) & 255u, (w[2] >> 16) & 255u, w[2] >> 24);
+  } else {
+    uint32_t* o = reinterpret_cast<uint32_t*>(out + (n * (long)W * H + (long)oy * W + ox) * 3);
+    o[0] = w[0]; o[1] = w[1]; o[2] = w[2];
+  }
 }
 
 // ---- YUYV → BGR ingest (cv::COLOR_YUV2BGR_YUYV, BT.601 limited range, 20-bit fixed point) --------------------------------
@@ -1306,6 +1373,33 @@ hipError_t launch_mask_blend(const uint8_t* ofinal, int outW, int outH, Rect4 in
   return hipGetLastError();
 }
 
+// the mixed batch (bsx_step_batch_mixed): the geometry of launch_mask_blend, every position's background / flip / filter from the descriptor table — the strips
+// outside the ROI by outside_roi_mixed_k, the ROI by the MIX instantiations (one tile launch whatever the settings); the descriptor table travels in the
+// kernels' `bg` argument, so the dense instantiations keep their argument list
+hipError_t launch_mask_blend_mixed(const uint8_t* ofinal, int outW, int outH, Rect4 in_roi, ResizeTab tab, uint8_t* mask, int W, int H, Rect4 roi,
+                                   const MixDesc* desc, const uint8_t* frames, uint8_t* out, int n, hipStream_t s, int flags, const int* slot_of) {
+  flags &= 1 | 8 | 16;
+  if (roi.x != 0 || roi.y != 0 || roi.w != W || roi.h != H)
+    outside_roi_mixed_k<<<dim3(blocks_for((long)(W / 4) * H), n), kThreads, 0, s>>>(desc, frames, out, W, H, roi, flags);
+  const int ntx = (roi.w + kTW - 1) / kTW, nty = (roi.h + kTH - 1) / kTH;
+  if ((unsigned long long)ntx * nty * (unsigned long long)n >= (1ull << 31)) return hipErrorInvalidValue;
+  static const bool xcd_on = !(BSX_DBG_ENV("BSX_XCD_TILES") && atoi(BSX_DBG_ENV("BSX_XCD_TILES")) == 0);
+  const bool shared_lines = ((roi.x * 3) & 127) != 0 || ((W * 3) & 127) != 0;
+  const int nf = (xcd_on && shared_lines) ? n : 0;
+  const dim3 grid((unsigned)(ntx * nty) * (unsigned)n);
+  if (hipError_t e = launch_tile_class(ofinal, outW, outH, in_roi, tab, roi, n, s, slot_of)) return e;
+  static const bool plain_stores = BSX_DBG_ENV("BSX_TILE_PLAIN_STORES") != nullptr;
+  if (plain_stores) flags |= 128;
+  const uint8_t* const d = reinterpret_cast<const uint8_t*>(desc);
+  const bool yin = (flags & 16) != 0;
+  if (mask_tile_usable(tab)) {
+    if (yin) mask_tile_k<true, true, false, false, true><<<grid, kThreads, 0, s>>>(ofinal, outW, outH, in_roi, tab, mask, W, H, roi, d, 0, frames, out, flags, ntx, nty, nf, 0, nty, slot_of);
+    else mask_tile_k<true, false, false, false, true><<<grid, kThreads, 0, s>>>(ofinal, outW, outH, in_roi, tab, mask, W, H, roi, d, 0, frames, out, flags, ntx, nty, nf, 0, nty, slot_of);
+  } else if (yin) mask_upscale_blur_k<true, true, true><<<grid, kThreads, 0, s>>>(ofinal, outW, outH, in_roi, tab, mask, W, H, roi, d, 0, frames, out, flags, ntx, nty, nf, slot_of);
+  else mask_upscale_blur_k<true, false, true><<<grid, kThreads, 0, s>>>(ofinal, outW, outH, in_roi, tab, mask, W, H, roi, d, 0, frames, out, flags, ntx, nty, nf, slot_of);
+  return hipGetLastError();
+}
+
 hipError_t launch_blend(const uint8_t* bg, size_t bg_stride, const uint8_t* frames, const uint8_t* masks, uint8_t* out, size_t npix, int n,
                         hipStream_t s, const int* slot_of) {
   // lane-coalesced form: 4-byte alignment and whole 4-pixel groups are enough; anything else takes the per-pixel kernel
@@ -1376,7 +1470,9 @@ __global__ __launch_bounds__(kThreads) void gauss_blur_k(const uint8_t* __restri
                                                          int opts, const int* __restrict__ slot_of) {
   __shared__ __attribute__((aligned(16))) uint8_t s_src[3 * kGSH * kGSrcStride];          // [plane][row][col]; MODE >= 1: later the packed output tile [row][kGOStride]
   __shared__ __attribute__((aligned(16))) uint16_t s_h[3 * kGHPlane];                     // [plane][col][row], gh_col()
-  const size_t img = (size_t)blockIdx.z * (size_t)W * H * 3;
+  // MODE 0 / 1 read slot_of as a position list when one is given (bsx_step_batch_mixed: the positions of one blur size): image blockIdx.z of the launch is image
+  // slot_of[blockIdx.z] of src and dst; MODE 2 reads it as the frames' state slots (below)
+  const size_t img = (size_t)(MODE < 2 && slot_of ? (unsigned)slot_of[blockIdx.z] : blockIdx.z) * (size_t)W * H * 3;
   const uint8_t* in = src + img;
   uint8_t* out = dst + img;
   const int x0 = blockIdx.x * kGTW, y0 = blockIdx.y * kGTH, r = gc.r;
@@ -1537,17 +1633,19 @@ static void gauss_launch(dim3 grid, hipStream_t s, const uint8_t* src, uint8_t* 
     default: break;
   }
 }
-hipError_t launch_gauss_blur(const uint8_t* src, uint8_t* dst, int w, int h, int ksize, int n, hipStream_t s) {
+hipError_t launch_gauss_blur(const uint8_t* src, uint8_t* dst, int w, int h, int ksize, int n, hipStream_t s, const int* positions) {
   GaussCoef gc;
   const int opts = gauss_opts(src, w);
   if (!gauss_coefficients(ksize, &gc, (opts & 1) ? (-(ksize / 2)) & 3 : 0)) return hipErrorInvalidValue;
-  if (ksize == 1) return hipMemcpyAsync(dst, src, (size_t)n * w * h * 3, hipMemcpyDeviceToDevice, s);
+  if (ksize == 1) return positions ? hipErrorInvalidValue : hipMemcpyAsync(dst, src, (size_t)n * w * h * 3, hipMemcpyDeviceToDevice, s);
   const bool words = gauss_words(src, dst, nullptr, w);
   for (int n0 = 0; n0 < n; n0 += kMaxGridY) {
     const int nn = n - n0 < kMaxGridY ? n - n0 : kMaxGridY;
     const dim3 grid((w + kGTW - 1) / kGTW, (h + kGTH - 1) / kGTH, nn);
-    if (words) gauss_launch<1>(grid, s, src + (size_t)n0 * w * h * 3, dst + (size_t)n0 * w * h * 3, nullptr, w, h, gc, opts);
-    else gauss_launch<0>(grid, s, src + (size_t)n0 * w * h * 3, dst + (size_t)n0 * w * h * 3, nullptr, w, h, gc, opts);
+    const size_t off = positions ? 0 : (size_t)n0 * w * h * 3;           // a position list addresses the images itself
+    const int* pos = positions ? positions + n0 : nullptr;
+    if (words) gauss_launch<1>(grid, s, src + off, dst + off, nullptr, w, h, gc, opts, pos);
+    else gauss_launch<0>(grid, s, src + off, dst + off, nullptr, w, h, gc, opts, pos);
   }
   return hipGetLastError();
 }

@@ -21,6 +21,7 @@
  *   bsx_step_batch_pipelined  … with the CalcMask worker's overlap of segmentation and blending  app/deepseg.cc:159-285, 634-661
  *   bsx_step_batch_vcam    … with the resize to the virtual camera's geometry (--vg) fused  app/deepseg.cc:634-681 (the resize: :675-679)
  *   bsx_step_batch_streams … for the streams that HAVE a new frame, addressed by id  app/deepseg.cc:182-216 (one filter step per new frame)
+ *   bsx_step_batch_mixed   … with each stream's own settings: -b / -p bgblur / -H / -V and the s / h / v keys  app/deepseg.cc:387-437, 596-673, 777-790
  *   bsx_reset_streams      bsx_reset for a chosen subset of the streams (a slot reused for a new camera)
  *                          (set_input_frame → mask → alpha_blend), batched
  *   bsx_resize_bgr         grab_background() cv::resize   app/background.cc:178-194
@@ -195,6 +196,32 @@ BSX_API int bsx_step_batch_ex(bsx_ctx* ctx, const uint8_t* d_frames, const uint8
  * bsx_step_batch_pipelined, bsx_step_batch_vcam and bsx_process_batch keep the dense contract (frame i = stream i). */
 BSX_API int bsx_step_batch_streams(bsx_ctx* ctx, const int* ids, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_frame_stride,
                                    uint8_t* d_out, int n, void* stream, unsigned flags);
+
+/* BSX_STREAM_FILTER_OFF: the reference with its filter switched off ('s' key, app/deepseg.cc:639-664, 782-783): the composite IS the camera frame (then
+ * flipped / packed as set); the mask pipeline still runs, so the stream's temporal state and persistent mask advance exactly as with the filter on. */
+#define BSX_STREAM_FILTER_OFF 32u
+typedef struct bsx_stream_setting {
+  const uint8_t* d_bg;  /* [height][width][3] BGR on the context's device, 4-byte aligned; any number of streams may point at the same image */
+  unsigned flags;       /* BSX_STEP_FLIP_H | BSX_STEP_FLIP_V | BSX_STEP_BGBLUR(k) | BSX_STREAM_FILTER_OFF */
+} bsx_stream_setting;
+/* One main-loop iteration of a batch whose streams do NOT share one setting — what one reference process per camera does with its own -b, -p bgblur, -H / -V
+ * and its run-time s / h / v keys (app/deepseg.cc:387-437, 596-673, 777-790) — in ONE mask pipeline launch sequence and one tile launch:
+ *   - ids: NULL = the dense contract (frame i is stream i); otherwise exactly the rules, staging and refusals of bsx_step_batch_streams;
+ *   - flags (batch-wide, the buffer layouts): BSX_STEP_YUYV | BSX_STEP_NO_MASK | BSX_STEP_YUYV_IN only;
+ *   - settings[0..n): host memory, read before the call returns; entry i belongs to position i.  The composite of position i (stream s):
+ *     BSX_STREAM_FILTER_OFF: frame i itself; BSX_STEP_BGBLUR(k): alpha_blend(GaussianBlur(frame i, k), frame i, mask s) (d_bg is not read); otherwise
+ *     alpha_blend(d_bg, frame i, mask s) — then the stream's own flip, then the YUYV pack if the batch asks for it.  A filter-off stream ignores its d_bg and blur
+ *     size (toggling the filter is one bit, as the 's' key is), but a blur size that is set must still be valid;
+ *   - result: per stream, composite, persistent mask and ofinal are bit-identical to bsx_step_batch_streams of that one stream with its d_bg and flags | its own
+ *     flags; a filter-off stream's state and mask are those of that call with any background, its composite the frame (converted from YUYV with
+ *     BSX_STEP_YUYV_IN) flipped as bsx_flip_bgr and packed as bsx_bgr_to_yuyv;
+ *   - n == 0: returns 0 and enqueues nothing;
+ *   - BSX_EINVAL before anything is enqueued, with a bsx_last_error text naming the position and value, for: the ids errors of bsx_step_batch_streams; settings
+ *     NULL with n > 0; a flag bit outside the sets above (a stream's or the batch's); a blur size that is even or above 31; a NULL or unaligned d_bg on a stream that
+ *     reads it; d_out overlapping d_frames or any stream's background (there is no in-place form); a pending pipelined composite; an odd width with YUYV out or in;
+ *     and every context or buffer the fused tile route does not take (width, roi.x, roi.w multiples of 4, 4-byte aligned buffers, no onmask callback). */
+BSX_API int bsx_step_batch_mixed(bsx_ctx* ctx, const int* ids, const uint8_t* d_frames, const bsx_stream_setting* settings,
+                                 uint8_t* d_out, int n, void* stream, unsigned flags);
 
 /* Reset the temporal state of the listed streams only (ofinal → 0, persistent mask → 255, as bsx_reset does for all) — a slot reused for a new camera.  The
  * other streams' state is untouched, and a pending pipelined composite is NOT dropped: the call is refused (BSX_EINVAL) while one is pending.  Same ids rules,
