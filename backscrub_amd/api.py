@@ -82,6 +82,8 @@ SYMBOLS = [
     ("bsx_step_batch_streams", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_uint]),
     ("bsx_reset_streams", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
     ("bsx_step_batch_mixed", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(_StreamSetting), C.c_void_p, C.c_int, C.c_void_p, C.c_uint]),
+    ("bsx_step_batch_vcam_mixed", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(_StreamSetting), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                            C.c_uint]),
     ("bsx_resize_bgr", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("bsx_bgr_to_yuyv", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("bsx_yuyv_to_bgr", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
@@ -289,7 +291,14 @@ class MaskGen:
             _check(lib().bsx_step_batch_mixed(self.h, arr, None, None, None, 0, _stream_ptr(), 0), self.h, "bsx_step_batch_mixed")
             return out
         self._step_out(out, n, yuyv)
-        st = (_StreamSetting * n)()
+        st = self._settings(settings)
+        flags = (1 if yuyv else 0) | (8 if no_mask else 0) | (16 if yuyv_in else 0)
+        _check(lib().bsx_step_batch_mixed(self.h, arr, _ptr(frames), st, _ptr(out), n, _stream_ptr(), flags), self.h, "bsx_step_batch_mixed")
+        return out
+
+    def _settings(self, settings):
+        """a list of StreamSetting → the C array of bsx_stream_setting, each one checked"""
+        st = (_StreamSetting * len(settings))()
         for i, s in enumerate(settings):
             if not isinstance(s, StreamSetting):
                 raise BsxError("settings[%d] is not a StreamSetting" % i)
@@ -298,9 +307,7 @@ class MaskGen:
                 raise BsxError("settings[%d]: bg is required unless bgblur or filter_off is set" % i)
             st[i].d_bg = self._setting_bg(s.bg, i) if s.bg is not None else None
             st[i].flags = s.flags()
-        flags = (1 if yuyv else 0) | (8 if no_mask else 0) | (16 if yuyv_in else 0)
-        _check(lib().bsx_step_batch_mixed(self.h, arr, _ptr(frames), st, _ptr(out), n, _stream_ptr(), flags), self.h, "bsx_step_batch_mixed")
-        return out
+        return st
 
     def reset_streams(self, ids):
         """reset the temporal state of the listed streams only (ofinal -> 0, mask -> 255; bsx_reset_streams) — a slot reused for a new camera"""
@@ -310,16 +317,46 @@ class MaskGen:
     def step_vcam(self, frames, bg, out, flip_h=False, flip_v=False, yuyv=False, yuyv_in=False, bgblur=0):
         """one main-loop iteration at the virtual camera's geometry (--vg, app/deepseg.cc:634-681): blend, flip, cv::resize to out's size and optionally the
         YUYV pack in one pass (bsx_step_batch_vcam).  out: contiguous cuda uint8 [>=n, out_h, out_w, 3], or [.., 2] with yuyv; out_w, out_h come from its shape."""
-        ch = 2 if yuyv else 3
-        if (out.dim() != 4 or out.shape[3] != ch or out.shape[1] <= 0 or out.shape[2] <= 0 or not out.is_contiguous() or not out.is_cuda
-                or out.dtype != _torch().uint8 or (yuyv and out.shape[2] % 2)):
-            raise BsxError("out must be a contiguous cuda uint8 tensor [n,out_h,out_w,%d]%s" % (ch, " with an even out_w" if yuyv else ""))
+        self._vcam_out(out, yuyv)
         n = self._n(frames, yuyv_in)
         if out.shape[0] < n:
             raise BsxError("out holds %d frames, the batch has %d" % (out.shape[0], n))
         flags, stride = self._step_flags(bg, n, flip_h, flip_v, yuyv, False, yuyv_in, bgblur)
         _check(lib().bsx_step_batch_vcam(self.h, _ptr(frames), _ptr(bg), stride, _ptr(out), int(out.shape[2]), int(out.shape[1]), n, _stream_ptr(), flags),
                self.h, "bsx_step_batch_vcam")
+        return out
+
+    def _vcam_out(self, out, yuyv):
+        """the output of a step at the virtual camera's geometry: out_w, out_h come from its shape"""
+        ch = 2 if yuyv else 3
+        if (out.dim() != 4 or out.shape[3] != ch or out.shape[1] <= 0 or out.shape[2] <= 0 or not out.is_contiguous() or not out.is_cuda
+                or out.dtype != _torch().uint8 or (yuyv and out.shape[2] % 2)):
+            raise BsxError("out must be a contiguous cuda uint8 tensor [n,out_h,out_w,%d]%s" % (ch, " with an even out_w" if yuyv else ""))
+
+    def step_vcam_mixed(self, frames, out, settings, ids=None, yuyv=False, yuyv_in=False):
+        """step_vcam where every stream has its OWN settings and the batch may be a chosen subset of the streams (bsx_step_batch_vcam_mixed): settings[i] (a
+        StreamSetting: background image, flip, bgblur, filter switch) belongs to frames[i] / out[i]; blend, the stream's flip, cv::resize to out's size and
+        optionally the YUYV pack in one pass.  ids: None = frame i is stream i, else the stream ids as in step_streams.  out: contiguous cuda uint8
+        [>=n, out_h, out_w, 3], or [.., 2] with yuyv; out_w, out_h come from its shape.  yuyv / yuyv_in are batch-wide (they define the buffer layouts)."""
+        settings = list(settings)
+        arr, n_ids = _ids(ids) if ids is not None else (None, None)
+        empty = ids is not None and n_ids == 0
+        if not empty:
+            self._vcam_out(out, yuyv)
+        n = 0 if empty else self._n(frames, yuyv_in)
+        if ids is not None and n_ids != n:
+            raise BsxError("%d ids for a batch of %d frames" % (n_ids, n))
+        if len(settings) != n:
+            raise BsxError("%d settings for a batch of %d frames" % (len(settings), n))
+        if n == 0:
+            _check(lib().bsx_step_batch_vcam_mixed(self.h, arr, None, None, None, 0, 0, 0, _stream_ptr(), 0), self.h, "bsx_step_batch_vcam_mixed")
+            return out
+        if out.shape[0] < n:
+            raise BsxError("out holds %d frames, the batch has %d" % (out.shape[0], n))
+        st = self._settings(settings)
+        flags = (1 if yuyv else 0) | (16 if yuyv_in else 0)
+        _check(lib().bsx_step_batch_vcam_mixed(self.h, arr, _ptr(frames), st, _ptr(out), int(out.shape[2]), int(out.shape[1]), n, _stream_ptr(), flags),
+               self.h, "bsx_step_batch_vcam_mixed")
         return out
 
     def step_pipelined(self, frames, bg, out, flip_h=False, flip_v=False, yuyv=False, no_mask=False, yuyv_in=False):

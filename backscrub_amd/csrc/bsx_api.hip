@@ -477,10 +477,10 @@ int refuse_pending(bsx_ctx* c, const char* fn) {
 // camera's raw 4:2:2 frames instead of BGR), BSX_STEP_BGBLUR(ksize) (background = blur of the stream's own frame); all folded into the kernels where they apply
 struct StepReq {
   const uint8_t* frames; const uint8_t* bg; size_t bg_stride; uint8_t* out;
-  int out_w, out_h, n;            // out_w x out_h: the capture size, except for bsx_step_batch_vcam
+  int out_w, out_h, n;            // out_w x out_h: the capture size, except for bsx_step_batch_vcam / _vcam_mixed
   unsigned flags; hipStream_t s;
   const int* ids;                 // bsx_step_batch_streams: the DEVICE copy of the stream ids (staged after the checks): frame i's state is slot ids[i]
-  const MixDesc* mix = nullptr;   // bsx_step_batch_mixed: the DEVICE descriptor table (staged after the checks) — position i's background / flip / filter-off
+  const MixDesc* mix = nullptr;   // bsx_step_batch_mixed / _vcam_mixed: the DEVICE descriptor table (staged after the checks) — position i's background / flip / filter-off
   const int* mix_pos = nullptr;   // ... followed by the positions of its blur streams, grouped by blur size (bsx_ctx::mix_blur)
   bool mix_bgr = false;           // ... some position composites over a blur of its frame: a YUYV batch is converted to BGR first
   bool mix_blur_due = false;      // ... blur groups not yet launched (BlurToScratch)
@@ -493,7 +493,7 @@ struct StepReq {
   bool out_overlaps(const uint8_t* p, size_t bytes) const { return out < p + bytes && p < out + out_bytes(); }
   bool overlap(const bsx_ctx* c) const { return out_overlaps(frames, (size_t)n * c->width * c->height * (yin() ? 2 : 3)); }
 };
-enum class Entry { Step, Streams, Vcam, Pipelined, Mixed };
+enum class Entry { Step, Streams, Vcam, Pipelined, Mixed, VcamMixed };
 
 // The fused tile kernel — mask up-scale + blur + blend [+ flip][+ YUYV pack] per tile, YUYV input converted on load — takes the request: no onmask callback
 // (the persistent masks are written by the same launch), the kernel's geometry and alignment, and no overlap it would read after writing
@@ -517,6 +517,19 @@ int check_step(bsx_ctx* c, const char* fn, const StepReq& r, Entry kind) {
     if (r.overlap(c)) return refuse(c, fn, "output overlaps the frames (the mixed step has no in-place form)");
     if (c->onmask || !mask_blend_fusable(c->width, c->height, c->roi, nullptr, 0, r.frames, r.out))
       return refuse(c, fn, "needs the fused mask + blend geometry (width, ROI x and width multiples of 4, 4-byte aligned buffers, no onmask callback)");
+    return BSX_OK;
+  }
+  if (kind == Entry::VcamMixed) {
+    // the batch's own rules at the virtual camera's geometry: the vcam step's (any capture width, ROI and alignment: its kernel has a byte-wise form and the masks
+    // come from process_impl), with the mixed step's layout-only flags; the per-position rules ran in mix_check
+    if (!r.frames || !r.out || r.n <= 0 || r.n > c->n_streams) return refuse(c, fn, "null buffer or batch size out of range");
+    if (r.flags & BSX_STEP_NO_MASK) return refuse(c, fn, "unsupported flags 0x%x (the no-mask step has no vcam form)", r.flags);
+    if (r.flags & ~(BSX_STEP_YUYV | BSX_STEP_YUYV_IN)) return refuse(c, fn, "flags 0x%x has bits outside yuyv / yuyv-in", r.flags);
+    if (r.out_w <= 0 || r.out_h <= 0) return refuse(c, fn, "output size %d x %d must be positive", r.out_w, r.out_h);
+    if (const int rc = refuse_pending(c, fn)) return rc;
+    if (r.yuyv() && (r.out_w & 1)) return refuse(c, fn, "YUYV output needs an even width (out_w = %d)", r.out_w);
+    if (r.yin() && (c->width & 1)) return refuse(c, fn, "YUYV input needs an even capture width (width = %d)", c->width);
+    if (r.overlap(c)) return refuse(c, fn, "output overlaps the frames (each output pixel reads a neighbourhood of input pixels)");
     return BSX_OK;
   }
   if (!r.frames || (!r.bg && !blur) || !r.out || r.n <= 0 || r.n > c->n_streams) return refuse(c, fn, "null buffer or batch size out of range");
@@ -543,12 +556,14 @@ int check_step(bsx_ctx* c, const char* fn, const StepReq& r, Entry kind) {
 
 // YuyvToBgr: YUYV frames the fused kernels do not read (or the blur needs as BGR) into the BGR scratch, then the BGR form; BlurToScratch: the blurred frames
 // into a scratch background, then the step with it; BlurBlend: masks, then blur + blend in one pass; Tile: masks, then mask up-scale + blur + blend per tile in
-// ONE launch; Composite: masks, then the plain blend [into a scratch, + flip][+ YUYV pack]; Vcam: masks, then blend + flip + resize [+ pack] in one pass
+// ONE launch; Composite: masks, then the plain blend [into a scratch, + flip][+ YUYV pack]; Vcam: masks, then blend + flip + resize [+ pack] in one pass (with
+// r.mix: every position by its own descriptor)
 enum class Route { YuyvToBgr, BlurToScratch, BlurBlend, Tile, Composite, Vcam };
 Route route_of(const bsx_ctx* c, const StepReq& r) {
-  if (r.mix) {                    // bsx_step_batch_mixed: [YUYV -> BGR] -> [blur groups into the scratch] -> ONE tile launch
+  if (r.mix) {                    // bsx_step_batch_mixed / _vcam_mixed: [YUYV -> BGR] -> [blur groups into the scratch] -> ONE tile launch / ONE resize-pass launch
     if (r.yin() && (r.mix_bgr || !prep_yuyv_fusable(c->width, c->roi, c->tab_down.tab))) return Route::YuyvToBgr;
-    return r.mix_blur_due ? Route::BlurToScratch : Route::Tile;
+    if (r.mix_blur_due) return Route::BlurToScratch;
+    return r.resize(c) ? Route::Vcam : Route::Tile;
   }
   const bool resize = r.resize(c);
   if (r.yin() && (r.bgblur() || !(resize ? prep_yuyv_fusable(c->width, c->roi, c->tab_down.tab) : tile_fusable(c, r)))) return Route::YuyvToBgr;
@@ -680,10 +695,14 @@ int run_step(bsx_ctx* c, StepReq r) {
       case Route::Tile: return run_tile(c, r);
       case Route::Composite: return run_composite(c, r);
       case Route::Vcam: {
-        if (const int rc = process_impl(c, r.frames, r.n, 0, r.s, r.yin())) return rc;
+        if (const int rc = process_impl(c, r.frames, r.n, 0, r.s, r.yin(), r.ids)) return rc;
         bsx_roctx::Range range("bsx:vcam");
-        BSX_HIP(c, launch_vcam_blend_resize(r.frames, r.yin(), r.bg, r.bg_stride, c->d_masks, r.out, c->width, c->height, vt->d.tab, vt->direct || c->vcam_direct, r.n,
-                                            r.s, r.flags & 7u));
+        if (r.mix)                // (vt->direct holds for every flip combination: vcam_tile_fits)
+          BSX_HIP(c, launch_vg_mixed(r.frames, r.yin(), r.mix, c->d_masks, r.ids, r.out, c->width, c->height, vt->d.tab, vt->direct || c->vcam_direct, r.n, r.s,
+                                     r.yuyv() ? 1u : 0u));
+        else
+          BSX_HIP(c, launch_vcam_blend_resize(r.frames, r.yin(), r.bg, r.bg_stride, c->d_masks, r.out, c->width, c->height, vt->d.tab, vt->direct || c->vcam_direct, r.n,
+                                              r.s, r.flags & 7u));
         return BSX_OK;
       }
     }
@@ -751,8 +770,9 @@ constexpr unsigned kStreamFlags = BSX_STEP_FLIP_H | BSX_STEP_FLIP_V | 0xFF00u | 
 static_assert(BSX_STEP_FLIP_H == kMixFlipH && BSX_STEP_FLIP_V == kMixFlipV && BSX_STREAM_FILTER_OFF == kMixFilterOff, "descriptor flags = the public bits");
 inline int setting_blur(const bsx_stream_setting& st) { return (st.flags & BSX_STREAM_FILTER_OFF) ? 0 : (int)((st.flags >> 8) & 255u); }   // 0: no blur to make
 
-// host-side validation of settings[0..n), next to ids_check: nothing is enqueued before it passes
-int mix_check(bsx_ctx* c, const char* fn, const bsx_stream_setting* st, const StepReq& r) {
+// host-side validation of settings[0..n), next to ids_check: nothing is enqueued before it passes.  any_align (the step at the virtual camera's geometry): a
+// background may lie at any address — its stream then takes the kernel's byte form
+int mix_check(bsx_ctx* c, const char* fn, const bsx_stream_setting* st, const StepReq& r, bool any_align) {
   if (r.n > 0 && !st) return refuse(c, fn, "settings is NULL");
   const size_t img = (size_t)c->width * c->height * 3;
   for (int i = 0; i < r.n; i++) {
@@ -762,8 +782,8 @@ int mix_check(bsx_ctx* c, const char* fn, const bsx_stream_setting* st, const St
     if (k && (k > 31 || !(k & 1))) return refuse(c, fn, "settings[%d]: blur size %d must be odd and <= 31", i, k);
     if ((f & BSX_STREAM_FILTER_OFF) || k) continue;               // reads no background
     if (!st[i].d_bg) return refuse(c, fn, "settings[%d]: d_bg is NULL", i);
-    if ((uintptr_t)st[i].d_bg & 3) return refuse(c, fn, "settings[%d]: d_bg %p is not 4-byte aligned", i, (const void*)st[i].d_bg);
-    if (r.frames && r.out && r.out_overlaps(st[i].d_bg, img)) return refuse(c, fn, "settings[%d]: output overlaps the background %p", i, (const void*)st[i].d_bg);
+    if (!any_align && ((uintptr_t)st[i].d_bg & 3)) return refuse(c, fn, "settings[%d]: d_bg %p is not 4-byte aligned", i, (const void*)st[i].d_bg);
+    if (r.frames && r.out && r.out_w > 0 && r.out_h > 0 && r.out_overlaps(st[i].d_bg, img)) return refuse(c, fn, "settings[%d]: output overlaps the background %p", i, (const void*)st[i].d_bg);
   }
   return BSX_OK;
 }
@@ -807,8 +827,12 @@ int mix_stage(bsx_ctx* c, const bsx_stream_setting* st, StepReq& r, int k) {
 // and run
 int step_call(bsx_ctx* c, const char* fn, Entry kind, StepReq r, const int* host_ids = nullptr, const bsx_stream_setting* settings = nullptr) {
   if (!c) return BSX_EINVAL;
-  if (kind != Entry::Vcam) { r.out_w = c->width; r.out_h = c->height; }
-  const bool mixed = kind == Entry::Mixed;
+  if (kind != Entry::Vcam && kind != Entry::VcamMixed) { r.out_w = c->width; r.out_h = c->height; }
+  if (kind == Entry::VcamMixed && !r.resize(c)) {                 // the capture size: bsx_step_batch_mixed with its own refusals (the no-mask form stays refused)
+    if (r.flags & BSX_STEP_NO_MASK) return refuse(c, fn, "unsupported flags 0x%x (the no-mask step has no vcam form)", r.flags);
+    kind = Entry::Mixed;
+  }
+  const bool mixed = kind == Entry::Mixed || kind == Entry::VcamMixed;
   if (kind == Entry::Streams || (mixed && host_ids)) {
     if (const int rc = ids_check(c, fn, host_ids, r.n)) return rc;
   } else if (mixed) {                                             // the dense form: the count rules of ids_check
@@ -816,7 +840,7 @@ int step_call(bsx_ctx* c, const char* fn, Entry kind, StepReq r, const int* host
     if (r.n > c->n_streams) return refuse(c, fn, "n = %d exceeds the context's %d streams", r.n, c->n_streams);
   }
   if ((kind == Entry::Streams || mixed) && r.n == 0) return refuse_pending(c, fn);   // (check_step refuses a pending composite for n > 0)
-  if (mixed) { if (const int rc = mix_check(c, fn, settings, r)) return rc; }
+  if (mixed) { if (const int rc = mix_check(c, fn, settings, r, kind == Entry::VcamMixed)) return rc; }
   if (const int rc = check_step(c, fn, r, kind)) return rc;
   DeviceGuard guard(c->device);
   if (kind != Entry::Streams && !mixed) return run_step(c, r);
@@ -1110,6 +1134,12 @@ int bsx_reset_streams(bsx_ctx* c, const int* ids, int n, void* stream) {
 }
 
 // ---- the main loop at the virtual camera's geometry (--vg, app/deepseg.cc:634-681): blend → flip → resize → YUYV pack with the resize folded in -----------------
+int bsx_step_batch_vcam_mixed(bsx_ctx* c, const int* ids, const uint8_t* d_frames, const bsx_stream_setting* settings, uint8_t* d_out, int out_w, int out_h, int n,
+                              void* stream, unsigned flags) {
+  return step_call(c, "bsx_step_batch_vcam_mixed", Entry::VcamMixed, StepReq{d_frames, nullptr, 0, d_out, out_w, out_h, n, flags, (hipStream_t)stream, nullptr}, ids,
+                   settings);
+}
+
 int bsx_step_batch_vcam(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_frame_stride, uint8_t* d_out, int out_w, int out_h, int n, void* stream,
                         unsigned flags) {
   return step_call(c, "bsx_step_batch_vcam", Entry::Vcam, StepReq{d_frames, d_bg, bg_frame_stride, d_out, out_w, out_h, n, flags, (hipStream_t)stream, nullptr});

@@ -148,6 +148,10 @@ hipError_t launch_gauss_blend(const uint8_t* frames, const uint8_t* masks, uint8
 bool vcam_tile_fits(const int* xofs, const int* yofs, int sw, int sh, int dw, int dh);
 hipError_t launch_vcam_blend_resize(const uint8_t* frames, bool yuyv_in, const uint8_t* bg, size_t bg_stride, const uint8_t* masks, uint8_t* out, int W, int H,
                                     ResizeTab tab, bool direct, int n, hipStream_t s, unsigned flags);
+// the same pass with every position's own settings (bsx_step_batch_vcam_mixed): desc[i] (device) gives position i's background, flip bits and filter switch, its
+// mask is slot slot_of[i]'s (device; NULL: slot i).  flags: bit 0 (YUYV pack) only — the flips are the descriptors'.  Any background alignment (byte form per stream)
+hipError_t launch_vg_mixed(const uint8_t* frames, bool yuyv_in, const MixDesc* desc, const uint8_t* masks, const int* slot_of, uint8_t* out, int W, int H,
+                           ResizeTab tab, bool direct, int n, hipStream_t s, unsigned flags);
 // bsx_reset_streams: state slots ids[0..n) (a device array) back to their initial values, ofinal -> 0 and mask -> 255 (what bsx_reset does for every slot)
 hipError_t launch_reset_slots(uint8_t* ofinal, size_t ofinal_bytes, uint8_t* masks, size_t mask_bytes, const int* ids, int n, hipStream_t s);
 // fill

@@ -1043,50 +1043,82 @@ static_assert(kVW * kVH == 2 * 4 * kThreads, "vcam tile: two 4-pixel groups per 
 constexpr int kVcYuyvOut = 1, kVcFlipH = 2, kVcFlipV = 4, kVcWords = 8, kVcOutWords = 16;      // bits of the kernel's `opt` word
 struct __attribute__((packed, aligned(4))) VcW2 { uint32_t x, y; };
 
-// composite of ONE pixel (cx, cy) as B | G << 8 | R << 16: byte loads, any geometry (YIN: U / V from the macropixel of column cx & ~1, yuyv_to_bgr_k's integers)
+// the frame's pixel (cx, cy), p = cy * W + cx, as B | G << 8 | R << 16: byte loads (YIN: U / V from the macropixel of column cx & ~1, yuyv_to_bgr_k's integers)
 template <bool YIN>
-__device__ __forceinline__ uint32_t vcam_px(const uint8_t* __restrict__ fr, const uint8_t* __restrict__ bgp, const uint8_t* __restrict__ mk, int W, int cx, int cy) {
-  const long p = (long)cy * W + cx;
-  const uint8_t* a = bgp + p * 3;
-  const uint32_t aw = (uint32_t)a[0] | ((uint32_t)a[1] << 8) | ((uint32_t)a[2] << 16);
-  uint32_t bw;
+__device__ __forceinline__ uint32_t vcam_frame_px(const uint8_t* __restrict__ fr, int W, int cx, int cy, long p) {
   if constexpr (YIN) {
     const uint8_t* q = fr + ((long)cy * W + (cx & ~1)) * 2;
-    bw = yuv_tap_to_bgr((uint32_t)q[(cx & 1) * 2] | ((uint32_t)q[1] << 8) | ((uint32_t)q[3] << 16));
+    return yuv_tap_to_bgr((uint32_t)q[(cx & 1) * 2] | ((uint32_t)q[1] << 8) | ((uint32_t)q[3] << 16));
   } else {
     const uint8_t* b = fr + p * 3;
-    bw = (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16);
+    return (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16);
   }
+}
+// composite of ONE pixel (cx, cy) as B | G << 8 | R << 16: byte loads, any geometry.
+// SEL (the per-stream form, vg_mixed_k): with `off` (workgroup-uniform: the stream's filter is switched off) the composite IS the frame pixel — neither the
+// background nor the mask is read.  A template parameter: the dense kernel compiles to what it was.
+template <bool YIN, bool SEL = false>
+__device__ __forceinline__ uint32_t vcam_px(const uint8_t* __restrict__ fr, const uint8_t* __restrict__ bgp, const uint8_t* __restrict__ mk, int W, int cx, int cy,
+                                            bool off = false) {
+  const long p = (long)cy * W + cx;
+  if constexpr (SEL) {               // the frame's load goes out first, whatever the switch says: the background's and the mask's then join it in flight
+    const uint32_t fw = vcam_frame_px<YIN>(fr, W, cx, cy, p);
+    if (off) return fw & 0xffffffu;
+    const uint8_t* a = bgp + p * 3;
+    const uint32_t m = (uint32_t)mk[p] * 0x00010001u;
+    return blend_word((uint32_t)a[0] | ((uint32_t)a[1] << 8) | ((uint32_t)a[2] << 16), fw, m, m);
+  }
+  const uint8_t* a = bgp + p * 3;
+  const uint32_t aw = (uint32_t)a[0] | ((uint32_t)a[1] << 8) | ((uint32_t)a[2] << 16);
+  const uint32_t bw = vcam_frame_px<YIN>(fr, W, cx, cy, p);
   const uint32_t m = (uint32_t)mk[p] * 0x00010001u;
   return blend_word(aw, bw, m, m);                                   // byte 3: 0 blended with 0
 }
-// composite of the 4-pixel group (cx .. cx + 3, cy) as four pixel words.  words: W % 4 == 0 and 4-byte aligned images (cx % 4 == 0 here) — 12 B of background,
-// 12 B (YIN: 8 B) of frame and 4 mask bytes, blend_quad; else pixel by pixel, columns past the row's end left 0 (no tap reads them: x1 <= W - 1)
+// the frame's 4-pixel group at p (12 B, YIN: 8 B) as three BGR words, and three such words as four pixel words
 template <bool YIN>
+__device__ __forceinline__ void vcam_frame_quad(const uint8_t* __restrict__ fr, long p, uint32_t b3[3]) {
+  if constexpr (YIN) {
+    const VcW2 y = *reinterpret_cast<const VcW2*>(fr + p * 2);
+    yuyv4_to_bgr3(y.x, y.y, b3);
+  } else {
+    const u3v bv = *reinterpret_cast<const u3v*>(fr + p * 3);
+    b3[0] = bv.x; b3[1] = bv.y; b3[2] = bv.z;
+  }
+}
+__device__ __forceinline__ void vcam_quad_words(const uint32_t o[3], uint32_t w[4]) {
+  w[0] = o[0] & 0xffffffu;
+  w[1] = (o[0] >> 24) | ((o[1] & 0xffffu) << 8);
+  w[2] = (o[1] >> 16) | ((o[2] & 0xffu) << 16);
+  w[3] = o[2] >> 8;
+}
+// composite of the 4-pixel group (cx .. cx + 3, cy) as four pixel words.  words: W % 4 == 0 and 4-byte aligned images (cx % 4 == 0 here) — 12 B of background,
+// 12 B (YIN: 8 B) of frame and 4 mask bytes, blend_quad; else pixel by pixel, columns past the row's end left 0 (no tap reads them: x1 <= W - 1).  SEL / off: as vcam_px
+template <bool YIN, bool SEL = false>
 __device__ __forceinline__ void vcam_group(const uint8_t* __restrict__ fr, const uint8_t* __restrict__ bgp, const uint8_t* __restrict__ mk, int W, int cx, int cy,
-                                           bool words, uint32_t w[4]) {
+                                           bool words, uint32_t w[4], bool off = false) {
   if (words) {
     const long p = (long)cy * W + cx;
+    if constexpr (SEL) {             // (the frame's load first, as in vcam_px)
+      uint32_t f3[3], o[3];
+      vcam_frame_quad<YIN>(fr, p, f3);
+      if (off) { vcam_quad_words(f3, w); return; }
+      const u3v av = *reinterpret_cast<const u3v*>(bgp + p * 3);
+      const uint32_t a3[3] = {av.x, av.y, av.z};
+      blend_quad(a3, f3, *reinterpret_cast<const uint32_t*>(mk + p), o);
+      vcam_quad_words(o, w);
+      return;
+    }
     const u3v av = *reinterpret_cast<const u3v*>(bgp + p * 3);
     uint32_t b3[3];
-    if constexpr (YIN) {
-      const VcW2 y = *reinterpret_cast<const VcW2*>(fr + p * 2);
-      yuyv4_to_bgr3(y.x, y.y, b3);
-    } else {
-      const u3v bv = *reinterpret_cast<const u3v*>(fr + p * 3);
-      b3[0] = bv.x; b3[1] = bv.y; b3[2] = bv.z;
-    }
+    vcam_frame_quad<YIN>(fr, p, b3);
     const uint32_t a3[3] = {av.x, av.y, av.z};
     uint32_t o[3];
     blend_quad(a3, b3, *reinterpret_cast<const uint32_t*>(mk + p), o);
-    w[0] = o[0] & 0xffffffu;
-    w[1] = (o[0] >> 24) | ((o[1] & 0xffffu) << 8);
-    w[2] = (o[1] >> 16) | ((o[2] & 0xffu) << 16);
-    w[3] = o[2] >> 8;
+    vcam_quad_words(o, w);
     return;
   }
 #pragma unroll
-  for (int k = 0; k < 4; k++) w[k] = cx + k < W ? vcam_px<YIN>(fr, bgp, mk, W, cx + k, cy) : 0u;
+  for (int k = 0; k < 4; k++) w[k] = cx + k < W ? vcam_px<YIN, SEL>(fr, bgp, mk, W, cx + k, cy, off) : 0u;
 }
 // one output channel from the four tap words: sample_linear's horizontal pass (11-bit coefficients) and vertical pass
 __device__ __forceinline__ uint32_t vcam_lerp(uint32_t t00, uint32_t t01, uint32_t t10, uint32_t t11, int a0, int a1, int b0, int b1, int sh) {
@@ -1094,86 +1126,25 @@ __device__ __forceinline__ uint32_t vcam_lerp(uint32_t t00, uint32_t t01, uint32
   const int h1 = (int)((t10 >> sh) & 255u) * a0 + (int)((t11 >> sh) & 255u) * a1;
   return (uint32_t)((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2) & 255u;
 }
+// (the body: vcam_tile.inc)
 template <bool DIRECT, bool YIN>
 __global__ __launch_bounds__(kThreads) void vcam_blend_resize_k(const uint8_t* __restrict__ frames, const uint8_t* __restrict__ bg, long bg_stride,
                                                                const uint8_t* __restrict__ masks, uint8_t* __restrict__ out, int W, int H, ResizeTab tab, int ntx,
                                                                int opt) {
-  __shared__ uint32_t s_px[DIRECT ? 1 : kVLdsWords];
-  const int tid = threadIdx.x, ty = (int)blockIdx.x / ntx, tx = (int)blockIdx.x - ty * ntx;
-  const long n = blockIdx.y;
-  const int dw = tab.dw, dh = tab.dh;
-  const int dx0 = tx * kVW, dy0 = ty * kVH, dx1 = min(dx0 + kVW, dw) - 1, dy1 = min(dy0 + kVH, dh) - 1;
-  const bool fh = (opt & kVcFlipH) != 0, fv = (opt & kVcFlipV) != 0;
-  const uint8_t* fr = frames + n * (long)W * H * (YIN ? 2 : 3);
-  const uint8_t* bgp = bg + n * bg_stride;
-  const uint8_t* mk = masks + n * (long)W * H;
-  int gx0 = 0, cy_lo = 0, rw = 0;                                   // LDS image: composite rows cy_lo.., columns gx0.., rw words per row
-  if constexpr (!DIRECT) {
-    const int fx_lo = tab.xofs[dx0], fx_hi = min(tab.xofs[dx1] + 1, W - 1);
-    const int fy_lo = min(max(tab.yofs[dy0], 0), H - 1), fy_hi = min(max(tab.yofs[dy1] + 1, 0), H - 1);
-    const int cx_lo = fh ? W - 1 - fx_hi : fx_lo, cx_hi = fh ? W - 1 - fx_lo : fx_hi;
-    cy_lo = fv ? H - 1 - fy_hi : fy_lo;
-    gx0 = cx_lo & ~3;
-    const int ng = ((cx_hi - gx0) >> 2) + 1, items = (fy_hi - fy_lo + 1) * ng;     // rows * ng * 4 <= kVLdsWords: vcam_tile_fits
-    rw = 4 * ng;
-    const bool words = (opt & kVcWords) != 0;
-    for (int i = tid; i < items; i += kThreads) {
-      const int r = i / ng, g = i - r * ng;
-      uint32_t w[4];
-      vcam_group<YIN>(fr, bgp, mk, W, gx0 + 4 * g, cy_lo + r, words, w);
-      *reinterpret_cast<uint4*>(s_px + r * rw + 4 * g) = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-    __syncthreads();
-  }
-  const bool yout = (opt & kVcYuyvOut) != 0, owords = (opt & kVcOutWords) != 0;
-#pragma unroll
-  for (int j = 0; j < 2; j++) {
-    const int gi = tid + j * kThreads, ry = gi / (kVW / 4), dy = dy0 + ry, dx = dx0 + 4 * (gi - ry * (kVW / 4));
-    if (dy > dy1 || dx > dx1) continue;
-    const int sy = tab.yofs[dy], b0 = tab.ya[2 * dy], b1 = tab.ya[2 * dy + 1];
-    int y0 = min(max(sy, 0), H - 1), y1 = min(max(sy + 1, 0), H - 1);
-    if (fv) { y0 = H - 1 - y0; y1 = H - 1 - y1; }
-    const int cnt = min(4, dx1 - dx + 1);
-    uint32_t q[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const int d = min(dx + k, dx1);                                // past the tile's last column: the last pixel again (never stored)
-      const int a0 = tab.xa[2 * d], a1 = tab.xa[2 * d + 1];
-      int x0 = tab.xofs[d], x1 = min(x0 + 1, W - 1);
-      if (fh) { x0 = W - 1 - x0; x1 = W - 1 - x1; }
-      uint32_t t00, t01, t10, t11;
-      if constexpr (DIRECT) {
-        t00 = vcam_px<YIN>(fr, bgp, mk, W, x0, y0); t01 = vcam_px<YIN>(fr, bgp, mk, W, x1, y0);
-        t10 = vcam_px<YIN>(fr, bgp, mk, W, x0, y1); t11 = vcam_px<YIN>(fr, bgp, mk, W, x1, y1);
-      } else {
-        const int r0 = (y0 - cy_lo) * rw - gx0, r1 = (y1 - cy_lo) * rw - gx0;
-        t00 = s_px[r0 + x0]; t01 = s_px[r0 + x1]; t10 = s_px[r1 + x0]; t11 = s_px[r1 + x1];
-      }
-      q[k] = vcam_lerp(t00, t01, t10, t11, a0, a1, b0, b1, 0) | (vcam_lerp(t00, t01, t10, t11, a0, a1, b0, b1, 8) << 8) |
-             (vcam_lerp(t00, t01, t10, t11, a0, a1, b0, b1, 16) << 16);
-    }
-    const long o = n * (long)dw * dh + (long)dy * dw + dx;
-    if (yout) {                                                      // dw even: cnt is 2 or 4, whole pairs
-      const uint32_t p0 = yuyv_pair(q[0] & 255u, (q[0] >> 8) & 255u, q[0] >> 16, q[1] & 255u, (q[1] >> 8) & 255u, q[1] >> 16);
-      const uint32_t p1 = yuyv_pair(q[2] & 255u, (q[2] >> 8) & 255u, q[2] >> 16, q[3] & 255u, (q[3] >> 8) & 255u, q[3] >> 16);
-      uint8_t* op = out + o * 2;
-      if (owords && cnt == 4) *reinterpret_cast<VcW2*>(op) = VcW2{p0, p1};
-      else if (owords) *reinterpret_cast<uint32_t*>(op) = p0;
-      else {
-#pragma unroll
-        for (int b = 0; b < 4; b++) { op[b] = (uint8_t)(p0 >> (8 * b)); if (cnt == 4) op[4 + b] = (uint8_t)(p1 >> (8 * b)); }
-      }
-    } else {
-      uint8_t* op = out + o * 3;
-      if (owords && cnt == 4) {
-        *reinterpret_cast<u3v*>(op) = u3v{q[0] | (q[1] << 24), (q[1] >> 8) | (q[2] << 16), (q[2] >> 16) | (q[3] << 8)};
-      } else {
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-          if (k < cnt) { op[3 * k] = (uint8_t)q[k]; op[3 * k + 1] = (uint8_t)(q[k] >> 8); op[3 * k + 2] = (uint8_t)(q[k] >> 16); }
-      }
-    }
-  }
+  constexpr bool SEL = false;
+  [[maybe_unused]] const int* const slot_of = nullptr;
+#include "vcam_tile.inc"
+}
+// The per-stream form (bsx_step_batch_vcam_mixed): every position with its own background, flip bits and filter switch (desc[n]) and the mask of its own slot —
+// the same body with SEL.  A kernel of its own, not a further parameter of the dense one, whose instantiations stay the four they were.
+static_assert(kVcFlipH == (int)kMixFlipH && kVcFlipV == (int)kMixFlipV, "a descriptor's flip bits are the opt word's");
+template <bool DIRECT, bool YIN>
+__global__ __launch_bounds__(kThreads) void vg_mixed_k(const uint8_t* __restrict__ frames, const MixDesc* __restrict__ desc, const uint8_t* __restrict__ masks,
+                                                      const int* __restrict__ slot_of, uint8_t* __restrict__ out, int W, int H, ResizeTab tab, int ntx, int opt) {
+  constexpr bool SEL = true;
+  const uint8_t* bg = reinterpret_cast<const uint8_t*>(desc);
+  long bg_stride = 0;
+#include "vcam_tile.inc"
 }
 
 }  // namespace
@@ -1669,6 +1640,8 @@ hipError_t launch_gauss_blend(const uint8_t* frames, const uint8_t* masks, uint8
 // ---- composite at the virtual camera's geometry --------------------------------------------------------------------------------
 // Does the source footprint of every output tile (both column orders: the footprint's 4-pixel grid depends on the horizontal flip) fit vcam_blend_resize_k's
 // LDS staging area?  The same arithmetic as the kernel's; every (tile column, tile row) pair exists, so the largest product is the largest width times height.
+// All four flip combinations are covered, which the per-stream kernel (vg_mixed_k: every workgroup its own flips) relies on: a vertical flip mirrors the rows
+// fy_lo .. fy_hi as a block — the kernel stages fy_hi - fy_lo + 1 rows either way — and the column count does not depend on it.
 bool vcam_tile_fits(const int* xofs, const int* yofs, int sw, int sh, int dw, int dh) {
   auto clampi = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
   int max_rows = 0, max_cols = 0;
@@ -1706,6 +1679,30 @@ hipError_t launch_vcam_blend_resize(const uint8_t* frames, bool yuyv_in, const u
     if (direct) { if (yuyv_in) BSX_VC(true, true); else BSX_VC(true, false); }
     else { if (yuyv_in) BSX_VC(false, true); else BSX_VC(false, false); }
 #undef BSX_VC
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_vg_mixed(const uint8_t* frames, bool yuyv_in, const MixDesc* desc, const uint8_t* masks, const int* slot_of, uint8_t* out, int W, int H,
+                           ResizeTab tab, bool direct, int n, hipStream_t s, unsigned flags) {
+  if (tab.mode != 0 || tab.sw != W || tab.sh != H || (yuyv_in && (W & 1)) || ((flags & 1) && (tab.dw & 1)) || (flags & ~1u)) return hipErrorInvalidValue;
+  const int ntx = (tab.dw + kVW - 1) / kVW, nty = (tab.dh + kVH - 1) / kVH;
+  if ((long)ntx * nty >= (1l << 31)) return hipErrorInvalidValue;
+  const bool words = W % 4 == 0 && ((((uintptr_t)frames) | ((uintptr_t)masks)) & 3) == 0;      // and the position's background: decided per workgroup
+  const bool owords = (((uintptr_t)out) & 3) == 0 && ((flags & 1) || tab.dw % 4 == 0);
+  const int opt = (int)(flags & 1u) | (words ? kVcWords : 0) | (owords ? kVcOutWords : 0);
+  const size_t fb = (size_t)W * H * (yuyv_in ? 2 : 3), ob = (size_t)tab.dw * tab.dh * ((flags & 1) ? 2 : 3);
+  for (int n0 = 0; n0 < n; n0 += kMaxGridY) {
+    const int nn = n - n0 < kMaxGridY ? n - n0 : kMaxGridY;
+    const dim3 grid((unsigned)(ntx * nty), (unsigned)nn);
+    const uint8_t* f = frames + (size_t)n0 * fb;
+    const uint8_t* m = slot_of ? masks : masks + (size_t)n0 * W * H;
+    const int* so = slot_of ? slot_of + n0 : nullptr;
+    uint8_t* o = out + (size_t)n0 * ob;
+#define BSX_VG(D, Y) vg_mixed_k<D, Y><<<grid, kThreads, 0, s>>>(f, desc + n0, m, so, o, W, H, tab, ntx, opt)
+    if (direct) { if (yuyv_in) BSX_VG(true, true); else BSX_VG(true, false); }
+    else { if (yuyv_in) BSX_VG(false, true); else BSX_VG(false, false); }
+#undef BSX_VG
   }
   return hipGetLastError();
 }

@@ -1,0 +1,109 @@
+// The body of the two kernels that composite at the virtual camera's geometry (kernels_img.hip: vcam_blend_resize_k, SEL = false, and vg_mixed_k, SEL = true), included
+// INSIDE each kernel: one output tile of position n = blockIdx.y.  It is shared as text and not as a device function because the dense kernel has to stay the code
+// it was: with the body in an inlined function the compiler schedules and allocates the same statements differently.  The including kernel provides the names
+//   frames, bg, bg_stride, masks, slot_of, out, W, H, tab, ntx, opt   and   constexpr bool SEL
+// SEL: `bg` is the batch's MixDesc table — position n's background, its own flip bits and its filter switch come from desc[n] (one 16-byte uniform load), its mask
+// is slot slot_of[n]'s (NULL: slot n); all of it is workgroup-uniform, so the tile's footprint below is the workgroup's own.  Filter off: the composite is the frame
+// (vcam_px / vcam_group with `off`); a background that is not 4-byte aligned takes the byte form for its stream alone.
+  __shared__ uint32_t s_px[DIRECT ? 1 : kVLdsWords];
+  const int tid = threadIdx.x, ty = (int)blockIdx.x / ntx, tx = (int)blockIdx.x - ty * ntx;
+  const long n = blockIdx.y;
+  const int dw = tab.dw, dh = tab.dh;
+  const int dx0 = tx * kVW, dy0 = ty * kVH, dx1 = min(dx0 + kVW, dw) - 1, dy1 = min(dy0 + kVH, dh) - 1;
+  [[maybe_unused]] bool off = false;
+  [[maybe_unused]] long slot = n;
+  if constexpr (SEL) {                                               // position n's descriptor: background, flips, filter switch; its mask is its slot's
+    unsigned fl;
+    bg = mix_desc(bg, (int)n, &fl); bg_stride = 0;
+    off = (fl & kMixFilterOff) != 0;
+    opt |= (int)(fl & (kMixFlipH | kMixFlipV));
+    if (!off && ((uintptr_t)bg & 3u)) opt &= ~kVcWords;
+    if (slot_of) slot = slot_of[n];
+  }
+  const bool fh = (opt & kVcFlipH) != 0, fv = (opt & kVcFlipV) != 0;
+  const uint8_t* fr = frames + n * (long)W * H * (YIN ? 2 : 3);
+  const uint8_t* bgp = bg + (SEL ? 0l : n * bg_stride);
+  const uint8_t* mk = masks + (SEL ? slot : n) * (long)W * H;
+  int gx0 = 0, cy_lo = 0, rw = 0;                                   // LDS image: composite rows cy_lo.., columns gx0.., rw words per row
+  if constexpr (!DIRECT) {
+    const int fx_lo = tab.xofs[dx0], fx_hi = min(tab.xofs[dx1] + 1, W - 1);
+    const int fy_lo = min(max(tab.yofs[dy0], 0), H - 1), fy_hi = min(max(tab.yofs[dy1] + 1, 0), H - 1);
+    const int cx_lo = fh ? W - 1 - fx_hi : fx_lo, cx_hi = fh ? W - 1 - fx_lo : fx_hi;
+    cy_lo = fv ? H - 1 - fy_hi : fy_lo;
+    gx0 = cx_lo & ~3;
+    const int ng = ((cx_hi - gx0) >> 2) + 1, items = (fy_hi - fy_lo + 1) * ng;     // rows * ng * 4 <= kVLdsWords: vcam_tile_fits
+    rw = 4 * ng;
+    const bool words = (opt & kVcWords) != 0;
+    // the staging loop, once per value of the filter switch: with `off` a literal the loop of a filtered stream is the dense kernel's — its three loads go out
+    // back to back — where a run-time test inside the loop leaves the frame's load waiting behind the mask's (measured: docs/design/05d-image-kernels.md)
+#define BSX_VG_STAGE(OFF)                                                                    \
+    for (int i = tid; i < items; i += kThreads) {                                            \
+      const int r = i / ng, g = i - r * ng;                                                  \
+      uint32_t w[4];                                                                         \
+      vcam_group<YIN, SEL>(fr, bgp, mk, W, gx0 + 4 * g, cy_lo + r, words, w, OFF);           \
+      *reinterpret_cast<uint4*>(s_px + r * rw + 4 * g) = make_uint4(w[0], w[1], w[2], w[3]); \
+    }
+    if constexpr (SEL) {
+      if (off) { BSX_VG_STAGE(true) } else { BSX_VG_STAGE(false) }
+    } else {
+      BSX_VG_STAGE(false)
+    }
+#undef BSX_VG_STAGE
+    __syncthreads();
+  }
+  const bool yout = (opt & kVcYuyvOut) != 0, owords = (opt & kVcOutWords) != 0;
+#pragma unroll
+  for (int j = 0; j < 2; j++) {
+    const int gi = tid + j * kThreads, ry = gi / (kVW / 4), dy = dy0 + ry, dx = dx0 + 4 * (gi - ry * (kVW / 4));
+    if (dy > dy1 || dx > dx1) continue;
+    const int sy = tab.yofs[dy], b0 = tab.ya[2 * dy], b1 = tab.ya[2 * dy + 1];
+    int y0 = min(max(sy, 0), H - 1), y1 = min(max(sy + 1, 0), H - 1);
+    if (fv) { y0 = H - 1 - y0; y1 = H - 1 - y1; }
+    const int cnt = min(4, dx1 - dx + 1);
+    uint32_t q[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const int d = min(dx + k, dx1);                                // past the tile's last column: the last pixel again (never stored)
+      const int a0 = tab.xa[2 * d], a1 = tab.xa[2 * d + 1];
+      int x0 = tab.xofs[d], x1 = min(x0 + 1, W - 1);
+      if (fh) { x0 = W - 1 - x0; x1 = W - 1 - x1; }
+      uint32_t t00, t01, t10, t11;
+      if constexpr (DIRECT) {
+#define BSX_VG_TAPS(OFF)                                                                                                 \
+        t00 = vcam_px<YIN, SEL>(fr, bgp, mk, W, x0, y0, OFF); t01 = vcam_px<YIN, SEL>(fr, bgp, mk, W, x1, y0, OFF); \
+        t10 = vcam_px<YIN, SEL>(fr, bgp, mk, W, x0, y1, OFF); t11 = vcam_px<YIN, SEL>(fr, bgp, mk, W, x1, y1, OFF);
+        if constexpr (SEL) {                                         // (once per value of the filter switch, as the staging loop)
+          if (off) { BSX_VG_TAPS(true) } else { BSX_VG_TAPS(false) }
+        } else {
+          BSX_VG_TAPS(false)
+        }
+#undef BSX_VG_TAPS
+      } else {
+        const int r0 = (y0 - cy_lo) * rw - gx0, r1 = (y1 - cy_lo) * rw - gx0;
+        t00 = s_px[r0 + x0]; t01 = s_px[r0 + x1]; t10 = s_px[r1 + x0]; t11 = s_px[r1 + x1];
+      }
+      q[k] = vcam_lerp(t00, t01, t10, t11, a0, a1, b0, b1, 0) | (vcam_lerp(t00, t01, t10, t11, a0, a1, b0, b1, 8) << 8) |
+             (vcam_lerp(t00, t01, t10, t11, a0, a1, b0, b1, 16) << 16);
+    }
+    const long o = n * (long)dw * dh + (long)dy * dw + dx;
+    if (yout) {                                                      // dw even: cnt is 2 or 4, whole pairs
+      const uint32_t p0 = yuyv_pair(q[0] & 255u, (q[0] >> 8) & 255u, q[0] >> 16, q[1] & 255u, (q[1] >> 8) & 255u, q[1] >> 16);
+      const uint32_t p1 = yuyv_pair(q[2] & 255u, (q[2] >> 8) & 255u, q[2] >> 16, q[3] & 255u, (q[3] >> 8) & 255u, q[3] >> 16);
+      uint8_t* op = out + o * 2;
+      if (owords && cnt == 4) *reinterpret_cast<VcW2*>(op) = VcW2{p0, p1};
+      else if (owords) *reinterpret_cast<uint32_t*>(op) = p0;
+      else {
+#pragma unroll
+        for (int b = 0; b < 4; b++) { op[b] = (uint8_t)(p0 >> (8 * b)); if (cnt == 4) op[4 + b] = (uint8_t)(p1 >> (8 * b)); }
+      }
+    } else {
+      uint8_t* op = out + o * 3;
+      if (owords && cnt == 4) {
+        *reinterpret_cast<u3v*>(op) = u3v{q[0] | (q[1] << 24), (q[1] >> 8) | (q[2] << 16), (q[2] >> 16) | (q[3] << 8)};
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+          if (k < cnt) { op[3 * k] = (uint8_t)q[k]; op[3 * k + 1] = (uint8_t)(q[k] >> 8); op[3 * k + 2] = (uint8_t)(q[k] >> 16); }
+      }
+    }
+  }

@@ -22,6 +22,7 @@
  *   bsx_step_batch_vcam    … with the resize to the virtual camera's geometry (--vg) fused  app/deepseg.cc:634-681 (the resize: :675-679)
  *   bsx_step_batch_streams … for the streams that HAVE a new frame, addressed by id  app/deepseg.cc:182-216 (one filter step per new frame)
  *   bsx_step_batch_mixed   … with each stream's own settings: -b / -p bgblur / -H / -V and the s / h / v keys  app/deepseg.cc:387-437, 596-673, 777-790
+ *   bsx_step_batch_vcam_mixed  … both: each stream's own settings, written at the virtual camera's geometry  app/deepseg.cc:387-437, 634-681
  *   bsx_reset_streams      bsx_reset for a chosen subset of the streams (a slot reused for a new camera)
  *                          (set_input_frame → mask → alpha_blend), batched
  *   bsx_resize_bgr         grab_background() cv::resize   app/background.cc:178-194
@@ -122,7 +123,7 @@ BSX_API int bsx_process_host(bsx_ctx* ctx, int stream_idx, const uint8_t* h_bgr,
                      uint8_t* h_mask, size_t mask_stride);
 
 /* Batched device path: frames [n][height][width][3] u8 contiguous (n <= n_streams; frame i
- * belongs to stream i — the dense contract; only bsx_step_batch_streams takes stream ids).  Updates each stream's temporal state and its persistent full-frame
+ * belongs to stream i — the dense contract; bsx_step_batch_streams, bsx_step_batch_mixed and bsx_step_batch_vcam_mixed take stream ids).  Updates each stream's temporal state and its persistent full-frame
  * mask.  If d_masks != NULL the masks are also copied there ([n][height][width]).
  * Asynchronous on `stream` unless callbacks are set (each callback needs a stream sync). */
 BSX_API int bsx_process_batch(bsx_ctx* ctx, const uint8_t* d_frames, int n, uint8_t* d_masks, void* stream);
@@ -193,7 +194,8 @@ BSX_API int bsx_step_batch_ex(bsx_ctx* ctx, const uint8_t* d_frames, const uint8
  *   - BSX_EINVAL, with a bsx_last_error text naming the offending position and value, for a duplicate id, an id out of range, n < 0 or n > n_streams; also for
  *     a pending pipelined composite and every argument bsx_step_batch_ex refuses.  All checks run on the host before anything is enqueued: a refused call changes
  *     no state.
- * bsx_step_batch_pipelined, bsx_step_batch_vcam and bsx_process_batch keep the dense contract (frame i = stream i). */
+ * bsx_step_batch_mixed and bsx_step_batch_vcam_mixed take the same ids (or NULL for the dense form); bsx_step_batch_pipelined, bsx_step_batch_vcam and
+ * bsx_process_batch keep the dense contract (frame i = stream i). */
 BSX_API int bsx_step_batch_streams(bsx_ctx* ctx, const int* ids, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_frame_stride,
                                    uint8_t* d_out, int n, void* stream, unsigned flags);
 
@@ -257,6 +259,29 @@ BSX_API int bsx_step_batch_pipelined(bsx_ctx* ctx, const uint8_t* d_frames, cons
  *   - out_w == width and out_h == height: the call IS bsx_step_batch_ex(flags). */
 BSX_API int bsx_step_batch_vcam(bsx_ctx* ctx, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_frame_stride,
                                 uint8_t* d_out, int out_w, int out_h, int n, void* stream, unsigned flags);
+
+/* bsx_step_batch_vcam for a chosen subset of the streams, each with its OWN settings — one reference process per camera with its own -b, -p bgblur, -H / -V,
+ * its s / h / v keys AND its --vg — in one mask pipeline and ONE pass that reads each position's descriptor, frame, background and mask taps and writes the
+ * output at (out_w, out_h): no capture-size composite, no full-size resized image, no caller-owned scratch.
+ *   - ids: NULL = the dense contract (frame i is stream i); otherwise exactly the rules, staging ring and refusals of bsx_step_batch_streams: the temporal state
+ *     and persistent mask of stream ids[i] advance in place, every other stream is untouched;
+ *   - settings[0..n): the bsx_stream_setting of bsx_step_batch_mixed, same flag set and meaning (d_bg: a capture-size background; BSX_STEP_FLIP_H | BSX_STEP_FLIP_V |
+ *     BSX_STEP_BGBLUR(k) | BSX_STREAM_FILTER_OFF); here d_bg may lie at any address (an unaligned image costs its own stream the byte-wise loads);
+ *   - flags (batch-wide, the buffer layouts): BSX_STEP_YUYV | BSX_STEP_YUYV_IN only; BSX_STEP_NO_MASK is refused, as bsx_step_batch_vcam refuses it;
+ *   - d_out: [n][out_h][out_w][3], or [..][2] with BSX_STEP_YUYV — one output size per call;
+ *   - result for position i (stream s), in the reference's order: C = the capture-size composite bsx_step_batch_mixed defines for settings[i] (the blend over
+ *     d_bg, over the blur of the stream's own frame, or — filter off — the frame itself: neither background nor mask is read); F = cv::flip(C) with the stream's
+ *     own flip bits; R = cv::resize(F, Size(out_w, out_h)) with the integers of bsx_resize_bgr (the 2x2 area mean at an exact factor of 2, as bsx_step_batch_vcam);
+ *     convert_rgb_to_yuyv(R) if the batch asks for it.  Persistent mask and ofinal of stream s are those of bsx_step_batch_streams for that stream;
+ *   - geometry: as bsx_step_batch_vcam, NOT as bsx_step_batch_mixed — any capture width, ROI and buffer alignment, and an onmask callback, are accepted;
+ *   - out_w == width and out_h == height: the call IS bsx_step_batch_mixed(ids, ..., flags), with that call's own refusals (its geometry included);
+ *   - n == 0: returns 0 and enqueues nothing;
+ *   - BSX_EINVAL before anything is enqueued, with a bsx_last_error text naming the position and value, for: the ids errors of bsx_step_batch_streams; settings
+ *     NULL with n > 0; a flag bit outside the sets above (a stream's or the batch's); a blur size that is even or above 31; a NULL d_bg on a stream that reads
+ *     it; out_w or out_h <= 0; an odd out_w with BSX_STEP_YUYV; an odd capture width with BSX_STEP_YUYV_IN; d_out overlapping d_frames or any stream's background;
+ *     a pending pipelined composite.  A refused call changes no state. */
+BSX_API int bsx_step_batch_vcam_mixed(bsx_ctx* ctx, const int* ids, const uint8_t* d_frames, const bsx_stream_setting* settings,
+                                      uint8_t* d_out, int out_w, int out_h, int n, void* stream, unsigned flags);
 
 /* cv::resize(src, dst, Size(dw,dh)) with INTER_LINEAR on packed BGR u8 (device pointers, n images). */
 BSX_API int bsx_resize_bgr(bsx_ctx* ctx, const uint8_t* d_src, int sw, int sh, uint8_t* d_dst, int dw, int dh, int n, void* stream);
