@@ -40,6 +40,10 @@ class _StreamSetting(C.Structure):          # bsx.h bsx_stream_setting
     _fields_ = [("d_bg", C.c_void_p), ("flags", C.c_uint)]
 
 
+class _ResizeItem(C.Structure):             # bsx.h bsx_resize_item
+    _fields_ = [("d_src", C.c_void_p), ("sw", C.c_int), ("sh", C.c_int), ("d_dst", C.c_void_p)]
+
+
 class StreamSetting:
     """one stream's settings for MaskGen.step_mixed — what one reference process takes as -b <image> (bg), -H / -V (flip_h / flip_v), -p bgblur:<k> (bgblur)
     and toggles at run time with the s / h / v keys (filter_off, flip_h, flip_v; app/deepseg.cc:387-437, 624-673, 777-790).  bg: a cuda uint8 [H,W,3] image
@@ -85,6 +89,7 @@ SYMBOLS = [
     ("bsx_step_batch_vcam_mixed", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(_StreamSetting), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                             C.c_uint]),
     ("bsx_resize_bgr", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    ("bsx_resize_bgr_batch", C.c_int, [C.c_void_p, C.POINTER(_ResizeItem), C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("bsx_bgr_to_yuyv", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("bsx_yuyv_to_bgr", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("bsx_background_load", C.c_void_p, [C.c_void_p, C.c_char_p, C.c_int]),
@@ -92,6 +97,7 @@ SYMBOLS = [
     ("bsx_background_free", None, [C.c_void_p]),
     ("bsx_background_info", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     ("bsx_background_grab", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    ("bsx_background_grab_batch", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_double, C.POINTER(C.c_int), C.c_void_p]),
     ("bsx_media_decode", C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.POINTER(C.c_uint8)), C.c_char_p, C.c_size_t]),
     ("bsx_media_free", None, [C.POINTER(C.c_uint8)]),
     ("bsx_live_new", C.c_void_p, [C.c_void_p]),
@@ -429,6 +435,40 @@ class MaskGen:
                self.h, "bsx_resize_bgr")
         return dst
 
+    def _batch_out(self, out, n, dw, dh):
+        """the output of a batch of n images dw x dh: cuda:<device> uint8 [n,dh,dw,3] whose images are contiguous; the batch dimension may be strided (any stride
+        >= one image: the C ABI takes one destination per image, of any alignment).  None: a new contiguous tensor."""
+        torch = _torch()
+        if out is None:
+            return torch.empty((n, dh, dw, 3), dtype=torch.uint8, device="cuda:%d" % self.device)
+        ok = (out.dtype == torch.uint8 and out.is_cuda and out.device.index == self.device and out.dim() == 4 and tuple(out.shape) == (n, dh, dw, 3)
+              and tuple(out.stride()[1:]) == (dw * 3, 3, 1) and (n <= 1 or out.stride(0) >= dh * dw * 3))
+        if not ok:
+            raise BsxError("out must be a cuda:%d uint8 tensor [%d,%d,%d,3] with contiguous images that do not overlap" % (self.device, n, dh, dw))
+        return out
+
+    def resize_bgr_batch(self, srcs, dw, dh, out=None):
+        """cv::resize of n images, each of its OWN size, to dw x dh in one launch (bsx_resize_bgr_batch; the integers of resize_bgr).  srcs: a sequence of
+        contiguous cuda uint8 [sh_i, sw_i, 3] tensors on the context's device; out: see _batch_out.  Returns out ([n, dh, dw, 3])."""
+        torch = _torch()
+        srcs = list(srcs)
+        n, dw, dh = len(srcs), int(dw), int(dh)
+        if n > self.n_streams:
+            raise BsxError("%d images for a context of %d streams" % (n, self.n_streams))
+        if dw <= 0 or dh <= 0:
+            raise BsxError("output size %d x %d is not positive" % (dw, dh))
+        for i, t in enumerate(srcs):
+            ok = (isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.is_cuda and t.device.index == self.device and t.dim() == 3 and t.shape[2] == 3
+                  and t.shape[0] > 0 and t.shape[1] > 0 and t.is_contiguous())
+            if not ok:
+                raise BsxError("srcs[%d] must be a contiguous cuda:%d uint8 tensor [h,w,3]" % (i, self.device))
+        out = self._batch_out(out, n, dw, dh)
+        items = (_ResizeItem * max(n, 1))()
+        for i, t in enumerate(srcs):
+            items[i].d_src, items[i].sw, items[i].sh, items[i].d_dst = t.data_ptr(), int(t.shape[1]), int(t.shape[0]), out.data_ptr() + i * out.stride(0)
+        _check(lib().bsx_resize_bgr_batch(self.h, items, n, dw, dh, _stream_ptr()), self.h, "bsx_resize_bgr_batch")
+        return out
+
     def bgr_to_yuyv(self, bgr):
         torch = _torch()
         n, h, w, _ = bgr.shape
@@ -616,6 +656,41 @@ class Background:
             self.close()
         except Exception:
             pass
+
+
+def grab_backgrounds(backgrounds, width, height, out=None, at=None):
+    """grab_background for a batch of sources in ONE launch (bsx_background_grab_batch): out[i] = the current picture of backgrounds[i] resized to width x height
+    — what StreamSetting.bg of stream i points at, grabbed every tick.  backgrounds: Background objects of ONE MaskGen (a source may appear more than once);
+    out: cuda uint8 [n,height,width,3] on that MaskGen's device (MaskGen._batch_out; None: a new tensor); at: seconds since the start of playback — every
+    animation shows picture floor(at * fps) mod n_frames, the same in every run — or None for the clock, read once for the whole batch.
+    → (frame numbers: 1 for a still, picture c of an animation as c + 1; out)"""
+    backgrounds = list(backgrounds)
+    n, width, height = len(backgrounds), int(width), int(height)
+    for i, b in enumerate(backgrounds):
+        if not isinstance(b, Background) or not getattr(b, "h", None):
+            raise BsxError("backgrounds[%d] is not an open Background" % i)
+        if b.mg is not backgrounds[0].mg:
+            raise BsxError("backgrounds[%d] belongs to another MaskGen than backgrounds[0]" % i)
+    if n == 0:
+        if out is None:
+            raise BsxError("an empty batch has no MaskGen to allocate `out` on: pass out")
+        return [], out
+    mg = backgrounds[0].mg
+    if n > mg.n_streams:
+        raise BsxError("%d backgrounds for a context of %d streams" % (n, mg.n_streams))
+    if width <= 0 or height <= 0:
+        raise BsxError("output size %d x %d is not positive" % (width, height))
+    if at is not None:
+        at = float(at)
+        if not (0.0 <= at < float("inf")):
+            raise BsxError("at = %r must be a time >= 0 (None: the clock)" % at)
+    out = mg._batch_out(out, n, width, height)
+    arr = (C.c_void_p * n)(*[b.h for b in backgrounds])
+    nos = (C.c_int * n)()
+    stride = int(out.stride(0)) if n > 1 else width * height * 3
+    rc = lib().bsx_background_grab_batch(arr, n, width, height, _ptr(out), stride, -1.0 if at is None else at, nos, _stream_ptr())
+    _check(rc, mg.h, "bsx_background_grab_batch")
+    return list(nos), out
 
 
 class Live:

@@ -6,6 +6,7 @@
 #include "debug_switches.hpp"
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -22,6 +23,7 @@
 #include "kernels.hpp"
 #include "roctx_ranges.hpp"
 #include "plan.hpp"
+#include "refusal.hpp"
 #include "rtc.hpp"
 #include "specialised.hpp"
 #include "tflite_model.hpp"
@@ -177,6 +179,12 @@ struct bsx_ctx {
   struct MixBlur { int ksize, off, count; };
   std::vector<MixBlur> mix_blur;            // the staged call's blur groups: ksize, first index into the position list, count
   size_t mix_entry_bytes() const { return (size_t)n_streams * (sizeof(MixDesc) + sizeof(int)); }
+  // bsx_resize_bgr_batch: per ring entry (the same entries and events again) the call's n_streams ResizeBatchDesc (kernels.hpp), built in the pinned entry, copied
+  // to the device entry in one hipMemcpyAsync.  Allocated on the first batch call.
+  ResizeBatchDesc* h_rsz = nullptr;         // pinned [kIdRing][n_streams]
+  ResizeBatchDesc* d_rsz = nullptr;         // device, likewise
+  struct Span { uintptr_t begin, end; int item; bool dst; };
+  std::vector<Span> rsz_spans;              // host scratch of the overlap check: the call's sources and destinations, sorted by address
   bool act16 = false;                  // BSX_ACT16=1: 16-bit activation STORAGE for the segmented Meet / MLKit networks (g1) — opt-in, IoU-gated; needs the specialised middle kernel
 
   // stream-0 view of a graph tensor (network input/output have dedicated buffers; intermediates are batch-major in
@@ -468,6 +476,17 @@ int refuse(bsx_ctx* c, const char* fn, const char* fmt, ...) {
   c->last_error = std::string("error: ") + fn + ": " + buf + "\n";
   return BSX_EINVAL;
 }
+}  // namespace
+// the same for a call made from live.cpp (refusal.hpp): also kept per thread, for the call that has no context to name (bsx_last_error(NULL))
+int bsx::refuse_call(bsx_ctx* c, const char* fn, const char* fmt, ...) {
+  char buf[256];
+  va_list ap;
+  va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
+  g_last_error = std::string("error: ") + fn + ": " + buf + "\n";
+  if (c) c->last_error = g_last_error;
+  return BSX_EINVAL;
+}
+namespace {
 // every entry point that advances the temporal state refuses while the two-deep pipeline holds a composite that reads it
 int refuse_pending(bsx_ctx* c, const char* fn) {
   return c->pend.active ? refuse(c, fn, "a pipelined composite is pending (flush with bsx_step_batch_pipelined(ctx, NULL, ...) first)") : BSX_OK;
@@ -852,6 +871,71 @@ int step_call(bsx_ctx* c, const char* fn, Entry kind, StepReq r, const int* host
   return ids_release(c, entry, r.s, rc ? rc : run_step(c, r));
 }
 
+// ---- bsx_resize_bgr / bsx_resize_bgr_batch: the resize tables of the backgrounds, one per distinct (sw, sh, dw, dh), uploaded on first use ---------------------
+int bg_tab(bsx_ctx* c, int sw, int sh, int dw, int dh, const DevResizeTab** out) {
+  auto key = std::make_pair(std::make_pair(sw, sh), std::make_pair(dw, dh));
+  auto it = c->bg_tabs.find(key);
+  if (it == c->bg_tabs.end()) {
+    DevResizeTab d;
+    int rc = upload_tab(c, make_resize_tab(sw, sh, dw, dh), &d);
+    if (rc) return rc;
+    it = c->bg_tabs.emplace(key, d).first;
+  }
+  *out = &it->second;
+  return BSX_OK;
+}
+// host-side validation of items[0..n): nothing is enqueued before it passes.  A destination may overlap neither a source picture nor another destination (the
+// launch reads and writes them in no order); sources may overlap each other — two entries may name one picture.  Sorted by address, one sweep.
+int resize_batch_check(bsx_ctx* c, const char* fn, const bsx_resize_item* items, int n, int dw, int dh) {
+  if (n < 0) return refuse(c, fn, "n = %d is negative", n);
+  if (n > c->n_streams) return refuse(c, fn, "n = %d exceeds the context's %d streams", n, c->n_streams);
+  if (n == 0) return BSX_OK;
+  if (!items) return refuse(c, fn, "items is NULL");
+  if (dw <= 0 || dh <= 0) return refuse(c, fn, "output size %d x %d is not positive", dw, dh);
+  const size_t out_bytes = (size_t)dw * dh * 3;
+  std::vector<bsx_ctx::Span>& sp = c->rsz_spans;
+  sp.clear();
+  for (int i = 0; i < n; i++) {
+    const bsx_resize_item& it = items[i];
+    if (!it.d_src) return refuse(c, fn, "items[%d]: d_src is NULL", i);
+    if (!it.d_dst) return refuse(c, fn, "items[%d]: d_dst is NULL", i);
+    if (it.sw <= 0 || it.sh <= 0) return refuse(c, fn, "items[%d]: source size %d x %d is not positive", i, it.sw, it.sh);
+    sp.push_back({(uintptr_t)it.d_src, (uintptr_t)it.d_src + (size_t)it.sw * it.sh * 3, i, false});
+    sp.push_back({(uintptr_t)it.d_dst, (uintptr_t)it.d_dst + out_bytes, i, true});
+  }
+  std::sort(sp.begin(), sp.end(), [](const bsx_ctx::Span& a, const bsx_ctx::Span& b) { return a.begin < b.begin; });
+  const bsx_ctx::Span* far_any = nullptr;   // of the spans that begin at or below the current one: the one that ends last, and the destination that ends last
+  const bsx_ctx::Span* far_dst = nullptr;
+  for (const bsx_ctx::Span& v : sp) {
+    const bsx_ctx::Span* hit = v.dst ? far_any : far_dst;
+    if (hit && hit->end > v.begin) {
+      const bsx_ctx::Span& d = v.dst ? v : *hit;          // name the destination first: it is the one the caller placed wrongly
+      const bsx_ctx::Span& o = v.dst ? *hit : v;
+      return refuse(c, fn, "items[%d]: d_dst %p overlaps the %s of items[%d] (%p)", d.item, (const void*)d.begin, o.dst ? "destination" : "source picture", o.item,
+                    (const void*)o.begin);
+    }
+    if (!far_any || v.end > far_any->end) far_any = &v;
+    if (v.dst && (!far_dst || v.end > far_dst->end)) far_dst = &v;
+  }
+  return BSX_OK;
+}
+// items[0..n) as ResizeBatchDesc into ring entry k (pinned), one copy to the device entry on s
+int resize_batch_stage(bsx_ctx* c, const bsx_resize_item* items, int n, int dw, int dh, hipStream_t s, int k, const ResizeBatchDesc** d_desc) {
+  const size_t N = (size_t)c->n_streams;
+  if (!c->h_rsz) BSX_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_rsz), bsx_ctx::kIdRing * N * sizeof(ResizeBatchDesc), hipHostMallocDefault));
+  if (!c->d_rsz) BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_rsz), bsx_ctx::kIdRing * N * sizeof(ResizeBatchDesc)));
+  ResizeBatchDesc* hd = c->h_rsz + (size_t)k * N;
+  const DevResizeTab* t = nullptr;
+  for (int i = 0; i < n; i++) {
+    if (!t || t->tab.sw != items[i].sw || t->tab.sh != items[i].sh)           // (a run of equal sizes looks its table up once)
+      if (const int rc = bg_tab(c, items[i].sw, items[i].sh, dw, dh, &t)) return rc;
+    hd[i] = ResizeBatchDesc{items[i].d_src, items[i].d_dst, t->tab.xofs, t->tab.xa, t->tab.yofs, t->tab.ya, t->tab.sw, t->tab.sh, t->tab.mode, 0};
+  }
+  BSX_HIP(c, hipMemcpyAsync(c->d_rsz + (size_t)k * N, hd, (size_t)n * sizeof(ResizeBatchDesc), hipMemcpyHostToDevice, s));
+  *d_desc = c->d_rsz + (size_t)k * N;
+  return BSX_OK;
+}
+
 // ---- two-deep pipeline: mask pipeline of batch k  ||  composite of batch k - 1 ------------------------------------------------------------------
 // The composite (HBM-bound) of the batch handed over by the previous call goes to comp_stream, the mask pipeline (latency-bound) of this call's batch to the
 // caller's stream (the reference's CalcMask worker next to its blend loop, app/deepseg.cc:182-216, 634-681); the only shared object, the model-resolution
@@ -1009,6 +1093,8 @@ void bsx_delete(bsx_ctx* c) {
   if (c->h_ids) (void)hipHostFree(c->h_ids);
   if (c->d_mix) (void)hipFree(c->d_mix);
   if (c->h_mix) (void)hipHostFree(c->h_mix);
+  if (c->d_rsz) (void)hipFree(c->d_rsz);
+  if (c->h_rsz) (void)hipHostFree(c->h_rsz);
   delete c;
 }
 
@@ -1186,16 +1272,28 @@ int bsx_step_batch_pipelined(bsx_ctx* c, const uint8_t* d_frames, const uint8_t*
 int bsx_resize_bgr(bsx_ctx* c, const uint8_t* d_src, int sw, int sh, uint8_t* d_dst, int dw, int dh, int n, void* stream) {
   if (!c || !d_src || !d_dst || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || n <= 0) return BSX_EINVAL;
   DeviceGuard guard(c->device);
-  auto key = std::make_pair(std::make_pair(sw, sh), std::make_pair(dw, dh));
-  auto it = c->bg_tabs.find(key);
-  if (it == c->bg_tabs.end()) {
-    DevResizeTab d;
-    int rc = upload_tab(c, make_resize_tab(sw, sh, dw, dh), &d);
-    if (rc) return rc;
-    it = c->bg_tabs.emplace(key, d).first;
-  }
-  BSX_HIP(c, launch_resize_bgr(d_src, d_dst, it->second.tab, n, pick(c, stream)));
+  const DevResizeTab* t = nullptr;
+  if (const int rc = bg_tab(c, sw, sh, dw, dh, &t)) return rc;
+  BSX_HIP(c, launch_resize_bgr(d_src, d_dst, t->tab, n, pick(c, stream)));
   return BSX_OK;
+}
+
+// n images, each of its own size, to dw x dh in ONE launch: checked on the host, the descriptors through the staging ring, the tables from bg_tabs
+int bsx_resize_bgr_batch(bsx_ctx* c, const bsx_resize_item* items, int n, int dw, int dh, void* stream) {
+  if (!c) return BSX_EINVAL;
+  if (const int rc = resize_batch_check(c, "bsx_resize_bgr_batch", items, n, dw, dh)) return rc;
+  if (n == 0) return BSX_OK;
+  DeviceGuard guard(c->device);
+  hipStream_t s = pick(c, stream);
+  int entry = 0;
+  if (const int rc = ring_acquire(c, &entry)) return rc;
+  const ResizeBatchDesc* d_desc = nullptr;
+  int rc = resize_batch_stage(c, items, n, dw, dh, s, entry, &d_desc);
+  if (!rc) {
+    const hipError_t e = launch_resize_bgr_batch(d_desc, n, dw, dh, s);
+    if (e != hipSuccess) { report(c, c->ondebug, c->caller_ctx, "error: HIP %s while resizing a batch\n", hipGetErrorString(e)); rc = BSX_EDEVICE; }
+  }
+  return ids_release(c, entry, s, rc);
 }
 
 int bsx_flip_bgr(bsx_ctx* c, const uint8_t* d_src, uint8_t* d_dst, int w, int h, int n, int code, void* stream) {

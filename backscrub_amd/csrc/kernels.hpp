@@ -129,6 +129,16 @@ hipError_t launch_blend(const uint8_t* bg, size_t bg_stride, const uint8_t* fram
                         int n, hipStream_t s, const int* slot_of = nullptr);
 // generic BGR resize (background → frame size).  background.cc:186,190
 hipError_t launch_resize_bgr(const uint8_t* src, uint8_t* dst, ResizeTab tab, int n, hipStream_t s);
+// n resizes to ONE output size in ONE launch (bsx_resize_bgr_batch): block row i of the grid reads desc[i] (a DEVICE array, one uniform load per workgroup) —
+// its source, its destination (dw x dh x 3 bytes, any alignment: a 4-byte aligned one with dw % 4 == 0 is stored as dwords) and the table of (sw x sh -> dw x dh),
+// whose mode (ResizeTab::mode) may differ from one descriptor to the next.  The integers of launch_resize_bgr.
+struct alignas(16) ResizeBatchDesc {
+  const uint8_t* src; uint8_t* dst;
+  const int* xofs; const short* xa; const int* yofs; const short* ya;     // ResizeTab's tables (null in modes 1 and 2)
+  int sw, sh, mode, pad;
+};
+static_assert(sizeof(ResizeBatchDesc) == 64, "four 16-byte uniform loads per workgroup");
+hipError_t launch_resize_bgr_batch(const ResizeBatchDesc* desc, int n, int dw, int dh, hipStream_t s);
 // BGR → YUYV.  deepseg.cc:87-106
 hipError_t launch_bgr_to_yuyv(const uint8_t* bgr, uint8_t* yuyv, int w, int h, int n, hipStream_t s);
 // YUYV → BGR ingest.  deepseg.cc:553 (CAP_PROP_CONVERT_RGB), :725

@@ -921,6 +921,46 @@ __global__ __launch_bounds__(kThreads) void resize_bgr_k(const uint8_t* __restri
   o[0] = (uint8_t)v[0]; o[1] = (uint8_t)v[1]; o[2] = (uint8_t)v[2];
 }
 
+// ---- n BGR resizes of one output size in ONE launch (bsx_resize_bgr_batch / bsx_background_grab_batch) ------------------------------------------
+// Block row blockIdx.y reads descriptor blockIdx.y: its own source (of its own size, so the three table modes can meet in one launch), its own destination.
+// The index is the block's, so the descriptor arrives through uniform (scalar) loads; its pointers are rebuilt as global-memory pointers (mix_desc: a pointer
+// read from memory is otherwise a generic one and everything through it a flat access).  A lane makes FOUR adjacent pixels of one output row — sample_linear,
+// the integers of resize_bgr_k — and stores them as three dwords when the row is whole groups and that destination is 4-byte aligned (group g of an image lies
+// at byte 12 g); any other destination takes byte stores, twelve partial writes where the other form has three full ones.  Same bytes either way.
+template <typename T>
+__device__ __forceinline__ T* as_global(T* p) { return (T*)(__attribute__((address_space(1))) T*)(uint64_t)p; }
+
+__global__ __launch_bounds__(kThreads) void resize_bgr_batch_k(const ResizeBatchDesc* __restrict__ desc, int dw, int dh) {
+  const unsigned gpr = ((unsigned)dw + 3u) / 4u, g = blockIdx.x * kThreads + threadIdx.x;
+  if (g >= gpr * (unsigned)dh) return;
+  const ResizeBatchDesc d = desc[blockIdx.y];
+  ResizeTab tab;
+  tab.xofs = as_global(d.xofs); tab.xa = as_global(d.xa); tab.yofs = as_global(d.yofs); tab.ya = as_global(d.ya);
+  tab.sw = d.sw; tab.sh = d.sh; tab.dw = dw; tab.dh = dh; tab.mode = d.mode;
+  const uint8_t* const src = as_global(d.src);
+  uint8_t* const dst = as_global(d.dst);
+  const int y = (int)(g / gpr), x = (int)(g - (unsigned)y * gpr) * 4;
+  uint8_t* const o = dst + ((long)y * dw + x) * 3;
+  if ((dw & 3) == 0 && ((uintptr_t)dst & 3) == 0) {                 // (uniform: the launch's width, the descriptor's pointer)
+    int v[12];
+#pragma unroll
+    for (int k = 0; k < 4; k++) sample_linear<3>(src, (long)tab.sw * 3, tab, x + k, y, v + 3 * k);
+    uint32_t w[3];
+#pragma unroll
+    for (int j = 0; j < 3; j++) w[j] = (uint32_t)v[4 * j] | ((uint32_t)v[4 * j + 1] << 8) | ((uint32_t)v[4 * j + 2] << 16) | ((uint32_t)v[4 * j + 3] << 24);
+    uint32_t* const ow = reinterpret_cast<uint32_t*>(o);
+    ow[0] = w[0]; ow[1] = w[1]; ow[2] = w[2];
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    if (x + k >= dw) break;
+    int v[3];
+    sample_linear<3>(src, (long)tab.sw * 3, tab, x + k, y, v);
+    o[3 * k] = (uint8_t)v[0]; o[3 * k + 1] = (uint8_t)v[1]; o[3 * k + 2] = (uint8_t)v[2];
+  }
+}
+
 __global__ __launch_bounds__(kThreads) void yuyv_k(const uint8_t* __restrict__ in, uint32_t* __restrict__ out, long pairs) {
   long i = (long)blockIdx.x * kThreads + threadIdx.x;
   if (i >= pairs) return;
@@ -1393,6 +1433,16 @@ hipError_t launch_resize_bgr(const uint8_t* src, uint8_t* dst, ResizeTab tab, in
   for (int n0 = 0; n0 < n; n0 += kMaxGridY) {
     const int nn = n - n0 < kMaxGridY ? n - n0 : kMaxGridY;
     resize_bgr_k<<<dim3(blocks_for((long)tab.dw * tab.dh), nn), kThreads, 0, s>>>(src + (size_t)n0 * tab.sw * tab.sh * 3, dst + (size_t)n0 * tab.dw * tab.dh * 3, tab);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_resize_bgr_batch(const ResizeBatchDesc* desc, int n, int dw, int dh, hipStream_t s) {
+  const long groups = (long)((dw + 3) / 4) * dh;
+  if (groups >= (1l << 31)) return hipErrorInvalidValue;
+  for (int n0 = 0; n0 < n; n0 += kMaxGridY) {
+    const int nn = n - n0 < kMaxGridY ? n - n0 : kMaxGridY;
+    resize_bgr_batch_k<<<dim3(blocks_for(groups), nn), kThreads, 0, s>>>(desc + n0, dw, dh);
   }
   return hipGetLastError();
 }

@@ -4,17 +4,19 @@
 //                      compositing background, played in real time, looping at the end of the stream, and `grab` = the current picture resized to
 //                      the camera size together with its frame number.  Here the pictures are decoded once (media.cpp) and kept ON THE GPU; which
 //                      one is current is a pure function of the clock — picture floor(t * fps) mod n, reported as 1..n like the reference's counter
-//                      of pictures read — so there is no reader thread, no lock and no per-frame upload: a grab is one resize launch.
+//                      of pictures read — so there is no reader thread, no lock and no per-frame upload: a grab is one resize launch, and the grab of
+//                      a whole batch of sources (bsx_background_grab_batch: one clock reading, or the caller's own time) is one launch as well.
 //   bsx_live_*         what class CalcMask provides (/root/reference/app/deepseg.cc:159-286): the camera loop hands over frames and polls for
 //                      masks and never waits for the segmentation; a mask may lag its frame.  Here the worker is the GPU queue itself: a frame
 //                      is copied into a pinned slot and its upload, the whole mask pipeline and the mask's download are enqueued on a private
 //                      HIP stream with an event behind them; `get_output_mask` polls that event.  Two submissions may be in flight; a frame that
 //                      arrives while both are busy replaces the waiting one (the newest frame wins, as with the reference's double buffer).
 //
-// Only the C ABI of bsx.h and the HIP runtime are used here; nothing touches a kernel directly.
+// Only the C ABI of bsx.h and the HIP runtime are used here (and refusal.hpp, for the text of a refused call); nothing touches a kernel directly.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -25,6 +27,7 @@
 
 #include "../../include/bsx.h"
 #include "media.hpp"
+#include "refusal.hpp"
 
 using namespace bsx;
 
@@ -179,6 +182,58 @@ int bsx_background_grab(bsx_background* b, int width, int height, uint8_t* d_bgr
   const uint8_t* src = b->d_pictures + (size_t)c * b->width * b->height * 3;
   if (bsx_resize_bgr(b->ctx, src, b->width, b->height, d_bgr_out, width, height, 1, stream) != BSX_OK) return -1;
   return (int)c + 1;
+}
+
+// grab_background for n sources at once: the pictures are picked here — all at the caller's time, or all at ONE reading of the clock — and resized by one
+// bsx_resize_bgr_batch launch.  Everything is checked before that call, so a refusal has enqueued nothing and written no frame number.
+int bsx_background_grab_batch(bsx_background* const* bgs, int n, int width, int height, uint8_t* d_bgr_out, size_t out_stride, double at_seconds, int* frame_nos,
+                              void* stream) {
+  static const char* const fn = "bsx_background_grab_batch";
+  if (n < 0) return refuse_call(nullptr, fn, "n = %d is negative", n);
+  if (n == 0) return BSX_OK;
+  if (!bgs) return refuse_call(nullptr, fn, "bgs is NULL");
+  bsx_ctx* ctx = nullptr;
+  for (int i = 0; i < n && !ctx; i++) if (bgs[i]) ctx = bgs[i]->ctx;
+  for (int i = 0; i < n; i++) {
+    if (!bgs[i]) return refuse_call(ctx, fn, "bgs[%d] is NULL", i);
+    if (bgs[i]->ctx != ctx) return refuse_call(ctx, fn, "bgs[%d] belongs to another context (%p) than bgs[0] (%p)", i, (const void*)bgs[i]->ctx, (const void*)ctx);
+  }
+  bsx_info info;
+  if (bsx_get_info(ctx, &info) != BSX_OK) return BSX_EINVAL;
+  if (n > info.n_streams) return refuse_call(ctx, fn, "n = %d exceeds the context's %d streams", n, info.n_streams);
+  if (width <= 0 || height <= 0) return refuse_call(ctx, fn, "output size %d x %d is not positive", width, height);
+  if (!d_bgr_out) return refuse_call(ctx, fn, "d_bgr_out is NULL");
+  const size_t img = (size_t)width * height * 3;
+  if (out_stride < img) return refuse_call(ctx, fn, "out_stride = %zu is less than one %d x %d image (%zu bytes)", out_stride, width, height, img);
+  if (!std::isfinite(at_seconds)) return refuse_call(ctx, fn, "at_seconds = %f is not a time", at_seconds);
+  // no output slice may lie over ANY picture of a source (not only the current one: a refusal must not depend on the time).  Of the slices that end above
+  // the first picture's first byte, the lowest one decides: if it begins below the last picture's end it overlaps, and if it does not, no later one does.
+  const uintptr_t o0 = (uintptr_t)d_bgr_out;
+  for (int j = 0; j < n; j++) {
+    const uintptr_t p0 = (uintptr_t)bgs[j]->d_pictures, p1 = p0 + (size_t)bgs[j]->n_pictures * bgs[j]->width * bgs[j]->height * 3;
+    const uintptr_t i = p0 < o0 + img ? 0 : (p0 - o0 - img) / out_stride + 1;
+    if (i < (uintptr_t)n && o0 + i * out_stride < p1)
+      return refuse_call(ctx, fn, "output %d (%p) overlaps the pictures of bgs[%d] (%p)", (int)i, (const void*)(o0 + i * out_stride), j, (const void*)p0);
+  }
+  try {
+    std::vector<bsx_resize_item> items((size_t)n);
+    std::vector<int> nos((size_t)n);
+    const Clock::time_point now = Clock::now();                     // ONE reading for the whole batch
+    for (int i = 0; i < n; i++) {
+      const bsx_background* b = bgs[i];
+      long c = 0;
+      if (b->animated) {
+        const double t = at_seconds >= 0 ? at_seconds : std::chrono::duration<double>(now - b->t0).count();
+        const double q = std::floor(t * b->fps);                    // pictures shown so far (fmod of whole numbers is exact)
+        c = std::isfinite(q) && q >= 0 ? (long)std::fmod(q, (double)b->n_pictures) : 0;
+      }
+      items[(size_t)i] = bsx_resize_item{b->d_pictures + (size_t)c * b->width * b->height * 3, b->width, b->height, d_bgr_out + (size_t)i * out_stride};
+      nos[(size_t)i] = (int)c + 1;
+    }
+    const int rc = bsx_resize_bgr_batch(ctx, items.data(), n, width, height, stream);
+    if (rc == BSX_OK && frame_nos) memcpy(frame_nos, nos.data(), (size_t)n * sizeof(int));
+    return rc;
+  } catch (...) { return BSX_EDEVICE; }
 }
 
 bsx_live* bsx_live_new(bsx_ctx* ctx) {

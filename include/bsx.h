@@ -26,12 +26,14 @@
  *   bsx_reset_streams      bsx_reset for a chosen subset of the streams (a slot reused for a new camera)
  *                          (set_input_frame → mask → alpha_blend), batched
  *   bsx_resize_bgr         grab_background() cv::resize   app/background.cc:178-194
+ *   bsx_resize_bgr_batch   … of n images of their own sizes in one launch
  *   bsx_bgr_to_yuyv        convert_rgb_to_yuyv()          app/deepseg.cc:87-106
  *   bsx_yuyv_to_bgr        VideoCapture's YUYV->BGR       app/deepseg.cc:553,725 (cv::COLOR_YUV2BGR_YUYV)
  *   bsx_flip_bgr           cv::flip of the output frame   app/deepseg.cc:667-673 (flipHorizontal / flipVertical)
  *   bsx_gaussian_blur_bgr  cv::GaussianBlur of the background app/deepseg.cc:415-431,652-658 (-p bgblur:<n>: blur the camera frame itself
  *                          (or the background image) and composite over it)
  *   bsx_background_*       load_background / grab_background + reader thread   app/background.cc:29-104,126-194
+ *   bsx_background_grab_batch  grab_background() of every camera's own source, once per main-loop iteration   app/deepseg.cc:648-651
  *   bsx_live_*             class CalcMask (worker thread, double buffering)     app/deepseg.cc:159-286
  *   bsx_profile_batch      the per-stage timers           app/deepseg.cc:137-156,701-720 (timinginfo_t)
  *   bsx_get_info           the geometry of backscrub_ctx_t lib/libbackscrub.cc:28-54,234-246
@@ -286,6 +288,18 @@ BSX_API int bsx_step_batch_vcam_mixed(bsx_ctx* ctx, const int* ids, const uint8_
 /* cv::resize(src, dst, Size(dw,dh)) with INTER_LINEAR on packed BGR u8 (device pointers, n images). */
 BSX_API int bsx_resize_bgr(bsx_ctx* ctx, const uint8_t* d_src, int sw, int sh, uint8_t* d_dst, int dw, int dh, int n, void* stream);
 
+/* n images, each of its own size, resized (the integers of bsx_resize_bgr) to dw x dh in ONE launch: image i is d_src [sh][sw][3] -> d_dst [dh][dw][3], device
+ * pointers of any alignment (a 4-byte aligned d_dst with dw % 4 == 0 is written as whole words, any other one byte-wise; the bytes are the same).
+ *   - items is a HOST array, read before the call returns; the descriptors reach the device through the staging ring of bsx_step_batch_streams (no host
+ *     synchronisation unless the caller runs a ring's length ahead of the GPU), the resize tables come from the cache bsx_resize_bgr fills: one per distinct
+ *     (sw, sh, dw, dh), uploaded when it is first used;
+ *   - n <= n_streams of the context; n == 0 returns 0 and enqueues nothing;
+ *   - the same source may appear in several items; nothing is deduplicated;
+ *   - BSX_EINVAL before anything is enqueued, with a bsx_last_error text naming the position and value, for: n < 0 or n > n_streams; items NULL with n > 0; a
+ *     non-positive size; a NULL d_src or d_dst; a d_dst that overlaps a source picture or another destination. */
+typedef struct bsx_resize_item { const uint8_t* d_src; int sw, sh; uint8_t* d_dst; } bsx_resize_item;
+BSX_API int bsx_resize_bgr_batch(bsx_ctx* ctx, const bsx_resize_item* items, int n, int dw, int dh, void* stream);
+
 /* BGR u8 [n][h][w][3] -> YUYV 4:2:2 [n][h][w][2] exactly as convert_rgb_to_yuyv (byte order Y0 V Y1 U). */
 BSX_API int bsx_bgr_to_yuyv(bsx_ctx* ctx, const uint8_t* d_bgr, uint8_t* d_yuyv, int w, int h, int n, void* stream);
 
@@ -315,6 +329,19 @@ BSX_API int bsx_background_info(const bsx_background* bg, int* width, int* heigh
  * Returns the frame number or -1 on error: 1 for a still image; for an animation the reference's count of pictures read since the last rewind, i.e.
  * picture c (= floor(t * fps) mod n, t since the background was created: real-time playback, looping at the end) is reported as c + 1. */
 BSX_API int bsx_background_grab(bsx_background* bg, int width, int height, uint8_t* d_bgr_out, void* stream);
+/* grab_background() for n sources at once, in ONE launch (bsx_resize_bgr_batch): output i = the current picture of bgs[i] resized to width x height, at
+ * d_bgr_out + i * out_stride — what a bsx_stream_setting's d_bg points at, grabbed every tick (out_stride a multiple of 4 keeps every slice 4-byte aligned).
+ *   - at_seconds >= 0: picture floor(at_seconds * fps_i) mod n_i of every animation (a still is always its one picture) — "the backgrounds as of tick t", the
+ *     same for every caller and every run; at_seconds < 0: the clock, read ONCE for the whole batch (t_i = now - creation of bgs[i], as bsx_background_grab);
+ *   - frame_nos (host, may be NULL): entry i = what bsx_background_grab would have returned for it (1 for a still, picture c as c + 1);
+ *   - bgs and frame_nos are host arrays, read / written before the call returns; the same source may appear in several entries (a caller who wants one output
+ *     shared by many streams lists it once and points those settings at it); n <= n_streams of the sources' context; n == 0 returns 0 and enqueues nothing;
+ *   - returns 0, or BSX_EINVAL before anything is enqueued — the text, naming the position and value, is bsx_last_error of the sources' context and of
+ *     bsx_last_error(NULL) — for: n < 0 or n > n_streams; bgs NULL with n > 0, a NULL entry, an entry of another context than bgs[0]'s; a non-positive size; a NULL
+ *     d_bgr_out; out_stride < width * height * 3; at_seconds NaN or infinite; an output that overlaps the pictures of a source.  A refused call writes no
+ *     frame_nos. */
+BSX_API int bsx_background_grab_batch(bsx_background* const* bgs, int n, int width, int height, uint8_t* d_bgr_out, size_t out_stride, double at_seconds,
+                                      int* frame_nos, void* stream);
 /* host-only decode of the same formats (no GPU): frames → malloc'ed [n][h][w][3] BGR; returns n (> 0) or a negative BSX_E* code */
 BSX_API int bsx_media_decode(const char* path, int* width, int* height, double* fps, uint8_t** h_bgr, char* errbuf, size_t errcap);
 BSX_API void bsx_media_free(uint8_t* h_bgr);
