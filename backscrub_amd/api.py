@@ -44,6 +44,19 @@ class _ResizeItem(C.Structure):             # bsx.h bsx_resize_item
     _fields_ = [("d_src", C.c_void_p), ("sw", C.c_int), ("sh", C.c_int), ("d_dst", C.c_void_p)]
 
 
+class _Geometry(C.Structure):               # bsx.h bsx_geometry
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("n_streams", C.c_int)]
+
+
+class _GeomInfo(C.Structure):               # bsx.h bsx_geom_info
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("n_streams", C.c_int), ("first_stream", C.c_int), ("roi", C.c_int * 4), ("in_roi", C.c_int * 4),
+                ("mask_offset", C.c_size_t)]
+
+
+class _GeomItem(C.Structure):               # bsx.h bsx_geom_item
+    _fields_ = [("d_frame", C.c_void_p), ("d_out", C.c_void_p), ("setting", _StreamSetting)]
+
+
 class StreamSetting:
     """one stream's settings for MaskGen.step_mixed — what one reference process takes as -b <image> (bg), -H / -V (flip_h / flip_v), -p bgblur:<k> (bgblur)
     and toggles at run time with the s / h / v keys (filter_off, flip_h, flip_v; app/deepseg.cc:387-437, 624-673, 777-790).  bg: a cuda uint8 [H,W,3] image
@@ -85,6 +98,10 @@ SYMBOLS = [
     ("bsx_step_batch_vcam", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint]),
     ("bsx_step_batch_streams", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_uint]),
     ("bsx_reset_streams", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
+    ("bsx_new_geoms", C.c_void_p, [C.c_char_p, C.c_size_t, C.POINTER(_Geometry), C.c_int, C.c_int, DEBUG_FN, STAGE_FN, STAGE_FN, STAGE_FN, C.c_void_p]),
+    ("bsx_geom_count", C.c_int, [C.c_void_p]),
+    ("bsx_get_geom_info", C.c_int, [C.c_void_p, C.c_int, C.POINTER(_GeomInfo)]),
+    ("bsx_step_batch_geoms", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(_GeomItem), C.c_int, C.c_void_p, C.c_uint]),
     ("bsx_step_batch_mixed", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(_StreamSetting), C.c_void_p, C.c_int, C.c_void_p, C.c_uint]),
     ("bsx_step_batch_vcam_mixed", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(_StreamSetting), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                             C.c_uint]),
@@ -188,6 +205,93 @@ class MaskGen:
         _check(L.bsx_get_info(self.h, C.byref(info)), self.h, "bsx_get_info")
         self.info = {k: (list(getattr(info, k)) if k in ("roi", "in_roi") else getattr(info, k)) for k, _ in _Info._fields_}
         self.width, self.height, self.n_streams, self.device = width, height, n_streams, device
+
+    @classmethod
+    def with_geometries(cls, model_path, geometries, device=0, threads=2, ondebug=None, onprep=None, oninfer=None, onmask=None, caller_ctx=None):
+        """a context for cameras of several capture sizes (bsx_new_geoms): geometries = [(width, height, n_streams), ...], at most 8 distinct sizes.  Streams are
+        numbered class after class; step_geoms advances any mix of them in one launch sequence.  width / height / info are class 0's, n_streams the total."""
+        geometries = [tuple(int(v) for v in g) for g in geometries]
+        if not geometries or any(len(g) != 3 for g in geometries):
+            raise BsxError("geometries must be a non-empty list of (width, height, n_streams)")
+        L = lib()
+        self = cls.__new__(cls)
+        self._cbs = (DEBUG_FN(ondebug) if ondebug else DEBUG_FN(), STAGE_FN(onprep) if onprep else STAGE_FN(),
+                     STAGE_FN(oninfer) if oninfer else STAGE_FN(), STAGE_FN(onmask) if onmask else STAGE_FN())
+        arr = (_Geometry * len(geometries))(*[_Geometry(*g) for g in geometries])
+        self.h = L.bsx_new_geoms(os.fsencode(model_path), threads, arr, len(geometries), device, *self._cbs, caller_ctx)
+        if not self.h:
+            raise BsxError("bsx_new_geoms failed: %s" % (L.bsx_last_error(None) or b"").decode(errors="replace").strip())
+        info = _Info()
+        _check(L.bsx_get_info(self.h, C.byref(info)), self.h, "bsx_get_info")
+        self.info = {k: (list(getattr(info, k)) if k in ("roi", "in_roi") else getattr(info, k)) for k, _ in _Info._fields_}
+        self.width, self.height, self.n_streams, self.device = info.width, info.height, info.n_streams, device
+        return self
+
+    def geometries(self):
+        """the context's geometry classes: a list of dicts (width, height, n_streams, first_stream, roi, in_roi, mask_offset) — one entry for a one-geometry context"""
+        if getattr(self, "_geoms", None) is None:
+            out = []
+            for g in range(lib().bsx_geom_count(self.h)):
+                gi = _GeomInfo()
+                _check(lib().bsx_get_geom_info(self.h, g, C.byref(gi)), self.h, "bsx_get_geom_info")
+                out.append({k: (list(getattr(gi, k)) if k in ("roi", "in_roi") else getattr(gi, k)) for k, _ in _GeomInfo._fields_})
+            self._geoms = out
+        return self._geoms
+
+    def _geom_of(self, stream):
+        for g in self.geometries():
+            if g["first_stream"] <= stream < g["first_stream"] + g["n_streams"]:
+                return g
+        raise BsxError("stream %d is out of range [0, %d)" % (stream, self.n_streams))
+
+    def _on_device(self, t):
+        return t.is_cuda and t.device.index == self.device
+
+    def masks_of(self, stream):
+        """torch u8 view [H_g, W_g] of the persistent mask of one stream, at the capture size of its class"""
+        stream = int(stream)
+        g = self._geom_of(stream)
+        px = g["width"] * g["height"]
+        p, b = C.c_void_p(), C.c_size_t()
+        _check(lib().bsx_debug_buffer(self.h, 3, C.byref(p), C.byref(b)), self.h, "bsx_debug_buffer")
+        return _as_torch(p.value + g["mask_offset"] + (stream - g["first_stream"]) * px, px, "uint8", (g["height"], g["width"]), self.device)
+
+    def step_geoms(self, ids, frames, outs, settings, yuyv=False, no_mask=False):
+        """one main-loop iteration for streams of ANY mix of the context's geometry classes (bsx_step_batch_geoms): ids[i] names the stream of position i, frames[i]
+        (cuda uint8 [H_g, W_g, 3]), outs[i] ([H_g, W_g, 3], or [.., 2] with yuyv) and settings[i] (a StreamSetting: bg at the class's size, flip_h, flip_v,
+        filter_off; no bgblur) have the capture size of that stream's class.  One prep launch, one network pass, one tile launch whatever the mix."""
+        torch = _torch()
+        arr, n = _ids(ids)
+        frames, outs, settings = list(frames), list(outs), list(settings)
+        if len(frames) != n or len(outs) != n or len(settings) != n:
+            raise BsxError("%d ids for %d frames, %d outs and %d settings" % (n, len(frames), len(outs), len(settings)))
+        items = (_GeomItem * max(n, 1))()
+        ch = 2 if yuyv else 3
+        for i in range(n):
+            g = self._geom_of(int(arr[i]))
+            H, W = g["height"], g["width"]
+
+            def ok(t, c):
+                return isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and self._on_device(t) and tuple(t.shape) == (H, W, c) and t.is_contiguous()
+            if not ok(frames[i], 3):
+                raise BsxError("frames[%d] must be a contiguous cuda:%d uint8 tensor [%d,%d,3] (stream %d)" % (i, self.device, H, W, arr[i]))
+            if not ok(outs[i], ch):
+                raise BsxError("outs[%d] must be a contiguous cuda:%d uint8 tensor [%d,%d,%d] (stream %d)" % (i, self.device, H, W, ch, arr[i]))
+            s = settings[i]
+            if not isinstance(s, StreamSetting):
+                raise BsxError("settings[%d] is not a StreamSetting" % i)
+            if s.bgblur:
+                raise BsxError("settings[%d]: bgblur is not taken by step_geoms" % i)
+            if not s.filter_off and s.bg is None:
+                raise BsxError("settings[%d]: bg is required unless filter_off is set" % i)
+            if s.bg is not None and not ok(s.bg, 3):
+                raise BsxError("settings[%d].bg must be a contiguous cuda:%d uint8 tensor [%d,%d,3] (stream %d)" % (i, self.device, H, W, arr[i]))
+            items[i].d_frame, items[i].d_out = frames[i].data_ptr(), outs[i].data_ptr()
+            items[i].setting.d_bg = s.bg.data_ptr() if s.bg is not None else None
+            items[i].setting.flags = s.flags()
+        flags = (1 if yuyv else 0) | (8 if no_mask else 0)
+        _check(lib().bsx_step_batch_geoms(self.h, arr, items, n, _stream_ptr(), flags), self.h, "bsx_step_batch_geoms")
+        return outs
 
     # ---- batched device path -----------------------------------------------------------------
     def process_batch(self, frames, masks_out=None):

@@ -185,6 +185,26 @@ struct bsx_ctx {
   ResizeBatchDesc* d_rsz = nullptr;         // device, likewise
   struct Span { uintptr_t begin, end; int item; bool dst; };
   std::vector<Span> rsz_spans;              // host scratch of the overlap check: the call's sources and destinations, sorted by address
+  // Geometry classes (bsx_new_geoms): class 0 IS the context's own geometry — width, height, roi, in_roi, both tables and the first bytes of d_masks above — so every
+  // one-geometry path reads what it always read; classes 1.. add their own ROIs and tables and their own slice of the ONE d_masks allocation.  Streams are numbered
+  // class after class.  Model-side state (ofinal by slot, arena, network buffers, weights, kernels) exists once.  bsx_step_batch_geoms advances streams of any mix of
+  // classes in one launch sequence (kernels.hpp: GeomClass / GeomDesc / GeomSpans); every other stepping entry point refuses a context with more than one class.
+  struct Geom {
+    int width = 0, height = 0, n_streams = 0, first = 0;
+    Rect4 roi{}, in_roi{};
+    DevResizeTab tab_down, tab_up;     // class 0: copies of the context's (the device memory is owned there)
+    size_t mask_offset = 0, tiles_per_frame = 0;
+    int outside_blocks = 0;            // outside-ROI workgroups of one position (0: the ROI is the frame)
+    bool fusable = false, xcd = false; // on the fused tile route (geom_class_fusable); mask tiles of a frame on one XCD (geom_class_xcd)
+  };
+  std::vector<Geom> geoms;
+  size_t mask_bytes = 0;                    // the whole d_masks allocation
+  GeomClass* d_geom_classes = nullptr;      // device copy of the class records (uploaded by bsx_new_geoms; for a one-class context on its first geoms step)
+  uint8_t* d_geom_tile_class = nullptr;     // one byte per workgroup of the largest ragged tile grid (every stream of every class) + 4; null: BSX_NO_UNIFORM_TILES
+  GeomDesc* h_geo = nullptr;                // pinned [kIdRing][n_streams]: the descriptors of a geoms step, ordered by class (the ring entries and events of the ids)
+  GeomDesc* d_geo = nullptr;                // device, likewise
+  std::vector<int> geo_order, geo_ids;      // host scratch: the call's positions ordered by class, their stream ids in that order
+  int geom_of(int stream) const { int g = 0; while (g + 1 < (int)geoms.size() && stream >= geoms[g + 1].first) g++; return g; }
   bool act16 = false;                  // BSX_ACT16=1: 16-bit activation STORAGE for the segmented Meet / MLKit networks (g1) — opt-in, IoU-gated; needs the specialised middle kernel
 
   // stream-0 view of a graph tensor (network input/output have dedicated buffers; intermediates are batch-major in
@@ -255,6 +275,32 @@ int model_type_from_name(const std::string& n) {  // lib/libbackscrub.cc:116-130
   return BSX_MODEL_UNKNOWN;
 }
 
+// what bsx_step_batch_geoms needs on the device beyond the context's own state: the class records, the class bytes of the ragged tile grid, the descriptor ring.
+// Idempotent: bsx_new_geoms calls it for a context of several classes, the first geoms step of a one-class context does (like h_mix: allocated on first use).
+int geoms_device_state(bsx_ctx* c) {
+  if (c->d_geo) return BSX_OK;
+  const size_t G = c->geoms.size(), N = (size_t)c->n_streams;
+  std::vector<GeomClass> rec(G);
+  size_t tiles = 0;
+  for (size_t g = 0; g < G; g++) {
+    const bsx_ctx::Geom& q = c->geoms[g];
+    rec[g] = GeomClass{q.width, q.height, (q.roi.w + mask_tile_width() - 1) / mask_tile_width(), (q.roi.h + mask_tile_height() - 1) / mask_tile_height(), q.roi, q.in_roi,
+                       q.tab_down.tab, q.tab_up.tab};
+    tiles += (size_t)q.n_streams * q.tiles_per_frame;
+  }
+  if (!c->d_geom_classes) {
+    BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_geom_classes), G * sizeof(GeomClass)));
+    BSX_HIP(c, hipMemcpy(c->d_geom_classes, rec.data(), G * sizeof(GeomClass), hipMemcpyHostToDevice));
+  }
+  if (!c->no_uniform_tiles && !c->d_geom_tile_class) {
+    BSX_HIP(c, hipMalloc(&c->d_geom_tile_class, tiles + 4));        // (+4: the tile kernel reads the aligned word around a byte)
+    BSX_HIP(c, hipMemset(c->d_geom_tile_class, 0, tiles + 4));
+  }
+  if (!c->h_geo) BSX_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_geo), bsx_ctx::kIdRing * N * sizeof(GeomDesc), hipHostMallocDefault));
+  BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_geo), bsx_ctx::kIdRing * N * sizeof(GeomDesc)));
+  return BSX_OK;
+}
+
 int init_device_state(bsx_ctx* c) {
   BSX_HIP(c, hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
   const size_t N = (size_t)c->n_streams;
@@ -308,9 +354,9 @@ int init_device_state(bsx_ctx* c) {
   if (BSX_DBG_ENV("BSX_NO_GRAPH")) c->graph_state = -1;
   c->in_u8 = v.u8in && ((c->use_program && c->plan.seg.on) || (!c->use_program && head0_u8_ok(c->plan)));
   BSX_HIP(c, hipMalloc(&c->d_ofinal, N * c->outW * c->outH));
-  BSX_HIP(c, hipMalloc(&c->d_masks, N * c->width * c->height));
+  BSX_HIP(c, hipMalloc(&c->d_masks, c->mask_bytes));                       // (one geometry: N * width * height)
   BSX_HIP(c, hipMemset(c->d_ofinal, 0, N * c->outW * c->outH));            // :257 leaves it uninitialised; defined as 0
-  BSX_HIP(c, hipMemset(c->d_masks, 255, N * c->width * c->height));        // :248
+  BSX_HIP(c, hipMemset(c->d_masks, 255, c->mask_bytes));                   // :248
   // bilateralFilter(d=5, sigmaColor=100, sigmaSpace=100) tables (OpenCV bilateral_filter):
   {
     const double sigma_color = 100.0, sigma_space = 100.0;
@@ -338,13 +384,28 @@ int init_device_state(bsx_ctx* c) {
   if (rc) return rc;
   // one class byte per (stream, mask tile) for the tile kernel's uniform-tile shortcut (kernels_img.hip: tile_class_k); absent = every tile on the general path
   c->tiles_per_frame = (size_t)((c->roi.w + mask_tile_width() - 1) / mask_tile_width()) * (size_t)((c->roi.h + mask_tile_height() - 1) / mask_tile_height());
-  if (!c->no_uniform_tiles && c->tab_up.tab.mode == 0 && c->tab_up.tab.tile_ok) {
+  if (!c->no_uniform_tiles && c->tab_up.tab.mode == 0 && c->tab_up.tab.tile_ok && c->geoms.size() <= 1) {      // (several classes: only the geoms step runs, with its own)
     BSX_HIP(c, hipMalloc(&c->d_tile_class, N * c->tiles_per_frame + 4));          // (+4: the tile kernel reads the aligned word around a byte)
     BSX_HIP(c, hipMemset(c->d_tile_class, 0, N * c->tiles_per_frame + 4));
     c->tab_up.tab.tile_class = c->d_tile_class;
   }
   // canvas outside in_roi is written as 0 by the prep kernel on every frame (the reference keeps a
   // persistent zeroed in_u8_bgr, :251); nothing else to initialise.
+  // geometry classes: class 0 is what was just built; the others get their own tables; with more than one class the device records go up now
+  for (size_t g = 0; g < c->geoms.size(); g++) {
+    bsx_ctx::Geom& G = c->geoms[g];
+    if (g == 0) { G.tab_down = c->tab_down; G.tab_up = c->tab_up; }
+    else {
+      if ((rc = upload_tab(c, make_resize_tab(G.roi.w, G.roi.h, G.in_roi.w, G.in_roi.h), &G.tab_down))) return rc;
+      if ((rc = upload_tab(c, make_resize_tab(G.in_roi.w, G.in_roi.h, G.roi.w, G.roi.h), &G.tab_up))) return rc;
+    }
+    G.tab_up.tab.tile_class = nullptr;                             // (the geoms step's class bytes travel as a kernel argument)
+    G.tiles_per_frame = (size_t)((G.roi.w + mask_tile_width() - 1) / mask_tile_width()) * (size_t)((G.roi.h + mask_tile_height() - 1) / mask_tile_height());
+    G.outside_blocks = geom_outside_blocks(G.width, G.height, G.roi);
+    G.fusable = geom_class_fusable(G.width, G.roi, G.tab_up.tab);
+    G.xcd = geom_class_xcd(G.width, G.roi);
+  }
+  if (c->geoms.size() > 1) return geoms_device_state(c);
   return BSX_OK;
 }
 
@@ -490,6 +551,11 @@ namespace {
 // every entry point that advances the temporal state refuses while the two-deep pipeline holds a composite that reads it
 int refuse_pending(bsx_ctx* c, const char* fn) {
   return c->pend.active ? refuse(c, fn, "a pipelined composite is pending (flush with bsx_step_batch_pipelined(ctx, NULL, ...) first)") : BSX_OK;
+}
+
+// every entry point that works at "the" capture size refuses a context of several geometry classes (bsx_new_geoms): only bsx_step_batch_geoms steps those
+int refuse_geoms(bsx_ctx* c, const char* fn) {
+  return c->geoms.size() > 1 ? refuse(c, fn, "context has %d geometries (only bsx_step_batch_geoms steps such a context)", (int)c->geoms.size()) : BSX_OK;
 }
 
 // flags (bsx.h): BSX_STEP_YUYV (the composite leaves as YUYV 4:2:2), BSX_STEP_FLIP_H / _V (cv::flip of the composite), BSX_STEP_NO_MASK, BSX_STEP_YUYV_IN (the
@@ -846,6 +912,7 @@ int mix_stage(bsx_ctx* c, const bsx_stream_setting* st, StepReq& r, int k) {
 // and run
 int step_call(bsx_ctx* c, const char* fn, Entry kind, StepReq r, const int* host_ids = nullptr, const bsx_stream_setting* settings = nullptr) {
   if (!c) return BSX_EINVAL;
+  if (const int rc = refuse_geoms(c, fn)) return rc;
   if (kind != Entry::Vcam && kind != Entry::VcamMixed) { r.out_w = c->width; r.out_h = c->height; }
   if (kind == Entry::VcamMixed && !r.resize(c)) {                 // the capture size: bsx_step_batch_mixed with its own refusals (the no-mask form stays refused)
     if (r.flags & BSX_STEP_NO_MASK) return refuse(c, fn, "unsupported flags 0x%x (the no-mask step has no vcam form)", r.flags);
@@ -884,6 +951,20 @@ int bg_tab(bsx_ctx* c, int sw, int sh, int dw, int dh, const DevResizeTab** out)
   *out = &it->second;
   return BSX_OK;
 }
+// Does a destination among the spans overlap a source or another destination?  Sorted by address, one sweep; *d = the destination (named first: it is the one the
+// caller placed wrongly), *o = what it overlaps.
+bool spans_overlap(std::vector<bsx_ctx::Span>& sp, const bsx_ctx::Span** d, const bsx_ctx::Span** o) {
+  std::sort(sp.begin(), sp.end(), [](const bsx_ctx::Span& a, const bsx_ctx::Span& b) { return a.begin < b.begin; });
+  const bsx_ctx::Span* far_any = nullptr;   // of the spans that begin at or below the current one: the one that ends last, and the destination that ends last
+  const bsx_ctx::Span* far_dst = nullptr;
+  for (const bsx_ctx::Span& v : sp) {
+    const bsx_ctx::Span* hit = v.dst ? far_any : far_dst;
+    if (hit && hit->end > v.begin) { *d = v.dst ? &v : hit; *o = v.dst ? hit : &v; return true; }
+    if (!far_any || v.end > far_any->end) far_any = &v;
+    if (v.dst && (!far_dst || v.end > far_dst->end)) far_dst = &v;
+  }
+  return false;
+}
 // host-side validation of items[0..n): nothing is enqueued before it passes.  A destination may overlap neither a source picture nor another destination (the
 // launch reads and writes them in no order); sources may overlap each other — two entries may name one picture.  Sorted by address, one sweep.
 int resize_batch_check(bsx_ctx* c, const char* fn, const bsx_resize_item* items, int n, int dw, int dh) {
@@ -903,20 +984,11 @@ int resize_batch_check(bsx_ctx* c, const char* fn, const bsx_resize_item* items,
     sp.push_back({(uintptr_t)it.d_src, (uintptr_t)it.d_src + (size_t)it.sw * it.sh * 3, i, false});
     sp.push_back({(uintptr_t)it.d_dst, (uintptr_t)it.d_dst + out_bytes, i, true});
   }
-  std::sort(sp.begin(), sp.end(), [](const bsx_ctx::Span& a, const bsx_ctx::Span& b) { return a.begin < b.begin; });
-  const bsx_ctx::Span* far_any = nullptr;   // of the spans that begin at or below the current one: the one that ends last, and the destination that ends last
-  const bsx_ctx::Span* far_dst = nullptr;
-  for (const bsx_ctx::Span& v : sp) {
-    const bsx_ctx::Span* hit = v.dst ? far_any : far_dst;
-    if (hit && hit->end > v.begin) {
-      const bsx_ctx::Span& d = v.dst ? v : *hit;          // name the destination first: it is the one the caller placed wrongly
-      const bsx_ctx::Span& o = v.dst ? *hit : v;
-      return refuse(c, fn, "items[%d]: d_dst %p overlaps the %s of items[%d] (%p)", d.item, (const void*)d.begin, o.dst ? "destination" : "source picture", o.item,
-                    (const void*)o.begin);
-    }
-    if (!far_any || v.end > far_any->end) far_any = &v;
-    if (v.dst && (!far_dst || v.end > far_dst->end)) far_dst = &v;
-  }
+  const bsx_ctx::Span* d = nullptr;
+  const bsx_ctx::Span* o = nullptr;
+  if (spans_overlap(sp, &d, &o))
+    return refuse(c, fn, "items[%d]: d_dst %p overlaps the %s of items[%d] (%p)", d->item, (const void*)d->begin, o->dst ? "destination" : "source picture", o->item,
+                  (const void*)o->begin);
   return BSX_OK;
 }
 // items[0..n) as ResizeBatchDesc into ring entry k (pinned), one copy to the device entry on s
@@ -933,6 +1005,102 @@ int resize_batch_stage(bsx_ctx* c, const bsx_resize_item* items, int n, int dw, 
   }
   BSX_HIP(c, hipMemcpyAsync(c->d_rsz + (size_t)k * N, hd, (size_t)n * sizeof(ResizeBatchDesc), hipMemcpyHostToDevice, s));
   *d_desc = c->d_rsz + (size_t)k * N;
+  return BSX_OK;
+}
+
+// ---- bsx_step_batch_geoms: streams of any mix of geometry classes in ONE prep launch, ONE network pass, ONE tile-class and ONE tile launch ----------------------
+// Checked on the host (ids, then every position against the class of its id, then the overlaps), then: the positions ordered by class, their ids and descriptors
+// through the staging ring, the per-class spans of the ragged grids by value in the kernel arguments.
+constexpr unsigned kGeomStreamFlags = BSX_STEP_FLIP_H | BSX_STEP_FLIP_V | BSX_STREAM_FILTER_OFF;
+
+int geoms_check(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item* items, int n, unsigned flags) {
+  if (!items) return refuse(c, fn, "items is NULL");
+  if (flags & BSX_STEP_YUYV_IN) return refuse(c, fn, "flags 0x%x: YUYV input frames are not taken by the multi-geometry step", flags);
+  if (flags & ~(BSX_STEP_YUYV | BSX_STEP_NO_MASK)) return refuse(c, fn, "flags 0x%x has bits outside yuyv / no-mask", flags);
+  if (const int rc = refuse_pending(c, fn)) return rc;
+  if (c->onmask) return refuse(c, fn, "needs the fused mask + blend route (no onmask callback)");
+  const bool yuyv = (flags & BSX_STEP_YUYV) != 0;
+  std::vector<bsx_ctx::Span>& sp = c->rsz_spans;
+  sp.clear();
+  for (int i = 0; i < n; i++) {
+    const bsx_geom_item& it = items[i];
+    const int g = c->geom_of(ids[i]);
+    const bsx_ctx::Geom& G = c->geoms[g];
+    const unsigned f = it.setting.flags;
+    if (f & 0xFF00u) return refuse(c, fn, "items[%d]: setting flags 0x%x asks for a background blur, which the multi-geometry step does not take", i, f);
+    if (f & ~kGeomStreamFlags) return refuse(c, fn, "items[%d]: setting flags 0x%x has bits outside flip / filter-off", i, f);
+    if (!it.d_frame) return refuse(c, fn, "items[%d]: d_frame is NULL", i);
+    if ((uintptr_t)it.d_frame & 3) return refuse(c, fn, "items[%d]: d_frame %p is not 4-byte aligned", i, (const void*)it.d_frame);
+    if (!it.d_out) return refuse(c, fn, "items[%d]: d_out is NULL", i);
+    if ((uintptr_t)it.d_out & 3) return refuse(c, fn, "items[%d]: d_out %p is not 4-byte aligned", i, (const void*)it.d_out);
+    if (yuyv && (G.width & 1)) return refuse(c, fn, "items[%d]: YUYV output needs an even width (stream %d is of class %d, %d x %d)", i, ids[i], g, G.width, G.height);
+    if (!G.fusable)
+      return refuse(c, fn, "items[%d]: stream %d is of class %d (%d x %d), which is off the fused tile route (width, roi.x, roi.w multiples of 4, a tiled linear mask up-scale)",
+                    i, ids[i], g, G.width, G.height);
+    const size_t px = (size_t)G.width * G.height;
+    sp.push_back({(uintptr_t)it.d_frame, (uintptr_t)it.d_frame + px * 3, i, false});
+    sp.push_back({(uintptr_t)it.d_out, (uintptr_t)it.d_out + px * (yuyv ? 2 : 3), i, true});
+    if (f & BSX_STREAM_FILTER_OFF) continue;                          // reads no background
+    if (!it.setting.d_bg) return refuse(c, fn, "items[%d]: setting.d_bg is NULL", i);
+    if ((uintptr_t)it.setting.d_bg & 3) return refuse(c, fn, "items[%d]: setting.d_bg %p is not 4-byte aligned", i, (const void*)it.setting.d_bg);
+    sp.push_back({(uintptr_t)it.setting.d_bg, (uintptr_t)it.setting.d_bg + px * 3, i, false});
+  }
+  const bsx_ctx::Span* d = nullptr;
+  const bsx_ctx::Span* o = nullptr;
+  if (spans_overlap(sp, &d, &o))
+    return refuse(c, fn, "items[%d]: d_out %p overlaps %s of items[%d] (%p)", d->item, (const void*)d->begin, o->dst ? "the output" : "a frame or background", o->item,
+                  (const void*)o->begin);
+  return BSX_OK;
+}
+
+// the checked call on the context's device, ring entry k acquired
+int geoms_run(bsx_ctx* c, const int* ids, const bsx_geom_item* items, int n, hipStream_t s, unsigned flags, int k) {
+  const int G = (int)c->geoms.size();
+  // positions ordered by class (a counting sort: stable, so a class keeps the caller's order)
+  int count[kMaxGeoms] = {0};
+  for (int i = 0; i < n; i++) count[c->geom_of(ids[i])]++;
+  GeomSpans prep{}, tiles{}, outside{};
+  unsigned xcd_mask = 0;
+  for (int g = 0; g < kMaxGeoms; g++) {
+    const int cnt = g < G ? count[g] : 0;
+    const int per_t = g < G ? (int)c->geoms[g].tiles_per_frame : 0, per_o = g < G ? c->geoms[g].outside_blocks : 0;
+    if ((long)tiles.wg[g] + (long)cnt * per_t >= (1l << 31) || (long)outside.wg[g] + (long)cnt * per_o >= (1l << 31)) {
+      c->last_error = "error: bsx_step_batch_geoms: the batch needs more than 2^31 workgroups\n"; return BSX_EDEVICE; }
+    prep.pos[g + 1] = tiles.pos[g + 1] = outside.pos[g + 1] = tiles.pos[g] + cnt;
+    tiles.wg[g + 1] = tiles.wg[g] + cnt * per_t; tiles.per[g] = per_t;
+    outside.wg[g + 1] = outside.wg[g] + cnt * per_o; outside.per[g] = per_o;
+    if (g < G && c->geoms[g].xcd) xcd_mask |= 1u << g;
+  }
+  c->geo_order.resize((size_t)n); c->geo_ids.resize((size_t)n);
+  int next[kMaxGeoms];
+  for (int g = 0; g < kMaxGeoms; g++) next[g] = tiles.pos[g];
+  for (int i = 0; i < n; i++) c->geo_order[(size_t)next[c->geom_of(ids[i])]++] = i;
+  GeomDesc* hd = c->h_geo + (size_t)k * c->n_streams;
+  for (int j = 0; j < n; j++) {
+    const int i = c->geo_order[(size_t)j], id = ids[i];
+    const bsx_ctx::Geom& q = c->geoms[c->geom_of(id)];
+    const bsx_geom_item& it = items[i];
+    c->geo_ids[(size_t)j] = id;
+    const bool off = (it.setting.flags & BSX_STREAM_FILTER_OFF) != 0;
+    hd[j] = GeomDesc{it.d_frame, it.d_out, off ? nullptr : it.setting.d_bg, c->d_masks + q.mask_offset + (size_t)(id - q.first) * q.width * q.height,
+                     it.setting.flags & (kMixFlipH | kMixFlipV | kMixFilterOff), id, {0, 0}};
+  }
+  const int* d_ids = nullptr;
+  if (const int rc = ids_copy(c, c->geo_ids.data(), n, s, k, &d_ids)) return rc;
+  GeomDesc* const dd = c->d_geo + (size_t)k * c->n_streams;
+  BSX_HIP(c, hipMemcpyAsync(dd, hd, (size_t)n * sizeof(GeomDesc), hipMemcpyHostToDevice, s));
+  {
+    bsx_roctx::Range range("bsx:prep");
+    float* f32 = !c->in_u8 ? c->tensor_ptr(c->plan.input) : nullptr;
+    BSX_HIP(c, launch_prep_geoms(c->d_geom_classes, dd, prep, f32, c->in_u8 ? c->d_net_in_u8 : nullptr, c->inW, c->inH, c->bilateral, n, s));
+  }
+  if (c->onprep) { BSX_HIP(c, hipStreamSynchronize(s)); c->onprep(c->caller_ctx); }
+  const bool fused_decode = infer_decodes(c);
+  if (const int rc = run_infer(c, n, s, !fused_decode, 0, d_ids)) return rc;
+  if (c->oninfer) { BSX_HIP(c, hipStreamSynchronize(s)); c->oninfer(c->caller_ctx); }
+  if (!fused_decode) { if (const int rc = run_decode(c, n, s, 0, d_ids)) return rc; }
+  bsx_roctx::Range range("bsx:mask+blend");
+  BSX_HIP(c, launch_mask_blend_geoms(c->d_geom_classes, dd, tiles, xcd_mask, outside, c->d_ofinal, c->outW, c->outH, c->d_geom_tile_class, n, s, (int)flags));
   return BSX_OK;
 }
 
@@ -990,10 +1158,27 @@ int bsx_device_count(void) {
 
 const char* bsx_last_error(const bsx_ctx* ctx) { return ctx ? ctx->last_error.c_str() : g_last_error.c_str(); }
 
-bsx_ctx* bsx_new(const char* model_path, size_t threads, size_t width, size_t height, int n_streams, int device, bsx_debug_fn ondebug,
-                 bsx_stage_fn onprep, bsx_stage_fn oninfer, bsx_stage_fn onmask, void* caller_ctx) {
-  if (!model_path || !width || !height || n_streams <= 0 || n_streams > 65535) {   // grid.z of the mask kernel carries the stream index
-    report(nullptr, ondebug, caller_ctx, "error: bad arguments to bsx_new\n"); return nullptr; }
+// ROI geometry of a width x height capture for the loaded model, float arithmetic truncated to int exactly as lib/libbackscrub.cc:230-246; false: empty or out of range
+static bool capture_rois(const bsx_ctx* c, size_t width, size_t height, Rect4* roi, Rect4* in_roi) {
+  float ratio = (float)c->inH / (float)c->inW;
+  float frameratio = (float)height / (float)width;
+  if (frameratio < ratio) {
+    *roi = Rect4{(int)((width - height / ratio) / 2), 0, (int)(height / ratio), (int)height};
+    *in_roi = Rect4{0, 0, c->inW, c->inH};
+  } else {
+    *roi = Rect4{0, 0, (int)width, (int)height};
+    *in_roi = Rect4{(int)((c->inW - c->inH / frameratio) / 2), 0, (int)(c->inH / frameratio), c->inH};
+  }
+  return !(roi->w <= 0 || roi->h <= 0 || roi->x < 0 || roi->x + roi->w > (int)width || in_roi->w <= 0 || in_roi->x < 0 || in_roi->x + in_roi->w > c->inW ||
+           in_roi->x + in_roi->w > c->outW || in_roi->h > c->outH);
+}
+
+// bsx_new / bsx_new_geoms: geoms[0..n_geoms) checked by the caller (positive sizes and counts, total <= 65535); class 0 becomes the context's own geometry
+static bsx_ctx* new_ctx(const char* model_path, size_t threads, const bsx_geometry* geoms, int n_geoms, int device, bsx_debug_fn ondebug, bsx_stage_fn onprep,
+                        bsx_stage_fn oninfer, bsx_stage_fn onmask, void* caller_ctx) {
+  const size_t width = (size_t)geoms[0].width, height = (size_t)geoms[0].height;
+  int n_streams = 0;
+  for (int g = 0; g < n_geoms; g++) n_streams += geoms[g].n_streams;
   try {   // nothing may throw across the C ABI (std::bad_alloc / length_error from a hostile model file included)
   std::unique_ptr<bsx_ctx> c(new bsx_ctx);
   c->ondebug = ondebug; c->onprep = onprep; c->oninfer = oninfer; c->onmask = onmask; c->caller_ctx = caller_ctx;
@@ -1022,24 +1207,36 @@ bsx_ctx* bsx_new(const char* model_path, size_t threads, size_t width, size_t he
   // the per-launch path (BSX_NO_FRAME_PROGRAM) executes the plain step list: it needs the unsegmented plan
   const bool segments = BSX_DBG_ENV("BSX_NO_SEGMENTS") == nullptr && BSX_DBG_ENV("BSX_NO_FRAME_PROGRAM") == nullptr;
   if (!build_plan(c->graph, &c->plan, &err, !no_reuse, segments)) { report(nullptr, ondebug, caller_ctx, "error: unable to build GPU plan: %s\n", err.c_str()); return nullptr; }
-  // ROI geometry, float arithmetic truncated to int exactly as lib/libbackscrub.cc:230-246
-  float ratio = (float)c->inH / (float)c->inW;
-  float frameratio = (float)height / (float)width;
-  if (frameratio < ratio) {
-    c->roi = Rect4{(int)((width - height / ratio) / 2), 0, (int)(height / ratio), (int)height};
-    c->in_roi = Rect4{0, 0, c->inW, c->inH};
-  } else {
-    c->roi = Rect4{0, 0, (int)width, (int)height};
-    c->in_roi = Rect4{(int)((c->inW - c->inH / frameratio) / 2), 0, (int)(c->inH / frameratio), c->inH};
-  }
-  if (c->roi.w <= 0 || c->roi.h <= 0 || c->roi.x < 0 || c->roi.x + c->roi.w > c->width || c->in_roi.w <= 0 || c->in_roi.x < 0 ||
-      c->in_roi.x + c->in_roi.w > c->inW || c->in_roi.x + c->in_roi.w > c->outW || c->in_roi.h > c->outH) {
+  if (!capture_rois(c.get(), width, height, &c->roi, &c->in_roi)) {
     report(nullptr, ondebug, caller_ctx, "error: frame/model geometry yields an empty or out-of-range ROI\n");
     return nullptr;
   }
+  c->no_mask_tile = BSX_DBG_ENV("BSX_NO_MASK_TILE") != nullptr;
+  // the geometry classes: streams numbered class after class, one slice of the mask allocation each.  With more than one class, every class must be one the
+  // geoms step takes — the rule bsx_step_batch_mixed applies per call (the fused tile route), applied here, before any device work
+  for (int g = 0; g < n_geoms; g++) {
+    bsx_ctx::Geom G;
+    G.width = geoms[g].width; G.height = geoms[g].height; G.n_streams = geoms[g].n_streams;
+    G.first = g ? c->geoms[g - 1].first + c->geoms[g - 1].n_streams : 0;
+    G.mask_offset = c->mask_bytes;
+    c->mask_bytes += (size_t)G.n_streams * G.width * G.height;
+    if (!capture_rois(c.get(), (size_t)G.width, (size_t)G.height, &G.roi, &G.in_roi)) {
+      report(nullptr, ondebug, caller_ctx, "error: bsx_new_geoms: geoms[%d] (%d x %d): frame/model geometry yields an empty or out-of-range ROI\n", g, G.width, G.height);
+      return nullptr;
+    }
+    if (n_geoms > 1) {
+      const HostResizeTab up = make_resize_tab(G.in_roi.w, G.in_roi.h, G.roi.w, G.roi.h);
+      const bool tiles = up.mode == 0 && !c->no_mask_tile && mask_tile_fits(up.xofs.data(), up.yofs.data(), up.sw, up.sh, up.dw, up.dh);
+      if ((G.width & 3) || (G.roi.x & 3) || (G.roi.w & 3) || !tiles) {
+        report(nullptr, ondebug, caller_ctx, "error: bsx_new_geoms: geoms[%d] (%d x %d) is off the fused tile route: width %d, roi.x %d and roi.w %d must be multiples of 4 and "
+               "the mask up-scale %d x %d -> %d x %d a tiled linear one\n", g, G.width, G.height, G.width, G.roi.x, G.roi.w, G.in_roi.w, G.in_roi.h, G.roi.w, G.roi.h);
+        return nullptr;
+      }
+    }
+    c->geoms.push_back(G);
+  }
   c->no_mask_blend_fusion = BSX_DBG_ENV("BSX_NO_MASK_BLEND_FUSION") != nullptr;
   c->no_bgblur_fusion = BSX_DBG_ENV("BSX_NO_BGBLUR_FUSION") != nullptr;
-  c->no_mask_tile = BSX_DBG_ENV("BSX_NO_MASK_TILE") != nullptr;
   c->vcam_direct = BSX_DBG_ENV("BSX_VCAM_DIRECT") != nullptr;
   c->no_uniform_tiles = getenv("BSX_NO_UNIFORM_TILES") != nullptr;
   c->tail_generic = BSX_DBG_ENV("BSX_TAIL_GENERIC") != nullptr;
@@ -1072,6 +1269,33 @@ bsx_ctx* bsx_new(const char* model_path, size_t threads, size_t width, size_t he
   }
 }
 
+bsx_ctx* bsx_new(const char* model_path, size_t threads, size_t width, size_t height, int n_streams, int device, bsx_debug_fn ondebug,
+                 bsx_stage_fn onprep, bsx_stage_fn oninfer, bsx_stage_fn onmask, void* caller_ctx) {
+  if (!model_path || !width || !height || width > 0x7fffffffu || height > 0x7fffffffu || n_streams <= 0 || n_streams > 65535) {   // grid.z of the mask kernel carries the stream index
+    report(nullptr, ondebug, caller_ctx, "error: bad arguments to bsx_new\n"); return nullptr; }
+  const bsx_geometry one{(int)width, (int)height, n_streams};
+  return new_ctx(model_path, threads, &one, 1, device, ondebug, onprep, oninfer, onmask, caller_ctx);
+}
+
+bsx_ctx* bsx_new_geoms(const char* model_path, size_t threads, const bsx_geometry* geoms, int n_geoms, int device, bsx_debug_fn ondebug, bsx_stage_fn onprep,
+                       bsx_stage_fn oninfer, bsx_stage_fn onmask, void* caller_ctx) {
+  const char* fn = "error: bsx_new_geoms:";
+  if (!model_path || !geoms) { report(nullptr, ondebug, caller_ctx, "%s model_path or geoms is NULL\n", fn); return nullptr; }
+  if (n_geoms < 1 || n_geoms > BSX_MAX_GEOMS) { report(nullptr, ondebug, caller_ctx, "%s n_geoms = %d is outside [1, %d]\n", fn, n_geoms, BSX_MAX_GEOMS); return nullptr; }
+  long total = 0;
+  for (int g = 0; g < n_geoms; g++) {
+    if (geoms[g].width <= 0 || geoms[g].height <= 0) { report(nullptr, ondebug, caller_ctx, "%s geoms[%d]: size %d x %d is not positive\n", fn, g, geoms[g].width, geoms[g].height); return nullptr; }
+    if (geoms[g].n_streams <= 0) { report(nullptr, ondebug, caller_ctx, "%s geoms[%d] (%d x %d): n_streams = %d is not positive\n", fn, g, geoms[g].width, geoms[g].height, geoms[g].n_streams); return nullptr; }
+    for (int k = 0; k < g; k++)
+      if (geoms[k].width == geoms[g].width && geoms[k].height == geoms[g].height) {
+        report(nullptr, ondebug, caller_ctx, "%s geoms[%d] (%d x %d) repeats the size of geoms[%d]\n", fn, g, geoms[g].width, geoms[g].height, k); return nullptr; }
+    total += geoms[g].n_streams;
+    if (total > 65535) { report(nullptr, ondebug, caller_ctx, "%s geoms[%d] (%d x %d) brings the total to %ld streams, above 65535\n", fn, g, geoms[g].width, geoms[g].height, total); return nullptr; }
+  }
+  if (n_geoms > 1 && onmask) { report(nullptr, ondebug, caller_ctx, "%s an onmask callback needs a context of one geometry (%d given)\n", fn, n_geoms); return nullptr; }
+  return new_ctx(model_path, threads, geoms, n_geoms, device, ondebug, onprep, oninfer, onmask, caller_ctx);
+}
+
 void bsx_delete(bsx_ctx* c) {
   if (!c) return;
   DeviceGuard guard(c->device);
@@ -1095,6 +1319,11 @@ void bsx_delete(bsx_ctx* c) {
   if (c->h_mix) (void)hipHostFree(c->h_mix);
   if (c->d_rsz) (void)hipFree(c->d_rsz);
   if (c->h_rsz) (void)hipHostFree(c->h_rsz);
+  for (size_t g = 1; g < c->geoms.size(); g++) { if (c->geoms[g].tab_down.mem) (void)hipFree(c->geoms[g].tab_down.mem); if (c->geoms[g].tab_up.mem) (void)hipFree(c->geoms[g].tab_up.mem); }
+  if (c->d_geom_classes) (void)hipFree(c->d_geom_classes);
+  if (c->d_geom_tile_class) (void)hipFree(c->d_geom_tile_class);
+  if (c->d_geo) (void)hipFree(c->d_geo);
+  if (c->h_geo) (void)hipHostFree(c->h_geo);
   delete c;
 }
 
@@ -1119,7 +1348,7 @@ int bsx_reset(bsx_ctx* c, void* stream) {
   const size_t N = (size_t)c->n_streams;
   c->pend.active = false;                                          // a composite still pending in the two-deep pipeline is dropped with the state it belongs to
   BSX_HIP(c, hipMemsetAsync(c->d_ofinal, 0, N * c->outW * c->outH, s));
-  BSX_HIP(c, hipMemsetAsync(c->d_masks, 255, N * c->width * c->height, s));
+  BSX_HIP(c, hipMemsetAsync(c->d_masks, 255, c->mask_bytes, s));
   return BSX_OK;
 }
 
@@ -1127,6 +1356,7 @@ uint8_t* bsx_masks_device(bsx_ctx* c) { return c ? c->d_masks : nullptr; }
 
 int bsx_process_batch(bsx_ctx* c, const uint8_t* d_frames, int n, uint8_t* d_masks, void* stream) {
   if (!c || !d_frames || n <= 0 || n > c->n_streams) return BSX_EINVAL;
+  if (const int rc = refuse_geoms(c, "bsx_process_batch")) return rc;
   if (const int rc = refuse_pending(c, "bsx_process_batch")) return rc;
   DeviceGuard guard(c->device);
   hipStream_t s = pick(c, stream);
@@ -1137,6 +1367,7 @@ int bsx_process_batch(bsx_ctx* c, const uint8_t* d_frames, int n, uint8_t* d_mas
 
 int bsx_process_host(bsx_ctx* c, int stream_idx, const uint8_t* h_bgr, size_t bgr_stride, uint8_t* h_mask, size_t mask_stride) {
   if (!c || !h_bgr || !h_mask || stream_idx < 0 || stream_idx >= c->n_streams) return BSX_EINVAL;
+  if (const int rc = refuse_geoms(c, "bsx_process_host")) return rc;
   if (bgr_stride < (size_t)c->width * 3 || mask_stride < (size_t)c->width) return BSX_ESIZE;
   if (const int rc = refuse_pending(c, "bsx_process_host")) return rc;
   DeviceGuard guard(c->device);
@@ -1175,6 +1406,7 @@ int bsx_process_host(bsx_ctx* c, int stream_idx, const uint8_t* h_bgr, size_t bg
 int bsx_composite_batch(bsx_ctx* c, const uint8_t* d_bg, size_t bg_frame_stride, const uint8_t* d_frames, const uint8_t* d_masks, uint8_t* d_out,
                         int n, void* stream) {
   if (!c || !d_bg || !d_frames || !d_out || n <= 0) return BSX_EINVAL;
+  if (const int rc = refuse_geoms(c, "bsx_composite_batch")) return rc;
   if (!d_masks) { if (n > c->n_streams) return BSX_EINVAL; d_masks = c->d_masks; }
   DeviceGuard guard(c->device);
   bsx_roctx::Range range("bsx:blend");
@@ -1203,6 +1435,34 @@ int bsx_step_batch_mixed(bsx_ctx* c, const int* ids, const uint8_t* d_frames, co
   return step_call(c, "bsx_step_batch_mixed", Entry::Mixed, StepReq{d_frames, nullptr, 0, d_out, 0, 0, n, flags, (hipStream_t)stream, nullptr}, ids, settings);
 }
 
+int bsx_geom_count(const bsx_ctx* c) { return c ? (int)c->geoms.size() : BSX_EINVAL; }
+
+int bsx_get_geom_info(const bsx_ctx* c, int g, bsx_geom_info* o) {
+  if (!c || !o || g < 0 || g >= (int)c->geoms.size()) return BSX_EINVAL;
+  const bsx_ctx::Geom& G = c->geoms[(size_t)g];
+  memset(o, 0, sizeof *o);
+  o->width = G.width; o->height = G.height; o->n_streams = G.n_streams; o->first_stream = G.first;
+  int r[4] = {G.roi.x, G.roi.y, G.roi.w, G.roi.h}, q[4] = {G.in_roi.x, G.in_roi.y, G.in_roi.w, G.in_roi.h};
+  memcpy(o->roi, r, sizeof r); memcpy(o->in_roi, q, sizeof q);
+  o->mask_offset = G.mask_offset;
+  return BSX_OK;
+}
+
+// ids (host): position i is stream ids[i], whose class decides the geometry of items[i]; see bsx.h
+int bsx_step_batch_geoms(bsx_ctx* c, const int* ids, const bsx_geom_item* items, int n, void* stream, unsigned flags) {
+  const char* fn = "bsx_step_batch_geoms";
+  if (!c) return BSX_EINVAL;
+  if (const int rc = ids_check(c, fn, ids, n)) return rc;
+  if (n == 0) return refuse_pending(c, fn);
+  if (const int rc = geoms_check(c, fn, ids, items, n, flags)) return rc;
+  DeviceGuard guard(c->device);
+  hipStream_t s = pick(c, stream);
+  if (const int rc = geoms_device_state(c)) return rc;
+  int entry = 0;
+  if (const int rc = ring_acquire(c, &entry)) return rc;
+  return ids_release(c, entry, s, geoms_run(c, ids, items, n, s, flags, entry));
+}
+
 int bsx_reset_streams(bsx_ctx* c, const int* ids, int n, void* stream) {
   if (!c) return BSX_EINVAL;
   if (const int rc = ids_check(c, "bsx_reset_streams", ids, n)) return rc;
@@ -1212,10 +1472,29 @@ int bsx_reset_streams(bsx_ctx* c, const int* ids, int n, void* stream) {
   hipStream_t s = pick(c, stream);
   const int* d_ids = nullptr;
   int entry = 0;
-  if (const int rc = ids_stage(c, ids, n, s, &d_ids, &entry)) return rc;
-  const hipError_t e = launch_reset_slots(c->d_ofinal, (size_t)c->outW * c->outH, c->d_masks, (size_t)c->width * c->height, d_ids, n, s);
+  if (c->geoms.size() <= 1) {
+    if (const int rc = ids_stage(c, ids, n, s, &d_ids, &entry)) return rc;
+    const hipError_t e = launch_reset_slots(c->d_ofinal, (size_t)c->outW * c->outH, c->d_masks, (size_t)c->width * c->height, d_ids, n, s);
+    int rc = BSX_OK;
+    if (e != hipSuccess) { report(c, c->ondebug, c->caller_ctx, "error: HIP %s while resetting streams\n", hipGetErrorString(e)); rc = BSX_EDEVICE; }
+    return ids_release(c, entry, s, rc);
+  }
+  // several classes: the ids ordered by class, one launch per class present — a slot's mask has its class's size and lies in its class's slice (masks of slot s of
+  // class g: d_masks + mask_offset + (s - first) * bytes, i.e. slot-indexed from the slice's base moved back by `first` slots)
+  c->geo_ids.assign(ids, ids + n);
+  std::stable_sort(c->geo_ids.begin(), c->geo_ids.end(), [&](int a, int b) { return c->geom_of(a) < c->geom_of(b); });
+  if (const int rc = ids_stage(c, c->geo_ids.data(), n, s, &d_ids, &entry)) return rc;
   int rc = BSX_OK;
-  if (e != hipSuccess) { report(c, c->ondebug, c->caller_ctx, "error: HIP %s while resetting streams\n", hipGetErrorString(e)); rc = BSX_EDEVICE; }
+  for (int j = 0; j < n && rc == BSX_OK;) {
+    const bsx_ctx::Geom& G = c->geoms[(size_t)c->geom_of(c->geo_ids[(size_t)j])];
+    int e2 = j;
+    while (e2 < n && c->geo_ids[(size_t)e2] < G.first + G.n_streams) e2++;
+    const size_t mb = (size_t)G.width * G.height;
+    uint8_t* const base = reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(c->d_masks) + G.mask_offset - (size_t)G.first * mb);
+    const hipError_t e = launch_reset_slots(c->d_ofinal, (size_t)c->outW * c->outH, base, mb, d_ids + j, e2 - j, s);
+    if (e != hipSuccess) { report(c, c->ondebug, c->caller_ctx, "error: HIP %s while resetting streams\n", hipGetErrorString(e)); rc = BSX_EDEVICE; }
+    j = e2;
+  }
   return ids_release(c, entry, s, rc);
 }
 
@@ -1233,6 +1512,7 @@ int bsx_step_batch_vcam(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg
 
 int bsx_step_batch_pipelined(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_frame_stride, uint8_t* d_out, int n, void* stream, unsigned flags) {
   if (!c) return BSX_EINVAL;
+  if (const int rc = refuse_geoms(c, "bsx_step_batch_pipelined")) return rc;
   hipStream_t s = pick(c, stream);
   if (!d_frames) {                                                  // flush: the composite of the last batch, on the caller's stream
     DeviceGuard guard(c->device);
@@ -1331,7 +1611,7 @@ int bsx_debug_buffer(bsx_ctx* c, int which, void** d_ptr, size_t* bytes) {
     case 0: *d_ptr = c->tensor_ptr(c->plan.input); *bytes = N * c->inW * c->inH * c->inC * 4; break;
     case 1: *d_ptr = c->tensor_ptr(c->plan.output); *bytes = N * c->outW * c->outH * c->outC * 4; break;
     case 2: *d_ptr = c->d_ofinal; *bytes = N * c->outW * c->outH; break;
-    case 3: *d_ptr = c->d_masks; *bytes = N * c->width * c->height; break;
+    case 3: *d_ptr = c->d_masks; *bytes = c->mask_bytes; break;
     default: return BSX_EINVAL;
   }
   return BSX_OK;
@@ -1339,6 +1619,7 @@ int bsx_debug_buffer(bsx_ctx* c, int which, void** d_ptr, size_t* bytes) {
 
 int bsx_debug_run_stage(bsx_ctx* c, int stage, const uint8_t* d_frames, int n, void* stream) {
   if (!c || n <= 0 || n > c->n_streams) return BSX_EINVAL;
+  if (const int rc = refuse_geoms(c, "bsx_debug_run_stage")) return rc;
   if (stage >= 1 && stage <= 3) { if (const int rc = refuse_pending(c, "bsx_debug_run_stage")) return rc; }
   DeviceGuard guard(c->device);
   hipStream_t s = pick(c, stream);
@@ -1357,6 +1638,7 @@ int bsx_debug_run_stage(bsx_ctx* c, int stage, const uint8_t* d_frames, int n, v
 int bsx_profile_batch(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, size_t bg_stride, uint8_t* d_out, int n, int iters,
                       bsx_launch_stat* out, int cap, void* stream) {
   if (!c || !d_frames || !d_bg || !d_out || !out || n <= 0 || n > c->n_streams || iters <= 0) return BSX_EINVAL;
+  if (const int rc = refuse_geoms(c, "bsx_profile_batch")) return rc;
   if (const int rc = refuse_pending(c, "bsx_profile_batch")) return rc;
   DeviceGuard guard(c->device);
   hipStream_t s = pick(c, stream);
@@ -1465,6 +1747,7 @@ int bsx_profile_batch(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, 
 
 int bsx_debug_mask_tile_stats(bsx_ctx* c, int n, long* out4) {
   if (!c || !out4 || n <= 0 || n > c->n_streams) return BSX_EINVAL;
+  if (const int rc = refuse_geoms(c, "bsx_debug_mask_tile_stats")) return rc;
   DeviceGuard guard(c->device);
   out4[0] = (long)c->tiles_per_frame * n; out4[1] = out4[2] = 0; out4[3] = out4[0];
   if (!c->d_tile_class) return BSX_OK;                          // generic kernel / shortcut off: every tile is general

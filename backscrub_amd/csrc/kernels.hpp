@@ -124,6 +124,49 @@ static_assert(sizeof(MixDesc) == 16, "one 16-byte uniform load per workgroup");
 // from its frame; `flags`: the batch's bits only (bit 0 = YUYV out, bit 3 = no mask store, bit 4 = YUYV frames).  Same geometry as launch_mask_blend.
 hipError_t launch_mask_blend_mixed(const uint8_t* ofinal, int outW, int outH, Rect4 in_roi, ResizeTab tab, uint8_t* mask, int W, int H, Rect4 roi,
                                    const MixDesc* desc, const uint8_t* frames, uint8_t* out, int n, hipStream_t s, int flags, const int* slot_of = nullptr);
+// ---- bsx_step_batch_geoms: streams of several capture sizes ("geometry classes") in ONE prep launch, ONE network pass, ONE tile-class and ONE tile launch ------
+// The two ends of the pipeline that see the capture size read it per position.  Three pieces, each as cheap as its rate of change allows:
+//   GeomClass   one constant record per class, uploaded once: capture size, both ROIs, both resize tables, the mask tiling;
+//   GeomDesc    one record per position of a call, staged through the context's ring, ORDERED BY CLASS: the position's own frame / output / background / persistent
+//               mask pointers, its MixDesc flags and its state slot;
+//   GeomSpans   by value in the kernel arguments: per class the first position and the first workgroup of its segment of the (ragged) grid, and the workgroups
+//               one position takes.  A workgroup finds its class with compares on SGPRs, then position = pos[g] + local / per[g] and item = local % per[g] — no load
+//               in front of the tile-class byte but the kernel arguments themselves, exactly as in the mixed step; class record and descriptor are two independent
+//               uniform loads next to it.  (A binary search through a device prefix array would put a chain of dependent loads there, a per-workgroup table would
+//               stage a word per tile per call.)
+constexpr int kMaxGeoms = 8;
+struct alignas(16) GeomClass {
+  int W, H;
+  int ntx, nty;                  // mask tiles per ROI row / column (kTW x kTH)
+  Rect4 roi, in_roi;
+  ResizeTab down, up;            // ROI -> model canvas (prep), model output -> ROI (mask); up.tile_class is unused (the call's scratch travels as an argument)
+};
+struct alignas(16) GeomDesc {
+  const uint8_t* frame;          // [H][W][3] BGR of the position's class
+  uint8_t* out;                  // [H][W][3], or [H][W][2] with the batch's YUYV bit
+  const uint8_t* bg;             // the position's background (unread with kMixFilterOff)
+  uint8_t* mask;                 // the stream's persistent mask [H][W]
+  unsigned flags;                // kMixFlipH | kMixFlipV | kMixFilterOff
+  int slot;                      // the stream id: ofinal slot
+  int pad[2];
+};
+static_assert(sizeof(GeomDesc) == 48, "three 16-byte uniform loads per workgroup");
+struct GeomSpans {
+  int pos[kMaxGeoms + 1];        // class g owns positions [pos[g], pos[g + 1]) of the call (empty for a class the call does not touch; entries past the last class = n)
+  int wg[kMaxGeoms + 1];         // ... and workgroups [wg[g], wg[g + 1]) of the grid
+  int per[kMaxGeoms];            // workgroups per position of class g
+};
+// frame ROI -> model canvas -> bilateral -> network input of position i at input / input_u8 + i (launch_prep_fused with the geometry of each position's class)
+hipError_t launch_prep_geoms(const GeomClass* classes, const GeomDesc* desc, const GeomSpans& spans, float* input, uint32_t* input_u8, int inW, int inH, BilateralParams bp,
+                             int n, hipStream_t s);
+// launch_mask_blend_mixed with the geometry, buffers and settings of each position: [one outside-ROI launch,] one tile-class launch (tile_class != nullptr), one tile
+// launch.  tiles / outside: the ragged grids (per = mask tiles / outside-ROI workgroups of one position, 0 = none); tile_class: one byte per workgroup of `tiles`;
+// `flags`: the batch's bits (bit 0 = YUYV out, bit 3 = no mask store).  Every class must satisfy geom_class_fusable.
+bool geom_class_fusable(int W, const Rect4& roi, const ResizeTab& up);
+int geom_outside_blocks(int W, int H, const Rect4& roi);      // outside-ROI workgroups of one position (0: the ROI is the frame)
+bool geom_class_xcd(int W, const Rect4& roi);                // the class's mask tiles of one frame on one XCD (launch_mask_blend's shared_lines rule): bit g of xcd_mask
+hipError_t launch_mask_blend_geoms(const GeomClass* classes, const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const GeomSpans& outside, const uint8_t* ofinal,
+                                   int outW, int outH, uint8_t* tile_class, int n, hipStream_t s, int flags);
 // alpha blend.  deepseg.cc:108-134
 hipError_t launch_blend(const uint8_t* bg, size_t bg_stride, const uint8_t* frames, const uint8_t* masks, uint8_t* out, size_t npix,
                         int n, hipStream_t s, const int* slot_of = nullptr);

@@ -144,147 +144,22 @@ __global__ __launch_bounds__(kThreads) void prep_fused_k(const uint8_t* __restri
   unsigned f_, t_;
   xcd_frame_tile((unsigned)(ntx * nty), (unsigned)n_frames, &f_, &t_);      // a frame's tiles on ONE XCD: their shared halo lines are L2 hits
   const long n = f_;
-  const int tby = (int)t_ / ntx, tbx = (int)t_ - tby * ntx;
-  const int tx0 = tbx * TW, ty0 = tby * TH;
-  const int SW = TW + 2 * kCanvasPad, total = SW * (TH + 2 * kCanvasPad);
-  constexpr int FB = YIN ? 2 : 3;                                         // bytes per frame pixel
-  const uint8_t* src = frames + n * (long)W * H * FB + ((long)roi.y * W + roi.x) * FB;
-  const unsigned msw = 0xFFFFFFFFu / (unsigned)SW + 1u;                    // i / SW for i < 2^16
-  constexpr int kItems = (kPfS * kPfS + kThreads - 1) / kThreads;
-  // the colour-weight table of the bilateral filter: requested with the kernel's first loads (round 5) — staged where it is first used, behind the resize phase, its
-  // three loads per lane were one more memory round trip in front of the second barrier
-  float lut_v[3];
-#pragma unroll
-  for (int k = 0; k < 3; k++) lut_v[k] = bp.color_lut[tid + k * kThreads];
-  if constexpr (LINEAR) {
-    // INTER_LINEAR: everything that depends only on the tile COLUMN (reflected canvas x → source byte offset, coefficient pair, where the two taps sit inside the
-    // 8 bytes loaded) or only on the tile ROW (source row offsets, coefficient pair) is worked out once per column / row by the first lanes and kept in LDS; an item
-    // is then two table reads, four loads and arithmetic.  Two dependent memory round trips per LANE (tables, then all of its <= kItems samples at once) instead of
-    // two per SAMPLE — in the per-sample form (sample_linear inside `if (inside)`) the compiler waits for each sample before it starts the next.
-    // 8 source bytes [offc, offc + 8) cover both taps: offc = min(3 sx, row_bytes - 8) never reads past the image row; the taps are bytes s0.. and s1.. of them
-    // (s1 = s0 + 3, or s0 where cv::resize clamps the second tap onto the first), pulled out by v_perm_b32 with per-column selectors.  Same integers as sample_linear.
-    __shared__ int4 colT[kPfS], rowT[kPfS];                                // {offc | -1, a0 | a1 << 16, sel0, sel1}, {o0 | -1, o1, b0, b1}
-    const int rowlim = (W - roi.x) * FB, SHt = TH + 2 * kCanvasPad;
-    if (tid < SW) {
-      const int dx = reflect101(tx0 + tid - kCanvasPad, inW) - q.x;
-      int4 e = make_int4(-1, 0, 0, 0);
-      if (dx >= 0 && dx < q.w) {
-        const int sx = tab.xofs[dx], same = sx + 1 > tab.sw - 1;
-        const int a0 = tab.xa[2 * dx], a1 = tab.xa[2 * dx + 1];
-        if constexpr (YIN) {
-          // the 8 bytes from the macropixel of tap 0 hold both taps' macropixels (tap 1 = pixel sx + 1 sits in the same or in the next one; the window is pulled
-          // back by 4 where it would pass the row end — tap 1 is then in tap 0's macropixel).  Selector of a tap: its Y, its macropixel's U and V.
-          const int p1 = same ? sx : sx + 1, mb = (sx >> 1) * 4, offc = max(min(mb, rowlim - 8), 0), m0 = mb - offc, m1 = (p1 >> 1) * 4 - offc;
-          const int y0 = m0 + 2 * (sx & 1), y1 = m1 + 2 * (p1 & 1);
-          e = make_int4(offc, (a0 & 0xffff) | (a1 << 16), 0x0c000000 | ((m0 + 3) << 16) | ((m0 + 1) << 8) | y0, 0x0c000000 | ((m1 + 3) << 16) | ((m1 + 1) << 8) | y1);
-        } else {
-          const int offb = sx * 3, offc = max(min(offb, rowlim - 8), 0), s0 = offb - offc, s1 = same ? s0 : s0 + 3;
-          e = make_int4(offc, (a0 & 0xffff) | (a1 << 16), 0x0c000000 | ((s0 + 2) << 16) | ((s0 + 1) << 8) | s0, 0x0c000000 | ((s1 + 2) << 16) | ((s1 + 1) << 8) | s1);
-        }
-      }
-      colT[tid] = e;
-    } else if (tid >= 64 && tid < 64 + SHt) {
-      const int ly = tid - 64, dy = reflect101(ty0 + ly - kCanvasPad, inH) - q.y;
-      int4 e = make_int4(-1, 0, 0, 0);
-      if (dy >= 0 && dy < q.h) {
-        const int sy = tab.yofs[dy], sy0 = min(max(sy, 0), tab.sh - 1), sy1 = min(max(sy + 1, 0), tab.sh - 1);
-        e = make_int4(sy0 * W * FB, sy1 * W * FB, tab.ya[2 * dy], tab.ya[2 * dy + 1]);
-      }
-      rowT[ly] = e;
-    }
-    __syncthreads();
-    uint32_t lo0[kItems], hi0[kItems], lo1[kItems], hi1[kItems];
-#pragma unroll
-    for (int k = 0; k < kItems; k++) {                                     // every load of the lane is requested here
-      const int i = min(tid + k * kThreads, total - 1), ly = (int)__umulhi((unsigned)i, msw), lx = i - ly * SW;
-      const int co = max(colT[lx].x, 0), o0 = max(rowT[ly].x, 0), o1 = rowT[ly].y;
-      struct __attribute__((packed, aligned(1))) U8 { uint64_t v; };            // ONE 8-byte load per source row (byte-aligned: global_load_dwordx2), not two 4-byte ones
-      const uint64_t q0 = reinterpret_cast<const U8*>(src + (unsigned)(o0 + co))->v, q1 = reinterpret_cast<const U8*>(src + (unsigned)(o1 + co))->v;
-      lo0[k] = (uint32_t)q0; hi0[k] = (uint32_t)(q0 >> 32);
-      lo1[k] = (uint32_t)q1; hi1[k] = (uint32_t)(q1 >> 32);
-    }
-#pragma unroll
-    for (int k = 0; k < kItems; k++) {
-      const int i = tid + k * kThreads;
-      if (i < total) {
-        const int ly = (int)__umulhi((unsigned)i, msw), lx = i - ly * SW;
-        const int4 c = colT[lx], r = rowT[ly];
-        const int a0 = (short)(c.y & 0xffff), a1 = c.y >> 16, b0 = r.z, b1 = r.w;
-        uint32_t t00 = __builtin_amdgcn_perm(hi0[k], lo0[k], (uint32_t)c.z), t01 = __builtin_amdgcn_perm(hi0[k], lo0[k], (uint32_t)c.w);   // row 0: tap 0 / tap 1 as B | G << 8 | R << 16
-        uint32_t t10 = __builtin_amdgcn_perm(hi1[k], lo1[k], (uint32_t)c.z), t11 = __builtin_amdgcn_perm(hi1[k], lo1[k], (uint32_t)c.w);   // row 1
-        if constexpr (YIN) { t00 = yuv_tap_to_bgr(t00); t01 = yuv_tap_to_bgr(t01); t10 = yuv_tap_to_bgr(t10); t11 = yuv_tap_to_bgr(t11); }      // (the taps arrived as Y | U << 8 | V << 16)
-        uint32_t v = 0;                                                    // the model canvas outside in_roi (the bars) is 0
-#pragma unroll
-        for (int ch = 0; ch < 3; ch++) {
-          const int h0 = (int)((t00 >> (8 * ch)) & 255u) * a0 + (int)((t01 >> (8 * ch)) & 255u) * a1;
-          const int h1 = (int)((t10 >> (8 * ch)) & 255u) * a0 + (int)((t11 >> (8 * ch)) & 255u) * a1;
-          const int o = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
-          v |= (uint32_t)o << (8 * (2 - ch));                              // BGR2RGB
-        }
-        tile[ly * kPfS + lx] = (c.x >= 0 && r.x >= 0) ? v : 0u;
-      }
-    }
-  } else
-#pragma unroll
-  for (int k = 0; k < kItems; k++) {
-    const int i = tid + k * kThreads;
-    if (i < total) {
-      const int ly = (int)__umulhi((unsigned)i, msw), lx = i - ly * SW;
-      const int dx = reflect101(tx0 + lx - kCanvasPad, inW) - q.x, dy = reflect101(ty0 + ly - kCanvasPad, inH) - q.y;
-      uint32_t v = 0;                                                      // the model canvas outside in_roi (the bars) is 0
-      if (dx >= 0 && dx < q.w && dy >= 0 && dy < q.h) {
-        int bgr[3];
-        sample_linear<3>(src, (long)W * 3, tab, dx, dy, bgr);
-        v = (uint32_t)bgr[2] | ((uint32_t)bgr[1] << 8) | ((uint32_t)bgr[0] << 16);  // BGR2RGB
-      }
-      tile[ly * kPfS + lx] = v;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 3; k++) lut[tid + k * kThreads] = lut_v[k];
-  __syncthreads();
-  const int lx = tid & 31, x = tx0 + lx;
-  if (lx >= TW || x >= inW) return;
-  // two pixels of the lane (rows ly and ly + 8) per pass, their sums in the two halves of packed registers: v_pk_mul_f32 / v_pk_add_f32 do both pixels' multiply
-  // (add) of a channel in one instruction — 9 instead of 13 VALU instructions per pixel and tap, the same IEEE operations in the same order (no contraction).
-  typedef float f2 __attribute__((ext_vector_type(2)));
-  static_assert(kBilPix % 2 == 0, "pixel pairs");
-#pragma unroll 1
-  for (int it = 0; it < kBilPix; it += 2) {
-    const int lyA = (tid >> 5) + 8 * it, lyB = lyA + 8;                   // row B may lie outside the tile: it reads rows < kPfS of the LDS tile and is not stored
-    if (lyA >= TH || ty0 + lyA >= inH) return;
-    const uint32_t* ta = tile + (lyA + kCanvasPad) * kPfS + (lx + kCanvasPad);      // the centre pixel; tap (dy, dx) at ta[dy * kPfS + dx]
-    const uint32_t* tb = ta + 8 * kPfS;
-    const uint32_t cA0 = ta[0], cB0 = tb[0];
-    f2 sr = {0.f, 0.f}, sg = {0.f, 0.f}, sb = {0.f, 0.f}, ws = {0.f, 0.f};
-#pragma unroll
-    for (int k = 0; k < 13; k++) {
-      const uint32_t cA = ta[kTapY[k] * kPfS + kTapX[k]], cB = tb[kTapY[k] * kPfS + kTapX[k]];
-      f2 w = {lut[__builtin_amdgcn_sad_u8(cA, cA0, 0u)], lut[__builtin_amdgcn_sad_u8(cB, cB0, 0u)]};
-      w = w * (f2)(bp.space_w[k]);
-      const f2 rr = {(float)(cA & 255), (float)(cB & 255)}, gg = {(float)((cA >> 8) & 255), (float)((cB >> 8) & 255)}, bb = {(float)((cA >> 16) & 255), (float)((cB >> 16) & 255)};
-      sr = sr + rr * w;
-      sg = sg + gg * w;
-      sb = sb + bb * w;
-      ws = ws + w;
-    }
-#pragma unroll
-    for (int h = 0; h < 2; h++) {
-      const int y = ty0 + lyA + 8 * h;
-      if (h == 1 && (lyB >= TH || y >= inH)) break;
-      const unsigned p = (unsigned)(y * inW + x);
-      const float wi = __fdiv_rn(1.f, ws[h]);
-      int qr = __float2int_rn(__fmul_rn(sr[h], wi)), qg = __float2int_rn(__fmul_rn(sg[h], wi)), qb = __float2int_rn(__fmul_rn(sb[h], wi));
-      qr = min(max(qr, 0), 255); qg = min(max(qg, 0), 255); qb = min(max(qb, 0), 255);
-      if (OUT & 1) {
-        float* o = input + (n * (long)inW * inH + p) * 3;
-        o[0] = __fadd_rn(__fmul_rn((float)qr, bp.scale), bp.offset);
-        o[1] = __fadd_rn(__fmul_rn((float)qg, bp.scale), bp.offset);
-        o[2] = __fadd_rn(__fmul_rn((float)qb, bp.scale), bp.offset);
-      }
-      if (OUT & 2) input_u8[n * (long)inW * inH + p] = (uint32_t)qr | ((uint32_t)qg << 8) | ((uint32_t)qb << 16);
-    }
-  }
+#define BSX_PREP_FRAME n
+#include "prep_tile.inc"
+#undef BSX_PREP_FRAME
+}
+// the same body for ONE frame given by its own pointer (bsx_step_batch_geoms: prep_geoms_k below): tile t_ of its canvas, network input slot n
+template <int OUT, bool LINEAR>
+__device__ __forceinline__ void prep_geoms_tile(const uint8_t* __restrict__ frames, int W, int H, Rect4 roi, float* __restrict__ input, uint32_t* __restrict__ input_u8,
+                                                int inW, int inH, Rect4 q, const ResizeTab& tab, const BilateralParams& bp, int TW, int TH, int ntx, const long n,
+                                                const unsigned t_) {
+  __shared__ float lut[768];
+  __shared__ uint32_t tile[kPfS * kPfS];
+  constexpr bool YIN = false;
+  const int tid = threadIdx.x;
+#define BSX_PREP_FRAME 0l
+#include "prep_tile.inc"
+#undef BSX_PREP_FRAME
 }
 
 // ---- decode + temporal IIR -------------------------------------------------------------------
@@ -1034,6 +909,39 @@ __global__ __launch_bounds__(kThreads) void outside_roi_mixed_k(const MixDesc* _
   }
 }
 
+// the same for ONE position given by its own pointers (bsx_step_batch_geoms: outside_roi_geoms_k below) — the statements of outside_roi_mixed_k for group i of
+// the frame: bgp / fl = the position's descriptor, frame / out = ITS images.  (A function of its own and not the kernel's body: called from outside_roi_mixed_k
+// it changed that kernel's code.)
+__device__ __forceinline__ void outside_mixed_group(unsigned i, const uint8_t* __restrict__ bgp, unsigned fl, const uint8_t* __restrict__ frame, uint8_t* __restrict__ out,
+                                                    int W, int H, Rect4 roi, int flags) {
+  const unsigned gpr = (unsigned)W / 4;
+  if (i >= gpr * (unsigned)H) return;
+  const int row = (int)(i / gpr), x = (int)(i - (unsigned)row * gpr) * 4;
+  if (row >= roi.y && row < roi.y + roi.h && x >= roi.x && x < roi.x + roi.w) return;
+  const long px = (long)row * W + x;
+  uint32_t w[3];
+  if (!(fl & kMixFilterOff)) {
+    const uint32_t* p = reinterpret_cast<const uint32_t*>(bgp + px * 3);
+    w[0] = p[0]; w[1] = p[1]; w[2] = p[2];
+  } else if (flags & 16) {
+    const uint32_t* p = reinterpret_cast<const uint32_t*>(frame + px * 2);
+    yuyv4_to_bgr3(p[0], p[1], w);
+  } else {
+    const uint32_t* p = reinterpret_cast<const uint32_t*>(frame + px * 3);
+    w[0] = p[0]; w[1] = p[1]; w[2] = p[2];
+  }
+  const bool fh = (fl & kMixFlipH) != 0, fv = (fl & kMixFlipV) != 0;
+  if (fh) reverse4px(w);
+  const int oy = fv ? H - 1 - row : row, ox = fh ? W - 4 - x : x;
+  if (flags & 1) {
+    uint32_t* o = reinterpret_cast<uint32_t*>(out + ((long)oy * W + ox) * 2);
+    o[0] = yuyv_pair(w[0] & 255u, (w[0] >> 8) & 255u, (w[0] >> 16) & 255u, w[0] >> 24, w[1] & 255u, (w[1] >> 8) & 255u);
+    o[1] = yuyv_pair((w[1] >> 16) & 255u, w[1] >> 24, w[2] & 255u, (w[2] >> 8) & 255u, (w[2] >> 16) & 255u, w[2] >> 24);
+  } else {
+    uint32_t* o = reinterpret_cast<uint32_t*>(out + ((long)oy * W + ox) * 3);
+    o[0] = w[0]; o[1] = w[1]; o[2] = w[2];
+  }
+}
 // ---- YUYV → BGR ingest (cv::COLOR_YUV2BGR_YUYV, BT.601 limited range, 20-bit fixed point) --------------------------------
 __global__ __launch_bounds__(kThreads) void yuyv_to_bgr_k(const uint32_t* __restrict__ in, uint8_t* __restrict__ out, long pairs) {
   long i = (long)blockIdx.x * kThreads + threadIdx.x;
@@ -1286,40 +1194,12 @@ hipError_t launch_mask_upscale_blur(const uint8_t* ofinal, int outW, int outH, R
 constexpr int kClsMaxItems = 8192, kClsMaxTx = 16;
 __global__ __launch_bounds__(kThreads) void tile_class_k(const uint8_t* __restrict__ ofinal, int outW, int outH, Rect4 q, ResizeTab tab, Rect4 roi, int ntx, int nty,
                                                         const int* __restrict__ slot_of) {
-  __shared__ uint8_t f255[kClsMaxItems], f0[kClsMaxItems];
-  __shared__ int cmn[kClsMaxTx], cmx[kClsMaxTx];
   const int n = blockIdx.x, tid = threadIdx.x;
-  if (tid < ntx) {
-    const int tx0 = tid * kTW, gx_lo = max(tx0 - 2, 0), gx_hi = min(tx0 + kTW + 1, roi.w - 1);
-    cmn[tid] = tab.xofs[gx_lo]; cmx[tid] = min(tab.xofs[gx_hi] + 1, tab.sw - 1);
-  }
-  __syncthreads();
-  const uint8_t* const fr = ofinal + (long)(slot_of ? slot_of[n] : n) * outW * outH + (long)q.y * outW + q.x;      // state slot; the classes stay per position n
-  struct __attribute__((packed, aligned(1))) U4 { uint32_t v; };
-  const int items = tab.sh * ntx;
-  for (int i = tid; i < items; i += kThreads) {
-    const int r = i / ntx, tbx = i - r * ntx, c0 = cmn[tbx], len = cmx[tbx] - c0 + 1;
-    const uint8_t* p = fr + (unsigned)(r * outW + c0);
-    uint32_t a = 0xFFFFFFFFu, o = 0u;
-    if (len >= 4) {
-#pragma unroll 4
-      for (int k = 0; k + 4 <= len; k += 4) { const uint32_t w = reinterpret_cast<const U4*>(p + k)->v; a &= w; o |= w; }
-      const uint32_t w = reinterpret_cast<const U4*>(p + len - 4)->v;      // the last four bytes (overlapping the loop's: AND / OR do not care)
-      a &= w; o |= w;
-    } else {
-      for (int k = 0; k < len; k++) { const uint32_t w = p[k] * 0x01010101u; a &= w; o |= w; }
-    }
-    f255[i] = a == 0xFFFFFFFFu; f0[i] = o == 0u;
-  }
-  __syncthreads();
-  for (int t = tid; t < ntx * nty; t += kThreads) {
-    const int tby = t / ntx, tbx = t - tby * ntx, ty0 = tby * kTH;
-    const int gy_lo = max(ty0 - 2, 0), gy_hi = min(ty0 + kTH + 1, roi.h - 1);
-    const int smin = min(max(tab.yofs[gy_lo], 0), tab.sh - 1), smax = min(max(tab.yofs[gy_hi] + 1, 0), tab.sh - 1);
-    int all255 = 1, all0 = 1;
-    for (int r = smin; r <= smax; r++) { all255 &= f255[r * ntx + tbx]; all0 &= f0[r * ntx + tbx]; }
-    tab.tile_class[(size_t)n * (size_t)(ntx * nty) + t] = (uint8_t)(all255 ? 1 : (all0 ? 2 : 0));
-  }
+#define BSX_CLS_FRAME ofinal + (long)(slot_of ? slot_of[n] : n) * outW * outH + (long)q.y * outW + q.x      /* state slot; the classes stay per position n */
+#define BSX_CLS_BYTE(t) tab.tile_class[(size_t)n * (size_t)(ntx * nty) + t]
+#include "tile_class.inc"
+#undef BSX_CLS_FRAME
+#undef BSX_CLS_BYTE
 }
 
 hipError_t launch_tile_class(const uint8_t* ofinal, int outW, int outH, const Rect4& in_roi, const ResizeTab& tab, const Rect4& roi, int n, hipStream_t s, const int* slot_of) {
@@ -1408,6 +1288,227 @@ hipError_t launch_mask_blend_mixed(const uint8_t* ofinal, int outW, int outH, Re
     else mask_tile_k<true, false, false, false, true><<<grid, kThreads, 0, s>>>(ofinal, outW, outH, in_roi, tab, mask, W, H, roi, d, 0, frames, out, flags, ntx, nty, nf, 0, nty, slot_of);
   } else if (yin) mask_upscale_blur_k<true, true, true><<<grid, kThreads, 0, s>>>(ofinal, outW, outH, in_roi, tab, mask, W, H, roi, d, 0, frames, out, flags, ntx, nty, nf, slot_of);
   else mask_upscale_blur_k<true, false, true><<<grid, kThreads, 0, s>>>(ofinal, outW, outH, in_roi, tab, mask, W, H, roi, d, 0, frames, out, flags, ntx, nty, nf, slot_of);
+  return hipGetLastError();
+}
+
+// ---- bsx_step_batch_geoms: positions of several capture sizes in one prep, one tile-class, one tile [and one outside-ROI] launch (kernels.hpp: GeomClass, GeomDesc,
+// GeomSpans).  The kernels below are the bodies of prep_fused_k, tile_class_k, mask_tile_k<BLEND, .., MIX> and outside_roi_mixed_k with the geometry read per position;
+// they have names of their own, so no existing instantiation changes its template arguments, its mangled name or its code.
+namespace {
+// workgroup (or position) `id` of a ragged grid: its class g, the class's first workgroup w0, first position p0, one-past-last position p1 and workgroups per position
+// — compares and selects on SGPRs (id is workgroup-uniform, the spans are kernel arguments): nothing is loaded
+__device__ __forceinline__ void geom_span(const GeomSpans& sp, int id, int* g, int* w0, int* p0, int* p1, int* per) {
+  *g = 0; *w0 = sp.wg[0]; *p0 = sp.pos[0]; *p1 = sp.pos[1]; *per = sp.per[0];
+#pragma unroll
+  for (int k = 1; k < kMaxGeoms; k++)
+    if (id >= sp.wg[k]) { *g = k; *w0 = sp.wg[k]; *p0 = sp.pos[k]; *p1 = sp.pos[k + 1]; *per = sp.per[k]; }
+}
+__device__ __forceinline__ int geom_class_of_position(const GeomSpans& sp, int n) {
+  int g = 0;
+#pragma unroll
+  for (int k = 1; k < kMaxGeoms; k++) if (n >= sp.pos[k]) g = k;
+  return g;
+}
+// xcd_frame_tile for a SEGMENT of the grid: `local` = the workgroup's index inside its class's segment.  Workgroups whose indices agree modulo 8 share an XCD
+// whatever the segment's first workgroup is, so a frame's tiles still meet in one L2.
+__device__ __forceinline__ void xcd_frame_tile_at(unsigned local, unsigned tiles, unsigned n_frames, unsigned* frame, unsigned* tile) {
+  const unsigned full = (n_frames & ~7u) * tiles;
+  if (local < full) {
+    const unsigned xcd = local & 7u, l8 = local >> 3, gq = l8 / tiles;
+    *frame = 8u * gq + xcd;
+    *tile = l8 - gq * tiles;
+  } else {
+    const unsigned r = local - full, f = r / tiles;
+    *frame = (n_frames & ~7u) + f;
+    *tile = r - f * tiles;
+  }
+}
+// a resize table read from a class record: its pointers as global-memory pointers (as_global: a pointer read from memory is otherwise a generic one)
+__device__ __forceinline__ ResizeTab geom_tab(const ResizeTab& t) {
+  ResizeTab r = t;
+  r.xofs = as_global(t.xofs); r.xa = as_global(t.xa); r.yofs = as_global(t.yofs); r.ya = as_global(t.ya); r.tile_class = nullptr;
+  return r;
+}
+// descriptor n: three 16-byte uniform loads, the pointers rebuilt as global-memory pointers (mix_desc)
+struct GeomDescRegs { const uint8_t* frame; uint8_t* out; const uint8_t* bg; uint8_t* mask; unsigned flags; int slot; };
+__device__ __forceinline__ GeomDescRegs geom_desc(const GeomDesc* __restrict__ desc, int n) {
+  const uint4* p = reinterpret_cast<const uint4*>(desc) + 3 * (size_t)n;
+  const uint4 a = p[0], b = p[1], c = p[2];
+  typedef __attribute__((address_space(1))) uint8_t* gp;
+  GeomDescRegs d;
+  d.frame = (const uint8_t*)(gp)(((uint64_t)a.y << 32) | a.x);
+  d.out = (uint8_t*)(gp)(((uint64_t)a.w << 32) | a.z);
+  d.bg = (const uint8_t*)(gp)(((uint64_t)b.y << 32) | b.x);
+  d.mask = (uint8_t*)(gp)(((uint64_t)b.w << 32) | b.z);
+  d.flags = c.x; d.slot = (int)c.y;
+  return d;
+}
+
+// prep_fused_k per position: the uniform grid of the model canvas (ntx * nty tiles per position), frame, capture size, ROIs and the down-scale table from the position's
+// class.  The table mode is the class's (a run-time, workgroup-uniform choice between the two bodies prep_fused_k picks at launch); the body is prep_tile.inc.
+template <int OUT>
+__global__ __launch_bounds__(kThreads) void prep_geoms_k(const GeomClass* __restrict__ classes, const GeomDesc* __restrict__ desc, GeomSpans sp, float* __restrict__ input,
+                                                        uint32_t* __restrict__ input_u8, int inW, int inH, BilateralParams bp, int TW, int TH, int ntx, int nty, int n_frames) {
+  unsigned f_, t_;
+  xcd_frame_tile((unsigned)(ntx * nty), (unsigned)n_frames, &f_, &t_);
+  const int g = geom_class_of_position(sp, (int)f_);
+  const GeomClass c = classes[g];                                     // (uniform index: scalar loads) — independent of the descriptor's
+  const uint8_t* const frame = geom_desc(desc, (int)f_).frame;
+  const ResizeTab tab = geom_tab(c.down);
+  if (tab.mode == 0 && (c.W - c.roi.x) * 3 >= 8)                      // launch_prep_fused's rule for the LINEAR body
+    prep_geoms_tile<OUT, true>(frame, c.W, c.H, c.roi, input, input_u8, inW, inH, c.in_roi, tab, bp, TW, TH, ntx, (long)f_, t_);
+  else
+    prep_geoms_tile<OUT, false>(frame, c.W, c.H, c.roi, input, input_u8, inW, inH, c.in_roi, tab, bp, TW, TH, ntx, (long)f_, t_);
+}
+
+// tile_class_k per position: one workgroup per position, the class bytes at the position's place in the ragged tile grid (plain order: first workgroup of the class
+// + position in the class x tiles per frame + tile) — where mask_tile_geoms_k finds its byte without loading anything first
+__global__ __launch_bounds__(kThreads) void tile_class_geoms_k(const GeomClass* __restrict__ classes, const GeomDesc* __restrict__ desc, GeomSpans sp,
+                                                              const uint8_t* __restrict__ ofinal, int outW, int outH, uint8_t* __restrict__ tile_class) {
+  const int n = blockIdx.x, g = geom_class_of_position(sp, n);
+  const GeomClass c = classes[g];
+  const int slot = geom_desc(desc, n).slot;
+  uint8_t* const cls = tile_class + sp.wg[g] + (size_t)(n - sp.pos[g]) * (size_t)(c.ntx * c.nty);
+  const ResizeTab tab = geom_tab(c.up);
+  if (c.ntx > kClsMaxTx || tab.sh * c.ntx > kClsMaxItems) {           // out of the classifier's range (launch_tile_class): all general
+    for (int t = threadIdx.x; t < c.ntx * c.nty; t += kThreads) cls[t] = 0;
+    return;
+  }
+  const int tid = threadIdx.x, ntx = c.ntx, nty = c.nty;
+  const Rect4 roi = c.roi;
+#define BSX_CLS_FRAME ofinal + (long)slot * outW * outH + (long)c.in_roi.y * outW + c.in_roi.x
+#define BSX_CLS_BYTE(t) cls[t]
+#include "tile_class.inc"
+#undef BSX_CLS_FRAME
+#undef BSX_CLS_BYTE
+}
+
+// mask_tile_k<BLEND = true, YIN = false, F0 = false, WH = false, MIX = true> per position: the same phases through the same helpers, with the position's own bases
+// (index 0 of each) and its class's geometry.  The order of the loads is mask_tile_k's: class byte first (its address needs only the kernel arguments), class record
+// and descriptor — two independent uniform loads — next to it, the state slot only where it is consumed.
+__global__ __launch_bounds__(kThreads) void mask_tile_geoms_k(const GeomClass* __restrict__ classes, const GeomDesc* __restrict__ desc, GeomSpans sp, unsigned xcd_mask,
+                                                             const uint8_t* __restrict__ ofinal, int outW, int outH, const uint8_t* __restrict__ tile_class, int yuyv) {
+  __shared__ short col_c0[kHW], col_c1[kHW], col_a0[kHW], col_a1[kHW];
+  __shared__ short row_r0[kHH], row_r1[kHH], row_b0[kHH], row_b1[kHH];
+  __shared__ __attribute__((aligned(16))) uint16_t hq_hs[kMaxSrcRows * kHW > kHH * kTW ? kMaxSrcRows * kHW : kHH * kTW];
+  __shared__ __attribute__((aligned(16))) uint8_t up[kHH * kHW + 8];
+  uint16_t* const hq = hq_hs;
+  uint16_t* const hs = hq_hs;
+  uint8_t* const blk = up;
+  const int tid = threadIdx.x;
+  int g, w0, p0, p1, per;
+  geom_span(sp, (int)blockIdx.x, &g, &w0, &p0, &p1, &per);
+  unsigned f_, t_;
+  xcd_frame_tile_at(blockIdx.x - (unsigned)w0, (unsigned)per, ((xcd_mask >> g) & 1u) ? (unsigned)(p1 - p0) : 0u, &f_, &t_);
+  const int n = p0 + (int)f_;                                          // the position (descriptor index)
+  int uniform = 0;
+  if (tile_class) {                                                    // the aligned word that holds the byte: a scalar load
+    const uintptr_t ca = (uintptr_t)tile_class + (size_t)w0 + (size_t)f_ * (size_t)per + (size_t)t_;
+    uniform = (int)((*reinterpret_cast<const uint32_t*>(ca & ~(uintptr_t)3) >> (8 * (unsigned)(ca & 3))) & 255u);
+  }
+  const GeomClass c = classes[g];
+  const GeomDescRegs d = geom_desc(desc, n);
+  const int W = c.W, H = c.H;
+  const Rect4 roi = c.roi, q = c.in_roi;
+  const ResizeTab tab = geom_tab(c.up);
+  const int tby = (int)t_ / c.ntx, tbx = (int)t_ - tby * c.ntx, tx0 = tbx * kTW, ty0 = tby * kTH;
+  yuyv = (yuyv & ~16) | (int)(d.flags & (kMixFlipH | kMixFlipV));
+  const int sel = (d.flags & kMixFilterOff) ? 2 : -1;
+  TileBlendOperands ops;
+  if (uniform) {
+    tile_load_blend_operands<true, false, true>(ops, d.bg, 0, d.frame, 0, W, H, roi, tx0, ty0, tid, uniform, 3, false, sel);
+    tile_vsum5_store<true, false, true>(hq_hs, d.mask, d.out, ops, 0, 0, W, H, roi, tx0, ty0, tid, yuyv, uniform, sel);
+    return;
+  }
+  const int gy_lo = max(ty0 - 2, 0), gy_hi = min(ty0 + kTH + 1, roi.h - 1);
+  const int gx_lo = max(tx0 - 2, 0), gx_hi = min(tx0 + kTW + 1, roi.w - 1);
+  const int smin = min(max(tab.yofs[gy_lo], 0), tab.sh - 1), smax = min(max(tab.yofs[gy_hi] + 1, 0), tab.sh - 1);
+  const int cmin = tab.xofs[gx_lo], cmax = min(tab.xofs[gx_hi] + 1, tab.sw - 1);
+  const int nsr = smax - smin + 1, ncol = cmax - cmin + 1;
+  const uint8_t* const base = ofinal + (long)d.slot * outW * outH + (long)(q.y + smin) * outW + q.x + cmin;
+  uint32_t raw[3];
+  const int br = tid >> 6, bc = tid & 63;
+#pragma unroll
+  for (int j = 0; j < 3; j++) { raw[j] = 0; if (br + 4 * j < nsr && bc < ncol) raw[j] = base[(unsigned)((br + 4 * j) * outW + bc)]; }
+  int t_s = 0, t_a0 = 0, t_a1 = 0;
+  if (tid < kHW) {
+    const int gx = reflect101(min(tx0 + tid - 2, roi.w + 1), roi.w);
+    t_s = tab.xofs[gx]; t_a0 = tab.xa[2 * gx]; t_a1 = tab.xa[2 * gx + 1];
+  } else if (tid >= 192 && tid < 192 + kHH) {
+    const int gy = reflect101(min(ty0 + (tid - 192) - 2, roi.h + 1), roi.h);
+    t_s = tab.yofs[gy]; t_a0 = tab.ya[2 * gy]; t_a1 = tab.ya[2 * gy + 1];
+  }
+  tile_load_blend_operands<true, false, true>(ops, d.bg, 0, d.frame, 0, W, H, roi, tx0, ty0, tid, 0, 3, false, sel);
+#pragma unroll
+  for (int j = 0; j < 3; j++) if (br + 4 * j < nsr && bc < ncol) blk[(br + 4 * j) * ncol + bc] = (uint8_t)raw[j];
+  if (nsr > 12 || ncol > 64)
+    for (int r = br; r < nsr; r += 4)
+      for (int cc = bc; cc < ncol; cc += 64)
+        if (r >= 12 || cc >= 64) blk[r * ncol + cc] = base[(unsigned)(r * outW + cc)];
+  if (tid < kHW) {
+    col_c0[tid] = (short)(t_s - cmin); col_c1[tid] = (short)(min(t_s + 1, tab.sw - 1) - cmin);
+    col_a0[tid] = (short)t_a0; col_a1[tid] = (short)t_a1;
+  } else if (tid >= 192 && tid < 192 + kHH) {
+    const int r = tid - 192;
+    row_r0[r] = (short)(min(max(t_s, 0), tab.sh - 1) - smin); row_r1[r] = (short)(min(max(t_s + 1, 0), tab.sh - 1) - smin);
+    row_b0[r] = (short)t_a0; row_b1[r] = (short)t_a1;
+  }
+  __syncthreads();
+  for (int r = tid / kHW, x = tid % kHW; r < nsr;) {
+    hq[r * kHW + x] = (uint16_t)((blk[r * ncol + col_c0[x]] * col_a0[x] + blk[r * ncol + col_c1[x]] * col_a1[x]) >> 4);
+    x += kThreads % kHW; r += kThreads / kHW;
+    if (x >= kHW) { x -= kHW; r++; }
+  }
+  __syncthreads();
+  tile_vertical_pass(hq, up, row_r0, row_r1, 0, row_b0, row_b1, tid);
+  __syncthreads();
+  tile_hsum5(up, hs, tid);
+  __syncthreads();
+  tile_vsum5_store<true, false, true>(hs, d.mask, d.out, ops, 0, 0, W, H, roi, tx0, ty0, tid, yuyv, 0, sel);
+}
+
+// outside_roi_mixed_k per position: sp.per[g] workgroups for every position of a class whose ROI is not the frame, none for the others
+__global__ __launch_bounds__(kThreads) void outside_roi_geoms_k(const GeomClass* __restrict__ classes, const GeomDesc* __restrict__ desc, GeomSpans sp, int flags) {
+  int g, w0, p0, p1, per;
+  geom_span(sp, (int)blockIdx.x, &g, &w0, &p0, &p1, &per);
+  const unsigned local = blockIdx.x - (unsigned)w0, pl = local / (unsigned)per, blk = local - pl * (unsigned)per;
+  const GeomClass c = classes[g];
+  const GeomDescRegs d = geom_desc(desc, p0 + (int)pl);
+  outside_mixed_group(blk * kThreads + threadIdx.x, d.bg, d.flags, d.frame, d.out, c.W, c.H, c.roi, flags & ~16);
+}
+}  // namespace
+
+bool geom_class_fusable(int W, const Rect4& roi, const ResizeTab& up) { return (W % 4) == 0 && (roi.x % 4) == 0 && (roi.w % 4) == 0 && mask_tile_usable(up); }
+int geom_outside_blocks(int W, int H, const Rect4& roi) {
+  return (roi.x != 0 || roi.y != 0 || roi.w != W || roi.h != H) ? (int)blocks_for((long)(W / 4) * H) : 0;
+}
+bool geom_class_xcd(int W, const Rect4& roi) {                           // launch_mask_blend's rule: one-XCD-per-frame order only where neighbouring tiles share cache lines
+  static const bool xcd_on = !(BSX_DBG_ENV("BSX_XCD_TILES") && atoi(BSX_DBG_ENV("BSX_XCD_TILES")) == 0);
+  return xcd_on && (((roi.x * 3) & 127) != 0 || ((W * 3) & 127) != 0);
+}
+
+hipError_t launch_prep_geoms(const GeomClass* classes, const GeomDesc* desc, const GeomSpans& spans, float* input, uint32_t* input_u8, int inW, int inH, BilateralParams bp,
+                             int n, hipStream_t s) {
+  if ((!input && !input_u8) || n <= 0) return hipErrorInvalidValue;
+  const int ntx = (inW + 31) / 32, nty = (inH + 31) / 32, TW = (inW + ntx - 1) / ntx, TH = (inH + nty - 1) / nty;      // launch_prep_fused's tiles
+  if ((unsigned long long)ntx * nty * (unsigned long long)n >= (1ull << 31)) return hipErrorInvalidValue;
+  static const bool xcd_on = !(BSX_DBG_ENV("BSX_XCD_TILES") && atoi(BSX_DBG_ENV("BSX_XCD_TILES")) == 0);
+  const dim3 grid((unsigned)(ntx * nty) * (unsigned)n);
+#define BSX_PG(O) prep_geoms_k<O><<<grid, kThreads, 0, s>>>(classes, desc, spans, input, input_u8, inW, inH, bp, TW, TH, ntx, nty, xcd_on ? n : 0)
+  if (input && input_u8) BSX_PG(3); else if (input_u8) BSX_PG(2); else BSX_PG(1);
+#undef BSX_PG
+  return hipGetLastError();
+}
+
+hipError_t launch_mask_blend_geoms(const GeomClass* classes, const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const GeomSpans& outside, const uint8_t* ofinal,
+                                   int outW, int outH, uint8_t* tile_class, int n, hipStream_t s, int flags) {
+  flags &= 1 | 8;
+  if (n <= 0 || tiles.wg[kMaxGeoms] <= 0) return hipErrorInvalidValue;
+  if (outside.wg[kMaxGeoms] > 0) outside_roi_geoms_k<<<dim3((unsigned)outside.wg[kMaxGeoms]), kThreads, 0, s>>>(classes, desc, outside, flags);
+  if (tile_class) tile_class_geoms_k<<<dim3((unsigned)n), kThreads, 0, s>>>(classes, desc, tiles, ofinal, outW, outH, tile_class);
+  static const bool plain_stores = BSX_DBG_ENV("BSX_TILE_PLAIN_STORES") != nullptr;
+  if (plain_stores) flags |= 128;
+  mask_tile_geoms_k<<<dim3((unsigned)tiles.wg[kMaxGeoms]), kThreads, 0, s>>>(classes, desc, tiles, xcd_mask, ofinal, outW, outH, tile_class, flags);
   return hipGetLastError();
 }
 

@@ -239,6 +239,7 @@ int bsx_background_grab_batch(bsx_background* const* bgs, int n, int width, int 
 bsx_live* bsx_live_new(bsx_ctx* ctx) {
   bsx_info info;
   if (!ctx || bsx_get_info(ctx, &info) != BSX_OK) return nullptr;
+  if (bsx_geom_count(ctx) > 1) { refuse_call(ctx, "bsx_live_new", "context has %d geometries (the live mode works at one capture size)", bsx_geom_count(ctx)); return nullptr; }
   bsx_live* l = new bsx_live;
   l->ctx = ctx; l->width = info.width; l->height = info.height; l->device = info.device;
   const size_t fb = (size_t)info.width * info.height * 3, mb = (size_t)info.width * info.height;

@@ -23,6 +23,8 @@
  *   bsx_step_batch_streams … for the streams that HAVE a new frame, addressed by id  app/deepseg.cc:182-216 (one filter step per new frame)
  *   bsx_step_batch_mixed   … with each stream's own settings: -b / -p bgblur / -H / -V and the s / h / v keys  app/deepseg.cc:387-437, 596-673, 777-790
  *   bsx_step_batch_vcam_mixed  … both: each stream's own settings, written at the virtual camera's geometry  app/deepseg.cc:387-437, 634-681
+ *   bsx_new_geoms          bs_maskgen_new() for cameras of several capture sizes in ONE context  lib/libbackscrub.cc:161-259 (the ROIs of :234-246 once per size)
+ *   bsx_step_batch_geoms   … for streams of different capture sizes together: one prep launch, one network pass, one tile launch  app/deepseg.cc:634-673
  *   bsx_reset_streams      bsx_reset for a chosen subset of the streams (a slot reused for a new camera)
  *                          (set_input_frame → mask → alpha_blend), batched
  *   bsx_resize_bgr         grab_background() cv::resize   app/background.cc:178-194
@@ -130,7 +132,7 @@ BSX_API int bsx_process_host(bsx_ctx* ctx, int stream_idx, const uint8_t* h_bgr,
  * Asynchronous on `stream` unless callbacks are set (each callback needs a stream sync). */
 BSX_API int bsx_process_batch(bsx_ctx* ctx, const uint8_t* d_frames, int n, uint8_t* d_masks, void* stream);
 
-/* Device pointer of the persistent masks [n_streams][height][width] (valid until bsx_delete;
+/* Device pointer of the persistent masks [n_streams][height][width] (a context of several classes: class after class, bsx_get_geom_info; valid until bsx_delete;
  * contents valid after the process call that produced them has completed on its stream) —
  * the analogue of `mask = ctx.mask` aliasing the lib-owned buffer (lib/libbackscrub.cc:374). */
 BSX_API uint8_t* bsx_masks_device(bsx_ctx* ctx);
@@ -226,6 +228,58 @@ typedef struct bsx_stream_setting {
  *     and every context or buffer the fused tile route does not take (width, roi.x, roi.w multiples of 4, 4-byte aligned buffers, no onmask callback). */
 BSX_API int bsx_step_batch_mixed(bsx_ctx* ctx, const int* ids, const uint8_t* d_frames, const bsx_stream_setting* settings,
                                  uint8_t* d_out, int n, void* stream, unsigned flags);
+
+/* ---- cameras of different capture sizes in one context ----
+ * Nothing in the network depends on the capture size: only the two ends of the pipeline see the frame (the ROI down-scale into the model canvas, and the mask
+ * up-scale + blur + blend).  A context made by bsx_new_geoms holds up to BSX_MAX_GEOMS geometry classes (capture sizes); weights, arena, network buffers, compiled
+ * kernels and the model-resolution temporal state exist once, every class has its own ROIs, resize tables and its own slice of the persistent masks.
+ *   - streams are numbered class after class: class g owns ids [first_g, first_g + geoms[g].n_streams), first_0 = 0;
+ *   - n_geoms == 1 IS bsx_new(model_path, threads, width, height, n_streams, ...): the same context, every entry point as before;
+ *   - returns NULL, with a message (through ondebug or stderr, and bsx_last_error(NULL)) that names the class index and its size, for: n_geoms outside
+ *     [1, BSX_MAX_GEOMS]; a non-positive size or stream count; two classes of the same size; more than 65535 streams in total; an onmask callback with more than one
+ *     class; and, with more than one class, a class the fused tile route does not take (width, roi.x and roi.w multiples of 4 and a tiled linear mask up-scale: the rule
+ *     bsx_step_batch_mixed applies per call, applied at creation).  With segm_lite (160 x 96, its ratio held as a float) the reference's ROI arithmetic gives some
+ *     16:9 sizes a ROI width that is no multiple of 4 — 1920x1080 -> 1799, 960x540 -> 899, 848x480 -> 799 — and those are refused; 1280x720 and 640x360 are fine;
+ *   - on a context of more than one class these work: bsx_step_batch_geoms, bsx_reset, bsx_reset_streams, bsx_get_info (class 0's geometry, the total n_streams),
+ *     bsx_geom_count / bsx_get_geom_info, bsx_masks_device, bsx_last_error, bsx_delete, bsx_plan_describe, bsx_debug_buffer (0-2 as always; 3 = the whole mask
+ *     allocation), bsx_debug_tensor*, and everything that takes its own w, h (bsx_resize_bgr*, bsx_bgr_to_yuyv, bsx_yuyv_to_bgr, bsx_flip_bgr, bsx_gaussian_blur_bgr,
+ *     bsx_background_*).  Every other entry point — the dense, by-id, mixed, vcam and pipelined steps, process, composite, profile, live, the debug stages and tile
+ *     statistics — returns BSX_EINVAL ("context has N geometries"; bsx_live_new: NULL) and enqueues nothing. */
+#define BSX_MAX_GEOMS 8
+typedef struct bsx_geometry { int width, height, n_streams; } bsx_geometry;
+BSX_API bsx_ctx* bsx_new_geoms(const char* model_path, size_t threads, const bsx_geometry* geoms, int n_geoms, int device,
+                               bsx_debug_fn ondebug, bsx_stage_fn onprep, bsx_stage_fn oninfer, bsx_stage_fn onmask, void* caller_ctx);
+
+/* The classes of a context (1 for one made by bsx_new) and the geometry of class g.  The persistent mask of stream s of class g is
+ * bsx_masks_device() + mask_offset + (s - first_stream) * width * height. */
+typedef struct bsx_geom_info {
+  int width, height, n_streams, first_stream;
+  int roi[4], in_roi[4];          /* as bsx_info, for this class */
+  size_t mask_offset;             /* bytes from bsx_masks_device() to the class's [n_streams][height][width] masks */
+} bsx_geom_info;
+BSX_API int bsx_geom_count(const bsx_ctx* ctx);
+BSX_API int bsx_get_geom_info(const bsx_ctx* ctx, int g, bsx_geom_info* out);
+
+/* One main-loop iteration for the streams named in ids[0..n), of ANY mix of the context's classes, each with its own buffers and settings — in one prep launch, one
+ * pass of the network, one tile-class and one tile launch (and at most one launch for the strips outside the ROIs), whatever the number of classes.
+ *   - ids: required (the id decides the class): n distinct ids in any order, classes may interleave; rules, staging ring and refusal texts of bsx_step_batch_streams;
+ *   - items[0..n): host memory, read before the call returns; entry i belongs to stream ids[i].  d_frame / d_out / setting.d_bg have the capture size of THAT stream's
+ *     class; setting.flags: BSX_STEP_FLIP_H | BSX_STEP_FLIP_V | BSX_STREAM_FILTER_OFF;
+ *   - flags (batch-wide, the buffer layouts): BSX_STEP_YUYV | BSX_STEP_NO_MASK;
+ *   - result, per stream: composite, persistent mask and ofinal are bit-identical to bsx_step_batch_mixed of that one stream in a one-geometry context of its size
+ *     with the same setting and flags.  Other streams' state is untouched;
+ *   - works on every context, also one made by bsx_new (then it is the mixed step with per-position pointers instead of packed arrays);
+ *   - n == 0: returns 0 and enqueues nothing;
+ *   - BSX_EINVAL before anything is enqueued, with a bsx_last_error text naming the position and value, for: the ids errors of bsx_step_batch_streams; items NULL; a
+ *     NULL or not 4-byte aligned d_frame, d_out, or d_bg that is read; a flag bit outside the sets above (BSX_STEP_BGBLUR in a setting and BSX_STEP_YUYV_IN are not
+ *     taken); an odd class width with YUYV out; an output overlapping any frame, background or other output of the call; a pending pipelined composite; an onmask
+ *     callback; a stream whose class is off the fused tile route (possible only in a one-class context).  A refused call changes no state. */
+typedef struct bsx_geom_item {
+  const uint8_t* d_frame;       /* [height_g][width_g][3] BGR of the stream's class, 4-byte aligned */
+  uint8_t* d_out;               /* [height_g][width_g][3], or [..][2] with BSX_STEP_YUYV, 4-byte aligned */
+  bsx_stream_setting setting;   /* d_bg at the capture size of that class; BSX_STEP_FLIP_H | BSX_STEP_FLIP_V | BSX_STREAM_FILTER_OFF */
+} bsx_geom_item;
+BSX_API int bsx_step_batch_geoms(bsx_ctx* ctx, const int* ids, const bsx_geom_item* items, int n, void* stream, unsigned flags);
 
 /* Reset the temporal state of the listed streams only (ofinal → 0, persistent mask → 255, as bsx_reset does for all) — a slot reused for a new camera.  The
  * other streams' state is untouched, and a pending pipelined composite is NOT dropped: the call is refused (BSX_EINVAL) while one is pending.  Same ids rules,
