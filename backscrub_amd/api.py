@@ -657,7 +657,7 @@ class MaskGen:
         if stream is not None:
             n = lib().bsx_debug_tensor_of(self.h, idx, stream, None, 0)
             if n < 0:
-                raise BsxError("tensor %d not materialised" % idx)
+                raise BsxError("tensor %d not materialised: %s" % (idx, (lib().bsx_last_error(self.h) or b"").decode(errors="replace").strip()))
             a = np.empty(n, np.float32)
             lib().bsx_debug_tensor_of(self.h, idx, stream, a.ctypes.data_as(C.POINTER(C.c_float)), n)
             return a

@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libbsx.so")
 # the same sources with -DBSX_DEBUG_SWITCHES (csrc/debug_switches.hpp): the A/B knobs, alternate code paths and work-skipping experiments the default build leaves
-# out.  Test infrastructure — tests/test_gpu_switch_variants.py and the tools/ experiments load it through BSX_LIBRARY; nothing ships or measures with it.
+# out.  Test infrastructure — the `debug_switches` tests (tests/test_gpu_parity.py, tests/test_gpu_layers.py) and the tools/ experiments load it through BSX_LIBRARY; nothing ships or measures with it.
 OBJ_DBG = os.path.join(CSRC, "build_dbg")
 LIB_DBG = os.path.join(HERE, "libbsx_dbg.so")
 SOURCES = ["tflite_model.cpp", "plan.cpp", "gen_mid.cpp", "gen_seg.cpp", "rtc.cpp", "specialised.cpp", "media.cpp", "jpeg.cpp", "live.cpp", "kernels_nn.hip", "kernels_img.hip", "kernels_frame.hip", "kernels_seg.hip", "bsx_api.hip"]

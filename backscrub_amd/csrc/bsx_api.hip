@@ -139,6 +139,10 @@ struct bsx_ctx {
   std::map<std::pair<std::pair<int, int>, std::pair<int, int>>, DevResizeTab> bg_tabs;
   std::map<std::pair<int, int>, VcamTab> vcam_tabs;   // (out_w, out_h) -> the capture -> vcam table of bsx_step_batch_vcam
   std::string last_error, plan_text;
+  bool arena_poison = false;           // BSX_ARENA_POISON (debug build): the activation arena is filled with 0xFF bytes — NaNs — in front of every network stage, so a tensor
+                                       // the read-back entry serves although nothing wrote it comes back non-finite (tests/test_gpu_layers.py)
+  bool last_net_logits = true;         // did the last network stage write the logits buffer (false: its last kernel decoded straight into the temporal state)
+  int last_net_n = 0;                  // frames of the last network stage: the launchers choose some fusions by batch size (chain3_on), the read-back entry answers for that run
   bool keep_logits = false;            // BSX_KEEP_LOGITS: segmented plans write the logits and run the stand-alone decode (A/B, debugging)
   bool no_mask_blend_fusion = false;   // BSX_NO_MASK_BLEND_FUSION, read once at bsx_new (no getenv on the per-step path)
   bool no_bgblur_fusion = false;       // BSX_NO_BGBLUR_FUSION: BSX_STEP_BGBLUR always as blur pass + step (the A/B switch of the single-pass form)
@@ -459,10 +463,18 @@ int state_write_fence(bsx_ctx* c, hipStream_t s) {
   BSX_HIP(c, hipStreamWaitEvent(s, ev, 0));
   return BSX_OK;
 }
+// does the specialised middle kernel compute micro-op i's arena output chunk by chunk inside the depthwise after it (gen_mid.cpp: the tensor is never stored)?
+bool program_op_elided(const bsx_ctx* c, int i) { return c->kern.mid && !BSX_DBG_ENV("BSX_RTC_FINE") && mid_pw_feeds_dw(c->plan, i); }
 bool infer_decodes(const bsx_ctx* c) { return (c->use_program && c->plan.seg.on && !c->keep_logits) || argmax_tail(c); }
 // ids (device, nullable): the id form of a step — frame i's temporal state is slot ids[i] (then slot == 0); nullptr = slots [slot, slot + n)
 int run_infer(bsx_ctx* c, int n, hipStream_t s, bool logits = true, int slot = 0, const int* ids = nullptr, LaunchTimer* t = nullptr) {
   bsx_roctx::Range range("bsx:network");
+  c->last_net_n = n;
+  c->last_net_logits = logits;
+  if (c->arena_poison) {       // (the logits buffer too: a stage that decodes inside its last kernel never writes it, and the entry must not serve the previous stage's)
+    BSX_HIP(c, hipMemsetAsync(c->d_arena, 0xFF, c->plan.arena_floats_per_stream * (size_t)c->n_streams * sizeof(float), s));
+    BSX_HIP(c, hipMemsetAsync(c->d_net_out, 0xFF, (size_t)c->n_streams * c->outW * c->outH * c->outC * sizeof(float), s));
+  }
   if (c->use_program && c->plan.seg.on) {
     // the four segment kernels: the graph-specialised ones where the context loaded them (c->kern.seg), else the ahead-of-time instances
     const SegPlan& sp = c->plan.seg;
@@ -1241,6 +1253,7 @@ static bsx_ctx* new_ctx(const char* model_path, size_t threads, const bsx_geomet
   c->no_uniform_tiles = getenv("BSX_NO_UNIFORM_TILES") != nullptr;
   c->tail_generic = BSX_DBG_ENV("BSX_TAIL_GENERIC") != nullptr;
   c->keep_logits = BSX_DBG_ENV("BSX_KEEP_LOGITS") != nullptr;
+  c->arena_poison = BSX_DBG_ENV("BSX_ARENA_POISON") != nullptr;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) {
     report(nullptr, ondebug, caller_ctx, "error: HIP device %d not available (%d visible)\n", device, ndev); return nullptr; }
@@ -1253,11 +1266,20 @@ static bsx_ctx* new_ctx(const char* model_path, size_t threads, const bsx_geomet
              c->use_program ? "ON" : "off", c->plan.program.size(), c->plan.program_lds_floats, c->plan.program_lds_floats / 256.0,
              c->plan.program_lds_tensors, c->plan.program_global_tensors);
     c->plan_text += line;
+    if (no_reuse) c->plan_text += "arena: every tensor in a slot of its own (debug switch)\n";
+    if (c->arena_poison) c->plan_text += "arena: filled with NaN bytes in front of every network stage (debug switch)\n";
     if (c->use_program) c->plan_text += "program execution: " + c->kern.mid_note + "\n";
     if (c->use_program && c->plan.seg.on) c->plan_text += c->plan.seg_text;
     if (c->use_program && c->plan.seg.on) c->plan_text += "segment execution: " + c->kern.seg_note + "\n";
     if (c->use_program && c->kern.mid) c->plan_text += mid_barrier_line(c->plan, c->act16);
-    for (size_t i = 0; i < c->plan.program_labels.size(); i++) { c->plan_text += "P" + std::to_string(i) + " " + c->plan.program_labels[i] + "\n"; }
+    for (size_t i = 0; i < c->plan.program_labels.size(); i++) {
+      c->plan_text += "P" + std::to_string(i) + " " + c->plan.program_labels[i];
+      if (i < c->plan.program_out_tensor.size()) {            // the tensor the op leaves behind, and where: the read-back entry serves the "hbm" ones only
+        const int sp = c->plan.program[i].out.space;
+        c->plan_text += " -> t" + std::to_string(c->plan.program_out_tensor[i]) + (sp == kLocLds ? " lds" : (program_op_elided(c.get(), (int)i) ? " elided" : (sp == kLocOutput ? " output" : " hbm")));
+      }
+      c->plan_text += "\n";
+    }
   }
   return c.release();
   } catch (const std::exception& e) {
@@ -1797,7 +1819,8 @@ int bsx_model_describe(const char* model_path, char* buf, size_t cap) {
     snprintf(head, sizeof head, "program micro-ops=%zu lds_floats=%d lds_tensors=%d hbm_tensors=%d arena_bytes_per_frame=%ld placement_policy=%u lds_blocks=%zu lds_check=%s\n", p.program.size(),
              p.program_lds_floats, p.program_lds_tensors, p.program_global_tensors, p.program_arena_bytes, p.program_policy, p.program_blocks.size(), p.program_check.c_str());
     out += head;
-    for (size_t i = 0; i < p.program_labels.size(); i++) out += "P" + std::to_string(i) + " " + p.program_labels[i] + "\n";
+    for (size_t i = 0; i < p.program_labels.size(); i++)
+      out += "P" + std::to_string(i) + " " + p.program_labels[i] + (i < p.program_out_tensor.size() ? " -> t" + std::to_string(p.program_out_tensor[i]) : std::string()) + "\n";
     if (p.seg.on) out += p.seg_text;
     if (!p.program.empty()) out += mid_barrier_line(p, false);
     if (BSX_DBG_ENV("BSX_PLAN_BLOCKS"))           // debugging: the LDS reservations of the program (float offset, length, first / last step, owner)
@@ -1873,10 +1896,45 @@ const char* bsx_plan_describe(bsx_ctx* c) { return c ? c->plan_text.c_str() : ""
 // error, so the inspection entry points refuse arena tensors in that mode (network input / output keep their f32 buffers).
 static bool debug_tensor_readable(const bsx_ctx* c, int t) { return !c->act16 || t == c->plan.input || t == c->plan.output; }
 
+// An arena offset alone does not mean that the tensor exists: the planner gives every step output one before it decides what stays in LDS, what a fused launch keeps
+// in registers and what the generated kernel elides.  Returns why the path that executes this context never writes tensor t to the arena (nullptr: it does) — from
+// the plan and from the choices the launchers made for the last network stage (the same predicates: program_op_elided, chain3_on, the ir_on rule of launch_step).
+static const char* debug_tensor_unstored(const bsx_ctx* c, int t) {
+  const Plan& p = c->plan;
+  if (t == p.input) return nullptr;
+  if (t == p.output) return c->last_net_logits ? nullptr : "the last network stage decoded inside its final kernel and wrote no logits";
+  if (c->use_program) {
+    if (p.seg.on && std::find(p.seg_stored.begin(), p.seg_stored.end(), t) != p.seg_stored.end()) return nullptr;
+    for (size_t i = 0; i < p.program.size() && i < p.program_out_tensor.size(); i++) {
+      if (p.program_out_tensor[i] != t) continue;
+      if (p.program[i].out.space == kLocLds) return "the frame program keeps it in LDS";
+      if (p.program[i].out.space != kLocGlobal) return "the frame program writes it to a buffer of its own";
+      if (program_op_elided(c, (int)i)) return "the specialised middle kernel computes it chunk by chunk inside the depthwise that reads it";
+      return nullptr;
+    }
+    return p.seg.on ? "it lives inside a segment kernel or a fused micro-op (LDS / registers only)" : "it lives inside a fused micro-op (LDS / registers only)";
+  }
+  const int NS = (int)p.steps.size();
+  const int n = c->last_net_n > 0 ? c->last_net_n : c->n_streams;
+  const bool ir_on = c->d_weights16 && c->f16_terms > 0;                      // launch_step: when the expand + depthwise pairs run as one kernel
+  for (int j = 0; j < NS; j++) {
+    const Step& st = p.steps[j];
+    if (st.out != t) continue;
+    if (p.steps[0].fuse_head0 && j < 2) return "the fused head kernel (stem + depthwise + 1x1) keeps it in LDS";
+    if (st.fuse_dw >= 0 && ir_on) return "the fused expand + depthwise kernel keeps it in LDS";
+    if (st.chain_first >= 0 && chain3_on(p, j, n, c->d_weights16, c->f16_terms)) return "the chained 1x1 kernel keeps it in registers";
+    if (st.chain_mid >= 0 && j < st.chain_mid && chain3_on(p, st.chain_mid, n, c->d_weights16, c->f16_terms)) return "the chained 1x1 kernel keeps it in registers";
+    return nullptr;
+  }
+  return "no step of this plan writes it";
+}
+
 static long debug_tensor_at(bsx_ctx* c, int t, int stream_idx, float* h_out, long cap) {
-  if (!c || t < 0 || t >= (int)c->graph.tensors.size() || c->plan.tensor_off[t] < 0 || stream_idx < 0 || stream_idx >= c->n_streams) return BSX_EINVAL;
-  if (h_out && cap < 0) return BSX_EINVAL;
+  if (!c) return BSX_EINVAL;
+  if (t < 0 || t >= (int)c->graph.tensors.size() || stream_idx < 0 || stream_idx >= c->n_streams || (h_out && cap < 0)) { c->last_error = "bsx_debug_tensor: tensor or stream index out of range"; return BSX_EINVAL; }
+  if (c->plan.tensor_off[t] < 0) { c->last_error = "bsx_debug_tensor: tensor " + std::to_string(t) + " has no place in the arena (a constant, or fused away by the planner)"; return BSX_EINVAL; }
   if (!debug_tensor_readable(c, t)) { c->last_error = "bsx_debug_tensor: arena tensors are stored as f16 under BSX_ACT16 and are not readable through this entry"; return BSX_EINVAL; }
+  if (const char* why = debug_tensor_unstored(c, t)) { c->last_error = "bsx_debug_tensor: tensor " + std::to_string(t) + " is never written to the arena on this path: " + why; return BSX_EINVAL; }
   DeviceGuard guard(c->device);
   const long n = (long)c->graph.tensors[t].elems();
   if (!h_out) return n;

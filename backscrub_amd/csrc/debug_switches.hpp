@@ -6,7 +6,7 @@
 //
 // DEBUG SWITCHES — A/B timing knobs, alternate code paths kept for cross-checking, and experiments that make kernels SKIP WORK (results are then wrong on
 // purpose) — go through BSX_DBG_ENV().  The default build compiles it to a null pointer: the switch names are not even in the binary, and setting them does nothing
-// (tests/test_cabi.py: `strings libbsx.so`; tests/test_gpu_switch_variants.py runs the alternate paths against libbsx_dbg.so, built with -DBSX_DEBUG_SWITCHES).
+// (tests/test_cabi.py: `strings libbsx.so`; tests/test_gpu_parity.py and tests/test_gpu_layers.py run the alternate paths against libbsx_dbg.so, built with -DBSX_DEBUG_SWITCHES).
 #pragma once
 #include <cstdlib>
 

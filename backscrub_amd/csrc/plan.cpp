@@ -113,6 +113,7 @@ static void lower_frame_program(const Graph& g, Plan* plan, const std::vector<St
   plan->program.clear();
   plan->program_scratch_floats = scratch;
   plan->program_labels.clear();
+  plan->program_out_tensor.clear();
   plan->program_blocks.clear();
   plan->program_check.clear();
   plan->program_ext_offs.clear();
@@ -280,6 +281,7 @@ static void lower_frame_program(const Graph& g, Plan* plan, const std::vector<St
   }
   std::vector<MicroOp> prog;
   std::vector<std::string> labels;
+  std::vector<int> out_t;                  // per micro-op: the tensor its `out` holds
   std::vector<int> tail_ws(NS, -1), tail_rows(NS, 0);
   auto tail_pattern = [&](int s) {
     if (s + 2 >= NS || BSX_DBG_ENV("BSX_PROGRAM_NO_TAIL")) return false;
@@ -416,6 +418,7 @@ static void lower_frame_program(const Graph& g, Plan* plan, const std::vector<St
     if (BSX_DBG_ENV("BSX_PROGRAM_NOP")) m.kind = 99;
     if (const char* only = BSX_DBG_ENV("BSX_PROGRAM_ONLY")) { if (atoi(only) != s) m.kind = 99; }   // timing experiments: one live op
     prog.push_back(m);
+    out_t.push_back(st.out);
     {
       char buf[200];
       snprintf(buf, sizeof buf, "%-12s %dx%dx%d->%dx%dx%d%s%s in:%s out:%s", st.label.c_str(), st.H, st.W, st.Cin, st.OH, st.OW, st.Cout,
@@ -427,6 +430,7 @@ static void lower_frame_program(const Graph& g, Plan* plan, const std::vector<St
   if (!BSX_DBG_ENV("BSX_PROGRAM_NO_SE")) {
     std::vector<MicroOp> fusedp;
     std::vector<std::string> flabels;
+    std::vector<int> fout;
     for (size_t i = 0; i < prog.size(); i++) {
       const MicroOp& g0 = prog[i];
       auto is_fc = [&](size_t k, const Loc& in) {
@@ -450,6 +454,7 @@ static void lower_frame_program(const Graph& g, Plan* plan, const std::vector<St
         m.magic_w = (unsigned)((0x100000000ull + (unsigned long long)m.W - 1) / (unsigned long long)m.W);
         fusedp.push_back(m);
         flabels.push_back("tail[pw+dw+tconv] " + labels[i]);
+        fout.push_back(out_t[i + 2]);
         i += 2;
         continue;
       }
@@ -468,17 +473,21 @@ static void lower_frame_program(const Graph& g, Plan* plan, const std::vector<St
         }
         fusedp.push_back(m);
         flabels.push_back("se[" + std::to_string(m.n_fc) + "fc" + (m.fc_stage[0] ? "+w1" : "") + (m.fc_stage[1] ? "+w2" : "") + "] " + labels[i]);
+        fout.push_back(out_t[i + used - 1]);
         i += used - 1;
       } else {
         fusedp.push_back(g0);
         flabels.push_back(labels[i]);
+        fout.push_back(out_t[i]);
       }
     }
     prog.swap(fusedp);
     labels.swap(flabels);
+    out_t.swap(fout);
   }
   plan->program = std::move(prog);
   plan->program_labels = std::move(labels);
+  plan->program_out_tensor = std::move(out_t);
   plan->program_lds_floats = high;
   if (BSX_DBG_ENV("BSX_PLAN_DEBUG"))
     for (const auto& b : plan->program_blocks) fprintf(stderr, "lds block [%6d, %6d) steps [%2d, %2d] %s\n", b.off, b.off + b.len, b.from, b.until, b.what.c_str());
@@ -722,6 +731,7 @@ static bool build_segments(Graph& g, Plan* plan) {
   for (int t : {hpw.out, g1.out, f1a.out, f1b.out, pwb.out, up2, kg.out, kf1.out, kp1.out, kd.out, up, tg.out, tf1.out, tf2.out, tpw.out, tdw.out})
     if (t != g.output) plan->tensor_off[t] = -1;
   plan->arena_floats_per_stream = top;
+  plan->seg_stored = {A, b0, B, c0, lo};             // written by head, head, k2, k2, k3 (lo2 and the level-2 gate are outputs of the middle program)
 
   h.a_off = plan->tensor_off[A]; h.b0_off = plan->tensor_off[b0]; h.part_a_off = plan->tensor_off[pA]; h.part_b0_off = plan->tensor_off[pb0];
   k2.b0_off = plan->tensor_off[b0]; k2.B_off = plan->tensor_off[B]; k2.c0_off = plan->tensor_off[c0]; k2.part_B_off = plan->tensor_off[pB];
@@ -767,12 +777,15 @@ static bool build_segments(Graph& g, Plan* plan) {
 #endif
   char line[256];
   plan->seg_text.clear();
-  auto add = [&](const char* name, int TR, int TC, int ty, int tx, int lds) {
-    snprintf(line, sizeof line, "segment %-5s tile %dx%d, %dx%d tiles per frame, LDS %.1f KiB\n", name, TR, TC, ty, tx, lds / 256.0);
+  // (the tensors a segment leaves in the arena: what crosses into the next kernel — the read-back entry serves these and nothing else of a segment)
+  auto add = [&](const char* name, int TR, int TC, int ty, int tx, int lds, std::initializer_list<int> stores) {
+    snprintf(line, sizeof line, "segment %-5s tile %dx%d, %dx%d tiles per frame, LDS %.1f KiB, stores", name, TR, TC, ty, tx, lds / 256.0);
     plan->seg_text += line;
+    for (int t : stores) plan->seg_text += " t" + std::to_string(t);
+    plan->seg_text += stores.size() ? "\n" : " the network output\n";
   };
-  add("head", h.TR, h.TC, h.tiles_y, h.tiles_x, h.lds_floats); add("k2", k2.TR, k2.TC, k2.tiles_y, k2.tiles_x, k2.lds_floats);
-  add("k3", k3.TR, k3.TC, k3.tiles_y, k3.tiles_x, k3.lds_floats); add("tail", tl.TR, tl.TC, tl.tiles_y, tl.tiles_x, tl.lds_floats);
+  add("head", h.TR, h.TC, h.tiles_y, h.tiles_x, h.lds_floats, {A, b0}); add("k2", k2.TR, k2.TC, k2.tiles_y, k2.tiles_x, k2.lds_floats, {B, c0});
+  add("k3", k3.TR, k3.TC, k3.tiles_y, k3.tiles_x, k3.lds_floats, {lo}); add("tail", tl.TR, tl.TC, tl.tiles_y, tl.tiles_x, tl.lds_floats, {});
   return true;
 }
 
@@ -1316,6 +1329,7 @@ bool build_plan(const Graph& g_in, Plan* plan, std::string* err, bool reuse_aren
   }
   if (!seg_ok) {
     plan->seg = SegPlan();
+    plan->seg_stored.clear();
     build_frame_program(g, plan, plan->steps);
   }
   // ---- per-launch path (graphs without a frame program: DeepLab): expand 1x1 → depthwise 3x3 pairs of the inverted-residual blocks run as

@@ -129,6 +129,7 @@ struct Plan {
   // whole-network per-frame program (empty when some step has no micro-op form)
   std::vector<MicroOp> program;
   std::vector<std::string> program_labels;
+  std::vector<int> program_out_tensor; // per micro-op: the graph tensor its `out` holds (a fused op: its LAST step's output — the tensors between its steps exist nowhere)
   // geometry of the workgroup that runs the program for one frame (round 6): lanes per workgroup and the LDS block it may plan into.  1024 lanes + the whole 160 KiB
   // = one frame per CU (rounds 1-5); 512 lanes + 80 KiB = two frames per CU at the same 16 waves.  Chosen per plan by mid_geometry_for() below.
   int mid_lanes = kFrameThreads;
@@ -147,7 +148,8 @@ struct Plan {
   SegPlan seg;
   unsigned program_policy = 0;          // the placement policy build_frame_program kept (bit 0 long-lived tensors to the arena, bit 1 expanded tensors elided, bit 2 small tensors top-down)
   long program_arena_bytes = 0;         // arena (HBM / L2) bytes one frame's program touches: every use of an operand that is not LDS-resident
-  std::string seg_text;                 // one line per segment kernel (tiles, LDS) for bsx_plan_describe
+  std::string seg_text;                 // one line per segment kernel (tiles, LDS, the tensors it stores in the arena) for bsx_plan_describe
+  std::vector<int> seg_stored;          // graph tensors a segment kernel writes to the arena (the boundary tensors; everything else in a segment lives in LDS / registers)
   std::string describe() const;
 };
 

@@ -421,8 +421,10 @@ BSX_API int bsx_debug_buffer(bsx_ctx* ctx, int which, void** d_ptr, size_t* byte
 BSX_API int bsx_debug_run_stage(bsx_ctx* ctx, int stage, const uint8_t* d_frames, int n, void* stream);
 /* Per-launch description of the fused plan, one line per GPU launch; returned string is owned by ctx. */
 BSX_API const char* bsx_plan_describe(bsx_ctx* ctx);
-/* Copy out the value of graph tensor `tensor_idx` for stream 0 after an infer (only tensors that survive
- * fusion are available); returns element count or negative error.  h_out may be NULL to query the size. */
+/* Copy out the value of graph tensor `tensor_idx` for stream 0 after an infer; returns element count or negative error.  h_out may be NULL to query the size.
+ * Only tensors that the executing path writes to HBM are served: a tensor that the planner fused away, that the frame program keeps in LDS or elides, or that
+ * lives inside a fused launch is refused with BSX_EINVAL, and bsx_last_error names the reason (so are arena tensors under BSX_ACT16: they are stored as halves).
+ * Without the debug build's BSX_ARENA_NO_REUSE a served tensor's arena slot may since have been reused by a later step. */
 BSX_API long bsx_debug_tensor(bsx_ctx* ctx, int tensor_idx, float* h_out, long cap);
 /* The same for stream `stream_idx` of the last batch (full-batch parity tests: every stream against its twin). */
 BSX_API long bsx_debug_tensor_of(bsx_ctx* ctx, int tensor_idx, int stream_idx, float* h_out, long cap);

@@ -1,5 +1,11 @@
-"""Layer-by-layer comparison of the GPU network against the CPU oracle (run on a GPU box).
-Usage: BSX_ARENA_NO_REUSE=1 python tools/debug_layers.py <model.tflite|key> [W H]"""
+"""Layer-by-layer audit of the GPU network against float64 (run on a GPU box; needs libbsx_dbg.so, the build with the debug switches).
+
+Usage: python tools/debug_layers.py <model.tflite|key> [W H]     (execution-path switches such as BSX_NO_RTC=1 or BSX_F16_GEMM=off are taken from the environment)
+
+The same helper and the same table as tests/test_gpu_layers.py (tests/f64_graph.py: audit): per tensor the path stores, its distance from a float64 evaluation of the
+operators since the nearest stored tensors upstream (local), the oracle's distance on the same operators (loc.oracle), their ratio (a tensor passes up to 8) and the
+accumulated error against the unforced float64 run.  The arena is planned without reuse and filled with NaNs in front of the network stage, so a tensor that is
+listed was written by this run."""
 import os
 import sys
 
@@ -7,42 +13,46 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 os.environ.setdefault("BSX_ARENA_NO_REUSE", "1")
+os.environ.setdefault("BSX_ARENA_POISON", "1")
+from backscrub_amd import build  # noqa: E402
+
+os.environ.setdefault("BSX_LIBRARY", build.LIB_DBG)
 import torch  # noqa: E402
 
 import backscrub_amd  # noqa: E402
-from backscrub_amd import synth  # noqa: E402
-from oracle import oracle_py as O  # noqa: E402
-
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import f64_graph as G  # noqa: E402
+from backscrub_amd import tflite_io  # noqa: E402
 from conftest import MODEL_KEYS, model_path  # noqa: E402
+from oracle import oracle_py as O  # noqa: E402
 
 arg = sys.argv[1] if len(sys.argv) > 1 else "lite"
 path = model_path(arg) if arg in MODEL_KEYS else arg
 W, H = (int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (640, 480)
-mg = backscrub_amd.MaskGen(path, W, H, n_streams=1)
-print(mg.plan())
+m = tflite_io.load(path)
+frames = G.audit_frames(W, H)
+mg = backscrub_amd.MaskGen(path, W, H, n_streams=len(frames))
+plan = mg.plan()
+print(plan)
+if "slot of its own" not in plan or "NaN bytes" not in plan:      # the release library ignores both switches: its table would list slots that were reused or never written
+    sys.exit("the loaded library (%s) does not honour BSX_ARENA_NO_REUSE / BSX_ARENA_POISON: build libbsx_dbg.so (python -m backscrub_amd.build) and load that" %
+             os.environ["BSX_LIBRARY"])
 oc = O.Ctx(path, W, H)
-f = synth.frame(W, H, 0)
-mg.run_stage(0, torch.from_numpy(f[None]).cuda())
-mg.run_stage(1, n=1)
+mg.run_stage(0, torch.from_numpy(np.stack([f for _, f in frames])).cuda())
+mg.run_stage(1, n=len(frames))
 torch.cuda.synchronize()
-oc.prep(f)
-oc.infer()
-om = oc.model()
 bad = 0
-for t in range(om.n_tensors):
-    try:
-        g = mg.graph_tensor(t)
-    except backscrub_amd.BsxError:
-        continue
-    w = om.tensor(t).ravel()
-    if w.size != g.size or w.size == 0:
-        continue
-    scale = max(1.0, float(np.abs(w).max()))
-    err = float(np.abs(g - w).max()) / scale
-    flag = "" if err < 1e-4 else "  <<<<<< MISMATCH"
-    if flag:
-        bad += 1
-    print("tensor %3d shape %-18s rel err %.3g%s" % (t, om.shape(t), err, flag))
-print("mismatching tensors:", bad)
+for i, (name, f) in enumerate(frames):
+    x = oc.prep(f)
+    oc.infer()
+    dev = G.read_stored(mg, len(m.tensors), i)
+    dev.pop(m.inputs[0], None)
+    rows = G.audit(path, x[None], dev, G.oracle_tensors(oc.model(), sorted(dev)), model=m)
+    n, ratio, at, acc, acc_at = G.summary(rows)
+    print("---- stream %d: %s — %d stored tensors, worst local ratio %.2f at t%d, worst accumulated error %.1f ulps at t%d" % (i, name, n, ratio, at, acc, acc_at))
+    print(G.format_table(rows))
+    bad += len(G.failing(rows)) + sum(not r["finite"] for r in rows)
+print("tensors over the bar or non-finite:", bad)
+mg.close()
+sys.exit(1 if bad else 0)
