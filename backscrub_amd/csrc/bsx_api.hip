@@ -125,6 +125,7 @@ struct bsx_ctx {
   uint8_t* d_host_frame = nullptr;  // staging for bsx_process_host
   uint8_t* d_bgr_scratch = nullptr; // BGR composite of bsx_step_batch_yuyv / _ex when the fused epilogue does not apply (lazy)
   uint8_t* d_bgr_scratch2 = nullptr; // ... its flipped copy when a YUYV pack follows (lazy)
+  uint8_t* d_mask_scratch = nullptr; // BSX_STEP_NO_MASK on the unfused route: the batch's full-resolution masks for the blend alone, 255 outside the ROI (lazy)
   uint8_t* d_bgblur_scratch = nullptr; // BSX_STEP_BGBLUR when the single pass does not apply: the blurred frames (lazy)
   uint8_t* d_bgr_in_scratch = nullptr; // BSX_STEP_YUYV_IN where the fused kernels do not apply: the batch converted to BGR (lazy)
   float* d_color_lut = nullptr;
@@ -516,10 +517,10 @@ int run_decode(bsx_ctx* c, int n, hipStream_t s, int slot = 0, const int* ids = 
 }
 // the mask up-scale table with its tile-class scratch re-based to stream `slot` (lanes run concurrently on disjoint slot ranges)
 ResizeTab tab_up_at(const bsx_ctx* c, int slot) { ResizeTab t = c->tab_up.tab; if (t.tile_class) t.tile_class += (size_t)slot * c->tiles_per_frame; return t; }
-int run_mask(bsx_ctx* c, int n, hipStream_t s, int slot = 0, const int* ids = nullptr, LaunchTimer* t = nullptr) {
+int run_mask(bsx_ctx* c, int n, hipStream_t s, int slot = 0, const int* ids = nullptr, LaunchTimer* t = nullptr, uint8_t* masks = nullptr) {
   bsx_roctx::Range range("bsx:mask");
   BSX_LAUNCH(c, t, s, launch_mask_upscale_blur(c->d_ofinal + (size_t)slot * c->outW * c->outH, c->outW, c->outH, c->in_roi, tab_up_at(c, slot),
-                                      c->d_masks + (size_t)slot * c->width * c->height, c->width, c->height, c->roi, n, s, ids));
+                                      (masks ? masks : c->d_masks) + (size_t)slot * c->width * c->height, c->width, c->height, c->roi, n, s, ids));
   return BSX_OK;
 }
 // prep → [onprep] → network → [oninfer] → decode (unless the network decodes) for n frames whose state lives in slots [slot, slot + n) — or, with ids
@@ -533,10 +534,11 @@ int enqueue_masks(bsx_ctx* c, const uint8_t* d_frames, int n, hipStream_t s, boo
   return fused_decode ? BSX_OK : run_decode(c, n, s, slot, ids, t);
 }
 // bs_maskgen_process: the masks of n frames into the persistent masks of their slots
-int process_impl(bsx_ctx* c, const uint8_t* d_frames, int n, int slot, hipStream_t s, bool yuyv_in = false, const int* ids = nullptr) {
+// masks: where the full-resolution masks go instead of the persistent ones (run_composite's BSX_STEP_NO_MASK form)
+int process_impl(bsx_ctx* c, const uint8_t* d_frames, int n, int slot, hipStream_t s, bool yuyv_in = false, const int* ids = nullptr, uint8_t* masks = nullptr) {
   if (const int rc = enqueue_masks(c, d_frames, n, s, yuyv_in, slot, ids)) return rc;
   if (c->onmask) { BSX_HIP(c, hipStreamSynchronize(s)); c->onmask(c->caller_ctx); }   // :363
-  return run_mask(c, n, s, slot, ids);
+  return run_mask(c, n, s, slot, ids, nullptr, masks);
 }
 
 // ---- the batch step: every step entry point builds a StepReq, check_step refuses it before anything is enqueued, run_step takes the routes route_of picks -----
@@ -723,11 +725,22 @@ int run_tile(bsx_ctx* c, const StepReq& r) {
 
 // the unfused geometry: the composite with the persistent masks of the batch's slots, into a context-owned BGR scratch when a flip and / or a pack follows
 int run_composite(bsx_ctx* c, const StepReq& r) {
-  if (const int rc = process_impl(c, r.frames, r.n, 0, r.s, false, r.ids)) return rc;
   const size_t px = (size_t)c->width * c->height, need = (size_t)c->n_streams * px * 3;
+  // BSX_STEP_NO_MASK (bsx.h): the persistent masks keep what the last storing call wrote — here the blend is a launch of its own and reads the masks from memory, so
+  // they go to a scratch that only this route sees (the mask kernels write the ROI; outside it the mask is 255 for good: set once, before the first use)
+  uint8_t* masks = c->d_masks;
+  if ((r.flags & BSX_STEP_NO_MASK) && !c->onmask) {
+    if (!c->d_mask_scratch) {
+      BSX_HIP(c, hipMalloc(&c->d_mask_scratch, (size_t)c->n_streams * px));
+      BSX_HIP(c, hipMemsetAsync(c->d_mask_scratch, 0xFF, (size_t)c->n_streams * px, r.s));
+      BSX_HIP(c, hipStreamSynchronize(r.s));                      // (once per context: a later call may come on another stream)
+    }
+    masks = c->d_mask_scratch;
+  }
+  if (const int rc = process_impl(c, r.frames, r.n, 0, r.s, false, r.ids, masks == c->d_masks ? nullptr : masks)) return rc;
   if ((r.yuyv() || r.flip()) && !c->d_bgr_scratch) BSX_HIP(c, hipMalloc(&c->d_bgr_scratch, need));
   uint8_t* dst = (r.yuyv() || r.flip()) ? c->d_bgr_scratch : r.out;
-  { bsx_roctx::Range range("bsx:blend"); BSX_HIP(c, launch_blend(r.bg, r.bg_stride, r.frames, c->d_masks, dst, px, r.n, r.s, r.ids)); }
+  { bsx_roctx::Range range("bsx:blend"); BSX_HIP(c, launch_blend(r.bg, r.bg_stride, r.frames, masks, dst, px, r.n, r.s, r.ids)); }
   const uint8_t* bgr = dst;
   if (r.flip()) {
     const int code = r.flip() == (BSX_STEP_FLIP_H | BSX_STEP_FLIP_V) ? -1 : (r.flip() == BSX_STEP_FLIP_H ? 1 : 0);
@@ -1324,7 +1337,7 @@ void bsx_delete(bsx_ctx* c) {
   if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
   for (auto& kv : c->host_graphs) if (kv.second) (void)hipGraphExecDestroy(kv.second);
   unload_specialised(&c->kern);
-  void* ptrs[] = {c->d_arena, c->d_net_in, c->d_net_in_u8, c->d_net_out, c->d_weights, c->d_ofinal, c->d_masks, c->d_host_frame, c->d_bgr_scratch, c->d_bgr_scratch2, c->d_bgblur_scratch, c->d_bgr_in_scratch, c->d_color_lut, c->tab_down.mem, c->tab_up.mem, c->d_program, c->d_weights16, c->d_tile_class};
+  void* ptrs[] = {c->d_arena, c->d_net_in, c->d_net_in_u8, c->d_net_out, c->d_weights, c->d_ofinal, c->d_masks, c->d_host_frame, c->d_bgr_scratch, c->d_bgr_scratch2, c->d_mask_scratch, c->d_bgblur_scratch, c->d_bgr_in_scratch, c->d_color_lut, c->tab_down.mem, c->tab_up.mem, c->d_program, c->d_weights16, c->d_tile_class};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (auto& kv : c->bg_tabs) if (kv.second.mem) (void)hipFree(kv.second.mem);
   for (auto& kv : c->vcam_tabs) if (kv.second.d.mem) (void)hipFree(kv.second.d.mem);

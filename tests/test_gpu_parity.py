@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import MODEL_KEYS, model_path, synthetic_model_path
+from geometry_cases import mask_of_state
 
 pytestmark = pytest.mark.gpu
 
@@ -296,6 +297,10 @@ def test_generic_mask_kernel_matches_tile_kernel(bs, oracle, res, monkeypatch, d
         for i in range(n):
             want = oc[i].process(frames[i])
             assert _iou_fg(got_m[i], want) >= 0.999
+            # whatever the network's float result decided: the mask and the composite the DEVICE'S OWN state implies, by the oracle's resize, blur and blend
+            own = mask_of_state(oracle, got_of[i], mg.info, W, H)
+            assert np.array_equal(got_m[i], own), "fused, generic=%s stream %d: %d mask bytes differ from the device state's mask" % (generic, i, (got_m[i] != own).sum())
+            assert np.array_equal(got_o[i], oracle.alpha_blend(bg, frames[i], own)), "fused, generic=%s stream %d: composite" % (generic, i)
             if np.array_equal(got_of[i], oc[i].ofinal()):    # same model-resolution mask → everything after it is integer work
                 assert np.array_equal(got_m[i], want), "fused, generic=%s stream %d" % (generic, i)
                 assert np.array_equal(got_o[i], oracle.alpha_blend(bg, frames[i], want))
@@ -1225,9 +1230,14 @@ def test_partial_batches_and_odd_frame_sizes(bs, oracle):
             mg.step(_dev(frames), _dev(bg), out[:n])
             got_m = mg.masks().cpu().numpy()
             got_o = out.cpu().numpy()
+            got_of = mg.ofinal().cpu().numpy()
             for i in range(n):
                 want = oc[i].process(frames[i])
                 assert _iou_fg(got_m[i], want) >= 0.999, (W, H, t, i)
+                # whatever the network's float result decided: the mask and the composite the DEVICE'S OWN state implies, by the oracle's resize, blur and blend
+                own = mask_of_state(oracle, got_of[i], mg.info, W, H)
+                assert np.array_equal(got_m[i], own), (W, H, t, i, int((got_m[i] != own).sum()))
+                assert np.array_equal(got_o[i], oracle.alpha_blend(bg, frames[i], own)), (W, H, t, i)
                 if np.array_equal(got_m[i], want):
                     assert np.array_equal(got_o[i], oracle.alpha_blend(bg, frames[i], want))
             for i in range(n, cap):                             # untouched streams keep their previous state exactly

@@ -8,6 +8,10 @@ dynamic LDS, stream and event (numbered by first use), copy / set / allocation s
 
     python tools/step_trace.py --out a.json [--debug]         # one library (BSX_LIBRARY selects it), every configuration
     python tools/step_trace.py --diff a.json b.json            # calls whose return code or trace differ
+
+trace_all(sizes=[(model, W, H[, n_streams])], brief=True) is the geometry audit's form (tests/test_geometry_host.py): one context per listed size, the short call
+list of drive(brief=True) — the plain step, one call per flag route that picks another image kernel, the mixed step, stages 0 / 3 / 4 — and the context's own
+roi / in_roi under "_info".  roi_sweep() (child, --roi-sweep) creates one context per size of a list and returns the rectangles bsx_get_info reports.
 """
 import argparse
 import ctypes as C
@@ -50,8 +54,9 @@ def model_file(key):
 
 
 # ---- child: runs under the stub -------------------------------------------------------------------------------------------------------------------------------
-def drive(model, W, H, n):
-    """every call of the matrix on one context → {key: {"rc", "error", "log": [first, last)}}"""
+def drive(model, W, H, n, brief=False):
+    """every call of the matrix on one context → {key: {"rc", "error", "log": [first, last)}}; brief: the geometry audit's short list (the plain step, one call
+    per flag route that picks another image kernel, the stage entries) and the context's own geometry under "_info" """
     sys.path.insert(0, ROOT)
     import numpy as np
     from backscrub_amd import api
@@ -97,6 +102,20 @@ def drive(model, W, H, n):
     def pipe(key, flags=0, frames=fr, b=bg, o=out, nn=n):
         run("pipe_" + key, lambda: L.bsx_step_batch_pipelined(ctx, P(frames), P(b), 0, P(o), nn, None, flags))
 
+    if brief:
+        run("step", lambda: L.bsx_step_batch(ctx, P(fr), P(bg), 0, P(out), n, None))
+        for key, flags, frames, o in [("flip_h", FH, fr, out), ("yuyv", YUYV, fr, out2), ("yuyv_flip", YUYV | FH, fr, out2), ("no_mask_flip_v", NOMASK | FV, fr, out),
+                                      ("yuyv_in", YIN, yu, out), ("in_place", 0, fr, fr)]:
+            ex(key, flags, frames, bg, o)
+        st = (api._StreamSetting * n)()
+        for i in range(n):
+            st[i].d_bg, st[i].flags = at["bgs"] + i * fb, (FH, FV, 0)[i % 3]
+        run("mixed", lambda: L.bsx_step_batch_mixed(ctx, None, P(fr), st, P(out), n, None, 0))
+        for st_ in (0, 3, 4):
+            run("stage_%d" % st_, lambda: L.bsx_debug_run_stage(ctx, st_, P(yu if st_ == 4 else fr), n, None))
+        run("delete", lambda: L.bsx_delete(ctx) or 0)
+        calls["_info"] = {k: (list(getattr(info, k)) if k in ("roi", "in_roi") else getattr(info, k)) for k, _ in api._Info._fields_}
+        return calls
     run("process_batch", lambda: L.bsx_process_batch(ctx, P(fr), n, None, None))
     run("process_batch_masks", lambda: L.bsx_process_batch(ctx, P(fr), n, P(out), None))
     run("step", lambda: L.bsx_step_batch(ctx, P(fr), P(bg), 0, P(out), n, None))
@@ -214,14 +233,37 @@ def normalise(lines):
     return out
 
 
-def configs(debug):
+def roi_sweep(model, sizes):
+    """child, under the stub: one context per (W, H) of `sizes` → [[W, H, roi or None, in_roi or None]] (None: bsx_new refused the size)"""
+    sys.path.insert(0, ROOT)
+    from backscrub_amd import api
+    L = C.CDLL(api.lib_path())
+    for name, res, args in api.SYMBOLS:
+        f = getattr(L, name)
+        f.restype, f.argtypes = res, args
+    out = []
+    info = api._Info()
+    for W, H in sizes:
+        ctx = L.bsx_new(model.encode(), 2, W, H, 1, 0, api.DEBUG_FN(), api.STAGE_FN(), api.STAGE_FN(), api.STAGE_FN(), None)
+        if not ctx:
+            out.append([W, H, None, None])
+            continue
+        L.bsx_get_info(ctx, C.byref(info))
+        out.append([W, H, list(info.roi), list(info.in_roi)])
+        L.bsx_delete(ctx)
+    return out
+
+
+def configs(debug, sizes=None):
+    if sizes is not None:                                       # the geometry audit: [(model, W, H)] or [(model, W, H, n_streams)]
+        return [tuple(s[:3]) + ("",) + tuple(s[3:4]) for s in sizes]
     geo = [(m, W, H, "") for m in MODELS for W, H in GEOMETRIES]
     if debug:
         geo += [(m, 640, 480, sw) for sw in SWITCHES for m in MODELS]
     return geo
 
 
-def trace_all(debug, n, only=None):
+def trace_all(debug, n, only=None, sizes=None, brief=False):
     stub = build_stub()
     sys.path.insert(0, ROOT)
     from backscrub_amd import build as _b
@@ -229,19 +271,19 @@ def trace_all(debug, n, only=None):
     result = {}
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:
-        for model, W, H, sw in configs(debug):
+        for model, W, H, sw, *own_n in configs(debug, sizes):
             name = "%s %dx%d %s" % (model, W, H, sw or "-")
             if only and not re.search(only, name):
                 continue
             log = os.path.join(tmp, "hip_%d.log" % len(result))
             env = dict(os.environ, LD_PRELOAD=stub, BSX_STUB_LOG=log, BSX_STUB_NDEV="1", BSX_LIBRARY=lib)
-            nn = n
+            nn = own_n[0] if own_n else n
             if sw:
                 k, _, v = sw.partition("=")
                 env[k] = v or "1"
                 if k == "BSX_LANES":
                     nn = 16 * int(v)                 # lanes are taken from 16 streams per lane on
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", model_file(model), str(W), str(H), str(nn)], env=env,
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", model_file(model), str(W), str(H), str(nn)] + (["--brief"] if brief else []), env=env,
                                capture_output=True, text=True, timeout=1800)
             if r.returncode != 0:
                 raise RuntimeError("%s: child failed\n%s" % (name, r.stderr[-3000:]))
@@ -249,8 +291,11 @@ def trace_all(debug, n, only=None):
             if "error" in d:
                 raise RuntimeError("%s: %s" % (name, d["error"]))
             logl = open(log).read().splitlines() if os.path.exists(log) else []
+            info = d.pop("_info", None)
             result[name] = {k: {"rc": c["rc"], "error": c["error"], "trace": normalise(logl[c["log"][0]:c["log"][1]])} for k, c in d.items()}
             print("%-40s %3d calls, %6d HIP calls" % (name, len(d), sum(len(c["trace"]) for c in result[name].values())), file=sys.stderr)
+            if info is not None:
+                result[name]["_info"] = info
     return result
 
 
@@ -263,6 +308,8 @@ def diff(a, b):
             out.append((cfg, "*", "configuration missing on one side"))
             continue
         for k in sorted(set(ca) | set(cb)):
+            if k.startswith("_"):                                # "_info": the context's geometry, not a call
+                continue
             count += 1
             x, y = ca.get(k), cb.get(k)
             if x is None or y is None:
@@ -277,6 +324,8 @@ def diff(a, b):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--child", nargs=4, metavar=("MODEL", "W", "H", "N"), help=argparse.SUPPRESS)
+    ap.add_argument("--brief", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--roi-sweep", nargs=2, metavar=("MODEL", "SIZES_JSON"), help=argparse.SUPPRESS)
     ap.add_argument("--out", help="write the traces of the library BSX_LIBRARY names (default: the in-tree build) here")
     ap.add_argument("--debug", action="store_true", help="the debug library (libbsx_dbg.so by default), with every debug switch configuration")
     ap.add_argument("--only", help="regular expression: only the configurations whose name matches")
@@ -284,7 +333,9 @@ def main():
     ap.add_argument("--diff", nargs=2, metavar=("A", "B"))
     a = ap.parse_args()
     if a.child:
-        print(json.dumps(drive(a.child[0], int(a.child[1]), int(a.child[2]), int(a.child[3]))))
+        print(json.dumps(drive(a.child[0], int(a.child[1]), int(a.child[2]), int(a.child[3]), a.brief)))
+    elif a.roi_sweep:
+        print(json.dumps(roi_sweep(a.roi_sweep[0], json.load(open(a.roi_sweep[1])))))
     elif a.diff:
         count, d = diff(json.load(open(a.diff[0])), json.load(open(a.diff[1])))
         for cfg, k, what in d:
