@@ -466,6 +466,28 @@ int state_write_fence(bsx_ctx* c, hipStream_t s) {
 }
 // does the specialised middle kernel compute micro-op i's arena output chunk by chunk inside the depthwise after it (gen_mid.cpp: the tensor is never stored)?
 bool program_op_elided(const bsx_ctx* c, int i) { return c->kern.mid && !BSX_DBG_ENV("BSX_RTC_FINE") && mid_pw_feeds_dw(c->plan, i); }
+
+// Is tensor t — one that debug_tensor_unstored() says this path writes — held as packed halves?  The same predicates as the writers:
+//   BSX_ACT16 (segmented frame program): what the segment kernels exchange (H16: Plan::seg_stored) and every arena ACTIVATION operand of the generated middle kernel
+//     (generate_mid_source's asp(): convolution, depthwise and resize outputs); a squeeze-excite op's vectors stay f32 (fc_apply stores through sp_of());
+//   BSX_F16_GEMM=fast16 (per-launch path): the depthwise output of a fused expand + depthwise pair when ir_out16() held for the last network stage's batch.
+// The halves start at the tensor's own arena place (frame-major or batch-major like the f32 form), element i at half i.
+bool debug_tensor_half(const bsx_ctx* c, int t) {
+  const Plan& p = c->plan;
+  if (t == p.input || t == p.output) return false;
+  if (c->use_program) {
+    if (!c->act16) return false;
+    if (p.seg.on && std::find(p.seg_stored.begin(), p.seg_stored.end(), t) != p.seg_stored.end()) return true;
+    for (size_t i = 0; i < p.program.size() && i < p.program_out_tensor.size(); i++)
+      if (p.program_out_tensor[i] == t) return p.program[i].kind != kMicroSe;
+    return false;
+  }
+  const int n = c->last_net_n > 0 ? c->last_net_n : c->n_streams;
+  for (int j = 1; j < (int)p.steps.size(); j++)
+    if (p.steps[j].out == t) return p.steps[j - 1].fuse_dw == j && ir_out16(p, p.steps[j - 1], n, c->d_weights16, c->f16_terms, BSX_DBG_ENV("BSX_NO_PW_GEMM") != nullptr);
+  return false;
+}
+
 bool infer_decodes(const bsx_ctx* c) { return (c->use_program && c->plan.seg.on && !c->keep_logits) || argmax_tail(c); }
 // ids (device, nullable): the id form of a step — frame i's temporal state is slot ids[i] (then slot == 0); nullptr = slots [slot, slot + n)
 int run_infer(bsx_ctx* c, int n, hipStream_t s, bool logits = true, int slot = 0, const int* ids = nullptr, LaunchTimer* t = nullptr) {
@@ -1275,6 +1297,13 @@ static bsx_ctx* new_ctx(const char* model_path, size_t threads, const bsx_geomet
   c->plan_text = c->plan.describe();
   {
     char line[256];
+    for (size_t i = 0; i < c->plan.steps.size(); i++) {      // reduced-precision storage of the per-launch path: one line per fused pair whose output may leave as halves
+      if (c->use_program || !c->d_weights16 || !ir_out16_planned(c->plan, c->plan.steps[i], c->f16_terms)) continue;
+      const Step& dd = c->plan.steps[c->plan.steps[i].fuse_dw];
+      snprintf(line, sizeof line, "f16 storage: steps %zu and %d (expand + depthwise) store t%d (%dx%dx%d per frame) as f16 at %ld pixels and more, step %d reads it as f16\n", i,
+               c->plan.steps[i].fuse_dw, dd.out, dd.OH, dd.OW, dd.Cout, kOut16MinRows, c->plan.steps[i].fuse_dw + 1);
+      c->plan_text += line;
+    }
     snprintf(line, sizeof line, "frame program: %s, %zu micro-ops, LDS %d floats (%.1f KiB), %d tensors in LDS, %d in HBM\n",
              c->use_program ? "ON" : "off", c->plan.program.size(), c->plan.program_lds_floats, c->plan.program_lds_floats / 256.0,
              c->plan.program_lds_tensors, c->plan.program_global_tensors);
@@ -1282,7 +1311,18 @@ static bsx_ctx* new_ctx(const char* model_path, size_t threads, const bsx_geomet
     if (no_reuse) c->plan_text += "arena: every tensor in a slot of its own (debug switch)\n";
     if (c->arena_poison) c->plan_text += "arena: filled with NaN bytes in front of every network stage (debug switch)\n";
     if (c->use_program) c->plan_text += "program execution: " + c->kern.mid_note + "\n";
-    if (c->use_program && c->plan.seg.on) c->plan_text += c->plan.seg_text;
+    if (c->use_program && c->plan.seg.on) {
+      std::string seg = c->plan.seg_text;
+      if (c->act16)                     // the storage width of what the segment kernels leave in the arena: "stores t33:f16 t41:f16"
+        for (size_t at = seg.find(" stores t"); at != std::string::npos; at = seg.find(" stores t", at)) {
+          for (at += 7; at + 2 < seg.size() && seg[at] == ' ' && seg[at + 1] == 't' && isdigit((unsigned char)seg[at + 2]); ) {
+            for (at += 2; at < seg.size() && isdigit((unsigned char)seg[at]); at++) {}
+            seg.insert(at, ":f16");
+            at += 4;
+          }
+        }
+      c->plan_text += seg;
+    }
     if (c->use_program && c->plan.seg.on) c->plan_text += "segment execution: " + c->kern.seg_note + "\n";
     if (c->use_program && c->kern.mid) c->plan_text += mid_barrier_line(c->plan, c->act16);
     for (size_t i = 0; i < c->plan.program_labels.size(); i++) {
@@ -1290,6 +1330,7 @@ static bsx_ctx* new_ctx(const char* model_path, size_t threads, const bsx_geomet
       if (i < c->plan.program_out_tensor.size()) {            // the tensor the op leaves behind, and where: the read-back entry serves the "hbm" ones only
         const int sp = c->plan.program[i].out.space;
         c->plan_text += " -> t" + std::to_string(c->plan.program_out_tensor[i]) + (sp == kLocLds ? " lds" : (program_op_elided(c.get(), (int)i) ? " elided" : (sp == kLocOutput ? " output" : " hbm")));
+        if (sp == kLocGlobal && !program_op_elided(c.get(), (int)i) && debug_tensor_half(c.get(), c->plan.program_out_tensor[i])) c->plan_text += " f16";
       }
       c->plan_text += "\n";
     }
@@ -1905,10 +1946,6 @@ int bsx_model_precompile(const char* model_path, const char* arch, char* msg, si
 
 const char* bsx_plan_describe(bsx_ctx* c) { return c ? c->plan_text.c_str() : ""; }
 
-// BSX_ACT16 stores the arena tensors of the segmented networks as packed halves at their own strides: reading them back as f32 would return garbage without an
-// error, so the inspection entry points refuse arena tensors in that mode (network input / output keep their f32 buffers).
-static bool debug_tensor_readable(const bsx_ctx* c, int t) { return !c->act16 || t == c->plan.input || t == c->plan.output; }
-
 // An arena offset alone does not mean that the tensor exists: the planner gives every step output one before it decides what stays in LDS, what a fused launch keeps
 // in registers and what the generated kernel elides.  Returns why the path that executes this context never writes tensor t to the arena (nullptr: it does) — from
 // the plan and from the choices the launchers made for the last network stage (the same predicates: program_op_elided, chain3_on, the ir_on rule of launch_step).
@@ -1944,18 +1981,26 @@ static const char* debug_tensor_unstored(const bsx_ctx* c, int t) {
 
 static long debug_tensor_at(bsx_ctx* c, int t, int stream_idx, float* h_out, long cap) {
   if (!c) return BSX_EINVAL;
-  if (t < 0 || t >= (int)c->graph.tensors.size() || stream_idx < 0 || stream_idx >= c->n_streams || (h_out && cap < 0)) { c->last_error = "bsx_debug_tensor: tensor or stream index out of range"; return BSX_EINVAL; }
+  if (t < 0 || t >= (int)c->plan.tensor_off.size() || t >= (int)c->plan.tensor_elems.size() || stream_idx < 0 || stream_idx >= c->n_streams || (h_out && cap < 0)) { c->last_error = "bsx_debug_tensor: tensor or stream index out of range"; return BSX_EINVAL; }
   if (c->plan.tensor_off[t] < 0) { c->last_error = "bsx_debug_tensor: tensor " + std::to_string(t) + " has no place in the arena (a constant, or fused away by the planner)"; return BSX_EINVAL; }
-  if (!debug_tensor_readable(c, t)) { c->last_error = "bsx_debug_tensor: arena tensors are stored as f16 under BSX_ACT16 and are not readable through this entry"; return BSX_EINVAL; }
   if (const char* why = debug_tensor_unstored(c, t)) { c->last_error = "bsx_debug_tensor: tensor " + std::to_string(t) + " is never written to the arena on this path: " + why; return BSX_EINVAL; }
   DeviceGuard guard(c->device);
-  const long n = (long)c->graph.tensors[t].elems();
+  const long n = c->plan.tensor_elems[t];              // (the plan's count: a rewrite's synthetic tensor — the 1x1 convolution moved below its resize — has no entry in the file's graph)
   if (!h_out) return n;
   // network input / output and the per-launch arena are batch-major (stream i at + i * elems); the per-frame program's arena is frame-major
   const float* p = (t == c->plan.input || t == c->plan.output || !c->use_program) ? c->tensor_ptr(t) + (size_t)stream_idx * (size_t)n
                                                                                  : c->tensor_ptr(t) + (size_t)stream_idx * c->plan.arena_floats_per_stream;
   if (hipDeviceSynchronize() != hipSuccess) return BSX_EDEVICE;
-  if (hipMemcpy(h_out, p, sizeof(float) * (size_t)std::min(n, cap), hipMemcpyDeviceToHost) != hipSuccess) return BSX_EDEVICE;
+  const size_t take = (size_t)std::min(n, cap);
+  if (debug_tensor_half(c, t)) {       // packed halves: stream i's start at half i * elems of a batch-major tensor, at the frame's own arena slice of a frame-major one
+    const bool batch_major = !c->use_program;
+    const _Float16* ph = reinterpret_cast<const _Float16*>(batch_major ? c->tensor_ptr(t) : p) + (batch_major ? (size_t)stream_idx * (size_t)n : 0);
+    std::vector<_Float16> h(take);
+    if (take && hipMemcpy(h.data(), ph, sizeof(_Float16) * take, hipMemcpyDeviceToHost) != hipSuccess) return BSX_EDEVICE;
+    for (size_t i = 0; i < take; i++) h_out[i] = (float)h[i];
+    return n;
+  }
+  if (hipMemcpy(h_out, p, sizeof(float) * take, hipMemcpyDeviceToHost) != hipSuccess) return BSX_EDEVICE;
   return n;
 }
 

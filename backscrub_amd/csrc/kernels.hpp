@@ -37,6 +37,22 @@ inline bool chain3_on(const Plan& plan, int mid, int n, const uint16_t* weights1
   return weights16 && (f16_terms & 15) == 3 && M >= 8192 && M * plan.steps[b.chain_first].Cin < (1l << 31);
 }
 
+// Reduced-precision storage (f16_terms bit 4, BSX_F16_GEMM=fast16): is the output of the fused expand + depthwise pair that starts at step `expand` stored as packed
+// halves ([n][OH*OW][C], at the tensor's own arena place) for n streams?  `expand` is the pair's first step, a step of `plan`.  Only when the depthwise output's single reader is a 1x1 convolution that will take the
+// f16-input GEMM (Step::in_from_fused_dw, same row rule on both sides).  Asked by the pair's launch and by the read-back entry; ir_out16_planned is the part
+// that does not depend on the batch (what the plan text announces).
+constexpr long kOut16MinRows = 8192;
+inline bool ir_out16_planned(const Plan& plan, const Step& expand, int f16_terms) {
+  if (!(f16_terms & 16)) return false;
+  const int dw = expand.fuse_dw;
+  return dw >= 0 && (size_t)dw + 1 < plan.steps.size() && plan.steps[dw + 1].in_from_fused_dw && plan.steps[dw + 1].in0 == plan.steps[dw].out;
+}
+inline bool ir_out16(const Plan& plan, const Step& expand, int n, const uint16_t* weights16, int f16_terms, bool no_gemm) {
+  if (!weights16 || no_gemm || !ir_out16_planned(plan, expand, f16_terms)) return false;
+  const Step& dws = plan.steps[expand.fuse_dw];
+  return (long)n * dws.OH * dws.OW >= kOut16MinRows;
+}
+
 // DeepLab tail: the graph's final RESIZE_BILINEAR fused with the 21-way argmax + temporal IIR (the full-resolution logits never exist)
 bool resize_argmax_fusable(const Step& st);
 // generic = the scalar first-maximum scan (what more than 24 classes take; tests force it for the 21-class graph)

@@ -266,6 +266,19 @@ __device__ __forceinline__ void split_pair(float a, float b, unsigned& hi, unsig
   asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(lo) : "v"(hi), "v"(a));
   asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(lo) : "v"(hi), "v"(b));
 }
+// Two floats as packed halves for the 1-TERM forms, where the half IS the MFMA operand: round to nearest even (v_cvt_pk_f16_f32), half an ulp of error and no
+// bias — round-toward-zero is for the hi part of a split, whose lo part absorbs the error.  Clamped to the largest half first, so that like the truncating
+// conversion it never produces inf, which a zero weight of the K padding would turn into NaN.  The clamp is two compares, both false for a NaN (v_med3, v_min
+// and v_max return the constant instead): a NaN activation stays NaN in the operand and in every output it reaches, as in the f32 and 3-term forms, so a
+// poisoned arena still shows a tensor nobody wrote in what is computed from it.
+__device__ __forceinline__ float clamp_half_range(float x) {
+  x = x > 65504.f ? 65504.f : x;
+  return x < -65504.f ? -65504.f : x;
+}
+__device__ __forceinline__ unsigned pack_rn(float a, float b) {
+  const f2v v = {clamp_half_range(a), clamp_half_range(b)};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, h2v));
+}
 template <int TERMS, typename Q>                    // Q: float4 or f4v
 __device__ __forceinline__ void split8(const Q v0, const Q v1, h8v& hi, h8v& lo) {
   u4v h, l;
@@ -276,8 +289,8 @@ __device__ __forceinline__ void split8(const Q v0, const Q v1, h8v& hi, h8v& lo)
     split_pair(v1.x, v1.y, a, b); h.z = a; l.z = b;
     split_pair(v1.z, v1.w, a, b); h.w = a; l.w = b;
   } else {
-    h.x = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(v0.x, v0.y)); h.y = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(v0.z, v0.w));
-    h.z = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(v1.x, v1.y)); h.w = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(v1.z, v1.w));
+    h.x = pack_rn(v0.x, v0.y); h.y = pack_rn(v0.z, v0.w);
+    h.z = pack_rn(v1.x, v1.y); h.w = pack_rn(v1.z, v1.w);
     l = h;
   }
   hi = __builtin_bit_cast(h8v, h);
@@ -456,7 +469,7 @@ __global__ __launch_bounds__(kThreads, NTW > 4 ? 3 : 4) void pw_gemm_f16s_k(cons
         split_pair(v.z, v.w, a, b); hi.y = a; lo.y = b;
         *reinterpret_cast<u2v*>(&Al[row * kHSA + kq]) = lo;
       } else {
-        hi.x = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(v.x, v.y)); hi.y = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(v.z, v.w));
+        hi.x = pack_rn(v.x, v.y); hi.y = pack_rn(v.z, v.w);
       }
       *reinterpret_cast<u2v*>(&Ah[row * kHSA + kq]) = hi;
     }
@@ -1770,8 +1783,7 @@ hipError_t launch_step(const Step& st, const Plan& plan, float* arena, float* ne
         const int slabs = st.k16_pad / 32;
         static const int ir_phases = BSX_DBG_ENV("BSX_IR_PHASES") ? atoi(BSX_DBG_ENV("BSX_IR_PHASES")) : 3;      // timing experiments: 1 = expand only, 2 = depthwise only
         // reduced-precision storage (f16_terms bit 4): only when the depthwise output's single reader is a GEMM that will take the f16 form (same M rule)
-        const bool out16 = (f16_terms & 16) && (size_t)st.fuse_dw + 1 < plan.steps.size() && plan.steps[st.fuse_dw + 1].in_from_fused_dw &&
-                           plan.steps[st.fuse_dw + 1].in0 == dws.out && (long)n * dws.OH * dws.OW >= 8192 && !no_gemm;
+        const bool out16 = ir_out16(plan, st, n, weights16, f16_terms, no_gemm);
         // 1024-lane workgroups (four waves per SIMD, <= 128 registers, input rows straight into the MFMA layout: no LDS left for sixteen re-order
         // buffers) for the whole-frame 32-channel layers.  Measured per K: 16 input channels (64-byte rows: nothing to coalesce) 149 -> 134 us;
         // 32 channels equal; 48 (two slabs) +5 %; 80 (three slabs) spills at 128 registers, 1.06 -> 1.72 ms.  Default: the 16-channel layers only

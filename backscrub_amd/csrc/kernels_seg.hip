@@ -79,6 +79,14 @@ template <bool H16> __device__ __forceinline__ void stg4(float* base, unsigned i
   if (H16) *reinterpret_cast<h4s*>(reinterpret_cast<_Float16*>(base) + idx) = h4s{(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
   else *reinterpret_cast<float4*>(base + idx) = v;
 }
+// What every reader of a half-stored tensor gets back.  A kernel that goes on computing with a value it also stores (the head's 1x1 behind A, k2's behind B, every
+// pooled partial sum) uses the STORED value in the 16-bit storage mode: its own arithmetic, the next kernel and the gate's pooled mean then all see one tensor —
+// the one in the arena — and each stored tensor can be checked against the tensors it was computed from (tests/test_gpu_layers_reduced.py).  This is part of what
+// the mode DEFINES: its results are those of a network whose stored activations are halves, not of the f32 network with halves on the side.
+template <bool H16> __device__ __forceinline__ float4 as_stored(float4 v) {
+  if (H16) return make_float4((float)(_Float16)v.x, (float)(_Float16)v.y, (float)(_Float16)v.z, (float)(_Float16)v.w);
+  return v;
+}
 // ---- LDS tile layouts (bank model: MI355X_MICROARCH.md §LDS; evaluated for every access pattern of this file by tests/test_lds_layouts.py) ----------------------------
 // A tile pixel is 16 floats = four 16-byte channel quads.  Stored densely ([pixel][16], quad q at +4q) the MFMA epilogue's ds_write_b128 — 8 consecutive lanes = 8
 // consecutive pixels, ONE quad — touches two of the eight 16-byte slots of its 128-byte window (4-way conflict: 32 LDS cycles for an instruction that costs 13), the MFMA
@@ -426,7 +434,7 @@ __global__ __launch_bounds__(kSegThreads) void seg_head_k(
     float4 v = acc_quad(acc);
     const int x2 = 16 * rt.ct + xe, gy = ar0 + rt.row, gx = ac0 + x2;
     v = f4add(v, bias_s);
-    v = STEM_HSWISH ? hswish4(v) : clamp4(v, cl_stem);
+    v = as_stored<H16>(STEM_HSWISH ? hswish4(v) : clamp4(v, cl_stem));
     // (lanes past the tile's last column hold the stem of column AC - 1, as the clamped read of the two-loop form did; their results are dropped below)
     f4acc pa = {0.f, 0.f, 0.f, 0.f};
     if (!(d.dbg_skip & 2)) {
@@ -477,7 +485,7 @@ __global__ __launch_bounds__(kSegThreads) void seg_head_k(
   for (int py = wave; py < d.TR && !(d.dbg_skip & 4); py += 4) {
     if (r0 + py >= d.H2) break;
     if (px < d.TC && c0 + px < d.W2) {
-      const float4 v = clamp4(tof4(dw3x3(x_f, AC * 16, 2 * py, cox, wd) + bias_d), cl_dw);
+      const float4 v = as_stored<H16>(clamp4(tof4(dw3x3(x_f, AC * 16, 2 * py, cox, wd) + bias_d), cl_dw));
       stg4<H16>(b0_out, (unsigned)(((r0 + py) * d.W2 + c0 + px) * 16 + 4 * quad), v);
       sumB = f4add(sumB, v);
     }
@@ -549,7 +557,7 @@ __global__ __launch_bounds__(kSegThreads) __attribute__((amdgpu_waves_per_eu(6, 
     float4 v = acc_quad(acc);
     const int x2 = 16 * rt.ct + xe, hy = br0 + rt.row, hx = bc0 + x2;
     if (x2 < BC) {
-      v = clamp4(f4add(v, bias_a), cl_a);
+      v = as_stored<H16>(clamp4(f4add(v, bias_a), cl_a));
       st4(B_t + (rt.row * RW + 16 * rt.ct) * 16 + la, v);
       const bool row_owned = hy >= max(2 * r0, 0) && hy < min(2 * r0 + 2 * d.TR, d.H2);
       if (row_owned && hx >= 2 * c0 && hx < min(2 * c0 + 2 * d.TC, d.W2)) {
@@ -737,7 +745,7 @@ __global__ __launch_bounds__(kSegThreads) void seg_k3_k(
     const f4acc acc = mma16(f4add(dv, tof4(zc)), wr);                  // dw epilogue: activation, then + residual z; straight into pw2
     float4 v = acc_quad(acc);
     if (xe < d.TC && c0 + xe < d.W2) {
-      v = clamp4(f4add(v, bias2), cl_2);
+      v = as_stored<H16>(clamp4(f4add(v, bias2), cl_2));
       stg4<H16>(lo_out, (unsigned)(((r0 + py) * d.W2 + c0 + xe) * 16 + cq4), v);
       sum = f4add(sum, v);
     }

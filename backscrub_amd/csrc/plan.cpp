@@ -1371,6 +1371,8 @@ bool build_plan(const Graph& g_in, Plan* plan, std::string* err, bool reuse_aren
       }
     }
   }
+  plan->tensor_elems.assign(plan->tensor_off.size(), 0);
+  for (size_t t = 0; t < plan->tensor_elems.size() && t < g.tensors.size(); t++) plan->tensor_elems[t] = (long)g.tensors[t].elems();
   return true;
 }
 

@@ -123,6 +123,7 @@ struct Plan {
   std::vector<float> weights;         // packed weight arena (host copy)
   std::vector<uint16_t> weights16;    // IEEE half bit patterns: hi/lo split of the large pointwise-conv weights (split-f16 MFMA GEMM)
   std::vector<long> tensor_off;       // per graph tensor: float offset per stream-slot unit, -1 if not materialised
+  std::vector<long> tensor_elems;     // elements of every tensor tensor_off knows, the synthetic ones of the rewrites included (the read-back entry serves those too)
   size_t arena_floats_per_stream = 0; // arena size = this * n_streams
   int input = -1, output = -1;
   double macs_per_frame = 0;

@@ -423,7 +423,10 @@ BSX_API int bsx_debug_run_stage(bsx_ctx* ctx, int stage, const uint8_t* d_frames
 BSX_API const char* bsx_plan_describe(bsx_ctx* ctx);
 /* Copy out the value of graph tensor `tensor_idx` for stream 0 after an infer; returns element count or negative error.  h_out may be NULL to query the size.
  * Only tensors that the executing path writes to HBM are served: a tensor that the planner fused away, that the frame program keeps in LDS or elides, or that
- * lives inside a fused launch is refused with BSX_EINVAL, and bsx_last_error names the reason (so are arena tensors under BSX_ACT16: they are stored as halves).
+ * lives inside a fused launch is refused with BSX_EINVAL, and bsx_last_error names the reason.  A tensor that the path stores as packed halves (arena activations
+ * under BSX_ACT16, the fused blocks' depthwise outputs under BSX_F16_GEMM=fast16 from 8192 rows of the last network stage) is served widened to f32.
+ * Indices from the file's tensor count upwards name the tensors a graph rewrite created (a 1x1 convolution moved below its resize stores one where the file has
+ * none; the plan text shows them as the `t<idx>` of the rewrite's steps): served under the same rule, BSX_EINVAL past the last of them.
  * Without the debug build's BSX_ARENA_NO_REUSE a served tensor's arena slot may since have been reused by a later step. */
 BSX_API long bsx_debug_tensor(bsx_ctx* ctx, int tensor_idx, float* h_out, long cap);
 /* The same for stream `stream_idx` of the last batch (full-batch parity tests: every stream against its twin). */

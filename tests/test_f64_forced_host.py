@@ -204,3 +204,147 @@ def test_a_border_row_column_or_corner_taken_from_its_neighbour_fails(model):
             checked.setdefault(what, []).append(t)
     for what in ("last row", "last column", "first row", "first column", "corner pixel"):
         assert {stem, dw2} <= set(checked.get(what, [])), "%s: asserted on %s only" % (what, checked.get(what, []))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The bars of the reduced-precision audit (f64_graph: audit_reduced), proven the same way
+# ------------------------------------------------------------------------------------------------------------------------------
+# Stand-in devices, all from f64_graph's operators on PyTorch's f32 CPU kernels:
+#   half storage   the cut tensors other than the network output are rounded to half; downstream operators consume the rounded values
+#   f16 operands   the operators operand_rounding_rule names run on x.half().float() and w.half().float()
+#   both
+RULE_STREAMS = 9          # the batch at which every 1x1 convolution of DeepLab's 33x33 levels has its 8192 rows: the widest rule
+
+
+def _cuts(m, dev):
+    every = sorted(dev)
+    return (("every tensor", every), ("every 12th + output", sorted(set(every[::12] + [m.outputs[0]]))))
+
+
+@functools.lru_cache(maxsize=None)
+def _rule(model):
+    import backscrub_amd
+    from backscrub_amd import tflite_io
+    return G.operand_rounding_rule(backscrub_amd.model_describe(_path(model)), tflite_io.load(_path(model)), "fast", RULE_STREAMS)
+
+
+def _stand_in(m, x, cut, half_storage, rounding, fault=None):
+    """tensor index → f32 array over `cut` of the stand-in device.  fault: (tensor, callable f32 tensor → stored f32 tensor) replaces the storing of one cut tensor;
+    (tensor, "slab") drops input channels 32..63 from that convolution."""
+    val = G._constants(m, torch.float32)
+    val[m.inputs[0]] = torch.from_numpy(np.asarray(x, dtype=np.float32))
+    cut, dev, out = set(cut), {}, m.outputs[0]
+    for op in m.ops:
+        o = op.outputs[0]
+        r = (rounding or {}).get(o)
+        if fault and fault[0] == o and fault[1] == "slab":
+            assert op.name == "CONV_2D" and r
+            v2 = dict(val)
+            xz = val[op.inputs[0]].clone()
+            xz[..., 32:64] = 0
+            v2[op.inputs[0]] = xz
+            v = G._eval(op, v2, torch.float32, w16=r, x16=True)
+        else:
+            v = G._eval(op, val, torch.float32, w16=r, x16=bool(r))
+        if o in cut and op.name != "DEQUANTIZE":
+            if fault and fault[0] == o and callable(fault[1]):
+                v = fault[1](v)
+            elif half_storage and o != out:
+                v = v.half().float()
+            dev[o] = v.numpy().copy()
+        val[o] = v
+    return dev
+
+
+STAND_INS = [(model, "half storage") for model in MODELS] + [("deeplab-synthetic", "f16 operands"), ("deeplab-synthetic", "both")]
+
+
+@pytest.mark.parametrize("model,kind", STAND_INS, ids=["%s-%s" % (a, b.replace(" ", "_")) for a, b in STAND_INS])
+def test_the_reduced_precision_stand_ins_pass_at_half_the_bar(model, kind):
+    """Fairness of (a) and (b): with B32 HALVED (the "<= 4 of 8" of the f32 proof) no element of any stand-in is outside its interval, on the five inputs and both
+    cut sets; nothing overflows a half."""
+    if not os.path.exists(_path(model)):
+        pytest.fail("model fixture %s is missing" % _path(model))
+    half_storage, rounding = kind != "f16 operands", (_rule(model) if kind != "half storage" else {})
+    if kind != "half storage":
+        assert len(rounding) >= 30 and any(isinstance(s, tuple) for s in rounding.values()), "the rule names %d operators" % len(rounding)
+    for inp in INPUTS:
+        path, x, ot, exact, m, dev0 = _case(model, inp)
+        for cutname, cut in _cuts(m, dev0):
+            dev = _stand_in(m, x, cut, half_storage, rounding)
+            half = set(cut) - {m.outputs[0]} if half_storage else set()
+            rows = G.audit_reduced(path, x, dev, ot, half, rounding, exact, m, bar_scale=0.5)
+            outside = sum(r["outside"] for r in rows)
+            print("%-18s %-13s %-9s %-20s %3d tensors (%3d as halves), %d elements outside, largest allowance %.3g, largest magnitude %.4g" % (
+                model, kind, inp, cutname, len(rows), len(half), outside, max(r["allow"] for r in rows), max(r["scale"] for r in rows)))
+            assert len(rows) == len(cut) and all(r["finite"] for r in rows)
+            assert not G.failing_reduced(rows), "%s / %s / %s / %s\n%s" % (model, kind, inp, cutname, G.format_table_reduced(rows))
+
+
+def _trunc16(v):
+    h = v.half()
+    bits = torch.where(h.float().abs() > v.abs(), h.view(torch.int16) - 1, h.view(torch.int16))      # one half ulp toward zero where nearest-even went away from it
+    return bits.view(torch.float16).float()
+
+
+def _largest_channel(v):
+    return int(v.abs().reshape(-1, v.shape[-1]).max(0).values.argmax())
+
+
+def _scaled(v):
+    b = v.clone()
+    b[..., _largest_channel(v)] *= 1 + 2.0 ** -9
+    return b.half().float()
+
+
+def _swapped(v):
+    b = v.half().float().clone()
+    px = b[:, -1, -1]
+    c = int((px[0, 1:] - px[0, :-1]).abs().argmax())             # the adjacent pair of the last pixel that differs most
+    b[:, -1, -1, [c, c + 1]] = b[:, -1, -1, [c + 1, c]]
+    return b
+
+
+def _last_column(v):
+    b = v.half().float().clone()
+    b[:, :, -1] = b[:, :, -2]
+    return b
+
+
+FAULTS = {"truncation toward zero": _trunc16, "one channel scaled by 1 + 2^-9": _scaled, "two adjacent channels swapped at the last pixel": _swapped,
+          "last column from its inward neighbour": _last_column}
+
+
+@pytest.mark.parametrize("fault", list(FAULTS), ids=[re_id.replace(" ", "_").replace("^", "") for re_id in FAULTS])
+def test_a_storage_fault_in_one_cut_tensor_fails_there_and_nowhere_else(fault):
+    """Sharpness of (a), at the FULL bar: each storage fault, injected into one tensor of the sparse cut of lite on the noise network input, puts elements of that
+    tensor outside their interval and of no other tensor."""
+    path, x, ot, exact, m, dev0 = _case("lite", "noise tensor")
+    cut = _cuts(m, dev0)[1][1]
+    half = set(cut) - {m.outputs[0]}
+    clean = G.audit_reduced(path, x, _stand_in(m, x, cut, True, {}), ot, half, {}, exact, m)
+    assert not G.failing_reduced(clean)
+    spatial = [t for t in cut if t in half and dev0[t].ndim == 4 and min(dev0[t].shape[1:3]) >= 4][:4]
+    assert len(spatial) == 4
+    for t in spatial:
+        rows = G.audit_reduced(path, x, _stand_in(m, x, cut, True, {}, fault=(t, FAULTS[fault])), ot, half, {}, exact, m)
+        got = {r["t"]: r["outside"] for r in rows if r["outside"]}
+        print("lite t%-3d %-20s %-48s elements outside: %s" % (t, "x".join(map(str, dev0[t].shape)), fault, got))
+        assert set(got) == {t}, "%s in t%d: tensors with elements outside their interval: %s" % (fault, t, got)
+
+
+def test_a_dropped_k_slab_of_one_1x1_convolution_fails_there_and_nowhere_else():
+    """Sharpness of (b): the f16-operand stand-in of DeepLab with input channels 32..63 missing from ONE 1x1 convolution (one K slab of the GEMM) fails at that
+    convolution's output and at no other tensor — the allowance, 2^-11 of the absolute products, is far below one slab's contribution."""
+    model = "deeplab-synthetic"
+    path, x, ot, exact, m, dev0 = _case(model, "noise")
+    rounding = _rule(model)
+    cut = _cuts(m, dev0)[0][1]
+    prod = G.producers(m)
+    t = next(o for o in sorted(rounding) if rounding[o] is True and prod[o].opts["act"] == 0 and int(m.tensors[prod[o].inputs[1]].shape[3]) >= 96)
+    clean = G.audit_reduced(path, x, _stand_in(m, x, cut, False, rounding), ot, set(), rounding, exact, m)
+    assert not G.failing_reduced(clean)
+    rows = G.audit_reduced(path, x, _stand_in(m, x, cut, False, rounding, fault=(t, "slab")), ot, set(), rounding, exact, m)
+    got = {r["t"]: r["outside"] for r in rows if r["outside"]}
+    print("%s t%d (%s): elements outside: %s" % (model, t, "x".join(map(str, dev0[t].shape)), got))
+    assert set(got) == {t}

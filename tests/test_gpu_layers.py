@@ -58,22 +58,42 @@ def _case_id(c):
     return "%s-%s-%s" % (arch, "real" if real else "synthetic", re.sub(r"[^a-z0-9]+", "_", _paths(arch)[i][0].lower()).strip("_")[:40])
 
 
-def stored_by_plan(plan, n_file_tensors, n, f16_gemm):
+SEGMENT_STORES = r"^segment .* stores((?: t\d+(?::f16)?)+)$"
+
+
+def segment_stores(plan, width=None):
+    """the tensors the segment lines say their kernels store (width "f16": only those marked as packed halves, "t33:f16")"""
+    named = [t for mm in re.finditer(SEGMENT_STORES, plan, re.M) for t in mm.group(1).split()]
+    return {int(t[1:].split(":")[0]) for t in named if width is None or t.endswith(":" + width)}
+
+
+def half_by_plan(plan, n_file_tensors, n):
+    """The stored tensors the plan text marks as 16-bit storage for a batch of n: "hbm f16" on a P line of the frame program, "t33:f16" on a segment line, and — per-launch
+    path — the "f16 storage:" line of a fused expand + depthwise pair, which names the pixel count from which its output is stored as halves."""
+    half = {int(m.group(1)) for m in re.finditer(r"^P\d+ .* -> t(\d+) hbm f16$", plan, re.M)} | segment_stores(plan, "f16")
+    for m in re.finditer(r"^f16 storage: .* store t(\d+) \((\d+)x(\d+)x\d+ per frame\) as f16 at (\d+) pixels and more", plan, re.M):
+        if n * int(m.group(2)) * int(m.group(3)) >= int(m.group(4)):
+            half.add(int(m.group(1)))
+    return {t for t in half if t < n_file_tensors}
+
+
+def stored_by_plan(plan, n_file_tensors, n, f16_gemm, chained=None):
     """The file tensors the plan text says this path writes to HBM, the network output included, the network input not.
     per-launch path: every step's output, minus the interiors of the fused launches the text announces (fused head; expand + depthwise where the f16 GEMM
-    kernels run; the chain of three 1x1 convolutions from 8192 pixels up).  frame program: the outputs its P lines mark "hbm" (or "output"), plus — segmented — what
+    kernels run; the chain of three 1x1 convolutions from 8192 pixels up — chained: the split-f16 mode only, i.e. not under BSX_F16_GEMM=fast / fast16; default: as
+    f16_gemm).  frame program: the outputs its P lines mark "hbm" (or "output"), plus — segmented — what
     the segment lines store."""
     steps = [(int(m.group(1)), int(m.group(2)), int(m.group(3)), int(m.group(4))) for m in            # (index, OH, OW, output tensor)
              re.finditer(r"^\s*(\d+) \w+\s+\S.*?\s+in \d+x\d+x\d+ -> out (\d+)x(\d+)x\d+ .* t-?\d+->t(\d+)$", plan, re.M)]
     assert steps, "no step lines in the plan text"
     program_on = re.search(r"^frame program: ON", plan, re.M) is not None
+    chained = f16_gemm if chained is None else chained
     stored = set()
     if program_on:
-        for m in re.finditer(r"^P\d+ .* -> t(\d+) (lds|hbm|elided|output)$", plan, re.M):
+        for m in re.finditer(r"^P\d+ .* -> t(\d+) (lds|hbm|elided|output)(?: f16)?$", plan, re.M):
             if m.group(2) in ("hbm", "output"):
                 stored.add(int(m.group(1)))
-        for m in re.finditer(r"^segment .* stores((?: t\d+)+)$", plan, re.M):
-            stored |= {int(t[1:]) for t in m.group(1).split()}
+        stored |= segment_stores(plan)
         stored.add(steps[-1][3])
     else:
         out_of = {i: out for i, _, _, out in steps}
@@ -88,7 +108,7 @@ def stored_by_plan(plan, n_file_tensors, n, f16_gemm):
             if m and f16_gemm:
                 stored.discard(out_of[int(m.group(1)) - 1])
             m = re.search(r"\^ chained with steps (\d+) and (\d+) at 8192 pixels and more", line)
-            if m and f16_gemm and owner:
+            if m and chained and owner:
                 mid = int(owner.group(1))
                 if n * dims[mid][0] * dims[mid][1] >= 8192:
                     stored -= {out_of[int(m.group(1))], out_of[mid]}
@@ -173,7 +193,7 @@ def test_every_stored_tensor_against_float64(case, oracle, monkeypatch, debug_sw
                 problems.append("stream %d (%s): network output off by %.3g from float64, the oracle by %.3g: bar %.3g" % (i, names[i], out["acc"], out["acc_oracle"], out_bar))
         # ---- what the stored set must contain
         if program_on and "segment head" in plan:
-            named = {int(t[1:]) for mm in re.finditer(r"^segment .* stores((?: t\d+)+)$", plan, re.M) for t in mm.group(1).split()}
+            named = segment_stores(plan)
             assert {t for t in named if t < nt} | {t_out} <= expected and len(named) >= 5
         if pname == NO_FUSION:
             assert not program_on
