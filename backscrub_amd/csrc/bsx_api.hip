@@ -1955,6 +1955,7 @@ static const char* debug_tensor_unstored(const bsx_ctx* c, int t) {
   if (t == p.output) return c->last_net_logits ? nullptr : "the last network stage decoded inside its final kernel and wrote no logits";
   if (c->use_program) {
     if (p.seg.on && std::find(p.seg_stored.begin(), p.seg_stored.end(), t) != p.seg_stored.end()) return nullptr;
+    if (p.seg.on && std::find(p.seg_partials.begin(), p.seg_partials.end(), t) != p.seg_partials.end()) return nullptr;      // (synthetic: past the file's tensors)
     for (size_t i = 0; i < p.program.size() && i < p.program_out_tensor.size(); i++) {
       if (p.program_out_tensor[i] != t) continue;
       if (p.program[i].out.space == kLocLds) return "the frame program keeps it in LDS";

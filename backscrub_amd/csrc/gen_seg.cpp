@@ -56,6 +56,8 @@ std::string seg_constants_text(const SegPlan& sp, const char* pre) {
   gate("gate", K2.gate); conv("pw_a", K2.pw_a); conv("pw_b", K2.pw_b); dw("dw", K2.dw);
   P("  t.b0_off = %lldll; t.B_off = %lldll; t.c0_off = %lldll; t.part_B_off = %lldll; t.TR = %d; t.TC = %d; t.tiles_y = %d; t.tiles_x = %d; t.lds_floats = %d; t.rw = %d; t.m_ct = %uu;\n",
           K2.b0_off, K2.B_off, K2.c0_off, K2.part_B_off, K2.TR, K2.TC, K2.tiles_y, K2.tiles_x, K2.lds_floats, K2.rw, K2.m_ct);
+  P("  t.wst.form = %d; t.wst.off = %d; t.wst.floats = %d; t.wst.stride = %d; t.wst.buf_floats = %d; t.wst.bias_off = %d; t.wst.dw_off = %d; t.wst.dwb_off = %d;\n",
+          K2.wst.form, K2.wst.off, K2.wst.floats, K2.wst.stride, K2.wst.buf_floats, K2.wst.bias_off, K2.wst.dw_off, K2.wst.dwb_off);
   end(K2.dbg_skip);
   P("constexpr SegK3 %sK3 = [] { SegK3 t{};\n  t.H2 = %d; t.W2 = %d; t.HL = %d; t.WL = %d; t.half_pixel = %d; t.align_corners = %d;\n", pre, K3.H2, K3.W2, K3.HL, K3.WL, K3.half_pixel, K3.align_corners);
   conv("pw1", K3.pw1); conv("pw2", K3.pw2); dw("dw", K3.dw);

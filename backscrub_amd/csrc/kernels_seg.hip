@@ -163,10 +163,14 @@ __device__ __forceinline__ void load_wtile(float (&wr)[4], const float* __restri
 // trip stages the partial sums and both FC weight blocks in LDS (`stage`, <= kGateStageFloats floats, may alias a tile region that
 // is not live yet); everything after runs from LDS: a per-workgroup serial chain of dependent global loads here was most of the
 // first version's run time.
+// `publish` runs in front of the FIRST barrier, behind the requests of the prologue's own loads: LDS stores of the caller (k2's staged weights) that every later phase
+// may read, without a barrier of their own and without a memory round trip in front of the prologue's.
 constexpr int kGateStageFloats = kSegGateStageFloats;
-__device__ __forceinline__ void seg_gate(const SegGate& gt, const float* __restrict__ fa, const float* __restrict__ w, float* scr, float* stage) {
+struct NoPublish { __device__ __forceinline__ void operator()() const {} };
+template <class Publish = NoPublish>
+__device__ __forceinline__ void seg_gate(const SegGate& gt, const float* __restrict__ fa, const float* __restrict__ w, float* scr, float* stage, Publish publish = Publish()) {
   float* s_gate = scr + kScrGate;
-  if (gt.timing_skip) { if (threadIdx.x < 16) s_gate[threadIdx.x] = 0.5f; __syncthreads(); return; }      // upper bound of what hoisting the gate out could buy
+  if (gt.timing_skip) { if (threadIdx.x < 16) s_gate[threadIdx.x] = 0.5f; publish(); __syncthreads(); return; }      // upper bound of what hoisting the gate out could buy
   float* s_mean = scr + kScrGate + 16;
   float* s_hid = scr + kScrGate + 48;
   const int tid = threadIdx.x;
@@ -195,6 +199,7 @@ __device__ __forceinline__ void seg_gate(const SegGate& gt, const float* __restr
     if (tid < f1.Cout) b1[tid] = (w + f1.b_off)[(unsigned)tid];
     if (gt.n_fc == 2 && tid < f2.Cout) b2[tid] = (w + f2.b_off)[(unsigned)tid];
   }
+  publish();
   __syncthreads();
   const int Cm = gt.sum_parts ? 16 : 16 * gt.n_parts;
   if (tid < Cm) {
@@ -503,10 +508,10 @@ __global__ __launch_bounds__(kSegThreads) void seg_head_k(
 // The expanded tensor x (72 channels) exists only 16 channels at a time, in LDS.
 // ==================================================================================================================================
 #ifdef BSX_SEG_RTC
-extern "C" __global__ __launch_bounds__(kSegThreads) __attribute__((amdgpu_waves_per_eu(6, 6))) void bsx_seg_k2(
+extern "C" __global__ __launch_bounds__(kSegThreads) __attribute__((amdgpu_waves_per_eu(kSegK2Waves, kSegK2Waves))) void bsx_seg_k2(
 #else
 template <bool H16>
-__global__ __launch_bounds__(kSegThreads) __attribute__((amdgpu_waves_per_eu(6, 6))) void seg_k2_k(
+__global__ __launch_bounds__(kSegThreads) __attribute__((amdgpu_waves_per_eu(kSegK2Waves, kSegK2Waves))) void seg_k2_k(
 #endif
     const SegK2 d_rt, float* __restrict__ arena, long per_frame, const float* __restrict__ w, int n_frames) {
   BSX_SEG_D(SegK2, K2);
@@ -518,6 +523,11 @@ __global__ __launch_bounds__(kSegThreads) __attribute__((amdgpu_waves_per_eu(6, 
   float* fa = arena + (size_t)f * (size_t)per_frame;
   float* B_t = seg_smem + kScrFloats;                               // [BR][RW][16]
   float* x_t = B_t + BR * RW * 16;
+#ifdef BSX_SEG_RTC
+  // the staged weights lie behind both tiles and behind the gate's staging area, and end where the launch's dynamic LDS (lds_floats) ends
+  static_assert(d.wst.form == 0 || (d.wst.off >= kScrFloats + 2 * BR * RW * 16 && d.wst.off >= kScrFloats + kGateStageFloats && d.wst.off + d.wst.floats == d.lds_floats),
+                "k2: staged weights outside the planned LDS");
+#endif
   const float* b0_in = fa + d.b0_off;
   float* B_out = fa + d.B_off;
   float* c0_out = fa + d.c0_off;
@@ -537,11 +547,57 @@ __global__ __launch_bounds__(kSegThreads) __attribute__((amdgpu_waves_per_eu(6, 
       if (gy >= 0 && gy < d.H2 && gx >= 0 && gx < d.W2) b0v[j] = ldg4<H16>(b0_in, (unsigned)((gy * d.W2 + gx) * 16 + 4 * g));
     }
   }
-  seg_gate(d.gate, fa, w, seg_smem, B_t);
-  const float4 sv = ld4(seg_smem + kScrGate + 4 * g);
+  // ... and with them the weights the later phases need (SegStage, plan.cpp).  form >= 1: pw_a's tile + bias wait in registers across the gate, where the kernel is far
+  // below its register step, and pw_b's tile + bias of channel group 0 go to LDS; form 2: the depthwise weights + biases of all groups too — 16-byte pieces through
+  // registers, stored in front of the gate's first barrier.  The expand loop below then never waits for HBM / L2 in front of a use: it was one dependent round trip per
+  // channel group for the 1x1 tile (1-2 us each at this occupancy), one for the depthwise weights behind it, and one for pw_a behind the gate.  Same floats into the
+  // same instructions: bit-identical to form 0.
+  // (The graph-specialised build only: the ahead-of-time instance — descriptor as a kernel argument, what runs where hipRTC is unavailable — sits at 78 of its 80
+  // registers and spills 20-44 bytes with any staged form, whose LDS addresses it cannot fold into instruction offsets; it reads its weights from global memory
+  // whatever the plan's form and leaves the block unused.)
+#ifdef BSX_SEG_RTC
+  constexpr SegStage st = d.wst;
+#else
+  const SegStage st{};
+#endif
+  float* sw = seg_smem + st.off;
+  // one group's pw_b tile + bias as 68 pieces: lanes 0..63 = (row tid & 15, columns 4 * (tid >> 4) ..), lanes 64..67 the bias
+  auto pwb_fetch = [&](int grp) {
+    float4 v = f4zero();
+    if (tid < 64) v = ld4(w + d.pw_b.w_off + (unsigned)((tid & 15) * d.pw_b.cout_pad + 16 * grp + 4 * (tid >> 4)));
+    else if (tid < 68) v = ld4(w + d.pw_b.b_off + 16 * grp + 4 * (tid - 64));
+    return v;
+  };
+  auto pwb_store = [&](int buf, float4 v) {
+    float* dst = sw + buf * st.buf_floats;
+    if (tid < 64) st4(dst + (tid & 15) * st.stride + 4 * (tid >> 4), v);
+    else if (tid < 68) st4(dst + st.bias_off + 4 * (tid - 64), v);
+  };
   float wr[4];
-  load_wtile(wr, w, d.pw_a, 0, li, g);
-  const float4 bias_a = ld4(w + d.pw_a.b_off + cq4);
+  float4 bias_a, sf[3];
+  if (st.form >= 1) {
+    load_wtile(wr, w, d.pw_a, 0, li, g);
+    bias_a = ld4(w + d.pw_a.b_off + cq4);
+    sf[0] = pwb_fetch(0);
+    if (st.form >= 2) {
+      if (4 * tid < 9 * d.dw.C) sf[1] = ld4(w + d.dw.w_off + 4 * tid);
+      if (4 * tid < d.dw.C) sf[2] = ld4(w + d.dw.b_off + 4 * tid);
+    }
+  }
+  seg_gate(d.gate, fa, w, seg_smem, B_t, [&] {
+    if (st.form >= 1) {
+      pwb_store(0, sf[0]);
+      if (st.form >= 2) {
+        if (4 * tid < 9 * d.dw.C) st4(sw + st.dw_off + 4 * tid, sf[1]);
+        if (4 * tid < d.dw.C) st4(sw + st.dwb_off + 4 * tid, sf[2]);
+      }
+    }
+  });
+  const float4 sv = ld4(seg_smem + kScrGate + 4 * g);
+  if (st.form == 0) {
+    load_wtile(wr, w, d.pw_a, 0, li, g);
+    bias_a = ld4(w + d.pw_a.b_off + cq4);
+  }
   const Clamp cl_a = clamp_of(d.pw_a.act), cl_b = clamp_of(d.pw_b.act), cl_dw = clamp_of(d.dw.act);
 
   // 1. B on the region the depthwise needs
@@ -577,8 +633,17 @@ __global__ __launch_bounds__(kSegThreads) __attribute__((amdgpu_waves_per_eu(6, 
   const int C = d.dw.C, ngrp = (C + 15) >> 4, quad = lane & 3, px = lane >> 2;
   const int cox[3] = {col_b(2 * px, quad, RW >> 1), col_b(2 * px + 1, quad, RW >> 1), col_b(2 * px + 2, quad, RW >> 1)};   // x_t: de-interleaved columns (swz_b)
   for (int grp = 0; grp < ngrp && !(d.dbg_skip & 2); grp++) {
-    load_wtile(wr, w, d.pw_b, 16 * grp, li, g);
-    const float4 bias_b = ld4(w + d.pw_b.b_off + 16 * grp + cq4);
+    float4 bias_b, nxt;
+    if (st.form >= 1) {                                             // staged rows: stride = 4 (mod 8), conflict-free (tests/test_k2_staging.py)
+      const float* tb = sw + (grp & 1) * st.buf_floats;
+#pragma unroll
+      for (int r = 0; r < 4; r++) wr[r] = tb[(4 * g + r) * st.stride + li];
+      bias_b = ld4(tb + st.bias_off + cq4);
+      if (grp + 1 < ngrp) nxt = pwb_fetch(grp + 1);                 // lands during this group's work; stored in front of the group's last barrier
+    } else {
+      load_wtile(wr, w, d.pw_b, 16 * grp, li, g);
+      bias_b = ld4(w + d.pw_b.b_off + 16 * grp + cq4);
+    }
     for (int t = wave; t < ntile; t += 4) {
       const RowTile rt = row_tile(t, ctiles, d.m_ct);
       // (columns >= BC of the row hold nothing: their lanes feed MFMA columns whose results are dropped below — a column of D depends on the same column of B only)
@@ -594,10 +659,14 @@ __global__ __launch_bounds__(kSegThreads) __attribute__((amdgpu_waves_per_eu(6, 
     const int ch = 16 * grp + 4 * quad;
     f4v wd[9];
     f4v bias_d = {0.f, 0.f, 0.f, 0.f};
-    if (ch < C) {
+    if (ch < C && st.form < 2) {
 #pragma unroll
       for (int k = 0; k < 9; k++) wd[k] = ldv(w + d.dw.w_off + (unsigned)(k * C + ch));
       bias_d = ldv(w + d.dw.b_off + ch);
+    } else if (ch < C) {
+#pragma unroll
+      for (int k = 0; k < 9; k++) wd[k] = ldv(sw + st.dw_off + k * C + ch);
+      bias_d = ldv(sw + st.dwb_off + ch);
     }
     __syncthreads();
     if (ch < C && px < d.TC && c0 + px < d.W3)
@@ -605,6 +674,7 @@ __global__ __launch_bounds__(kSegThreads) __attribute__((amdgpu_waves_per_eu(6, 
         const float4 v = clamp4(tof4(dw3x3(x_t, RW * 16, 2 * py, cox, wd) + bias_d), cl_dw);
         stg4<H16>(c0_out, (unsigned)(((r0 + py) * d.W3 + c0 + px) * C + ch), v);
       }
+    if (st.form >= 1 && grp + 1 < ngrp) pwb_store((grp + 1) & 1, nxt);        // (that buffer was last read a group ago: two barriers back)
     __syncthreads();
   }
 }

@@ -695,7 +695,11 @@ static bool build_segments(Graph& g, Plan* plan) {
   k2.H2 = hdw.OH; k2.W2 = hdw.OW; k2.H3 = kdw.OH; k2.W3 = kdw.OW; k2.dw_pt = kdw.pad_t; k2.dw_pl = kdw.pad_l;
   k2.pw_a = conv_w(pwa); k2.pw_b = conv_w(pwb); k2.dw = dw_w(kdw);
   split(k2.H3, tgt[2], &k2.TR, &k2.tiles_y); split(k2.W3, tgt[3], &k2.TC, &k2.tiles_x);
+  // the 1x1 expand's weights staged in LDS behind the tiles, where that keeps the workgroups per CU (BSX_K2_GLOBAL_W=1, debug build: never — the A/B and the
+  // bit-identity reference of tests/test_gpu_k2_staging.py; BSX_K2_LDS_CAP=<bytes>: the LDS a CU is taken to have, e.g. to force form 2 at one workgroup fewer)
   k2.lds_floats = seg_k2_lds_floats(k2);
+  k2.wst = seg_k2_stage(k2, k2.lds_floats, dbg_env_int(BSX_DBG_ENV("BSX_K2_LDS_CAP"), 160 * 1024), BSX_DBG_ENV("BSX_K2_GLOBAL_W") ? 0 : 2);
+  k2.lds_floats += k2.wst.floats;
   k2.rw = seg_row_width(2 * k2.TC + 1); k2.m_ct = (65536u + (unsigned)(k2.rw / 16) - 1) / (unsigned)(k2.rw / 16);
   if (k2.TC > 15 || ((2 * k2.TR + 1) * (k2.rw / 16) + 3) / 4 > 6) return seg_fail(31);
   SegK3& k3 = sp.k3;
@@ -731,6 +735,7 @@ static bool build_segments(Graph& g, Plan* plan) {
   for (int t : {hpw.out, g1.out, f1a.out, f1b.out, pwb.out, up2, kg.out, kf1.out, kp1.out, kd.out, up, tg.out, tf1.out, tf2.out, tpw.out, tdw.out})
     if (t != g.output) plan->tensor_off[t] = -1;
   plan->arena_floats_per_stream = top;
+  plan->seg_partials = {pA, pb0, pB, plo};
   plan->seg_stored = {A, b0, B, c0, lo};             // written by head, head, k2, k2, k3 (lo2 and the level-2 gate are outputs of the middle program)
 
   h.a_off = plan->tensor_off[A]; h.b0_off = plan->tensor_off[b0]; h.part_a_off = plan->tensor_off[pA]; h.part_b0_off = plan->tensor_off[pb0];
@@ -775,17 +780,22 @@ static bool build_segments(Graph& g, Plan* plan) {
     if (FILE* f = fopen(path, "w")) { fputs(seg_constants_text(sp, "kProbe").c_str(), f); fclose(f); }
   }
 #endif
-  char line[256];
+  char line[256], k2_note[64] = "";
   plan->seg_text.clear();
   // (the tensors a segment leaves in the arena: what crosses into the next kernel — the read-back entry serves these and nothing else of a segment)
   auto add = [&](const char* name, int TR, int TC, int ty, int tx, int lds, std::initializer_list<int> stores) {
-    snprintf(line, sizeof line, "segment %-5s tile %dx%d, %dx%d tiles per frame, LDS %.1f KiB, stores", name, TR, TC, ty, tx, lds / 256.0);
+    snprintf(line, sizeof line, "segment %-5s tile %dx%d, %dx%d tiles per frame, LDS %.1f KiB%s, stores", name, TR, TC, ty, tx, lds / 256.0, k2_note);
     plan->seg_text += line;
     for (int t : stores) plan->seg_text += " t" + std::to_string(t);
     plan->seg_text += stores.size() ? "\n" : " the network output\n";
   };
-  add("head", h.TR, h.TC, h.tiles_y, h.tiles_x, h.lds_floats, {A, b0}); add("k2", k2.TR, k2.TC, k2.tiles_y, k2.tiles_x, k2.lds_floats, {B, c0});
+  add("head", h.TR, h.TC, h.tiles_y, h.tiles_x, h.lds_floats, {A, b0});
+  snprintf(k2_note, sizeof k2_note, " (weights staged: form %d, %d B)", k2.wst.form, k2.wst.floats * 4);
+  add("k2", k2.TR, k2.TC, k2.tiles_y, k2.tiles_x, k2.lds_floats, {B, c0});
+  k2_note[0] = 0;
   add("k3", k3.TR, k3.TC, k3.tiles_y, k3.tiles_x, k3.lds_floats, {lo}); add("tail", tl.TR, tl.TC, tl.tiles_y, tl.tiles_x, tl.lds_floats, {});
+  snprintf(line, sizeof line, "segment partial sums ([tiles][16] f32): A t%d, b0 t%d, B t%d, lo t%d\n", pA, pb0, pB, plo);
+  plan->seg_text += line;
   return true;
 }
 

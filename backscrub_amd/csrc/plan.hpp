@@ -151,6 +151,7 @@ struct Plan {
   long program_arena_bytes = 0;         // arena (HBM / L2) bytes one frame's program touches: every use of an operand that is not LDS-resident
   std::string seg_text;                 // one line per segment kernel (tiles, LDS, the tensors it stores in the arena) for bsx_plan_describe
   std::vector<int> seg_stored;          // graph tensors a segment kernel writes to the arena (the boundary tensors; everything else in a segment lives in LDS / registers)
+  std::vector<int> seg_partials;        // the synthetic tensors of the pooled partial sums the segment kernels exchange ([tiles][16] f32 of A, b0, B, lo): readable like the stored tensors
   std::string describe() const;
 };
 

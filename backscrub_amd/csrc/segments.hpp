@@ -41,6 +41,7 @@ struct SegGate {                                                                
 };
 
 constexpr int kSegThreads = 256;
+constexpr int kSegK2Waves = 6;      // k2's waves per SIMD (80 registers: its amdgpu_waves_per_eu) = workgroups per CU, one wave of each on every SIMD
 constexpr int kSegMaxC = 16;        // channel count of every tensor at the segment boundaries (A, b0, B, lo2, lo)
 
 struct SegHead {
@@ -56,6 +57,14 @@ struct SegHead {
   unsigned m_ct = 0;                                      // ceil(65536 / (rw / 16))
 };
 
+// k2's weights in LDS (seg_k2_k): the expand loop then reads them at LDS latency instead of waiting for a global round trip per channel group.
+//   form 0: nothing staged;
+//   form 1: pw_b's [16][16] tile + bias of ONE channel group at a time, double-buffered: group 0's with the kernel's first loads, group g + 1's requested when group g
+//           starts (one 16-byte piece in 68 lanes: 4 registers) and stored behind its depthwise;
+//   form 2: form 1 + the whole depthwise block ([9][C] weights + [C] bias), copied once with the kernel's first loads.
+// Layout from `off` (floats in seg_smem, behind x_t): tile buffer b at b * buf_floats (rows at k * stride, bias at bias_off), depthwise weights at dw_off, bias at dwb_off.
+struct SegStage { int form = 0, off = 0, floats = 0, stride = 0, buf_floats = 0, bias_off = 0, dw_off = 0, dwb_off = 0; };
+
 struct SegK2 {
   int H2 = 0, W2 = 0, H3 = 0, W3 = 0;                     // b0 / B resolution, c0 resolution
   int dw_pt = 0, dw_pl = 0;
@@ -68,6 +77,7 @@ struct SegK2 {
   int dbg_skip = 0;                                       // BSX_SEG_SKIP (timing experiments, results invalid): bit mask of phases this kernel skips
   int rw = 0;                                             // LDS row width of the B region: 16 * ceil((2TC+1) / 16)
   unsigned m_ct = 0;
+  SegStage wst;                                           // staged weights (plan.cpp: seg_k2_stage); lds_floats includes wst.floats
 };
 
 struct SegK3 {
@@ -114,6 +124,33 @@ inline int seg_head_lds_floats(const SegHead& d) {
   return (win > 512 ? win : 512) + AR * AC * 16;                           // + x = act(pw(stem)) (the stem output itself stays in registers: seg_head_k)
 }
 inline int seg_k2_lds_floats(const SegK2& d) { const int v = 2 * (2 * d.TR + 1) * seg_row_width(2 * d.TC + 1) * 16; return kSegScratchFloats + (v > kSegGateStageFloats ? v : kSegGateStageFloats); }
+// ---- k2's staged weights --------------------------------------------------------------------------------------------------------------------------------------
+// Row stride of a staged pw_b tile: the lanes of one ds_read_b32 (two groups of 32: channel-row groups g = 0, 1 and g = 2, 3; lane (li, g) reads row 4g + r,
+// column li) must fall on 32 distinct banks, i.e. four rows further must be 16 banks further: stride = 4 (mod 8).  A dense tile (16) or the weights' own row
+// length (cout_pad, a multiple of 16) puts all four row groups on the same 16 banks.
+constexpr int kSegStageStride = 20;
+inline int seg_k2_wgs_per_cu(int lds_floats, int lds_cap_bytes) { const int by_lds = lds_cap_bytes / (lds_floats * 4); return by_lds < kSegK2Waves ? by_lds : kSegK2Waves; }
+// The largest form whose LDS keeps as many workgroups on a CU (lds_cap_bytes of LDS; at most kSegK2Waves by the kernel's registers) as form 0 does; `base_floats` =
+// seg_k2_lds_floats, the block goes behind it.  max_form caps the choice (the debug build's switch).  The copies move 16-byte pieces, at most one per lane and part.
+inline SegStage seg_k2_stage(const SegK2& d, int base_floats, int lds_cap_bytes, int max_form) {
+  SegStage best;
+  const int wgs0 = seg_k2_wgs_per_cu(base_floats, lds_cap_bytes);
+  const int ncol = (d.dw.C + 15) / 16 * 16, C = d.dw.C;
+  const bool ok1 = ncol <= d.pw_b.cout_pad && d.pw_b.Cin == 16 && d.pw_b.w_off % 4 == 0 && d.pw_b.b_off % 4 == 0 && d.pw_b.cout_pad % 4 == 0;
+  const bool ok2 = ok1 && C % 4 == 0 && 9 * C / 4 <= kSegThreads && d.dw.w_off % 4 == 0 && d.dw.b_off % 4 == 0;
+  for (int form = 1; form <= 2 && form <= max_form; form++) {
+    if (!(form == 1 ? ok1 : ok2)) break;
+    SegStage s;
+    s.form = form; s.off = base_floats; s.stride = kSegStageStride;
+    s.bias_off = 16 * s.stride;
+    s.buf_floats = s.bias_off + 16;
+    s.floats = 2 * s.buf_floats;
+    if (form == 2) { s.dw_off = s.floats; s.dwb_off = s.dw_off + 9 * C; s.floats = s.dwb_off + C; }
+    if (wgs0 < 1 || seg_k2_wgs_per_cu(base_floats + s.floats, lds_cap_bytes) != wgs0) break;
+    best = s;
+  }
+  return best;
+}
 // The staged window of the low-resolution tensor a k3 / tail tile interpolates from ([LR][LC][20] floats) was reserved at its worst case (12 x 16 pixels = 15 KB) for
 // every geometry; a 2x up-sampling tile of 16 x 14 pixels reads 10 x 9.  The planner now walks the tiles of the actual geometry with the kernels' own index
 // arithmetic (up_axis, TFLite's clamping) and reserves the largest window + one row and one column of margin: k3 43.5 -> 33 KB (4 workgroups per CU instead
