@@ -545,15 +545,19 @@ int run_mask(bsx_ctx* c, int n, hipStream_t s, int slot = 0, const int* ids = nu
                                       (masks ? masks : c->d_masks) + (size_t)slot * c->width * c->height, c->width, c->height, c->roi, n, s, ids));
   return BSX_OK;
 }
-// prep → [onprep] → network → [oninfer] → decode (unless the network decodes) for n frames whose state lives in slots [slot, slot + n) — or, with ids
-// (device, slot = 0), in slots ids[0..n).  yuyv_in: YUYV frames (only where prep_yuyv_fusable).  t: bsx_profile_batch's timer (launches only, no callbacks).
-int enqueue_masks(bsx_ctx* c, const uint8_t* d_frames, int n, hipStream_t s, bool yuyv_in, int slot, const int* ids, LaunchTimer* t = nullptr) {
-  if (const int rc = run_prep(c, d_frames, n, s, false, yuyv_in, t)) return rc;
+// what follows prep, whichever launch did it: [onprep] → network → [oninfer] → decode (unless the network decodes) for n frames whose state lives in slots
+// [slot, slot + n) — or, with ids (device, slot = 0), in slots ids[0..n).  t: bsx_profile_batch's timer (launches only, no callbacks).
+int infer_after_prep(bsx_ctx* c, int n, hipStream_t s, int slot, const int* ids, LaunchTimer* t = nullptr) {
   if (c->onprep && !t) { BSX_HIP(c, hipStreamSynchronize(s)); c->onprep(c->caller_ctx); }   // :303
   const bool fused_decode = infer_decodes(c);
   if (const int rc = run_infer(c, n, s, !fused_decode, slot, ids, t)) return rc;
   if (c->oninfer && !t) { BSX_HIP(c, hipStreamSynchronize(s)); c->oninfer(c->caller_ctx); } // :311
   return fused_decode ? BSX_OK : run_decode(c, n, s, slot, ids, t);
+}
+// prep, then the above.  yuyv_in: YUYV frames (only where prep_yuyv_fusable).
+int enqueue_masks(bsx_ctx* c, const uint8_t* d_frames, int n, hipStream_t s, bool yuyv_in, int slot, const int* ids, LaunchTimer* t = nullptr) {
+  if (const int rc = run_prep(c, d_frames, n, s, false, yuyv_in, t)) return rc;
+  return infer_after_prep(c, n, s, slot, ids, t);
 }
 // bs_maskgen_process: the masks of n frames into the persistent masks of their slots
 // masks: where the full-resolution masks go instead of the persistent ones (run_composite's BSX_STEP_NO_MASK form)
@@ -1141,11 +1145,7 @@ int geoms_run(bsx_ctx* c, const int* ids, const bsx_geom_item* items, int n, hip
     float* f32 = !c->in_u8 ? c->tensor_ptr(c->plan.input) : nullptr;
     BSX_HIP(c, launch_prep_geoms(c->d_geom_classes, dd, prep, f32, c->in_u8 ? c->d_net_in_u8 : nullptr, c->inW, c->inH, c->bilateral, n, s));
   }
-  if (c->onprep) { BSX_HIP(c, hipStreamSynchronize(s)); c->onprep(c->caller_ctx); }
-  const bool fused_decode = infer_decodes(c);
-  if (const int rc = run_infer(c, n, s, !fused_decode, 0, d_ids)) return rc;
-  if (c->oninfer) { BSX_HIP(c, hipStreamSynchronize(s)); c->oninfer(c->caller_ctx); }
-  if (!fused_decode) { if (const int rc = run_decode(c, n, s, 0, d_ids)) return rc; }
+  if (const int rc = infer_after_prep(c, n, s, 0, d_ids)) return rc;
   bsx_roctx::Range range("bsx:mask+blend");
   BSX_HIP(c, launch_mask_blend_geoms(c->d_geom_classes, dd, tiles, xcd_mask, outside, c->d_ofinal, c->outW, c->outH, c->d_geom_tile_class, n, s, (int)flags));
   return BSX_OK;

@@ -103,6 +103,20 @@ hipError_t launch_tile_class(const uint8_t* ofinal, int outW, int outH, const Re
                              const int* slot_of = nullptr);
 
 struct Rect4 { int x, y, w, h; };
+inline bool roi_is_frame(int W, int H, const Rect4& roi) { return roi.x == 0 && roi.y == 0 && roi.w == W && roi.h == H; }      // nothing outside the ROI to fill
+
+// ---- launch rule of the kernels whose workgroups are the tiles of n independent frames (mfma_tile.hpp: xcd_frame_tile), one statement for every launcher ----
+// BSX_XCD_TILES (debug build, A/B timing; read once per process): 0 = plain frame-major workgroup order everywhere; 2 = the one-XCD-per-frame order also where it
+// measured slower (the fused DeepLab head's bands); unset = 1.
+int xcd_tiles_mode();
+inline int xcd_frames(int n) { return xcd_tiles_mode() ? n : 0; }      // the kernels' n_frames argument: 0 tells xcd_frame_tile to keep the plain order
+// The mask tile launches (mask_tile_k, mask_upscale_blur_k) of n frames: tiles per ROI row / column, the flat grid and nf, the kernels' n_frames argument.
+struct MaskTileGrid {
+  int ntx, nty, nf;
+  bool ok;                       // false: 2^31 workgroups or more — the launcher refuses
+  dim3 grid(int rows, int n) const { return dim3((unsigned)(ntx * rows) * (unsigned)n); }      // `rows` of the nty tile rows of each frame
+};
+MaskTileGrid mask_tile_grid(int W, const Rect4& roi, int n);
 
 struct BilateralParams {
   float space_w[13];

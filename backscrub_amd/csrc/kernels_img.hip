@@ -576,6 +576,8 @@ __global__ __launch_bounds__(kThreads) void mask_upscale_blur_k(const uint8_t* _
 // lane's table entries and its composite operands are all requested back to back.  Steps 2-5 then run from LDS only.
 // Used when the host verified that every tile's source block fits (ResizeTab::tile_ok); other cases take the kernel above.
 constexpr int kSrcBlockBytes = kHH * kHW;        // the raw block lives in `up` until step 3 overwrites it
+// a tile's class byte (tile_class_k), read through the aligned word that holds it: a SCALAR load (uniform address), not a vector load + readfirstlane
+__device__ __forceinline__ int tile_class_byte(uintptr_t ca) { return (int)((*reinterpret_cast<const uint32_t*>(ca & ~(uintptr_t)3) >> (8 * (unsigned)(ca & 3))) & 255u); }
 // F0: the launch has no flag set (no YUYV out, no flip, mask stored, default load order) — the default step.  A template parameter like YIN because this kernel pays
 // for every wave-uniform branch it carries: with the YUYV-in conversion behind a run-time flag the BGR step's launch was 12-15 % slower (profiles/r06l: 105-111 ->
 // 94-97 us at configs[1], 1064-1114 -> 946-955 us at the configs[4] slice), code that never ran.
@@ -621,10 +623,7 @@ __global__ __launch_bounds__(kThreads) void mask_tile_k(const uint8_t* __restric
   constexpr bool yin = YIN;                                                                         // BSX_STEP_YUYV_IN
   TileBlendOperands ops;
   if (early_bg) tile_load_blend_operands<BLEND, WH>(ops, bg, bg_stride, frames, n, W, H, roi, tx0, ty0, tid, 0, 1, yin);
-  if (tab.tile_class) {                                     // the aligned word that holds the byte: a SCALAR load (uniform address), not a vector load + readfirstlane
-    const uintptr_t ca = (uintptr_t)tab.tile_class + (size_t)n * (size_t)(ntx * nty_all) + (size_t)(tby * ntx + tbx);
-    uniform = (int)((*reinterpret_cast<const uint32_t*>(ca & ~(uintptr_t)3) >> (8 * (unsigned)(ca & 3))) & 255u);
-  }
+  if (tab.tile_class) uniform = tile_class_byte((uintptr_t)tab.tile_class + (size_t)n * (size_t)(ntx * nty_all) + (size_t)(tby * ntx + tbx));
   int sel = -1;                                             // MIX: 2 = the filter is off — the mask is formed as always, the composite is the frame
   if constexpr (MIX) {
     unsigned fl;
@@ -641,60 +640,13 @@ __global__ __launch_bounds__(kThreads) void mask_tile_k(const uint8_t* __restric
     tile_vsum5_store<BLEND, WH, MIX>(hq_hs, mask, outp, ops, n, ms, W, H, roi, tx0, ty0, tid, yuyv, uniform, sel);
     return;
   }
-  // extents of the source block: xofs / yofs are monotonic, so the extreme destination rows / columns give them
-  // (requesting these four scalar table reads together with the class byte — one scalar round trip instead of two in front of the general path — measured: no
-  //  difference on any configuration, profiles/r05e)
-  const int gy_lo = max(ty0 - 2, 0), gy_hi = min(ty0 + kTH + 1, roi.h - 1);
-  const int gx_lo = max(tx0 - 2, 0), gx_hi = min(tx0 + kTW + 1, roi.w - 1);
-  const int smin = min(max(tab.yofs[gy_lo], 0), tab.sh - 1), smax = min(max(tab.yofs[gy_hi] + 1, 0), tab.sh - 1);
-  const int cmin = tab.xofs[gx_lo], cmax = min(tab.xofs[gx_hi] + 1, tab.sw - 1);
-  const int nsr = smax - smin + 1, ncol = cmax - cmin + 1;
-  const int ms = slot_of ? slot_of[n] : n;
-  const uint8_t* const base = ofinal + (long)ms * outW * outH + (long)(q.y + smin) * outW + q.x + cmin;
-  // (a) raw block: 12 rows x 64 columns in three loads per lane cover the usual 5x up-scale; anything larger loops below
-  uint32_t raw[3];
-  const int br = tid >> 6, bc = tid & 63;
-#pragma unroll
-  for (int j = 0; j < 3; j++) { raw[j] = 0; if (br + 4 * j < nsr && bc < ncol) raw[j] = base[(unsigned)((br + 4 * j) * outW + bc)]; }
-  // (b) this lane's table entries
-  int t_s = 0, t_a0 = 0, t_a1 = 0;
-  if (tid < kHW) {
-    const int gx = reflect101(min(tx0 + tid - 2, roi.w + 1), roi.w);
-    t_s = tab.xofs[gx]; t_a0 = tab.xa[2 * gx]; t_a1 = tab.xa[2 * gx + 1];
-  } else if (tid >= 192 && tid < 192 + kHH) {
-    const int gy = reflect101(min(ty0 + (tid - 192) - 2, roi.h + 1), roi.h);
-    t_s = tab.yofs[gy]; t_a0 = tab.ya[2 * gy]; t_a1 = tab.ya[2 * gy + 1];
-  }
-  // (c) composite operands (the shared background is already on its way)
-  tile_load_blend_operands<BLEND, WH, MIX>(ops, bg, bg_stride, frames, n, W, H, roi, tx0, ty0, tid, 0, early_bg ? 2 : 3, yin, sel);
-  // 1. block and tables into LDS
-#pragma unroll
-  for (int j = 0; j < 3; j++) if (br + 4 * j < nsr && bc < ncol) blk[(br + 4 * j) * ncol + bc] = (uint8_t)raw[j];
-  if (nsr > 12 || ncol > 64)
-    for (int r = br; r < nsr; r += 4)
-      for (int cc = bc; cc < ncol; cc += 64)
-        if (r >= 12 || cc >= 64) blk[r * ncol + cc] = base[(unsigned)(r * outW + cc)];
-  if (tid < kHW) {
-    col_c0[tid] = (short)(t_s - cmin); col_c1[tid] = (short)(min(t_s + 1, tab.sw - 1) - cmin);
-    col_a0[tid] = (short)t_a0; col_a1[tid] = (short)t_a1;
-  } else if (tid >= 192 && tid < 192 + kHH) {
-    const int r = tid - 192;
-    row_r0[r] = (short)(min(max(t_s, 0), tab.sh - 1) - smin); row_r1[r] = (short)(min(max(t_s + 1, 0), tab.sh - 1) - smin);
-    row_b0[r] = (short)t_a0; row_b1[r] = (short)t_a1;
-  }
-  __syncthreads();
-  // 2. horizontal pass of the block rows: hq[r][x] = (S0*a0 + S1*a1) >> 4, all 132 columns, k = r * 132 + x walks without a division
-  for (int r = tid / kHW, x = tid % kHW; r < nsr;) {
-    hq[r * kHW + x] = (uint16_t)((blk[r * ncol + col_c0[x]] * col_a0[x] + blk[r * ncol + col_c1[x]] * col_a1[x]) >> 4);
-    x += kThreads % kHW; r += kThreads / kHW;
-    if (x >= kHW) { x -= kHW; r++; }
-  }
-  __syncthreads();
-  tile_vertical_pass(hq, up, row_r0, row_r1, 0, row_b0, row_b1, tid);                             // 3.
-  __syncthreads();
-  tile_hsum5(up, hs, tid);                                                                       // 4.
-  __syncthreads();
-  tile_vsum5_store<BLEND, WH, MIX>(hs, mask, outp, ops, n, ms, W, H, roi, tx0, ty0, tid, yuyv, 0, sel);   // 5.
+#define BSX_MT_FRAME n                                   /* the general path: steps (a)-(c) and 1-5, shared with mask_tile_geoms_k */
+#define BSX_MT_SLOT (slot_of ? slot_of[n] : n)
+#define BSX_MT_MASK_SLOT ms
+#include "mask_tile.inc"
+#undef BSX_MT_FRAME
+#undef BSX_MT_SLOT
+#undef BSX_MT_MASK_SLOT
 }
 
 // ---- alpha blend (deepseg.cc:108-134), stand-alone: bsx_composite_batch ---------------------------------------------------------------
@@ -1097,6 +1049,30 @@ __global__ __launch_bounds__(kThreads) void vg_mixed_k(const uint8_t* __restrict
 
 }  // namespace
 
+// ---- the launch rule shared by the launchers below (kernels.hpp) ----
+int xcd_tiles_mode() {
+  static const int mode = dbg_env_int(BSX_DBG_ENV("BSX_XCD_TILES"), 1);
+  return mode;
+}
+
+MaskTileGrid mask_tile_grid(int W, const Rect4& roi, int n) {
+  MaskTileGrid g;
+  g.ntx = (roi.w + kTW - 1) / kTW; g.nty = (roi.h + kTH - 1) / kTH;
+  g.ok = (unsigned long long)g.ntx * g.nty * (unsigned long long)n < (1ull << 31);
+  // one-XCD-per-frame order only where neighbouring tiles SHARE cache lines, i.e. the ROI's rows do not start on a 128-byte line (roi.x = 80 / 280: measured
+  // mask+blend 0.480 -> 0.464 ms at 256 HD MLKit streams); on line-aligned geometries nothing is shared and the plain order measured 2-3 % faster (profiles/r03o)
+  const bool shared_lines = ((roi.x * 3) & 127) != 0 || ((W * 3) & 127) != 0;
+  g.nf = shared_lines ? xcd_frames(n) : 0;
+  return g;
+}
+
+// the debug build's A/B switches of the tile kernels as bits of their flag word (each launcher applies the bits its kernels read): bit 6 (BSX_NO_EARLY_BG) = request a
+// shared background only after the tile's class is known (rounds 1-4), bit 7 (BSX_TILE_PLAIN_STORES) = the composite leaves with plain instead of nontemporal stores
+static int tile_debug_bits() {
+  static const int bits = (BSX_DBG_ENV("BSX_NO_EARLY_BG") ? 64 : 0) | (BSX_DBG_ENV("BSX_TILE_PLAIN_STORES") ? 128 : 0);
+  return bits;
+}
+
 // resize + bilateral in one launch (prep_fused_k); input (f32 [n][inH][inW][3]) and / or input_u8 (R|G<<8|B<<16 [n][inH][inW]): whichever is non-null is written
 bool prep_yuyv_fusable(int W, Rect4 roi, const ResizeTab& tab) {      // the YIN form of prep_fused_k: INTER_LINEAR proper, whole macropixels, an 8-byte window inside the row
   return tab.mode == 0 && (W & 1) == 0 && (roi.x & 1) == 0 && (W - roi.x) * 2 >= 8;
@@ -1108,7 +1084,6 @@ hipError_t launch_prep_fused(const uint8_t* frames, int W, int H, Rect4 roi, flo
   if (yuyv_in && !prep_yuyv_fusable(W, roi, tab)) return hipErrorInvalidValue;      // (the caller converts the frames first: bsx_api.hip step_impl)
   const int ntx = (inW + 31) / 32, nty = (inH + 31) / 32, TW = (inW + ntx - 1) / ntx, TH = (inH + nty - 1) / nty;      // even tiles, <= 32 x 32
   const long per_frame = (long)inW * inH;
-  static const bool xcd_on = !(BSX_DBG_ENV("BSX_XCD_TILES") && atoi(BSX_DBG_ENV("BSX_XCD_TILES")) == 0);      // A/B timing: 0 = plain frame-major workgroup order
   const int chunk = 1 << 20;                                            // frames per launch: keeps the 1-D grid far below 2^31 workgroups
   for (int n0 = 0; n0 < n; n0 += chunk) {
     const int nn = n - n0 < chunk ? n - n0 : chunk;
@@ -1116,8 +1091,8 @@ hipError_t launch_prep_fused(const uint8_t* frames, int W, int H, Rect4 roi, flo
     const uint8_t* fr = frames + (size_t)n0 * W * H * (yuyv_in ? 2 : 3);
     float* f = input ? input + (size_t)n0 * per_frame * 3 : nullptr;
     uint32_t* u = input_u8 ? input_u8 + (size_t)n0 * per_frame : nullptr;
-#define BSX_PF(O, L) prep_fused_k<O, L><<<grid, kThreads, 0, s>>>(fr, W, H, roi, f, u, inW, inH, in_roi, tab, bp, TW, TH, ntx, nty, xcd_on ? nn : 0)
-#define BSX_PFY(O) prep_fused_k<O, true, true><<<grid, kThreads, 0, s>>>(fr, W, H, roi, f, u, inW, inH, in_roi, tab, bp, TW, TH, ntx, nty, xcd_on ? nn : 0)
+#define BSX_PF(O, L) prep_fused_k<O, L><<<grid, kThreads, 0, s>>>(fr, W, H, roi, f, u, inW, inH, in_roi, tab, bp, TW, TH, ntx, nty, xcd_frames(nn))
+#define BSX_PFY(O) prep_fused_k<O, true, true><<<grid, kThreads, 0, s>>>(fr, W, H, roi, f, u, inW, inH, in_roi, tab, bp, TW, TH, ntx, nty, xcd_frames(nn))
     if (yuyv_in) { if (f && u) BSX_PFY(3); else if (u) BSX_PFY(2); else BSX_PFY(1); }
     else
     if (tab.mode == 0 && (W - roi.x) * 3 >= 8) { if (f && u) BSX_PF(3, true); else if (u) BSX_PF(2, true); else BSX_PF(1, true); }   // (the 8-byte tap window needs an 8-byte row)
@@ -1172,14 +1147,10 @@ static bool mask_tile_usable(const ResizeTab& tab) { return tab.mode == 0 && tab
 
 hipError_t launch_mask_upscale_blur(const uint8_t* ofinal, int outW, int outH, Rect4 in_roi, ResizeTab tab, uint8_t* mask, int W, int H, Rect4 roi,
                                     int n, hipStream_t s, const int* slot_of) {
-  const int ntx = (roi.w + kTW - 1) / kTW, nty = (roi.h + kTH - 1) / kTH;
-  if ((unsigned long long)ntx * nty * (unsigned long long)n >= (1ull << 31)) return hipErrorInvalidValue;
-  static const bool xcd_on = !(BSX_DBG_ENV("BSX_XCD_TILES") && atoi(BSX_DBG_ENV("BSX_XCD_TILES")) == 0);      // A/B timing: 0 = plain frame-major workgroup order
-  // one-XCD-per-frame order only where neighbouring tiles SHARE cache lines, i.e. the ROI's rows do not start on a 128-byte line (roi.x = 80 / 280: measured
-  // mask+blend 0.480 -> 0.464 ms at 256 HD MLKit streams); on line-aligned geometries nothing is shared and the plain order measured 2-3 % faster (profiles/r03o)
-  const bool shared_lines = ((roi.x * 3) & 127) != 0 || ((W * 3) & 127) != 0;
-  const int nf = (xcd_on && shared_lines) ? n : 0;
-  dim3 grid((unsigned)(ntx * nty) * (unsigned)n);
+  const MaskTileGrid g = mask_tile_grid(W, roi, n);
+  if (!g.ok) return hipErrorInvalidValue;
+  const int ntx = g.ntx, nty = g.nty, nf = g.nf;
+  const dim3 grid = g.grid(nty, n);
   if (hipError_t e = launch_tile_class(ofinal, outW, outH, in_roi, tab, roi, n, s, slot_of)) return e;
   if (mask_tile_usable(tab)) mask_tile_k<false><<<grid, kThreads, 0, s>>>(ofinal, outW, outH, in_roi, tab, mask, W, H, roi, nullptr, 0, nullptr, nullptr, 0, ntx, nty, nf, 0, nty, slot_of);
   else mask_upscale_blur_k<false><<<grid, kThreads, 0, s>>>(ofinal, outW, outH, in_roi, tab, mask, W, H, roi, nullptr, 0, nullptr, nullptr, 0, ntx, nty, nf, slot_of);
@@ -1224,26 +1195,20 @@ hipError_t launch_mask_blend(const uint8_t* ofinal, int outW, int outH, Rect4 in
   // ((a*255 + b*0)/255 == a): those strips are copied, the ROI is composited by the mask tiles
   // `yuyv`: bit 0 = YUYV output, bits 1-2 = horizontal / vertical flip of the composite, bit 3 = do not store the full-resolution mask, bit 4 = `frames` is YUYV
   // 4:2:2 (bsx.h: BSX_STEP_*); outside the ROI no frame pixel is read
-  if ((yuyv & 6) && (roi.x != 0 || roi.y != 0 || roi.w != W || roi.h != H))
+  const bool strips = !roi_is_frame(W, H, roi);
+  if (strips && (yuyv & 6))
     outside_roi_flip_k<<<dim3(blocks_for((long)(W / 4) * H), n), kThreads, 0, s>>>(bg, (long)bg_stride, out, W, H, roi, yuyv);
-  else if ((yuyv & 1) && (roi.x != 0 || roi.y != 0 || roi.w != W || roi.h != H))
+  else if (strips && (yuyv & 1))
     outside_roi_yuyv_k<<<dim3(blocks_for((long)(W / 2) * H), n), kThreads, 0, s>>>(bg, (long)bg_stride, reinterpret_cast<uint32_t*>(out), W, H, roi);
-  else if (roi.x != 0 || roi.y != 0 || roi.w != W || roi.h != H)
+  else if (strips)
     outside_roi_copy_k<<<dim3(blocks_for(((long)(H - roi.h) * (W * 3 / 4) + (long)roi.h * ((W - roi.w) * 3 / 4) + 3) / 4), n), kThreads, (size_t)lds_pad, s>>>(bg, (long)bg_stride, out, W, H,
                                                                                                                                  roi);
-  const int ntx = (roi.w + kTW - 1) / kTW, nty = (roi.h + kTH - 1) / kTH;
-  if ((unsigned long long)ntx * nty * (unsigned long long)n >= (1ull << 31)) return hipErrorInvalidValue;
-  static const bool xcd_on = !(BSX_DBG_ENV("BSX_XCD_TILES") && atoi(BSX_DBG_ENV("BSX_XCD_TILES")) == 0);      // A/B timing: 0 = plain frame-major workgroup order
-  // one-XCD-per-frame order only where neighbouring tiles SHARE cache lines, i.e. the ROI's rows do not start on a 128-byte line (roi.x = 80 / 280: measured
-  // mask+blend 0.480 -> 0.464 ms at 256 HD MLKit streams); on line-aligned geometries nothing is shared and the plain order measured 2-3 % faster (profiles/r03o)
-  const bool shared_lines = ((roi.x * 3) & 127) != 0 || ((W * 3) & 127) != 0;
-  const int nf = (xcd_on && shared_lines) ? n : 0;
-  dim3 grid((unsigned)(ntx * nty) * (unsigned)n);
+  const MaskTileGrid g = mask_tile_grid(W, roi, n);
+  if (!g.ok) return hipErrorInvalidValue;
+  const int ntx = g.ntx, nty = g.nty, nf = g.nf;
+  const dim3 grid = g.grid(nty, n);
   if (hipError_t e = launch_tile_class(ofinal, outW, outH, in_roi, tab, roi, n, s, slot_of)) return e;
-  static const bool no_early_bg = BSX_DBG_ENV("BSX_NO_EARLY_BG") != nullptr;      // A/B timing: bit 6 of the flag word = request a shared background only after the tile's class is known (rounds 1-4)
-  if (no_early_bg) yuyv |= 64;
-  static const bool plain_stores = BSX_DBG_ENV("BSX_TILE_PLAIN_STORES") != nullptr;      // A/B timing: bit 7 = the composite leaves with plain instead of nontemporal stores
-  if (plain_stores) yuyv |= 128;
+  yuyv |= tile_debug_bits();
   const bool yin = (yuyv & 16) != 0;
   if (mask_tile_usable(tab)) {
     const bool f0 = (yuyv & ~16) == 0;
@@ -1253,7 +1218,7 @@ hipError_t launch_mask_blend(const uint8_t* ofinal, int outW, int outH, Rect4 in
     const int nty_whole = whole_x ? roi.h / kTH : 0;
 #define BSX_MT(Y, F, WHL, GRID, NTY, TYB) mask_tile_k<true, Y, F, WHL><<<GRID, kThreads, (size_t)lds_pad, s>>>(ofinal, outW, outH, in_roi, tab, mask, W, H, roi, bg, (long)bg_stride, frames, out, yuyv, ntx, NTY, nf, TYB, nty, slot_of)
     if (nty_whole > 0) {
-      const dim3 gw((unsigned)(ntx * nty_whole) * (unsigned)n), gr((unsigned)(ntx * (nty - nty_whole)) * (unsigned)n);
+      const dim3 gw = g.grid(nty_whole, n), gr = g.grid(nty - nty_whole, n);
       if (yin) { BSX_MT(true, true, true, gw, nty_whole, 0); if (nty > nty_whole) BSX_MT(true, true, false, gr, nty - nty_whole, nty_whole); }
       else { BSX_MT(false, true, true, gw, nty_whole, 0); if (nty > nty_whole) BSX_MT(false, true, false, gr, nty - nty_whole, nty_whole); }
     } else if (yin) { if (f0) BSX_MT(true, true, false, grid, nty, 0); else BSX_MT(true, false, false, grid, nty, 0); }
@@ -1270,17 +1235,14 @@ hipError_t launch_mask_blend(const uint8_t* ofinal, int outW, int outH, Rect4 in
 hipError_t launch_mask_blend_mixed(const uint8_t* ofinal, int outW, int outH, Rect4 in_roi, ResizeTab tab, uint8_t* mask, int W, int H, Rect4 roi,
                                    const MixDesc* desc, const uint8_t* frames, uint8_t* out, int n, hipStream_t s, int flags, const int* slot_of) {
   flags &= 1 | 8 | 16;
-  if (roi.x != 0 || roi.y != 0 || roi.w != W || roi.h != H)
+  if (!roi_is_frame(W, H, roi))
     outside_roi_mixed_k<<<dim3(blocks_for((long)(W / 4) * H), n), kThreads, 0, s>>>(desc, frames, out, W, H, roi, flags);
-  const int ntx = (roi.w + kTW - 1) / kTW, nty = (roi.h + kTH - 1) / kTH;
-  if ((unsigned long long)ntx * nty * (unsigned long long)n >= (1ull << 31)) return hipErrorInvalidValue;
-  static const bool xcd_on = !(BSX_DBG_ENV("BSX_XCD_TILES") && atoi(BSX_DBG_ENV("BSX_XCD_TILES")) == 0);
-  const bool shared_lines = ((roi.x * 3) & 127) != 0 || ((W * 3) & 127) != 0;
-  const int nf = (xcd_on && shared_lines) ? n : 0;
-  const dim3 grid((unsigned)(ntx * nty) * (unsigned)n);
+  const MaskTileGrid g = mask_tile_grid(W, roi, n);
+  if (!g.ok) return hipErrorInvalidValue;
+  const int ntx = g.ntx, nty = g.nty, nf = g.nf;
+  const dim3 grid = g.grid(nty, n);
   if (hipError_t e = launch_tile_class(ofinal, outW, outH, in_roi, tab, roi, n, s, slot_of)) return e;
-  static const bool plain_stores = BSX_DBG_ENV("BSX_TILE_PLAIN_STORES") != nullptr;
-  if (plain_stores) flags |= 128;
+  flags |= tile_debug_bits() & 128;                                     // (no early background request to switch off here)
   const uint8_t* const d = reinterpret_cast<const uint8_t*>(desc);
   const bool yin = (flags & 16) != 0;
   if (mask_tile_usable(tab)) {
@@ -1292,8 +1254,10 @@ hipError_t launch_mask_blend_mixed(const uint8_t* ofinal, int outW, int outH, Re
 }
 
 // ---- bsx_step_batch_geoms: positions of several capture sizes in one prep, one tile-class, one tile [and one outside-ROI] launch (kernels.hpp: GeomClass, GeomDesc,
-// GeomSpans).  The kernels below are the bodies of prep_fused_k, tile_class_k, mask_tile_k<BLEND, .., MIX> and outside_roi_mixed_k with the geometry read per position;
-// they have names of their own, so no existing instantiation changes its template arguments, its mangled name or its code.
+// GeomSpans).  The kernels below are the bodies of prep_fused_k, tile_class_k, mask_tile_k<BLEND, .., MIX> and outside_roi_mixed_k with the geometry read per position.
+// They keep names of their own, so no dense instantiation changes its template arguments or its mangled name, and they share the TEXT of those bodies (prep_tile.inc,
+// tile_class.inc, mask_tile.inc; outside_mixed_group): what one stream computes cannot differ between the two forms.  That sharing changes no kernel's code is checked,
+// not assumed: tools/isa_same.py compares every kernel's assembly with another revision's.
 namespace {
 // workgroup (or position) `id` of a ragged grid: its class g, the class's first workgroup w0, first position p0, one-past-last position p1 and workgroups per position
 // — compares and selects on SGPRs (id is workgroup-uniform, the spans are kernel arguments): nothing is loaded
@@ -1308,20 +1272,6 @@ __device__ __forceinline__ int geom_class_of_position(const GeomSpans& sp, int n
 #pragma unroll
   for (int k = 1; k < kMaxGeoms; k++) if (n >= sp.pos[k]) g = k;
   return g;
-}
-// xcd_frame_tile for a SEGMENT of the grid: `local` = the workgroup's index inside its class's segment.  Workgroups whose indices agree modulo 8 share an XCD
-// whatever the segment's first workgroup is, so a frame's tiles still meet in one L2.
-__device__ __forceinline__ void xcd_frame_tile_at(unsigned local, unsigned tiles, unsigned n_frames, unsigned* frame, unsigned* tile) {
-  const unsigned full = (n_frames & ~7u) * tiles;
-  if (local < full) {
-    const unsigned xcd = local & 7u, l8 = local >> 3, gq = l8 / tiles;
-    *frame = 8u * gq + xcd;
-    *tile = l8 - gq * tiles;
-  } else {
-    const unsigned r = local - full, f = r / tiles;
-    *frame = (n_frames & ~7u) + f;
-    *tile = r - f * tiles;
-  }
 }
 // a resize table read from a class record: its pointers as global-memory pointers (as_global: a pointer read from memory is otherwise a generic one)
 __device__ __forceinline__ ResizeTab geom_tab(const ResizeTab& t) {
@@ -1383,9 +1333,9 @@ __global__ __launch_bounds__(kThreads) void tile_class_geoms_k(const GeomClass* 
 #undef BSX_CLS_BYTE
 }
 
-// mask_tile_k<BLEND = true, YIN = false, F0 = false, WH = false, MIX = true> per position: the same phases through the same helpers, with the position's own bases
-// (index 0 of each) and its class's geometry.  The order of the loads is mask_tile_k's: class byte first (its address needs only the kernel arguments), class record
-// and descriptor — two independent uniform loads — next to it, the state slot only where it is consumed.
+// mask_tile_k<BLEND = true, YIN = false, F0 = false, WH = false, MIX = true> per position: its own prologue and uniform-tile branch, then mask_tile.inc with the
+// position's own bases (index 0 of each) and its class's geometry.  The order of the loads is mask_tile_k's: class byte first (its address needs only the kernel
+// arguments), class record and descriptor — two independent uniform loads — next to it, the state slot only where it is consumed.
 __global__ __launch_bounds__(kThreads) void mask_tile_geoms_k(const GeomClass* __restrict__ classes, const GeomDesc* __restrict__ desc, GeomSpans sp, unsigned xcd_mask,
                                                              const uint8_t* __restrict__ ofinal, int outW, int outH, const uint8_t* __restrict__ tile_class, int yuyv) {
   __shared__ short col_c0[kHW], col_c1[kHW], col_a0[kHW], col_a1[kHW];
@@ -1402,10 +1352,7 @@ __global__ __launch_bounds__(kThreads) void mask_tile_geoms_k(const GeomClass* _
   xcd_frame_tile_at(blockIdx.x - (unsigned)w0, (unsigned)per, ((xcd_mask >> g) & 1u) ? (unsigned)(p1 - p0) : 0u, &f_, &t_);
   const int n = p0 + (int)f_;                                          // the position (descriptor index)
   int uniform = 0;
-  if (tile_class) {                                                    // the aligned word that holds the byte: a scalar load
-    const uintptr_t ca = (uintptr_t)tile_class + (size_t)w0 + (size_t)f_ * (size_t)per + (size_t)t_;
-    uniform = (int)((*reinterpret_cast<const uint32_t*>(ca & ~(uintptr_t)3) >> (8 * (unsigned)(ca & 3))) & 255u);
-  }
+  if (tile_class) uniform = tile_class_byte((uintptr_t)tile_class + (size_t)w0 + (size_t)f_ * (size_t)per + (size_t)t_);
   const GeomClass c = classes[g];
   const GeomDescRegs d = geom_desc(desc, n);
   const int W = c.W, H = c.H;
@@ -1415,56 +1362,22 @@ __global__ __launch_bounds__(kThreads) void mask_tile_geoms_k(const GeomClass* _
   yuyv = (yuyv & ~16) | (int)(d.flags & (kMixFlipH | kMixFlipV));
   const int sel = (d.flags & kMixFilterOff) ? 2 : -1;
   TileBlendOperands ops;
+  constexpr bool BLEND = true, WH = false, MIX = true, yin = false, early_bg = false;      // mask_tile.inc's names: the instantiation, the position's descriptor
+  constexpr long bg_stride = 0;
+  const uint8_t *const bg = d.bg, *const frames = d.frame;
+  uint8_t *const mask = d.mask, *const outp = d.out;
   if (uniform) {
-    tile_load_blend_operands<true, false, true>(ops, d.bg, 0, d.frame, 0, W, H, roi, tx0, ty0, tid, uniform, 3, false, sel);
-    tile_vsum5_store<true, false, true>(hq_hs, d.mask, d.out, ops, 0, 0, W, H, roi, tx0, ty0, tid, yuyv, uniform, sel);
+    tile_load_blend_operands<BLEND, WH, MIX>(ops, bg, bg_stride, frames, 0, W, H, roi, tx0, ty0, tid, uniform, 3, yin, sel);
+    tile_vsum5_store<BLEND, WH, MIX>(hq_hs, mask, outp, ops, 0, 0, W, H, roi, tx0, ty0, tid, yuyv, uniform, sel);
     return;
   }
-  const int gy_lo = max(ty0 - 2, 0), gy_hi = min(ty0 + kTH + 1, roi.h - 1);
-  const int gx_lo = max(tx0 - 2, 0), gx_hi = min(tx0 + kTW + 1, roi.w - 1);
-  const int smin = min(max(tab.yofs[gy_lo], 0), tab.sh - 1), smax = min(max(tab.yofs[gy_hi] + 1, 0), tab.sh - 1);
-  const int cmin = tab.xofs[gx_lo], cmax = min(tab.xofs[gx_hi] + 1, tab.sw - 1);
-  const int nsr = smax - smin + 1, ncol = cmax - cmin + 1;
-  const uint8_t* const base = ofinal + (long)d.slot * outW * outH + (long)(q.y + smin) * outW + q.x + cmin;
-  uint32_t raw[3];
-  const int br = tid >> 6, bc = tid & 63;
-#pragma unroll
-  for (int j = 0; j < 3; j++) { raw[j] = 0; if (br + 4 * j < nsr && bc < ncol) raw[j] = base[(unsigned)((br + 4 * j) * outW + bc)]; }
-  int t_s = 0, t_a0 = 0, t_a1 = 0;
-  if (tid < kHW) {
-    const int gx = reflect101(min(tx0 + tid - 2, roi.w + 1), roi.w);
-    t_s = tab.xofs[gx]; t_a0 = tab.xa[2 * gx]; t_a1 = tab.xa[2 * gx + 1];
-  } else if (tid >= 192 && tid < 192 + kHH) {
-    const int gy = reflect101(min(ty0 + (tid - 192) - 2, roi.h + 1), roi.h);
-    t_s = tab.yofs[gy]; t_a0 = tab.ya[2 * gy]; t_a1 = tab.ya[2 * gy + 1];
-  }
-  tile_load_blend_operands<true, false, true>(ops, d.bg, 0, d.frame, 0, W, H, roi, tx0, ty0, tid, 0, 3, false, sel);
-#pragma unroll
-  for (int j = 0; j < 3; j++) if (br + 4 * j < nsr && bc < ncol) blk[(br + 4 * j) * ncol + bc] = (uint8_t)raw[j];
-  if (nsr > 12 || ncol > 64)
-    for (int r = br; r < nsr; r += 4)
-      for (int cc = bc; cc < ncol; cc += 64)
-        if (r >= 12 || cc >= 64) blk[r * ncol + cc] = base[(unsigned)(r * outW + cc)];
-  if (tid < kHW) {
-    col_c0[tid] = (short)(t_s - cmin); col_c1[tid] = (short)(min(t_s + 1, tab.sw - 1) - cmin);
-    col_a0[tid] = (short)t_a0; col_a1[tid] = (short)t_a1;
-  } else if (tid >= 192 && tid < 192 + kHH) {
-    const int r = tid - 192;
-    row_r0[r] = (short)(min(max(t_s, 0), tab.sh - 1) - smin); row_r1[r] = (short)(min(max(t_s + 1, 0), tab.sh - 1) - smin);
-    row_b0[r] = (short)t_a0; row_b1[r] = (short)t_a1;
-  }
-  __syncthreads();
-  for (int r = tid / kHW, x = tid % kHW; r < nsr;) {
-    hq[r * kHW + x] = (uint16_t)((blk[r * ncol + col_c0[x]] * col_a0[x] + blk[r * ncol + col_c1[x]] * col_a1[x]) >> 4);
-    x += kThreads % kHW; r += kThreads / kHW;
-    if (x >= kHW) { x -= kHW; r++; }
-  }
-  __syncthreads();
-  tile_vertical_pass(hq, up, row_r0, row_r1, 0, row_b0, row_b1, tid);
-  __syncthreads();
-  tile_hsum5(up, hs, tid);
-  __syncthreads();
-  tile_vsum5_store<true, false, true>(hs, d.mask, d.out, ops, 0, 0, W, H, roi, tx0, ty0, tid, yuyv, 0, sel);
+#define BSX_MT_FRAME 0                                               /* the position's own bases: index 0 of each */
+#define BSX_MT_SLOT d.slot
+#define BSX_MT_MASK_SLOT 0
+#include "mask_tile.inc"
+#undef BSX_MT_FRAME
+#undef BSX_MT_SLOT
+#undef BSX_MT_MASK_SLOT
 }
 
 // outside_roi_mixed_k per position: sp.per[g] workgroups for every position of a class whose ROI is not the frame, none for the others
@@ -1480,21 +1393,17 @@ __global__ __launch_bounds__(kThreads) void outside_roi_geoms_k(const GeomClass*
 
 bool geom_class_fusable(int W, const Rect4& roi, const ResizeTab& up) { return (W % 4) == 0 && (roi.x % 4) == 0 && (roi.w % 4) == 0 && mask_tile_usable(up); }
 int geom_outside_blocks(int W, int H, const Rect4& roi) {
-  return (roi.x != 0 || roi.y != 0 || roi.w != W || roi.h != H) ? (int)blocks_for((long)(W / 4) * H) : 0;
+  return roi_is_frame(W, H, roi) ? 0 : (int)blocks_for((long)(W / 4) * H);
 }
-bool geom_class_xcd(int W, const Rect4& roi) {                           // launch_mask_blend's rule: one-XCD-per-frame order only where neighbouring tiles share cache lines
-  static const bool xcd_on = !(BSX_DBG_ENV("BSX_XCD_TILES") && atoi(BSX_DBG_ENV("BSX_XCD_TILES")) == 0);
-  return xcd_on && (((roi.x * 3) & 127) != 0 || ((W * 3) & 127) != 0);
-}
+bool geom_class_xcd(int W, const Rect4& roi) { return mask_tile_grid(W, roi, 1).nf != 0; }      // launch_mask_blend's rule, asked for one frame
 
 hipError_t launch_prep_geoms(const GeomClass* classes, const GeomDesc* desc, const GeomSpans& spans, float* input, uint32_t* input_u8, int inW, int inH, BilateralParams bp,
                              int n, hipStream_t s) {
   if ((!input && !input_u8) || n <= 0) return hipErrorInvalidValue;
   const int ntx = (inW + 31) / 32, nty = (inH + 31) / 32, TW = (inW + ntx - 1) / ntx, TH = (inH + nty - 1) / nty;      // launch_prep_fused's tiles
   if ((unsigned long long)ntx * nty * (unsigned long long)n >= (1ull << 31)) return hipErrorInvalidValue;
-  static const bool xcd_on = !(BSX_DBG_ENV("BSX_XCD_TILES") && atoi(BSX_DBG_ENV("BSX_XCD_TILES")) == 0);
   const dim3 grid((unsigned)(ntx * nty) * (unsigned)n);
-#define BSX_PG(O) prep_geoms_k<O><<<grid, kThreads, 0, s>>>(classes, desc, spans, input, input_u8, inW, inH, bp, TW, TH, ntx, nty, xcd_on ? n : 0)
+#define BSX_PG(O) prep_geoms_k<O><<<grid, kThreads, 0, s>>>(classes, desc, spans, input, input_u8, inW, inH, bp, TW, TH, ntx, nty, xcd_frames(n))
   if (input && input_u8) BSX_PG(3); else if (input_u8) BSX_PG(2); else BSX_PG(1);
 #undef BSX_PG
   return hipGetLastError();
@@ -1506,8 +1415,7 @@ hipError_t launch_mask_blend_geoms(const GeomClass* classes, const GeomDesc* des
   if (n <= 0 || tiles.wg[kMaxGeoms] <= 0) return hipErrorInvalidValue;
   if (outside.wg[kMaxGeoms] > 0) outside_roi_geoms_k<<<dim3((unsigned)outside.wg[kMaxGeoms]), kThreads, 0, s>>>(classes, desc, outside, flags);
   if (tile_class) tile_class_geoms_k<<<dim3((unsigned)n), kThreads, 0, s>>>(classes, desc, tiles, ofinal, outW, outH, tile_class);
-  static const bool plain_stores = BSX_DBG_ENV("BSX_TILE_PLAIN_STORES") != nullptr;
-  if (plain_stores) flags |= 128;
+  flags |= tile_debug_bits() & 128;
   mask_tile_geoms_k<<<dim3((unsigned)tiles.wg[kMaxGeoms]), kThreads, 0, s>>>(classes, desc, tiles, xcd_mask, ofinal, outW, outH, tile_class, flags);
   return hipGetLastError();
 }

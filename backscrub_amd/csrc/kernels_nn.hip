@@ -1704,8 +1704,7 @@ hipError_t launch_resize_argmax_iir(const Step& st, const float* x, uint8_t* ofi
   const int ntx = (st.OW + kFusedTW - 1) / kFusedTW, nty = (st.OH + kFusedTH - 1) / kFusedTH;
   if ((unsigned long long)ntx * nty * (unsigned long long)n >= (1ull << 31)) return hipErrorInvalidValue;
   const dim3 grid((unsigned)(ntx * nty) * (unsigned)n);
-  static const bool xcd_on = !(BSX_DBG_ENV("BSX_XCD_TILES") && atoi(BSX_DBG_ENV("BSX_XCD_TILES")) == 0);      // A/B timing: 0 = plain frame-major workgroup order
-  const int nf = xcd_on ? n : 0;
+  const int nf = xcd_frames(n);
   const int person = 15;                                           // lib/libbackscrub.cc:330 (pascal VOC class 15)
   if (!generic && st.Cin == 21 && person == 15) resize_argmax_iir_k<true, 21, 15><<<grid, kThreads, 0, s>>>(x, ofinal, st.H, st.W, st.Cin, st.OH, st.OW, hs, ws, st.half_pixel, person, ntx, nty, nf, slot_of);   // DeepLab / PASCAL VOC
   else if (!generic && st.Cin <= 24 && person < st.Cin) resize_argmax_iir_k<true><<<grid, kThreads, 0, s>>>(x, ofinal, st.H, st.W, st.Cin, st.OH, st.OW, hs, ws, st.half_pixel, person, ntx, nty, nf, slot_of);
@@ -1856,7 +1855,7 @@ hipError_t launch_step(const Step& st, const Plan& plan, float* arena, float* ne
         const int BH = head0_band_rows(st.W, st.OW), nb = (st.OH + BH - 1) / BH;
         const size_t fl = (size_t)head0_lds_floats(st.W, st.OW, BH);
         static const int h0_phases = BSX_DBG_ENV("BSX_H0_PHASES") ? atoi(BSX_DBG_ENV("BSX_H0_PHASES")) : 15;   // timing experiments
-        static const bool h0_xcd = BSX_DBG_ENV("BSX_XCD_TILES") && atoi(BSX_DBG_ENV("BSX_XCD_TILES")) == 2;      // one-XCD-per-frame band order: measured SLOWER here (0.927 vs 0.908 ms, profiles/r03o) — only with BSX_XCD_TILES=2
+        const bool h0_xcd = xcd_tiles_mode() == 2;      // one-XCD-per-frame band order: measured SLOWER here (0.927 vs 0.908 ms, profiles/r03o) — only with BSX_XCD_TILES=2
         const bool u8_fits = (long)(2 * (BH + 2) + 1) * st.W <= 4 * 3 * kH0Threads;                // three 4-pixel loads per lane cover the band's rows
         if (net_in_u8 && st.in0 == plan.input && !u8_fits) return hipErrorInvalidValue;            // (bsx_api decides with the same rule: head0_u8_ok)
         if (net_in_u8 && st.in0 == plan.input)

@@ -978,9 +978,6 @@ hipError_t seg_prepare() {
   return e;
 }
 
-// n_frames = 0 tells xcd_frame_tile to keep the plain (frame-major) workgroup order: BSX_XCD_TILES=0, read once per process, for A/B timing
-static int xcd_frames(int n) { static const bool on = !(BSX_DBG_ENV("BSX_XCD_TILES") && atoi(BSX_DBG_ENV("BSX_XCD_TILES")) == 0); return on ? n : 0; }
-
 // fn: the graph-specialised kernel (specialised.hpp), or nullptr for the ahead-of-time instance of the variant.
 // h16: the boundary tensors are stored as halves (BSX_ACT16; the middle program must have been generated for the same storage)
 // u8: net_in points at the 8-bit network input ([n][H0][W0] u32 pixels, prep_fused_k<2>) and (scale, offset) is the model's normalisation

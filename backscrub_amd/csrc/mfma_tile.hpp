@@ -32,8 +32,10 @@ __device__ __forceinline__ float4 quad_transpose(const f4acc acc, int q) {
 // every halo line is fetched from HBM once per XCD that touches it (PMC: prep_fused_k fetched 147 MB for 94 MB of touched pixels).  Here XCD k walks frames
 // k, k + 8, k + 16, … tile by tile, so a frame's tiles — and their shared halo lines — meet in ONE L2.  Bijective for any frame count (the last n % 8 frames
 // keep the plain order); speed only, never correctness.
-__device__ __forceinline__ void xcd_frame_tile(unsigned tiles, unsigned n_frames, unsigned* frame, unsigned* tile) {
-  const unsigned id = blockIdx.x, full = (n_frames & ~7u) * tiles;
+// xcd_frame_tile_at: the same for a SEGMENT of the grid, `id` = the workgroup's index inside the segment (mask_tile_geoms_k: inside its class's).  Workgroups whose
+// indices agree modulo 8 share an XCD whatever the segment's first workgroup is, so a frame's tiles still meet in one L2.
+__device__ __forceinline__ void xcd_frame_tile_at(unsigned id, unsigned tiles, unsigned n_frames, unsigned* frame, unsigned* tile) {
+  const unsigned full = (n_frames & ~7u) * tiles;
   if (id < full) {
     const unsigned xcd = id & 7u, local = id >> 3, g = local / tiles;
     *frame = 8u * g + xcd;
@@ -44,5 +46,6 @@ __device__ __forceinline__ void xcd_frame_tile(unsigned tiles, unsigned n_frames
     *tile = r - f * tiles;
   }
 }
+__device__ __forceinline__ void xcd_frame_tile(unsigned tiles, unsigned n_frames, unsigned* frame, unsigned* tile) { xcd_frame_tile_at(blockIdx.x, tiles, n_frames, frame, tile); }
 
 }  // namespace bsx
