@@ -488,6 +488,8 @@ bool debug_tensor_half(const bsx_ctx* c, int t) {
   return false;
 }
 
+// k3 runs in its per-frame form: the plan takes it and the context loaded the specialised module (the ahead-of-time fallback is the tile form and the gate launch)
+bool k3_frame_runs(const bsx_ctx* c) { return c->use_program && c->plan.seg.on && c->plan.seg.k3f.on && c->kern.k3_frame != nullptr; }
 bool infer_decodes(const bsx_ctx* c) { return (c->use_program && c->plan.seg.on && !c->keep_logits) || argmax_tail(c); }
 // ids (device, nullable): the id form of a step — frame i's temporal state is slot ids[i] (then slot == 0); nullptr = slots [slot, slot + n)
 int run_infer(bsx_ctx* c, int n, hipStream_t s, bool logits = true, int slot = 0, const int* ids = nullptr, LaunchTimer* t = nullptr) {
@@ -507,8 +509,12 @@ int run_infer(bsx_ctx* c, int n, hipStream_t s, bool logits = true, int slot = 0
     BSX_LAUNCH(c, t, s, launch_seg_head(fn[0], sp.head, c->d_arena, pf, in, c->d_weights, n, s, c->act16, c->in_u8, c->norm_scale, c->norm_offset));
     BSX_LAUNCH(c, t, s, launch_seg_k2(fn[1], sp.k2, c->d_arena, pf, c->d_weights, n, s, c->act16));
     BSX_LAUNCH(c, t, s, launch_program(c, n, s));
-    BSX_LAUNCH(c, t, s, launch_seg_k3(fn[2], sp.k3, c->d_arena, pf, c->d_weights, n, s, c->act16));
-    if (sp.tail.pre_gate_off >= 0) BSX_LAUNCH(c, t, s, launch_seg_gate(sp.tail.gate, c->d_arena, pf, c->d_weights, sp.tail.pre_gate_off, n, s));
+    if (k3_frame_runs(c)) {    // k3's per-frame form: lo, its partial sums and the tail's gate vector in one launch
+      BSX_LAUNCH(c, t, s, launch_seg_k3_frame(c->kern.k3_frame, sp.k3f, c->d_arena, pf, c->d_weights, n, s));
+    } else {
+      BSX_LAUNCH(c, t, s, launch_seg_k3(fn[2], sp.k3, c->d_arena, pf, c->d_weights, n, s, c->act16));
+      if (sp.tail.pre_gate_off >= 0) BSX_LAUNCH(c, t, s, launch_seg_gate(sp.tail.gate, c->d_arena, pf, c->d_weights, sp.tail.pre_gate_off, n, s));
+    }
     if (!logits) { const int frc = state_write_fence(c, s); if (frc) return frc; }       // the decoding tail reads and writes d_ofinal
     BSX_LAUNCH(c, t, s, launch_seg_tail(fn[3], sp.tail, c->d_arena, pf, c->d_net_out, c->d_ofinal + (size_t)slot * c->outW * c->outH, c->d_weights, logits, n, s,
                                         c->act16, ids));
@@ -1324,6 +1330,8 @@ static bsx_ctx* new_ctx(const char* model_path, size_t threads, const bsx_geomet
       c->plan_text += seg;
     }
     if (c->use_program && c->plan.seg.on) c->plan_text += "segment execution: " + c->kern.seg_note + "\n";
+    if (c->use_program && c->plan.seg.on && c->plan.seg.k3f.on && !c->kern.k3_frame)
+      c->plan_text += "segment k3 execution: tiles and the gate launch (the per-frame form is part of the specialised module only)\n";
     if (c->use_program && c->kern.mid) c->plan_text += mid_barrier_line(c->plan, c->act16);
     for (size_t i = 0; i < c->plan.program_labels.size(); i++) {
       c->plan_text += "P" + std::to_string(i) + " " + c->plan.program_labels[i];
@@ -1721,7 +1729,7 @@ int bsx_profile_batch(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, 
   const bool seg = c->use_program && c->plan.seg.on;
   const bool fused_decode = infer_decodes(c);
   const bool atail = argmax_tail(c);
-  const int n_net = c->use_program ? (seg ? (c->plan.seg.tail.pre_gate_off >= 0 ? 6 : 5) : 1) : (int)c->plan.steps.size();
+  const int n_net = c->use_program ? (seg ? (c->plan.seg.tail.pre_gate_off >= 0 && !k3_frame_runs(c) ? 6 : 5) : 1) : (int)c->plan.steps.size();
   const bool fuse_tail = tile_fusable(c, StepReq{d_frames, d_bg, bg_stride, d_out, c->width, c->height, n, 0u, s, nullptr});
   const int L = 1 + n_net + (fused_decode ? 0 : 1) + (fuse_tail ? 1 : 2) + (fuse_tail ? 1 : 0);   // + a stand-alone blend launch when the step's tail is fused
   if (cap < L) return BSX_EINVAL;
@@ -1768,8 +1776,12 @@ int bsx_profile_batch(bsx_ctx* c, const uint8_t* d_frames, const uint8_t* d_bg, 
     put(j++, "seg_head", N * ((c->in_u8 ? 4.0 * c->inW * c->inH : 4.0 * ein) + 4.0 * (eA + eb0)), N * 2.0 * macs(0, 2));
     put(j++, "seg_k2", N * 4.0 * (eb0 + eb0 + ec0), N * 2.0 * macs(3, 8));
     put(j++, "frame_program", N * 4.0 * (ec0 + elo2) + 4.0 * c->plan.weights.size(), N * 2.0 * macs(9, NS - 11));
-    put(j++, "seg_k3", N * 4.0 * (eb0 + elo2 + elo), N * 2.0 * macs(NS - 10, NS - 8));
-    if (sp.tail.pre_gate_off >= 0) put(j++, "seg_gate", N * 4.0 * (16.0 * (sp.tail.gate.part[0].n + sp.tail.gate.part[1].n) + 16.0), 0);      // the tail's gate, once per frame
+    const double egate = 16.0 * (sp.tail.gate.part[0].n + sp.tail.gate.part[1].n) + 16.0, fgate = 2.0 * macs(NS - 5, NS - 4);      // the tail's gate, once per frame
+    if (k3_frame_runs(c)) put(j++, "seg_k3", N * 4.0 * (eb0 + elo2 + elo + egate), N * (2.0 * macs(NS - 10, NS - 8) + fgate));      // the per-frame form: the gate's work is this launch's
+    else {
+      put(j++, "seg_k3", N * 4.0 * (eb0 + elo2 + elo), N * 2.0 * macs(NS - 10, NS - 8));
+      if (sp.tail.pre_gate_off >= 0) put(j++, "seg_gate", N * 4.0 * egate, 0);
+    }
     put(j++, fused_decode ? "seg_tail+decode" : "seg_tail", N * (4.0 * (eA + elo) + (fused_decode ? 2.0 * c->outW * c->outH : 4.0 * eout)), N * 2.0 * macs(NS - 7, NS - 1));
   } else if (c->use_program) {
     // algorithmic bytes of the fused network = its input tensor + its output tensor + the weights once
@@ -1929,6 +1941,7 @@ int bsx_model_precompile(const char* model_path, const char* arch, char* msg, si
       if (!b.seg.code.empty()) {
         long worst = 0;
         for (const char* k : {"bsx_seg_head", "bsx_seg_k2", "bsx_seg_k3", "bsx_seg_tail"}) worst = std::max(worst, code_object_scratch_bytes(b.seg.code, k));
+        if (b.seg_k3_frame) worst = std::max(worst, code_object_scratch_bytes(b.seg.code, "bsx_seg_k3f"));
         char sm[256];
         snprintf(sm, sizeof sm, "; segment kernels %s (%zu bytes of source, %zu bytes of code object, %ld B of scratch)", b.seg.cached ? "cached" : "compiled", b.seg.source.size(),
                  b.seg.code.size(), worst);

@@ -85,8 +85,9 @@ std::string generate_seg_source(const Plan& plan, bool h16, bool u8in, std::stri
   if (at == std::string::npos) return fail("embedded source has no constants marker");
   src.replace(at, mark.size(), seg_constants_text(sp, "kSeg"));
   char head[512];
-  snprintf(head, sizeof head, "#define BSXS_SEG_RTC 1\n#define BSXS_SEG_HS %d\n#define BSXS_SEG_H16 %d\n#define BSXS_SEG_U8 %d\n#define BSXS_SEG_SIG %d\n#define BSXS_SEG_CO %d\n",
-           sp.head.stem.act == kActHswish ? 1 : 0, h16 ? 1 : 0, u8in ? 1 : 0, sig ? 1 : 0, sp.tail.Co);
+  // BSXS_SEG_K3F: the plan takes k3's per-frame form — the text then has a fifth kernel, bsx_seg_k3f, whose layout is seg_k3f_layout(kSegK3) evaluated by the compiler
+  snprintf(head, sizeof head, "#define BSXS_SEG_RTC 1\n#define BSXS_SEG_HS %d\n#define BSXS_SEG_H16 %d\n#define BSXS_SEG_U8 %d\n#define BSXS_SEG_SIG %d\n#define BSXS_SEG_CO %d\n#define BSXS_SEG_K3F %d\n",
+           sp.head.stem.act == kActHswish ? 1 : 0, h16 ? 1 : 0, u8in ? 1 : 0, sig ? 1 : 0, sp.tail.Co, sp.k3f.on ? 1 : 0);
   return std::string(head) + src;
 }
 

@@ -71,6 +71,7 @@ hipError_t launch_seg_head(hipFunction_t fn, const SegHead& d, float* arena, lon
                            float in_scale, float in_offset);
 hipError_t launch_seg_k2(hipFunction_t fn, const SegK2& d, float* arena, long per_frame, const float* weights, int n, hipStream_t s, bool h16);
 hipError_t launch_seg_k3(hipFunction_t fn, const SegK3& d, float* arena, long per_frame, const float* weights, int n, hipStream_t s, bool h16);
+hipError_t launch_seg_k3_frame(hipFunction_t fn, const SegK3F& L, float* arena, long per_frame, const float* weights, int n, hipStream_t s);
 hipError_t launch_seg_gate(const SegGate& gt, float* arena, long per_frame, const float* weights, long long out_off, int n, hipStream_t s);
 // logits = true: write the network output tensor (debug / stage tests; ahead of time only); false: decode + temporal IIR straight into `ofinal`
 hipError_t launch_seg_tail(hipFunction_t fn, const SegTail& d, float* arena, long per_frame, float* net_out, uint8_t* ofinal, const float* weights, bool logits, int n,

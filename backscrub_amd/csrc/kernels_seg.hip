@@ -827,6 +827,226 @@ __global__ __launch_bounds__(kSegThreads) void seg_k3_k(
 }
 
 // ==================================================================================================================================
+// k3, per-frame form (segments.hpp: SegK3F): blockIdx.x = frame, 1024 lanes = 16 waves, one workgroup per CU — the whole of seg_k3_k's frame and seg_gate_k's work in
+// one dependent chain instead of tiles_y * tiles_x chains in one and a half rounds plus a launch.  The arithmetic is the tile form's, instruction for instruction:
+//   phase A  gated_compute's body per row tile (one z row, 16 columns of block tx: columns tx * TC - 1 ..) on absolute coordinates, weights and lo2 from LDS;
+//   phase B  seg_k3_k's depthwise + pw2 per (tile, wave-of-the-tile-form) unit: a unit adds its rows' `sum` in that wave's order, wave_reduce16<0> puts it where the
+//            tile's workgroup would have, and 16 lanes per tile add the 16 slots as store_partials does — the partial sums of lo are the tile form's bits;
+//   gate     seg_gate's slices, means and FC layers on the first 256 lanes (its decomposition is tid >> 4 over 256 lanes), part 1 read from the partial sums in LDS.
+// The 256-lane kernels share none of this text by template: they keep their code (and registers) to the instruction.  No global load behind the first barrier.
+// In the graph-specialised module only (gen_seg.cpp defines BSX_SEG_K3F where the plan takes the form): the ahead-of-time fallback keeps seg_k3_k + seg_gate_k, the
+// same bits — tests/test_device_order.py wants that fallback's k3 launch to be seg_k3_k, and a 1024-lane instance with the descriptor in registers needs 120 of them.
+// ==================================================================================================================================
+#if defined(BSX_SEG_RTC) && BSX_SEG_K3F
+// one FC layer of the gate on the first 256 lanes (seg_gate's `fc`): lane = (output, slice of the inputs), 8 consecutive lanes meet through DPP
+__device__ __forceinline__ void frame_gate_fc(const SegFc& f, const float* x, const float* wl, const float* bl, float* y, int tid) {
+  const int out = tid >> 3, ks = tid & 7, kper = f.Cin >> 3;
+  float acc = 0.f;
+  if (out < f.Cout)
+    for (int j = 0; j < kper; j++) acc = fmaf(x[ks * kper + j], wl[out * f.Cin + ks * kper + j], acc);
+  acc += dpp_quad(acc, 1);
+  acc += dpp_quad(acc, 2);
+  acc += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, acc), 0x141, 0xf, 0xf, true));
+  if (out < f.Cout && ks == 0) y[out] = sg_act(acc + bl[out], f.act);
+}
+constexpr SegK3F kSegK3F = seg_k3f_layout(kSegK3);
+static_assert(kSegK3F.on && kSegTAIL.pre_gate_off >= 0 && kSegTAIL.gate.n_parts == 2 && kSegTAIL.gate.part[1].off == kSegK3.part_lo_off &&
+              kSegTAIL.gate.part[1].n == kSegK3.tiles_y * kSegK3.tiles_x, "k3: the per-frame form does not fit this plan");
+extern "C" __global__ __launch_bounds__(kSegK3FThreads) void bsx_seg_k3f(float* __restrict__ arena, long per_frame, const float* __restrict__ w) {
+  constexpr SegK3 d = kSegK3;
+  constexpr SegK3F L = kSegK3F;
+  constexpr SegGate gt = kSegTAIL.gate;
+  constexpr long long pre_gate_off = kSegTAIL.pre_gate_off;
+  __shared__ __attribute__((aligned(16))) float smem[L.lds_floats];   // (static: the planned size is a constant here, and the function needs no attribute for its 100+ KiB)
+  float* fa = arena + (size_t)blockIdx.x * (size_t)per_frame;
+  const int tid = threadIdx.x, lane = tid & 63, wave = wave_uniform(tid >> 6), li = lane & 15, g = lane >> 4, cq4 = 4 * g;
+  const int H = d.H2, W = d.W2, TX = d.tiles_x, ZRW = TX * 256, ntile = (H + 2) * TX, tiles = d.tiles_y * TX, LRW = d.WL * kLoStride;
+  const bool half_pixel = d.half_pixel != 0;
+  float* z_t = smem + L.z_off;                                      // [H + 2][TX][16][16]: row zy = image row zy - 1
+  float* l_t = smem + L.lo_off;                                     // lo2 [HL][WL][16]
+  float* sw = smem + L.w_off;
+  float* s_red = smem + L.red_off;
+  float* s_plo = smem + L.plo_off;
+  float* s_g2 = smem + kSegK3FGate;
+  float* lo_out = fa + d.lo_off;
+  // ---- every global read of the frame: skip operands (registers), lo2, the level-2 gate, every weight, the tail gate's A partial sums and FC weights
+  float4 sk[kSegK3FRows];
+#pragma unroll
+  for (int j = 0; j < kSegK3FRows; j++) {
+    const int t = wave + 16 * j, zy = t / TX, tx = t - zy * TX, iy = zy - 1, ix = tx * d.TC - 1 + li;
+    sk[j] = f4zero();
+    if (t < ntile && iy >= 0 && iy < H && ix >= 0 && ix < W) sk[j] = ldg4<H16>(fa + d.skip_off, (unsigned)((iy * W + ix) * 16 + cq4));
+  }
+  const int npl = d.HL * d.WL * 4;                                  // 16-byte pieces of lo2: piece p = quad p & 3 of pixel p >> 2
+  float4 lv[kSegK3FLoPieces];
+#pragma unroll
+  for (int j = 0; j < kSegK3FLoPieces; j++) {
+    const int p = tid + kSegK3FThreads * j;
+    lv[j] = f4zero();
+    if (p < npl) lv[j] = ldg4<H16>(fa + d.lo2_off, (unsigned)(4 * p));
+  }
+  // weights: piece wp of kSegK3FWPieces on lanes 256 .. (the first 256 lanes carry the gate's loads); a 1x1 tile piece = row (q & 15), columns 4 * (q >> 4) ..
+  const int wp = tid - 256;
+  int w_dst = 0;
+  float4 wv = f4zero();
+  if (wp >= 0 && wp < kSegK3FWPieces) {
+    const float* src;
+    if (wp < 64) { src = w + d.pw1.w_off + (unsigned)((wp & 15) * d.pw1.cout_pad + 4 * (wp >> 4)); w_dst = (wp & 15) * kSegK3FWStride + 4 * (wp >> 4); }
+    else if (wp < 68) { src = w + d.pw1.b_off + 4 * (wp - 64); w_dst = kSegK3FWB1 + 4 * (wp - 64); }
+    else if (wp < 104) { src = w + d.dw.w_off + 4 * (wp - 68); w_dst = kSegK3FWDw + 4 * (wp - 68); }
+    else if (wp < 108) { src = w + d.dw.b_off + 4 * (wp - 104); w_dst = kSegK3FWDwB + 4 * (wp - 104); }
+    else if (wp < 172) { const int q = wp - 108; src = w + d.pw2.w_off + (unsigned)((q & 15) * d.pw2.cout_pad + 4 * (q >> 4)); w_dst = kSegK3FWPw2 + (q & 15) * kSegK3FWStride + 4 * (q >> 4); }
+    else { src = w + d.pw2.b_off + 4 * (wp - 172); w_dst = kSegK3FWB2 + 4 * (wp - 172); }
+    wv = ld4(src);
+  }
+  float g2 = 0.f;
+  if (tid >= 512 && tid < 528) g2 = fa[d.g_off + (tid - 512)];
+  // the tail gate's staging area, as seg_gate lays it out
+  const SegFc &f1 = gt.fc[0], &f2 = gt.fc[1];
+  const int w1n = f1.Cin * f1.Cout, w2n = gt.n_fc == 2 ? f2.Cin * f2.Cout : 0;
+  float* s_gate = smem + kScrGate;
+  float* s_mean = smem + kScrGate + 16;
+  float* s_hid = smem + kScrGate + 48;
+  float* ps = smem + L.stage_off;
+  float* w1 = ps + 512;
+  float* b1 = w1 + w1n;
+  float* w2 = b1 + f1.Cout;
+  float* b2 = w2 + w2n;
+  const int gc = tid & 15, gslice = tid >> 4;
+  if (tid < kSegThreads) {
+    {
+      const float* src = fa + gt.part[0].off;
+      float s = 0.f;
+#pragma unroll 4
+      for (int i = gslice; i < gt.part[0].n; i += 16) s += src[(unsigned)(i * 16 + gc)];
+      ps[gslice * 16 + gc] = s;
+    }
+    const float* g1 = w + f1.w_off;
+    const float* gw2 = w + f2.w_off;
+    for (int i = tid; i < w1n; i += kSegThreads) w1[i] = g1[(unsigned)i];
+    for (int i = tid; i < w2n; i += kSegThreads) w2[i] = gw2[(unsigned)i];
+    if (tid < f1.Cout) b1[tid] = (w + f1.b_off)[(unsigned)tid];
+    if (gt.n_fc == 2 && tid < f2.Cout) b2[tid] = (w + f2.b_off)[(unsigned)tid];
+  }
+#pragma unroll
+  for (int j = 0; j < kSegK3FLoPieces; j++) {
+    const int p = tid + kSegK3FThreads * j, pix = p >> 2, ly = pix / d.WL, lx = pix - ly * d.WL;
+    if (p < npl) st4(l_t + ly * LRW + col_l(lx, p & 3), lv[j]);
+  }
+  if (wp >= 0 && wp < kSegK3FWPieces) st4(sw + w_dst, wv);
+  if (tid >= 512 && tid < 528) s_g2[tid - 512] = g2;
+  __syncthreads();
+
+  // ---- phase A: z = act(pw1(skip * g + up(lo2))), zero outside the image (gated_compute's arithmetic; the window offsets ly0 / lx0 are 0: the whole of lo2 is here)
+  {
+    float wr[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) wr[r] = sw[(4 * g + r) * kSegK3FWStride + li];
+    const float4 bias = ld4(sw + kSegK3FWB1 + cq4);
+    const float4 gv = ld4(s_g2 + cq4);
+    const Clamp cl = clamp_of(d.pw1.act);
+#pragma unroll
+    for (int j = 0; j < kSegK3FRows; j++) {
+      const int t = wave + 16 * j;
+      if (t >= ntile) break;
+      const int zy = t / TX, tx = t - zy * TX, iy = zy - 1, ix = tx * d.TC - 1 + li;
+      int x0, x1, y0, y1;
+      float dx, dy;
+      up_axis(min(max(ix, 0), W - 1), d.ws, half_pixel, d.WL, &x0, &x1, &dx);
+      const int xo0 = col_l(x0, g), xo1 = col_l(x1, g);
+      const bool ecol_in = ix >= 0 && ix < W;
+      const bool row_in = iy >= 0 && iy < H;                           // scalar
+      up_axis(min(max(iy, 0), H - 1), d.hs, half_pixel, d.HL, &y0, &y1, &dy);
+      const float* l0 = l_t + y0 * LRW;
+      const float* l1 = l_t + y1 * LRW;
+      const float4 ta = ld4(l0 + xo0), tb = ld4(l1 + xo0), tc = ld4(l0 + xo1), td = ld4(l1 + xo1);
+      const float w00 = (1.f - dy) * (1.f - dx), w10 = dy * (1.f - dx), w01 = (1.f - dy) * dx, w11 = dy * dx;
+      const float4 s4 = sk[j];
+      float4 a;
+      a.x = fmaf(s4.x, gv.x, fmaf(td.x, w11, fmaf(tc.x, w01, fmaf(tb.x, w10, ta.x * w00))));
+      a.y = fmaf(s4.y, gv.y, fmaf(td.y, w11, fmaf(tc.y, w01, fmaf(tb.y, w10, ta.y * w00))));
+      a.z = fmaf(s4.z, gv.z, fmaf(td.z, w11, fmaf(tc.z, w01, fmaf(tb.z, w10, ta.z * w00))));
+      a.w = fmaf(s4.w, gv.w, fmaf(td.w, w11, fmaf(tc.w, w01, fmaf(tb.w, w10, ta.w * w00))));
+      const f4acc acc = mma16(a, wr);
+      float4 v = acc_quad(acc);
+      v = (ecol_in && row_in) ? clamp4(f4add(v, bias), cl) : f4zero();
+      st4(z_t + zy * ZRW + tx * 256 + col_a(li, g), v);
+    }
+  }
+  // ---- phase B: t = z + act(dw3x3(z)) on the MFMA's own lanes, straight into pw2 (seg_k3_k's loop; unit u = (tile u >> 2, that tile's wave u & 3))
+  {
+    const int pc = min(li, 13);
+    const int coz[3] = {col_a(pc, g), col_a(pc + 1, g), col_a(pc + 2, g)};
+    f4v wd[9];
+#pragma unroll
+    for (int k = 0; k < 9; k++) wd[k] = ldv(sw + kSegK3FWDw + k * 16 + cq4);
+    const f4v bias_d = ldv(sw + kSegK3FWDwB + cq4);
+    const Clamp cl_dw = clamp_of(d.dw.act), cl_2 = clamp_of(d.pw2.act);
+    float wr[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) wr[r] = sw[kSegK3FWPw2 + (4 * g + r) * kSegK3FWStride + li];
+    const float4 bias2 = ld4(sw + kSegK3FWB2 + cq4);
+    __syncthreads();
+    for (int u = wave; u < 4 * tiles; u += 16) {
+      const int t = u >> 2, ow = u & 3, ty = t / TX, tx = t - ty * TX, r0 = ty * d.TR, c0 = tx * d.TC;
+      const float* zb = z_t + tx * 256;                               // the tile's block: its row py + fy is frame row r0 + py + fy
+      float4 sum = f4zero();
+      for (int py = ow; py < d.TR && r0 + py < H; py += 4) {
+        const f4v zc = ldv(zb + (r0 + py + 1) * ZRW + coz[1]);
+        const float4 dv = clamp4(tof4(dw3x3(zb, ZRW, r0 + py, coz, wd) + bias_d), cl_dw);
+        const f4acc acc = mma16(f4add(dv, tof4(zc)), wr);
+        float4 v = acc_quad(acc);
+        if (li < d.TC && c0 + li < W) {
+          v = as_stored<H16>(clamp4(f4add(v, bias2), cl_2));
+          stg4<H16>(lo_out, (unsigned)(((r0 + py) * W + c0 + li) * 16 + cq4), v);
+          sum = f4add(sum, v);
+        }
+      }
+      wave_reduce16<0>(sum, s_red + t * 256, ow, lane);
+    }
+  }
+  __syncthreads();
+  if (tid < 16 * tiles) {                                             // store_partials, one tile per 16 lanes
+    const float* r = s_red + (tid >> 4) * 256;
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; j++) s += r[j * 16 + (tid & 15)];
+    (fa + d.part_lo_off)[tid] = s;
+    s_plo[tid] = s;
+  }
+  __syncthreads();
+  // ---- the tail's gate: seg_gate from its slice sums on, part 1 from LDS
+  if (tid < kSegThreads) {
+    float s = 0.f;
+#pragma unroll 4
+    for (int i = gslice; i < gt.part[1].n; i += 16) s += s_plo[i * 16 + gc];
+    ps[256 + gslice * 16 + gc] = s;
+  }
+  __syncthreads();
+  const int Cm = gt.sum_parts ? 16 : 16 * gt.n_parts;
+  if (tid < Cm) {
+    float m = 0.f;
+    for (int k = 0; k < gt.n_parts; k++) {
+      if (!gt.sum_parts && (tid >> 4) != k) continue;
+      float s = 0.f;
+#pragma unroll
+      for (int sl = 0; sl < 16; sl++) s += ps[k * 256 + sl * 16 + (tid & 15)];
+      m += s / gt.part[k].hw;
+    }
+    s_mean[tid] = m;
+  }
+  __syncthreads();
+  if (tid < kSegThreads) frame_gate_fc(f1, s_mean, w1, b1, gt.n_fc == 1 ? s_gate : s_hid, tid);
+  __syncthreads();
+  if (gt.n_fc == 2) {
+    if (tid < kSegThreads) frame_gate_fc(f2, s_hid, w2, b2, s_gate, tid);
+    __syncthreads();
+  }
+  if (tid < 16) fa[pre_gate_off + tid] = s_gate[tid];
+}
+#endif
+
+// ==================================================================================================================================
 // tail (decoder level 1 + output): g = gate(GAP(A), GAP(lo)); z = act(pw(A * g + up(lo))); t = z + act(dw3x3(z));
 // out = act3(Convolution2DTransposeBias 2x2 (t)) → logits (LOGITS) or straight into decode + temporal IIR on `ofinal`.
 // Tile = TR x TC (<= 14) at the A resolution = 2TR x 2TC output pixels.  Phase B lanes = the MFMA's: lane (li, g) = (pixel li of the tile row, channel
@@ -998,6 +1218,12 @@ hipError_t launch_seg_k3(hipFunction_t fn, const SegK3& d, float* arena, long pe
   int nf = xcd_frames(n);
   void* args[] = {(void*)&d, &arena, &per_frame, &weights, &nf};
   return seg_launch(fn, seg_k3_instance(h16), d.tiles_y * d.tiles_x, n, (size_t)d.lds_floats * sizeof(float), s, args);
+}
+// k3's per-frame form, the tail's gate included (bsx_seg_k3f of the specialised module, there where SegK3F::on): grid = frames, 1024 lanes, its LDS a static array.
+hipError_t launch_seg_k3_frame(hipFunction_t fn, const SegK3F& L, float* arena, long per_frame, const float* weights, int n, hipStream_t s) {
+  if (!fn || !L.on) return hipErrorInvalidValue;
+  void* args[] = {&arena, &per_frame, &weights};
+  return hipModuleLaunchKernel(fn, (unsigned)n, 1, 1, kSegK3FThreads, 1, 1, 0, s, args, nullptr);
 }
 // logits: the stage-debug variant, ahead of time only (the specialised tail is the decode-fused one)
 hipError_t launch_seg_tail(hipFunction_t fn, const SegTail& d, float* arena, long per_frame, float* net_out, uint8_t* ofinal, const float* weights, bool logits, int n,

@@ -736,6 +736,7 @@ static bool build_segments(Graph& g, Plan* plan) {
     if (t != g.output) plan->tensor_off[t] = -1;
   plan->arena_floats_per_stream = top;
   plan->seg_partials = {pA, pb0, pB, plo};
+  if (pgt >= 0) plan->seg_partials.push_back(pgt);   // (the tail's gate vector: written by the gate launch or by k3's per-frame form, readable like the partial sums)
   plan->seg_stored = {A, b0, B, c0, lo};             // written by head, head, k2, k2, k3 (lo2 and the level-2 gate are outputs of the middle program)
 
   h.a_off = plan->tensor_off[A]; h.b0_off = plan->tensor_off[b0]; h.part_a_off = plan->tensor_off[pA]; h.part_b0_off = plan->tensor_off[pb0];
@@ -754,6 +755,14 @@ static bool build_segments(Graph& g, Plan* plan) {
   if (const char* e = BSX_DBG_ENV("BSX_SEG_SKIP")) sscanf(e, "%d,%d,%d,%d", &h.dbg_skip, &k2.dbg_skip, &k3.dbg_skip, &tl.dbg_skip);      // "head,k2,k3,tail" phase masks
   tl.pre_gate_off = pgt >= 0 ? plan->tensor_off[pgt] : -1;
   if (tl.gate.fc[0].Cin != (tl.gate.sum_parts ? 16 : 32) || k2.gate.fc[0].Cin != 16) return seg_fail(27);
+  // k3's per-frame form where a frame's z, lo2, weights and scratch fit one CU's LDS (segments.hpp: seg_k3f_layout): one 1024-lane workgroup per frame does the tiles'
+  // work and finishes the tail's gate, so the gate launch goes too.  The tile descriptor above stays what it was: the fallback (BSX_K3_TILES=1, debug build — the A/B and
+  // the bit-identity reference of tests/test_gpu_k3_frame.py) and the geometry the per-frame form's partial sums are laid out by.
+  const char* k3f_why = "";
+  sp.k3f = seg_k3f_layout(k3);
+  if (!sp.k3f.on) k3f_why = sp.k3f.lds_floats > 160 * 256 ? "a frame does not fit the LDS" : "the shape is outside the per-frame kernel's limits";
+  else if (pgt < 0 || tl.gate.timing_skip || k3.dbg_skip) { sp.k3f.on = 0; k3f_why = "a debug switch of the gate or of k3 is set"; }
+  else if (BSX_DBG_ENV("BSX_K3_TILES")) { sp.k3f.on = 0; k3f_why = "switched off"; }
 
   // ---- the middle: steps 9 .. NS-15, then the level-2 gate with its pooled inputs replaced: GAP(B) arrives as partial sums
   //      from k2, GAP(up2) == GAP(lo2) (uniform 2x interpolation weights)
@@ -795,6 +804,11 @@ static bool build_segments(Graph& g, Plan* plan) {
   k2_note[0] = 0;
   add("k3", k3.TR, k3.TC, k3.tiles_y, k3.tiles_x, k3.lds_floats, {lo}); add("tail", tl.TR, tl.TC, tl.tiles_y, tl.tiles_x, tl.lds_floats, {});
   snprintf(line, sizeof line, "segment partial sums ([tiles][16] f32): A t%d, b0 t%d, B t%d, lo t%d\n", pA, pb0, pB, plo);
+  plan->seg_text += line;
+  // which form of k3 runs (the "tile" line above is the tile form's geometry either way)
+  if (sp.k3f.on) snprintf(line, sizeof line, "segment k3 form: per-frame, one %d-lane workgroup per frame, LDS %d B, finishes gate(tail) t%d\n", kSegK3FThreads, sp.k3f.lds_floats * 4, pgt);
+  else if (pgt >= 0) snprintf(line, sizeof line, "segment k3 form: tiles, then a launch for gate(tail) t%d (%s; per-frame LDS %d B)\n", pgt, k3f_why, sp.k3f.lds_floats * 4);
+  else snprintf(line, sizeof line, "segment k3 form: tiles, the gate inside the tail (%s)\n", k3f_why);
   plan->seg_text += line;
   return true;
 }

@@ -184,11 +184,59 @@ inline int seg_k3_lds_floats(const SegK3& d) { return kSegScratchFloats + (d.TR 
 inline int seg_tail_lds_floats(const SegTail& d) { const int v = (d.TR + 2) * 256; return kSegScratchFloats + (v > kSegGateStageFloats ? v : kSegGateStageFloats) + (d.lo_floats > 0 ? d.lo_floats : kSegLoTileFloats); }
 #endif
 
+// ---- k3, per-frame form (seg_k3_frame: one 1024-lane workgroup per frame, the tail's gate finished in the same launch) ------------------------------------------
+// Where a frame's whole z fits one CU's LDS the six-odd tile workgroups of a frame — each a chain of prefetch, barrier, weight round trip, MFMAs, weight round trip,
+// barrier, depthwise, reduce, barrier — become ONE chain per frame on 16 waves, every weight staged in LDS by the first loads, and the workgroup that has just summed
+// lo finishes the tail's gate (seg_gate's arithmetic) instead of a launch of its own.  LDS, in floats from seg_smem:
+//   [0, kSegScratchFloats)  the gate's scratch (kScrGate ..) and the level-2 gate vector at kSegK3FGate
+//   z_off      z = act(pw1(..)) of the whole frame as [H2 + 2][tiles_x][16 columns][16]: block tx holds columns tx * TC - 1 .. tx * TC + 14, exactly the window the tile
+//              form's tile computes (two columns per tile boundary are computed twice, at no extra MFMA tile where 16 * tiles_x covers them anyway); rows once
+//   lo_off     lo2, whole: [HL][WL][16] in the col_l layout
+//   w_off      pw1 tile (16 rows at kSegStageStride) + bias, depthwise 9 x 16 + bias, pw2 tile + bias (kSegK3FW*)
+//   red_off    [tiles][16 slots][16]: the meeting points of wave_reduce16, one set per tile of the tile form — the partial sums keep that form's additions and order
+//   plo_off    [tiles][16] partial sums of lo (also stored at part_lo_off), part 1 of the tail's gate
+//   stage_off  seg_gate's staging area (kSegGateStageFloats)
+constexpr int kSegK3FThreads = 1024;
+constexpr int kSegK3FRows = 5;                    // phase A: row tiles (one z row x 16 columns) per wave
+constexpr int kSegK3FLoPieces = 2;                // 16-byte pieces of lo2 per lane
+constexpr int kSegK3FGate = 80;                   // the level-2 gate vector inside the scratch block (behind the tail gate's vector, means and hidden layer)
+constexpr int kSegK3FWStride = 20;                // = kSegStageStride: rows of a staged 1x1 tile (4 mod 8: the operand reads are conflict-free)
+constexpr int kSegK3FWB1 = 16 * kSegK3FWStride;   // the staged weight block, floats from w_off: pw1's tile at 0, its bias here,
+constexpr int kSegK3FWDw = kSegK3FWB1 + 16;       // the depthwise weights [9][16],
+constexpr int kSegK3FWDwB = kSegK3FWDw + 9 * 16;  // their bias,
+constexpr int kSegK3FWPw2 = kSegK3FWDwB + 16;     // pw2's tile
+constexpr int kSegK3FWB2 = kSegK3FWPw2 + 16 * kSegK3FWStride;   // and bias
+constexpr int kSegK3FWFloats = kSegK3FWB2 + 16;
+constexpr int kSegK3FWPieces = kSegK3FWFloats / 4 - 2 * 16;     // 16-byte pieces the copy moves (a tile row is 16 of its 20 floats)
+struct SegK3F {
+  int on = 0;                                     // the planner takes the form: the shape fits (seg_k3f_layout) and nothing switches it off
+  int lds_floats = 0;
+  int z_off = 0, lo_off = 0, w_off = 0, red_off = 0, plo_off = 0, stage_off = 0;
+};
+// The layout for k3's geometry; on = the form fits: at most kSegK3FRows row tiles per wave, lo2 in kSegK3FLoPieces pieces per lane, one lane per partial sum, weights
+// that move in 16-byte pieces, and everything within 160 KiB.  Evaluated by the planner and, as a constant expression, by the graph-specialised kernel.
+constexpr SegK3F seg_k3f_layout(const SegK3& d) {
+  SegK3F L;
+  const int tiles = d.tiles_y * d.tiles_x, waves = kSegK3FThreads / 64;
+  L.z_off = kSegScratchFloats;
+  L.lo_off = L.z_off + (d.H2 + 2) * d.tiles_x * 256;
+  L.w_off = L.lo_off + d.HL * d.WL * kSegLoStride;
+  L.red_off = L.w_off + kSegK3FWFloats;
+  L.plo_off = L.red_off + tiles * 256;
+  L.stage_off = L.plo_off + tiles * 16;
+  L.lds_floats = L.stage_off + kSegGateStageFloats;
+  L.on = tiles >= 1 && tiles * 16 <= kSegK3FThreads && (d.H2 + 2) * d.tiles_x <= waves * kSegK3FRows && d.HL * d.WL * 4 <= kSegK3FLoPieces * kSegK3FThreads &&
+         d.TC <= 14 && d.pw1.cout_pad % 4 == 0 && d.pw2.cout_pad % 4 == 0 && d.pw1.w_off % 4 == 0 && d.pw2.w_off % 4 == 0 && d.pw1.b_off % 4 == 0 && d.pw2.b_off % 4 == 0 &&
+         d.dw.w_off % 4 == 0 && d.dw.b_off % 4 == 0 && d.dw.C == 16 && L.lds_floats <= 160 * 256;
+  return L;
+}
+
 struct SegPlan {
   bool on = false;
   SegHead head;
   SegK2 k2;
   SegK3 k3;
+  SegK3F k3f;                                     // k3's per-frame form (k3f.on: it runs in k3's place and the tail's gate launch is dropped)
   SegTail tail;
 };
 

@@ -65,7 +65,7 @@ void build_seg(const Plan& plan, KernelVariant v, const std::string& arch, Speci
 bool load_module(const std::vector<char>& code, const char* const* names, int n, hipModule_t* mod, hipFunction_t* fn) {
   hipModule_t m = nullptr;
   if (hipModuleLoadData(&m, code.data()) != hipSuccess) { (void)hipGetLastError(); return false; }
-  hipFunction_t f[4] = {};
+  hipFunction_t f[5] = {};
   for (int i = 0; i < n; i++) {
     if (hipModuleGetFunction(&f[i], m, names[i]) != hipSuccess) { (void)hipModuleUnload(m); (void)hipGetLastError(); return false; }
   }
@@ -80,6 +80,7 @@ SpecialisedBuild build_specialised(const Plan& plan, KernelVariant v, const std:
   SpecialisedBuild b;
   if (parts & kBuildMid) build_mid(plan, v.act16, arch, &b);
   if (parts & kBuildSeg) build_seg(plan, v, arch, &b.seg);
+  b.seg_k3_frame = plan.seg.on && plan.seg.k3f.on;
   return b;
 }
 
@@ -90,7 +91,7 @@ void no_specialised(const char* why, SpecialisedKernels* k) {
 
 void load_specialised(const SpecialisedBuild& b, SpecialisedKernels* k) {
   static const char* const kMid[] = {"bsx_mid"};
-  static const char* const kSeg[] = {"bsx_seg_head", "bsx_seg_k2", "bsx_seg_k3", "bsx_seg_tail"};
+  static const char* const kSeg[] = {"bsx_seg_head", "bsx_seg_k2", "bsx_seg_k3", "bsx_seg_tail", "bsx_seg_k3f"};
   k->mid_note = b.mid.fallback;
   if (!b.mid.code.empty()) {
     if (!load_module(b.mid.code, kMid, 1, &k->mid_mod, &k->mid)) k->mid_note = "interpreted (code object did not load)";
@@ -99,8 +100,13 @@ void load_specialised(const SpecialisedBuild& b, SpecialisedKernels* k) {
   }
   k->seg_note = b.seg.fallback;
   if (!b.seg.code.empty()) {
-    if (!load_module(b.seg.code, kSeg, 4, &k->seg_mod, k->seg)) k->seg_note = "ahead-of-time kernels (code object did not load)";
-    else k->seg_note = std::string("specialised kernels (hipRTC") + (b.seg.cached ? ", from the cache)" : ", compiled now)");
+    hipFunction_t fn[5] = {};
+    if (!load_module(b.seg.code, kSeg, b.seg_k3_frame ? 5 : 4, &k->seg_mod, fn)) k->seg_note = "ahead-of-time kernels (code object did not load)";
+    else {
+      std::copy(fn, fn + 4, k->seg);
+      k->k3_frame = fn[4];
+    }
+    if (k->seg_mod) k->seg_note = std::string("specialised kernels (hipRTC") + (b.seg.cached ? ", from the cache)" : ", compiled now)");
   }
 }
 

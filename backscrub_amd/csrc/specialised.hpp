@@ -35,6 +35,7 @@ struct SpecialisedCode {
 struct SpecialisedBuild {
   SpecialisedCode mid, seg;
   bool opaque_tid = false;    // the middle kernel's form
+  bool seg_k3_frame = false;  // the segment source has bsx_seg_k3f (the plan takes k3's per-frame form)
   long scratch = -1;          // the middle kernel's scratch bytes per lane, from its kernel descriptor (-1: unreadable)
 };
 enum : unsigned { kBuildMid = 1, kBuildSeg = 2 };
@@ -45,6 +46,7 @@ struct SpecialisedKernels {
   hipModule_t mid_mod = nullptr, seg_mod = nullptr;
   hipFunction_t mid = nullptr;
   hipFunction_t seg[4] = {};      // bsx_seg_head, bsx_seg_k2, bsx_seg_k3, bsx_seg_tail
+  hipFunction_t k3_frame = nullptr;   // bsx_seg_k3f: part of the segment module where the plan takes k3's per-frame form (SegPlan::k3f.on), loaded with the four or not at all
   std::string mid_note, seg_note; // plan(): "program execution: <mid_note>", "segment execution: <seg_note>"
 };
 // Nothing specialised, for `why` (BSX_NO_RTC, no device properties).

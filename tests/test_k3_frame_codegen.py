@@ -1,0 +1,170 @@
+"""k3's per-frame form (csrc/segments.hpp: SegK3F / seg_k3f_layout, csrc/kernels_seg.hip: bsx_seg_k3f) — what can be checked without a GPU.
+
+Where a frame's z, lo2, the weights and the scratch fit one CU's LDS, one 1024-lane workgroup per frame does the work of seg_k3_k's tiles and finishes the tail's gate:
+segm_lite takes the form, segm_full and MLKit keep the tiles and the gate launch.  The kernel is part of the graph-specialised module; it stages every weight in LDS
+with its first loads."""
+import os
+import re
+import subprocess
+
+import pytest
+
+from conftest import ROOT, model_path
+
+HIPCC = "/opt/rocm/bin/hipcc"
+CSRC = os.path.join(ROOT, "backscrub_amd", "csrc")
+LDS_CU = 160 * 1024
+
+FRAME_LINE = r"^segment k3 form: per-frame, one 1024-lane workgroup per frame, LDS (\d+) B, finishes gate\(tail\) t(\d+)$"
+TILES_LINE = r"^segment k3 form: tiles, then a launch for gate\(tail\) t(\d+) \((.*); per-frame LDS (\d+) B\)$"
+TILE_RE = r"segment \w+\s+tile"
+
+
+@pytest.fixture(scope="module")
+def api():
+    from backscrub_amd import api as a
+    a.lib()
+    return a
+
+
+@pytest.fixture(scope="module")
+def lite(api, tmp_path_factory):
+    """(specialised source of segm_lite, its assembly for gfx950), compiled once"""
+    src = api.model_seg_source(model_path("lite"))
+    p = tmp_path_factory.mktemp("k3f") / "seg.hip"
+    p.write_text(src)
+    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "--cuda-device-only", "-S", "-o", str(p) + ".s", str(p)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return src, open(str(p) + ".s").read()
+
+
+def k3_constants(src):
+    blk = src[src.index("constexpr SegK3 kSegK3 = [] {"):]
+    blk = blk[:blk.index("return t; }();")]
+    return {k: int(v) for k, v in re.findall(r"t\.([\w.\[\]]+) = (-?\d+)(?:ll|u)?;", blk)}
+
+
+def header_constants():
+    hdr = open(os.path.join(CSRC, "segments.hpp")).read()
+    env = {}
+    for name, expr in re.findall(r"constexpr int (kSeg(?:K3F\w+|ScratchFloats|GateStageFloats)) = ([^;]+);", hdr):
+        env[name] = eval(expr.replace("/", "//"), {}, env)                                               # noqa: S307 — integer expressions over earlier constants
+    return env
+
+
+def test_the_planner_takes_the_form_where_a_frame_fits(api, lite):
+    d = api.model_describe(model_path("lite"))
+    m = re.search(FRAME_LINE, d, re.M)
+    assert m, d
+    lds = int(m.group(1))
+    assert lds <= LDS_CU
+    # the figure is the layout's: scratch + z [H2 + 2][tiles_x][16][16] + lo2 + weights + meeting points + partial sums + the gate's staging area
+    k, c = k3_constants(lite[0]), header_constants()
+    tiles = k["tiles_y"] * k["tiles_x"]
+    z, lo2 = (k["H2"] + 2) * k["tiles_x"] * 256, k["HL"] * k["WL"] * 16
+    assert lds == 4 * (c["kSegScratchFloats"] + z + lo2 + c["kSegK3FWFloats"] + tiles * 256 + tiles * 16 + c["kSegGateStageFloats"])
+    assert (k["H2"] + 2) * k["tiles_x"] <= 16 * c["kSegK3FRows"]                                          # at most 5 row tiles per wave in phase A
+    # the gate tensor the line names is the synthetic one behind the partial sums
+    ps = re.search(r"^segment partial sums .* lo t(\d+)$", d, re.M)
+    assert ps and int(m.group(2)) == int(ps.group(1)) + 1
+    for key in ("full", "mlkit"):
+        d = api.model_describe(model_path(key))
+        t = re.search(TILES_LINE, d, re.M)
+        assert t and not re.search(FRAME_LINE, d, re.M), d
+        assert int(t.group(3)) > LDS_CU and "does not fit" in t.group(2)
+        assert "#define BSXS_SEG_K3F 0\n" in api.model_seg_source(model_path(key))                      # the kernel's text is compiled out of their modules
+    assert "#define BSXS_SEG_K3F 1\n" in lite[0]
+
+
+@pytest.mark.parametrize("key", ["lite", "full", "mlkit"])
+def test_the_tile_lines_still_parse_and_the_new_line_is_not_one_of_them(api, key):
+    d = api.model_describe(model_path(key))
+    kib = {m.group(1): float(m.group(2)) for m in re.finditer(r"segment (\w+)\s+tile \S+ \S+ tiles per frame, LDS ([\d.]+) KiB", d)}
+    assert set(kib) == {"head", "k2", "k3", "tail"}, kib
+    new = [l for l in d.splitlines() if l.startswith("segment k3 form:")]
+    assert len(new) == 1 and not re.search(TILE_RE, new[0]) and " stores t" not in new[0]
+    assert len([l for l in d.splitlines() if re.match(TILE_RE, l)]) == 4
+
+
+def test_the_code_object(lite):
+    src, asm = lite
+    for k in ("bsx_seg_head", "bsx_seg_k2", "bsx_seg_k3", "bsx_seg_tail", "bsx_seg_k3f"):
+        assert ".amdhsa_kernel %s\n" % k in asm, k
+    blk = asm[asm.index(".amdhsa_kernel bsx_seg_k3f"):]
+    blk = blk[:blk.index(".end_amdhsa_kernel")]
+    vg = int(re.search(r"\.amdhsa_next_free_vgpr (\d+)", blk).group(1))
+    sc = int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", blk).group(1))
+    lds = int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", blk).group(1))
+    assert sc == 0 and vg <= 128, (vg, sc)                                                                 # 16 waves per CU
+    k, c = k3_constants(src), header_constants()
+    assert lds <= LDS_CU and lds >= 4 * (k["H2"] + 2) * k["tiles_x"] * 256
+    # every global read sits in front of the first barrier; behind it the kernel reads LDS and stores lo, its partial sums and the gate vector
+    body = asm[asm.index("\nbsx_seg_k3f:"):asm.index(".amdhsa_kernel bsx_seg_k3f")]
+    first = body.index("s_barrier")
+    assert len(re.findall(r"^\s+global_load_", body[:first], re.M)) >= c["kSegK3FRows"] + 3
+    assert not re.findall(r"^\s+(?:global|buffer|flat|scratch)_load_", body[first:], re.M)
+    assert re.findall(r"^\s+v_mfma_f32_16x16x4", body, re.M) and re.findall(r"^\s+global_store_dwordx4 ", body[first:], re.M)
+
+
+# ---- bank model (MI355X LDS), as in tests/test_k2_staging.py: ds_read_b32 = two groups of 32 lanes over 32 banks; ds_read_b128 = four groups of 16 lanes over 16
+#      16-byte slots; ds_write_b128 = eight groups of eight consecutive lanes over eight slots
+G32 = [list(range(0, 32)), list(range(32, 64))]
+G128 = [[0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27], [4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31]]
+G128 = G128 + [[l + 32 for l in g] for g in G128]
+W128 = [list(range(8 * k, 8 * k + 8)) for k in range(8)]
+
+
+def cycles(groups, unit, nslots, addr_of_lane, active=lambda l: True):
+    tot = 0
+    for grp in groups:
+        slots = {}
+        for l in grp:
+            if active(l):
+                a = addr_of_lane(l)
+                assert a % unit == 0
+                slots.setdefault((a // unit) % nslots, set()).add(a)
+        tot += max([len(v) for v in slots.values()] + [1])
+    return tot
+
+
+def test_the_staged_weights_are_read_and_copied_without_bank_conflicts(lite):
+    c = header_constants()
+    k = k3_constants(lite[0])
+    kern = open(os.path.join(CSRC, "kernels_seg.hip")).read()
+    S = c["kSegK3FWStride"]
+    assert S % 8 == 4 and S >= 16 and c["kSegK3FWB1"] == 16 * S and c["kSegK3FWDw"] == c["kSegK3FWB1"] + 16 and c["kSegK3FWDwB"] == c["kSegK3FWDw"] + 144
+    assert c["kSegK3FWPw2"] == c["kSegK3FWDwB"] + 16 and c["kSegK3FWB2"] == c["kSegK3FWPw2"] + 16 * S and c["kSegK3FWFloats"] == c["kSegK3FWB2"] + 16
+    assert c["kSegK3FWPieces"] == 2 * (64 + 4) + 36 + 4
+    # the kernel's own index expressions
+    read1, read2 = "(4 * g + r) * kSegK3FWStride + li", "kSegK3FWPw2 + (4 * g + r) * kSegK3FWStride + li"
+    assert "wr[r] = sw[%s];" % read1 in kern and "wr[r] = sw[%s];" % read2 in kern
+    assert "wd[k] = ldv(sw + kSegK3FWDw + k * 16 + cq4);" in kern and "ld4(sw + kSegK3FWB1 + cq4)" in kern and "ld4(sw + kSegK3FWB2 + cq4)" in kern
+    st1, st2 = "(wp & 15) * kSegK3FWStride + 4 * (wp >> 4)", "kSegK3FWPw2 + (q & 15) * kSegK3FWStride + 4 * (q >> 4)"
+    assert "w_dst = %s;" % st1 in kern and "w_dst = %s;" % st2 in kern
+    tiles = k["tiles_y"] * k["tiles_x"]
+    w_off = c["kSegScratchFloats"] + (k["H2"] + 2) * k["tiles_x"] * 256 + k["HL"] * k["WL"] * 16      # seg_k3f_layout
+    assert w_off % 4 == 0 and tiles >= 1
+    for base, read, store in ((0, read1, st1), (c["kSegK3FWPw2"], read2, st2)):
+        rd = eval("lambda g, r, li: " + read, dict(c))                                                   # noqa: S307
+        for r in range(4):
+            assert cycles(G32, 1, 32, lambda l: w_off + rd(l >> 4, r, l & 15)) == 2                        # one cycle per group of 32 lanes
+            assert cycles(G32, 1, 32, lambda l: w_off + base + (4 * (l >> 4) + r) * 16 + (l & 15)) == 4    # a dense tile would be 2-way
+        stv = eval("lambda wp, q: " + store, dict(c))                                                    # noqa: S307
+        cells = sorted(stv(p, p) for p in range(64))
+        assert cells == sorted(base + row * S + 4 * q for row in range(16) for q in range(4))              # every cell of the tile once
+        assert cycles(W128, 4, 8, lambda l: w_off + stv(l, l)) == 8                                        # 64 pieces = one wave's worth: eight lanes on eight slots
+    for off in [c["kSegK3FWDw"] + 16 * tap for tap in range(9)] + [c["kSegK3FWDwB"], c["kSegK3FWB1"], c["kSegK3FWB2"]]:
+        assert cycles(G128, 4, 16, lambda l: w_off + off + 4 * (l >> 4)) == 4                              # one quad per row of 16 lanes: a broadcast
+    # the copy of the depthwise block and the biases: consecutive pieces, consecutive lanes
+    assert cycles(W128, 4, 8, lambda l: w_off + c["kSegK3FWDw"] + 4 * l, lambda l: l < 36) == 8
+
+
+def test_the_debug_switch_forces_the_tile_form_and_is_not_in_the_release_library(api, monkeypatch, debug_switches):
+    from backscrub_amd import build
+    assert re.search(FRAME_LINE, api.model_describe(model_path("lite")), re.M)
+    monkeypatch.setenv("BSX_K3_TILES", "1")
+    d = api.model_describe(model_path("lite"))
+    t = re.search(TILES_LINE, d, re.M)
+    assert t and not re.search(FRAME_LINE, d, re.M) and int(t.group(3)) <= LDS_CU, d
+    assert "#define BSXS_SEG_K3F 0\n" in api.model_seg_source(model_path("lite"))
+    assert b"BSX_K3_TILES" not in open(build.LIB, "rb").read() and b"BSX_K3_TILES" in open(build.LIB_DBG, "rb").read()
