@@ -8,6 +8,7 @@ then a shared-library link.  The .so is git-ignored but travels to the GPU box.
 from __future__ import annotations
 
 import os
+import re
 import subprocess
 import sys
 
@@ -20,7 +21,7 @@ LIB = os.path.join(HERE, "libbsx.so")
 OBJ_DBG = os.path.join(CSRC, "build_dbg")
 LIB_DBG = os.path.join(HERE, "libbsx_dbg.so")
 SOURCES = ["tflite_model.cpp", "plan.cpp", "gen_mid.cpp", "gen_seg.cpp", "rtc.cpp", "specialised.cpp", "media.cpp", "jpeg.cpp", "live.cpp", "kernels_nn.hip", "kernels_img.hip", "kernels_frame.hip", "kernels_seg.hip", "bsx_api.hip"]
-HEADERS = ["mid_prelude.hip", "vcam_tile.inc", "prep_tile.inc", "tile_class.inc", "mask_tile.inc", "debug_switches.hpp", "gen_mid.hpp", "gen_seg.hpp", "rtc.hpp", "specialised.hpp", "media.hpp", "refusal.hpp", "tflite_model.hpp", "plan.hpp", "kernels.hpp", "frame_program.hpp", "segments.hpp", "mfma_tile.hpp", "roctx_ranges.hpp", os.path.join("..", "..", "include", "bsx.h")]
+HEADERS = ["mid_prelude.hip", "vcam_tile.inc", "prep_tile.inc", "tile_class.inc", "mask_tile.inc", "seg_gate.inc", "seg_gated_row.inc", "seg_k3_rows.inc", "debug_switches.hpp", "gen_mid.hpp", "gen_seg.hpp", "rtc.hpp", "specialised.hpp", "media.hpp", "refusal.hpp", "tflite_model.hpp", "plan.hpp", "kernels.hpp", "frame_program.hpp", "segments.hpp", "mfma_tile.hpp", "roctx_ranges.hpp", os.path.join("..", "..", "include", "bsx.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
          "-Wno-unused-result", "-fvisibility=hidden", "-fvisibility-inlines-hidden"]      # only the BSX_API entry points of include/bsx.h are exported
@@ -79,18 +80,29 @@ typedef unsigned int uint32_t;
 """
 
 
-def embed_seg_source():
-    """csrc/segments.hpp + mfma_tile.hpp + kernels_seg.hip → <objdir>/seg_rtc_src.inc: ONE flattened, comment-stripped text as a C++ raw string literal (gen_seg.cpp) —
-    what hipRTC compiles, with the loaded graph's descriptors as constants, when a context is created.  The files guard their host-only parts with __HIPCC_RTC__."""
-    parts = [SEG_RTC_PREAMBLE]
-    for f in ("segments.hpp", "mfma_tile.hpp", "kernels_seg.hip"):
+def seg_rtc_text():
+    """The hipRTC translation unit of the segment kernels: csrc/segments.hpp + mfma_tile.hpp + kernels_seg.hip flattened and comment-stripped, a local
+    `#include "name.inc"` (a body several kernels share: seg_gated_row.inc, seg_k3_rows.inc) spliced in place — hipRTC has no include path to find it on."""
+    def flat(f):
         t = strip_line_comments(open(os.path.join(CSRC, f)).read())
-        t = "\n".join(l for l in t.split("\n") if l.strip() != "#pragma once")
-        parts.append(t)
-    text = "\n".join(parts)
+        lines = []
+        for l in t.split("\n"):
+            m = re.fullmatch(r'\s*#include "(\w+\.inc)"\s*', l)
+            if m:
+                lines.append(flat(m.group(1)))
+            elif l.strip() != "#pragma once":
+                lines.append(l)
+        return "\n".join(lines)
+    text = "\n".join([SEG_RTC_PREAMBLE] + [flat(f) for f in ("segments.hpp", "mfma_tile.hpp", "kernels_seg.hip")])
     # every macro of the embedded text gets its own prefix: the release library's strings carry no BSX_ name but the documented user modes (tests/test_cabi.py)
-    text = text.replace("BSX_", "BSXS_")
-    assert ')BSXSEG"' not in text and "BSXS_SEG_CONSTANTS" in text
+    return text.replace("BSX_", "BSXS_")
+
+
+def embed_seg_source():
+    """seg_rtc_text() → <objdir>/seg_rtc_src.inc as a C++ raw string literal (gen_seg.cpp) — what hipRTC compiles, with the loaded graph's descriptors as constants,
+    when a context is created.  The files guard their host-only parts with __HIPCC_RTC__."""
+    text = seg_rtc_text()
+    assert ')BSXSEG"' not in text and "BSXS_SEG_CONSTANTS" in text and ".inc" not in text
     # string literals are limited in length by some compilers: cut into adjacent raw strings (concatenated by the compiler)
     chunks = [text[i:i + 8000] for i in range(0, len(text), 8000)]
     body = "\n".join('R"BSXSEG(' + c + ')BSXSEG"' for c in chunks) + "\n"

@@ -169,69 +169,25 @@ constexpr int kGateStageFloats = kSegGateStageFloats;
 struct NoPublish { __device__ __forceinline__ void operator()() const {} };
 template <class Publish = NoPublish>
 __device__ __forceinline__ void seg_gate(const SegGate& gt, const float* __restrict__ fa, const float* __restrict__ w, float* scr, float* stage, Publish publish = Publish()) {
-  float* s_gate = scr + kScrGate;
-  if (gt.timing_skip) { if (threadIdx.x < 16) s_gate[threadIdx.x] = 0.5f; publish(); __syncthreads(); return; }      // upper bound of what hoisting the gate out could buy
-  float* s_mean = scr + kScrGate + 16;
-  float* s_hid = scr + kScrGate + 48;
+  if (gt.timing_skip) { if (threadIdx.x < 16) scr[kScrGate + threadIdx.x] = 0.5f; publish(); __syncthreads(); return; }      // upper bound of what hoisting the gate out could buy
   const int tid = threadIdx.x;
-  const SegFc &f1 = gt.fc[0], &f2 = gt.fc[1];
-  const int w1n = f1.Cin * f1.Cout, w2n = gt.n_fc == 2 ? f2.Cin * f2.Cout : 0;
-  float* ps = stage;                      // [2 parts][16 slices][16 channels] slice sums (every pooled tensor here has 16 channels)
-  float* w1 = ps + 512;
-  float* b1 = w1 + w1n;
-  float* w2 = b1 + f1.Cout;
-  float* b2 = w2 + w2n;
-  {
-    const int c = tid & 15, slice = tid >> 4;
-    for (int k = 0; k < gt.n_parts; k++) {
-      const float* src = fa + gt.part[k].off;
-      float s = 0.f;
-#pragma unroll 4
-      for (int i = slice; i < gt.part[k].n; i += 16) s += src[(unsigned)(i * 16 + c)];
-      ps[k * 256 + slice * 16 + c] = s;
-    }
-  }
-  {
-    const float* g1 = w + f1.w_off;
-    const float* g2 = w + f2.w_off;
-    for (int i = tid; i < w1n; i += kSegThreads) w1[i] = g1[(unsigned)i];
-    for (int i = tid; i < w2n; i += kSegThreads) w2[i] = g2[(unsigned)i];
-    if (tid < f1.Cout) b1[tid] = (w + f1.b_off)[(unsigned)tid];
-    if (gt.n_fc == 2 && tid < f2.Cout) b2[tid] = (w + f2.b_off)[(unsigned)tid];
-  }
+#define BSX_GATE_SCR scr
+#define BSX_GATE_STAGE stage
+#define BSX_GATE_SRC(k) fa + gt.part[k].off
+#define BSX_GATE_K k
+#define BSX_GATE_FC_LANE true
+#define BSX_GATE_FC_CAPTURE &
+#define BSX_GATE_PART 1
+#include "seg_gate.inc"
+  for (int k = 0; k < gt.n_parts; k++)
+#define BSX_GATE_PART 2
+#include "seg_gate.inc"
+#define BSX_GATE_PART 3
+#include "seg_gate.inc"
   publish();
   __syncthreads();
-  const int Cm = gt.sum_parts ? 16 : 16 * gt.n_parts;
-  if (tid < Cm) {
-    float m = 0.f;
-    for (int k = 0; k < gt.n_parts; k++) {
-      if (!gt.sum_parts && (tid >> 4) != k) continue;
-      float s = 0.f;
-#pragma unroll
-      for (int sl = 0; sl < 16; sl++) s += ps[k * 256 + sl * 16 + (tid & 15)];
-      m += s / gt.part[k].hw;
-    }
-    s_mean[tid] = m;
-  }
-  __syncthreads();
-  // FC layers: lane = (output, slice of the inputs) — 8 consecutive lanes share an output and meet through DPP.  (One lane per output walked
-  // its whole weight row with a stride of Cin floats: every lane on the same two LDS banks, a 16-way conflict per step, 2 us per layer.)
-  auto fc = [&](const SegFc& f, const float* x, const float* wl, const float* bl, float* y) {
-    const int out = tid >> 3, ks = tid & 7, kper = f.Cin >> 3;               // Cin is 16 or 32 (checked by the planner)
-    float acc = 0.f;
-    if (out < f.Cout)
-      for (int j = 0; j < kper; j++) acc = fmaf(x[ks * kper + j], wl[out * f.Cin + ks * kper + j], acc);
-    acc += dpp_quad(acc, 1);
-    acc += dpp_quad(acc, 2);
-    acc += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, acc), 0x141, 0xf, 0xf, true));   // row_half_mirror: both quads of the 8
-    if (out < f.Cout && ks == 0) y[out] = sg_act(acc + bl[out], f.act);
-  };
-  fc(f1, s_mean, w1, b1, gt.n_fc == 1 ? s_gate : s_hid);
-  __syncthreads();
-  if (gt.n_fc == 2) {
-    fc(f2, s_hid, w2, b2, s_gate);
-    __syncthreads();
-  }
+#define BSX_GATE_PART 4
+#include "seg_gate.inc"
 }
 
 // ---- per-tile partial sums of a 16-channel tensor → partials[tile][16] -------------------------------------------------------
@@ -257,11 +213,12 @@ __device__ __forceinline__ void wave_reduce16(float4 v, float* s_red, int wave, 
     if ((lane & 12) == 12) st4(s_red + (wave * 4 + (lane >> 4)) * 16 + 4 * (lane & 3), v);     // slot (wave, row), channels 4 * quad
   }
 }
+// s += channel c of a tile's 16 slots, in slot order.  (A macro: as a function it moved the code of k3's per-frame form — tools/isa_same.py.)
+#define BSX_SLOTS_SUM16(s, s_red, c) _Pragma("unroll") for (int j = 0; j < 16; j++) s += (s_red)[j * 16 + (c)]
 __device__ __forceinline__ void store_partials(const float* s_red, float* dst /* 16 floats */) {   // after a barrier
   if (threadIdx.x < 16) {
     float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < 16; j++) s += s_red[j * 16 + threadIdx.x];
+    BSX_SLOTS_SUM16(s, s_red, threadIdx.x);
     dst[threadIdx.x] = s;
   }
 }
@@ -747,24 +704,10 @@ __device__ __forceinline__ void gated_compute(const GatedPre& pre, const float* 
   for (int j = 0; j < kGatedRows; j++) {
     const int zy = wave + 4 * j, iy = r0 - 1 + zy;
     if (zy >= ZH) break;
-    const bool row_in = iy >= 0 && iy < H;                           // scalar
-    int y0, y1;
-    float dy;
-    up_axis(min(max(iy, 0), H - 1), hs, half_pixel, HL, &y0, &y1, &dy);
-    const float* l0 = l_t + (y0 - pre.ly0) * pre.LC * kLoStride;
-    const float* l1 = l_t + (y1 - pre.ly0) * pre.LC * kLoStride;
-    const float4 ta = ld4(l0 + xo0), tb = ld4(l1 + xo0), tc = ld4(l0 + xo1), td = ld4(l1 + xo1);
-    const float w00 = (1.f - dy) * (1.f - dx), w10 = dy * (1.f - dx), w01 = (1.f - dy) * dx, w11 = dy * dx;
-    const float4 sk = pre.s[j];
-    float4 a;
-    a.x = fmaf(sk.x, gv.x, fmaf(td.x, w11, fmaf(tc.x, w01, fmaf(tb.x, w10, ta.x * w00))));
-    a.y = fmaf(sk.y, gv.y, fmaf(td.y, w11, fmaf(tc.y, w01, fmaf(tb.y, w10, ta.y * w00))));
-    a.z = fmaf(sk.z, gv.z, fmaf(td.z, w11, fmaf(tc.z, w01, fmaf(tb.z, w10, ta.z * w00))));
-    a.w = fmaf(sk.w, gv.w, fmaf(td.w, w11, fmaf(tc.w, w01, fmaf(tb.w, w10, ta.w * w00))));
-    const f4acc acc = mma16(a, wr);
-    float4 v = acc_quad(acc);
-    v = (ecol_in && row_in) ? clamp4(f4add(v, bias), cl) : f4zero();
-    if (xe < ZC) st4(z_t + zy * 256 + col_a(xe, g), v);
+#define BSX_GR_LO_ROW(y) (l_t + ((y) - pre.ly0) * pre.LC * kLoStride)
+#define BSX_GR_SKIP pre.s[j]
+#define BSX_GR_STORE(v) if (xe < ZC) st4(z_t + zy * 256 + col_a(xe, g), v)
+#include "seg_gated_row.inc"
   }
 }
 
@@ -808,18 +751,11 @@ __global__ __launch_bounds__(kSegThreads) void seg_k3_k(
   const float4 bias2 = ld4(w + d.pw2.b_off + cq4);
   __syncthreads();
   float4 sum = f4zero();
-  const int xe = li;
-  for (int py = wave; py < d.TR && r0 + py < d.H2; py += 4) {
-    const f4v zc = ldv(z_t + (py + 1) * 256 + coz[1]);
-    const float4 dv = clamp4(tof4(dw3x3(z_t, 256, py, coz, wd) + bias_d), cl_dw);
-    const f4acc acc = mma16(f4add(dv, tof4(zc)), wr);                  // dw epilogue: activation, then + residual z; straight into pw2
-    float4 v = acc_quad(acc);
-    if (xe < d.TC && c0 + xe < d.W2) {
-      v = as_stored<H16>(clamp4(f4add(v, bias2), cl_2));
-      stg4<H16>(lo_out, (unsigned)(((r0 + py) * d.W2 + c0 + xe) * 16 + cq4), v);
-      sum = f4add(sum, v);
-    }
-  }
+#define BSX_K3R_FIRST wave
+#define BSX_K3R_Z z_t
+#define BSX_K3R_ZRW 256
+#define BSX_K3R_ZROW(py) (py)
+#include "seg_k3_rows.inc"
   float* s_red = seg_smem + kScrRed;
   wave_reduce16<0>(sum, s_red, wave, lane);
   __syncthreads();
@@ -828,27 +764,19 @@ __global__ __launch_bounds__(kSegThreads) void seg_k3_k(
 
 // ==================================================================================================================================
 // k3, per-frame form (segments.hpp: SegK3F): blockIdx.x = frame, 1024 lanes = 16 waves, one workgroup per CU — the whole of seg_k3_k's frame and seg_gate_k's work in
-// one dependent chain instead of tiles_y * tiles_x chains in one and a half rounds plus a launch.  The arithmetic is the tile form's, instruction for instruction:
-//   phase A  gated_compute's body per row tile (one z row, 16 columns of block tx: columns tx * TC - 1 ..) on absolute coordinates, weights and lo2 from LDS;
-//   phase B  seg_k3_k's depthwise + pw2 per (tile, wave-of-the-tile-form) unit: a unit adds its rows' `sum` in that wave's order, wave_reduce16<0> puts it where the
+// one dependent chain instead of tiles_y * tiles_x chains in one and a half rounds plus a launch.  Each phase is the tile form's own text, included with this form's operands:
+//   phase A  seg_gated_row.inc (gated_compute's row) per row tile — one z row, 16 columns of block tx: columns tx * TC - 1 .. — weights and the whole of lo2 from LDS;
+//   phase B  seg_k3_rows.inc (seg_k3_k's rows) per (tile, wave-of-the-tile-form) unit: a unit adds its rows' `sum` in that wave's order, wave_reduce16<0> puts it where the
 //            tile's workgroup would have, and 16 lanes per tile add the 16 slots as store_partials does — the partial sums of lo are the tile form's bits;
-//   gate     seg_gate's slices, means and FC layers on the first 256 lanes (its decomposition is tid >> 4 over 256 lanes), part 1 read from the partial sums in LDS.
-// The 256-lane kernels share none of this text by template: they keep their code (and registers) to the instruction.  No global load behind the first barrier.
+//   gate     seg_gate.inc on the first 256 lanes, in this kernel's order: part 0 and the FC weights with the first loads, part 1 from the partial sums in LDS behind phase B.
+// Sharing the text moved no instruction of either form: tools/isa_same.py compares the ahead-of-time instances and the graph-specialised modules with another
+// revision's, symbol by symbol (profiles/r14a_isa_same.txt); tests/test_gpu_k3_frame.py keeps the two forms' results bit-identical.  No global load behind the first barrier.
 // In the graph-specialised module only (gen_seg.cpp defines BSX_SEG_K3F where the plan takes the form): the ahead-of-time fallback keeps seg_k3_k + seg_gate_k, the
 // same bits — tests/test_device_order.py wants that fallback's k3 launch to be seg_k3_k, and a 1024-lane instance with the descriptor in registers needs 120 of them.
 // ==================================================================================================================================
 #if defined(BSX_SEG_RTC) && BSX_SEG_K3F
-// one FC layer of the gate on the first 256 lanes (seg_gate's `fc`): lane = (output, slice of the inputs), 8 consecutive lanes meet through DPP
-__device__ __forceinline__ void frame_gate_fc(const SegFc& f, const float* x, const float* wl, const float* bl, float* y, int tid) {
-  const int out = tid >> 3, ks = tid & 7, kper = f.Cin >> 3;
-  float acc = 0.f;
-  if (out < f.Cout)
-    for (int j = 0; j < kper; j++) acc = fmaf(x[ks * kper + j], wl[out * f.Cin + ks * kper + j], acc);
-  acc += dpp_quad(acc, 1);
-  acc += dpp_quad(acc, 2);
-  acc += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, acc), 0x141, 0xf, 0xf, true));
-  if (out < f.Cout && ks == 0) y[out] = sg_act(acc + bl[out], f.act);
-}
+// load_wtile from the staged tile at sw + base: rows of kSegK3FWStride floats, conflict-free (tests/test_k3_frame_codegen.py).  (As a function it moved this kernel's code.)
+#define BSX_K3F_WTILE(wr, base) _Pragma("unroll") for (int r = 0; r < 4; r++) wr[r] = sw[base + (4 * g + r) * kSegK3FWStride + li];
 constexpr SegK3F kSegK3F = seg_k3f_layout(kSegK3);
 static_assert(kSegK3F.on && kSegTAIL.pre_gate_off >= 0 && kSegTAIL.gate.n_parts == 2 && kSegTAIL.gate.part[1].off == kSegK3.part_lo_off &&
               kSegTAIL.gate.part[1].n == kSegK3.tiles_y * kSegK3.tiles_x, "k3: the per-frame form does not fit this plan");
@@ -860,7 +788,7 @@ extern "C" __global__ __launch_bounds__(kSegK3FThreads) void bsx_seg_k3f(float* 
   __shared__ __attribute__((aligned(16))) float smem[L.lds_floats];   // (static: the planned size is a constant here, and the function needs no attribute for its 100+ KiB)
   float* fa = arena + (size_t)blockIdx.x * (size_t)per_frame;
   const int tid = threadIdx.x, lane = tid & 63, wave = wave_uniform(tid >> 6), li = lane & 15, g = lane >> 4, cq4 = 4 * g;
-  const int H = d.H2, W = d.W2, TX = d.tiles_x, ZRW = TX * 256, ntile = (H + 2) * TX, tiles = d.tiles_y * TX, LRW = d.WL * kLoStride;
+  const int H = d.H2, W = d.W2, TX = d.tiles_x, ZRW = TX * 256, ntile = (H + 2) * TX, tiles = d.tiles_y * TX, HL = d.HL, LRW = d.WL * kLoStride;
   const bool half_pixel = d.half_pixel != 0;
   float* z_t = smem + L.z_off;                                      // [H + 2][TX][16][16]: row zy = image row zy - 1
   float* l_t = smem + L.lo_off;                                     // lo2 [HL][WL][16]
@@ -870,12 +798,12 @@ extern "C" __global__ __launch_bounds__(kSegK3FThreads) void bsx_seg_k3f(float* 
   float* s_g2 = smem + kSegK3FGate;
   float* lo_out = fa + d.lo_off;
   // ---- every global read of the frame: skip operands (registers), lo2, the level-2 gate, every weight, the tail gate's A partial sums and FC weights
-  float4 sk[kSegK3FRows];
+  float4 skp[kSegK3FRows];
 #pragma unroll
   for (int j = 0; j < kSegK3FRows; j++) {
     const int t = wave + 16 * j, zy = t / TX, tx = t - zy * TX, iy = zy - 1, ix = tx * d.TC - 1 + li;
-    sk[j] = f4zero();
-    if (t < ntile && iy >= 0 && iy < H && ix >= 0 && ix < W) sk[j] = ldg4<H16>(fa + d.skip_off, (unsigned)((iy * W + ix) * 16 + cq4));
+    skp[j] = f4zero();
+    if (t < ntile && iy >= 0 && iy < H && ix >= 0 && ix < W) skp[j] = ldg4<H16>(fa + d.skip_off, (unsigned)((iy * W + ix) * 16 + cq4));
   }
   const int npl = d.HL * d.WL * 4;                                  // 16-byte pieces of lo2: piece p = quad p & 3 of pixel p >> 2
   float4 lv[kSegK3FLoPieces];
@@ -901,32 +829,19 @@ extern "C" __global__ __launch_bounds__(kSegK3FThreads) void bsx_seg_k3f(float* 
   }
   float g2 = 0.f;
   if (tid >= 512 && tid < 528) g2 = fa[d.g_off + (tid - 512)];
-  // the tail gate's staging area, as seg_gate lays it out
-  const SegFc &f1 = gt.fc[0], &f2 = gt.fc[1];
-  const int w1n = f1.Cin * f1.Cout, w2n = gt.n_fc == 2 ? f2.Cin * f2.Cout : 0;
-  float* s_gate = smem + kScrGate;
-  float* s_mean = smem + kScrGate + 16;
-  float* s_hid = smem + kScrGate + 48;
-  float* ps = smem + L.stage_off;
-  float* w1 = ps + 512;
-  float* b1 = w1 + w1n;
-  float* w2 = b1 + f1.Cout;
-  float* b2 = w2 + w2n;
-  const int gc = tid & 15, gslice = tid >> 4;
+#define BSX_GATE_SCR smem                                            // the tail gate (seg_gate.inc): its first pooled tensor and the FC weights
+#define BSX_GATE_STAGE smem + L.stage_off
+#define BSX_GATE_SRC(k) ((k) == 0 ? fa + gt.part[0].off : s_plo)      // the second pooled tensor is lo: its partial sums are still in LDS
+#define BSX_GATE_FC_LANE tid < kSegThreads
+#define BSX_GATE_FC_CAPTURE tid
+#define BSX_GATE_PART 1
+#include "seg_gate.inc"
   if (tid < kSegThreads) {
-    {
-      const float* src = fa + gt.part[0].off;
-      float s = 0.f;
-#pragma unroll 4
-      for (int i = gslice; i < gt.part[0].n; i += 16) s += src[(unsigned)(i * 16 + gc)];
-      ps[gslice * 16 + gc] = s;
-    }
-    const float* g1 = w + f1.w_off;
-    const float* gw2 = w + f2.w_off;
-    for (int i = tid; i < w1n; i += kSegThreads) w1[i] = g1[(unsigned)i];
-    for (int i = tid; i < w2n; i += kSegThreads) w2[i] = gw2[(unsigned)i];
-    if (tid < f1.Cout) b1[tid] = (w + f1.b_off)[(unsigned)tid];
-    if (gt.n_fc == 2 && tid < f2.Cout) b2[tid] = (w + f2.b_off)[(unsigned)tid];
+#define BSX_GATE_K 0
+#define BSX_GATE_PART 2
+#include "seg_gate.inc"
+#define BSX_GATE_PART 3
+#include "seg_gate.inc"
   }
 #pragma unroll
   for (int j = 0; j < kSegK3FLoPieces; j++) {
@@ -940,37 +855,25 @@ extern "C" __global__ __launch_bounds__(kSegK3FThreads) void bsx_seg_k3f(float* 
   // ---- phase A: z = act(pw1(skip * g + up(lo2))), zero outside the image (gated_compute's arithmetic; the window offsets ly0 / lx0 are 0: the whole of lo2 is here)
   {
     float wr[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) wr[r] = sw[(4 * g + r) * kSegK3FWStride + li];
+    BSX_K3F_WTILE(wr, 0)
     const float4 bias = ld4(sw + kSegK3FWB1 + cq4);
     const float4 gv = ld4(s_g2 + cq4);
     const Clamp cl = clamp_of(d.pw1.act);
+    const float hs = d.hs;
 #pragma unroll
     for (int j = 0; j < kSegK3FRows; j++) {
       const int t = wave + 16 * j;
       if (t >= ntile) break;
       const int zy = t / TX, tx = t - zy * TX, iy = zy - 1, ix = tx * d.TC - 1 + li;
-      int x0, x1, y0, y1;
-      float dx, dy;
+      int x0, x1;
+      float dx;
       up_axis(min(max(ix, 0), W - 1), d.ws, half_pixel, d.WL, &x0, &x1, &dx);
       const int xo0 = col_l(x0, g), xo1 = col_l(x1, g);
       const bool ecol_in = ix >= 0 && ix < W;
-      const bool row_in = iy >= 0 && iy < H;                           // scalar
-      up_axis(min(max(iy, 0), H - 1), d.hs, half_pixel, d.HL, &y0, &y1, &dy);
-      const float* l0 = l_t + y0 * LRW;
-      const float* l1 = l_t + y1 * LRW;
-      const float4 ta = ld4(l0 + xo0), tb = ld4(l1 + xo0), tc = ld4(l0 + xo1), td = ld4(l1 + xo1);
-      const float w00 = (1.f - dy) * (1.f - dx), w10 = dy * (1.f - dx), w01 = (1.f - dy) * dx, w11 = dy * dx;
-      const float4 s4 = sk[j];
-      float4 a;
-      a.x = fmaf(s4.x, gv.x, fmaf(td.x, w11, fmaf(tc.x, w01, fmaf(tb.x, w10, ta.x * w00))));
-      a.y = fmaf(s4.y, gv.y, fmaf(td.y, w11, fmaf(tc.y, w01, fmaf(tb.y, w10, ta.y * w00))));
-      a.z = fmaf(s4.z, gv.z, fmaf(td.z, w11, fmaf(tc.z, w01, fmaf(tb.z, w10, ta.z * w00))));
-      a.w = fmaf(s4.w, gv.w, fmaf(td.w, w11, fmaf(tc.w, w01, fmaf(tb.w, w10, ta.w * w00))));
-      const f4acc acc = mma16(a, wr);
-      float4 v = acc_quad(acc);
-      v = (ecol_in && row_in) ? clamp4(f4add(v, bias), cl) : f4zero();
-      st4(z_t + zy * ZRW + tx * 256 + col_a(li, g), v);
+#define BSX_GR_LO_ROW(y) (l_t + (y) * LRW)
+#define BSX_GR_SKIP skp[j]
+#define BSX_GR_STORE(v) st4(z_t + zy * ZRW + tx * 256 + col_a(li, g), v)
+#include "seg_gated_row.inc"
     }
   }
   // ---- phase B: t = z + act(dw3x3(z)) on the MFMA's own lanes, straight into pw2 (seg_k3_k's loop; unit u = (tile u >> 2, that tile's wave u & 3))
@@ -983,65 +886,38 @@ extern "C" __global__ __launch_bounds__(kSegK3FThreads) void bsx_seg_k3f(float* 
     const f4v bias_d = ldv(sw + kSegK3FWDwB + cq4);
     const Clamp cl_dw = clamp_of(d.dw.act), cl_2 = clamp_of(d.pw2.act);
     float wr[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) wr[r] = sw[kSegK3FWPw2 + (4 * g + r) * kSegK3FWStride + li];
+    BSX_K3F_WTILE(wr, kSegK3FWPw2)
     const float4 bias2 = ld4(sw + kSegK3FWB2 + cq4);
     __syncthreads();
     for (int u = wave; u < 4 * tiles; u += 16) {
       const int t = u >> 2, ow = u & 3, ty = t / TX, tx = t - ty * TX, r0 = ty * d.TR, c0 = tx * d.TC;
       const float* zb = z_t + tx * 256;                               // the tile's block: its row py + fy is frame row r0 + py + fy
       float4 sum = f4zero();
-      for (int py = ow; py < d.TR && r0 + py < H; py += 4) {
-        const f4v zc = ldv(zb + (r0 + py + 1) * ZRW + coz[1]);
-        const float4 dv = clamp4(tof4(dw3x3(zb, ZRW, r0 + py, coz, wd) + bias_d), cl_dw);
-        const f4acc acc = mma16(f4add(dv, tof4(zc)), wr);
-        float4 v = acc_quad(acc);
-        if (li < d.TC && c0 + li < W) {
-          v = as_stored<H16>(clamp4(f4add(v, bias2), cl_2));
-          stg4<H16>(lo_out, (unsigned)(((r0 + py) * W + c0 + li) * 16 + cq4), v);
-          sum = f4add(sum, v);
-        }
-      }
+#define BSX_K3R_FIRST ow
+#define BSX_K3R_Z zb
+#define BSX_K3R_ZRW ZRW
+#define BSX_K3R_ZROW(py) (r0 + (py))
+#include "seg_k3_rows.inc"
       wave_reduce16<0>(sum, s_red + t * 256, ow, lane);
     }
   }
   __syncthreads();
-  if (tid < 16 * tiles) {                                             // store_partials, one tile per 16 lanes
+  if (tid < 16 * tiles) {                                             // store_partials, one tile per 16 lanes; the sums stay in LDS for the gate
     const float* r = s_red + (tid >> 4) * 256;
     float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < 16; j++) s += r[j * 16 + (tid & 15)];
+    BSX_SLOTS_SUM16(s, r, tid & 15);
     (fa + d.part_lo_off)[tid] = s;
     s_plo[tid] = s;
   }
   __syncthreads();
-  // ---- the tail's gate: seg_gate from its slice sums on, part 1 from LDS
-  if (tid < kSegThreads) {
-    float s = 0.f;
-#pragma unroll 4
-    for (int i = gslice; i < gt.part[1].n; i += 16) s += s_plo[i * 16 + gc];
-    ps[256 + gslice * 16 + gc] = s;
-  }
+  // ---- the tail's gate: its second pooled tensor from LDS, then seg_gate's means and FC chain
+  if (tid < kSegThreads)
+#define BSX_GATE_K 1
+#define BSX_GATE_PART 2
+#include "seg_gate.inc"
   __syncthreads();
-  const int Cm = gt.sum_parts ? 16 : 16 * gt.n_parts;
-  if (tid < Cm) {
-    float m = 0.f;
-    for (int k = 0; k < gt.n_parts; k++) {
-      if (!gt.sum_parts && (tid >> 4) != k) continue;
-      float s = 0.f;
-#pragma unroll
-      for (int sl = 0; sl < 16; sl++) s += ps[k * 256 + sl * 16 + (tid & 15)];
-      m += s / gt.part[k].hw;
-    }
-    s_mean[tid] = m;
-  }
-  __syncthreads();
-  if (tid < kSegThreads) frame_gate_fc(f1, s_mean, w1, b1, gt.n_fc == 1 ? s_gate : s_hid, tid);
-  __syncthreads();
-  if (gt.n_fc == 2) {
-    if (tid < kSegThreads) frame_gate_fc(f2, s_hid, w2, b2, s_gate, tid);
-    __syncthreads();
-  }
+#define BSX_GATE_PART 4
+#include "seg_gate.inc"
   if (tid < 16) fa[pre_gate_off + tid] = s_gate[tid];
 }
 #endif

@@ -11,6 +11,7 @@ import subprocess
 import pytest
 
 from conftest import ROOT, model_path
+from seg_text import seg_kernel_text
 
 HIPCC = "/opt/rocm/bin/hipcc"
 CSRC = os.path.join(ROOT, "backscrub_amd", "csrc")
@@ -83,7 +84,7 @@ def test_the_specialised_source_carries_the_form_and_compiles_within_k2s_budget(
     sc = int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", blk).group(1))
     lds = int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", blk).group(1))
     assert sc == 0 and vg <= 80 and lds == 0, (vg, sc, lds)
-    launch = open(os.path.join(CSRC, "kernels_seg.hip")).read()
+    launch = seg_kernel_text()
     assert "seg_launch(fn, seg_k2_instance(h16), d.tiles_y * d.tiles_x, n, (size_t)d.lds_floats * sizeof(float), s, args)" in launch
     # the expand loop reads its 1x1 tiles and depthwise weights from LDS: what is left of global loads is the b0 operands (<= 6), the first copies (3), pw_a's
     # tile + bias (5) and the next group's piece (tile or bias lanes: 2 per group but the last); form 0 has 10 depthwise loads per group alone
@@ -121,7 +122,7 @@ def cycles(groups, unit, nslots, addr_of_lane, active=lambda l: True):
 def test_the_staged_reads_and_the_copies_are_conflict_free(key, compiled):
     src, _ = compiled[key]
     k = k2_constants(src)
-    kern = open(os.path.join(CSRC, "kernels_seg.hip")).read()
+    kern = seg_kernel_text()
     # the kernel's own index expressions
     read, store = "(4 * g + r) * st.stride + li", "(tid & 15) * st.stride + 4 * (tid >> 4)"
     assert "wr[r] = tb[%s];" % read in kern and "bias_b = ld4(tb + st.bias_off + cq4);" in kern and "const float* tb = sw + (grp & 1) * st.buf_floats;" in kern

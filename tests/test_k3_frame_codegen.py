@@ -10,6 +10,7 @@ import subprocess
 import pytest
 
 from conftest import ROOT, model_path
+from seg_text import seg_kernel_text
 
 HIPCC = "/opt/rocm/bin/hipcc"
 CSRC = os.path.join(ROOT, "backscrub_amd", "csrc")
@@ -130,22 +131,22 @@ def cycles(groups, unit, nslots, addr_of_lane, active=lambda l: True):
 def test_the_staged_weights_are_read_and_copied_without_bank_conflicts(lite):
     c = header_constants()
     k = k3_constants(lite[0])
-    kern = open(os.path.join(CSRC, "kernels_seg.hip")).read()
+    kern = seg_kernel_text()
     S = c["kSegK3FWStride"]
     assert S % 8 == 4 and S >= 16 and c["kSegK3FWB1"] == 16 * S and c["kSegK3FWDw"] == c["kSegK3FWB1"] + 16 and c["kSegK3FWDwB"] == c["kSegK3FWDw"] + 144
     assert c["kSegK3FWPw2"] == c["kSegK3FWDwB"] + 16 and c["kSegK3FWB2"] == c["kSegK3FWPw2"] + 16 * S and c["kSegK3FWFloats"] == c["kSegK3FWB2"] + 16
     assert c["kSegK3FWPieces"] == 2 * (64 + 4) + 36 + 4
     # the kernel's own index expressions
-    read1, read2 = "(4 * g + r) * kSegK3FWStride + li", "kSegK3FWPw2 + (4 * g + r) * kSegK3FWStride + li"
-    assert "wr[r] = sw[%s];" % read1 in kern and "wr[r] = sw[%s];" % read2 in kern
+    read = "base + (4 * g + r) * kSegK3FWStride + li"                                                     # stated once, for both tiles
+    assert kern.count("wr[r] = sw[%s];" % read) == 1 and "BSX_K3F_WTILE(wr, 0)\n" in kern and "BSX_K3F_WTILE(wr, kSegK3FWPw2)\n" in kern
     assert "wd[k] = ldv(sw + kSegK3FWDw + k * 16 + cq4);" in kern and "ld4(sw + kSegK3FWB1 + cq4)" in kern and "ld4(sw + kSegK3FWB2 + cq4)" in kern
     st1, st2 = "(wp & 15) * kSegK3FWStride + 4 * (wp >> 4)", "kSegK3FWPw2 + (q & 15) * kSegK3FWStride + 4 * (q >> 4)"
-    assert "w_dst = %s;" % st1 in kern and "w_dst = %s;" % st2 in kern
+    assert kern.count("w_dst = %s;" % st1) == 1 and kern.count("w_dst = %s;" % st2) == 1
     tiles = k["tiles_y"] * k["tiles_x"]
     w_off = c["kSegScratchFloats"] + (k["H2"] + 2) * k["tiles_x"] * 256 + k["HL"] * k["WL"] * 16      # seg_k3f_layout
     assert w_off % 4 == 0 and tiles >= 1
-    for base, read, store in ((0, read1, st1), (c["kSegK3FWPw2"], read2, st2)):
-        rd = eval("lambda g, r, li: " + read, dict(c))                                                   # noqa: S307
+    for base, store in ((0, st1), (c["kSegK3FWPw2"], st2)):
+        rd = eval("lambda g, r, li: " + read, dict(c, base=base))                                        # noqa: S307
         for r in range(4):
             assert cycles(G32, 1, 32, lambda l: w_off + rd(l >> 4, r, l & 15)) == 2                        # one cycle per group of 32 lanes
             assert cycles(G32, 1, 32, lambda l: w_off + base + (4 * (l >> 4) + r) * 16 + (l & 15)) == 4    # a dense tile would be 2-way

@@ -104,9 +104,9 @@ def wr128(f, active=lambda l: True):
 
 
 def _seg_fn(name, args="int x"):
-    import os
     import re
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "backscrub_amd", "csrc", "kernels_seg.hip")).read()
+    from seg_text import seg_kernel_text
+    src = seg_kernel_text()
     m = re.search(r"__device__\s+__forceinline__\s+int\s+%s\(%s\)\s*\{\s*return\s+([^;]+);\s*\}" % (name, re.escape(args)), src)
     assert m, "%s(%s) not found in kernels_seg.hip" % (name, args)
     expr = m.group(1)
