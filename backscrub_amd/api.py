@@ -102,6 +102,7 @@ SYMBOLS = [
     ("bsx_geom_count", C.c_int, [C.c_void_p]),
     ("bsx_get_geom_info", C.c_int, [C.c_void_p, C.c_int, C.POINTER(_GeomInfo)]),
     ("bsx_step_batch_geoms", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(_GeomItem), C.c_int, C.c_void_p, C.c_uint]),
+    ("bsx_step_batch_vcam_geoms", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(_GeomItem), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint]),
     ("bsx_step_batch_mixed", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(_StreamSetting), C.c_void_p, C.c_int, C.c_void_p, C.c_uint]),
     ("bsx_step_batch_vcam_mixed", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(_StreamSetting), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                             C.c_uint]),
@@ -291,6 +292,49 @@ class MaskGen:
             items[i].setting.flags = s.flags()
         flags = (1 if yuyv else 0) | (8 if no_mask else 0)
         _check(lib().bsx_step_batch_geoms(self.h, arr, items, n, _stream_ptr(), flags), self.h, "bsx_step_batch_geoms")
+        return outs
+
+    def step_vcam_geoms(self, ids, frames, outs, settings, yuyv=False):
+        """step_geoms with every composite written at ONE common size, the virtual camera's (bsx_step_batch_vcam_geoms): frames[i] and settings[i].bg have the
+        capture size of the class of ids[i]; every outs[i] is a cuda uint8 [out_h, out_w, 3] (or [.., 2] with yuyv) — the size is taken from outs[0].  Blend ->
+        flip -> resize -> [pack] in one pass per position: no capture-size composite is stored."""
+        torch = _torch()
+        arr, n = _ids(ids)
+        frames, outs, settings = list(frames), list(outs), list(settings)
+        if len(frames) != n or len(outs) != n or len(settings) != n:
+            raise BsxError("%d ids for %d frames, %d outs and %d settings" % (n, len(frames), len(outs), len(settings)))
+        items = (_GeomItem * max(n, 1))()
+        ch = 2 if yuyv else 3
+        out_h = out_w = 0
+        if n:
+            if not isinstance(outs[0], torch.Tensor) or outs[0].dim() != 3 or outs[0].shape[2] != ch:
+                raise BsxError("outs[0] must be a cuda:%d uint8 tensor [out_h,out_w,%d]: it gives the output size" % (self.device, ch))
+            out_h, out_w = int(outs[0].shape[0]), int(outs[0].shape[1])
+            if yuyv and (out_w & 1):
+                raise BsxError("YUYV output needs an even width (outs[0] is %d wide)" % out_w)
+        for i in range(n):
+            g = self._geom_of(int(arr[i]))
+            H, W = g["height"], g["width"]
+
+            def ok(t, shape):
+                return isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and self._on_device(t) and tuple(t.shape) == shape and t.is_contiguous()
+            if not ok(frames[i], (H, W, 3)):
+                raise BsxError("frames[%d] must be a contiguous cuda:%d uint8 tensor [%d,%d,3] (stream %d)" % (i, self.device, H, W, arr[i]))
+            if not ok(outs[i], (out_h, out_w, ch)):
+                raise BsxError("outs[%d] must be a contiguous cuda:%d uint8 tensor [%d,%d,%d] (the size of outs[0])" % (i, self.device, out_h, out_w, ch))
+            s = settings[i]
+            if not isinstance(s, StreamSetting):
+                raise BsxError("settings[%d] is not a StreamSetting" % i)
+            if s.bgblur:
+                raise BsxError("settings[%d]: bgblur is not taken by step_vcam_geoms" % i)
+            if not s.filter_off and s.bg is None:
+                raise BsxError("settings[%d]: bg is required unless filter_off is set" % i)
+            if s.bg is not None and not ok(s.bg, (H, W, 3)):
+                raise BsxError("settings[%d].bg must be a contiguous cuda:%d uint8 tensor [%d,%d,3] (stream %d)" % (i, self.device, H, W, arr[i]))
+            items[i].d_frame, items[i].d_out = frames[i].data_ptr(), outs[i].data_ptr()
+            items[i].setting.d_bg = s.bg.data_ptr() if s.bg is not None else None
+            items[i].setting.flags = s.flags()
+        _check(lib().bsx_step_batch_vcam_geoms(self.h, arr, items, n, out_w, out_h, _stream_ptr(), 1 if yuyv else 0), self.h, "bsx_step_batch_vcam_geoms")
         return outs
 
     # ---- batched device path -----------------------------------------------------------------

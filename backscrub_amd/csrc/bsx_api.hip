@@ -209,6 +209,10 @@ struct bsx_ctx {
   GeomDesc* h_geo = nullptr;                // pinned [kIdRing][n_streams]: the descriptors of a geoms step, ordered by class (the ring entries and events of the ids)
   GeomDesc* d_geo = nullptr;                // device, likewise
   std::vector<int> geo_order, geo_ids;      // host scratch: the call's positions ordered by class, their stream ids in that order
+  // bsx_step_batch_vcam_geoms: per output size the device array of one VgClass per class (kernels.hpp) — capture size, capture -> output table, per-tap bit — built
+  // and uploaded on the first call at that size.  Class 0's table is the one in vcam_tabs (shared with bsx_step_batch_vcam); the others' memory is owned here.
+  struct VgGeoms { VgClass* d_rec = nullptr; std::vector<void*> mem; };
+  std::map<std::pair<int, int>, VgGeoms> vg_geoms;
   int geom_of(int stream) const { int g = 0; while (g + 1 < (int)geoms.size() && stream >= geoms[g + 1].first) g++; return g; }
   bool act16 = false;                  // BSX_ACT16=1: 16-bit activation STORAGE for the segmented Meet / MLKit networks (g1) — opt-in, IoU-gated; needs the specialised middle kernel
 
@@ -599,9 +603,9 @@ int refuse_pending(bsx_ctx* c, const char* fn) {
   return c->pend.active ? refuse(c, fn, "a pipelined composite is pending (flush with bsx_step_batch_pipelined(ctx, NULL, ...) first)") : BSX_OK;
 }
 
-// every entry point that works at "the" capture size refuses a context of several geometry classes (bsx_new_geoms): only bsx_step_batch_geoms steps those
+// every entry point that works at "the" capture size refuses a context of several geometry classes (bsx_new_geoms): only bsx_step_batch_geoms and bsx_step_batch_vcam_geoms step those
 int refuse_geoms(bsx_ctx* c, const char* fn) {
-  return c->geoms.size() > 1 ? refuse(c, fn, "context has %d geometries (only bsx_step_batch_geoms steps such a context)", (int)c->geoms.size()) : BSX_OK;
+  return c->geoms.size() > 1 ? refuse(c, fn, "context has %d geometries (only bsx_step_batch_geoms and bsx_step_batch_vcam_geoms step such a context)", (int)c->geoms.size()) : BSX_OK;
 }
 
 // flags (bsx.h): BSX_STEP_YUYV (the composite leaves as YUYV 4:2:2), BSX_STEP_FLIP_H / _V (cv::flip of the composite), BSX_STEP_NO_MASK, BSX_STEP_YUYV_IN (the
@@ -785,22 +789,31 @@ int run_composite(bsx_ctx* c, const StepReq& r) {
   return BSX_OK;
 }
 
-// the capture -> (out_w, out_h) table of bsx_step_batch_vcam, built once per output size
+// A (sw, sh) -> (dw, dh) table as the resize pass of the vcam kernels takes it: always linear.  The 2x2 area mean becomes taps 2d and 2d + 1 with coefficients
+// 1024 / 1024, the copy of equal sizes taps d and d + 1 with 2048 / 0 (the same integers in both cases: kernels_img.hip); `direct`: the tile footprints do not fit
+// the kernel's LDS staging area
+int vcam_tab_build(bsx_ctx* c, int sw, int sh, int dw, int dh, VcamTab* v) {
+  HostResizeTab h = make_resize_tab(sw, sh, dw, dh);
+  if (h.mode != 0) {
+    const int step = h.mode == 2 ? 2 : 1;
+    const short a0 = h.mode == 2 ? 1024 : 2048, a1 = h.mode == 2 ? 1024 : 0;
+    h.mode = 0;
+    h.xofs.resize(dw); h.xa.resize(2 * (size_t)dw); h.yofs.resize(dh); h.ya.resize(2 * (size_t)dh);
+    for (int d = 0; d < dw; d++) { h.xofs[d] = step * d; h.xa[2 * d] = a0; h.xa[2 * d + 1] = a1; }
+    for (int d = 0; d < dh; d++) { h.yofs[d] = step * d; h.ya[2 * d] = a0; h.ya[2 * d + 1] = a1; }
+  }
+  v->direct = !vcam_tile_fits(h.xofs.data(), h.yofs.data(), h.sw, h.sh, h.dw, h.dh);
+  const int rc = upload_tab(c, h, &v->d);
+  if (rc && v->d.mem) { (void)hipFree(v->d.mem); v->d.mem = nullptr; }
+  return rc;
+}
+// the capture -> (out_w, out_h) table of bsx_step_batch_vcam (class 0 of bsx_step_batch_vcam_geoms), built once per output size
 int vcam_tab(bsx_ctx* c, int out_w, int out_h, const VcamTab** out) {
   auto key = std::make_pair(out_w, out_h);
   auto it = c->vcam_tabs.find(key);
   if (it == c->vcam_tabs.end()) {
-    HostResizeTab h = make_resize_tab(c->width, c->height, out_w, out_h);
-    if (h.mode == 2) {              // the 2x2 area mean as a linear table: taps 2d and 2d + 1, coefficients 1024 / 1024 (the same integers: kernels_img.hip)
-      h.mode = 0;
-      h.xofs.resize(out_w); h.xa.assign(2 * (size_t)out_w, 1024); h.yofs.resize(out_h); h.ya.assign(2 * (size_t)out_h, 1024);
-      for (int d = 0; d < out_w; d++) h.xofs[d] = 2 * d;
-      for (int d = 0; d < out_h; d++) h.yofs[d] = 2 * d;
-    }
     VcamTab v;
-    v.direct = !vcam_tile_fits(h.xofs.data(), h.yofs.data(), h.sw, h.sh, h.dw, h.dh);
-    int rc = upload_tab(c, h, &v.d);
-    if (rc) { if (v.d.mem) (void)hipFree(v.d.mem); return rc; }
+    if (const int rc = vcam_tab_build(c, c->width, c->height, out_w, out_h, &v)) return rc;
     it = c->vcam_tabs.emplace(key, v).first;
   }
   *out = &it->second;
@@ -1110,24 +1123,28 @@ int geoms_check(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item*
   return BSX_OK;
 }
 
-// the checked call on the context's device, ring entry k acquired
-int geoms_run(bsx_ctx* c, const int* ids, const bsx_geom_item* items, int n, hipStream_t s, unsigned flags, int k) {
+// The front of a checked geoms call on the context's device, ring entry k acquired: the positions ordered by class, ids and descriptors through the ring, ONE prep
+// launch and the network.  Leaves the descriptors' device copy, the ragged grids of the back end and the classes whose tiles keep to one XCD.
+struct GeomsStaged { const GeomDesc* desc = nullptr; GeomSpans tiles{}, outside{}; unsigned xcd_mask = 0; };
+int geoms_front(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item* items, int n, hipStream_t s, int k, GeomsStaged* st) {
   const int G = (int)c->geoms.size();
   // positions ordered by class (a counting sort: stable, so a class keeps the caller's order)
   int count[kMaxGeoms] = {0};
   for (int i = 0; i < n; i++) count[c->geom_of(ids[i])]++;
-  GeomSpans prep{}, tiles{}, outside{};
+  GeomSpans prep{};
+  GeomSpans &tiles = st->tiles, &outside = st->outside;
   unsigned xcd_mask = 0;
   for (int g = 0; g < kMaxGeoms; g++) {
     const int cnt = g < G ? count[g] : 0;
     const int per_t = g < G ? (int)c->geoms[g].tiles_per_frame : 0, per_o = g < G ? c->geoms[g].outside_blocks : 0;
     if ((long)tiles.wg[g] + (long)cnt * per_t >= (1l << 31) || (long)outside.wg[g] + (long)cnt * per_o >= (1l << 31)) {
-      c->last_error = "error: bsx_step_batch_geoms: the batch needs more than 2^31 workgroups\n"; return BSX_EDEVICE; }
+      c->last_error = std::string("error: ") + fn + ": the batch needs more than 2^31 workgroups\n"; return BSX_EDEVICE; }
     prep.pos[g + 1] = tiles.pos[g + 1] = outside.pos[g + 1] = tiles.pos[g] + cnt;
     tiles.wg[g + 1] = tiles.wg[g] + cnt * per_t; tiles.per[g] = per_t;
     outside.wg[g + 1] = outside.wg[g] + cnt * per_o; outside.per[g] = per_o;
     if (g < G && c->geoms[g].xcd) xcd_mask |= 1u << g;
   }
+  st->xcd_mask = xcd_mask;
   c->geo_order.resize((size_t)n); c->geo_ids.resize((size_t)n);
   int next[kMaxGeoms];
   for (int g = 0; g < kMaxGeoms; g++) next[g] = tiles.pos[g];
@@ -1146,14 +1163,111 @@ int geoms_run(bsx_ctx* c, const int* ids, const bsx_geom_item* items, int n, hip
   if (const int rc = ids_copy(c, c->geo_ids.data(), n, s, k, &d_ids)) return rc;
   GeomDesc* const dd = c->d_geo + (size_t)k * c->n_streams;
   BSX_HIP(c, hipMemcpyAsync(dd, hd, (size_t)n * sizeof(GeomDesc), hipMemcpyHostToDevice, s));
+  st->desc = dd;
   {
     bsx_roctx::Range range("bsx:prep");
     float* f32 = !c->in_u8 ? c->tensor_ptr(c->plan.input) : nullptr;
     BSX_HIP(c, launch_prep_geoms(c->d_geom_classes, dd, prep, f32, c->in_u8 ? c->d_net_in_u8 : nullptr, c->inW, c->inH, c->bilateral, n, s));
   }
-  if (const int rc = infer_after_prep(c, n, s, 0, d_ids)) return rc;
+  return infer_after_prep(c, n, s, 0, d_ids);
+}
+
+// the checked call on the context's device, ring entry k acquired
+int geoms_run(bsx_ctx* c, const int* ids, const bsx_geom_item* items, int n, hipStream_t s, unsigned flags, int k) {
+  GeomsStaged st;
+  if (const int rc = geoms_front(c, "bsx_step_batch_geoms", ids, items, n, s, k, &st)) return rc;
   bsx_roctx::Range range("bsx:mask+blend");
-  BSX_HIP(c, launch_mask_blend_geoms(c->d_geom_classes, dd, tiles, xcd_mask, outside, c->d_ofinal, c->outW, c->outH, c->d_geom_tile_class, n, s, (int)flags));
+  BSX_HIP(c, launch_mask_blend_geoms(c->d_geom_classes, st.desc, st.tiles, st.xcd_mask, st.outside, c->d_ofinal, c->outW, c->outH, c->d_geom_tile_class, n, s, (int)flags));
+  return BSX_OK;
+}
+
+// ---- bsx_step_batch_vcam_geoms: the geoms step with every composite written at ONE common size, the virtual camera's ------------------------------------------
+// geoms_run's shape: the same front, then [one tile-class launch,] ONE masks-only tile launch and ONE resize pass over every position's frame, background and mask
+// taps.  Outside a ROI the persistent mask is 255 from reset on, so nothing there needs a launch; no capture-size composite is stored.
+int vcam_geoms_check(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item* items, int n, int out_w, int out_h, unsigned flags) {
+  if (!items) return refuse(c, fn, "items is NULL");
+  if (out_w <= 0 || out_h <= 0) return refuse(c, fn, "output size %d x %d must be positive", out_w, out_h);
+  if (flags & BSX_STEP_NO_MASK) return refuse(c, fn, "unsupported flags 0x%x (the no-mask step has no vcam form)", flags);
+  if (flags & BSX_STEP_YUYV_IN) return refuse(c, fn, "flags 0x%x: YUYV input frames are not taken by the multi-geometry step", flags);
+  if (flags & ~BSX_STEP_YUYV) return refuse(c, fn, "flags 0x%x has bits outside yuyv", flags);
+  if (const int rc = refuse_pending(c, fn)) return rc;
+  if (c->onmask) return refuse(c, fn, "needs the fused mask route (no onmask callback)");
+  const bool yuyv = (flags & BSX_STEP_YUYV) != 0;
+  if (yuyv && (out_w & 1)) return refuse(c, fn, "YUYV output needs an even width (out_w = %d)", out_w);
+  const size_t out_bytes = (size_t)out_w * out_h * (yuyv ? 2 : 3);
+  std::vector<bsx_ctx::Span>& sp = c->rsz_spans;
+  sp.clear();
+  for (int i = 0; i < n; i++) {
+    const bsx_geom_item& it = items[i];
+    const int g = c->geom_of(ids[i]);
+    const bsx_ctx::Geom& G = c->geoms[g];
+    const unsigned f = it.setting.flags;
+    if (f & 0xFF00u) return refuse(c, fn, "items[%d]: setting flags 0x%x asks for a background blur, which the multi-geometry step does not take", i, f);
+    if (f & ~kGeomStreamFlags) return refuse(c, fn, "items[%d]: setting flags 0x%x has bits outside flip / filter-off", i, f);
+    if (!it.d_frame) return refuse(c, fn, "items[%d]: d_frame is NULL", i);
+    if ((uintptr_t)it.d_frame & 3) return refuse(c, fn, "items[%d]: d_frame %p is not 4-byte aligned", i, (const void*)it.d_frame);
+    if (!it.d_out) return refuse(c, fn, "items[%d]: d_out is NULL", i);
+    if ((uintptr_t)it.d_out & 3) return refuse(c, fn, "items[%d]: d_out %p is not 4-byte aligned", i, (const void*)it.d_out);
+    if (!G.fusable)
+      return refuse(c, fn, "items[%d]: stream %d is of class %d (%d x %d), which is off the fused tile route (width, roi.x, roi.w multiples of 4, a tiled linear mask up-scale); "
+                    "bsx_step_batch_vcam_mixed takes such a context", i, ids[i], g, G.width, G.height);
+    const size_t px = (size_t)G.width * G.height;
+    sp.push_back({(uintptr_t)it.d_frame, (uintptr_t)it.d_frame + px * 3, i, false});
+    sp.push_back({(uintptr_t)it.d_out, (uintptr_t)it.d_out + out_bytes, i, true});
+    if (f & BSX_STREAM_FILTER_OFF) continue;                          // reads no background
+    if (!it.setting.d_bg) return refuse(c, fn, "items[%d]: setting.d_bg is NULL", i);
+    if ((uintptr_t)it.setting.d_bg & 3) return refuse(c, fn, "items[%d]: setting.d_bg %p is not 4-byte aligned", i, (const void*)it.setting.d_bg);
+    sp.push_back({(uintptr_t)it.setting.d_bg, (uintptr_t)it.setting.d_bg + px * 3, i, false});
+  }
+  const bsx_ctx::Span* d = nullptr;
+  const bsx_ctx::Span* o = nullptr;
+  if (spans_overlap(sp, &d, &o))
+    return refuse(c, fn, "items[%d]: d_out %p overlaps %s of items[%d] (%p)", d->item, (const void*)d->begin, o->dst ? "the output" : "a frame or background", o->item,
+                  (const void*)o->begin);
+  return BSX_OK;
+}
+
+// the class records of (out_w, out_h), built and uploaded on the first call at that size
+int vg_geoms_records(bsx_ctx* c, int out_w, int out_h, const VgClass** out) {
+  const auto key = std::make_pair(out_w, out_h);
+  auto it = c->vg_geoms.find(key);
+  if (it == c->vg_geoms.end()) {
+    const size_t G = c->geoms.size();
+    std::vector<VgClass> rec(G);
+    bsx_ctx::VgGeoms v;
+    int rc = BSX_OK;
+    for (size_t g = 0; g < G && rc == BSX_OK; g++) {
+      const bsx_ctx::Geom& q = c->geoms[g];
+      VcamTab own;
+      const VcamTab* t = &own;
+      if (g == 0) rc = vcam_tab(c, out_w, out_h, &t);
+      else if ((rc = vcam_tab_build(c, q.width, q.height, out_w, out_h, &own)) == BSX_OK) v.mem.push_back(own.d.mem);
+      if (rc == BSX_OK) rec[g] = VgClass{q.width, q.height, (t->direct || c->vcam_direct) ? 1 : 0, 0, t->d.tab};
+    }
+    if (rc == BSX_OK && hipMalloc(reinterpret_cast<void**>(&v.d_rec), G * sizeof(VgClass)) != hipSuccess) rc = BSX_EDEVICE;
+    if (rc == BSX_OK && hipMemcpy(v.d_rec, rec.data(), G * sizeof(VgClass), hipMemcpyHostToDevice) != hipSuccess) rc = BSX_EDEVICE;
+    if (rc != BSX_OK) {
+      for (void* m : v.mem) if (m) (void)hipFree(m);
+      if (v.d_rec) (void)hipFree(v.d_rec);
+      if (c->last_error.empty()) c->last_error = "error: bsx_step_batch_vcam_geoms: the class records could not be uploaded\n";
+      return rc;
+    }
+    it = c->vg_geoms.emplace(key, std::move(v)).first;
+  }
+  *out = it->second.d_rec;
+  return BSX_OK;
+}
+
+int vcam_geoms_run(bsx_ctx* c, const int* ids, const bsx_geom_item* items, int n, int out_w, int out_h, hipStream_t s, unsigned flags, int k) {
+  const char* fn = "bsx_step_batch_vcam_geoms";
+  const long out_tiles = (long)((out_w + 63) / 64) * ((out_h + 31) / 32);      // the resize pass's 64 x 32 output tiles (kernels_img.hip)
+  if (out_tiles * n >= (1l << 31)) { c->last_error = std::string("error: ") + fn + ": the batch needs more than 2^31 workgroups\n"; return BSX_EDEVICE; }
+  const VgClass* vg = nullptr;
+  if (const int rc = vg_geoms_records(c, out_w, out_h, &vg)) return rc;
+  GeomsStaged st;
+  if (const int rc = geoms_front(c, fn, ids, items, n, s, k, &st)) return rc;
+  bsx_roctx::Range range("bsx:mask+vcam");
+  BSX_HIP(c, launch_vcam_geoms(c->d_geom_classes, vg, st.desc, st.tiles, st.xcd_mask, c->d_ofinal, c->outW, c->outH, c->d_geom_tile_class, out_w, out_h, n, s, flags & 1u));
   return BSX_OK;
 }
 
@@ -1390,6 +1504,7 @@ void bsx_delete(bsx_ctx* c) {
   for (void* p : ptrs) if (p) (void)hipFree(p);
   for (auto& kv : c->bg_tabs) if (kv.second.mem) (void)hipFree(kv.second.mem);
   for (auto& kv : c->vcam_tabs) if (kv.second.d.mem) (void)hipFree(kv.second.d.mem);
+  for (auto& kv : c->vg_geoms) { for (void* m : kv.second.mem) if (m) (void)hipFree(m); if (kv.second.d_rec) (void)hipFree(kv.second.d_rec); }
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   for (int k = 1; k < 4; k++) { if (c->lane_stream[k]) (void)hipStreamDestroy(c->lane_stream[k]); if (c->ev_join[k]) (void)hipEventDestroy(c->ev_join[k]); }
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
@@ -1545,6 +1660,21 @@ int bsx_step_batch_geoms(bsx_ctx* c, const int* ids, const bsx_geom_item* items,
   int entry = 0;
   if (const int rc = ring_acquire(c, &entry)) return rc;
   return ids_release(c, entry, s, geoms_run(c, ids, items, n, s, flags, entry));
+}
+
+// bsx_step_batch_geoms with every d_out at (out_w, out_h); see bsx.h
+int bsx_step_batch_vcam_geoms(bsx_ctx* c, const int* ids, const bsx_geom_item* items, int n, int out_w, int out_h, void* stream, unsigned flags) {
+  const char* fn = "bsx_step_batch_vcam_geoms";
+  if (!c) return BSX_EINVAL;
+  if (const int rc = ids_check(c, fn, ids, n)) return rc;
+  if (n == 0) return refuse_pending(c, fn);
+  if (const int rc = vcam_geoms_check(c, fn, ids, items, n, out_w, out_h, flags)) return rc;
+  DeviceGuard guard(c->device);
+  hipStream_t s = pick(c, stream);
+  if (const int rc = geoms_device_state(c)) return rc;
+  int entry = 0;
+  if (const int rc = ring_acquire(c, &entry)) return rc;
+  return ids_release(c, entry, s, vcam_geoms_run(c, ids, items, n, out_w, out_h, s, flags, entry));
 }
 
 int bsx_reset_streams(bsx_ctx* c, const int* ids, int n, void* stream) {

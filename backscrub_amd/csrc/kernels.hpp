@@ -198,6 +198,14 @@ int geom_outside_blocks(int W, int H, const Rect4& roi);      // outside-ROI wor
 bool geom_class_xcd(int W, const Rect4& roi);                // the class's mask tiles of one frame on one XCD (launch_mask_blend's shared_lines rule): bit g of xcd_mask
 hipError_t launch_mask_blend_geoms(const GeomClass* classes, const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const GeomSpans& outside, const uint8_t* ofinal,
                                    int outW, int outH, uint8_t* tile_class, int n, hipStream_t s, int flags);
+// bsx_step_batch_vcam_geoms: the geoms step whose outputs all have the virtual camera's size (out_w x out_h) — [one tile-class launch,] ONE masks-only tile launch
+// (the persistent masks, as launch_mask_blend_geoms writes them) and ONE resize pass that reads each position's frame, background and mask taps and writes its d_out:
+// the capture-size composite is never stored.  vg: one record per class (a DEVICE array, built once per output size): the capture size, the capture -> output table
+// (always linear: the copy and the 2x2 area mode expanded to one) and whether the class takes the per-tap form (!vcam_tile_fits, or the debug switch).
+// `flags`: bit 0 = YUYV pack; every d_out 4-byte aligned.
+struct alignas(16) VgClass { int W, H, direct, pad; ResizeTab tab; };
+hipError_t launch_vcam_geoms(const GeomClass* classes, const VgClass* vg, const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const uint8_t* ofinal, int outW,
+                             int outH, uint8_t* tile_class, int out_w, int out_h, int n, hipStream_t s, unsigned flags);
 // alpha blend.  deepseg.cc:108-134
 hipError_t launch_blend(const uint8_t* bg, size_t bg_stride, const uint8_t* frames, const uint8_t* masks, uint8_t* out, size_t npix,
                         int n, hipStream_t s, const int* slot_of = nullptr);

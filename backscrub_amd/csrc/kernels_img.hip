@@ -1033,6 +1033,9 @@ __global__ __launch_bounds__(kThreads) void vcam_blend_resize_k(const uint8_t* _
                                                                int opt) {
   constexpr bool SEL = false;
   [[maybe_unused]] const int* const slot_of = nullptr;
+#define BSX_VT_TILE blockIdx.x                           /* grid: output tiles x positions */
+#define BSX_VT_POS blockIdx.y
+#define BSX_VT_DESC(fl) bg = mix_desc(bg, (int)n, &fl); bg_stride = 0
 #include "vcam_tile.inc"
 }
 // The per-stream form (bsx_step_batch_vcam_mixed): every position with its own background, flip bits and filter switch (desc[n]) and the mask of its own slot —
@@ -1046,6 +1049,9 @@ __global__ __launch_bounds__(kThreads) void vg_mixed_k(const uint8_t* __restrict
   long bg_stride = 0;
 #include "vcam_tile.inc"
 }
+#undef BSX_VT_TILE
+#undef BSX_VT_POS
+#undef BSX_VT_DESC
 
 }  // namespace
 
@@ -1808,6 +1814,103 @@ hipError_t launch_reset_slots(uint8_t* ofinal, size_t ofinal_bytes, uint8_t* mas
 
 hipError_t launch_fill_u8(uint8_t* p, uint8_t v, size_t bytes, hipStream_t s) {
   return hipMemsetAsync(p, v, bytes, s);
+}
+
+// (Both kernels are templates of one instance, launched by the file's last launcher: the compiler emits plain kernels first and instances in the order of their first
+//  use, and numbers a file's functions as it emits them.  The numbers appear in the assembly of every function behind; as the last two, these move no other
+//  kernel's text, which tools/isa_same.py compares with earlier revisions'.)
+namespace {
+// ---- bsx_step_batch_vcam_geoms: the back end of the geoms step at the virtual camera's geometry — the persistent masks by mask_geoms_k, then ONE resize pass over
+// frame, background and mask taps of every position (vg_geoms_k); no capture-size composite exists.
+// mask_tile_k<BLEND = false> per position: mask_tile_geoms_k's prologue and uniform-tile branch (class byte first, class record and descriptor as two independent
+// uniform loads), then mask_tile.inc without the composite.  Writes the position's persistent mask only: frame, background and output pointers are not read.
+template <int = 0>
+__global__ __launch_bounds__(kThreads) void mask_geoms_k(const GeomClass* __restrict__ classes, const GeomDesc* __restrict__ desc, GeomSpans sp, unsigned xcd_mask,
+                                                        const uint8_t* __restrict__ ofinal, int outW, int outH, const uint8_t* __restrict__ tile_class) {
+  __shared__ short col_c0[kHW], col_c1[kHW], col_a0[kHW], col_a1[kHW];
+  __shared__ short row_r0[kHH], row_r1[kHH], row_b0[kHH], row_b1[kHH];
+  __shared__ __attribute__((aligned(16))) uint16_t hq_hs[kMaxSrcRows * kHW > kHH * kTW ? kMaxSrcRows * kHW : kHH * kTW];
+  __shared__ __attribute__((aligned(16))) uint8_t up[kHH * kHW + 8];
+  uint16_t* const hq = hq_hs;
+  uint16_t* const hs = hq_hs;
+  uint8_t* const blk = up;
+  const int tid = threadIdx.x;
+  int g, w0, p0, p1, per;
+  geom_span(sp, (int)blockIdx.x, &g, &w0, &p0, &p1, &per);
+  unsigned f_, t_;
+  xcd_frame_tile_at(blockIdx.x - (unsigned)w0, (unsigned)per, ((xcd_mask >> g) & 1u) ? (unsigned)(p1 - p0) : 0u, &f_, &t_);
+  const int n = p0 + (int)f_;                                          // the position (descriptor index)
+  int uniform = 0;
+  if (tile_class) uniform = tile_class_byte((uintptr_t)tile_class + (size_t)w0 + (size_t)f_ * (size_t)per + (size_t)t_);
+  const GeomClass c = classes[g];
+  const GeomDescRegs d = geom_desc(desc, n);
+  const int W = c.W, H = c.H;
+  const Rect4 roi = c.roi, q = c.in_roi;
+  const ResizeTab tab = geom_tab(c.up);
+  const int tby = (int)t_ / c.ntx, tbx = (int)t_ - tby * c.ntx, tx0 = tbx * kTW, ty0 = tby * kTH;
+  TileBlendOperands ops;
+  constexpr bool BLEND = false, WH = false, MIX = false, yin = false, early_bg = false;      // mask_tile.inc's names: masks only
+  constexpr long bg_stride = 0;
+  constexpr int yuyv = 0, sel = -1;
+  const uint8_t *const bg = nullptr, *const frames = nullptr;
+  uint8_t *const mask = d.mask, *const outp = nullptr;
+  if (uniform) {
+    tile_vsum5_store<BLEND, WH, MIX>(hq_hs, mask, outp, ops, 0, 0, W, H, roi, tx0, ty0, tid, yuyv, uniform, sel);
+    return;
+  }
+#define BSX_MT_FRAME 0                                               /* the position's own bases: index 0 of each */
+#define BSX_MT_SLOT d.slot
+#define BSX_MT_MASK_SLOT 0
+#include "mask_tile.inc"
+#undef BSX_MT_FRAME
+#undef BSX_MT_SLOT
+#undef BSX_MT_MASK_SLOT
+}
+
+// vg_mixed_k per position: a flat grid of `per` output tiles for each of the call's positions (one output size for all of them).  Capture size, table and the choice
+// between the staged and the per-tap form come from the record of the position's class (workgroup-uniform, as prep_geoms_k chooses between its two bodies); frame,
+// background, mask and output are the position's own pointers, flips and filter switch its descriptor's.  The body is vcam_tile.inc, once per form.
+template <int = 0>
+__global__ __launch_bounds__(kThreads) void vg_geoms_k(const VgClass* __restrict__ vg, const GeomDesc* __restrict__ desc, GeomSpans sp, int per, int ntx, int opt) {
+  const unsigned pn = blockIdx.x / (unsigned)per, tile_ = blockIdx.x - pn * (unsigned)per;
+  const int g = geom_class_of_position(sp, (int)pn);
+  const VgClass c = vg[g];                                            // (uniform index: scalar loads) — independent of the descriptor's
+  const GeomDescRegs d = geom_desc(desc, (int)pn);
+  const int W = c.W, H = c.H;
+  const ResizeTab tab = geom_tab(c.tab);
+  const uint8_t *const frames = d.frame, *const bg = d.bg, *const masks = d.mask;
+  uint8_t* const out = d.out;
+  if ((W & 3) == 0 && ((((uintptr_t)frames) | ((uintptr_t)masks)) & 3) == 0) opt |= kVcWords;      // launch_vg_mixed's rule, per position
+  constexpr bool SEL = true, YIN = false;
+  constexpr long bg_stride = 0;
+  [[maybe_unused]] const int* const slot_of = nullptr;
+#define BSX_VT_TILE tile_
+#define BSX_VT_POS 0l                                                /* the position's own bases: index 0 of each */
+#define BSX_VT_DESC(fl) fl = d.flags
+  if (c.direct) {
+    constexpr bool DIRECT = true;
+#include "vcam_tile.inc"
+  } else {
+    constexpr bool DIRECT = false;
+#include "vcam_tile.inc"
+  }
+#undef BSX_VT_TILE
+#undef BSX_VT_POS
+#undef BSX_VT_DESC
+}
+}  // namespace
+
+hipError_t launch_vcam_geoms(const GeomClass* classes, const VgClass* vg, const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const uint8_t* ofinal, int outW,
+                             int outH, uint8_t* tile_class, int out_w, int out_h, int n, hipStream_t s, unsigned flags) {
+  if (n <= 0 || tiles.wg[kMaxGeoms] <= 0 || out_w <= 0 || out_h <= 0 || (flags & ~1u) || ((flags & 1) && (out_w & 1))) return hipErrorInvalidValue;
+  const int ntx = (out_w + kVW - 1) / kVW, nty = (out_h + kVH - 1) / kVH;
+  if ((unsigned long long)ntx * nty * (unsigned long long)n >= (1ull << 31)) return hipErrorInvalidValue;
+  if (tile_class) tile_class_geoms_k<<<dim3((unsigned)n), kThreads, 0, s>>>(classes, desc, tiles, ofinal, outW, outH, tile_class);
+  mask_geoms_k<><<<dim3((unsigned)tiles.wg[kMaxGeoms]), kThreads, 0, s>>>(classes, desc, tiles, xcd_mask, ofinal, outW, outH, tile_class);
+  const bool owords = (flags & 1) || out_w % 4 == 0;                   // (every d_out is 4-byte aligned: checked by the caller)
+  const int opt = (int)(flags & 1u) | (owords ? kVcOutWords : 0);
+  vg_geoms_k<><<<dim3((unsigned)(ntx * nty) * (unsigned)n), kThreads, 0, s>>>(vg, desc, tiles, ntx * nty, ntx, opt);
+  return hipGetLastError();
 }
 
 }  // namespace bsx

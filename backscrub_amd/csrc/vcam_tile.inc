@@ -1,20 +1,24 @@
-// The body of the two kernels that composite at the virtual camera's geometry (kernels_img.hip: vcam_blend_resize_k, SEL = false, and vg_mixed_k, SEL = true), included
-// INSIDE each kernel: one output tile of position n = blockIdx.y.  It is shared as text and not as a device function because the dense kernel has to stay the code
-// it was: with the body in an inlined function the compiler schedules and allocates the same statements differently.  The including kernel provides the names
-//   frames, bg, bg_stride, masks, slot_of, out, W, H, tab, ntx, opt   and   constexpr bool SEL
-// SEL: `bg` is the batch's MixDesc table — position n's background, its own flip bits and its filter switch come from desc[n] (one 16-byte uniform load), its mask
-// is slot slot_of[n]'s (NULL: slot n); all of it is workgroup-uniform, so the tile's footprint below is the workgroup's own.  Filter off: the composite is the frame
-// (vcam_px / vcam_group with `off`); a background that is not 4-byte aligned takes the byte form for its stream alone.
+// The body of the kernels that composite at the virtual camera's geometry (kernels_img.hip: vcam_blend_resize_k, SEL = false; vg_mixed_k, SEL = true; and
+// vg_geoms_k, SEL = true with every operand per position), included INSIDE each kernel: one output tile of one position.  It is shared as text and not as a device
+// function because the dense kernel has to stay the code it was: with the body in an inlined function the compiler schedules and allocates the same statements
+// differently.  The including kernel provides the names
+//   frames, bg, bg_stride, masks, slot_of, out, W, H, tab, ntx, opt   and   constexpr bool DIRECT, YIN, SEL
+// and three expressions, the way mask_tile.inc takes BSX_MT_FRAME: BSX_VT_TILE, the workgroup's tile inside the output image; BSX_VT_POS, the position n that
+// indexes frames, masks and out (0 where these are the position's own bases); and BSX_VT_DESC(fl), the statement that fetches position n's descriptor.
+// SEL: position n's background, its own flip bits (fl) and its filter switch come from its descriptor (BSX_VT_DESC: in vg_mixed_k one 16-byte uniform load from the
+// MixDesc table that travels in `bg`), its mask is slot slot_of[n]'s (NULL: slot n); all of it is workgroup-uniform, so the tile's footprint below is the
+// workgroup's own.  Filter off: the composite is the frame (vcam_px / vcam_group with `off`); a background that is not 4-byte aligned takes the byte form for its
+// stream alone.
   __shared__ uint32_t s_px[DIRECT ? 1 : kVLdsWords];
-  const int tid = threadIdx.x, ty = (int)blockIdx.x / ntx, tx = (int)blockIdx.x - ty * ntx;
-  const long n = blockIdx.y;
+  const int tid = threadIdx.x, ty = (int)(BSX_VT_TILE) / ntx, tx = (int)(BSX_VT_TILE) - ty * ntx;
+  const long n = BSX_VT_POS;
   const int dw = tab.dw, dh = tab.dh;
   const int dx0 = tx * kVW, dy0 = ty * kVH, dx1 = min(dx0 + kVW, dw) - 1, dy1 = min(dy0 + kVH, dh) - 1;
   [[maybe_unused]] bool off = false;
   [[maybe_unused]] long slot = n;
   if constexpr (SEL) {                                               // position n's descriptor: background, flips, filter switch; its mask is its slot's
     unsigned fl;
-    bg = mix_desc(bg, (int)n, &fl); bg_stride = 0;
+    BSX_VT_DESC(fl);
     off = (fl & kMixFilterOff) != 0;
     opt |= (int)(fl & (kMixFlipH | kMixFlipV));
     if (!off && ((uintptr_t)bg & 3u)) opt &= ~kVcWords;

@@ -25,6 +25,7 @@
  *   bsx_step_batch_vcam_mixed  … both: each stream's own settings, written at the virtual camera's geometry  app/deepseg.cc:387-437, 634-681
  *   bsx_new_geoms          bs_maskgen_new() for cameras of several capture sizes in ONE context  lib/libbackscrub.cc:161-259 (the ROIs of :234-246 once per size)
  *   bsx_step_batch_geoms   … for streams of different capture sizes together: one prep launch, one network pass, one tile launch  app/deepseg.cc:634-673
+ *   bsx_step_batch_vcam_geoms  … the same streams, every composite written at the virtual camera's one size  app/deepseg.cc:634-681
  *   bsx_reset_streams      bsx_reset for a chosen subset of the streams (a slot reused for a new camera)
  *                          (set_input_frame → mask → alpha_blend), batched
  *   bsx_resize_bgr         grab_background() cv::resize   app/background.cc:178-194
@@ -240,8 +241,8 @@ BSX_API int bsx_step_batch_mixed(bsx_ctx* ctx, const int* ids, const uint8_t* d_
  *     class; and, with more than one class, a class the fused tile route does not take (width, roi.x and roi.w multiples of 4 and a tiled linear mask up-scale: the rule
  *     bsx_step_batch_mixed applies per call, applied at creation).  With segm_lite (160 x 96, its ratio held as a float) the reference's ROI arithmetic gives some
  *     16:9 sizes a ROI width that is no multiple of 4 — 1920x1080 -> 1799, 960x540 -> 899, 848x480 -> 799 — and those are refused; 1280x720 and 640x360 are fine;
- *   - on a context of more than one class these work: bsx_step_batch_geoms, bsx_reset, bsx_reset_streams, bsx_get_info (class 0's geometry, the total n_streams),
- *     bsx_geom_count / bsx_get_geom_info, bsx_masks_device, bsx_last_error, bsx_delete, bsx_plan_describe, bsx_debug_buffer (0-2 as always; 3 = the whole mask
+ *   - on a context of more than one class these work: bsx_step_batch_geoms, bsx_step_batch_vcam_geoms, bsx_reset, bsx_reset_streams, bsx_get_info (class 0's
+ *     geometry, the total n_streams), bsx_geom_count / bsx_get_geom_info, bsx_masks_device, bsx_last_error, bsx_delete, bsx_plan_describe, bsx_debug_buffer (0-2 as always; 3 = the whole mask
  *     allocation), bsx_debug_tensor*, and everything that takes its own w, h (bsx_resize_bgr*, bsx_bgr_to_yuyv, bsx_yuyv_to_bgr, bsx_flip_bgr, bsx_gaussian_blur_bgr,
  *     bsx_background_*).  Every other entry point — the dense, by-id, mixed, vcam and pipelined steps, process, composite, profile, live, the debug stages and tile
  *     statistics — returns BSX_EINVAL ("context has N geometries"; bsx_live_new: NULL) and enqueues nothing. */
@@ -280,6 +281,28 @@ typedef struct bsx_geom_item {
   bsx_stream_setting setting;   /* d_bg at the capture size of that class; BSX_STEP_FLIP_H | BSX_STEP_FLIP_V | BSX_STREAM_FILTER_OFF */
 } bsx_geom_item;
 BSX_API int bsx_step_batch_geoms(bsx_ctx* ctx, const int* ids, const bsx_geom_item* items, int n, void* stream, unsigned flags);
+
+/* bsx_step_batch_geoms with every composite written at ONE common size, the virtual camera's (--vg, app/deepseg.cc:674-681): a conference or gallery server that
+ * takes cameras of several capture sizes and sends every participant out at out_w x out_h.  One prep launch, one pass of the network, one tile-class launch, one
+ * masks-only tile launch and ONE resize pass that reads each position's frame, background and mask taps and writes its output, whatever the number of classes:
+ * no capture-size composite, no full-size resized image, no caller-owned scratch, no host synchronisation.
+ *   - ids, items: the rules of bsx_step_batch_geoms (required ids, any order, classes may interleave, the same staging ring).  items[i].d_frame and
+ *     items[i].setting.d_bg have the capture size of the class of ids[i]; items[i].d_out is [out_h][out_w][3], or [out_h][out_w][2] with BSX_STEP_YUYV — the same
+ *     size for every position; setting.flags: BSX_STEP_FLIP_H | BSX_STEP_FLIP_V | BSX_STREAM_FILTER_OFF;
+ *   - flags (batch-wide): BSX_STEP_YUYV only;
+ *   - result, per stream: the output is byte-identical to bsx_resize_bgr(C, W_g, H_g -> out_w, out_h) [then bsx_bgr_to_yuyv], C being the BGR composite
+ *     bsx_step_batch_geoms writes for the same item, its flip included — blend -> flip -> resize -> pack, the order of bsx_step_batch_vcam (an exact 2x down-scale is
+ *     the 2x2 area mean; an output of a class's own size is that class's composite).  The persistent mask and ofinal of every stream of the context, those that
+ *     sit out included, are byte-identical to that call's;
+ *   - the per-class capture -> output tables of each (out_w, out_h) are built and uploaded on the first call at that size and kept by the context;
+ *   - works on every context, also one made by bsx_new (then it is bsx_step_batch_vcam_mixed with per-position pointers);
+ *   - n == 0: returns 0 and enqueues nothing;
+ *   - BSX_EINVAL before anything is enqueued, with a bsx_last_error text naming the position and value, for: the ids errors of bsx_step_batch_streams; items NULL;
+ *     out_w or out_h <= 0; BSX_STEP_NO_MASK (it has no vcam form), BSX_STEP_YUYV_IN and any other batch flag bit; a blur size or a foreign bit in a setting; a NULL
+ *     or not 4-byte aligned d_frame, d_out, or d_bg that is read; an odd out_w with BSX_STEP_YUYV; an output (out_w x out_h) overlapping any frame, background or
+ *     other output of the call; a pending pipelined composite; an onmask callback; a stream whose class is off the fused tile route (possible only in a one-class
+ *     context, which bsx_step_batch_vcam_mixed takes).  A refused call changes no state.  BSX_EDEVICE for a batch of 2^31 workgroups or more. */
+BSX_API int bsx_step_batch_vcam_geoms(bsx_ctx* ctx, const int* ids, const bsx_geom_item* items, int n, int out_w, int out_h, void* stream, unsigned flags);
 
 /* Reset the temporal state of the listed streams only (ofinal → 0, persistent mask → 255, as bsx_reset does for all) — a slot reused for a new camera.  The
  * other streams' state is untouched, and a pending pipelined composite is NOT dropped: the call is refused (BSX_EINVAL) while one is pending.  Same ids rules,
