@@ -24,8 +24,16 @@ DEBUG_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p)
 STAGE_FN = C.CFUNCTYPE(None, C.c_void_p)
 
 
+BSX_STREAM_FILTER_OFF = 32          # bsx.h: bits of bsx_stream_setting.flags next to the flip bits and the blur size
+BSX_STREAM_YUYV_IN = 64             # ... in an item of step_geoms / step_vcam_geoms only: that item's frame is YUYV 4:2:2
+
+
 class BsxError(RuntimeError):
     pass
+
+
+class BsxFrameFormatError(BsxError, ValueError):
+    """a frame tensor of step_geoms / step_vcam_geoms whose shape is not that of its item's class and pixel format ([H,W,3] BGR, [H,W,2] with yuyv_in)"""
 
 
 class _Info(C.Structure):
@@ -60,18 +68,21 @@ class _GeomItem(C.Structure):               # bsx.h bsx_geom_item
 class StreamSetting:
     """one stream's settings for MaskGen.step_mixed — what one reference process takes as -b <image> (bg), -H / -V (flip_h / flip_v), -p bgblur:<k> (bgblur)
     and toggles at run time with the s / h / v keys (filter_off, flip_h, flip_v; app/deepseg.cc:387-437, 624-673, 777-790).  bg: a cuda uint8 [H,W,3] image
-    (any number of streams may share one); unused with bgblur or filter_off."""
-    __slots__ = ("bg", "flip_h", "flip_v", "bgblur", "filter_off")
+    (any number of streams may share one); unused with bgblur or filter_off.  yuyv_in (step_geoms / step_vcam_geoms only, where every item brings its own frame):
+    this item's frame is the camera's raw YUYV 4:2:2 [H,W,2] (BSX_STREAM_YUYV_IN); the mixed steps take the format batch-wide and refuse it."""
+    __slots__ = ("bg", "flip_h", "flip_v", "bgblur", "filter_off", "yuyv_in")
 
-    def __init__(self, bg=None, flip_h=False, flip_v=False, bgblur=0, filter_off=False):
+    def __init__(self, bg=None, flip_h=False, flip_v=False, bgblur=0, filter_off=False, yuyv_in=False):
         self.bg, self.flip_h, self.flip_v, self.bgblur, self.filter_off = bg, bool(flip_h), bool(flip_v), int(bgblur), bool(filter_off)
+        self.yuyv_in = bool(yuyv_in)
 
     def flags(self):
-        return (2 if self.flip_h else 0) | (4 if self.flip_v else 0) | ((self.bgblur & 255) << 8) | (32 if self.filter_off else 0)
+        return ((2 if self.flip_h else 0) | (4 if self.flip_v else 0) | ((self.bgblur & 255) << 8) | (BSX_STREAM_FILTER_OFF if self.filter_off else 0) |
+                (BSX_STREAM_YUYV_IN if self.yuyv_in else 0))
 
     def __repr__(self):
-        return "StreamSetting(bg=%s, flip_h=%s, flip_v=%s, bgblur=%d, filter_off=%s)" % (
-            "None" if self.bg is None else "<image>", self.flip_h, self.flip_v, self.bgblur, self.filter_off)
+        return "StreamSetting(bg=%s, flip_h=%s, flip_v=%s, bgblur=%d, filter_off=%s%s)" % (
+            "None" if self.bg is None else "<image>", self.flip_h, self.flip_v, self.bgblur, self.filter_off, ", yuyv_in=True" if self.yuyv_in else "")
 
 
 class LaunchStat(C.Structure):
@@ -259,8 +270,9 @@ class MaskGen:
 
     def step_geoms(self, ids, frames, outs, settings, yuyv=False, no_mask=False):
         """one main-loop iteration for streams of ANY mix of the context's geometry classes (bsx_step_batch_geoms): ids[i] names the stream of position i, frames[i]
-        (cuda uint8 [H_g, W_g, 3]), outs[i] ([H_g, W_g, 3], or [.., 2] with yuyv) and settings[i] (a StreamSetting: bg at the class's size, flip_h, flip_v,
-        filter_off; no bgblur) have the capture size of that stream's class.  One prep launch, one network pass, one tile launch whatever the mix."""
+        (cuda uint8 [H_g, W_g, 3] BGR, or the camera's raw YUYV 4:2:2 [H_g, W_g, 2] for an item whose setting has yuyv_in), outs[i] ([H_g, W_g, 3], or [.., 2]
+        with yuyv) and settings[i] (a StreamSetting: bg at the class's size, flip_h, flip_v, filter_off, yuyv_in; no bgblur) have the capture size of that
+        stream's class.  One prep launch, one network pass, one tile launch whatever the mix of sizes and pixel formats."""
         torch = _torch()
         arr, n = _ids(ids)
         frames, outs, settings = list(frames), list(outs), list(settings)
@@ -274,11 +286,13 @@ class MaskGen:
 
             def ok(t, c):
                 return isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and self._on_device(t) and tuple(t.shape) == (H, W, c) and t.is_contiguous()
-            if not ok(frames[i], 3):
-                raise BsxError("frames[%d] must be a contiguous cuda:%d uint8 tensor [%d,%d,3] (stream %d)" % (i, self.device, H, W, arr[i]))
+            s = settings[i]
+            fch = 2 if isinstance(s, StreamSetting) and s.yuyv_in else 3      # the item's own pixel format: YUYV 4:2:2 or BGR
+            if not ok(frames[i], fch):
+                raise BsxFrameFormatError("frames[%d] must be a contiguous cuda:%d uint8 tensor [%d,%d,%d] (stream %d%s)" % (
+                    i, self.device, H, W, fch, arr[i], ", a YUYV item" if fch == 2 else ""))
             if not ok(outs[i], ch):
                 raise BsxError("outs[%d] must be a contiguous cuda:%d uint8 tensor [%d,%d,%d] (stream %d)" % (i, self.device, H, W, ch, arr[i]))
-            s = settings[i]
             if not isinstance(s, StreamSetting):
                 raise BsxError("settings[%d] is not a StreamSetting" % i)
             if s.bgblur:
@@ -296,7 +310,8 @@ class MaskGen:
 
     def step_vcam_geoms(self, ids, frames, outs, settings, yuyv=False):
         """step_geoms with every composite written at ONE common size, the virtual camera's (bsx_step_batch_vcam_geoms): frames[i] and settings[i].bg have the
-        capture size of the class of ids[i]; every outs[i] is a cuda uint8 [out_h, out_w, 3] (or [.., 2] with yuyv) — the size is taken from outs[0].  Blend ->
+        capture size of the class of ids[i] (frames[i] is [H_g, W_g, 2] YUYV 4:2:2 where settings[i].yuyv_in); every outs[i] is a cuda uint8 [out_h, out_w, 3]
+        (or [.., 2] with yuyv) — the size is taken from outs[0].  Blend ->
         flip -> resize -> [pack] in one pass per position: no capture-size composite is stored."""
         torch = _torch()
         arr, n = _ids(ids)
@@ -318,11 +333,13 @@ class MaskGen:
 
             def ok(t, shape):
                 return isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and self._on_device(t) and tuple(t.shape) == shape and t.is_contiguous()
-            if not ok(frames[i], (H, W, 3)):
-                raise BsxError("frames[%d] must be a contiguous cuda:%d uint8 tensor [%d,%d,3] (stream %d)" % (i, self.device, H, W, arr[i]))
+            s = settings[i]
+            fch = 2 if isinstance(s, StreamSetting) and s.yuyv_in else 3      # the item's own pixel format: YUYV 4:2:2 or BGR
+            if not ok(frames[i], (H, W, fch)):
+                raise BsxFrameFormatError("frames[%d] must be a contiguous cuda:%d uint8 tensor [%d,%d,%d] (stream %d%s)" % (
+                    i, self.device, H, W, fch, arr[i], ", a YUYV item" if fch == 2 else ""))
             if not ok(outs[i], (out_h, out_w, ch)):
                 raise BsxError("outs[%d] must be a contiguous cuda:%d uint8 tensor [%d,%d,%d] (the size of outs[0])" % (i, self.device, out_h, out_w, ch))
-            s = settings[i]
             if not isinstance(s, StreamSetting):
                 raise BsxError("settings[%d] is not a StreamSetting" % i)
             if s.bgblur:

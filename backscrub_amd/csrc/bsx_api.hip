@@ -1081,11 +1081,30 @@ int resize_batch_stage(bsx_ctx* c, const bsx_resize_item* items, int n, int dw, 
 // ---- bsx_step_batch_geoms: streams of any mix of geometry classes in ONE prep launch, ONE network pass, ONE tile-class and ONE tile launch ----------------------
 // Checked on the host (ids, then every position against the class of its id, then the overlaps), then: the positions ordered by class, their ids and descriptors
 // through the staging ring, the per-class spans of the ragged grids by value in the kernel arguments.
-constexpr unsigned kGeomStreamFlags = BSX_STEP_FLIP_H | BSX_STEP_FLIP_V | BSX_STREAM_FILTER_OFF;
+constexpr unsigned kGeomStreamFlags = BSX_STEP_FLIP_H | BSX_STEP_FLIP_V | BSX_STREAM_FILTER_OFF | BSX_STREAM_YUYV_IN;
+static_assert(BSX_STREAM_YUYV_IN == kGeomYuyvIn, "descriptor flags = the public bits");
+
+// does any item of the call bring a YUYV frame?  Then the call takes the launchers whose kernels read the format per position (kernels.hpp: launch_*_geoms_fmt)
+inline bool geoms_any_yuyv(const bsx_geom_item* items, int n) {
+  for (int i = 0; i < n; i++) if (items[i].setting.flags & BSX_STREAM_YUYV_IN) return true;
+  return false;
+}
+// A YUYV item of class g: BSX_OK where the class has the fused YUYV prep (prep_yuyv_fusable), else the refusal, which names the table that is in the way.  There is
+// no conversion fallback here: the caller converts that stream with bsx_yuyv_to_bgr.
+int geoms_yuyv_item(bsx_ctx* c, const char* fn, int i, int id, int g, const bsx_ctx::Geom& G) {
+  const ResizeTab& t = G.tab_down.tab;
+  if (prep_yuyv_fusable(G.width, G.roi, t)) return BSX_OK;
+  char why[160];
+  if (t.mode == 1) snprintf(why, sizeof why, "its down-scale table is a copy (capture ROI %d x %d = model ROI)", G.roi.w, G.roi.h);
+  else if (t.mode == 2) snprintf(why, sizeof why, "its down-scale table is the 2x2 area mean (capture ROI %d x %d = twice the model ROI)", G.roi.w, G.roi.h);
+  else snprintf(why, sizeof why, "its down-scale table is linear but width %d and roi.x %d must be even and the ROI row at least 4 pixels", G.width, G.roi.x);
+  return refuse(c, fn, "items[%d]: stream %d is of class %d (%d x %d), which has no fused YUYV prep: %s; convert that stream's frames with bsx_yuyv_to_bgr and pass them as BGR",
+                i, id, g, G.width, G.height, why);
+}
 
 int geoms_check(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item* items, int n, unsigned flags) {
   if (!items) return refuse(c, fn, "items is NULL");
-  if (flags & BSX_STEP_YUYV_IN) return refuse(c, fn, "flags 0x%x: YUYV input frames are not taken by the multi-geometry step", flags);
+  if (flags & BSX_STEP_YUYV_IN) return refuse(c, fn, "flags 0x%x: YUYV input frames are not taken by the multi-geometry step as a batch flag (the format belongs to the item: the yuyv-in bit, 0x40, of items[i].setting.flags)", flags);
   if (flags & ~(BSX_STEP_YUYV | BSX_STEP_NO_MASK)) return refuse(c, fn, "flags 0x%x has bits outside yuyv / no-mask", flags);
   if (const int rc = refuse_pending(c, fn)) return rc;
   if (c->onmask) return refuse(c, fn, "needs the fused mask + blend route (no onmask callback)");
@@ -1098,7 +1117,7 @@ int geoms_check(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item*
     const bsx_ctx::Geom& G = c->geoms[g];
     const unsigned f = it.setting.flags;
     if (f & 0xFF00u) return refuse(c, fn, "items[%d]: setting flags 0x%x asks for a background blur, which the multi-geometry step does not take", i, f);
-    if (f & ~kGeomStreamFlags) return refuse(c, fn, "items[%d]: setting flags 0x%x has bits outside flip / filter-off", i, f);
+    if (f & ~kGeomStreamFlags) return refuse(c, fn, "items[%d]: setting flags 0x%x has bits outside flip / filter-off / yuyv-in", i, f);
     if (!it.d_frame) return refuse(c, fn, "items[%d]: d_frame is NULL", i);
     if ((uintptr_t)it.d_frame & 3) return refuse(c, fn, "items[%d]: d_frame %p is not 4-byte aligned", i, (const void*)it.d_frame);
     if (!it.d_out) return refuse(c, fn, "items[%d]: d_out is NULL", i);
@@ -1107,8 +1126,9 @@ int geoms_check(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item*
     if (!G.fusable)
       return refuse(c, fn, "items[%d]: stream %d is of class %d (%d x %d), which is off the fused tile route (width, roi.x, roi.w multiples of 4, a tiled linear mask up-scale)",
                     i, ids[i], g, G.width, G.height);
+    if (f & BSX_STREAM_YUYV_IN) if (const int rc = geoms_yuyv_item(c, fn, i, ids[i], g, G)) return rc;
     const size_t px = (size_t)G.width * G.height;
-    sp.push_back({(uintptr_t)it.d_frame, (uintptr_t)it.d_frame + px * 3, i, false});
+    sp.push_back({(uintptr_t)it.d_frame, (uintptr_t)it.d_frame + px * ((f & BSX_STREAM_YUYV_IN) ? 2 : 3), i, false});      // the frame's real extent
     sp.push_back({(uintptr_t)it.d_out, (uintptr_t)it.d_out + px * (yuyv ? 2 : 3), i, true});
     if (f & BSX_STREAM_FILTER_OFF) continue;                          // reads no background
     if (!it.setting.d_bg) return refuse(c, fn, "items[%d]: setting.d_bg is NULL", i);
@@ -1125,7 +1145,7 @@ int geoms_check(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item*
 
 // The front of a checked geoms call on the context's device, ring entry k acquired: the positions ordered by class, ids and descriptors through the ring, ONE prep
 // launch and the network.  Leaves the descriptors' device copy, the ragged grids of the back end and the classes whose tiles keep to one XCD.
-struct GeomsStaged { const GeomDesc* desc = nullptr; GeomSpans tiles{}, outside{}; unsigned xcd_mask = 0; };
+struct GeomsStaged { const GeomDesc* desc = nullptr; GeomSpans tiles{}, outside{}; unsigned xcd_mask = 0; bool fmt = false; };      // fmt: some item is YUYV — the *_fmt launchers
 int geoms_front(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item* items, int n, hipStream_t s, int k, GeomsStaged* st) {
   const int G = (int)c->geoms.size();
   // positions ordered by class (a counting sort: stable, so a class keeps the caller's order)
@@ -1157,8 +1177,9 @@ int geoms_front(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item*
     c->geo_ids[(size_t)j] = id;
     const bool off = (it.setting.flags & BSX_STREAM_FILTER_OFF) != 0;
     hd[j] = GeomDesc{it.d_frame, it.d_out, off ? nullptr : it.setting.d_bg, c->d_masks + q.mask_offset + (size_t)(id - q.first) * q.width * q.height,
-                     it.setting.flags & (kMixFlipH | kMixFlipV | kMixFilterOff), id, {0, 0}};
+                     it.setting.flags & (kMixFlipH | kMixFlipV | kMixFilterOff | kGeomYuyvIn), id, {0, 0}};
   }
+  st->fmt = geoms_any_yuyv(items, n);
   const int* d_ids = nullptr;
   if (const int rc = ids_copy(c, c->geo_ids.data(), n, s, k, &d_ids)) return rc;
   GeomDesc* const dd = c->d_geo + (size_t)k * c->n_streams;
@@ -1167,7 +1188,7 @@ int geoms_front(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item*
   {
     bsx_roctx::Range range("bsx:prep");
     float* f32 = !c->in_u8 ? c->tensor_ptr(c->plan.input) : nullptr;
-    BSX_HIP(c, launch_prep_geoms(c->d_geom_classes, dd, prep, f32, c->in_u8 ? c->d_net_in_u8 : nullptr, c->inW, c->inH, c->bilateral, n, s));
+    BSX_HIP(c, (st->fmt ? launch_prep_geoms_fmt : launch_prep_geoms)(c->d_geom_classes, dd, prep, f32, c->in_u8 ? c->d_net_in_u8 : nullptr, c->inW, c->inH, c->bilateral, n, s));
   }
   return infer_after_prep(c, n, s, 0, d_ids);
 }
@@ -1177,7 +1198,7 @@ int geoms_run(bsx_ctx* c, const int* ids, const bsx_geom_item* items, int n, hip
   GeomsStaged st;
   if (const int rc = geoms_front(c, "bsx_step_batch_geoms", ids, items, n, s, k, &st)) return rc;
   bsx_roctx::Range range("bsx:mask+blend");
-  BSX_HIP(c, launch_mask_blend_geoms(c->d_geom_classes, st.desc, st.tiles, st.xcd_mask, st.outside, c->d_ofinal, c->outW, c->outH, c->d_geom_tile_class, n, s, (int)flags));
+  BSX_HIP(c, (st.fmt ? launch_mask_blend_geoms_fmt : launch_mask_blend_geoms)(c->d_geom_classes, st.desc, st.tiles, st.xcd_mask, st.outside, c->d_ofinal, c->outW, c->outH, c->d_geom_tile_class, n, s, (int)flags));
   return BSX_OK;
 }
 
@@ -1188,7 +1209,7 @@ int vcam_geoms_check(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_
   if (!items) return refuse(c, fn, "items is NULL");
   if (out_w <= 0 || out_h <= 0) return refuse(c, fn, "output size %d x %d must be positive", out_w, out_h);
   if (flags & BSX_STEP_NO_MASK) return refuse(c, fn, "unsupported flags 0x%x (the no-mask step has no vcam form)", flags);
-  if (flags & BSX_STEP_YUYV_IN) return refuse(c, fn, "flags 0x%x: YUYV input frames are not taken by the multi-geometry step", flags);
+  if (flags & BSX_STEP_YUYV_IN) return refuse(c, fn, "flags 0x%x: YUYV input frames are not taken by the multi-geometry step as a batch flag (the format belongs to the item: the yuyv-in bit, 0x40, of items[i].setting.flags)", flags);
   if (flags & ~BSX_STEP_YUYV) return refuse(c, fn, "flags 0x%x has bits outside yuyv", flags);
   if (const int rc = refuse_pending(c, fn)) return rc;
   if (c->onmask) return refuse(c, fn, "needs the fused mask route (no onmask callback)");
@@ -1203,7 +1224,7 @@ int vcam_geoms_check(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_
     const bsx_ctx::Geom& G = c->geoms[g];
     const unsigned f = it.setting.flags;
     if (f & 0xFF00u) return refuse(c, fn, "items[%d]: setting flags 0x%x asks for a background blur, which the multi-geometry step does not take", i, f);
-    if (f & ~kGeomStreamFlags) return refuse(c, fn, "items[%d]: setting flags 0x%x has bits outside flip / filter-off", i, f);
+    if (f & ~kGeomStreamFlags) return refuse(c, fn, "items[%d]: setting flags 0x%x has bits outside flip / filter-off / yuyv-in", i, f);
     if (!it.d_frame) return refuse(c, fn, "items[%d]: d_frame is NULL", i);
     if ((uintptr_t)it.d_frame & 3) return refuse(c, fn, "items[%d]: d_frame %p is not 4-byte aligned", i, (const void*)it.d_frame);
     if (!it.d_out) return refuse(c, fn, "items[%d]: d_out is NULL", i);
@@ -1211,8 +1232,9 @@ int vcam_geoms_check(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_
     if (!G.fusable)
       return refuse(c, fn, "items[%d]: stream %d is of class %d (%d x %d), which is off the fused tile route (width, roi.x, roi.w multiples of 4, a tiled linear mask up-scale); "
                     "bsx_step_batch_vcam_mixed takes such a context", i, ids[i], g, G.width, G.height);
+    if (f & BSX_STREAM_YUYV_IN) if (const int rc = geoms_yuyv_item(c, fn, i, ids[i], g, G)) return rc;
     const size_t px = (size_t)G.width * G.height;
-    sp.push_back({(uintptr_t)it.d_frame, (uintptr_t)it.d_frame + px * 3, i, false});
+    sp.push_back({(uintptr_t)it.d_frame, (uintptr_t)it.d_frame + px * ((f & BSX_STREAM_YUYV_IN) ? 2 : 3), i, false});      // the frame's real extent
     sp.push_back({(uintptr_t)it.d_out, (uintptr_t)it.d_out + out_bytes, i, true});
     if (f & BSX_STREAM_FILTER_OFF) continue;                          // reads no background
     if (!it.setting.d_bg) return refuse(c, fn, "items[%d]: setting.d_bg is NULL", i);
@@ -1267,7 +1289,7 @@ int vcam_geoms_run(bsx_ctx* c, const int* ids, const bsx_geom_item* items, int n
   GeomsStaged st;
   if (const int rc = geoms_front(c, fn, ids, items, n, s, k, &st)) return rc;
   bsx_roctx::Range range("bsx:mask+vcam");
-  BSX_HIP(c, launch_vcam_geoms(c->d_geom_classes, vg, st.desc, st.tiles, st.xcd_mask, c->d_ofinal, c->outW, c->outH, c->d_geom_tile_class, out_w, out_h, n, s, flags & 1u));
+  BSX_HIP(c, (st.fmt ? launch_vcam_geoms_fmt : launch_vcam_geoms)(c->d_geom_classes, vg, st.desc, st.tiles, st.xcd_mask, c->d_ofinal, c->outW, c->outH, c->d_geom_tile_class, out_w, out_h, n, s, flags & 1u));
   return BSX_OK;
 }
 

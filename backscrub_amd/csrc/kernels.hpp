@@ -159,13 +159,14 @@ hipError_t launch_mask_blend_mixed(const uint8_t* ofinal, int outW, int outH, Re
 // The two ends of the pipeline that see the capture size read it per position.  Three pieces, each as cheap as its rate of change allows:
 //   GeomClass   one constant record per class, uploaded once: capture size, both ROIs, both resize tables, the mask tiling;
 //   GeomDesc    one record per position of a call, staged through the context's ring, ORDERED BY CLASS: the position's own frame / output / background / persistent
-//               mask pointers, its MixDesc flags and its state slot;
+//               mask pointers, its MixDesc flags, the format of its frame (kGeomYuyvIn) and its state slot;
 //   GeomSpans   by value in the kernel arguments: per class the first position and the first workgroup of its segment of the (ragged) grid, and the workgroups
 //               one position takes.  A workgroup finds its class with compares on SGPRs, then position = pos[g] + local / per[g] and item = local % per[g] — no load
 //               in front of the tile-class byte but the kernel arguments themselves, exactly as in the mixed step; class record and descriptor are two independent
 //               uniform loads next to it.  (A binary search through a device prefix array would put a chain of dependent loads there, a per-workgroup table would
 //               stage a word per tile per call.)
 constexpr int kMaxGeoms = 8;
+constexpr unsigned kGeomYuyvIn = 64u;      // GeomDesc::flags: the position's frame is YUYV 4:2:2 (BSX_STREAM_YUYV_IN) — read by the *_fmt launchers' kernels only
 struct alignas(16) GeomClass {
   int W, H;
   int ntx, nty;                  // mask tiles per ROI row / column (kTW x kTH)
@@ -173,11 +174,11 @@ struct alignas(16) GeomClass {
   ResizeTab down, up;            // ROI -> model canvas (prep), model output -> ROI (mask); up.tile_class is unused (the call's scratch travels as an argument)
 };
 struct alignas(16) GeomDesc {
-  const uint8_t* frame;          // [H][W][3] BGR of the position's class
+  const uint8_t* frame;          // [H][W][3] BGR of the position's class, or [H][W][2] YUYV (Y0 U Y1 V) with kGeomYuyvIn
   uint8_t* out;                  // [H][W][3], or [H][W][2] with the batch's YUYV bit
   const uint8_t* bg;             // the position's background (unread with kMixFilterOff)
   uint8_t* mask;                 // the stream's persistent mask [H][W]
-  unsigned flags;                // kMixFlipH | kMixFlipV | kMixFilterOff
+  unsigned flags;                // kMixFlipH | kMixFlipV | kMixFilterOff | kGeomYuyvIn
   int slot;                      // the stream id: ofinal slot
   int pad[2];
 };
@@ -206,6 +207,16 @@ hipError_t launch_mask_blend_geoms(const GeomClass* classes, const GeomDesc* des
 struct alignas(16) VgClass { int W, H, direct, pad; ResizeTab tab; };
 hipError_t launch_vcam_geoms(const GeomClass* classes, const VgClass* vg, const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const uint8_t* ofinal, int outW,
                              int outH, uint8_t* tile_class, int out_w, int out_h, int n, hipStream_t s, unsigned flags);
+// The three launchers above for a call in which at least one position's frame is YUYV 4:2:2 (kGeomYuyvIn in its descriptor): the same launch sequences with
+// the kernels that read a frame replaced by forms that choose, per workgroup and on a scalar, between the BGR and the YUYV inclusion of the same bodies — the
+// per-position forms of prep_fused_k<OUT, true, true>, mask_tile_k<true, true, false, false, true>, outside_roi_mixed_k's bit 4 and vg_mixed_k<DIRECT, true>.
+// Every YUYV position's class must satisfy prep_yuyv_fusable (checked by the caller); a call of BGR positions takes the launchers above, whose code is unchanged.
+hipError_t launch_prep_geoms_fmt(const GeomClass* classes, const GeomDesc* desc, const GeomSpans& spans, float* input, uint32_t* input_u8, int inW, int inH,
+                                 BilateralParams bp, int n, hipStream_t s);
+hipError_t launch_mask_blend_geoms_fmt(const GeomClass* classes, const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const GeomSpans& outside,
+                                       const uint8_t* ofinal, int outW, int outH, uint8_t* tile_class, int n, hipStream_t s, int flags);
+hipError_t launch_vcam_geoms_fmt(const GeomClass* classes, const VgClass* vg, const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const uint8_t* ofinal,
+                                 int outW, int outH, uint8_t* tile_class, int out_w, int out_h, int n, hipStream_t s, unsigned flags);
 // alpha blend.  deepseg.cc:108-134
 hipError_t launch_blend(const uint8_t* bg, size_t bg_stride, const uint8_t* frames, const uint8_t* masks, uint8_t* out, size_t npix,
                         int n, hipStream_t s, const int* slot_of = nullptr);

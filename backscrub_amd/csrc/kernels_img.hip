@@ -1913,4 +1913,195 @@ hipError_t launch_vcam_geoms(const GeomClass* classes, const VgClass* vg, const 
   return hipGetLastError();
 }
 
+// ---- the geoms steps with a frame format per position (BSX_STREAM_YUYV_IN in an item's setting: kGeomYuyvIn in its descriptor) --------------------------------------
+// The four kernels above that read a frame, each with the descriptor's format bit — workgroup-uniform, it arrives with the loads geom_desc makes anyway — choosing
+// ONCE between the YIN = true and the YIN = false inclusion of the shared body (prep_tile.inc, mask_tile.inc, vcam_tile.inc; outside_mixed_group reads the bit from its
+// flags), the way prep_geoms_k chooses between its two table modes.  Kernels of their own, launched only by the launchers below and only for a call with at least one
+// YUYV item: a call of BGR items launches prep_geoms_k, mask_tile_geoms_k, outside_roi_geoms_k and vg_geoms_k, the code it always did.  LDS is declared once per
+// kernel and shared by its inclusions (an array declared inside each inclusion would be allocated once per inclusion).  Templates used by the file's last launchers
+// for the reason given above mask_geoms_k.
+namespace {
+// prep_geoms_k + prep_fused_k<OUT, true, true> per position.  A YUYV position's class has a linear table and an even ROI column (prep_yuyv_fusable: the host refuses
+// the item otherwise), so the format bit alone selects the YIN body.
+template <int OUT>
+__global__ __launch_bounds__(kThreads) void prep_geoms_fmt_k(const GeomClass* __restrict__ classes, const GeomDesc* __restrict__ desc, GeomSpans sp, float* __restrict__ input,
+                                                            uint32_t* __restrict__ input_u8, int inW, int inH, BilateralParams bp, int TW, int TH, int ntx, int nty, int n_frames) {
+  __shared__ float lut[768];
+  __shared__ uint32_t tile[kPfS * kPfS];
+  const int tid = threadIdx.x;
+  unsigned f_, t_;
+  xcd_frame_tile((unsigned)(ntx * nty), (unsigned)n_frames, &f_, &t_);
+  const int g = geom_class_of_position(sp, (int)f_);
+  const GeomClass c = classes[g];                                     // (uniform index: scalar loads) — independent of the descriptor's
+  const GeomDescRegs d = geom_desc(desc, (int)f_);
+  const uint8_t* const frames = d.frame;
+  const ResizeTab tab = geom_tab(c.down);
+  const int W = c.W, H = c.H;
+  const Rect4 roi = c.roi, q = c.in_roi;
+  const long n = (long)f_;
+#define BSX_PREP_FRAME 0l                                            /* the position's own frame */
+  if (d.flags & kGeomYuyvIn) {
+    constexpr bool LINEAR = true, YIN = true;
+#include "prep_tile.inc"
+  } else if (tab.mode == 0 && (W - roi.x) * 3 >= 8) {                 // prep_geoms_k's choice
+    constexpr bool LINEAR = true, YIN = false;
+#include "prep_tile.inc"
+  } else {
+    constexpr bool LINEAR = false, YIN = false;
+#include "prep_tile.inc"
+  }
+#undef BSX_PREP_FRAME
+}
+
+// mask_tile_geoms_k + mask_tile_k<true, YIN, false, false, true> per position: mask_tile_geoms_k's prologue, then uniform-tile branch and mask_tile.inc once per format
+template <int = 0>
+__global__ __launch_bounds__(kThreads) void mask_tile_geoms_fmt_k(const GeomClass* __restrict__ classes, const GeomDesc* __restrict__ desc, GeomSpans sp, unsigned xcd_mask,
+                                                                 const uint8_t* __restrict__ ofinal, int outW, int outH, const uint8_t* __restrict__ tile_class, int flags) {
+  __shared__ short col_c0[kHW], col_c1[kHW], col_a0[kHW], col_a1[kHW];
+  __shared__ short row_r0[kHH], row_r1[kHH], row_b0[kHH], row_b1[kHH];
+  __shared__ __attribute__((aligned(16))) uint16_t hq_hs[kMaxSrcRows * kHW > kHH * kTW ? kMaxSrcRows * kHW : kHH * kTW];
+  __shared__ __attribute__((aligned(16))) uint8_t up[kHH * kHW + 8];
+  uint16_t* const hq = hq_hs;
+  uint16_t* const hs = hq_hs;
+  uint8_t* const blk = up;
+  const int tid = threadIdx.x;
+  int g, w0, p0, p1, per;
+  geom_span(sp, (int)blockIdx.x, &g, &w0, &p0, &p1, &per);
+  unsigned f_, t_;
+  xcd_frame_tile_at(blockIdx.x - (unsigned)w0, (unsigned)per, ((xcd_mask >> g) & 1u) ? (unsigned)(p1 - p0) : 0u, &f_, &t_);
+  const int n = p0 + (int)f_;                                          // the position (descriptor index)
+  int uniform = 0;
+  if (tile_class) uniform = tile_class_byte((uintptr_t)tile_class + (size_t)w0 + (size_t)f_ * (size_t)per + (size_t)t_);
+  const GeomClass c = classes[g];
+  const GeomDescRegs d = geom_desc(desc, n);
+  const int W = c.W, H = c.H;
+  const Rect4 roi = c.roi, q = c.in_roi;
+  const ResizeTab tab = geom_tab(c.up);
+  const int tby = (int)t_ / c.ntx, tbx = (int)t_ - tby * c.ntx, tx0 = tbx * kTW, ty0 = tby * kTH;
+  flags = (flags & ~16) | (int)(d.flags & (kMixFlipH | kMixFlipV));
+  const int sel = (d.flags & kMixFilterOff) ? 2 : -1;
+  TileBlendOperands ops;
+  constexpr bool BLEND = true, WH = false, MIX = true, early_bg = false;      // mask_tile.inc's names: the instantiation, the position's descriptor
+  constexpr long bg_stride = 0;
+  const uint8_t *const bg = d.bg, *const frames = d.frame;
+  uint8_t *const mask = d.mask, *const outp = d.out;
+#define BSX_MT_FRAME 0                                               /* the position's own bases: index 0 of each */
+#define BSX_MT_SLOT d.slot
+#define BSX_MT_MASK_SLOT 0
+#define BSX_MT_POSITION                                                                                                        \
+    if (uniform) {                                                                                                             \
+      tile_load_blend_operands<BLEND, WH, MIX>(ops, bg, bg_stride, frames, 0, W, H, roi, tx0, ty0, tid, uniform, 3, yin, sel); \
+      tile_vsum5_store<BLEND, WH, MIX>(hq_hs, mask, outp, ops, 0, 0, W, H, roi, tx0, ty0, tid, yuyv, uniform, sel);            \
+      return;                                                                                                                  \
+    }
+  if (d.flags & kGeomYuyvIn) {
+    constexpr bool yin = true;
+    const int yuyv = flags | 16;                                       // bit 4: the frame operand arrives as YUYV (tile_vsum5_store)
+    BSX_MT_POSITION
+#include "mask_tile.inc"
+  } else {
+    constexpr bool yin = false;
+    const int yuyv = flags;
+    BSX_MT_POSITION
+#include "mask_tile.inc"
+  }
+#undef BSX_MT_POSITION
+#undef BSX_MT_FRAME
+#undef BSX_MT_SLOT
+#undef BSX_MT_MASK_SLOT
+}
+
+// outside_roi_geoms_k with the position's format as bit 4 of the flags outside_mixed_group reads (a filter-off YUYV position's strips are its frame, converted)
+template <int = 0>
+__global__ __launch_bounds__(kThreads) void outside_roi_geoms_fmt_k(const GeomClass* __restrict__ classes, const GeomDesc* __restrict__ desc, GeomSpans sp, int flags) {
+  int g, w0, p0, p1, per;
+  geom_span(sp, (int)blockIdx.x, &g, &w0, &p0, &p1, &per);
+  const unsigned local = blockIdx.x - (unsigned)w0, pl = local / (unsigned)per, blk = local - pl * (unsigned)per;
+  const GeomClass c = classes[g];
+  const GeomDescRegs d = geom_desc(desc, p0 + (int)pl);
+  outside_mixed_group(blk * kThreads + threadIdx.x, d.bg, d.flags, d.frame, d.out, c.W, c.H, c.roi, (flags & ~16) | ((d.flags & kGeomYuyvIn) ? 16 : 0));
+}
+
+// vg_geoms_k + vg_mixed_k<DIRECT, YIN> per position: vcam_tile.inc once per (form, format), one staging area for all four
+template <int = 0>
+__global__ __launch_bounds__(kThreads) void vg_geoms_fmt_k(const VgClass* __restrict__ vg, const GeomDesc* __restrict__ desc, GeomSpans sp, int per, int ntx, int opt) {
+  __shared__ uint32_t s_px[kVLdsWords];
+  const unsigned pn = blockIdx.x / (unsigned)per, tile_ = blockIdx.x - pn * (unsigned)per;
+  const int g = geom_class_of_position(sp, (int)pn);
+  const VgClass c = vg[g];                                            // (uniform index: scalar loads) — independent of the descriptor's
+  const GeomDescRegs d = geom_desc(desc, (int)pn);
+  const int W = c.W, H = c.H;
+  const ResizeTab tab = geom_tab(c.tab);
+  const uint8_t *const frames = d.frame, *const bg = d.bg, *const masks = d.mask;
+  uint8_t* const out = d.out;
+  if ((W & 3) == 0 && ((((uintptr_t)frames) | ((uintptr_t)masks)) & 3) == 0) opt |= kVcWords;      // launch_vg_mixed's rule (the same for both formats), per position
+  constexpr bool SEL = true;
+  constexpr long bg_stride = 0;
+  [[maybe_unused]] const int* const slot_of = nullptr;
+#define BSX_VT_OWN_LDS
+#define BSX_VT_TILE tile_
+#define BSX_VT_POS 0l                                                /* the position's own bases: index 0 of each */
+#define BSX_VT_DESC(fl) fl = d.flags
+  if (d.flags & kGeomYuyvIn) {
+    constexpr bool YIN = true;
+    if (c.direct) {
+      constexpr bool DIRECT = true;
+#include "vcam_tile.inc"
+    } else {
+      constexpr bool DIRECT = false;
+#include "vcam_tile.inc"
+    }
+  } else {
+    constexpr bool YIN = false;
+    if (c.direct) {
+      constexpr bool DIRECT = true;
+#include "vcam_tile.inc"
+    } else {
+      constexpr bool DIRECT = false;
+#include "vcam_tile.inc"
+    }
+  }
+#undef BSX_VT_OWN_LDS
+#undef BSX_VT_TILE
+#undef BSX_VT_POS
+#undef BSX_VT_DESC
+}
+}  // namespace
+
+hipError_t launch_prep_geoms_fmt(const GeomClass* classes, const GeomDesc* desc, const GeomSpans& spans, float* input, uint32_t* input_u8, int inW, int inH,
+                                 BilateralParams bp, int n, hipStream_t s) {
+  if ((!input && !input_u8) || n <= 0) return hipErrorInvalidValue;
+  const int ntx = (inW + 31) / 32, nty = (inH + 31) / 32, TW = (inW + ntx - 1) / ntx, TH = (inH + nty - 1) / nty;      // launch_prep_fused's tiles
+  if ((unsigned long long)ntx * nty * (unsigned long long)n >= (1ull << 31)) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)(ntx * nty) * (unsigned)n);
+#define BSX_PG(O) prep_geoms_fmt_k<O><<<grid, kThreads, 0, s>>>(classes, desc, spans, input, input_u8, inW, inH, bp, TW, TH, ntx, nty, xcd_frames(n))
+  if (input && input_u8) BSX_PG(3); else if (input_u8) BSX_PG(2); else BSX_PG(1);
+#undef BSX_PG
+  return hipGetLastError();
+}
+
+hipError_t launch_mask_blend_geoms_fmt(const GeomClass* classes, const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const GeomSpans& outside,
+                                       const uint8_t* ofinal, int outW, int outH, uint8_t* tile_class, int n, hipStream_t s, int flags) {
+  flags &= 1 | 8;
+  if (n <= 0 || tiles.wg[kMaxGeoms] <= 0) return hipErrorInvalidValue;
+  if (outside.wg[kMaxGeoms] > 0) outside_roi_geoms_fmt_k<><<<dim3((unsigned)outside.wg[kMaxGeoms]), kThreads, 0, s>>>(classes, desc, outside, flags);
+  if (tile_class) tile_class_geoms_k<<<dim3((unsigned)n), kThreads, 0, s>>>(classes, desc, tiles, ofinal, outW, outH, tile_class);
+  flags |= tile_debug_bits() & 128;
+  mask_tile_geoms_fmt_k<><<<dim3((unsigned)tiles.wg[kMaxGeoms]), kThreads, 0, s>>>(classes, desc, tiles, xcd_mask, ofinal, outW, outH, tile_class, flags);
+  return hipGetLastError();
+}
+
+hipError_t launch_vcam_geoms_fmt(const GeomClass* classes, const VgClass* vg, const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const uint8_t* ofinal,
+                                 int outW, int outH, uint8_t* tile_class, int out_w, int out_h, int n, hipStream_t s, unsigned flags) {
+  if (n <= 0 || tiles.wg[kMaxGeoms] <= 0 || out_w <= 0 || out_h <= 0 || (flags & ~1u) || ((flags & 1) && (out_w & 1))) return hipErrorInvalidValue;
+  const int ntx = (out_w + kVW - 1) / kVW, nty = (out_h + kVH - 1) / kVH;
+  if ((unsigned long long)ntx * nty * (unsigned long long)n >= (1ull << 31)) return hipErrorInvalidValue;
+  if (tile_class) tile_class_geoms_k<<<dim3((unsigned)n), kThreads, 0, s>>>(classes, desc, tiles, ofinal, outW, outH, tile_class);
+  mask_geoms_k<><<<dim3((unsigned)tiles.wg[kMaxGeoms]), kThreads, 0, s>>>(classes, desc, tiles, xcd_mask, ofinal, outW, outH, tile_class);      // (reads no frame)
+  const bool owords = (flags & 1) || out_w % 4 == 0;                   // (every d_out is 4-byte aligned: checked by the caller)
+  const int opt = (int)(flags & 1u) | (owords ? kVcOutWords : 0);
+  vg_geoms_fmt_k<><<<dim3((unsigned)(ntx * nty) * (unsigned)n), kThreads, 0, s>>>(vg, desc, tiles, ntx * nty, ntx, opt);
+  return hipGetLastError();
+}
+
 }  // namespace bsx

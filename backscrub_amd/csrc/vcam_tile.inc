@@ -9,7 +9,10 @@
 // MixDesc table that travels in `bg`), its mask is slot slot_of[n]'s (NULL: slot n); all of it is workgroup-uniform, so the tile's footprint below is the
 // workgroup's own.  Filter off: the composite is the frame (vcam_px / vcam_group with `off`); a background that is not 4-byte aligned takes the byte form for its
 // stream alone.
+// BSX_VT_OWN_LDS (vg_geoms_fmt_k, which includes the body once per frame format): the includer declares s_px itself, one staging area for all of its inclusions.
+#ifndef BSX_VT_OWN_LDS
   __shared__ uint32_t s_px[DIRECT ? 1 : kVLdsWords];
+#endif
   const int tid = threadIdx.x, ty = (int)(BSX_VT_TILE) / ntx, tx = (int)(BSX_VT_TILE) - ty * ntx;
   const long n = BSX_VT_POS;
   const int dw = tab.dw, dh = tab.dh;

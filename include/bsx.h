@@ -207,6 +207,10 @@ BSX_API int bsx_step_batch_streams(bsx_ctx* ctx, const int* ids, const uint8_t* 
 /* BSX_STREAM_FILTER_OFF: the reference with its filter switched off ('s' key, app/deepseg.cc:639-664, 782-783): the composite IS the camera frame (then
  * flipped / packed as set); the mask pipeline still runs, so the stream's temporal state and persistent mask advance exactly as with the filter on. */
 #define BSX_STREAM_FILTER_OFF 32u
+/* BSX_STREAM_YUYV_IN: THIS item's frame is the camera's raw YUYV 4:2:2 ([height_g][width_g][2] bytes Y0 U Y1 V) — BSX_STEP_YUYV_IN as a property of one position.
+ * Taken only in items[i].setting.flags of bsx_step_batch_geoms and bsx_step_batch_vcam_geoms, whose positions each bring their own frame pointer; the mixed steps,
+ * whose frames are one packed array with one layout, keep the batch flag and refuse this bit. */
+#define BSX_STREAM_YUYV_IN 64u
 typedef struct bsx_stream_setting {
   const uint8_t* d_bg;  /* [height][width][3] BGR on the context's device, 4-byte aligned; any number of streams may point at the same image */
   unsigned flags;       /* BSX_STEP_FLIP_H | BSX_STEP_FLIP_V | BSX_STEP_BGBLUR(k) | BSX_STREAM_FILTER_OFF */
@@ -265,20 +269,29 @@ BSX_API int bsx_get_geom_info(const bsx_ctx* ctx, int g, bsx_geom_info* out);
  * pass of the network, one tile-class and one tile launch (and at most one launch for the strips outside the ROIs), whatever the number of classes.
  *   - ids: required (the id decides the class): n distinct ids in any order, classes may interleave; rules, staging ring and refusal texts of bsx_step_batch_streams;
  *   - items[0..n): host memory, read before the call returns; entry i belongs to stream ids[i].  d_frame / d_out / setting.d_bg have the capture size of THAT stream's
- *     class; setting.flags: BSX_STEP_FLIP_H | BSX_STEP_FLIP_V | BSX_STREAM_FILTER_OFF;
- *   - flags (batch-wide, the buffer layouts): BSX_STEP_YUYV | BSX_STEP_NO_MASK;
+ *     class; setting.flags: BSX_STEP_FLIP_H | BSX_STEP_FLIP_V | BSX_STREAM_FILTER_OFF | BSX_STREAM_YUYV_IN;
+ *   - the pixel format belongs to the item: with BSX_STREAM_YUYV_IN items[i].d_frame is that camera's raw YUYV 4:2:2, [height_g][width_g][2] bytes Y0 U Y1 V, and
+ *     cv::COLOR_YUV2BGR_YUYV (app/deepseg.cc:553, :725) is folded into the kernels that read it — no BGR frame exists; without the bit the frame is BGR.  Any mix of
+ *     the two formats in one call, with every other setting bit and batch flag.  A call with no YUYV item launches exactly the kernels it launched before the bit
+ *     existed; one YUYV item switches the call's prep, tile and outside-ROI launches to forms that read the format per position (still one launch each).  A
+ *     filter-off YUYV item's composite is its frame converted, then flipped and packed as set, inside the ROI and on the strips outside it;
+ *   - flags (batch-wide, the output layout and the mask store): BSX_STEP_YUYV | BSX_STEP_NO_MASK;
  *   - result, per stream: composite, persistent mask and ofinal are bit-identical to bsx_step_batch_mixed of that one stream in a one-geometry context of its size
- *     with the same setting and flags.  Other streams' state is untouched;
+ *     with the same setting and flags (BSX_STEP_YUYV_IN there for a YUYV item) — and so to this call with that item's frame first converted by bsx_yuyv_to_bgr.
+ *     Other streams' state is untouched;
  *   - works on every context, also one made by bsx_new (then it is the mixed step with per-position pointers instead of packed arrays);
  *   - n == 0: returns 0 and enqueues nothing;
  *   - BSX_EINVAL before anything is enqueued, with a bsx_last_error text naming the position and value, for: the ids errors of bsx_step_batch_streams; items NULL; a
- *     NULL or not 4-byte aligned d_frame, d_out, or d_bg that is read; a flag bit outside the sets above (BSX_STEP_BGBLUR in a setting and BSX_STEP_YUYV_IN are not
- *     taken); an odd class width with YUYV out; an output overlapping any frame, background or other output of the call; a pending pipelined composite; an onmask
- *     callback; a stream whose class is off the fused tile route (possible only in a one-class context).  A refused call changes no state. */
+ *     NULL or not 4-byte aligned d_frame, d_out, or d_bg that is read; a flag bit outside the sets above (BSX_STEP_BGBLUR in a setting is not taken, and neither is
+ *     the batch flag BSX_STEP_YUYV_IN: the format is the item's); an odd class width with YUYV out; an output overlapping any frame (over its real extent: W*H*2
+ *     bytes for a YUYV item), background or other output of the call; a pending pipelined composite; an onmask callback; a stream whose class is off the fused tile
+ *     route (possible only in a one-class context); a YUYV item whose class has no fused YUYV prep — a down-scale table that is not INTER_LINEAR proper (capture
+ *     ROI equal to the model ROI: a copy; exactly twice it: the 2x2 area mean), an odd width or ROI column.  The text names items[i], the stream, the class size and
+ *     the table; the caller converts that stream with bsx_yuyv_to_bgr and passes BGR (the library has no conversion fallback here).  A refused call changes no state. */
 typedef struct bsx_geom_item {
-  const uint8_t* d_frame;       /* [height_g][width_g][3] BGR of the stream's class, 4-byte aligned */
+  const uint8_t* d_frame;       /* [height_g][width_g][3] BGR of the stream's class, or [height_g][width_g][2] YUYV with BSX_STREAM_YUYV_IN; 4-byte aligned */
   uint8_t* d_out;               /* [height_g][width_g][3], or [..][2] with BSX_STEP_YUYV, 4-byte aligned */
-  bsx_stream_setting setting;   /* d_bg at the capture size of that class; BSX_STEP_FLIP_H | BSX_STEP_FLIP_V | BSX_STREAM_FILTER_OFF */
+  bsx_stream_setting setting;   /* d_bg at the capture size of that class; BSX_STEP_FLIP_H | BSX_STEP_FLIP_V | BSX_STREAM_FILTER_OFF | BSX_STREAM_YUYV_IN */
 } bsx_geom_item;
 BSX_API int bsx_step_batch_geoms(bsx_ctx* ctx, const int* ids, const bsx_geom_item* items, int n, void* stream, unsigned flags);
 
@@ -288,7 +301,8 @@ BSX_API int bsx_step_batch_geoms(bsx_ctx* ctx, const int* ids, const bsx_geom_it
  * no capture-size composite, no full-size resized image, no caller-owned scratch, no host synchronisation.
  *   - ids, items: the rules of bsx_step_batch_geoms (required ids, any order, classes may interleave, the same staging ring).  items[i].d_frame and
  *     items[i].setting.d_bg have the capture size of the class of ids[i]; items[i].d_out is [out_h][out_w][3], or [out_h][out_w][2] with BSX_STEP_YUYV — the same
- *     size for every position; setting.flags: BSX_STEP_FLIP_H | BSX_STEP_FLIP_V | BSX_STREAM_FILTER_OFF;
+ *     size for every position; setting.flags: BSX_STEP_FLIP_H | BSX_STEP_FLIP_V | BSX_STREAM_FILTER_OFF | BSX_STREAM_YUYV_IN (that item's d_frame is YUYV 4:2:2,
+ *     [height_g][width_g][2]: the rules of bsx_step_batch_geoms; the resize pass converts the taps it reads, the masks-only tile launch reads no frame);
  *   - flags (batch-wide): BSX_STEP_YUYV only;
  *   - result, per stream: the output is byte-identical to bsx_resize_bgr(C, W_g, H_g -> out_w, out_h) [then bsx_bgr_to_yuyv], C being the BGR composite
  *     bsx_step_batch_geoms writes for the same item, its flip included — blend -> flip -> resize -> pack, the order of bsx_step_batch_vcam (an exact 2x down-scale is
@@ -298,10 +312,11 @@ BSX_API int bsx_step_batch_geoms(bsx_ctx* ctx, const int* ids, const bsx_geom_it
  *   - works on every context, also one made by bsx_new (then it is bsx_step_batch_vcam_mixed with per-position pointers);
  *   - n == 0: returns 0 and enqueues nothing;
  *   - BSX_EINVAL before anything is enqueued, with a bsx_last_error text naming the position and value, for: the ids errors of bsx_step_batch_streams; items NULL;
- *     out_w or out_h <= 0; BSX_STEP_NO_MASK (it has no vcam form), BSX_STEP_YUYV_IN and any other batch flag bit; a blur size or a foreign bit in a setting; a NULL
- *     or not 4-byte aligned d_frame, d_out, or d_bg that is read; an odd out_w with BSX_STEP_YUYV; an output (out_w x out_h) overlapping any frame, background or
- *     other output of the call; a pending pipelined composite; an onmask callback; a stream whose class is off the fused tile route (possible only in a one-class
- *     context, which bsx_step_batch_vcam_mixed takes).  A refused call changes no state.  BSX_EDEVICE for a batch of 2^31 workgroups or more. */
+ *     out_w or out_h <= 0; BSX_STEP_NO_MASK (it has no vcam form), BSX_STEP_YUYV_IN (the format is the item's) and any other batch flag bit; a blur size or a
+ *     foreign bit in a setting; a NULL or not 4-byte aligned d_frame, d_out, or d_bg that is read; an odd out_w with BSX_STEP_YUYV; an output (out_w x out_h)
+ *     overlapping any frame (W*H*2 bytes for a YUYV item), background or other output of the call; a pending pipelined composite; an onmask callback; a stream whose
+ *     class is off the fused tile route (possible only in a one-class context, which bsx_step_batch_vcam_mixed takes); a YUYV item whose class has no fused YUYV
+ *     prep (as bsx_step_batch_geoms).  A refused call changes no state.  BSX_EDEVICE for a batch of 2^31 workgroups or more. */
 BSX_API int bsx_step_batch_vcam_geoms(bsx_ctx* ctx, const int* ids, const bsx_geom_item* items, int n, int out_w, int out_h, void* stream, unsigned flags);
 
 /* Reset the temporal state of the listed streams only (ofinal → 0, persistent mask → 255, as bsx_reset does for all) — a slot reused for a new camera.  The
