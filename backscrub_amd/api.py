@@ -52,6 +52,10 @@ class _ResizeItem(C.Structure):             # bsx.h bsx_resize_item
     _fields_ = [("d_src", C.c_void_p), ("sw", C.c_int), ("sh", C.c_int), ("d_dst", C.c_void_p)]
 
 
+class _BlurItem(C.Structure):               # bsx.h bsx_blur_item
+    _fields_ = [("d_src", C.c_void_p), ("d_dst", C.c_void_p), ("w", C.c_int), ("h", C.c_int), ("ksize", C.c_int), ("flags", C.c_uint)]
+
+
 class _Geometry(C.Structure):               # bsx.h bsx_geometry
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("n_streams", C.c_int)]
 
@@ -135,6 +139,7 @@ SYMBOLS = [
     ("bsx_live_get_output_mask", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     ("bsx_live_timings", C.c_int, [C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     ("bsx_gaussian_blur_bgr", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    ("bsx_gaussian_blur_bgr_batch", C.c_int, [C.c_void_p, C.POINTER(_BlurItem), C.c_int, C.c_void_p]),
     ("bsx_debug_gauss_coeffs", C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("bsx_flip_bgr", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("bsx_debug_buffer", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
@@ -660,6 +665,48 @@ class MaskGen:
             raise BsxError("out must be a contiguous tensor shaped like the input")
         _check(lib().bsx_gaussian_blur_bgr(self.h, C.c_void_p(bgr.data_ptr()), C.c_void_p(out.data_ptr()), w, h, n, int(ksize), _stream_ptr()),
                self.h, "bsx_gaussian_blur_bgr")
+        return out
+
+    def gaussian_blur_batch(self, srcs, ksizes, out=None):
+        """cv::GaussianBlur of n images, each of its OWN size, blur size and pixel format, in one launch (bsx_gaussian_blur_bgr_batch; the integers of
+        gaussian_blur, after yuyv_to_bgr for a YUYV image).  srcs: a sequence of contiguous cuda uint8 tensors on the context's device, [h,w,3] (BGR) or [h,w,2]
+        (the camera's raw YUYV 4:2:2); ksizes: one odd int of 1..31 for all, or one per image (1 = the image itself, converted); out: None (new tensors) or a
+        sequence of contiguous [h_i,w_i,3] tensors.  Returns the list of outputs — what a StreamSetting's bg takes."""
+        torch = _torch()
+        srcs = list(srcs)
+        n = len(srcs)
+        if n > self.n_streams:
+            raise BsxError("%d images for a context of %d streams" % (n, self.n_streams))
+        ks = [int(ksizes)] * n if isinstance(ksizes, (int, np.integer)) else [int(k) for k in ksizes]
+        if len(ks) != n:
+            raise BsxError("%d ksizes for %d images" % (len(ks), n))
+        for i, k in enumerate(ks):
+            if k < 1 or k > 31 or not (k & 1):
+                raise BsxError("ksizes[%d] = %d is not an odd number of 1..31" % (i, k))
+        for i, t in enumerate(srcs):
+            ok = (isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.dim() == 3 and t.shape[2] in (2, 3) and t.shape[0] > 0 and t.shape[1] > 0
+                  and t.is_contiguous())
+            if not ok:
+                raise BsxError("srcs[%d] must be a contiguous uint8 tensor [h,w,3] (BGR) or [h,w,2] (YUYV)" % i)
+        if out is not None:
+            out = list(out)
+            if len(out) != n:
+                raise BsxError("%d outputs for %d images" % (len(out), n))
+            for i, (o, t) in enumerate(zip(out, srcs)):
+                ok = isinstance(o, torch.Tensor) and o.dtype == torch.uint8 and tuple(o.shape) == (int(t.shape[0]), int(t.shape[1]), 3) and o.is_contiguous()
+                if not ok:
+                    raise BsxError("out[%d] must be a contiguous uint8 tensor [%d,%d,3]" % (i, int(t.shape[0]), int(t.shape[1])))
+        for what, ts in (("srcs", srcs), ("out", out or [])):
+            for i, t in enumerate(ts):
+                if not t.is_cuda or t.device.index != self.device:
+                    raise BsxError("%s[%d] is on %s, not on the context's cuda:%d" % (what, i, t.device, self.device))
+        if out is None:
+            out = [torch.empty((int(t.shape[0]), int(t.shape[1]), 3), dtype=torch.uint8, device="cuda:%d" % self.device) for t in srcs]
+        items = (_BlurItem * max(n, 1))()
+        for i, (t, o) in enumerate(zip(srcs, out)):
+            items[i].d_src, items[i].d_dst, items[i].w, items[i].h = t.data_ptr(), o.data_ptr(), int(t.shape[1]), int(t.shape[0])
+            items[i].ksize, items[i].flags = ks[i], BSX_STREAM_YUYV_IN if t.shape[2] == 2 else 0
+        _check(lib().bsx_gaussian_blur_bgr_batch(self.h, items, n, _stream_ptr()), self.h, "bsx_gaussian_blur_bgr_batch")
         return out
 
     def yuyv_to_bgr(self, yuyv):

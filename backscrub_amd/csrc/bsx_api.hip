@@ -188,6 +188,11 @@ struct bsx_ctx {
   // to the device entry in one hipMemcpyAsync.  Allocated on the first batch call.
   ResizeBatchDesc* h_rsz = nullptr;         // pinned [kIdRing][n_streams]
   ResizeBatchDesc* d_rsz = nullptr;         // device, likewise
+  // bsx_gaussian_blur_bgr_batch: per ring entry (the same entries and events again) the call's n_streams BlurDesc (kernels.hpp), ordered by image size, built in the
+  // pinned entry, copied to the device entry in one hipMemcpyAsync; d_blur_coef: the coefficient records of every (ksize, staging path), uploaded by the first call.
+  BlurDesc* h_blur = nullptr;               // pinned [kIdRing][n_streams]
+  BlurDesc* d_blur = nullptr;               // device, likewise
+  GaussCoef* d_blur_coef = nullptr;         // device [blur_coef_table_bytes()]
   struct Span { uintptr_t begin, end; int item; bool dst; };
   std::vector<Span> rsz_spans;              // host scratch of the overlap check: the call's sources and destinations, sorted by address
   // Geometry classes (bsx_new_geoms): class 0 IS the context's own geometry — width, height, roi, in_roi, both tables and the first bytes of d_masks above — so every
@@ -1078,6 +1083,84 @@ int resize_batch_stage(bsx_ctx* c, const bsx_resize_item* items, int n, int dw, 
   return BSX_OK;
 }
 
+// ---- bsx_gaussian_blur_bgr_batch: n images of their own sizes, blur sizes and pixel formats in ONE launch -----------------------------------------------------------
+// Host-side validation of items[0..n): nothing is enqueued before it passes.  Leaves the size class of every item in c->geo_ids (the distinct (w, h) pairs numbered
+// in the order of their first item) and the ragged grid in *spans: per class its positions and its 64 x 16 tiles.
+int blur_batch_check(bsx_ctx* c, const char* fn, const bsx_blur_item* items, int n, GeomSpans* spans, BlurTileCols* cols) {
+  if (n < 0) return refuse(c, fn, "n = %d is negative", n);
+  if (n > c->n_streams) return refuse(c, fn, "n = %d exceeds the context's %d streams", n, c->n_streams);
+  if (n == 0) return BSX_OK;
+  if (!items) return refuse(c, fn, "items is NULL");
+  std::vector<bsx_ctx::Span>& sp = c->rsz_spans;
+  sp.clear();
+  c->geo_ids.resize((size_t)n);
+  int cw[kMaxGeoms], ch[kMaxGeoms], count[kMaxGeoms] = {0}, G = 0;
+  for (int i = 0; i < n; i++) {
+    const bsx_blur_item& it = items[i];
+    if (it.w <= 0 || it.h <= 0) return refuse(c, fn, "items[%d]: size %d x %d is not positive", i, it.w, it.h);
+    if (it.ksize < 1 || it.ksize > 31 || !(it.ksize & 1)) return refuse(c, fn, "items[%d]: ksize %d is not an odd number of 1 .. 31", i, it.ksize);
+    if (!it.d_src) return refuse(c, fn, "items[%d]: d_src is NULL", i);
+    if (!it.d_dst) return refuse(c, fn, "items[%d]: d_dst is NULL", i);
+    if (it.flags & ~BSX_STREAM_YUYV_IN) return refuse(c, fn, "items[%d]: flags 0x%x has bits outside yuyv-in (0x%x)", i, it.flags, BSX_STREAM_YUYV_IN);
+    const bool yin = (it.flags & BSX_STREAM_YUYV_IN) != 0;
+    if (yin && (it.w & 1)) return refuse(c, fn, "items[%d]: a YUYV source needs an even width (w = %d)", i, it.w);
+    if (yin && ((uintptr_t)it.d_src & 3)) return refuse(c, fn, "items[%d]: YUYV d_src %p is not 4-byte aligned", i, (const void*)it.d_src);
+    const size_t px = (size_t)it.w * (size_t)it.h;
+    if (px * 3 > 0x7fffffffu) return refuse(c, fn, "items[%d]: size %d x %d is beyond the kernel's 32-bit offsets (w * h * 3 < 2^31)", i, it.w, it.h);
+    int g = 0;
+    while (g < G && (cw[g] != it.w || ch[g] != it.h)) g++;
+    if (g == G) {
+      if (G == kMaxGeoms) return refuse(c, fn, "items[%d]: %d x %d is distinct size %d of the call (at most %d)", i, it.w, it.h, G + 1, BSX_MAX_GEOMS);
+      cw[G] = it.w; ch[G] = it.h; G++;
+    }
+    c->geo_ids[(size_t)i] = g; count[g]++;
+    sp.push_back({(uintptr_t)it.d_src, (uintptr_t)it.d_src + px * (yin ? 2 : 3), i, false});      // the source's real extent
+    sp.push_back({(uintptr_t)it.d_dst, (uintptr_t)it.d_dst + px * 3, i, true});
+  }
+  const bsx_ctx::Span* d = nullptr;
+  const bsx_ctx::Span* o = nullptr;
+  if (spans_overlap(sp, &d, &o))
+    return refuse(c, fn, "items[%d]: d_dst %p overlaps the %s of items[%d] (%p)", d->item, (const void*)d->begin, o->dst ? "destination" : "source", o->item,
+                  (const void*)o->begin);
+  *spans = GeomSpans{};
+  *cols = BlurTileCols{};
+  for (int g = 0; g < kMaxGeoms; g++) {
+    const long per = g < G ? blur_tiles(cw[g], ch[g]) : 0, cnt = g < G ? count[g] : 0;
+    if ((long)spans->wg[g] + cnt * per >= (1l << 31)) { c->last_error = std::string("error: ") + fn + ": the batch needs more than 2^31 workgroups\n"; return BSX_EDEVICE; }
+    spans->pos[g + 1] = spans->pos[g] + (int)cnt;
+    spans->wg[g + 1] = spans->wg[g] + (int)(cnt * per);
+    spans->per[g] = (int)per;
+    cols->ntx[g] = g < G ? blur_tile_cols(cw[g]) : 0;
+  }
+  return BSX_OK;
+}
+// items[0..n) as BlurDesc, ordered by size class (a counting sort: stable, so a class keeps the caller's order), into ring entry k (pinned), one copy to the device
+// entry on s; the coefficient table on the first call
+int blur_batch_stage(bsx_ctx* c, const bsx_blur_item* items, int n, const GeomSpans& spans, hipStream_t s, int k, const BlurDesc** d_desc) {
+  const size_t N = (size_t)c->n_streams;
+  if (!c->h_blur) BSX_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_blur), bsx_ctx::kIdRing * N * sizeof(BlurDesc), hipHostMallocDefault));
+  if (!c->d_blur) BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_blur), bsx_ctx::kIdRing * N * sizeof(BlurDesc)));
+  if (!c->d_blur_coef) {
+    std::vector<uint8_t> tab(blur_coef_table_bytes(), 0);
+    blur_coef_table(reinterpret_cast<GaussCoef*>(tab.data()));
+    GaussCoef* dev = nullptr;
+    BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&dev), tab.size()));
+    const hipError_t e = hipMemcpy(dev, tab.data(), tab.size(), hipMemcpyHostToDevice);      // (once per context: complete before the first launch on any stream)
+    if (e != hipSuccess) { (void)hipFree(dev); BSX_HIP(c, e); }
+    c->d_blur_coef = dev;
+  }
+  int next[kMaxGeoms];
+  for (int g = 0; g < kMaxGeoms; g++) next[g] = spans.pos[g];
+  BlurDesc* hd = c->h_blur + (size_t)k * N;
+  for (int i = 0; i < n; i++) {
+    const bsx_blur_item& it = items[i];
+    hd[next[c->geo_ids[(size_t)i]]++] = BlurDesc{it.d_src, it.d_dst, it.w, it.h, it.ksize, it.flags & kGeomYuyvIn};
+  }
+  BSX_HIP(c, hipMemcpyAsync(c->d_blur + (size_t)k * N, hd, (size_t)n * sizeof(BlurDesc), hipMemcpyHostToDevice, s));
+  *d_desc = c->d_blur + (size_t)k * N;
+  return BSX_OK;
+}
+
 // ---- bsx_step_batch_geoms: streams of any mix of geometry classes in ONE prep launch, ONE network pass, ONE tile-class and ONE tile launch ----------------------
 // Checked on the host (ids, then every position against the class of its id, then the overlaps), then: the positions ordered by class, their ids and descriptors
 // through the staging ring, the per-class spans of the ragged grids by value in the kernel arguments.
@@ -1540,6 +1623,9 @@ void bsx_delete(bsx_ctx* c) {
   if (c->h_mix) (void)hipHostFree(c->h_mix);
   if (c->d_rsz) (void)hipFree(c->d_rsz);
   if (c->h_rsz) (void)hipHostFree(c->h_rsz);
+  if (c->d_blur) (void)hipFree(c->d_blur);
+  if (c->h_blur) (void)hipHostFree(c->h_blur);
+  if (c->d_blur_coef) (void)hipFree(c->d_blur_coef);
   for (size_t g = 1; g < c->geoms.size(); g++) { if (c->geoms[g].tab_down.mem) (void)hipFree(c->geoms[g].tab_down.mem); if (c->geoms[g].tab_up.mem) (void)hipFree(c->geoms[g].tab_up.mem); }
   if (c->d_geom_classes) (void)hipFree(c->d_geom_classes);
   if (c->d_geom_tile_class) (void)hipFree(c->d_geom_tile_class);
@@ -1824,6 +1910,27 @@ int bsx_gaussian_blur_bgr(bsx_ctx* c, const uint8_t* d_src, uint8_t* d_dst, int 
   DeviceGuard guard(c->device);
   BSX_HIP(c, launch_gauss_blur(d_src, d_dst, w, h, ksize, n, pick(c, stream)));
   return BSX_OK;
+}
+
+// n images, each of its own size, blur size and pixel format, blurred in ONE launch: checked on the host, the descriptors ordered by size through the staging ring,
+// the ragged grid's spans by value
+int bsx_gaussian_blur_bgr_batch(bsx_ctx* c, const bsx_blur_item* items, int n, void* stream) {
+  if (!c) return BSX_EINVAL;
+  GeomSpans spans{};
+  BlurTileCols cols{};
+  if (const int rc = blur_batch_check(c, "bsx_gaussian_blur_bgr_batch", items, n, &spans, &cols)) return rc;
+  if (n == 0) return BSX_OK;
+  DeviceGuard guard(c->device);
+  hipStream_t s = pick(c, stream);
+  int entry = 0;
+  if (const int rc = ring_acquire(c, &entry)) return rc;
+  const BlurDesc* d_desc = nullptr;
+  int rc = blur_batch_stage(c, items, n, spans, s, entry, &d_desc);
+  if (!rc) {
+    const hipError_t e = launch_blur_batch(d_desc, c->d_blur_coef, spans, cols, s);
+    if (e != hipSuccess) { report(c, c->ondebug, c->caller_ctx, "error: HIP %s while blurring a batch\n", hipGetErrorString(e)); rc = BSX_EDEVICE; }
+  }
+  return ids_release(c, entry, s, rc);
 }
 
 int bsx_bgr_to_yuyv(bsx_ctx* c, const uint8_t* d_bgr, uint8_t* d_yuyv, int w, int h, int n, void* stream) {

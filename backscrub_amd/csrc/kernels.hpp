@@ -245,6 +245,20 @@ bool gauss_coeff_words(int ksize, int shift, uint32_t* c4 /* [4][9] */, uint32_t
 // blur + alpha blend of the frames over their own blur (deepseg.cc:652-661 without -b), the blurred image never stored; fusable = 4-byte aligned images, w % 4 == 0
 bool gauss_blend_fusable(const uint8_t* frames, const uint8_t* masks, const uint8_t* out, int w, int ksize);
 hipError_t launch_gauss_blend(const uint8_t* frames, const uint8_t* masks, uint8_t* out, int w, int h, int ksize, int n, hipStream_t s, const int* slot_of = nullptr);
+// n blurs in ONE launch (bsx_gaussian_blur_bgr_batch): position i reads desc[i] (a DEVICE array ORDERED BY IMAGE SIZE, two 16-byte uniform loads per workgroup) —
+// its source (w x h BGR of any alignment, or with kGeomYuyvIn 4-byte aligned YUYV 4:2:2 of an even width), its destination (w x h BGR, any alignment: a 4-byte
+// aligned one with w % 4 == 0 is stored as dwords) and its blur size (odd, 1 .. 31; 1 = the image itself, converted for a YUYV source).  spans: the ragged grid —
+// per size class the first position, the first workgroup and the 64 x 16 tiles of one image (blur_tiles).  coef: the DEVICE copy of blur_coef_table's records.
+// The integers of launch_gauss_blur (after launch_yuyv_to_bgr for a YUYV source).
+struct alignas(16) BlurDesc { const uint8_t* src; uint8_t* dst; int w, h, ksize; unsigned flags; };
+static_assert(sizeof(BlurDesc) == 32, "two 16-byte uniform loads per workgroup");
+struct GaussCoef;
+size_t blur_coef_table_bytes();                                   // host: the size of the table, and its records (every odd ksize of 1 .. 31 x both staging paths)
+void blur_coef_table(GaussCoef* tab);
+inline long blur_tiles(int w, int h) { return (long)((w + 63) / 64) * (long)((h + 15) / 16); }
+struct BlurTileCols { int ntx[kMaxGeoms]; };                      // by value next to the spans: tiles per image row of class g (blur_tile_cols of its width)
+inline int blur_tile_cols(int w) { return (w + 63) / 64; }
+hipError_t launch_blur_batch(const BlurDesc* desc, const GaussCoef* coef, const GeomSpans& spans, const BlurTileCols& cols, hipStream_t s);
 // composite at the virtual camera's geometry: alpha blend → cv::flip (flags bits 1-2) → cv::resize to (tab.dw, tab.dh) → [YUYV pack (bit 0)] in one pass over
 // frames, background and the persistent masks (deepseg.cc:634-681).  `tab`: a linear table from the capture size (the 2x2 area mode expanded to one);
 // direct = !vcam_tile_fits(tab): every tap blended where it is read instead of the footprint staged in LDS.  yuyv_in: `frames` is YUYV 4:2:2

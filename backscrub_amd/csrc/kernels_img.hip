@@ -2104,4 +2104,212 @@ hipError_t launch_vcam_geoms_fmt(const GeomClass* classes, const VgClass* vg, co
   return hipGetLastError();
 }
 
+// ---- bsx_gaussian_blur_bgr_batch: n images, each of its own size, blur size and pixel format, in ONE launch ----------------------------------------------------------
+// gauss_blur_k's body with everything it takes from its kernel arguments read per position: a ragged grid of 64 x 16 tiles (GeomSpans: the positions ordered by image
+// size, per = tiles of one image), the position's BlurDesc by two uniform loads, its coefficient record from the context's device table by a uniform index — the
+// words stay in SGPRs, as gauss_blur_k's kernel arguments do.  Decided per workgroup, on scalars:
+//   * staging: the 4-pixel word path under gauss_blur_k's `xin` rule (rows dword aligned, the tile's source columns inside the image; sh = (-r) & 3), else the
+//     reflecting byte path (sh = 0) — the coefficient record follows (two records per blur size, blur_coef_index);
+//   * NT = ceil((ksize + 3 + sh) / 4): one of eight straight-line bodies (blur_passes<NT>), the way prep_geoms_k chooses its table mode;
+//   * output: whole dwords from the packed LDS tile (MODE 1's form) where w % 4 == 0 and dst is 4-byte aligned, else byte stores from the vertical pass (MODE 0's);
+//   * a YUYV position (kGeomYuyvIn) converts as it stages, yuyv_to_bgr_k's integers: on the word path a 4-pixel group is two whole macropixels (the planes start on
+//     a multiple of 4 columns), on the byte path pixel gx takes U and V from the macropixel of gx & ~1 after the reflection;
+//   * ksize 1 is the image itself (the conversion for a YUYV position): stored straight from the loaded pixels, no LDS.
+// A template of one instance launched by the file's last launcher for the reason given above mask_geoms_k.
+__host__ __device__ constexpr int blur_coef_index(int ksize, bool words) { return (ksize & ~1) | (words ? 1 : 0); }      // ksize odd, 1 .. 31: records 0 .. 31
+namespace {
+struct BlurDescRegs { const uint8_t* src; uint8_t* dst; int w, h, ksize; unsigned flags; };
+__device__ __forceinline__ BlurDescRegs blur_desc(const BlurDesc* __restrict__ desc, int n) {
+  const uint4* p = reinterpret_cast<const uint4*>(desc) + 2 * (size_t)n;
+  const uint4 a = p[0], b = p[1];
+  typedef __attribute__((address_space(1))) uint8_t* gp;
+  BlurDescRegs d;
+  d.src = (const uint8_t*)(gp)(((uint64_t)a.y << 32) | a.x);
+  d.dst = (uint8_t*)(gp)(((uint64_t)a.w << 32) | a.z);
+  d.w = (int)b.x; d.h = (int)b.y; d.ksize = (int)b.z; d.flags = b.w;
+  return d;
+}
+// pixel (gx, gy) of a position's image as B | G << 8 | R << 16: byte loads, any alignment (vcam_frame_px with the format as a run-time, workgroup-uniform bit)
+__device__ __forceinline__ uint32_t blur_src_px(const uint8_t* __restrict__ in, bool yin, int W, int gx, int gy) {
+  if (yin) {
+    const uint8_t* q = in + (unsigned)(gy * W + (gx & ~1)) * 2u;
+    return yuv_tap_to_bgr((uint32_t)q[(gx & 1) * 2] | ((uint32_t)q[1] << 8) | ((uint32_t)q[3] << 16));
+  }
+  const uint8_t* p = in + (unsigned)(gy * W + gx) * 3u;
+  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+}
+// gauss_blur_k's passes 2 and 3 for one NT, the coefficient words copied out of the record first (uniform address, constant offsets: scalar loads)
+template <int NT>
+__device__ __forceinline__ void blur_passes(uint8_t* s_src, uint16_t* s_h, const GaussCoef* __restrict__ gc, int SH, bool owords, uint8_t* __restrict__ out, int W, int H,
+                                            int x0, int y0) {
+  static_assert(NT >= 2 && NT <= 9, "tap words of the horizontal pass");
+  constexpr int NP = 2 * NT - 1;
+  uint32_t c4[4][NT], c2[2][NP];
+#pragma unroll
+  for (int j = 0; j < 4; j++)
+#pragma unroll
+    for (int t = 0; t < NT; t++) c4[j][t] = gc->c4[j][t];
+#pragma unroll
+  for (int h = 0; h < 2; h++)
+#pragma unroll
+    for (int t = 0; t < NP; t++) c2[h][t] = gc->c2[h][t];
+  __syncthreads();                                                    // the staged tile is complete (the coefficient loads above are in flight while the waves meet)
+  // horizontal pass: item = (plane, source row, group of 4 output columns)
+  for (int grp = threadIdx.x & 15, row = threadIdx.x >> 4, plane = 0; plane < 3;) {
+    const uint32_t* rowp = reinterpret_cast<const uint32_t*>(s_src + (plane * kGSH + row) * kGSrcStride) + grp;
+    uint32_t d[NT];
+#pragma unroll
+    for (int t = 0; t < NT; t++) d[t] = rowp[t];                           // stays inside the 96-byte row: 4 * (15 + NT) <= 96
+    uint32_t acc[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int t = 0; t < NT; t++) {
+#pragma unroll
+      for (int j = 0; j < 4; j++) acc[j] = __builtin_amdgcn_udot4(d[t], c4[j][t], acc[j], false);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) s_h[gh_col(plane, 4 * grp + j) + row] = (uint16_t)acc[j];
+    row += kGTH;
+    if (row >= SH) { row -= SH; plane++; }
+  }
+  __syncthreads();
+  // vertical pass: item = (plane, output column, pair of output rows)
+  for (int i = threadIdx.x; i < 3 * kGTW * (kGTH / 2); i += kThreads) {
+    const int m = i & (kGTH / 2 - 1), pc = i / (kGTH / 2), col = pc & (kGTW - 1), plane = pc / kGTW;
+    const uint32_t* colp = reinterpret_cast<const uint32_t*>(s_h + gh_col(plane, col)) + m;
+    uint32_t hd[NP];
+#pragma unroll
+    for (int t = 0; t < NP; t++) hd[t] = colp[t];                          // 2 (m + NP - 1) + 1 <= 47 < kGHStride
+    uint32_t a0 = 0, a1 = 0;
+#pragma unroll
+    for (int t = 0; t < NP; t++) {
+      a0 = __builtin_amdgcn_udot2(__builtin_bit_cast(us2v, hd[t]), __builtin_bit_cast(us2v, c2[0][t]), a0, false);
+      a1 = __builtin_amdgcn_udot2(__builtin_bit_cast(us2v, hd[t]), __builtin_bit_cast(us2v, c2[1][t]), a1, false);
+    }
+    const uint8_t v0 = (uint8_t)min((a0 + (1u << 15)) >> 16, 255u), v1 = (uint8_t)min((a1 + (1u << 15)) >> 16, 255u);
+    if (owords) {
+      s_src[(2 * m) * kGOStride + 3 * col + plane] = v0;
+      s_src[(2 * m + 1) * kGOStride + 3 * col + plane] = v1;
+    } else {
+      const int gx = x0 + col, gy = y0 + 2 * m;
+      if (gx < W) {
+        if (gy < H) out[(unsigned)(gy * W + gx) * 3u + plane] = v0;
+        if (gy + 1 < H) out[(unsigned)((gy + 1) * W + gx) * 3u + plane] = v1;
+      }
+    }
+  }
+}
+
+template <int = 0>
+__global__ __launch_bounds__(kThreads) void blur_batch_k(const BlurDesc* __restrict__ desc, const GaussCoef* __restrict__ coef, GeomSpans sp, BlurTileCols cols) {
+  __shared__ __attribute__((aligned(16))) uint8_t s_src[3 * kGSH * kGSrcStride];          // [plane][row][col]; whole-dword output: later the packed tile [row][kGOStride]
+  __shared__ __attribute__((aligned(16))) uint16_t s_h[3 * kGHPlane];                     // [plane][col][row], gh_col()
+  int g, w0, p0, p1, per;
+  geom_span(sp, (int)blockIdx.x, &g, &w0, &p0, &p1, &per);
+  const unsigned local = blockIdx.x - (unsigned)w0, pl = local / (unsigned)per, tile = local - pl * (unsigned)per;
+  const BlurDescRegs d = blur_desc(desc, p0 + (int)pl);
+  const int W = d.w, H = d.h, r = d.ksize >> 1;
+  const bool yin = (d.flags & kGeomYuyvIn) != 0;
+  const uint8_t* __restrict__ const in = d.src;
+  uint8_t* __restrict__ const out = d.dst;
+  // the class's tiles per image row travel with the spans (selected on SGPRs as geom_span selects, nothing loaded): the tile's coordinates do not wait for the
+  // descriptor's width
+  unsigned ntx = (unsigned)cols.ntx[0];
+#pragma unroll
+  for (int k = 1; k < kMaxGeoms; k++) if (g == k) ntx = (unsigned)cols.ntx[k];
+  const unsigned ty = tile / ntx, tx = tile - ty * ntx;
+  const int x0 = (int)tx * kGTW, y0 = (int)ty * kGTH;
+  if (r == 0) {                                                       // ksize 1: the (converted) pixels themselves
+    for (int i = threadIdx.x; i < kGTW * kGTH; i += kThreads) {
+      const int gx = x0 + (i & (kGTW - 1)), gy = y0 + i / kGTW;
+      if (gx < W && gy < H) {
+        const uint32_t px = blur_src_px(in, yin, W, gx, gy);
+        uint8_t* o = out + (unsigned)(gy * W + gx) * 3u;
+        o[0] = (uint8_t)px; o[1] = (uint8_t)(px >> 8); o[2] = (uint8_t)(px >> 16);
+      }
+    }
+    return;
+  }
+  const int SW = kGTW + 2 * r, SH = kGTH + 2 * r;                     // live part of the source tile
+  // 1. stage + de-interleave (reflected at the image border): gauss_blur_k's two paths, the choice and its sh made here
+  const bool rows4 = yin || (((W & 3) | (int)((uintptr_t)in & 3)) == 0);      // a YUYV image has an even width and a 4-byte aligned base (checked by the caller)
+  const int shw = (-r) & 3, Gw = (SW + shw + 3) >> 2;
+  const bool xin = rows4 && x0 - r - shw >= 0 && x0 - r - shw + 4 * Gw <= W;
+  const int sh = xin ? shw : 0;
+  if (xin) {                                                          // item = (row, group of 4 pixels) → one dword per plane
+    const int G = Gw;
+    int row = (int)threadIdx.x / G, grp = (int)threadIdx.x - row * G;
+    const int dr = kThreads / G, dc = kThreads - dr * G;
+    const unsigned xb = (unsigned)(x0 - r - sh);
+    while (row < SH) {
+      const int gy = reflect101_far(y0 - r + row, H);
+      uint32_t pb, pg, pr;
+      if (yin) {                                                      // two macropixels: Y0 U0 Y1 V0 | Y2 U1 Y3 V1
+        const uint32_t* p = reinterpret_cast<const uint32_t*>(in + ((unsigned)(gy * W) + xb + 4u * (unsigned)grp) * 2u);
+        const uint32_t q0 = p[0], q1 = p[1];
+        int bu0, gu0, ru0, bu1, gu1, ru1;
+        yuv_chroma((int)((q0 >> 8) & 255u) - 128, (int)(q0 >> 24) - 128, &bu0, &gu0, &ru0);
+        yuv_chroma((int)((q1 >> 8) & 255u) - 128, (int)(q1 >> 24) - 128, &bu1, &gu1, &ru1);
+        const int ya = yuv_luma(q0 & 255u), yb = yuv_luma((q0 >> 16) & 255u), yc = yuv_luma(q1 & 255u), yd = yuv_luma((q1 >> 16) & 255u);
+        pb = (sat_pk2_shr20(ya + bu0, yb + bu0) & 0xffffu) | (sat_pk2_shr20(yc + bu1, yd + bu1) << 16);
+        pg = (sat_pk2_shr20(ya + gu0, yb + gu0) & 0xffffu) | (sat_pk2_shr20(yc + gu1, yd + gu1) << 16);
+        pr = (sat_pk2_shr20(ya + ru0, yb + ru0) & 0xffffu) | (sat_pk2_shr20(yc + ru1, yd + ru1) << 16);
+      } else {
+        const uint32_t* p = reinterpret_cast<const uint32_t*>(in + ((unsigned)(gy * W) + xb + 4u * (unsigned)grp) * 3u);
+        const uint32_t d0 = p[0], d1 = p[1], d2 = p[2];               // B0 G0 R0 B1 | G1 R1 B2 G2 | R2 B3 G3 R3
+        pb = __builtin_amdgcn_perm(d2, __builtin_amdgcn_perm(d1, d0, 0x00060300u), 0x05020100u);
+        pg = __builtin_amdgcn_perm(d2, __builtin_amdgcn_perm(d1, d0, 0x00070401u), 0x06020100u);
+        pr = __builtin_amdgcn_perm(d2, __builtin_amdgcn_perm(d1, d0, 0x00000502u), 0x07040100u);
+      }
+      uint32_t* o = reinterpret_cast<uint32_t*>(s_src + row * kGSrcStride) + grp;
+      o[0] = pb; o[kGSH * kGSrcStride / 4] = pg; o[2 * kGSH * kGSrcStride / 4] = pr;
+      grp += dc; row += dr;
+      if (grp >= G) { grp -= G; row++; }
+    }
+  } else {
+    int row = (int)threadIdx.x / SW, col = (int)threadIdx.x - row * SW;
+    const int dr = kThreads / SW, dc = kThreads - dr * SW;
+    while (row < SH) {
+      const int gy = reflect101_far(y0 - r + row, H), gx = reflect101_far(x0 - r + col, W);
+      const uint32_t px = blur_src_px(in, yin, W, gx, gy);
+      s_src[(0 * kGSH + row) * kGSrcStride + col] = (uint8_t)px;
+      s_src[(1 * kGSH + row) * kGSrcStride + col] = (uint8_t)(px >> 8);
+      s_src[(2 * kGSH + row) * kGSrcStride + col] = (uint8_t)(px >> 16);
+      col += dc; row += dr;
+      if (col >= SW) { col -= SW; row++; }
+    }
+  }
+  // 2. + 3. the passes: NT = ceil((ksize + 3 + sh) / 4), a workgroup-uniform choice between straight-line bodies (each begins with the barrier behind the staging)
+  const bool owords = (((W & 3) | (int)((uintptr_t)out & 3)) == 0);
+  const GaussCoef* __restrict__ const gc = coef + blur_coef_index(d.ksize, xin);
+  switch ((d.ksize + sh + 6) >> 2) {
+#define BSX_BB(NT) case NT: blur_passes<NT>(s_src, s_h, gc, SH, owords, out, W, H, x0, y0); break;
+    BSX_BB(2) BSX_BB(3) BSX_BB(4) BSX_BB(5) BSX_BB(6) BSX_BB(7) BSX_BB(8) default: BSX_BB(9)
+#undef BSX_BB
+  }
+  if (owords) {                                                       // this lane's 4-pixel group of the packed tile: three whole dwords
+    __syncthreads();
+    const int orow = threadIdx.x >> 4, ogx = x0 + 4 * (threadIdx.x & 15), ogy = y0 + orow;
+    if (ogx < W && ogy < H) {
+      const uint32_t* bp = reinterpret_cast<const uint32_t*>(s_src + orow * kGOStride + 12 * (threadIdx.x & 15));
+      uint32_t* op = reinterpret_cast<uint32_t*>(out + (unsigned)(ogy * W + ogx) * 3u);
+      op[0] = bp[0]; op[1] = bp[1]; op[2] = bp[2];
+    }
+  }
+}
+}  // namespace
+
+// The device table bsx_gaussian_blur_bgr_batch uploads once: record blur_coef_index(ksize, words) for every odd ksize of 1 .. 31 and both staging paths.
+size_t blur_coef_table_bytes() { return (size_t)(2 * kGMaxR + 2) * sizeof(GaussCoef); }
+void blur_coef_table(GaussCoef* tab) {
+  for (int k = 1; k <= 2 * kGMaxR + 1; k += 2)
+    for (int words = 0; words < 2; words++) (void)gauss_coefficients(k, tab + blur_coef_index(k, words != 0), words ? (-(k / 2)) & 3 : 0);
+}
+
+hipError_t launch_blur_batch(const BlurDesc* desc, const GaussCoef* coef, const GeomSpans& spans, const BlurTileCols& cols, hipStream_t s) {
+  if (!desc || !coef || spans.wg[kMaxGeoms] <= 0) return hipErrorInvalidValue;
+  for (int g = 0; g < kMaxGeoms; g++) if (spans.per[g] > 0 && (cols.ntx[g] <= 0 || spans.per[g] % cols.ntx[g])) return hipErrorInvalidValue;
+  blur_batch_k<><<<dim3((unsigned)spans.wg[kMaxGeoms]), kThreads, 0, s>>>(desc, coef, spans, cols);
+  return hipGetLastError();
+}
+
 }  // namespace bsx

@@ -35,6 +35,7 @@
  *   bsx_flip_bgr           cv::flip of the output frame   app/deepseg.cc:667-673 (flipHorizontal / flipVertical)
  *   bsx_gaussian_blur_bgr  cv::GaussianBlur of the background app/deepseg.cc:415-431,652-658 (-p bgblur:<n>: blur the camera frame itself
  *                          (or the background image) and composite over it)
+ *   bsx_gaussian_blur_bgr_batch  cv::GaussianBlur of every camera's own frame, once per main-loop iteration  app/deepseg.cc:652-658
  *   bsx_background_*       load_background / grab_background + reader thread   app/background.cc:29-104,126-194
  *   bsx_background_grab_batch  grab_background() of every camera's own source, once per main-loop iteration   app/deepseg.cc:648-651
  *   bsx_live_*             class CalcMask (worker thread, double buffering)     app/deepseg.cc:159-286
@@ -248,6 +249,7 @@ BSX_API int bsx_step_batch_mixed(bsx_ctx* ctx, const int* ids, const uint8_t* d_
  *   - on a context of more than one class these work: bsx_step_batch_geoms, bsx_step_batch_vcam_geoms, bsx_reset, bsx_reset_streams, bsx_get_info (class 0's
  *     geometry, the total n_streams), bsx_geom_count / bsx_get_geom_info, bsx_masks_device, bsx_last_error, bsx_delete, bsx_plan_describe, bsx_debug_buffer (0-2 as always; 3 = the whole mask
  *     allocation), bsx_debug_tensor*, and everything that takes its own w, h (bsx_resize_bgr*, bsx_bgr_to_yuyv, bsx_yuyv_to_bgr, bsx_flip_bgr, bsx_gaussian_blur_bgr,
+ *     bsx_gaussian_blur_bgr_batch,
  *     bsx_background_*).  Every other entry point — the dense, by-id, mixed, vcam and pipelined steps, process, composite, profile, live, the debug stages and tile
  *     statistics — returns BSX_EINVAL ("context has N geometries"; bsx_live_new: NULL) and enqueues nothing. */
 #define BSX_MAX_GEOMS 8
@@ -407,6 +409,35 @@ BSX_API int bsx_flip_bgr(bsx_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int
  * OpenCV's 8-bit fixed-point coefficients; ksize odd, 1 <= ksize <= 31 (the reference's default strength is 25, app/deepseg.cc:429).
  * The "blur my own room" mode of the reference = this on the camera frames, then bsx_step_batch with bg_frame_stride = one frame. */
 BSX_API int bsx_gaussian_blur_bgr(bsx_ctx* ctx, const uint8_t* d_src, uint8_t* d_dst, int w, int h, int n, int ksize, void* stream);
+
+/* n blurs, each image of its own size, its own blur size and its own pixel format, in ONE kernel launch — "every camera's background is a blur of its own frame"
+ * (-p bgblur without -b, the reference's default, app/deepseg.cc:652-658) for a server whose cameras differ: the outputs are capture-size BGR images, what a
+ * bsx_stream_setting's d_bg points at, so a tick in blur mode is this call followed by bsx_step_batch_geoms / bsx_step_batch_vcam_geoms (the counterpart of
+ * bsx_background_grab_batch for animated backgrounds).
+ *   - d_dst of item i is byte-identical to bsx_gaussian_blur_bgr(d_src, d_dst, w, h, 1, ksize); with BSX_STREAM_YUYV_IN in its flags d_src is the camera's raw YUYV
+ *     4:2:2 ([h][w][2] bytes Y0 U Y1 V) and d_dst is identical to that call on the output of bsx_yuyv_to_bgr(d_src, ...) — converted as the blur reads it: no BGR
+ *     copy of the frame exists anywhere;
+ *   - ksize 1 is the frame itself (a copy of a BGR item, the conversion of a YUYV item), done in the same launch;
+ *   - the whole call is one launch, whatever the mix of sizes, blur sizes and formats; it takes at most BSX_MAX_GEOMS distinct (w, h) pairs (the grid is ragged: the
+ *     positions are ordered by size on the host, so one large image among many small ones launches no empty workgroups);
+ *   - items is a HOST array, read before the call returns; the descriptors reach the device through the staging ring of bsx_step_batch_streams (no host
+ *     synchronisation unless the caller runs a ring's length ahead of the GPU); the coefficient words of every blur size are uploaded once, by the first call;
+ *   - n <= n_streams of the context; n == 0 returns 0 and enqueues nothing; the same source may appear in several items (one frame at two blur sizes); works on
+ *     every context, a multi-class one included;
+ *   - BGR items take any alignment and any size (w % 4 != 0, images smaller than the blur radius), as bsx_gaussian_blur_bgr does, up to w * h * 3 < 2^31 bytes;
+ *   - BSX_EINVAL before anything is enqueued, with a bsx_last_error text naming items[i] and the offending value, for: n < 0 or n > n_streams; items NULL with
+ *     n > 0; a non-positive size (or one beyond 2^31 bytes); a ksize that is even, below 1 or above 31; a NULL d_src or d_dst; a flag bit other than
+ *     BSX_STREAM_YUYV_IN; a YUYV item with an odd w or a d_src that is not 4-byte aligned; a ninth distinct size; a d_dst that overlaps any source (its own
+ *     included; a YUYV source extends over w * h * 2 bytes) or another destination.  BSX_EDEVICE for a grid of 2^31 workgroups or more.  A refused call changes
+ *     nothing. */
+typedef struct bsx_blur_item {
+  const uint8_t* d_src;   /* [h][w][3] BGR, or with BSX_STREAM_YUYV_IN [h][w][2] YUYV 4:2:2 (Y0 U Y1 V) */
+  uint8_t* d_dst;         /* [h][w][3] BGR */
+  int w, h;
+  int ksize;              /* odd, 1..31 */
+  unsigned flags;         /* 0 | BSX_STREAM_YUYV_IN */
+} bsx_blur_item;
+BSX_API int bsx_gaussian_blur_bgr_batch(bsx_ctx* ctx, const bsx_blur_item* items, int n, void* stream);
 
 /* ---- background source (app/background.cc) ----
  * load_background(): a still image or an animation (GIF87a/89a, 8-bit non-interlaced PNG, binary PPM decoded in this library; other
