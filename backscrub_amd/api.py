@@ -743,6 +743,12 @@ class MaskGen:
         i = self.info
         return self._view(0, "float32", (self.n_streams, i["in_h"], i["in_w"], i["in_c"]))
 
+    def input_u8(self):
+        """torch u8 view [n_streams, in_h, in_w, 4] of the 8-bit network input the steps' prep writes (bytes R, G, B, 0 of each word), by POSITION in the last
+        call; BsxError where this context's stem reads the f32 form (input_tensor) instead"""
+        i = self.info
+        return self._view(4, "uint8", (self.n_streams, i["in_h"], i["in_w"], 4))
+
     def output_tensor(self):
         i = self.info
         return self._view(1, "float32", (self.n_streams, i["out_h"], i["out_w"], i["out_c"]))

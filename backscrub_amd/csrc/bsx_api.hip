@@ -1955,6 +1955,9 @@ int bsx_debug_buffer(bsx_ctx* c, int which, void** d_ptr, size_t* bytes) {
     case 1: *d_ptr = c->tensor_ptr(c->plan.output); *bytes = N * c->outW * c->outH * c->outC * 4; break;
     case 2: *d_ptr = c->d_ofinal; *bytes = N * c->outW * c->outH; break;
     case 3: *d_ptr = c->d_masks; *bytes = c->mask_bytes; break;
+    case 4:                                                       // what the step's prep writes where the stem has a byte path (in_u8); the f32 form stays unwritten there
+      if (!c->in_u8) return refuse(c, "bsx_debug_buffer", "which = 4: this context's stem reads the f32 network input, the 8-bit form is never written");
+      *d_ptr = c->d_net_in_u8; *bytes = N * c->inW * c->inH * sizeof(uint32_t); break;
     default: return BSX_EINVAL;
   }
   return BSX_OK;

@@ -483,7 +483,9 @@ BSX_API int bsx_live_timings(const bsx_live* live, long* waitns, long* loopns);
 
 /* ---- introspection used by the parity tests and the bench (stage-by-stage checks) ---- */
 /* Device pointer + element count of: 0 = model input tensor [n_streams][in_h][in_w][in_c] f32,
- * 1 = model output tensor f32, 2 = ofinal u8 [n_streams][out_h][out_w], 3 = masks u8. */
+ * 1 = model output tensor f32, 2 = ofinal u8 [n_streams][out_h][out_w], 3 = masks u8,
+ * 4 = the 8-bit network input the steps' prep writes, [n_streams][in_h][in_w] 32-bit words R | G<<8 | B<<16, indexed by POSITION in the call (a multi-geometry
+ *     call orders its positions by class, the caller's order kept within a class); BSX_EINVAL where the stem reads the f32 form (0) instead. */
 BSX_API int bsx_debug_buffer(bsx_ctx* ctx, int which, void** d_ptr, size_t* bytes);
 /* Run single stages on the current buffers (n streams): 0 = prep, 1 = infer, 2 = decode+IIR, 3 = upscale+blur, 4 = prep on raw YUYV 4:2:2 frames
  * (BSX_STEP_YUYV_IN's form of stage 0; BSX_EINVAL where the fused form does not apply). */
