@@ -246,7 +246,10 @@ static void lower_frame_program(const Graph& g, Plan* plan, const std::vector<St
   }
   // Weight staging slots.  stage[s] floats of step s are DMA'd to LDS while the PREVIOUS micro-op runs, so the slot must be
   // free from the first step of that previous micro-op (q) to s.  q is conservative: a GAP → FC.. chain may fuse into one op.
-  auto gemv_form = [&](const Step& st) { return st.kind == StepKind::PwConv && st.OH * st.OW <= 4 && st.OH * st.OW * st.Cout * 16 <= kLdsScratchFloats; };   // (a lowering with reduced scratch never contains one: see build_frame_program)
+  // (a lowering with reduced scratch never contains one: see build_frame_program.  in2 < 0: mo_gemv has the gate FCs' operands — input, per-channel scale, residual — and
+  //  no add operand; the x * s + a convolution of a decoder level keeps the matrix-core / VALU body at any pixel count.  A 16x16 or 8x8 network input, whose decoder
+  //  levels are 2x2 and 1x1, is where the two meet: tests/model_size_cases.py)
+  auto gemv_form = [&](const Step& st) { return st.kind == StepKind::PwConv && st.in2 < 0 && st.OH * st.OW <= 4 && st.OH * st.OW * st.Cout * 16 <= kLdsScratchFloats; };
   std::vector<int> stage(NS, 0), slot(NS, 0);
   std::vector<std::vector<int>> slots_from(NS);
   for (int s = 0; s < NS; s++) {
@@ -292,7 +295,10 @@ static void lower_frame_program(const Graph& g, Plan* plan, const std::vector<St
            a.OH * a.OW > 1024 && last[a.out] == s + 1 &&
            b.kind == StepKind::DwConv && b.in0 == a.out && b.residual == a.out && b.kh == 3 && b.kw == 3 && b.sh == 1 && b.sw == 1 && b.dh == 1 &&
            b.dw == 1 && b.pad_t == 1 && b.pad_l == 1 && last[b.out] == s + 2 &&
-           c2.kind == StepKind::TConv && c2.in0 == b.out && c2.kh == 2 && c2.kw == 2 && c2.Cout <= 4;
+           c2.kind == StepKind::TConv && c2.in0 == b.out && c2.kh == 2 && c2.kw == 2 && c2.Cout <= 4 &&
+           // the fused tail stores the whole 2x2 block of every input pixel: not the SAME-cropped form (odd input, OH = 2H - 1), whose last output row and column
+           // do not exist — the block's second row of the last input row would land behind the tensor.  That form keeps the stand-alone micro-op (bounded by OH * OW).
+           c2.OH == 2 * c2.H && c2.OW == 2 * c2.W;
   };
   for (int s = 0; s < NS; s++) {
     const Step& st = steps[s];

@@ -84,7 +84,13 @@ def _linear(op, x, w, b):
         y = F.linear(x.reshape(-1, x.shape[-1]), w, b)
         return y.reshape(tuple(x.shape[:-1]) + (y.shape[-1],)) if op.opts.get("keep_num_dims") else y
     assert op.code == 32                                          # Convolution2DTransposeBias: 2x2 stride 2, SAME → no overlap
-    return _nhwc(F.conv_transpose2d(_nchw(x), w.permute(3, 0, 1, 2).contiguous(), b, stride=2))     # [O,kh,kw,I] → [I,O,kh,kw]
+    y = _nhwc(F.conv_transpose2d(_nchw(x), w.permute(3, 0, 1, 2).contiguous(), b, stride=2))        # [O,kh,kw,I] → [I,O,kh,kw]
+    # the operator's own extent under SAME: stride * (in - 1) + k - pad, pad = max(0, k - (in - 1) % stride - 1) — 1 for an odd input, 0 for an even one; the
+    # operator's offset is pad / 2 = 0, so the full result is cropped at the bottom and right
+    kh, kw = int(w.shape[1]), int(w.shape[2])
+    oh = 2 * (x.shape[1] - 1) + kh - max(0, kh - (x.shape[1] - 1) % 2 - 1)
+    ow = 2 * (x.shape[2] - 1) + kw - max(0, kw - (x.shape[2] - 1) % 2 - 1)
+    return y[:, :oh, :ow]
 
 
 def f16(a):

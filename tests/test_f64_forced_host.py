@@ -19,17 +19,27 @@ import numpy as np
 import pytest
 
 from conftest import reference_model_path, synthetic_model_path
+from model_size_cases import BY_NAME, CASES as SIZE_CASES, model_file
 
 torch = pytest.importorskip("torch")
 
 import f64_graph as G  # noqa: E402
 
 W, H = 640, 480
-MODELS = ["lite", "full", "mlkit", "lite-synthetic", "full-synthetic", "mlkit-synthetic", "deeplab-synthetic"]
+SHIPPED = ["lite", "full", "mlkit", "lite-synthetic", "full-synthetic", "mlkit-synthetic", "deeplab-synthetic"]
+MODELS = SHIPPED + [c.name for c in SIZE_CASES]      # the Meet / MLKit graphs at other input sizes (tests/model_size_cases.py): the bar must be fair there too
 INPUTS = ["synthetic", "noise", "black", "white", "dot"]
+_SIZED = {}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _sized_models(tmp_path_factory):
+    _SIZED["dir"] = tmp_path_factory.mktemp("sized_models")
 
 
 def _path(model):
+    if model in BY_NAME:
+        return model_file(BY_NAME[model], _SIZED["dir"])
     key, _, syn = model.partition("-")
     return synthetic_model_path(key) if syn else reference_model_path(key)
 
@@ -164,7 +174,25 @@ def test_a_2_to_the_minus_16_change_of_one_channel_fails_there_and_downstream_on
     assert not missing, "no tensor of kind %s on which 2^-16 is above the bar" % missing
 
 
-@pytest.mark.parametrize("model", ["lite", "mlkit", "deeplab-synthetic"])
+EDGE_FAULTS = ("last row", "last column", "first row", "first column", "corner pixel")
+
+
+def _edge_fault(a, what):
+    b = a.copy()
+    if what == "last row":
+        b[:, -1] = b[:, -2]
+    elif what == "last column":
+        b[:, :, -1] = b[:, :, -2]
+    elif what == "first row":
+        b[:, 0] = b[:, 1]
+    elif what == "first column":
+        b[:, :, 0] = b[:, :, 1]
+    else:
+        b[:, -1, -1] = b[:, -2, -2]
+    return b
+
+
+@pytest.mark.parametrize("model", ["lite", "mlkit", "deeplab-synthetic", "lite-16x16", "lite-104x168"])
 def test_a_border_row_column_or_corner_taken_from_its_neighbour_fails(model):
     """Edges: what a kernel gets wrong at a SAME-padding edge or a tile edge.  On a noise network input (uniform f32 over the normalised range), in the stem's
     output, in the first stride-2 depthwise output, in the largest tensor of the decoder and in the network output: the last and first row, the last and first
@@ -180,18 +208,8 @@ def test_a_border_row_column_or_corner_taken_from_its_neighbour_fails(model):
     big = max((op.outputs[0] for op in spatial[len(spatial) // 2:-1]), key=lambda t: dev[t].size)
     out = m.outputs[0]
     for t in (stem, dw2, big, out):
-        for what in ("last row", "last column", "first row", "first column", "corner pixel"):
-            b = dev[t].copy()
-            if what == "last row":
-                b[:, -1] = b[:, -2]
-            elif what == "last column":
-                b[:, :, -1] = b[:, :, -2]
-            elif what == "first row":
-                b[:, 0] = b[:, 1]
-            elif what == "first column":
-                b[:, :, 0] = b[:, :, 1]
-            else:
-                b[:, -1, -1] = b[:, -2, -2]
+        for what in EDGE_FAULTS:
+            b = _edge_fault(dev[t], what)
             change = float(np.abs(b.astype(np.float64) - dev[t]).max())
             if t not in (stem, dw2) and not change > rows0[t]["bar"] + rows0[t]["local"]:
                 print("%-18s t%-3d %-18s %-13s: moves the tensor by %.3g, below its bar" % (model, t, "x".join(map(str, dev[t].shape)), what, change))
@@ -202,8 +220,33 @@ def test_a_border_row_column_or_corner_taken_from_its_neighbour_fails(model):
             print("%-18s t%-3d %-18s %-13s: failed at %s" % (model, t, "x".join(map(str, dev[t].shape)), what, fails))
             assert t in fails, "%s of t%d replaced by its neighbour passes" % (what, t)
             checked.setdefault(what, []).append(t)
-    for what in ("last row", "last column", "first row", "first column", "corner pixel"):
+    for what in EDGE_FAULTS:
         assert {stem, dw2} <= set(checked.get(what, [])), "%s: asserted on %s only" % (what, checked.get(what, []))
+    if model != "lite-16x16":
+        return
+    # The 16x16 graph shrinks to 1x1 in its middle: every tensor that still has two rows and two columns takes the five faults.  One that moves the tensor by more
+    # than its bar plus its own local error must fail there (the triangle inequality); a tensor counts as caught when all five did.
+    caught, small = [], []
+    for op in m.ops:
+        t = op.outputs[0]
+        if t not in dev or dev[t].ndim != 4:
+            continue
+        if min(dev[t].shape[1:3]) < 2:
+            small.append(t)
+            continue
+        n = 0
+        for what in EDGE_FAULTS:
+            b = _edge_fault(dev[t], what)
+            if not float(np.abs(b.astype(np.float64) - dev[t]).max()) > rows0[t]["bar"] + rows0[t]["local"]:
+                continue
+            mut = dict(dev)
+            mut[t] = b
+            assert t in G.failing(G.audit(path, x, mut, ot, exact, m)), "%s of t%d (%s) replaced by its neighbour passes" % (what, t, "x".join(map(str, dev[t].shape)))
+            n += 1
+        if n == len(EDGE_FAULTS):
+            caught.append(t)
+    print("%s: all five faults caught in %d tensors %s; %d tensors of fewer than two rows or columns skipped" % (model, len(caught), caught, len(small)))
+    assert len(caught) >= 10 and small
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -256,7 +299,7 @@ def _stand_in(m, x, cut, half_storage, rounding, fault=None):
     return dev
 
 
-STAND_INS = [(model, "half storage") for model in MODELS] + [("deeplab-synthetic", "f16 operands"), ("deeplab-synthetic", "both")]
+STAND_INS = [(model, "half storage") for model in SHIPPED] +[("deeplab-synthetic", "f16 operands"), ("deeplab-synthetic", "both")]
 
 
 @pytest.mark.parametrize("model,kind", STAND_INS, ids=["%s-%s" % (a, b.replace(" ", "_")) for a, b in STAND_INS])

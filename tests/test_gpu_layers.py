@@ -117,16 +117,24 @@ def stored_by_plan(plan, n_file_tensors, n, f16_gemm, chained=None):
 
 @pytest.mark.parametrize("case", CASES, ids=_case_id)
 def test_every_stored_tensor_against_float64(case, oracle, monkeypatch, debug_switches):
-    from backscrub_amd import tflite_io
-    bs = debug_switches
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a visible MI355X (torch.cuda.is_available() is False)")
     arch, real, pi = case
     pname, env = _paths(arch)[pi]
     path = reference_model_path(arch) if real else synthetic_model_path(arch)
     if real and not os.path.exists(path):
         pytest.fail("model fixture %s is missing" % path)
-    for k in KNOBS:
+    audit_every_stored_tensor(debug_switches, oracle, monkeypatch, path, arch, pname, env, weights="real" if real else "synthetic")
+
+
+def audit_every_stored_tensor(bs, oracle, monkeypatch, path, arch, pname, env, weights="synthetic", model=None, knobs=KNOBS, about_plan=None):
+    """The audit of one model file on one execution path (bs: the debug library's binding; arch: the architecture whose paths and input range apply; env: the path's
+    switches; model: the name on the printed and recorded lines, default arch; knobs: every switch to clear first; about_plan: called with the context's plan text
+    for what a caller has to assert of it).  tests/test_gpu_model_sizes.py runs it on the graphs of other input sizes."""
+    from backscrub_amd import tflite_io
+    if not torch.cuda.is_available():
+        pytest.fail("GPU tests need a visible MI355X (torch.cuda.is_available() is False)")
+    model = model or arch
+    real = weights == "real"
+    for k in knobs:
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
@@ -139,6 +147,8 @@ def test_every_stored_tensor_against_float64(case, oracle, monkeypatch, debug_sw
     try:
         plan = mg.plan()
         assert "slot of its own" in plan and "NaN bytes" in plan, "the loaded library ignores BSX_ARENA_NO_REUSE / BSX_ARENA_POISON"
+        if about_plan:
+            about_plan(plan)
         expected, step_outs, program_on = stored_by_plan(plan, nt, N_STEPPED, env.get("BSX_F16_GEMM") != "off")
         frames = G.audit_frames(W, H)
         oc = oracle.Ctx(path, W, H)
@@ -181,7 +191,7 @@ def test_every_stored_tensor_against_float64(case, oracle, monkeypatch, debug_sw
             assert len(rows) == len(expected) - len(set(excluded) & expected), "stream %d: %d of %d stored tensors audited" % (i, len(rows), len(expected))
             n, ratio, at, acc, acc_at = G.summary(rows)
             print("%-7s %-9s %-60s stream %d %-9s: %3d tensors audited, worst local ratio %5.2f at t%-3d, worst accumulated error %7.1f ulps at t%d" % (
-                arch, "real" if real else "synthetic", pname, i, names[i], n, ratio, at, acc, acc_at))
+                model, "real" if real else "synthetic", pname, i, names[i], n, ratio, at, acc, acc_at))
             record.append({"stream": i, "input": names[i], "audited": n, "worst_ratio": ratio, "worst_ratio_tensor": at, "worst_acc_ulps": acc, "worst_acc_tensor": acc_at})
             bad = G.failing(rows)
             if bad:
@@ -201,11 +211,11 @@ def test_every_stored_tensor_against_float64(case, oracle, monkeypatch, debug_sw
         out_path = os.environ.get("BSX_LAYER_AUDIT_OUT")
         if out_path:
             with open(out_path, "a") as f:
-                f.write(json.dumps({"model": arch, "weights": "real" if real else "synthetic", "path": pname, "stored": len(expected), "streams": record}) + "\n")
+                f.write(json.dumps({"model": model, "weights": "real" if real else "synthetic", "path": pname, "stored": len(expected), "streams": record}) + "\n")
         assert not problems, "\n".join(problems)
     finally:
         if oc is not None:
             oc.close()
         mg.close()
-        for k in KNOBS + ("BSX_ARENA_NO_REUSE", "BSX_ARENA_POISON"):
+        for k in tuple(knobs) + ("BSX_ARENA_NO_REUSE", "BSX_ARENA_POISON"):
             monkeypatch.delenv(k, raising=False)

@@ -1,6 +1,8 @@
 """Layer-by-layer audit of the GPU network against float64 (run on a GPU box; needs libbsx_dbg.so, the build with the debug switches).
 
 Usage: python tools/debug_layers.py <model.tflite|key> [W H]     (execution-path switches such as BSX_NO_RTC=1 or BSX_F16_GEMM=off are taken from the environment)
+       python tools/debug_layers.py --model-size family:HxW [W H]    a Meet-family ("lite") or MLKit ("mlkit") graph of that network input size, e.g. lite:104x168:
+                                                                     the model of tests/model_size_cases.py where that is one of its cases (same seed), written to a temporary directory
 
 The same helper and the same table as tests/test_gpu_layers.py (tests/f64_graph.py: audit): per tensor the path stores, its distance from a float64 evaluation of the
 operators since the nearest stored tensors upstream (local), the oracle's distance on the same operators (loc.oracle), their ratio (a tensor passes up to 8) and the
@@ -31,9 +33,23 @@ from backscrub_amd import tflite_io  # noqa: E402
 from conftest import MODEL_KEYS, model_path  # noqa: E402
 from oracle import oracle_py as O  # noqa: E402
 
-arg = sys.argv[1] if len(sys.argv) > 1 else "lite"
-path = model_path(arg) if arg in MODEL_KEYS else arg
-W, H = (int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (640, 480)
+argv = sys.argv[1:]
+if argv and argv[0] == "--model-size":
+    import re
+    import tempfile
+    from model_size_cases import CASES, Case, model_file  # noqa: E402
+    spec = re.fullmatch(r"(lite|mlkit):(\d+)x(\d+)", argv[1] if len(argv) > 1 else "")
+    if not spec:
+        sys.exit("--model-size takes family:HxW with family lite or mlkit, e.g. lite:104x168")
+    fam, mh, mw = spec.group(1), int(spec.group(2)), int(spec.group(3))
+    case = next((c for c in CASES if (c.family, c.H, c.W) == (fam, mh, mw)), None) or Case("%s-%dx%d" % (fam, mh, mw), fam, mh, mw, 4999, *([None] * 7))
+    path = model_file(case, tempfile.mkdtemp(prefix="bsx_model_size_"))
+    argv = argv[2:]
+else:
+    arg = argv[0] if argv else "lite"
+    path = model_path(arg) if arg in MODEL_KEYS else arg
+    argv = argv[1:]
+W, H = (int(argv[0]), int(argv[1])) if len(argv) > 1 else (640, 480)
 m = tflite_io.load(path)
 frames = G.audit_frames(W, H)
 mg = backscrub_amd.MaskGen(path, W, H, n_streams=len(frames))

@@ -129,8 +129,10 @@ class G:
         _, h, w, c = self.shape(x)
         wt = self.weight(self._rand((cout, 2, 2, c), c, gain), "tw")
         b = self.weight(self.rng.uniform(-0.2, 0.2, cout), "tb")
-        # TfLiteTransposeConvParams{padding=SAME(1), stride_w=2, stride_h=2}
-        return self.op("Convolution2DTransposeBias", [x, wt, b], [1, 2 * h, 2 * w, cout], custom=struct.pack("<iii", 1, 2, 2))
+        # TfLiteTransposeConvParams{padding=SAME(1), stride_w=2, stride_h=2}.  The operator computes its own output extent, stride * (in - 1) + kernel - pad with
+        # pad = 1 for an odd input under SAME (0 otherwise): 2h for an even h, 2h - 1 for an odd one (the full 2h result cropped at the bottom and right).
+        oh, ow = 2 * h - h % 2, 2 * w - w % 2
+        return self.op("Convolution2DTransposeBias", [x, wt, b], [1, oh, ow, cout], custom=struct.pack("<iii", 1, 2, 2))
 
     def model(self, inp, out, desc):
         return T.Model(self.t, self.ops, [inp], [out], desc)
@@ -234,13 +236,26 @@ def _deeplab(seed):
     return g.model(x, out, "synthetic deeplabv3-mnv2 257 (seed %d)" % seed)
 
 
+def build_sized(family: str, H: int, W: int, seed: int) -> T.Model:
+    """A Meet-family ("lite": the graph of segm_lite / segm_full) or MLKit ("mlkit") model with an H x W network input.  Nothing in the graph is tied to the shipped
+    sizes: every extent follows from H and W by the operators' own rules."""
+    if family not in ("lite", "mlkit"):
+        raise KeyError(family)
+    return _meet_family(H, W, family == "mlkit", seed)
+
+
+def sized_file_name(family: str, H: int, W: int) -> str:
+    """a file name with the substring the model-type sniffing looks for ("segm_" / "selfie")"""
+    return ("synthetic_selfie_mlkit_%dx%d.f16.tflite" if family == "mlkit" else "synthetic_segm_lite_%dx%d.tflite") % (H, W)
+
+
 def build(key: str, seed: int = 1234) -> T.Model:
     if key == "lite":
-        return _meet_family(96, 160, False, seed)
+        return build_sized("lite", 96, 160, seed)
     if key == "full":
-        return _meet_family(144, 256, False, seed + 1)
+        return build_sized("lite", 144, 256, seed + 1)
     if key == "mlkit":
-        return _meet_family(256, 256, True, seed + 2)
+        return build_sized("mlkit", 256, 256, seed + 2)
     if key == "deeplab":
         return _deeplab(seed + 3)
     raise KeyError(key)
