@@ -26,6 +26,7 @@ STAGE_FN = C.CFUNCTYPE(None, C.c_void_p)
 
 BSX_STREAM_FILTER_OFF = 32          # bsx.h: bits of bsx_stream_setting.flags next to the flip bits and the blur size
 BSX_STREAM_YUYV_IN = 64             # ... in an item of step_geoms / step_vcam_geoms only: that item's frame is YUYV 4:2:2
+BSX_GEOMS_EDGE_ROI = 1              # bsx.h: creation flag of bsx_new_geoms_ex (MaskGen.with_geometries(edge_roi=True))
 
 
 class BsxError(RuntimeError):
@@ -114,6 +115,7 @@ SYMBOLS = [
     ("bsx_step_batch_streams", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_uint]),
     ("bsx_reset_streams", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_void_p]),
     ("bsx_new_geoms", C.c_void_p, [C.c_char_p, C.c_size_t, C.POINTER(_Geometry), C.c_int, C.c_int, DEBUG_FN, STAGE_FN, STAGE_FN, STAGE_FN, C.c_void_p]),
+    ("bsx_new_geoms_ex", C.c_void_p, [C.c_char_p, C.c_size_t, C.POINTER(_Geometry), C.c_int, C.c_int, C.c_uint, DEBUG_FN, STAGE_FN, STAGE_FN, STAGE_FN, C.c_void_p]),
     ("bsx_geom_count", C.c_int, [C.c_void_p]),
     ("bsx_get_geom_info", C.c_int, [C.c_void_p, C.c_int, C.POINTER(_GeomInfo)]),
     ("bsx_step_batch_geoms", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(_GeomItem), C.c_int, C.c_void_p, C.c_uint]),
@@ -224,20 +226,31 @@ class MaskGen:
         self.width, self.height, self.n_streams, self.device = width, height, n_streams, device
 
     @classmethod
-    def with_geometries(cls, model_path, geometries, device=0, threads=2, ondebug=None, onprep=None, oninfer=None, onmask=None, caller_ctx=None):
+    def with_geometries(cls, model_path, geometries, device=0, threads=2, ondebug=None, onprep=None, oninfer=None, onmask=None, caller_ctx=None, edge_roi=False):
         """a context for cameras of several capture sizes (bsx_new_geoms): geometries = [(width, height, n_streams), ...], at most 8 distinct sizes.  Streams are
-        numbered class after class; step_geoms advances any mix of them in one launch sequence.  width / height / info are class 0's, n_streams the total."""
+        numbered class after class; step_geoms advances any mix of them in one launch sequence.  width / height / info are class 0's, n_streams the total.
+        edge_roi=True (bsx_new_geoms_ex with BSX_GEOMS_EDGE_ROI): sizes whose ROI is off the 4-pixel grid are taken too (segm_lite at 1920x1080); every width
+        must still be a multiple of 4."""
         geometries = [tuple(int(v) for v in g) for g in geometries]
         if not geometries or any(len(g) != 3 for g in geometries):
             raise BsxError("geometries must be a non-empty list of (width, height, n_streams)")
+        if not isinstance(edge_roi, (bool, np.bool_)):
+            raise BsxError("edge_roi must be True or False, not %r" % (edge_roi,))
+        if edge_roi:
+            for g, (w, _h, _n) in enumerate(geometries):
+                if w % 4:
+                    raise BsxError("geometries[%d]: width %d is not a multiple of 4 (edge_roi frees the ROI's column and width, not the frame's)" % (g, w))
         L = lib()
         self = cls.__new__(cls)
         self._cbs = (DEBUG_FN(ondebug) if ondebug else DEBUG_FN(), STAGE_FN(onprep) if onprep else STAGE_FN(),
                      STAGE_FN(oninfer) if oninfer else STAGE_FN(), STAGE_FN(onmask) if onmask else STAGE_FN())
         arr = (_Geometry * len(geometries))(*[_Geometry(*g) for g in geometries])
-        self.h = L.bsx_new_geoms(os.fsencode(model_path), threads, arr, len(geometries), device, *self._cbs, caller_ctx)
+        if edge_roi:
+            self.h = L.bsx_new_geoms_ex(os.fsencode(model_path), threads, arr, len(geometries), device, BSX_GEOMS_EDGE_ROI, *self._cbs, caller_ctx)
+        else:
+            self.h = L.bsx_new_geoms(os.fsencode(model_path), threads, arr, len(geometries), device, *self._cbs, caller_ctx)
         if not self.h:
-            raise BsxError("bsx_new_geoms failed: %s" % (L.bsx_last_error(None) or b"").decode(errors="replace").strip())
+            raise BsxError("%s failed: %s" % ("bsx_new_geoms_ex" if edge_roi else "bsx_new_geoms", (L.bsx_last_error(None) or b"").decode(errors="replace").strip()))
         info = _Info()
         _check(L.bsx_get_info(self.h, C.byref(info)), self.h, "bsx_get_info")
         self.info = {k: (list(getattr(info, k)) if k in ("roi", "in_roi") else getattr(info, k)) for k, _ in _Info._fields_}

@@ -206,8 +206,14 @@ struct bsx_ctx {
     size_t mask_offset = 0, tiles_per_frame = 0;
     int outside_blocks = 0;            // outside-ROI workgroups of one position (0: the ROI is the frame)
     bool fusable = false, xcd = false; // on the fused tile route (geom_class_fusable); mask tiles of a frame on one XCD (geom_class_xcd)
+    // a context made with BSX_GEOMS_EDGE_ROI: `edge` = roi.x or roi.w is off the 4-pixel grid — the geoms step then tiles the class in frame-anchored columns
+    // (tiles_per_frame counts those; kernels.hpp: launch_mask_blend_geoms_edge), the vcam step in ROI-anchored ones (vg_tiles_per_frame)
+    bool edge = false, shifted_tiles_fit = false;
+    size_t vg_tiles_per_frame = 0;
   };
   std::vector<Geom> geoms;
+  bool edge_roi = false;                    // made by bsx_new_geoms_ex with BSX_GEOMS_EDGE_ROI
+  GeomClass* d_geom_classes_vg = nullptr;   // the class records with ROI-anchored tile columns, where a class is `edge` (else the vcam step reads d_geom_classes)
   size_t mask_bytes = 0;                    // the whole d_masks allocation
   GeomClass* d_geom_classes = nullptr;      // device copy of the class records (uploaded by bsx_new_geoms; for a one-class context on its first geoms step)
   uint8_t* d_geom_tile_class = nullptr;     // one byte per workgroup of the largest ragged tile grid (every stream of every class) + 4; null: BSX_NO_UNIFORM_TILES
@@ -294,17 +300,25 @@ int model_type_from_name(const std::string& n) {  // lib/libbackscrub.cc:116-130
 int geoms_device_state(bsx_ctx* c) {
   if (c->d_geo) return BSX_OK;
   const size_t G = c->geoms.size(), N = (size_t)c->n_streams;
-  std::vector<GeomClass> rec(G);
+  std::vector<GeomClass> rec(G), rec_vg(G);
   size_t tiles = 0;
+  bool any_edge = false;
   for (size_t g = 0; g < G; g++) {
     const bsx_ctx::Geom& q = c->geoms[g];
-    rec[g] = GeomClass{q.width, q.height, (q.roi.w + mask_tile_width() - 1) / mask_tile_width(), (q.roi.h + mask_tile_height() - 1) / mask_tile_height(), q.roi, q.in_roi,
+    rec[g] = GeomClass{q.width, q.height, geom_tile_cols(q.roi, q.edge), (q.roi.h + mask_tile_height() - 1) / mask_tile_height(), q.roi, q.in_roi,
                        q.tab_down.tab, q.tab_up.tab};
-    tiles += (size_t)q.n_streams * q.tiles_per_frame;
+    rec_vg[g] = rec[g];
+    rec_vg[g].ntx = geom_tile_cols(q.roi, false);
+    any_edge = any_edge || q.edge;
+    tiles += (size_t)q.n_streams * q.tiles_per_frame;                // (frame-anchored columns are never fewer than ROI-anchored ones: one scratch serves both steps)
   }
   if (!c->d_geom_classes) {
     BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_geom_classes), G * sizeof(GeomClass)));
     BSX_HIP(c, hipMemcpy(c->d_geom_classes, rec.data(), G * sizeof(GeomClass), hipMemcpyHostToDevice));
+  }
+  if (any_edge && !c->d_geom_classes_vg) {
+    BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_geom_classes_vg), G * sizeof(GeomClass)));
+    BSX_HIP(c, hipMemcpy(c->d_geom_classes_vg, rec_vg.data(), G * sizeof(GeomClass), hipMemcpyHostToDevice));
   }
   if (!c->no_uniform_tiles && !c->d_geom_tile_class) {
     BSX_HIP(c, hipMalloc(&c->d_geom_tile_class, tiles + 4));        // (+4: the tile kernel reads the aligned word around a byte)
@@ -414,9 +428,12 @@ int init_device_state(bsx_ctx* c) {
       if ((rc = upload_tab(c, make_resize_tab(G.in_roi.w, G.in_roi.h, G.roi.w, G.roi.h), &G.tab_up))) return rc;
     }
     G.tab_up.tab.tile_class = nullptr;                             // (the geoms step's class bytes travel as a kernel argument)
-    G.tiles_per_frame = (size_t)((G.roi.w + mask_tile_width() - 1) / mask_tile_width()) * (size_t)((G.roi.h + mask_tile_height() - 1) / mask_tile_height());
+    G.edge = c->edge_roi && !geom_class_on_grid(G.roi);
+    const size_t tile_rows = (size_t)((G.roi.h + mask_tile_height() - 1) / mask_tile_height());
+    G.tiles_per_frame = (size_t)geom_tile_cols(G.roi, G.edge) * tile_rows;
+    G.vg_tiles_per_frame = (size_t)geom_tile_cols(G.roi, false) * tile_rows;
     G.outside_blocks = geom_outside_blocks(G.width, G.height, G.roi);
-    G.fusable = geom_class_fusable(G.width, G.roi, G.tab_up.tab);
+    G.fusable = G.edge ? geom_class_edge_fusable(G.width, G.roi, G.tab_up.tab, G.shifted_tiles_fit) : geom_class_fusable(G.width, G.roi, G.tab_up.tab);
     G.xcd = geom_class_xcd(G.width, G.roi);
   }
   if (c->geoms.size() > 1) return geoms_device_state(c);
@@ -1228,8 +1245,10 @@ int geoms_check(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item*
 
 // The front of a checked geoms call on the context's device, ring entry k acquired: the positions ordered by class, ids and descriptors through the ring, ONE prep
 // launch and the network.  Leaves the descriptors' device copy, the ragged grids of the back end and the classes whose tiles keep to one XCD.
-struct GeomsStaged { const GeomDesc* desc = nullptr; GeomSpans tiles{}, outside{}; unsigned xcd_mask = 0; bool fmt = false; };      // fmt: some item is YUYV — the *_fmt launchers
-int geoms_front(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item* items, int n, hipStream_t s, int k, GeomsStaged* st) {
+// edge: some position's class is off the 4-pixel grid (bsx_new_geoms_ex) — the geoms step then takes launch_mask_blend_geoms_edge
+struct GeomsStaged { const GeomDesc* desc = nullptr; GeomSpans tiles{}, outside{}; unsigned xcd_mask = 0; bool fmt = false, edge = false; };      // fmt: some item is YUYV — the *_fmt launchers
+// vg: the tile grid of the vcam step (ROI-anchored tile columns for every class)
+int geoms_front(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item* items, int n, hipStream_t s, int k, GeomsStaged* st, bool vg = false) {
   const int G = (int)c->geoms.size();
   // positions ordered by class (a counting sort: stable, so a class keeps the caller's order)
   int count[kMaxGeoms] = {0};
@@ -1239,13 +1258,14 @@ int geoms_front(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item*
   unsigned xcd_mask = 0;
   for (int g = 0; g < kMaxGeoms; g++) {
     const int cnt = g < G ? count[g] : 0;
-    const int per_t = g < G ? (int)c->geoms[g].tiles_per_frame : 0, per_o = g < G ? c->geoms[g].outside_blocks : 0;
+    const int per_t = g < G ? (int)(vg ? c->geoms[g].vg_tiles_per_frame : c->geoms[g].tiles_per_frame) : 0, per_o = g < G ? c->geoms[g].outside_blocks : 0;
     if ((long)tiles.wg[g] + (long)cnt * per_t >= (1l << 31) || (long)outside.wg[g] + (long)cnt * per_o >= (1l << 31)) {
       c->last_error = std::string("error: ") + fn + ": the batch needs more than 2^31 workgroups\n"; return BSX_EDEVICE; }
     prep.pos[g + 1] = tiles.pos[g + 1] = outside.pos[g + 1] = tiles.pos[g] + cnt;
     tiles.wg[g + 1] = tiles.wg[g] + cnt * per_t; tiles.per[g] = per_t;
     outside.wg[g + 1] = outside.wg[g] + cnt * per_o; outside.per[g] = per_o;
     if (g < G && c->geoms[g].xcd) xcd_mask |= 1u << g;
+    if (cnt && c->geoms[g].edge) st->edge = true;
   }
   st->xcd_mask = xcd_mask;
   c->geo_order.resize((size_t)n); c->geo_ids.resize((size_t)n);
@@ -1281,7 +1301,7 @@ int geoms_run(bsx_ctx* c, const int* ids, const bsx_geom_item* items, int n, hip
   GeomsStaged st;
   if (const int rc = geoms_front(c, "bsx_step_batch_geoms", ids, items, n, s, k, &st)) return rc;
   bsx_roctx::Range range("bsx:mask+blend");
-  BSX_HIP(c, (st.fmt ? launch_mask_blend_geoms_fmt : launch_mask_blend_geoms)(c->d_geom_classes, st.desc, st.tiles, st.xcd_mask, st.outside, c->d_ofinal, c->outW, c->outH, c->d_geom_tile_class, n, s, (int)flags));
+  BSX_HIP(c, (st.edge ? launch_mask_blend_geoms_edge : st.fmt ? launch_mask_blend_geoms_fmt : launch_mask_blend_geoms)(c->d_geom_classes, st.desc, st.tiles, st.xcd_mask, st.outside, c->d_ofinal, c->outW, c->outH, c->d_geom_tile_class, n, s, (int)flags));
   return BSX_OK;
 }
 
@@ -1370,9 +1390,9 @@ int vcam_geoms_run(bsx_ctx* c, const int* ids, const bsx_geom_item* items, int n
   const VgClass* vg = nullptr;
   if (const int rc = vg_geoms_records(c, out_w, out_h, &vg)) return rc;
   GeomsStaged st;
-  if (const int rc = geoms_front(c, fn, ids, items, n, s, k, &st)) return rc;
+  if (const int rc = geoms_front(c, fn, ids, items, n, s, k, &st, true)) return rc;
   bsx_roctx::Range range("bsx:mask+vcam");
-  BSX_HIP(c, (st.fmt ? launch_vcam_geoms_fmt : launch_vcam_geoms)(c->d_geom_classes, vg, st.desc, st.tiles, st.xcd_mask, c->d_ofinal, c->outW, c->outH, c->d_geom_tile_class, out_w, out_h, n, s, flags & 1u));
+  BSX_HIP(c, (st.fmt ? launch_vcam_geoms_fmt : launch_vcam_geoms)(c->d_geom_classes_vg ? c->d_geom_classes_vg : c->d_geom_classes, vg, st.desc, st.tiles, st.xcd_mask, c->d_ofinal, c->outW, c->outH, c->d_geom_tile_class, out_w, out_h, n, s, flags & 1u));
   return BSX_OK;
 }
 
@@ -1446,8 +1466,9 @@ static bool capture_rois(const bsx_ctx* c, size_t width, size_t height, Rect4* r
 }
 
 // bsx_new / bsx_new_geoms: geoms[0..n_geoms) checked by the caller (positive sizes and counts, total <= 65535); class 0 becomes the context's own geometry
+// geom_flags: bsx_new_geoms_ex's (BSX_GEOMS_EDGE_ROI), 0 from the other two
 static bsx_ctx* new_ctx(const char* model_path, size_t threads, const bsx_geometry* geoms, int n_geoms, int device, bsx_debug_fn ondebug, bsx_stage_fn onprep,
-                        bsx_stage_fn oninfer, bsx_stage_fn onmask, void* caller_ctx) {
+                        bsx_stage_fn oninfer, bsx_stage_fn onmask, void* caller_ctx, unsigned geom_flags = 0) {
   const size_t width = (size_t)geoms[0].width, height = (size_t)geoms[0].height;
   int n_streams = 0;
   for (int g = 0; g < n_geoms; g++) n_streams += geoms[g].n_streams;
@@ -1455,6 +1476,7 @@ static bsx_ctx* new_ctx(const char* model_path, size_t threads, const bsx_geomet
   std::unique_ptr<bsx_ctx> c(new bsx_ctx);
   c->ondebug = ondebug; c->onprep = onprep; c->oninfer = oninfer; c->onmask = onmask; c->caller_ctx = caller_ctx;
   c->threads = threads; c->width = (int)width; c->height = (int)height; c->n_streams = n_streams; c->device = device;
+  c->edge_roi = (geom_flags & BSX_GEOMS_EDGE_ROI) != 0;
   std::string err;
   if (!load_tflite(model_path, &c->graph, &err)) { report(nullptr, ondebug, caller_ctx, "error: %s\n", err.c_str()); return nullptr; }
   c->model_type = model_type_from_name(model_path);
@@ -1496,7 +1518,22 @@ static bsx_ctx* new_ctx(const char* model_path, size_t threads, const bsx_geomet
       report(nullptr, ondebug, caller_ctx, "error: bsx_new_geoms: geoms[%d] (%d x %d): frame/model geometry yields an empty or out-of-range ROI\n", g, G.width, G.height);
       return nullptr;
     }
-    if (n_geoms > 1) {
+    if (c->edge_roi) {
+      // the opt-in rule, for any number of classes: rows of whole dwords and the tiled linear up-scale, with the tiles anchored where each of the two steps puts them
+      const HostResizeTab up = make_resize_tab(G.in_roi.w, G.in_roi.h, G.roi.w, G.roi.h);
+      G.shifted_tiles_fit = up.mode == 0 && mask_tile_fits(up.xofs.data(), up.yofs.data(), up.sw, up.sh, up.dw, up.dh, geom_edge_shift(G.roi));
+      const bool tiles = up.mode == 0 && !c->no_mask_tile && G.roi.w >= 8 && G.shifted_tiles_fit && mask_tile_fits(up.xofs.data(), up.yofs.data(), up.sw, up.sh, up.dw, up.dh);
+      if (G.width & 3) {
+        report(nullptr, ondebug, caller_ctx, "error: bsx_new_geoms_ex: geoms[%d] (%d x %d): width %d is not a multiple of 4 (the edge-ROI flag frees roi.x and roi.w; a row "
+               "must still be whole dwords)\n", g, G.width, G.height, G.width);
+        return nullptr;
+      }
+      if (!tiles) {
+        report(nullptr, ondebug, caller_ctx, "error: bsx_new_geoms_ex: geoms[%d] (%d x %d) is off the fused tile route: the mask up-scale %d x %d -> %d x %d must be a tiled "
+               "linear one\n", g, G.width, G.height, G.in_roi.w, G.in_roi.h, G.roi.w, G.roi.h);
+        return nullptr;
+      }
+    } else if (n_geoms > 1) {
       const HostResizeTab up = make_resize_tab(G.in_roi.w, G.in_roi.h, G.roi.w, G.roi.h);
       const bool tiles = up.mode == 0 && !c->no_mask_tile && mask_tile_fits(up.xofs.data(), up.yofs.data(), up.sw, up.sh, up.dw, up.dh);
       if ((G.width & 3) || (G.roi.x & 3) || (G.roi.w & 3) || !tiles) {
@@ -1580,9 +1617,9 @@ bsx_ctx* bsx_new(const char* model_path, size_t threads, size_t width, size_t he
   return new_ctx(model_path, threads, &one, 1, device, ondebug, onprep, oninfer, onmask, caller_ctx);
 }
 
-bsx_ctx* bsx_new_geoms(const char* model_path, size_t threads, const bsx_geometry* geoms, int n_geoms, int device, bsx_debug_fn ondebug, bsx_stage_fn onprep,
-                       bsx_stage_fn oninfer, bsx_stage_fn onmask, void* caller_ctx) {
-  const char* fn = "error: bsx_new_geoms:";
+// the argument checks of bsx_new_geoms and bsx_new_geoms_ex (fn: the message prefix), then the context
+static bsx_ctx* new_geoms_checked(const char* fn, const char* model_path, size_t threads, const bsx_geometry* geoms, int n_geoms, int device, unsigned geom_flags,
+                                  bsx_debug_fn ondebug, bsx_stage_fn onprep, bsx_stage_fn oninfer, bsx_stage_fn onmask, void* caller_ctx) {
   if (!model_path || !geoms) { report(nullptr, ondebug, caller_ctx, "%s model_path or geoms is NULL\n", fn); return nullptr; }
   if (n_geoms < 1 || n_geoms > BSX_MAX_GEOMS) { report(nullptr, ondebug, caller_ctx, "%s n_geoms = %d is outside [1, %d]\n", fn, n_geoms, BSX_MAX_GEOMS); return nullptr; }
   long total = 0;
@@ -1596,7 +1633,23 @@ bsx_ctx* bsx_new_geoms(const char* model_path, size_t threads, const bsx_geometr
     if (total > 65535) { report(nullptr, ondebug, caller_ctx, "%s geoms[%d] (%d x %d) brings the total to %ld streams, above 65535\n", fn, g, geoms[g].width, geoms[g].height, total); return nullptr; }
   }
   if (n_geoms > 1 && onmask) { report(nullptr, ondebug, caller_ctx, "%s an onmask callback needs a context of one geometry (%d given)\n", fn, n_geoms); return nullptr; }
-  return new_ctx(model_path, threads, geoms, n_geoms, device, ondebug, onprep, oninfer, onmask, caller_ctx);
+  return new_ctx(model_path, threads, geoms, n_geoms, device, ondebug, onprep, oninfer, onmask, caller_ctx, geom_flags);
+}
+
+bsx_ctx* bsx_new_geoms(const char* model_path, size_t threads, const bsx_geometry* geoms, int n_geoms, int device, bsx_debug_fn ondebug, bsx_stage_fn onprep,
+                       bsx_stage_fn oninfer, bsx_stage_fn onmask, void* caller_ctx) {
+  return new_geoms_checked("error: bsx_new_geoms:", model_path, threads, geoms, n_geoms, device, 0, ondebug, onprep, oninfer, onmask, caller_ctx);
+}
+
+bsx_ctx* bsx_new_geoms_ex(const char* model_path, size_t threads, const bsx_geometry* geoms, int n_geoms, int device, unsigned flags, bsx_debug_fn ondebug,
+                          bsx_stage_fn onprep, bsx_stage_fn oninfer, bsx_stage_fn onmask, void* caller_ctx) {
+  if (flags == 0) return bsx_new_geoms(model_path, threads, geoms, n_geoms, device, ondebug, onprep, oninfer, onmask, caller_ctx);
+  if (const unsigned unknown = flags & ~BSX_GEOMS_EDGE_ROI) {
+    report(nullptr, ondebug, caller_ctx, "error: bsx_new_geoms_ex: flags 0x%x has the unknown bit 0x%x (known: 0x%x, the edge-ROI flag)\n", flags, unknown & (0u - unknown),
+           BSX_GEOMS_EDGE_ROI);
+    return nullptr;
+  }
+  return new_geoms_checked("error: bsx_new_geoms_ex:", model_path, threads, geoms, n_geoms, device, flags, ondebug, onprep, oninfer, onmask, caller_ctx);
 }
 
 void bsx_delete(bsx_ctx* c) {
@@ -1628,6 +1681,7 @@ void bsx_delete(bsx_ctx* c) {
   if (c->d_blur_coef) (void)hipFree(c->d_blur_coef);
   for (size_t g = 1; g < c->geoms.size(); g++) { if (c->geoms[g].tab_down.mem) (void)hipFree(c->geoms[g].tab_down.mem); if (c->geoms[g].tab_up.mem) (void)hipFree(c->geoms[g].tab_up.mem); }
   if (c->d_geom_classes) (void)hipFree(c->d_geom_classes);
+  if (c->d_geom_classes_vg) (void)hipFree(c->d_geom_classes_vg);
   if (c->d_geom_tile_class) (void)hipFree(c->d_geom_tile_class);
   if (c->d_geo) (void)hipFree(c->d_geo);
   if (c->h_geo) (void)hipHostFree(c->h_geo);

@@ -95,7 +95,7 @@ struct ResizeTab {
   // whole source block is 0xFF, 2 = 0x00, 0 = anything else).  nullptr (BSX_NO_UNIFORM_TILES at bsx_new: A/B timing, parity tests) = every tile on the general path
   uint8_t* tile_class = nullptr;
 };
-bool mask_tile_fits(const int* xofs, const int* yofs, int sw, int sh, int dw, int dh);
+bool mask_tile_fits(const int* xofs, const int* yofs, int sw, int sh, int dw, int dh, int shift = 0);      // shift: the first tile column starts `shift` columns left of the ROI (geom_edge_shift)
 int mask_tile_width();             // the mask tile kernel's tile geometry (kernels_img.hip: kTW x kTH)
 int mask_tile_height();
 // classify the mask tiles of n streams into tab.tile_class (see ResizeTab); launch_mask_upscale_blur / launch_mask_blend run it themselves
@@ -217,6 +217,20 @@ hipError_t launch_mask_blend_geoms_fmt(const GeomClass* classes, const GeomDesc*
                                        const uint8_t* ofinal, int outW, int outH, uint8_t* tile_class, int n, hipStream_t s, int flags);
 hipError_t launch_vcam_geoms_fmt(const GeomClass* classes, const VgClass* vg, const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const uint8_t* ofinal,
                                  int outW, int outH, uint8_t* tile_class, int out_w, int out_h, int n, hipStream_t s, unsigned flags);
+// ---- classes off the 4-pixel grid (bsx_new_geoms_ex with BSX_GEOMS_EDGE_ROI): W % 4 == 0, roi.x and roi.w free ----------------------------------------------------
+// The composite moves in 4-pixel groups of three aligned dwords, so the groups are anchored to the FRAME: with s = roi.x & 3 (geom_edge_shift) tile column tbx of a
+// class starts at ROI-relative column 128 tbx - s, and a class has ceil((s + roi.w) / 128) tile columns (geom_tile_cols: GeomClass::ntx, the spans and the tile-class
+// scratch all count those).  The tile launch owns every group that intersects the ROI — a straddling group's pixels outside the ROI have mask 255 by definition: their
+// composite is the background (the frame with the filter off) and their mask bytes are not stored — the outside-ROI launch the groups wholly outside.  A class on the
+// grid (s = 0, roi.w % 4 == 0) is the same record either way.  launch_mask_blend_geoms_edge is launch_mask_blend_geoms_fmt's launch sequence with kernels of its own
+// that take every class in this form and every position in its own format; a call that touches no such class takes the launchers above.  The vcam launchers need no
+// such form (their tile kernel stores masks only, bytewise at ragged edges): they are given class records whose ntx counts ROI-anchored columns.
+constexpr int geom_edge_shift(const Rect4& roi) { return roi.x & 3; }      // (constexpr: host and device code both call it)
+int geom_tile_cols(const Rect4& roi, bool edge);             // tile columns of one frame: ROI-anchored, or frame-anchored for the edge launcher
+inline bool geom_class_on_grid(const Rect4& roi) { return (roi.x & 3) == 0 && (roi.w & 3) == 0; }
+bool geom_class_edge_fusable(int W, const Rect4& roi, const ResizeTab& up, bool shifted_tiles_fit);      // shifted_tiles_fit: mask_tile_fits(.., geom_edge_shift(roi)) of `up`
+hipError_t launch_mask_blend_geoms_edge(const GeomClass* classes, const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const GeomSpans& outside,
+                                        const uint8_t* ofinal, int outW, int outH, uint8_t* tile_class, int n, hipStream_t s, int flags);
 // alpha blend.  deepseg.cc:108-134
 hipError_t launch_blend(const uint8_t* bg, size_t bg_stride, const uint8_t* frames, const uint8_t* masks, uint8_t* out, size_t npix,
                         int n, hipStream_t s, const int* slot_of = nullptr);

@@ -863,13 +863,15 @@ __global__ __launch_bounds__(kThreads) void outside_roi_mixed_k(const MixDesc* _
 
 // the same for ONE position given by its own pointers (bsx_step_batch_geoms: outside_roi_geoms_k below) — the statements of outside_roi_mixed_k for group i of
 // the frame: bgp / fl = the position's descriptor, frame / out = ITS images.  (A function of its own and not the kernel's body: called from outside_roi_mixed_k
-// it changed that kernel's code.)
+// it changed that kernel's code.)  EDGE (outside_roi_geoms_edge_k: roi.x and roi.w off the 4-pixel grid): a group that straddles a ROI bound belongs to the tile
+// launch — only groups WHOLLY outside the ROI are written here.
+template <bool EDGE = false>
 __device__ __forceinline__ void outside_mixed_group(unsigned i, const uint8_t* __restrict__ bgp, unsigned fl, const uint8_t* __restrict__ frame, uint8_t* __restrict__ out,
                                                     int W, int H, Rect4 roi, int flags) {
   const unsigned gpr = (unsigned)W / 4;
   if (i >= gpr * (unsigned)H) return;
   const int row = (int)(i / gpr), x = (int)(i - (unsigned)row * gpr) * 4;
-  if (row >= roi.y && row < roi.y + roi.h && x >= roi.x && x < roi.x + roi.w) return;
+  if (row >= roi.y && row < roi.y + roi.h && x + (EDGE ? 3 : 0) >= roi.x && x < roi.x + roi.w) return;
   const long px = (long)row * W + x;
   uint32_t w[3];
   if (!(fl & kMixFilterOff)) {
@@ -1134,14 +1136,14 @@ hipError_t launch_decode(int model_type, const float* logits, uint8_t* ofinal, i
 // Every tile's source block must fit the LDS staging area of mask_tile_k (host tables, checked once per ResizeTab).
 int mask_tile_width() { return kTW; }
 int mask_tile_height() { return kTH; }
-bool mask_tile_fits(const int* xofs, const int* yofs, int sw, int sh, int dw, int dh) {
+bool mask_tile_fits(const int* xofs, const int* yofs, int sw, int sh, int dw, int dh, int shift) {
   auto clampi = [](int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); };
   int max_rows = 0, max_cols = 0;
   for (int ty0 = 0; ty0 < dh; ty0 += kTH) {
     const int lo = std::max(ty0 - 2, 0), hi = std::min(ty0 + kTH + 1, dh - 1);
     max_rows = std::max(max_rows, clampi(yofs[hi] + 1, 0, sh - 1) - clampi(yofs[lo], 0, sh - 1) + 1);
   }
-  for (int tx0 = 0; tx0 < dw; tx0 += kTW) {
+  for (int tx0 = -shift; tx0 < dw; tx0 += kTW) {
     const int lo = std::max(tx0 - 2, 0), hi = std::min(tx0 + kTW + 1, dw - 1);
     max_cols = std::max(max_cols, std::min(xofs[hi] + 1, sw - 1) - xofs[lo] + 1);
   }
@@ -2309,6 +2311,203 @@ hipError_t launch_blur_batch(const BlurDesc* desc, const GaussCoef* coef, const 
   if (!desc || !coef || spans.wg[kMaxGeoms] <= 0) return hipErrorInvalidValue;
   for (int g = 0; g < kMaxGeoms; g++) if (spans.per[g] > 0 && (cols.ntx[g] <= 0 || spans.per[g] % cols.ntx[g])) return hipErrorInvalidValue;
   blur_batch_k<><<<dim3((unsigned)spans.wg[kMaxGeoms]), kThreads, 0, s>>>(desc, coef, spans, cols);
+  return hipGetLastError();
+}
+
+// ---- the geoms step for classes off the 4-pixel grid (kernels.hpp: launch_mask_blend_geoms_edge) -------------------------------------------------------------------
+// tile_class_geoms_k, mask_tile_geoms_fmt_k and outside_roi_geoms_fmt_k with the 4-pixel groups of the composite anchored to the frame.  A lane's group at ROI-relative
+// column gx = 128 tbx - (roi.x & 3) + 4 k is three aligned dwords of a frame whose width is a multiple of 4 (two for a YUYV frame), mirrors to an aligned group under
+// a horizontal flip and holds whole YUYV pairs; it may reach up to three columns outside the ROI on either side.  Kernels of their own at the end of the file (the
+// reason is given above mask_geoms_k), launched only for a call that touches such a class.
+namespace {
+// 0xFF in byte j where pixel gx + j of a group lies outside the ROI's columns [0, roi_w): those pixels have mask 255 by definition.  gx >= -3 and gx < roi_w.
+__device__ __forceinline__ uint32_t edge_outside_bytes(int gx, int roi_w) {
+  const int l = max(-gx, 0), r = min(roi_w - gx, 4);                  // the group's pixels inside the ROI are [l, r)
+  return (l ? (1u << (8 * l)) - 1u : 0u) | (r < 4 ? 0xFFFFFFFFu << (8 * r) : 0u);
+}
+// tile_load_blend_operands<true, false, true> for one position's own images (index 0, no stride), every group the tile launch owns: those with a pixel inside the ROI.
+// A filter-off position (sel = 2) has no background; a uniform-0 tile (frame only) still reads the background of a straddling group, whose pixels outside the ROI
+// are the background's.
+__device__ __forceinline__ void tile_load_blend_operands_edge(TileBlendOperands& o, const uint8_t* __restrict__ bg, const uint8_t* __restrict__ frame, int W, Rect4 roi,
+                                                              int tx0, int ty0, int tid, int uniform, bool yin, int sel) {
+  const int take = sel >= 0 ? sel : uniform;
+  const int ly0 = tid / (kTW / 4), gx = tx0 + (tid % (kTW / 4)) * 4;
+  const long pix0 = (long)(roi.y + ty0 + ly0) * W + roi.x + gx;        // frame coordinates: roi.x + gx is a multiple of 4 inside [0, W - 4] for every owned group
+  const int fb = yin ? 2 : 3;
+  const bool straddles = gx < 0 || gx + 3 >= roi.w;
+  const bool need_a = take != 2 || (sel < 0 && straddles), need_b = take != 1;
+  const uint8_t* const a0 = bg + pix0 * 3;
+  const uint8_t* const b0 = frame + pix0 * fb;
+#pragma unroll
+  for (int i = 0; i < kTileItems; i++) {
+    o.a[i][0] = o.a[i][1] = o.a[i][2] = 0;
+    o.b[i][0] = o.b[i][1] = o.b[i][2] = 0;
+    if (ty0 + ly0 + 8 * i < roi.h && gx < roi.w) {                     // (gx + 3 >= 0 always: tx0 >= -3)
+      const uint32_t* ap = reinterpret_cast<const uint32_t*>(a0 + (long)(8 * i) * W * 3);
+      const uint32_t* bp = reinterpret_cast<const uint32_t*>(b0 + (long)(8 * i) * W * fb);
+      if (need_a) { o.a[i][0] = ap[0]; o.a[i][1] = ap[1]; o.a[i][2] = ap[2]; }
+      if (need_b) {
+        o.b[i][0] = __builtin_nontemporal_load(bp); o.b[i][1] = __builtin_nontemporal_load(bp + 1);
+        if (!yin) o.b[i][2] = __builtin_nontemporal_load(bp + 2);
+      }
+    }
+  }
+}
+// tile_vsum5_store<true, false, true> likewise: the mask bytes of the group's pixels outside the ROI become 255 in registers — so the blend gives them the background
+// exactly ((a * 255 + b * 0) / 255 == a) — and only the bytes inside the ROI are stored: the persistent mask outside the ROI stays what reset made it.
+__device__ __forceinline__ void tile_vsum5_store_edge(const uint16_t* hs, uint8_t* __restrict__ mask, uint8_t* __restrict__ outp, const TileBlendOperands& o, int W, int H,
+                                                      Rect4 roi, int tx0, int ty0, int tid, int yuyv_flip, int uniform, int sel) {
+  const int take = sel >= 0 ? sel : uniform;
+  const int ly0 = tid / (kTW / 4), lx = (tid % (kTW / 4)) * 4;
+  const int gx = tx0 + lx;
+  if (gx >= roi.w) return;                                             // a group right of the ROI: the outside launch's
+  const uint32_t outside = edge_outside_bytes(gx, roi.w);
+  const int yuyv = yuyv_flip & 1;
+  const bool fh = (yuyv_flip & 2) != 0, fv = (yuyv_flip & 4) != 0, yin = (yuyv_flip & 16) != 0;
+  const int obpp = yuyv ? 2 : 3;
+  uint8_t* const dst0 = mask + (long)(roi.y + ty0 + ly0) * W + roi.x + gx;
+  const int oy0 = fv ? H - 1 - (roi.y + ty0 + ly0) : roi.y + ty0 + ly0, ox = fh ? W - 4 - (roi.x + gx) : roi.x + gx;
+  const long orow = fv ? -(long)W : (long)W;
+  uint8_t* const out0 = outp + ((long)oy0 * W + ox) * obpp;
+#pragma unroll
+  for (int i = 0; i < kTileItems; i++) {
+    const int ly = ly0 + 8 * i, gy = ty0 + ly;
+    if (gy >= roi.h) continue;
+    uint32_t packed = uniform == 1 ? 0xFFFFFFFFu : 0u;
+    if (!uniform) {
+      uint2 acc = *reinterpret_cast<const uint2*>(&hs[ly * kTW + lx]);
+#pragma unroll
+      for (int r = 1; r < 5; r++) {
+        const uint2 v = *reinterpret_cast<const uint2*>(&hs[(ly + r) * kTW + lx]);
+        acc.x = __builtin_bit_cast(uint32_t, __builtin_bit_cast(us2, acc.x) + __builtin_bit_cast(us2, v.x));
+        acc.y = __builtin_bit_cast(uint32_t, __builtin_bit_cast(us2, acc.y) + __builtin_bit_cast(us2, v.y));
+      }
+      const uint32_t m0 = (__umul24(acc.x & 0xffffu, 5243u) + 12u * 5243u) >> 17, m1 = (__umul24(acc.x >> 16, 5243u) + 12u * 5243u) >> 17;
+      const uint32_t m2 = (__umul24(acc.y & 0xffffu, 5243u) + 12u * 5243u) >> 17, m3 = (__umul24(acc.y >> 16, 5243u) + 12u * 5243u) >> 17;
+      packed = m0 | (m1 << 8) | (m2 << 16) | (m3 << 24);
+    }
+    packed |= outside;
+    uint8_t* dst = dst0 + (long)(8 * i) * W;
+    if (yuyv_flip & 8) { /* composite only (BSX_STEP_NO_MASK) */ }
+    else if (outside == 0 && ((uintptr_t)dst & 3) == 0) *reinterpret_cast<uint32_t*>(dst) = packed;
+    else for (int j = 0; j < 4; j++) if (!((outside >> (8 * j)) & 255u)) dst[j] = (uint8_t)(packed >> (8 * j));
+    uint32_t* op = reinterpret_cast<uint32_t*>(out0 + (long)(8 * i) * orow * obpp);
+    uint32_t o3[3];
+    if (take == 1) { o3[0] = o.a[i][0]; o3[1] = o.a[i][1]; o3[2] = o.a[i][2]; }
+    else if (take == 2 && (sel >= 0 || outside == 0)) tile_frame_bgr(o, i, yin, o3);
+    else { uint32_t b3[3]; tile_frame_bgr(o, i, yin, b3); blend_quad(o.a[i], b3, packed, o3); }      // (a uniform-0 tile's straddling group: packed = outside)
+    if (fh) reverse4px(o3);
+    if (yuyv) {
+      __builtin_nontemporal_store(yuyv_pair(o3[0] & 255u, (o3[0] >> 8) & 255u, (o3[0] >> 16) & 255u, o3[0] >> 24, o3[1] & 255u, (o3[1] >> 8) & 255u), op);
+      __builtin_nontemporal_store(yuyv_pair((o3[1] >> 16) & 255u, o3[1] >> 24, o3[2] & 255u, (o3[2] >> 8) & 255u, (o3[2] >> 16) & 255u, o3[2] >> 24), op + 1);
+    } else {
+      __builtin_nontemporal_store(u3v{o3[0], o3[1], o3[2]}, reinterpret_cast<u3v*>(op));
+    }
+  }
+}
+
+// tile_class_geoms_k over the frame-anchored tile columns: the class byte of the tile mask_tile_geoms_edge_k works on
+template <int = 0>
+__global__ __launch_bounds__(kThreads) void tile_class_geoms_edge_k(const GeomClass* __restrict__ classes, const GeomDesc* __restrict__ desc, GeomSpans sp,
+                                                                   const uint8_t* __restrict__ ofinal, int outW, int outH, uint8_t* __restrict__ tile_class) {
+  const int n = blockIdx.x, g = geom_class_of_position(sp, n);
+  const GeomClass c = classes[g];
+  const int slot = geom_desc(desc, n).slot;
+  uint8_t* const cls = tile_class + sp.wg[g] + (size_t)(n - sp.pos[g]) * (size_t)(c.ntx * c.nty);
+  const ResizeTab tab = geom_tab(c.up);
+  if (c.ntx > kClsMaxTx || tab.sh * c.ntx > kClsMaxItems) {           // out of the classifier's range (launch_tile_class): all general
+    for (int t = threadIdx.x; t < c.ntx * c.nty; t += kThreads) cls[t] = 0;
+    return;
+  }
+  const int tid = threadIdx.x, ntx = c.ntx, nty = c.nty;
+  const Rect4 roi = c.roi;
+#define BSX_CLS_FRAME ofinal + (long)slot * outW * outH + (long)c.in_roi.y * outW + c.in_roi.x
+#define BSX_CLS_BYTE(t) cls[t]
+#define BSX_CLS_SHIFT geom_edge_shift(roi)
+#include "tile_class.inc"
+#undef BSX_CLS_FRAME
+#undef BSX_CLS_BYTE
+#undef BSX_CLS_SHIFT
+}
+
+// mask_tile_geoms_fmt_k with tx0 = 128 tbx - (roi.x & 3) and the *_edge operands and stores: uniform-tile branch and mask_tile.inc once per format
+template <int = 0>
+__global__ __launch_bounds__(kThreads) void mask_tile_geoms_edge_k(const GeomClass* __restrict__ classes, const GeomDesc* __restrict__ desc, GeomSpans sp, unsigned xcd_mask,
+                                                                  const uint8_t* __restrict__ ofinal, int outW, int outH, const uint8_t* __restrict__ tile_class, int flags) {
+  __shared__ short col_c0[kHW], col_c1[kHW], col_a0[kHW], col_a1[kHW];
+  __shared__ short row_r0[kHH], row_r1[kHH], row_b0[kHH], row_b1[kHH];
+  __shared__ __attribute__((aligned(16))) uint16_t hq_hs[kMaxSrcRows * kHW > kHH * kTW ? kMaxSrcRows * kHW : kHH * kTW];
+  __shared__ __attribute__((aligned(16))) uint8_t up[kHH * kHW + 8];
+  uint16_t* const hq = hq_hs;
+  uint16_t* const hs = hq_hs;
+  uint8_t* const blk = up;
+  const int tid = threadIdx.x;
+  int g, w0, p0, p1, per;
+  geom_span(sp, (int)blockIdx.x, &g, &w0, &p0, &p1, &per);
+  unsigned f_, t_;
+  xcd_frame_tile_at(blockIdx.x - (unsigned)w0, (unsigned)per, ((xcd_mask >> g) & 1u) ? (unsigned)(p1 - p0) : 0u, &f_, &t_);
+  const int n = p0 + (int)f_;                                          // the position (descriptor index)
+  int uniform = 0;
+  if (tile_class) uniform = tile_class_byte((uintptr_t)tile_class + (size_t)w0 + (size_t)f_ * (size_t)per + (size_t)t_);
+  const GeomClass c = classes[g];
+  const GeomDescRegs d = geom_desc(desc, n);
+  const int W = c.W, H = c.H;
+  const Rect4 roi = c.roi, q = c.in_roi;
+  const ResizeTab tab = geom_tab(c.up);
+  const int tby = (int)t_ / c.ntx, tbx = (int)t_ - tby * c.ntx, tx0 = tbx * kTW - geom_edge_shift(roi), ty0 = tby * kTH;
+  flags = (flags & ~16) | (int)(d.flags & (kMixFlipH | kMixFlipV));
+  const int sel = (d.flags & kMixFilterOff) ? 2 : -1;
+  TileBlendOperands ops;
+  const uint8_t *const bg = d.bg, *const frames = d.frame;
+  uint8_t *const mask = d.mask, *const outp = d.out;
+#define BSX_MT_EDGE
+#define BSX_MT_SLOT d.slot
+#define BSX_MT_POSITION                                                                            \
+    if (uniform) {                                                                                 \
+      tile_load_blend_operands_edge(ops, bg, frames, W, roi, tx0, ty0, tid, uniform, yin, sel);    \
+      tile_vsum5_store_edge(hq_hs, mask, outp, ops, W, H, roi, tx0, ty0, tid, yuyv, uniform, sel); \
+      return;                                                                                      \
+    }
+  if (d.flags & kGeomYuyvIn) {
+    constexpr bool yin = true;
+    const int yuyv = flags | 16;                                       // bit 4: the frame operand arrives as YUYV (tile_vsum5_store_edge)
+    BSX_MT_POSITION
+#include "mask_tile.inc"
+  } else {
+    constexpr bool yin = false;
+    const int yuyv = flags;
+    BSX_MT_POSITION
+#include "mask_tile.inc"
+  }
+#undef BSX_MT_POSITION
+#undef BSX_MT_SLOT
+#undef BSX_MT_EDGE
+}
+
+// outside_roi_geoms_fmt_k for the groups wholly outside the ROI
+template <int = 0>
+__global__ __launch_bounds__(kThreads) void outside_roi_geoms_edge_k(const GeomClass* __restrict__ classes, const GeomDesc* __restrict__ desc, GeomSpans sp, int flags) {
+  int g, w0, p0, p1, per;
+  geom_span(sp, (int)blockIdx.x, &g, &w0, &p0, &p1, &per);
+  const unsigned local = blockIdx.x - (unsigned)w0, pl = local / (unsigned)per, blk = local - pl * (unsigned)per;
+  const GeomClass c = classes[g];
+  const GeomDescRegs d = geom_desc(desc, p0 + (int)pl);
+  outside_mixed_group<true>(blk * kThreads + threadIdx.x, d.bg, d.flags, d.frame, d.out, c.W, c.H, c.roi, (flags & ~16) | ((d.flags & kGeomYuyvIn) ? 16 : 0));
+}
+}  // namespace
+
+int geom_tile_cols(const Rect4& roi, bool edge) { return ((edge ? geom_edge_shift(roi) : 0) + roi.w + kTW - 1) / kTW; }
+bool geom_class_edge_fusable(int W, const Rect4& roi, const ResizeTab& up, bool shifted_tiles_fit) {
+  return (W % 4) == 0 && roi.w >= 8 && mask_tile_usable(up) && shifted_tiles_fit;      // (roi.w >= 8: the halo at column -5 reflects inside the ROI)
+}
+
+hipError_t launch_mask_blend_geoms_edge(const GeomClass* classes, const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const GeomSpans& outside,
+                                        const uint8_t* ofinal, int outW, int outH, uint8_t* tile_class, int n, hipStream_t s, int flags) {
+  flags &= 1 | 8;
+  if (n <= 0 || tiles.wg[kMaxGeoms] <= 0) return hipErrorInvalidValue;
+  if (outside.wg[kMaxGeoms] > 0) outside_roi_geoms_edge_k<><<<dim3((unsigned)outside.wg[kMaxGeoms]), kThreads, 0, s>>>(classes, desc, outside, flags);
+  if (tile_class) tile_class_geoms_edge_k<><<<dim3((unsigned)n), kThreads, 0, s>>>(classes, desc, tiles, ofinal, outW, outH, tile_class);
+  mask_tile_geoms_edge_k<><<<dim3((unsigned)tiles.wg[kMaxGeoms]), kThreads, 0, s>>>(classes, desc, tiles, xcd_mask, ofinal, outW, outH, tile_class, flags);
   return hipGetLastError();
 }
 

@@ -5,6 +5,9 @@
 // row_b0, row_b1, hq, hs, up, blk; and three expressions: BSX_MT_FRAME, the index of the frame inside `frames` / `outp`; BSX_MT_SLOT, the frame's state slot
 // inside `ofinal` — evaluated where `ms` is formed, behind the four table reads; and BSX_MT_MASK_SLOT, the index of the frame's mask inside `mask` — expanded
 // behind `const int ms`, the slot formed from BSX_MT_SLOT, which it may name.
+// With BSX_MT_EDGE defined (mask_tile_geoms_edge_k: a class whose ROI is off the 4-pixel grid) the tile's columns are anchored to the frame's 4-pixel groups: tx0 =
+// 128 tbx - (roi.x & 3), so the first tile starts up to three columns LEFT of the ROI (its halo at -5 reflects at the ROI's bound like every halo column), and the
+// composite's operands and stores are the *_edge forms, which own every group that intersects the ROI.  Positions are then single images: bg_stride 0, index 0.
   // extents of the source block: xofs / yofs are monotonic, so the extreme destination rows / columns give them
   // (requesting these four scalar table reads together with the class byte — one scalar round trip instead of two in front of the general path — measured: no
   //  difference on any configuration, profiles/r05e)
@@ -30,7 +33,11 @@
     t_s = tab.yofs[gy]; t_a0 = tab.ya[2 * gy]; t_a1 = tab.ya[2 * gy + 1];
   }
   // (c) composite operands (a shared background requested early is already on its way)
+#ifdef BSX_MT_EDGE
+  tile_load_blend_operands_edge(ops, bg, frames, W, roi, tx0, ty0, tid, 0, yin, sel);
+#else
   tile_load_blend_operands<BLEND, WH, MIX>(ops, bg, bg_stride, frames, BSX_MT_FRAME, W, H, roi, tx0, ty0, tid, 0, early_bg ? 2 : 3, yin, sel);
+#endif
   // 1. block and tables into LDS
 #pragma unroll
   for (int j = 0; j < 3; j++) if (br + 4 * j < nsr && bc < ncol) blk[(br + 4 * j) * ncol + bc] = (uint8_t)raw[j];
@@ -58,4 +65,8 @@
   __syncthreads();
   tile_hsum5(up, hs, tid);                                                                       // 4.
   __syncthreads();
+#ifdef BSX_MT_EDGE
+  tile_vsum5_store_edge(hs, mask, outp, ops, W, H, roi, tx0, ty0, tid, yuyv, 0, sel);                                                // 5.
+#else
   tile_vsum5_store<BLEND, WH, MIX>(hs, mask, outp, ops, BSX_MT_FRAME, BSX_MT_MASK_SLOT, W, H, roi, tx0, ty0, tid, yuyv, 0, sel);   // 5.
+#endif

@@ -1,10 +1,16 @@
 // tile_class.inc — the body of tile_class_k (kernels_img.hip), included by the kernel itself and by tile_class_geoms_k (the per-position form of
 // bsx_step_batch_geoms); an include for the reason prep_tile.inc is one.  The includer provides tid, outW, tab, roi, ntx, nty and two expressions: BSX_CLS_FRAME,
-// the frame's model-resolution state at in_roi's origin, and BSX_CLS_BYTE(t), the class byte of its tile t.
+// the frame's model-resolution state at in_roi's origin, and BSX_CLS_BYTE(t), the class byte of its tile t; optionally BSX_CLS_SHIFT, the columns (0-3) by which the
+// first tile column starts left of the ROI.
   __shared__ uint8_t f255[kClsMaxItems], f0[kClsMaxItems];
   __shared__ int cmn[kClsMaxTx], cmx[kClsMaxTx];
   if (tid < ntx) {
-    const int tx0 = tid * kTW, gx_lo = max(tx0 - 2, 0), gx_hi = min(tx0 + kTW + 1, roi.w - 1);
+#ifdef BSX_CLS_SHIFT                       /* tile columns anchored to the frame's 4-pixel groups (tile_class_geoms_edge_k): the tile mask_tile.inc works on */
+    const int tx0 = tid * kTW - (BSX_CLS_SHIFT);
+#else
+    const int tx0 = tid * kTW;
+#endif
+    const int gx_lo = max(tx0 - 2, 0), gx_hi = min(tx0 + kTW + 1, roi.w - 1);
     cmn[tid] = tab.xofs[gx_lo]; cmx[tid] = min(tab.xofs[gx_hi] + 1, tab.sw - 1);
   }
   __syncthreads();

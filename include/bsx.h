@@ -24,6 +24,7 @@
  *   bsx_step_batch_mixed   … with each stream's own settings: -b / -p bgblur / -H / -V and the s / h / v keys  app/deepseg.cc:387-437, 596-673, 777-790
  *   bsx_step_batch_vcam_mixed  … both: each stream's own settings, written at the virtual camera's geometry  app/deepseg.cc:387-437, 634-681
  *   bsx_new_geoms          bs_maskgen_new() for cameras of several capture sizes in ONE context  lib/libbackscrub.cc:161-259 (the ROIs of :234-246 once per size)
+ *   bsx_new_geoms_ex       … with creation flags: BSX_GEOMS_EDGE_ROI admits sizes whose ROI is off the 4-pixel grid (segm_lite at 1920x1080)  lib/libbackscrub.cc:234-246
  *   bsx_step_batch_geoms   … for streams of different capture sizes together: one prep launch, one network pass, one tile launch  app/deepseg.cc:634-673
  *   bsx_step_batch_vcam_geoms  … the same streams, every composite written at the virtual camera's one size  app/deepseg.cc:634-681
  *   bsx_reset_streams      bsx_reset for a chosen subset of the streams (a slot reused for a new camera)
@@ -245,7 +246,8 @@ BSX_API int bsx_step_batch_mixed(bsx_ctx* ctx, const int* ids, const uint8_t* d_
  *     [1, BSX_MAX_GEOMS]; a non-positive size or stream count; two classes of the same size; more than 65535 streams in total; an onmask callback with more than one
  *     class; and, with more than one class, a class the fused tile route does not take (width, roi.x and roi.w multiples of 4 and a tiled linear mask up-scale: the rule
  *     bsx_step_batch_mixed applies per call, applied at creation).  With segm_lite (160 x 96, its ratio held as a float) the reference's ROI arithmetic gives some
- *     16:9 sizes a ROI width that is no multiple of 4 — 1920x1080 -> 1799, 960x540 -> 899, 848x480 -> 799 — and those are refused; 1280x720 and 640x360 are fine;
+ *     16:9 sizes a ROI width that is no multiple of 4 — 1920x1080 -> 1799, 960x540 -> 899, 848x480 -> 799 — and those are refused; 1280x720 and 640x360 are fine
+ *     (bsx_new_geoms_ex with BSX_GEOMS_EDGE_ROI, below, takes them);
  *   - on a context of more than one class these work: bsx_step_batch_geoms, bsx_step_batch_vcam_geoms, bsx_reset, bsx_reset_streams, bsx_get_info (class 0's
  *     geometry, the total n_streams), bsx_geom_count / bsx_get_geom_info, bsx_masks_device, bsx_last_error, bsx_delete, bsx_plan_describe, bsx_debug_buffer (0-2 as always; 3 = the whole mask
  *     allocation), bsx_debug_tensor*, and everything that takes its own w, h (bsx_resize_bgr*, bsx_bgr_to_yuyv, bsx_yuyv_to_bgr, bsx_flip_bgr, bsx_gaussian_blur_bgr,
@@ -256,6 +258,20 @@ BSX_API int bsx_step_batch_mixed(bsx_ctx* ctx, const int* ids, const uint8_t* d_
 typedef struct bsx_geometry { int width, height, n_streams; } bsx_geometry;
 BSX_API bsx_ctx* bsx_new_geoms(const char* model_path, size_t threads, const bsx_geometry* geoms, int n_geoms, int device,
                                bsx_debug_fn ondebug, bsx_stage_fn onprep, bsx_stage_fn oninfer, bsx_stage_fn onmask, void* caller_ctx);
+
+/* bsx_new_geoms with creation flags.  flags == 0 IS bsx_new_geoms; a bit that is not listed here returns NULL with a message that names the bit.
+ *   BSX_GEOMS_EDGE_ROI  take classes whose ROI is off the 4-pixel grid: for any n_geoms from 1 up a class is admitted when its width is a multiple of 4 and its mask
+ *     up-scale is the tiled linear one; roi.x and roi.w are free (segm_lite at 1920x1080, 960x540, 848x480 and 1600x900, MLKit at 960x540 and 1600x900).  Still
+ *     refused, with the class index, its size and the value: a width that is no multiple of 4 (a row would not be whole dwords), and a class without the tiled
+ *     up-scale.  On such a context bsx_step_batch_geoms and bsx_step_batch_vcam_geoms take streams of those classes under all their other rules (4-byte aligned
+ *     d_frame / d_out / d_bg, no overlap, no blur bit, no onmask; a BSX_STREAM_YUYV_IN item still needs an even roi.x and a proper INTER_LINEAR down-scale, so
+ *     1920x1080 lite passes and a class with an odd roi.x is refused per item), with what they always compute: per stream byte-identical to
+ *     bsx_step_batch_streams of that stream in a one-geometry context of its size.  The launch count is unchanged; a call that touches such a class runs kernels
+ *     that anchor the composite's 4-pixel groups to the frame, a call that touches none runs exactly what it runs on a bsx_new_geoms context.  Every other entry
+ *     point behaves as on any context of that class count (bsx_step_batch_mixed keeps refusing a ROI off the grid). */
+#define BSX_GEOMS_EDGE_ROI 1u
+BSX_API bsx_ctx* bsx_new_geoms_ex(const char* model_path, size_t threads, const bsx_geometry* geoms, int n_geoms, int device, unsigned flags,
+                                  bsx_debug_fn ondebug, bsx_stage_fn onprep, bsx_stage_fn oninfer, bsx_stage_fn onmask, void* caller_ctx);
 
 /* The classes of a context (1 for one made by bsx_new) and the geometry of class g.  The persistent mask of stream s of class g is
  * bsx_masks_device() + mask_offset + (s - first_stream) * width * height. */
