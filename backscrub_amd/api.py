@@ -26,6 +26,8 @@ STAGE_FN = C.CFUNCTYPE(None, C.c_void_p)
 
 BSX_STREAM_FILTER_OFF = 32          # bsx.h: bits of bsx_stream_setting.flags next to the flip bits and the blur size
 BSX_STREAM_YUYV_IN = 64             # ... in an item of step_geoms / step_vcam_geoms only: that item's frame is YUYV 4:2:2
+BSX_MAX_OUT_SIZES = 4               # bsx.h: distinct output sizes of one bsx_step_batch_vcam_geoms_outs call
+BSX_MAX_OUTS_PER_ITEM = 4           # ... and output records that may name one item
 BSX_GEOMS_EDGE_ROI = 1              # bsx.h: creation flag of bsx_new_geoms_ex (MaskGen.with_geometries(edge_roi=True))
 
 
@@ -68,6 +70,10 @@ class _GeomInfo(C.Structure):               # bsx.h bsx_geom_info
 
 class _GeomItem(C.Structure):               # bsx.h bsx_geom_item
     _fields_ = [("d_frame", C.c_void_p), ("d_out", C.c_void_p), ("setting", _StreamSetting)]
+
+
+class _VcamOut(C.Structure):                # bsx.h bsx_vcam_out
+    _fields_ = [("item", C.c_int), ("out_w", C.c_int), ("out_h", C.c_int), ("d_out", C.c_void_p)]
 
 
 class StreamSetting:
@@ -120,6 +126,7 @@ SYMBOLS = [
     ("bsx_get_geom_info", C.c_int, [C.c_void_p, C.c_int, C.POINTER(_GeomInfo)]),
     ("bsx_step_batch_geoms", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(_GeomItem), C.c_int, C.c_void_p, C.c_uint]),
     ("bsx_step_batch_vcam_geoms", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(_GeomItem), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint]),
+    ("bsx_step_batch_vcam_geoms_outs", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(_GeomItem), C.c_int, C.POINTER(_VcamOut), C.c_int, C.c_void_p, C.c_uint]),
     ("bsx_step_batch_mixed", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(_StreamSetting), C.c_void_p, C.c_int, C.c_void_p, C.c_uint]),
     ("bsx_step_batch_vcam_mixed", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(_StreamSetting), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                             C.c_uint]),
@@ -371,6 +378,64 @@ class MaskGen:
             items[i].setting.flags = s.flags()
         _check(lib().bsx_step_batch_vcam_geoms(self.h, arr, items, n, out_w, out_h, _stream_ptr(), 1 if yuyv else 0), self.h, "bsx_step_batch_vcam_geoms")
         return outs
+
+    def step_vcam_geoms_outs(self, ids, frames, settings, outs, yuyv=False):
+        """step_vcam_geoms with several outputs per stream, each of its own size (bsx_step_batch_vcam_geoms_outs): outs is a sequence of (item_index, tensor) —
+        write the composite of position item_index at the tensor's size, a cuda uint8 [out_h, out_w, 3] (or [.., 2] with yuyv).  A position may be named by 0 to 4
+        records (with none its stream still advances), a call uses at most 4 distinct sizes.  Every stream is filtered once; one resize pass writes every record."""
+        torch = _torch()
+        arr, n = _ids(ids)
+        frames, settings, outs = list(frames), list(settings), list(outs)
+        if len(frames) != n or len(settings) != n:
+            raise BsxError("%d ids for %d frames and %d settings" % (n, len(frames), len(settings)))
+        items = (_GeomItem * max(n, 1))()
+        ch = 2 if yuyv else 3
+
+        def ok(t, shape):
+            return isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and self._on_device(t) and tuple(t.shape) == shape and t.is_contiguous()
+        for i in range(n):
+            g = self._geom_of(int(arr[i]))
+            H, W = g["height"], g["width"]
+            s = settings[i]
+            fch = 2 if isinstance(s, StreamSetting) and s.yuyv_in else 3      # the item's own pixel format: YUYV 4:2:2 or BGR
+            if not ok(frames[i], (H, W, fch)):
+                raise BsxFrameFormatError("frames[%d] must be a contiguous cuda:%d uint8 tensor [%d,%d,%d] (stream %d%s)" % (
+                    i, self.device, H, W, fch, arr[i], ", a YUYV item" if fch == 2 else ""))
+            if not isinstance(s, StreamSetting):
+                raise BsxError("settings[%d] is not a StreamSetting" % i)
+            if s.bgblur:
+                raise BsxError("settings[%d]: bgblur is not taken by step_vcam_geoms_outs" % i)
+            if not s.filter_off and s.bg is None:
+                raise BsxError("settings[%d]: bg is required unless filter_off is set" % i)
+            if s.bg is not None and not ok(s.bg, (H, W, 3)):
+                raise BsxError("settings[%d].bg must be a contiguous cuda:%d uint8 tensor [%d,%d,3] (stream %d)" % (i, self.device, H, W, arr[i]))
+            items[i].d_frame, items[i].d_out = frames[i].data_ptr(), None
+            items[i].setting.d_bg = s.bg.data_ptr() if s.bg is not None else None
+            items[i].setting.flags = s.flags()
+        m = len(outs)
+        recs = (_VcamOut * max(m, 1))()
+        named, sizes = {}, []
+        for j, rec in enumerate(outs):
+            if not isinstance(rec, (tuple, list)) or len(rec) != 2:
+                raise BsxError("outs[%d] must be a pair (item_index, tensor)" % j)
+            item, t = rec
+            if isinstance(item, bool) or not isinstance(item, (int, np.integer)) or not 0 <= int(item) < n:
+                raise BsxError("outs[%d]: item %r is not an index into the call's %d positions" % (j, item, n))
+            if not isinstance(t, torch.Tensor) or t.dim() != 3 or not ok(t, (int(t.shape[0]), int(t.shape[1]), ch)) or t.numel() == 0:
+                raise BsxError("outs[%d]: the output must be a contiguous, non-empty cuda:%d uint8 tensor [out_h,out_w,%d]" % (j, self.device, ch))
+            oh, ow = int(t.shape[0]), int(t.shape[1])
+            if yuyv and (ow & 1):
+                raise BsxError("outs[%d]: YUYV output needs an even width (the tensor is %d wide)" % (j, ow))
+            named[int(item)] = named.get(int(item), 0) + 1
+            if named[int(item)] > BSX_MAX_OUTS_PER_ITEM:
+                raise BsxError("outs[%d]: record %d of position %d (at most %d name one position)" % (j, named[int(item)], int(item), BSX_MAX_OUTS_PER_ITEM))
+            if (ow, oh) not in sizes:
+                sizes.append((ow, oh))
+                if len(sizes) > BSX_MAX_OUT_SIZES:
+                    raise BsxError("outs[%d]: %d x %d is distinct output size %d of the call (at most %d)" % (j, ow, oh, len(sizes), BSX_MAX_OUT_SIZES))
+            recs[j].item, recs[j].out_w, recs[j].out_h, recs[j].d_out = int(item), ow, oh, t.data_ptr()
+        _check(lib().bsx_step_batch_vcam_geoms_outs(self.h, arr, items, n, recs, m, _stream_ptr(), 1 if yuyv else 0), self.h, "bsx_step_batch_vcam_geoms_outs")
+        return [t for _i, t in outs]
 
     # ---- batched device path -----------------------------------------------------------------
     def process_batch(self, frames, masks_out=None):

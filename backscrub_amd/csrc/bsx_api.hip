@@ -27,6 +27,7 @@
 #include "rtc.hpp"
 #include "specialised.hpp"
 #include "tflite_model.hpp"
+#include "vcam_outs_plan.hpp"
 
 using namespace bsx;
 
@@ -222,8 +223,15 @@ struct bsx_ctx {
   std::vector<int> geo_order, geo_ids;      // host scratch: the call's positions ordered by class, their stream ids in that order
   // bsx_step_batch_vcam_geoms: per output size the device array of one VgClass per class (kernels.hpp) — capture size, capture -> output table, per-tap bit — built
   // and uploaded on the first call at that size.  Class 0's table is the one in vcam_tabs (shared with bsx_step_batch_vcam); the others' memory is owned here.
-  struct VgGeoms { VgClass* d_rec = nullptr; std::vector<void*> mem; };
+  struct VgGeoms { VgClass* d_rec = nullptr; std::vector<void*> mem; std::vector<VgClass> h_rec; };      // h_rec: the host's copy (bsx_step_batch_vcam_geoms_outs stages group records from it)
   std::map<std::pair<int, int>, VgGeoms> vg_geoms;
+  // bsx_step_batch_vcam_geoms_outs: per ring entry (the same entries and events as the ids) the call's group records — kMaxOutGroups VgOutGroup — then its output
+  // descriptors, at most BSX_MAX_OUTS_PER_ITEM * n_streams GeomDesc in group order, built in the pinned entry and copied to the device entry in one hipMemcpyAsync.
+  // Allocated on the first call of that entry point.
+  uint8_t* h_vo = nullptr;                  // pinned [kIdRing][vo_entry_bytes()]
+  uint8_t* d_vo = nullptr;                  // device, likewise
+  size_t vo_entry_bytes() const { return (size_t)kMaxOutGroups * sizeof(VgOutGroup) + (size_t)BSX_MAX_OUTS_PER_ITEM * (size_t)n_streams * sizeof(GeomDesc); }
+  std::vector<int> vo_class, vo_pos;        // host scratch: the class of each item, the position (place in the class-ordered descriptors) of each item
   int geom_of(int stream) const { int g = 0; while (g + 1 < (int)geoms.size() && stream >= geoms[g + 1].first) g++; return g; }
   bool act16 = false;                  // BSX_ACT16=1: 16-bit activation STORAGE for the segmented Meet / MLKit networks (g1) — opt-in, IoU-gated; needs the specialised middle kernel
 
@@ -1353,7 +1361,7 @@ int vcam_geoms_check(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_
 }
 
 // the class records of (out_w, out_h), built and uploaded on the first call at that size
-int vg_geoms_records(bsx_ctx* c, int out_w, int out_h, const VgClass** out) {
+int vg_geoms_records(bsx_ctx* c, int out_w, int out_h, const VgClass** out, const VgClass** host = nullptr) {
   const auto key = std::make_pair(out_w, out_h);
   auto it = c->vg_geoms.find(key);
   if (it == c->vg_geoms.end()) {
@@ -1377,9 +1385,11 @@ int vg_geoms_records(bsx_ctx* c, int out_w, int out_h, const VgClass** out) {
       if (c->last_error.empty()) c->last_error = "error: bsx_step_batch_vcam_geoms: the class records could not be uploaded\n";
       return rc;
     }
+    v.h_rec = std::move(rec);
     it = c->vg_geoms.emplace(key, std::move(v)).first;
   }
   *out = it->second.d_rec;
+  if (host) *host = it->second.h_rec.data();
   return BSX_OK;
 }
 
@@ -1393,6 +1403,98 @@ int vcam_geoms_run(bsx_ctx* c, const int* ids, const bsx_geom_item* items, int n
   if (const int rc = geoms_front(c, fn, ids, items, n, s, k, &st, true)) return rc;
   bsx_roctx::Range range("bsx:mask+vcam");
   BSX_HIP(c, (st.fmt ? launch_vcam_geoms_fmt : launch_vcam_geoms)(c->d_geom_classes_vg ? c->d_geom_classes_vg : c->d_geom_classes, vg, st.desc, st.tiles, st.xcd_mask, c->d_ofinal, c->outW, c->outH, c->d_geom_tile_class, out_w, out_h, n, s, flags & 1u));
+  return BSX_OK;
+}
+
+// ---- bsx_step_batch_vcam_geoms_outs: the vcam geoms step with several outputs per position, each of its own size -----------------------------------------------
+// vcam_geoms_run's shape: the same front, then [one tile-class launch,] ONE masks-only tile launch and ONE resize pass whose grid ranges over the output records
+// (vcam_outs_plan.hpp orders them into (class, size) groups).  The item checks are vcam_geoms_check's without d_out, which this entry point does not read.
+int vcam_outs_check(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item* items, int n, const bsx_vcam_out* outs, int m, unsigned flags, VcamOutsPlan* plan) {
+  if (!items) return refuse(c, fn, "items is NULL");
+  if (flags & BSX_STEP_NO_MASK) return refuse(c, fn, "unsupported flags 0x%x (the no-mask step has no vcam form)", flags);
+  if (flags & BSX_STEP_YUYV_IN) return refuse(c, fn, "flags 0x%x: YUYV input frames are not taken by the multi-geometry step as a batch flag (the format belongs to the item: the yuyv-in bit, 0x40, of items[i].setting.flags)", flags);
+  if (flags & ~BSX_STEP_YUYV) return refuse(c, fn, "flags 0x%x has bits outside yuyv", flags);
+  if (const int rc = refuse_pending(c, fn)) return rc;
+  if (c->onmask) return refuse(c, fn, "needs the fused mask route (no onmask callback)");
+  const bool yuyv = (flags & BSX_STEP_YUYV) != 0;
+  std::vector<bsx_ctx::Span>& sp = c->rsz_spans;
+  sp.clear();
+  c->vo_class.resize((size_t)n);
+  for (int i = 0; i < n; i++) {
+    const bsx_geom_item& it = items[i];
+    const int g = c->geom_of(ids[i]);
+    const bsx_ctx::Geom& G = c->geoms[g];
+    const unsigned f = it.setting.flags;
+    c->vo_class[(size_t)i] = g;
+    if (f & 0xFF00u) return refuse(c, fn, "items[%d]: setting flags 0x%x asks for a background blur, which the multi-geometry step does not take", i, f);
+    if (f & ~kGeomStreamFlags) return refuse(c, fn, "items[%d]: setting flags 0x%x has bits outside flip / filter-off / yuyv-in", i, f);
+    if (!it.d_frame) return refuse(c, fn, "items[%d]: d_frame is NULL", i);
+    if ((uintptr_t)it.d_frame & 3) return refuse(c, fn, "items[%d]: d_frame %p is not 4-byte aligned", i, (const void*)it.d_frame);
+    if (!G.fusable)
+      return refuse(c, fn, "items[%d]: stream %d is of class %d (%d x %d), which is off the fused tile route (width, roi.x, roi.w multiples of 4, a tiled linear mask up-scale)",
+                    i, ids[i], g, G.width, G.height);
+    if (f & BSX_STREAM_YUYV_IN) if (const int rc = geoms_yuyv_item(c, fn, i, ids[i], g, G)) return rc;
+    const size_t px = (size_t)G.width * G.height;
+    sp.push_back({(uintptr_t)it.d_frame, (uintptr_t)it.d_frame + px * ((f & BSX_STREAM_YUYV_IN) ? 2 : 3), i, false});      // the frame's real extent
+    if (f & BSX_STREAM_FILTER_OFF) continue;                          // reads no background
+    if (!it.setting.d_bg) return refuse(c, fn, "items[%d]: setting.d_bg is NULL", i);
+    if ((uintptr_t)it.setting.d_bg & 3) return refuse(c, fn, "items[%d]: setting.d_bg %p is not 4-byte aligned", i, (const void*)it.setting.d_bg);
+    sp.push_back({(uintptr_t)it.setting.d_bg, (uintptr_t)it.setting.d_bg + px * 3, i, false});
+  }
+  const int pr = vcam_outs_plan(c->vo_class.data(), n, outs, m, yuyv, plan);
+  if (pr == VcamOutsPlan::kRefused) return refuse(c, fn, "%s", plan->text);
+  if (pr == VcamOutsPlan::kTooLarge) { c->last_error = std::string("error: ") + fn + ": the batch needs more than 2^31 workgroups\n"; return BSX_EDEVICE; }
+  for (int j = 0; j < m; j++)
+    sp.push_back({(uintptr_t)outs[j].d_out, (uintptr_t)outs[j].d_out + (size_t)outs[j].out_w * outs[j].out_h * (yuyv ? 2 : 3), j, true});
+  const bsx_ctx::Span* d = nullptr;
+  const bsx_ctx::Span* o = nullptr;
+  if (spans_overlap(sp, &d, &o))
+    return refuse(c, fn, "outs[%d]: d_out %p overlaps %s[%d] (%p)", d->item, (const void*)d->begin, o->dst ? "the output of outs" : "a frame or background of items", o->item,
+                  (const void*)o->begin);
+  return BSX_OK;
+}
+
+int vcam_outs_run(bsx_ctx* c, const int* ids, const bsx_geom_item* items, int n, const bsx_vcam_out* outs, const VcamOutsPlan& plan, hipStream_t s, unsigned flags, int k) {
+  const char* fn = "bsx_step_batch_vcam_geoms_outs";
+  const size_t eb = c->vo_entry_bytes(), m = plan.order.size();
+  if (!c->h_vo) BSX_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_vo), bsx_ctx::kIdRing * eb, hipHostMallocDefault));
+  if (!c->d_vo) BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_vo), bsx_ctx::kIdRing * eb));
+  // the class records of every size of the call, from the per-size cache (built and uploaded on the first call at a size)
+  const VgClass* rec[kVoMaxSizes] = {};
+  for (int q = 0; q < plan.n_sizes; q++) {
+    const VgClass* dev = nullptr;
+    if (const int rc = vg_geoms_records(c, plan.sizes[q][0], plan.sizes[q][1], &dev, &rec[q])) return rc;
+  }
+  GeomsStaged st;
+  if (const int rc = geoms_front(c, fn, ids, items, n, s, k, &st, true)) return rc;
+  // groups and output descriptors into ring entry k: a record's descriptor is its position's (geoms_front left them in the pinned entry) with `out` replaced
+  VgOutGroup* const hg = reinterpret_cast<VgOutGroup*>(c->h_vo + (size_t)k * eb);
+  GeomDesc* const ho = reinterpret_cast<GeomDesc*>(hg + kMaxOutGroups);
+  const GeomDesc* const hd = c->h_geo + (size_t)k * c->n_streams;
+  c->vo_pos.resize((size_t)n);
+  for (int j = 0; j < n; j++) c->vo_pos[(size_t)c->geo_order[(size_t)j]] = j;
+  OutSpans sp{};
+  sp.ng = (int)plan.groups.size();
+  const unsigned yuyv = flags & 1u;
+  for (int g = 0; g < kMaxOutGroups; g++) {
+    sp.wg[g] = (int)plan.total_wg;
+    if (g >= sp.ng) { hg[g] = VgOutGroup{}; continue; }
+    const VcamOutsGroup& G = plan.groups[(size_t)g];
+    sp.wg[g] = (int)G.wg0; sp.rec[g] = G.first; sp.per[g] = G.per;
+    hg[g] = VgOutGroup{rec[G.size][G.cls], G.ntx, (int)yuyv | (G.words ? 16 : 0), {0, 0}};
+  }
+  sp.wg[kMaxOutGroups] = (int)plan.total_wg;
+  for (size_t q = 0; q < m; q++) {
+    const bsx_vcam_out& o = outs[plan.order[q]];
+    ho[q] = hd[c->vo_pos[(size_t)o.item]];
+    ho[q].out = o.d_out;
+  }
+  uint8_t* const dv = c->d_vo + (size_t)k * eb;
+  if (m) BSX_HIP(c, hipMemcpyAsync(dv, hg, (size_t)kMaxOutGroups * sizeof(VgOutGroup) + m * sizeof(GeomDesc), hipMemcpyHostToDevice, s));
+  bsx_roctx::Range range("bsx:mask+vcam");
+  BSX_HIP(c, launch_vcam_geoms_outs(c->d_geom_classes_vg ? c->d_geom_classes_vg : c->d_geom_classes, reinterpret_cast<const VgOutGroup*>(dv),
+                                    reinterpret_cast<const GeomDesc*>(dv + (size_t)kMaxOutGroups * sizeof(VgOutGroup)), sp, st.desc, st.tiles, st.xcd_mask, c->d_ofinal,
+                                    c->outW, c->outH, c->d_geom_tile_class, n, s, st.fmt));
   return BSX_OK;
 }
 
@@ -1684,6 +1786,8 @@ void bsx_delete(bsx_ctx* c) {
   if (c->d_geom_classes_vg) (void)hipFree(c->d_geom_classes_vg);
   if (c->d_geom_tile_class) (void)hipFree(c->d_geom_tile_class);
   if (c->d_geo) (void)hipFree(c->d_geo);
+  if (c->d_vo) (void)hipFree(c->d_vo);
+  if (c->h_vo) (void)hipHostFree(c->h_vo);
   if (c->h_geo) (void)hipHostFree(c->h_geo);
   delete c;
 }
@@ -1837,6 +1941,22 @@ int bsx_step_batch_vcam_geoms(bsx_ctx* c, const int* ids, const bsx_geom_item* i
   int entry = 0;
   if (const int rc = ring_acquire(c, &entry)) return rc;
   return ids_release(c, entry, s, vcam_geoms_run(c, ids, items, n, out_w, out_h, s, flags, entry));
+}
+
+// bsx_step_batch_vcam_geoms with several outputs per position, each of its own size; see bsx.h
+int bsx_step_batch_vcam_geoms_outs(bsx_ctx* c, const int* ids, const bsx_geom_item* items, int n, const bsx_vcam_out* outs, int m, void* stream, unsigned flags) {
+  const char* fn = "bsx_step_batch_vcam_geoms_outs";
+  if (!c) return BSX_EINVAL;
+  if (const int rc = ids_check(c, fn, ids, n)) return rc;
+  if (n == 0) return refuse_pending(c, fn);
+  VcamOutsPlan plan;
+  if (const int rc = vcam_outs_check(c, fn, ids, items, n, outs, m, flags, &plan)) return rc;
+  DeviceGuard guard(c->device);
+  hipStream_t s = pick(c, stream);
+  if (const int rc = geoms_device_state(c)) return rc;
+  int entry = 0;
+  if (const int rc = ring_acquire(c, &entry)) return rc;
+  return ids_release(c, entry, s, vcam_outs_run(c, ids, items, n, outs, plan, s, flags, entry));
 }
 
 int bsx_reset_streams(bsx_ctx* c, const int* ids, int n, void* stream) {

@@ -217,6 +217,21 @@ hipError_t launch_mask_blend_geoms_fmt(const GeomClass* classes, const GeomDesc*
                                        const uint8_t* ofinal, int outW, int outH, uint8_t* tile_class, int n, hipStream_t s, int flags);
 hipError_t launch_vcam_geoms_fmt(const GeomClass* classes, const VgClass* vg, const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const uint8_t* ofinal,
                                  int outW, int outH, uint8_t* tile_class, int out_w, int out_h, int n, hipStream_t s, unsigned flags);
+// bsx_step_batch_vcam_geoms_outs: launch_vcam_geoms' [tile-class launch and] masks-only tile launch over the call's positions, then ONE resize pass whose ragged grid
+// ranges over OUTPUT RECORDS of different sizes instead of positions of one size.  The records are ordered by (class of their item, output size); each such pair
+// that occurs is a group:
+//   VgOutGroup  one record per group of the call (a DEVICE array, staged per call): the VgClass of (class, size), the tiles per output row and the option bits of
+//               the body (bit 0 = YUYV pack, bit 4 = whole-dword stores: launch_vcam_geoms' rule, per size);
+//   odesc       one GeomDesc per output record, in group order: the descriptor of the record's position with `out` replaced by the record's buffer;
+//   OutSpans    by value in the kernel arguments: per group its first workgroup, its first record and the workgroups of one record (64 x 32 output tiles).  A
+//               workgroup finds its group with compares on SGPRs as geom_span does, then record = rec[g] + local / per[g] and tile = local % per[g]: nothing is
+//               loaded ahead of the group record and the descriptor, two independent uniform loads.  Entries past the last group: wg = the grid's size.
+// outs.wg[kMaxOutGroups] == 0 (no record): the masks-only step.  fmt: some position's frame is YUYV (launch_vcam_geoms_fmt's kernels and rules).
+constexpr int kMaxOutGroups = 32;
+struct alignas(16) VgOutGroup { VgClass c; int ntx, opt, pad[2]; };
+struct OutSpans { int wg[kMaxOutGroups + 1]; int rec[kMaxOutGroups]; int per[kMaxOutGroups]; int ng; };
+hipError_t launch_vcam_geoms_outs(const GeomClass* classes, const VgOutGroup* groups, const GeomDesc* odesc, const OutSpans& outs, const GeomDesc* desc,
+                                  const GeomSpans& tiles, unsigned xcd_mask, const uint8_t* ofinal, int outW, int outH, uint8_t* tile_class, int n, hipStream_t s, bool fmt);
 // ---- classes off the 4-pixel grid (bsx_new_geoms_ex with BSX_GEOMS_EDGE_ROI): W % 4 == 0, roi.x and roi.w free ----------------------------------------------------
 // The composite moves in 4-pixel groups of three aligned dwords, so the groups are anchored to the FRAME: with s = roi.x & 3 (geom_edge_shift) tile column tbx of a
 // class starts at ROI-relative column 128 tbx - s, and a class has ceil((s + roi.w) / 128) tile columns (geom_tile_cols: GeomClass::ntx, the spans and the tile-class

@@ -2511,4 +2511,120 @@ hipError_t launch_mask_blend_geoms_edge(const GeomClass* classes, const GeomDesc
   return hipGetLastError();
 }
 
+// ---- bsx_step_batch_vcam_geoms_outs: several outputs per position, each of its own size, in ONE resize pass (kernels.hpp: VgOutGroup, OutSpans) --------------------
+// vg_geoms_k / vg_geoms_fmt_k with a prologue of their own: the grid is ragged over up to 32 (class, size) groups of output records, so group record (capture size,
+// table, form, tiles per row, option bits) and descriptor (the position's pointers and flags, `out` the record's) are read per workgroup where vg_geoms_k takes
+// per, ntx and opt from its arguments.  The body is vcam_tile.inc, included as there.  Kernels of their own at the end of the file (the reason is given above
+// mask_geoms_k): bsx_step_batch_vcam_geoms keeps launching vg_geoms_k.
+static_assert(kVcYuyvOut == 1 && kVcOutWords == 16, "VgOutGroup::opt is written by the host (kernels.hpp)");
+namespace {
+// workgroup `id` of the ragged output grid: its group g, the group's first workgroup w0, first record r0 and workgroups per record — geom_span's compare chain over
+// kMaxOutGroups spans (a compare and four selects on SGPRs per span, nothing loaded but the kernel arguments), cut short in steps of eight spans by the call's
+// group count (a scalar branch): a call of up to 8 groups pays 7 steps, the simulcast of three classes x three sizes 15, a full call 31
+__device__ __forceinline__ void out_span(const OutSpans& sp, int id, int* g, int* w0, int* r0, int* per) {
+  *g = 0; *w0 = sp.wg[0]; *r0 = sp.rec[0]; *per = sp.per[0];
+#pragma unroll
+  for (int b = 0; b < kMaxOutGroups; b += 8) {
+    if (b && sp.ng <= b) break;
+#pragma unroll
+    for (int k = b ? b : 1; k < b + 8; k++)
+      if (id >= sp.wg[k]) { *g = k; *w0 = sp.wg[k]; *r0 = sp.rec[k]; *per = sp.per[k]; }
+  }
+}
+
+template <int = 0>
+__global__ __launch_bounds__(kThreads) void vg_outs_k(const VgOutGroup* __restrict__ groups, const GeomDesc* __restrict__ odesc, OutSpans sp) {
+  int g, w0, r0, per;
+  out_span(sp, (int)blockIdx.x, &g, &w0, &r0, &per);
+  const unsigned local = blockIdx.x - (unsigned)w0, rl = local / (unsigned)per, tile_ = local - rl * (unsigned)per;
+  const VgOutGroup G = groups[g];                                     // (uniform index: scalar loads) — independent of the descriptor's
+  const GeomDescRegs d = geom_desc(odesc, r0 + (int)rl);
+  const int W = G.c.W, H = G.c.H, ntx = G.ntx;
+  int opt = G.opt;
+  const ResizeTab tab = geom_tab(G.c.tab);
+  const uint8_t *const frames = d.frame, *const bg = d.bg, *const masks = d.mask;
+  uint8_t* const out = d.out;
+  if ((W & 3) == 0 && ((((uintptr_t)frames) | ((uintptr_t)masks)) & 3) == 0) opt |= kVcWords;      // launch_vg_mixed's rule, per position
+  constexpr bool SEL = true, YIN = false;
+  constexpr long bg_stride = 0;
+  [[maybe_unused]] const int* const slot_of = nullptr;
+#define BSX_VT_TILE tile_
+#define BSX_VT_POS 0l                                                /* the record's own bases: index 0 of each */
+#define BSX_VT_DESC(fl) fl = d.flags
+  if (G.c.direct) {
+    constexpr bool DIRECT = true;
+#include "vcam_tile.inc"
+  } else {
+    constexpr bool DIRECT = false;
+#include "vcam_tile.inc"
+  }
+#undef BSX_VT_TILE
+#undef BSX_VT_POS
+#undef BSX_VT_DESC
+}
+
+// vg_outs_k for a call with at least one YUYV item: vg_geoms_fmt_k's choice per (form, format), one staging area for all four inclusions
+template <int = 0>
+__global__ __launch_bounds__(kThreads) void vg_outs_fmt_k(const VgOutGroup* __restrict__ groups, const GeomDesc* __restrict__ odesc, OutSpans sp) {
+  __shared__ uint32_t s_px[kVLdsWords];
+  int g, w0, r0, per;
+  out_span(sp, (int)blockIdx.x, &g, &w0, &r0, &per);
+  const unsigned local = blockIdx.x - (unsigned)w0, rl = local / (unsigned)per, tile_ = local - rl * (unsigned)per;
+  const VgOutGroup G = groups[g];                                     // (uniform index: scalar loads) — independent of the descriptor's
+  const GeomDescRegs d = geom_desc(odesc, r0 + (int)rl);
+  const int W = G.c.W, H = G.c.H, ntx = G.ntx;
+  int opt = G.opt;
+  const ResizeTab tab = geom_tab(G.c.tab);
+  const uint8_t *const frames = d.frame, *const bg = d.bg, *const masks = d.mask;
+  uint8_t* const out = d.out;
+  if ((W & 3) == 0 && ((((uintptr_t)frames) | ((uintptr_t)masks)) & 3) == 0) opt |= kVcWords;      // launch_vg_mixed's rule (the same for both formats), per position
+  constexpr bool SEL = true;
+  constexpr long bg_stride = 0;
+  [[maybe_unused]] const int* const slot_of = nullptr;
+#define BSX_VT_OWN_LDS
+#define BSX_VT_TILE tile_
+#define BSX_VT_POS 0l                                                /* the record's own bases: index 0 of each */
+#define BSX_VT_DESC(fl) fl = d.flags
+  if (d.flags & kGeomYuyvIn) {
+    constexpr bool YIN = true;
+    if (G.c.direct) {
+      constexpr bool DIRECT = true;
+#include "vcam_tile.inc"
+    } else {
+      constexpr bool DIRECT = false;
+#include "vcam_tile.inc"
+    }
+  } else {
+    constexpr bool YIN = false;
+    if (G.c.direct) {
+      constexpr bool DIRECT = true;
+#include "vcam_tile.inc"
+    } else {
+      constexpr bool DIRECT = false;
+#include "vcam_tile.inc"
+    }
+  }
+#undef BSX_VT_OWN_LDS
+#undef BSX_VT_TILE
+#undef BSX_VT_POS
+#undef BSX_VT_DESC
+}
+}  // namespace
+
+hipError_t launch_vcam_geoms_outs(const GeomClass* classes, const VgOutGroup* groups, const GeomDesc* odesc, const OutSpans& outs, const GeomDesc* desc,
+                                  const GeomSpans& tiles, unsigned xcd_mask, const uint8_t* ofinal, int outW, int outH, uint8_t* tile_class, int n, hipStream_t s, bool fmt) {
+  const int total = outs.wg[kMaxOutGroups];
+  if (n <= 0 || tiles.wg[kMaxGeoms] <= 0 || total < 0 || outs.ng < 0 || outs.ng > kMaxOutGroups || (total > 0 && (!groups || !odesc || outs.ng == 0 || outs.wg[0] != 0)))
+    return hipErrorInvalidValue;
+  for (int k = 0; k < kMaxOutGroups; k++)                               // a group's span is whole records; past the last group every span is empty
+    if (k < outs.ng ? (outs.per[k] <= 0 || outs.wg[k + 1] <= outs.wg[k] || (outs.wg[k + 1] - outs.wg[k]) % outs.per[k]) : outs.wg[k] != total) return hipErrorInvalidValue;
+  if (tile_class) tile_class_geoms_k<<<dim3((unsigned)n), kThreads, 0, s>>>(classes, desc, tiles, ofinal, outW, outH, tile_class);
+  mask_geoms_k<><<<dim3((unsigned)tiles.wg[kMaxGeoms]), kThreads, 0, s>>>(classes, desc, tiles, xcd_mask, ofinal, outW, outH, tile_class);      // (reads no frame)
+  if (total > 0) {
+    if (fmt) vg_outs_fmt_k<><<<dim3((unsigned)total), kThreads, 0, s>>>(groups, odesc, outs);
+    else vg_outs_k<><<<dim3((unsigned)total), kThreads, 0, s>>>(groups, odesc, outs);
+  }
+  return hipGetLastError();
+}
+
 }  // namespace bsx

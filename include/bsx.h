@@ -27,6 +27,7 @@
  *   bsx_new_geoms_ex       … with creation flags: BSX_GEOMS_EDGE_ROI admits sizes whose ROI is off the 4-pixel grid (segm_lite at 1920x1080)  lib/libbackscrub.cc:234-246
  *   bsx_step_batch_geoms   … for streams of different capture sizes together: one prep launch, one network pass, one tile launch  app/deepseg.cc:634-673
  *   bsx_step_batch_vcam_geoms  … the same streams, every composite written at the virtual camera's one size  app/deepseg.cc:634-681
+ *   bsx_step_batch_vcam_geoms_outs  … the same streams, several outputs per stream, each of its own size (speaker + thumbnails, simulcast layers)
  *   bsx_reset_streams      bsx_reset for a chosen subset of the streams (a slot reused for a new camera)
  *                          (set_input_frame → mask → alpha_blend), batched
  *   bsx_resize_bgr         grab_background() cv::resize   app/background.cc:178-194
@@ -336,6 +337,34 @@ BSX_API int bsx_step_batch_geoms(bsx_ctx* ctx, const int* ids, const bsx_geom_it
  *     class is off the fused tile route (possible only in a one-class context, which bsx_step_batch_vcam_mixed takes); a YUYV item whose class has no fused YUYV
  *     prep (as bsx_step_batch_geoms).  A refused call changes no state.  BSX_EDEVICE for a batch of 2^31 workgroups or more. */
 BSX_API int bsx_step_batch_vcam_geoms(bsx_ctx* ctx, const int* ids, const bsx_geom_item* items, int n, int out_w, int out_h, void* stream, unsigned flags);
+
+/* bsx_step_batch_vcam_geoms with SEVERAL outputs per stream, each of its own size: a gallery that shows the active speaker at 1280x720 and everyone else at 320x180,
+ * a simulcast forwarder that publishes every camera at 640x360, 320x180 and 160x90.  Each stream is filtered ONCE (one prep launch, one pass of the network, one
+ * tile-class launch, one masks-only tile launch); ONE resize pass then writes every output record from its item's frame, background and mask taps — its grid ranges
+ * over the records, each with the tiles of its own size.  No capture-size composite is stored and none is read back per layer.
+ *   - ids, items[0..n): the rules of bsx_step_batch_vcam_geoms (required ids, any order, classes may interleave, the same staging ring; setting.flags:
+ *     BSX_STEP_FLIP_H | BSX_STEP_FLIP_V | BSX_STREAM_FILTER_OFF | BSX_STREAM_YUYV_IN, no blur).  items[i].d_out is NOT read;
+ *   - outs[0..m): host memory, read before the call returns, in any order.  outs[j] asks for the composite of items[outs[j].item] at out_w x out_h in d_out:
+ *     [out_h][out_w][3], or [out_h][out_w][2] with BSX_STEP_YUYV, 4-byte aligned.  An item may be named by 0 to BSX_MAX_OUTS_PER_ITEM records (with none its stream
+ *     still advances and its persistent mask is still written; two records may ask for the same size in different buffers); a call uses at most BSX_MAX_OUT_SIZES
+ *     distinct sizes;
+ *   - flags (batch-wide): BSX_STEP_YUYV only;
+ *   - result: every outs[j].d_out is byte-identical to what bsx_step_batch_vcam_geoms(.., out_w, out_h, ..) writes for that item; persistent mask and ofinal of every
+ *     stream of the context are byte-identical to bsx_step_batch_geoms'.  Each stream advances once, however many records name it;
+ *   - the per-class tables of each size come from the cache bsx_step_batch_vcam_geoms fills: a size seen before allocates and uploads nothing.  Records and
+ *     (class, size) groups travel through the staging ring: no host synchronisation unless the caller runs four calls ahead;
+ *   - works on every context (bsx_new, bsx_new_geoms, bsx_new_geoms_ex with BSX_GEOMS_EDGE_ROI);
+ *   - n == 0: returns 0 and enqueues nothing.  m == 0 with n > 0 is a masks-only step;
+ *   - BSX_EINVAL before anything is enqueued, with a bsx_last_error text naming outs[j] or items[i] and the value, for: every refusal of bsx_step_batch_vcam_geoms
+ *     that still applies (ids, items NULL, flag bits, a NULL or unaligned d_frame or d_bg that is read, a pending pipelined composite, an onmask callback, a class
+ *     off the fused route, a YUYV item without a fused YUYV prep); outs NULL with m > 0; m < 0; an item outside [0, n); a fifth record for one item; a fifth
+ *     distinct size; a non-positive size; an odd out_w with BSX_STEP_YUYV; a NULL or not 4-byte aligned d_out; an output overlapping any frame (W*H*2 bytes for a
+ *     YUYV item), background or other output of the call.  A refused call changes no state.  BSX_EDEVICE for a batch of 2^31 workgroups or more. */
+#define BSX_MAX_OUT_SIZES 4        /* distinct (out_w, out_h) in one call */
+#define BSX_MAX_OUTS_PER_ITEM 4    /* output records that may name one item */
+typedef struct bsx_vcam_out { int item; int out_w, out_h; uint8_t* d_out; } bsx_vcam_out;
+BSX_API int bsx_step_batch_vcam_geoms_outs(bsx_ctx* ctx, const int* ids, const bsx_geom_item* items, int n, const bsx_vcam_out* outs, int m, void* stream,
+                                           unsigned flags);
 
 /* Reset the temporal state of the listed streams only (ofinal → 0, persistent mask → 255, as bsx_reset does for all) — a slot reused for a new camera.  The
  * other streams' state is untouched, and a pending pipelined composite is NOT dropped: the call is refused (BSX_EINVAL) while one is pending.  Same ids rules,
