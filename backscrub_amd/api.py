@@ -76,6 +76,10 @@ class _VcamOut(C.Structure):                # bsx.h bsx_vcam_out
     _fields_ = [("item", C.c_int), ("out_w", C.c_int), ("out_h", C.c_int), ("d_out", C.c_void_p)]
 
 
+class _VcamOutNv12(C.Structure):            # bsx.h bsx_vcam_out_nv12
+    _fields_ = [("item", C.c_int), ("out_w", C.c_int), ("out_h", C.c_int), ("pitch_y", C.c_int), ("pitch_uv", C.c_int), ("d_y", C.c_void_p), ("d_uv", C.c_void_p)]
+
+
 class StreamSetting:
     """one stream's settings for MaskGen.step_mixed — what one reference process takes as -b <image> (bg), -H / -V (flip_h / flip_v), -p bgblur:<k> (bgblur)
     and toggles at run time with the s / h / v keys (filter_off, flip_h, flip_v; app/deepseg.cc:387-437, 624-673, 777-790).  bg: a cuda uint8 [H,W,3] image
@@ -127,12 +131,15 @@ SYMBOLS = [
     ("bsx_step_batch_geoms", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(_GeomItem), C.c_int, C.c_void_p, C.c_uint]),
     ("bsx_step_batch_vcam_geoms", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(_GeomItem), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint]),
     ("bsx_step_batch_vcam_geoms_outs", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(_GeomItem), C.c_int, C.POINTER(_VcamOut), C.c_int, C.c_void_p, C.c_uint]),
+    ("bsx_step_batch_vcam_geoms_outs_nv12", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(_GeomItem), C.c_int, C.POINTER(_VcamOutNv12), C.c_int, C.c_void_p,
+                                                      C.c_uint]),
     ("bsx_step_batch_mixed", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(_StreamSetting), C.c_void_p, C.c_int, C.c_void_p, C.c_uint]),
     ("bsx_step_batch_vcam_mixed", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(_StreamSetting), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                             C.c_uint]),
     ("bsx_resize_bgr", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("bsx_resize_bgr_batch", C.c_int, [C.c_void_p, C.POINTER(_ResizeItem), C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("bsx_bgr_to_yuyv", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    ("bsx_bgr_to_nv12", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     ("bsx_yuyv_to_bgr", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("bsx_background_load", C.c_void_p, [C.c_void_p, C.c_char_p, C.c_int]),
     ("bsx_background_from_frames", C.c_void_p, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int]),
@@ -379,17 +386,14 @@ class MaskGen:
         _check(lib().bsx_step_batch_vcam_geoms(self.h, arr, items, n, out_w, out_h, _stream_ptr(), 1 if yuyv else 0), self.h, "bsx_step_batch_vcam_geoms")
         return outs
 
-    def step_vcam_geoms_outs(self, ids, frames, settings, outs, yuyv=False):
-        """step_vcam_geoms with several outputs per stream, each of its own size (bsx_step_batch_vcam_geoms_outs): outs is a sequence of (item_index, tensor) —
-        write the composite of position item_index at the tensor's size, a cuda uint8 [out_h, out_w, 3] (or [.., 2] with yuyv).  A position may be named by 0 to 4
-        records (with none its stream still advances), a call uses at most 4 distinct sizes.  Every stream is filtered once; one resize pass writes every record."""
+    def _vcam_outs_items(self, ids, frames, settings, who):
+        """the ids and items of step_vcam_geoms_outs / step_vcam_geoms_outs_nv12, validated: (ctypes ids, n, ctypes items, the tensor check both use)"""
         torch = _torch()
         arr, n = _ids(ids)
-        frames, settings, outs = list(frames), list(settings), list(outs)
+        frames, settings = list(frames), list(settings)
         if len(frames) != n or len(settings) != n:
             raise BsxError("%d ids for %d frames and %d settings" % (n, len(frames), len(settings)))
         items = (_GeomItem * max(n, 1))()
-        ch = 2 if yuyv else 3
 
         def ok(t, shape):
             return isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and self._on_device(t) and tuple(t.shape) == shape and t.is_contiguous()
@@ -404,7 +408,7 @@ class MaskGen:
             if not isinstance(s, StreamSetting):
                 raise BsxError("settings[%d] is not a StreamSetting" % i)
             if s.bgblur:
-                raise BsxError("settings[%d]: bgblur is not taken by step_vcam_geoms_outs" % i)
+                raise BsxError("settings[%d]: bgblur is not taken by %s" % (i, who))
             if not s.filter_off and s.bg is None:
                 raise BsxError("settings[%d]: bg is required unless filter_off is set" % i)
             if s.bg is not None and not ok(s.bg, (H, W, 3)):
@@ -412,6 +416,16 @@ class MaskGen:
             items[i].d_frame, items[i].d_out = frames[i].data_ptr(), None
             items[i].setting.d_bg = s.bg.data_ptr() if s.bg is not None else None
             items[i].setting.flags = s.flags()
+        return arr, n, items, ok
+
+    def step_vcam_geoms_outs(self, ids, frames, settings, outs, yuyv=False):
+        """step_vcam_geoms with several outputs per stream, each of its own size (bsx_step_batch_vcam_geoms_outs): outs is a sequence of (item_index, tensor) —
+        write the composite of position item_index at the tensor's size, a cuda uint8 [out_h, out_w, 3] (or [.., 2] with yuyv).  A position may be named by 0 to 4
+        records (with none its stream still advances), a call uses at most 4 distinct sizes.  Every stream is filtered once; one resize pass writes every record."""
+        torch = _torch()
+        outs = list(outs)
+        arr, n, items, ok = self._vcam_outs_items(ids, frames, settings, "step_vcam_geoms_outs")
+        ch = 2 if yuyv else 3
         m = len(outs)
         recs = (_VcamOut * max(m, 1))()
         named, sizes = {}, []
@@ -436,6 +450,64 @@ class MaskGen:
             recs[j].item, recs[j].out_w, recs[j].out_h, recs[j].d_out = int(item), ow, oh, t.data_ptr()
         _check(lib().bsx_step_batch_vcam_geoms_outs(self.h, arr, items, n, recs, m, _stream_ptr(), 1 if yuyv else 0), self.h, "bsx_step_batch_vcam_geoms_outs")
         return [t for _i, t in outs]
+
+    def _nv12_planes(self, who, y, uv):
+        """the two views of an NV12 surface, validated: (out_w, out_h, pitch_y, pitch_uv).  y: uint8 [out_h, out_w] with strides (pitch_y, 1); uv: uint8
+        [out_h / 2, out_w] with strides (pitch_uv, 1) — U, V interleaved; sizes even, pitches multiples of 4, both 4-byte aligned."""
+        torch = _torch()
+        for name, t in (("y", y), ("uv", uv)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 2 or t.numel() == 0:
+                raise BsxError("%s: %s must be a non-empty uint8 tensor of two dimensions (it is %s)" % (who, name, "a %s" % type(t).__name__ if not isinstance(
+                    t, torch.Tensor) else "%s %s" % (t.dtype, tuple(t.shape))))
+            if not self._on_device(t):
+                raise BsxError("%s: %s must be on cuda:%d (it is on %s)" % (who, name, self.device, t.device))
+        oh, ow = int(y.shape[0]), int(y.shape[1])
+        if (ow | oh) & 1:
+            raise BsxError("%s: NV12 needs an even width and height (y is %d x %d)" % (who, ow, oh))
+        if tuple(uv.shape) != (oh // 2, ow):
+            raise BsxError("%s: uv must be [%d, %d] for a y of [%d, %d] (it is %s)" % (who, oh // 2, ow, oh, ow, list(uv.shape)))
+        pitch = []
+        for name, t in (("y", y), ("uv", uv)):
+            if t.stride(1) != 1:
+                raise BsxError("%s: %s has an inner stride of %d (the bytes of a row must be adjacent)" % (who, name, t.stride(1)))
+            p = int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), ow)      # (the stride of a single row means nothing: any pitch that holds the row)
+            if p < ow:
+                raise BsxError("%s: the pitch of %s, %d, is below out_w = %d" % (who, name, p, ow))
+            if p % 4:
+                raise BsxError("%s: the pitch of %s, %d, is not a multiple of 4" % (who, name, p))
+            if t.data_ptr() % 4:
+                raise BsxError("%s: %s at 0x%x is not 4-byte aligned" % (who, name, t.data_ptr()))
+            pitch.append(p)
+        return ow, oh, pitch[0], pitch[1]
+
+    def step_vcam_geoms_outs_nv12(self, ids, frames, settings, outs):
+        """step_vcam_geoms_outs with every output an NV12 surface with row pitches, as a video encoder takes it (bsx_step_batch_vcam_geoms_outs_nv12): outs is a
+        sequence of (item_index, y, uv) — y a cuda uint8 view [out_h, out_w] with strides (pitch_y, 1), uv [out_h / 2, out_w] with strides (pitch_uv, 1), U and V
+        interleaved; sizes and pitches are read from the views.  out_w and out_h even, pitches multiples of 4, both planes 4-byte aligned.  Y and chroma are the
+        bytes of the YUYV output of step_vcam_geoms_outs, the chroma averaged (truncating) over each pair of rows; bytes past out_w of a row are not written."""
+        outs = list(outs)
+        arr, n, items, _ok = self._vcam_outs_items(ids, frames, settings, "step_vcam_geoms_outs_nv12")
+        m = len(outs)
+        recs = (_VcamOutNv12 * max(m, 1))()
+        named, sizes = {}, []
+        for j, rec in enumerate(outs):
+            if not isinstance(rec, (tuple, list)) or len(rec) != 3:
+                raise BsxError("outs[%d] must be a triple (item_index, y, uv)" % j)
+            item, y, uv = rec
+            if isinstance(item, bool) or not isinstance(item, (int, np.integer)) or not 0 <= int(item) < n:
+                raise BsxError("outs[%d]: item %r is not an index into the call's %d positions" % (j, item, n))
+            ow, oh, py, puv = self._nv12_planes("outs[%d]" % j, y, uv)
+            named[int(item)] = named.get(int(item), 0) + 1
+            if named[int(item)] > BSX_MAX_OUTS_PER_ITEM:
+                raise BsxError("outs[%d]: record %d of position %d (at most %d name one position)" % (j, named[int(item)], int(item), BSX_MAX_OUTS_PER_ITEM))
+            if (ow, oh) not in sizes:
+                sizes.append((ow, oh))
+                if len(sizes) > BSX_MAX_OUT_SIZES:
+                    raise BsxError("outs[%d]: %d x %d is distinct output size %d of the call (at most %d)" % (j, ow, oh, len(sizes), BSX_MAX_OUT_SIZES))
+            r = recs[j]
+            r.item, r.out_w, r.out_h, r.pitch_y, r.pitch_uv, r.d_y, r.d_uv = int(item), ow, oh, py, puv, y.data_ptr(), uv.data_ptr()
+        _check(lib().bsx_step_batch_vcam_geoms_outs_nv12(self.h, arr, items, n, recs, m, _stream_ptr(), 0), self.h, "bsx_step_batch_vcam_geoms_outs_nv12")
+        return [(y, uv) for _i, y, uv in outs]
 
     # ---- batched device path -----------------------------------------------------------------
     def process_batch(self, frames, masks_out=None):
@@ -724,6 +796,29 @@ class MaskGen:
         _check(lib().bsx_bgr_to_yuyv(self.h, C.c_void_p(bgr.data_ptr()), C.c_void_p(out.data_ptr()), w, h, n, _stream_ptr()),
                self.h, "bsx_bgr_to_yuyv")
         return out
+
+    def bgr_to_nv12(self, bgr, pitch_y=None, pitch_uv=None):
+        """[n,h,w,3] u8 device frames → NV12 (bsx_bgr_to_nv12): (y, uv), views [n, h, w] and [n, h / 2, w] (U, V interleaved) of planes with rows of pitch_y and
+        pitch_uv bytes (default: w rounded up to a multiple of 4).  w and h even; bytes past w of a row are not written (the planes are allocated zeroed)."""
+        torch = _torch()
+        if not isinstance(bgr, torch.Tensor) or bgr.dtype != torch.uint8 or bgr.dim() != 4 or bgr.shape[3] != 3 or bgr.numel() == 0 or not bgr.is_contiguous():
+            raise BsxFrameFormatError("bgr must be a contiguous, non-empty uint8 tensor [n,h,w,3]")
+        if not self._on_device(bgr):
+            raise BsxError("bgr must be on cuda:%d (it is on %s)" % (self.device, bgr.device))
+        n, h, w, _ = (int(v) for v in bgr.shape)
+        if (w | h) & 1:
+            raise BsxFrameFormatError("NV12 needs an even width and height (bgr is %d x %d)" % (w, h))
+        pitch = []
+        for name, p in (("pitch_y", pitch_y), ("pitch_uv", pitch_uv)):
+            p = (w + 3) // 4 * 4 if p is None else p
+            if isinstance(p, bool) or not isinstance(p, (int, np.integer)) or p < w or p % 4:
+                raise BsxError("%s = %r must be a multiple of 4 and at least w = %d" % (name, p, w))
+            pitch.append(int(p))
+        y = torch.zeros((n, h, pitch[0]), dtype=torch.uint8, device=bgr.device)
+        uv = torch.zeros((n, h // 2, pitch[1]), dtype=torch.uint8, device=bgr.device)
+        _check(lib().bsx_bgr_to_nv12(self.h, C.c_void_p(bgr.data_ptr()), w, h, n, C.c_void_p(y.data_ptr()), pitch[0], C.c_void_p(uv.data_ptr()), pitch[1],
+                                     _stream_ptr()), self.h, "bsx_bgr_to_nv12")
+        return y[:, :, :w], uv[:, :, :w]
 
     def flip_bgr(self, bgr, code):
         """cv::flip(bgr, out, code) for [n,h,w,3] u8 device frames (deepseg.cc:667-673): 0 vertical, >0 horizontal, <0 both."""

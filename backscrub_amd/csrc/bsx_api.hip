@@ -27,6 +27,7 @@
 #include "rtc.hpp"
 #include "specialised.hpp"
 #include "tflite_model.hpp"
+#include "vcam_nv12_plan.hpp"
 #include "vcam_outs_plan.hpp"
 
 using namespace bsx;
@@ -227,10 +228,11 @@ struct bsx_ctx {
   std::map<std::pair<int, int>, VgGeoms> vg_geoms;
   // bsx_step_batch_vcam_geoms_outs: per ring entry (the same entries and events as the ids) the call's group records — kMaxOutGroups VgOutGroup — then its output
   // descriptors, at most BSX_MAX_OUTS_PER_ITEM * n_streams GeomDesc in group order, built in the pinned entry and copied to the device entry in one hipMemcpyAsync.
-  // Allocated on the first call of that entry point.
+  // Allocated on the first call of that entry point.  bsx_step_batch_vcam_geoms_outs_nv12 uses the same entries: behind the call's m descriptors its m plane
+  // records (VgNv12Rec, in the same order), so that its copy is one too.
   uint8_t* h_vo = nullptr;                  // pinned [kIdRing][vo_entry_bytes()]
   uint8_t* d_vo = nullptr;                  // device, likewise
-  size_t vo_entry_bytes() const { return (size_t)kMaxOutGroups * sizeof(VgOutGroup) + (size_t)BSX_MAX_OUTS_PER_ITEM * (size_t)n_streams * sizeof(GeomDesc); }
+  size_t vo_entry_bytes() const { return (size_t)kMaxOutGroups * sizeof(VgOutGroup) + (size_t)BSX_MAX_OUTS_PER_ITEM * (size_t)n_streams * (sizeof(GeomDesc) + sizeof(VgNv12Rec)); }
   std::vector<int> vo_class, vo_pos;        // host scratch: the class of each item, the position (place in the class-ordered descriptors) of each item
   int geom_of(int stream) const { int g = 0; while (g + 1 < (int)geoms.size() && stream >= geoms[g + 1].first) g++; return g; }
   bool act16 = false;                  // BSX_ACT16=1: 16-bit activation STORAGE for the segmented Meet / MLKit networks (g1) — opt-in, IoU-gated; needs the specialised middle kernel
@@ -1409,14 +1411,11 @@ int vcam_geoms_run(bsx_ctx* c, const int* ids, const bsx_geom_item* items, int n
 // ---- bsx_step_batch_vcam_geoms_outs: the vcam geoms step with several outputs per position, each of its own size -----------------------------------------------
 // vcam_geoms_run's shape: the same front, then [one tile-class launch,] ONE masks-only tile launch and ONE resize pass whose grid ranges over the output records
 // (vcam_outs_plan.hpp orders them into (class, size) groups).  The item checks are vcam_geoms_check's without d_out, which this entry point does not read.
-int vcam_outs_check(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item* items, int n, const bsx_vcam_out* outs, int m, unsigned flags, VcamOutsPlan* plan) {
-  if (!items) return refuse(c, fn, "items is NULL");
-  if (flags & BSX_STEP_NO_MASK) return refuse(c, fn, "unsupported flags 0x%x (the no-mask step has no vcam form)", flags);
-  if (flags & BSX_STEP_YUYV_IN) return refuse(c, fn, "flags 0x%x: YUYV input frames are not taken by the multi-geometry step as a batch flag (the format belongs to the item: the yuyv-in bit, 0x40, of items[i].setting.flags)", flags);
-  if (flags & ~BSX_STEP_YUYV) return refuse(c, fn, "flags 0x%x has bits outside yuyv", flags);
+// the part of the check that both output forms share, after the flags: the context's state and the items.  Leaves the items' frames and backgrounds in rsz_spans
+// and their classes in vo_class.
+int vcam_outs_items(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item* items, int n) {
   if (const int rc = refuse_pending(c, fn)) return rc;
   if (c->onmask) return refuse(c, fn, "needs the fused mask route (no onmask callback)");
-  const bool yuyv = (flags & BSX_STEP_YUYV) != 0;
   std::vector<bsx_ctx::Span>& sp = c->rsz_spans;
   sp.clear();
   c->vo_class.resize((size_t)n);
@@ -1441,6 +1440,17 @@ int vcam_outs_check(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_i
     if ((uintptr_t)it.setting.d_bg & 3) return refuse(c, fn, "items[%d]: setting.d_bg %p is not 4-byte aligned", i, (const void*)it.setting.d_bg);
     sp.push_back({(uintptr_t)it.setting.d_bg, (uintptr_t)it.setting.d_bg + px * 3, i, false});
   }
+  return BSX_OK;
+}
+
+int vcam_outs_check(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item* items, int n, const bsx_vcam_out* outs, int m, unsigned flags, VcamOutsPlan* plan) {
+  if (!items) return refuse(c, fn, "items is NULL");
+  if (flags & BSX_STEP_NO_MASK) return refuse(c, fn, "unsupported flags 0x%x (the no-mask step has no vcam form)", flags);
+  if (flags & BSX_STEP_YUYV_IN) return refuse(c, fn, "flags 0x%x: YUYV input frames are not taken by the multi-geometry step as a batch flag (the format belongs to the item: the yuyv-in bit, 0x40, of items[i].setting.flags)", flags);
+  if (flags & ~BSX_STEP_YUYV) return refuse(c, fn, "flags 0x%x has bits outside yuyv", flags);
+  if (const int rc = vcam_outs_items(c, fn, ids, items, n)) return rc;
+  const bool yuyv = (flags & BSX_STEP_YUYV) != 0;
+  std::vector<bsx_ctx::Span>& sp = c->rsz_spans;
   const int pr = vcam_outs_plan(c->vo_class.data(), n, outs, m, yuyv, plan);
   if (pr == VcamOutsPlan::kRefused) return refuse(c, fn, "%s", plan->text);
   if (pr == VcamOutsPlan::kTooLarge) { c->last_error = std::string("error: ") + fn + ": the batch needs more than 2^31 workgroups\n"; return BSX_EDEVICE; }
@@ -1454,8 +1464,36 @@ int vcam_outs_check(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_i
   return BSX_OK;
 }
 
-int vcam_outs_run(bsx_ctx* c, const int* ids, const bsx_geom_item* items, int n, const bsx_vcam_out* outs, const VcamOutsPlan& plan, hipStream_t s, unsigned flags, int k) {
-  const char* fn = "bsx_step_batch_vcam_geoms_outs";
+// ... of bsx_step_batch_vcam_geoms_outs_nv12: the same items, the records by vcam_nv12_plan.hpp, a plane's extent pitch * (rows - 1) + out_w.  Span::item of a plane
+// is 2 j for outs[j].d_y and 2 j + 1 for outs[j].d_uv.
+int vcam_nv12_check(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item* items, int n, const bsx_vcam_out_nv12* outs, int m, unsigned flags, VcamOutsPlan* plan) {
+  if (!items) return refuse(c, fn, "items is NULL");
+  if (flags) return refuse(c, fn, "flags 0x%x: this step takes no flags (an item's format and flips belong to items[i].setting.flags)", flags);
+  if (const int rc = vcam_outs_items(c, fn, ids, items, n)) return rc;
+  const int pr = vcam_nv12_plan(c->vo_class.data(), n, outs, m, plan);
+  if (pr == VcamOutsPlan::kRefused) return refuse(c, fn, "%s", plan->text);
+  if (pr == VcamOutsPlan::kTooLarge) { c->last_error = std::string("error: ") + fn + ": the batch needs more than 2^31 workgroups\n"; return BSX_EDEVICE; }
+  std::vector<bsx_ctx::Span>& sp = c->rsz_spans;
+  for (int j = 0; j < m; j++) {
+    const bsx_vcam_out_nv12& r = outs[j];
+    sp.push_back({(uintptr_t)r.d_y, (uintptr_t)r.d_y + vcam_nv12_extent(r.pitch_y, r.out_h, r.out_w), 2 * j, true});
+    sp.push_back({(uintptr_t)r.d_uv, (uintptr_t)r.d_uv + vcam_nv12_extent(r.pitch_uv, r.out_h / 2, r.out_w), 2 * j + 1, true});
+  }
+  const bsx_ctx::Span* d = nullptr;
+  const bsx_ctx::Span* o = nullptr;
+  if (spans_overlap(sp, &d, &o)) {
+    const char* const plane = (d->item & 1) ? "d_uv" : "d_y";
+    if (o->dst)
+      return refuse(c, fn, "outs[%d]: %s %p overlaps %s of outs[%d] (%p)", d->item / 2, plane, (const void*)d->begin, (o->item & 1) ? "d_uv" : "d_y", o->item / 2,
+                    (const void*)o->begin);
+    return refuse(c, fn, "outs[%d]: %s %p overlaps a frame or background of items[%d] (%p)", d->item / 2, plane, (const void*)d->begin, o->item, (const void*)o->begin);
+  }
+  return BSX_OK;
+}
+
+// outs: the BGR / YUYV records; nv12 (outs NULL): the NV12 records, whose plane records follow the descriptors in the ring entry
+int vcam_outs_run(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item* items, int n, const bsx_vcam_out* outs, const bsx_vcam_out_nv12* nv12,
+                  const VcamOutsPlan& plan, hipStream_t s, unsigned flags, int k) {
   const size_t eb = c->vo_entry_bytes(), m = plan.order.size();
   if (!c->h_vo) BSX_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_vo), bsx_ctx::kIdRing * eb, hipHostMallocDefault));
   if (!c->d_vo) BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_vo), bsx_ctx::kIdRing * eb));
@@ -1484,14 +1522,29 @@ int vcam_outs_run(bsx_ctx* c, const int* ids, const bsx_geom_item* items, int n,
     hg[g] = VgOutGroup{rec[G.size][G.cls], G.ntx, (int)yuyv | (G.words ? 16 : 0), {0, 0}};
   }
   sp.wg[kMaxOutGroups] = (int)plan.total_wg;
+  VgNv12Rec* const hn = reinterpret_cast<VgNv12Rec*>(ho + m);          // (48 m bytes behind a 16-byte aligned address)
   for (size_t q = 0; q < m; q++) {
-    const bsx_vcam_out& o = outs[plan.order[q]];
-    ho[q] = hd[c->vo_pos[(size_t)o.item]];
-    ho[q].out = o.d_out;
+    if (nv12) {
+      const bsx_vcam_out_nv12& o = nv12[plan.order[q]];
+      ho[q] = hd[c->vo_pos[(size_t)o.item]];
+      ho[q].out = o.d_y;
+      hn[q] = VgNv12Rec{o.d_uv, o.pitch_y, o.pitch_uv};
+    } else {
+      const bsx_vcam_out& o = outs[plan.order[q]];
+      ho[q] = hd[c->vo_pos[(size_t)o.item]];
+      ho[q].out = o.d_out;
+    }
   }
   uint8_t* const dv = c->d_vo + (size_t)k * eb;
-  if (m) BSX_HIP(c, hipMemcpyAsync(dv, hg, (size_t)kMaxOutGroups * sizeof(VgOutGroup) + m * sizeof(GeomDesc), hipMemcpyHostToDevice, s));
+  const size_t desc_at = (size_t)kMaxOutGroups * sizeof(VgOutGroup), nrec_at = desc_at + m * sizeof(GeomDesc);
+  if (m) BSX_HIP(c, hipMemcpyAsync(dv, hg, nrec_at + (nv12 ? m * sizeof(VgNv12Rec) : 0), hipMemcpyHostToDevice, s));
   bsx_roctx::Range range("bsx:mask+vcam");
+  if (nv12) {
+    BSX_HIP(c, launch_vcam_geoms_outs_nv12(c->d_geom_classes_vg ? c->d_geom_classes_vg : c->d_geom_classes, reinterpret_cast<const VgOutGroup*>(dv),
+                                           reinterpret_cast<const GeomDesc*>(dv + desc_at), reinterpret_cast<const VgNv12Rec*>(dv + nrec_at), sp, st.desc, st.tiles,
+                                           st.xcd_mask, c->d_ofinal, c->outW, c->outH, c->d_geom_tile_class, n, s, st.fmt));
+    return BSX_OK;
+  }
   BSX_HIP(c, launch_vcam_geoms_outs(c->d_geom_classes_vg ? c->d_geom_classes_vg : c->d_geom_classes, reinterpret_cast<const VgOutGroup*>(dv),
                                     reinterpret_cast<const GeomDesc*>(dv + (size_t)kMaxOutGroups * sizeof(VgOutGroup)), sp, st.desc, st.tiles, st.xcd_mask, c->d_ofinal,
                                     c->outW, c->outH, c->d_geom_tile_class, n, s, st.fmt));
@@ -1956,7 +2009,23 @@ int bsx_step_batch_vcam_geoms_outs(bsx_ctx* c, const int* ids, const bsx_geom_it
   if (const int rc = geoms_device_state(c)) return rc;
   int entry = 0;
   if (const int rc = ring_acquire(c, &entry)) return rc;
-  return ids_release(c, entry, s, vcam_outs_run(c, ids, items, n, outs, plan, s, flags, entry));
+  return ids_release(c, entry, s, vcam_outs_run(c, fn, ids, items, n, outs, nullptr, plan, s, flags, entry));
+}
+
+// bsx_step_batch_vcam_geoms_outs with every record an NV12 surface; see bsx.h
+int bsx_step_batch_vcam_geoms_outs_nv12(bsx_ctx* c, const int* ids, const bsx_geom_item* items, int n, const bsx_vcam_out_nv12* outs, int m, void* stream, unsigned flags) {
+  const char* fn = "bsx_step_batch_vcam_geoms_outs_nv12";
+  if (!c) return BSX_EINVAL;
+  if (const int rc = ids_check(c, fn, ids, n)) return rc;
+  if (n == 0) return refuse_pending(c, fn);
+  VcamOutsPlan plan;
+  if (const int rc = vcam_nv12_check(c, fn, ids, items, n, outs, m, flags, &plan)) return rc;
+  DeviceGuard guard(c->device);
+  hipStream_t s = pick(c, stream);
+  if (const int rc = geoms_device_state(c)) return rc;
+  int entry = 0;
+  if (const int rc = ring_acquire(c, &entry)) return rc;
+  return ids_release(c, entry, s, vcam_outs_run(c, fn, ids, items, n, nullptr, outs, plan, s, 0, entry));
 }
 
 int bsx_reset_streams(bsx_ctx* c, const int* ids, int n, void* stream) {
@@ -2111,6 +2180,21 @@ int bsx_bgr_to_yuyv(bsx_ctx* c, const uint8_t* d_bgr, uint8_t* d_yuyv, int w, in
   if (!c || !d_bgr || !d_yuyv || w <= 0 || h <= 0 || n <= 0) return BSX_EINVAL;
   DeviceGuard guard(c->device);
   BSX_HIP(c, launch_bgr_to_yuyv(d_bgr, d_yuyv, w, h, n, pick(c, stream)));
+  return BSX_OK;
+}
+
+int bsx_bgr_to_nv12(bsx_ctx* c, const uint8_t* d_bgr, int w, int h, int n, uint8_t* d_y, int pitch_y, uint8_t* d_uv, int pitch_uv, void* stream) {
+  const char* fn = "bsx_bgr_to_nv12";
+  if (!c) return BSX_EINVAL;
+  if (!d_bgr || !d_y || !d_uv) return refuse(c, fn, "d_bgr %p, d_y %p or d_uv %p is NULL", (const void*)d_bgr, (const void*)d_y, (const void*)d_uv);
+  if (w <= 0 || h <= 0 || n <= 0) return refuse(c, fn, "w = %d, h = %d and n = %d must be positive", w, h, n);
+  if ((w | h) & 1) return refuse(c, fn, "NV12 needs an even width and height (%d x %d)", w, h);
+  if (pitch_y < w || (pitch_y & 3)) return refuse(c, fn, "pitch_y = %d must be a multiple of 4 and at least w = %d", pitch_y, w);
+  if (pitch_uv < w || (pitch_uv & 3)) return refuse(c, fn, "pitch_uv = %d must be a multiple of 4 and at least w = %d", pitch_uv, w);
+  if ((uintptr_t)d_y & 3) return refuse(c, fn, "d_y %p is not 4-byte aligned", (const void*)d_y);
+  if ((uintptr_t)d_uv & 3) return refuse(c, fn, "d_uv %p is not 4-byte aligned", (const void*)d_uv);
+  DeviceGuard guard(c->device);
+  BSX_HIP(c, launch_bgr_to_nv12(d_bgr, w, h, n, d_y, pitch_y, d_uv, pitch_uv, pick(c, stream)));
   return BSX_OK;
 }
 

@@ -232,6 +232,14 @@ struct alignas(16) VgOutGroup { VgClass c; int ntx, opt, pad[2]; };
 struct OutSpans { int wg[kMaxOutGroups + 1]; int rec[kMaxOutGroups]; int per[kMaxOutGroups]; int ng; };
 hipError_t launch_vcam_geoms_outs(const GeomClass* classes, const VgOutGroup* groups, const GeomDesc* odesc, const OutSpans& outs, const GeomDesc* desc,
                                   const GeomSpans& tiles, unsigned xcd_mask, const uint8_t* ofinal, int outW, int outH, uint8_t* tile_class, int n, hipStream_t s, bool fmt);
+// bsx_step_batch_vcam_geoms_outs_nv12: launch_vcam_geoms_outs with every record written as NV12 — a Y plane (odesc's `out`) and an interleaved UV plane of half the
+// rows, each with a row pitch in bytes (multiples of 4, >= out_w; out_w and out_h even; both planes 4-byte aligned).  nrec: one VgNv12Rec per output record, in group
+// order like odesc, a DEVICE array staged with it: the kernel reads record r's planes and pitches with the workgroup-uniform index it reads odesc[r] with.  The
+// groups' option bits are not read.  The same three launches; the resize pass is vg_outs_nv12_k (vg_outs_nv12_fmt_k with fmt).
+struct alignas(16) VgNv12Rec { uint8_t* uv; int pitch_y, pitch_uv; };
+hipError_t launch_vcam_geoms_outs_nv12(const GeomClass* classes, const VgOutGroup* groups, const GeomDesc* odesc, const VgNv12Rec* nrec, const OutSpans& outs,
+                                       const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const uint8_t* ofinal, int outW, int outH, uint8_t* tile_class,
+                                       int n, hipStream_t s, bool fmt);
 // ---- classes off the 4-pixel grid (bsx_new_geoms_ex with BSX_GEOMS_EDGE_ROI): W % 4 == 0, roi.x and roi.w free ----------------------------------------------------
 // The composite moves in 4-pixel groups of three aligned dwords, so the groups are anchored to the FRAME: with s = roi.x & 3 (geom_edge_shift) tile column tbx of a
 // class starts at ROI-relative column 128 tbx - s, and a class has ceil((s + roi.w) / 128) tile columns (geom_tile_cols: GeomClass::ntx, the spans and the tile-class
@@ -263,6 +271,10 @@ static_assert(sizeof(ResizeBatchDesc) == 64, "four 16-byte uniform loads per wor
 hipError_t launch_resize_bgr_batch(const ResizeBatchDesc* desc, int n, int dw, int dh, hipStream_t s);
 // BGR → YUYV.  deepseg.cc:87-106
 hipError_t launch_bgr_to_yuyv(const uint8_t* bgr, uint8_t* yuyv, int w, int h, int n, hipStream_t s);
+// BGR → NV12: n tight [h][w][3] images into pitched planes, image i's at y + i * pitch_y * h and uv + i * pitch_uv * (h / 2).  w, h even; pitches multiples of 4,
+// >= w; planes 4-byte aligned.  Y and chroma are launch_bgr_to_yuyv's bytes, the chroma averaged (truncating) over each pair of rows: UV[r][2c] is the mean of byte 1
+// of the 4:2:2 words (2r, c) and (2r + 1, c), UV[r][2c + 1] that of byte 3.  Bytes [w, pitch) of a row are not written.
+hipError_t launch_bgr_to_nv12(const uint8_t* bgr, int w, int h, int n, uint8_t* y, int pitch_y, uint8_t* uv, int pitch_uv, hipStream_t s);
 // YUYV → BGR ingest.  deepseg.cc:553 (CAP_PROP_CONVERT_RGB), :725
 hipError_t launch_yuyv_to_bgr(const uint8_t* yuyv, uint8_t* bgr, int w, int h, int n, hipStream_t s);
 // cv::flip of the composited frame (code as cv::flip: 0 vertical, >0 horizontal, <0 both).  deepseg.cc:667-673

@@ -2611,18 +2611,196 @@ __global__ __launch_bounds__(kThreads) void vg_outs_fmt_k(const VgOutGroup* __re
 }
 }  // namespace
 
+// the ragged output grid as a launcher takes it: a group's span is whole records; past the last group every span is empty
+static bool out_spans_ok(const OutSpans& outs, const VgOutGroup* groups, const GeomDesc* odesc, const GeomSpans& tiles, int n) {
+  const int total = outs.wg[kMaxOutGroups];
+  if (n <= 0 || tiles.wg[kMaxGeoms] <= 0 || total < 0 || outs.ng < 0 || outs.ng > kMaxOutGroups || (total > 0 && (!groups || !odesc || outs.ng == 0 || outs.wg[0] != 0)))
+    return false;
+  for (int k = 0; k < kMaxOutGroups; k++)
+    if (k < outs.ng ? (outs.per[k] <= 0 || outs.wg[k + 1] <= outs.wg[k] || (outs.wg[k + 1] - outs.wg[k]) % outs.per[k]) : outs.wg[k] != total) return false;
+  return true;
+}
+
 hipError_t launch_vcam_geoms_outs(const GeomClass* classes, const VgOutGroup* groups, const GeomDesc* odesc, const OutSpans& outs, const GeomDesc* desc,
                                   const GeomSpans& tiles, unsigned xcd_mask, const uint8_t* ofinal, int outW, int outH, uint8_t* tile_class, int n, hipStream_t s, bool fmt) {
   const int total = outs.wg[kMaxOutGroups];
-  if (n <= 0 || tiles.wg[kMaxGeoms] <= 0 || total < 0 || outs.ng < 0 || outs.ng > kMaxOutGroups || (total > 0 && (!groups || !odesc || outs.ng == 0 || outs.wg[0] != 0)))
-    return hipErrorInvalidValue;
-  for (int k = 0; k < kMaxOutGroups; k++)                               // a group's span is whole records; past the last group every span is empty
-    if (k < outs.ng ? (outs.per[k] <= 0 || outs.wg[k + 1] <= outs.wg[k] || (outs.wg[k + 1] - outs.wg[k]) % outs.per[k]) : outs.wg[k] != total) return hipErrorInvalidValue;
+  if (!out_spans_ok(outs, groups, odesc, tiles, n)) return hipErrorInvalidValue;
   if (tile_class) tile_class_geoms_k<<<dim3((unsigned)n), kThreads, 0, s>>>(classes, desc, tiles, ofinal, outW, outH, tile_class);
   mask_geoms_k<><<<dim3((unsigned)tiles.wg[kMaxGeoms]), kThreads, 0, s>>>(classes, desc, tiles, xcd_mask, ofinal, outW, outH, tile_class);      // (reads no frame)
   if (total > 0) {
     if (fmt) vg_outs_fmt_k<><<<dim3((unsigned)total), kThreads, 0, s>>>(groups, odesc, outs);
     else vg_outs_k<><<<dim3((unsigned)total), kThreads, 0, s>>>(groups, odesc, outs);
+  }
+  return hipGetLastError();
+}
+
+// ---- bsx_step_batch_vcam_geoms_outs_nv12: the same resize pass, every record written as NV12 into two pitched planes (kernels.hpp: VgNv12Rec) ----------------------
+// vg_outs_k / vg_outs_fmt_k with vcam_tile.inc's NV12 form (BSX_VT_NV12: a lane's two groups are a row pair; Y and 2 x 2-subsampled chroma stored from the registers
+// that hold the four pixels).  The record's second plane and its two pitches come from a table of their own, one 16-byte uniform load beside the descriptor's: GeomDesc
+// keeps its layout.  G.opt's output bits are not read.  Kernels of their own at the end of the file, in a namespace of their own (the reason is given above
+// mask_geoms_k): every earlier kernel's text is what it was.
+static_assert(sizeof(VgNv12Rec) == 16, "vg_nv12_rec reads a record as one uint4");
+namespace {
+struct Nv12Regs { uint8_t* uv; int pitch_y, pitch_uv; };
+__device__ __forceinline__ Nv12Regs vg_nv12_rec(const VgNv12Rec* __restrict__ rec, int n) {
+  const uint4 v = reinterpret_cast<const uint4*>(rec)[n];
+  typedef __attribute__((address_space(1))) uint8_t* gp;
+  return Nv12Regs{(uint8_t*)(gp)(((uint64_t)v.y << 32) | v.x), (int)v.z, (int)v.w};
+}
+
+template <int = 0>
+__global__ __launch_bounds__(kThreads) void vg_outs_nv12_k(const VgOutGroup* __restrict__ groups, const GeomDesc* __restrict__ odesc, const VgNv12Rec* __restrict__ nrec,
+                                                           OutSpans sp) {
+  int g, w0, r0, per;
+  out_span(sp, (int)blockIdx.x, &g, &w0, &r0, &per);
+  const unsigned local = blockIdx.x - (unsigned)w0, rl = local / (unsigned)per, tile_ = local - rl * (unsigned)per;
+  const VgOutGroup G = groups[g];                                     // (uniform index: scalar loads) — independent of the descriptor's and the plane record's
+  const GeomDescRegs d = geom_desc(odesc, r0 + (int)rl);
+  const Nv12Regs nv = vg_nv12_rec(nrec, r0 + (int)rl);
+  const int W = G.c.W, H = G.c.H, ntx = G.ntx;
+  int opt = 0;
+  const ResizeTab tab = geom_tab(G.c.tab);
+  const uint8_t *const frames = d.frame, *const bg = d.bg, *const masks = d.mask;
+  uint8_t *const out = d.out, *const out_uv = nv.uv;                  // the Y plane, the UV plane
+  const int pitch_y = nv.pitch_y, pitch_uv = nv.pitch_uv;
+  if ((W & 3) == 0 && ((((uintptr_t)frames) | ((uintptr_t)masks)) & 3) == 0) opt |= kVcWords;      // launch_vg_mixed's rule, per position
+  constexpr bool SEL = true, YIN = false;
+  constexpr long bg_stride = 0;
+  [[maybe_unused]] const int* const slot_of = nullptr;
+#define BSX_VT_NV12
+#define BSX_VT_TILE tile_
+#define BSX_VT_POS 0l                                                /* the record's own bases: index 0 of each */
+#define BSX_VT_DESC(fl) fl = d.flags
+  if (G.c.direct) {
+    constexpr bool DIRECT = true;
+#include "vcam_tile.inc"
+  } else {
+    constexpr bool DIRECT = false;
+#include "vcam_tile.inc"
+  }
+#undef BSX_VT_TILE
+#undef BSX_VT_POS
+#undef BSX_VT_DESC
+#undef BSX_VT_NV12
+}
+
+// vg_outs_nv12_k for a call with at least one YUYV item: vg_outs_fmt_k's choice per (form, format), one staging area for all four inclusions
+template <int = 0>
+__global__ __launch_bounds__(kThreads) void vg_outs_nv12_fmt_k(const VgOutGroup* __restrict__ groups, const GeomDesc* __restrict__ odesc,
+                                                               const VgNv12Rec* __restrict__ nrec, OutSpans sp) {
+  __shared__ uint32_t s_px[kVLdsWords];
+  int g, w0, r0, per;
+  out_span(sp, (int)blockIdx.x, &g, &w0, &r0, &per);
+  const unsigned local = blockIdx.x - (unsigned)w0, rl = local / (unsigned)per, tile_ = local - rl * (unsigned)per;
+  const VgOutGroup G = groups[g];                                     // (uniform index: scalar loads) — independent of the descriptor's and the plane record's
+  const GeomDescRegs d = geom_desc(odesc, r0 + (int)rl);
+  const Nv12Regs nv = vg_nv12_rec(nrec, r0 + (int)rl);
+  const int W = G.c.W, H = G.c.H, ntx = G.ntx;
+  int opt = 0;
+  const ResizeTab tab = geom_tab(G.c.tab);
+  const uint8_t *const frames = d.frame, *const bg = d.bg, *const masks = d.mask;
+  uint8_t *const out = d.out, *const out_uv = nv.uv;                  // the Y plane, the UV plane
+  const int pitch_y = nv.pitch_y, pitch_uv = nv.pitch_uv;
+  if ((W & 3) == 0 && ((((uintptr_t)frames) | ((uintptr_t)masks)) & 3) == 0) opt |= kVcWords;      // launch_vg_mixed's rule (the same for both formats), per position
+  constexpr bool SEL = true;
+  constexpr long bg_stride = 0;
+  [[maybe_unused]] const int* const slot_of = nullptr;
+#define BSX_VT_NV12
+#define BSX_VT_OWN_LDS
+#define BSX_VT_TILE tile_
+#define BSX_VT_POS 0l                                                /* the record's own bases: index 0 of each */
+#define BSX_VT_DESC(fl) fl = d.flags
+  if (d.flags & kGeomYuyvIn) {
+    constexpr bool YIN = true;
+    if (G.c.direct) {
+      constexpr bool DIRECT = true;
+#include "vcam_tile.inc"
+    } else {
+      constexpr bool DIRECT = false;
+#include "vcam_tile.inc"
+    }
+  } else {
+    constexpr bool YIN = false;
+    if (G.c.direct) {
+      constexpr bool DIRECT = true;
+#include "vcam_tile.inc"
+    } else {
+      constexpr bool DIRECT = false;
+#include "vcam_tile.inc"
+    }
+  }
+#undef BSX_VT_OWN_LDS
+#undef BSX_VT_TILE
+#undef BSX_VT_POS
+#undef BSX_VT_DESC
+#undef BSX_VT_NV12
+}
+
+// bsx_bgr_to_nv12: one lane per block of 4 x 2 pixels (the 2-pixel block that ends a row of w % 4 == 2 included) — the two rows' yuyv_pair words, a Y dword per row
+// and one UV dword, the arithmetic of the NV12 form of vcam_tile.inc.  WORDS: w % 4 == 0 and a 4-byte aligned source, three dwords per row; else bytes.
+template <bool WORDS>
+__global__ __launch_bounds__(kThreads) void bgr_to_nv12_k(const uint8_t* __restrict__ bgr, uint8_t* __restrict__ yp, int pitch_y, uint8_t* __restrict__ uvp, int pitch_uv,
+                                                         int w, int h) {
+  const unsigned gpr = ((unsigned)w + 3) / 4, i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= gpr * ((unsigned)h / 2)) return;
+  const int r = (int)(i / gpr), x = 4 * (int)(i - (unsigned)r * gpr), cnt = min(4, w - x);
+  const long n = blockIdx.y;
+  const uint8_t* const src = bgr + n * (long)w * h * 3;
+  uint32_t c[2], yw[2];
+#pragma unroll
+  for (int j = 0; j < 2; j++) {
+    const uint8_t* const p = src + ((long)(2 * r + j) * w + x) * 3;
+    uint32_t p0, p1;
+    if constexpr (WORDS) {
+      const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
+      const uint32_t a = q[0], b = q[1], e = q[2];
+      p0 = yuyv_pair(a & 255u, (a >> 8) & 255u, (a >> 16) & 255u, a >> 24, b & 255u, (b >> 8) & 255u);
+      p1 = yuyv_pair((b >> 16) & 255u, b >> 24, e & 255u, (e >> 8) & 255u, (e >> 16) & 255u, e >> 24);
+    } else {
+      p0 = yuyv_pair(p[0], p[1], p[2], p[3], p[4], p[5]);
+      p1 = cnt == 4 ? yuyv_pair(p[6], p[7], p[8], p[9], p[10], p[11]) : p0;
+    }
+    yw[j] = __builtin_amdgcn_perm(p1, p0, 0x06040200u);
+    c[j] = __builtin_amdgcn_perm(p1, p0, 0x07050301u);
+  }
+  const uint32_t uv = (c[0] & c[1]) + (((c[0] ^ c[1]) >> 1) & 0x7f7f7f7fu);      // per byte (a + b) / 2, truncating
+  uint8_t* const y0 = yp + (n * (long)h + 2 * r) * pitch_y + x;
+  uint8_t* const u0 = uvp + (n * (long)(h / 2) + r) * pitch_uv + x;
+  if (cnt == 4) {
+    *reinterpret_cast<uint32_t*>(y0) = yw[0]; *reinterpret_cast<uint32_t*>(y0 + pitch_y) = yw[1]; *reinterpret_cast<uint32_t*>(u0) = uv;
+  } else {
+    *reinterpret_cast<uint16_t*>(y0) = (uint16_t)yw[0]; *reinterpret_cast<uint16_t*>(y0 + pitch_y) = (uint16_t)yw[1]; *reinterpret_cast<uint16_t*>(u0) = (uint16_t)uv;
+  }
+}
+}  // namespace
+
+hipError_t launch_vcam_geoms_outs_nv12(const GeomClass* classes, const VgOutGroup* groups, const GeomDesc* odesc, const VgNv12Rec* nrec, const OutSpans& outs,
+                                       const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const uint8_t* ofinal, int outW, int outH, uint8_t* tile_class,
+                                       int n, hipStream_t s, bool fmt) {
+  const int total = outs.wg[kMaxOutGroups];
+  if (!out_spans_ok(outs, groups, odesc, tiles, n) || (total > 0 && !nrec)) return hipErrorInvalidValue;
+  if (tile_class) tile_class_geoms_k<<<dim3((unsigned)n), kThreads, 0, s>>>(classes, desc, tiles, ofinal, outW, outH, tile_class);
+  mask_geoms_k<><<<dim3((unsigned)tiles.wg[kMaxGeoms]), kThreads, 0, s>>>(classes, desc, tiles, xcd_mask, ofinal, outW, outH, tile_class);      // (reads no frame)
+  if (total > 0) {
+    if (fmt) vg_outs_nv12_fmt_k<><<<dim3((unsigned)total), kThreads, 0, s>>>(groups, odesc, nrec, outs);
+    else vg_outs_nv12_k<><<<dim3((unsigned)total), kThreads, 0, s>>>(groups, odesc, nrec, outs);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_bgr_to_nv12(const uint8_t* bgr, int w, int h, int n, uint8_t* y, int pitch_y, uint8_t* uv, int pitch_uv, hipStream_t s) {
+  if (w <= 0 || h <= 0 || n <= 0 || ((w | h) & 1) || pitch_y < w || pitch_uv < w || ((pitch_y | pitch_uv) & 3) || (((uintptr_t)y | (uintptr_t)uv) & 3))
+    return hipErrorInvalidValue;
+  const long blocks = (long)((w + 3) / 4) * (h / 2);
+  if (blocks >= (1l << 31)) return hipErrorInvalidValue;
+  const bool words = (w & 3) == 0 && ((uintptr_t)bgr & 3) == 0;
+  for (int n0 = 0; n0 < n; n0 += kMaxGridY) {
+    const int nn = n - n0 < kMaxGridY ? n - n0 : kMaxGridY;
+    const uint8_t* const src = bgr + (size_t)n0 * w * h * 3;
+    uint8_t* const yp = y + (size_t)n0 * h * pitch_y;
+    uint8_t* const up = uv + (size_t)n0 * (h / 2) * pitch_uv;
+    if (words) bgr_to_nv12_k<true><<<dim3(blocks_for(blocks), nn), kThreads, 0, s>>>(src, yp, pitch_y, up, pitch_uv, w, h);
+    else bgr_to_nv12_k<false><<<dim3(blocks_for(blocks), nn), kThreads, 0, s>>>(src, yp, pitch_y, up, pitch_uv, w, h);
   }
   return hipGetLastError();
 }

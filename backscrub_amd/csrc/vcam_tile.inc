@@ -9,6 +9,10 @@
 // MixDesc table that travels in `bg`), its mask is slot slot_of[n]'s (NULL: slot n); all of it is workgroup-uniform, so the tile's footprint below is the
 // workgroup's own.  Filter off: the composite is the frame (vcam_px / vcam_group with `off`); a background that is not 4-byte aligned takes the byte form for its
 // stream alone.
+// BSX_VT_NV12 (vg_outs_nv12_k, vg_outs_nv12_fmt_k; undefined, the text is what it was): the tile is written as NV12 into two pitched planes.  The includer also
+// provides out_uv, pitch_y, pitch_uv (`out` is the Y plane; dw and dh even).  A lane's two 4-pixel groups are vertically adjacent — rows 2 (tid / 16) and
+// 2 (tid / 16) + 1 of the tile instead of tid / 16 and tid / 16 + 16 — so it holds both rows of its 2 x 2 chroma blocks: per row one Y dword, per pair one UV dword
+// (16 bits each for the 2-pixel group that ends a row of out_w % 4 == 2), the chroma bytes those of yuyv_pair, averaged over the two rows as it averages two pixels.
 // BSX_VT_OWN_LDS (vg_geoms_fmt_k, which includes the body once per frame format): the includer declares s_px itself, one staging area for all of its inclusions.
 #ifndef BSX_VT_OWN_LDS
   __shared__ uint32_t s_px[DIRECT ? 1 : kVLdsWords];
@@ -58,10 +62,18 @@
 #undef BSX_VG_STAGE
     __syncthreads();
   }
+#ifndef BSX_VT_NV12
   const bool yout = (opt & kVcYuyvOut) != 0, owords = (opt & kVcOutWords) != 0;
+#else
+  uint32_t nv_c = 0;                                                 // the chroma bytes (Ca0, Cb0, Ca1, Cb1) of the pair's upper row, kept for the lower one
+#endif
 #pragma unroll
   for (int j = 0; j < 2; j++) {
+#ifndef BSX_VT_NV12
     const int gi = tid + j * kThreads, ry = gi / (kVW / 4), dy = dy0 + ry, dx = dx0 + 4 * (gi - ry * (kVW / 4));
+#else
+    const int ry = 2 * (tid / (kVW / 4)) + j, dy = dy0 + ry, dx = dx0 + 4 * (tid % (kVW / 4));      // dy0 and dh even: both rows of a pair are inside, or neither
+#endif
     if (dy > dy1 || dx > dx1) continue;
     const int sy = tab.yofs[dy], b0 = tab.ya[2 * dy], b1 = tab.ya[2 * dy + 1];
     int y0 = min(max(sy, 0), H - 1), y1 = min(max(sy + 1, 0), H - 1);
@@ -92,6 +104,24 @@
       q[k] = vcam_lerp(t00, t01, t10, t11, a0, a1, b0, b1, 0) | (vcam_lerp(t00, t01, t10, t11, a0, a1, b0, b1, 8) << 8) |
              (vcam_lerp(t00, t01, t10, t11, a0, a1, b0, b1, 16) << 16);
     }
+#ifdef BSX_VT_NV12
+    {                                                                // dw even: cnt is 2 or 4, whole pairs; every address below is a multiple of 4
+      const uint32_t p0 = yuyv_pair(q[0] & 255u, (q[0] >> 8) & 255u, q[0] >> 16, q[1] & 255u, (q[1] >> 8) & 255u, q[1] >> 16);
+      const uint32_t p1 = yuyv_pair(q[2] & 255u, (q[2] >> 8) & 255u, q[2] >> 16, q[3] & 255u, (q[3] >> 8) & 255u, q[3] >> 16);
+      const uint32_t yw = __builtin_amdgcn_perm(p1, p0, 0x06040200u), cw = __builtin_amdgcn_perm(p1, p0, 0x07050301u);
+      uint8_t* const yp = out + (n * (long)dh + dy) * pitch_y + dx;
+      if (cnt == 4) *reinterpret_cast<uint32_t*>(yp) = yw;
+      else *reinterpret_cast<uint16_t*>(yp) = (uint16_t)yw;
+      if (j == 0) {
+        nv_c = cw;
+      } else {
+        const uint32_t uv = (nv_c & cw) + (((nv_c ^ cw) >> 1) & 0x7f7f7f7fu);      // per byte (a + b) / 2, truncating
+        uint8_t* const up = out_uv + (n * (long)(dh >> 1) + (dy >> 1)) * pitch_uv + dx;
+        if (cnt == 4) *reinterpret_cast<uint32_t*>(up) = uv;
+        else *reinterpret_cast<uint16_t*>(up) = (uint16_t)uv;
+      }
+    }
+#else
     const long o = n * (long)dw * dh + (long)dy * dw + dx;
     if (yout) {                                                      // dw even: cnt is 2 or 4, whole pairs
       const uint32_t p0 = yuyv_pair(q[0] & 255u, (q[0] >> 8) & 255u, q[0] >> 16, q[1] & 255u, (q[1] >> 8) & 255u, q[1] >> 16);
@@ -113,4 +143,5 @@
           if (k < cnt) { op[3 * k] = (uint8_t)q[k]; op[3 * k + 1] = (uint8_t)(q[k] >> 8); op[3 * k + 2] = (uint8_t)(q[k] >> 16); }
       }
     }
+#endif
   }

@@ -28,6 +28,7 @@
  *   bsx_step_batch_geoms   … for streams of different capture sizes together: one prep launch, one network pass, one tile launch  app/deepseg.cc:634-673
  *   bsx_step_batch_vcam_geoms  … the same streams, every composite written at the virtual camera's one size  app/deepseg.cc:634-681
  *   bsx_step_batch_vcam_geoms_outs  … the same streams, several outputs per stream, each of its own size (speaker + thumbnails, simulcast layers)
+ *   bsx_step_batch_vcam_geoms_outs_nv12  … every output an NV12 surface with row pitches, for a video encoder (bsx_bgr_to_nv12: the stand-alone conversion)
  *   bsx_reset_streams      bsx_reset for a chosen subset of the streams (a slot reused for a new camera)
  *                          (set_input_frame → mask → alpha_blend), batched
  *   bsx_resize_bgr         grab_background() cv::resize   app/background.cc:178-194
@@ -366,6 +367,37 @@ typedef struct bsx_vcam_out { int item; int out_w, out_h; uint8_t* d_out; } bsx_
 BSX_API int bsx_step_batch_vcam_geoms_outs(bsx_ctx* ctx, const int* ids, const bsx_geom_item* items, int n, const bsx_vcam_out* outs, int m, void* stream,
                                            unsigned flags);
 
+/* bsx_step_batch_vcam_geoms_outs writing every record as an NV12 SURFACE: a Y plane and an interleaved UV plane of half the rows, each with a row pitch — what a
+ * video encoder takes (a 160-wide simulcast layer in rows of 256 bytes).  The resize pass holds each group of four output pixels as B, G, R when it packs them; it
+ * stores Y and 2x2-subsampled chroma from there, 1.5 B/px, instead of a packed image that one conversion pass per layer size would read back.
+ * The definition.  No reference code writes 4:2:0, so NV12 is derived from the reference's own 4:2:2 packer: an NV12 output is a pure function of the YUYV output the
+ * library already produces.  For an output image C (BGR, out_w x out_h, both even) let Q = bsx_bgr_to_yuyv(C): [out_h][out_w / 2] words of bytes (Y0, Ca, Y1, Cb),
+ * the bytes of convert_rgb_to_yuyv (app/deepseg.cc:87-106).  Then
+ *     Y[y][2c] = Q[y][c].Y0,  Y[y][2c + 1] = Q[y][c].Y1                                            [out_h] rows of pitch_y bytes
+ *     UV[r][2c] = (Q[2r][c].Ca + Q[2r + 1][c].Ca) / 2,  UV[r][2c + 1] = (Q[2r][c].Cb + Q[2r + 1][c].Cb) / 2      [out_h / 2] rows of pitch_uv bytes
+ * the division integer and truncating: the reference's own averaging of two chroma samples (deepseg.cc:98-99) applied to the two rows.  Ca is the byte a YUYV
+ * consumer reads as U, so the plane is U, V interleaved: NV12.  Bytes [out_w, pitch) of every row of both planes are NOT written.
+ *   - everything of bsx_step_batch_vcam_geoms_outs but the output form: the ids / items rules, BSX_MAX_OUTS_PER_ITEM and BSX_MAX_OUT_SIZES, the table cache and the
+ *     staging ring (no host synchronisation unless four calls ahead), the front (one prep launch, the network, one tile-class launch, one masks-only tile launch),
+ *     ONE resize pass over all records;
+ *   - result: the planes of outs[j] are the definition applied to the BGR image bsx_step_batch_vcam_geoms_outs writes for that item at that size; persistent masks
+ *     and ofinal of every stream of the context are byte-identical to bsx_step_batch_geoms'.  Works on every context (bsx_new, bsx_new_geoms, bsx_new_geoms_ex with
+ *     BSX_GEOMS_EDGE_ROI).  n == 0: returns 0 and enqueues nothing.  m == 0 with n > 0 is a masks-only step;
+ *   - flags: 0;
+ *   - BSX_EINVAL before anything is enqueued, with a bsx_last_error text naming outs[j] or items[i] and the value, for: every refusal of
+ *     bsx_step_batch_vcam_geoms_outs that still applies; any bit in flags; an odd out_w or out_h; a pitch below out_w or not a multiple of 4; a NULL or not 4-byte
+ *     aligned plane; a plane overlapping any frame, background or other plane of the call, its own record's second plane included.  A refused call changes no state;
+ *   - overlap is judged on a plane's byte extent pitch * (rows - 1) + out_w: two records that interleave their rows inside one canvas are refused.
+ * Out of scope: writing a mosaic (several records into one canvas), I420 / three-plane output, NV12 input, odd sizes. */
+typedef struct bsx_vcam_out_nv12 {
+  int item; int out_w, out_h;          /* as bsx_vcam_out; out_w and out_h even */
+  int pitch_y, pitch_uv;               /* bytes per row of each plane: multiples of 4, >= out_w */
+  uint8_t* d_y;                        /* [out_h][pitch_y], 4-byte aligned */
+  uint8_t* d_uv;                       /* [out_h / 2][pitch_uv], 4-byte aligned */
+} bsx_vcam_out_nv12;
+BSX_API int bsx_step_batch_vcam_geoms_outs_nv12(bsx_ctx* ctx, const int* ids, const bsx_geom_item* items, int n, const bsx_vcam_out_nv12* outs, int m, void* stream,
+                                                unsigned flags /* 0 */);
+
 /* Reset the temporal state of the listed streams only (ofinal → 0, persistent mask → 255, as bsx_reset does for all) — a slot reused for a new camera.  The
  * other streams' state is untouched, and a pending pipelined composite is NOT dropped: the call is refused (BSX_EINVAL) while one is pending.  Same ids rules,
  * errors and staging as bsx_step_batch_streams; asynchronous on `stream`. */
@@ -441,6 +473,13 @@ BSX_API int bsx_resize_bgr_batch(bsx_ctx* ctx, const bsx_resize_item* items, int
 
 /* BGR u8 [n][h][w][3] -> YUYV 4:2:2 [n][h][w][2] exactly as convert_rgb_to_yuyv (byte order Y0 V Y1 U). */
 BSX_API int bsx_bgr_to_yuyv(bsx_ctx* ctx, const uint8_t* d_bgr, uint8_t* d_yuyv, int w, int h, int n, void* stream);
+
+/* BGR u8 [n][h][w][3] -> NV12 in pitched planes, by the definition at bsx_step_batch_vcam_geoms_outs_nv12: an NV12 image is a pure function of the YUYV image
+ * bsx_bgr_to_yuyv writes.  Image i's planes are at d_y + i * pitch_y * h ([h] rows of pitch_y bytes) and d_uv + i * pitch_uv * (h / 2) ([h / 2] rows of pitch_uv
+ * bytes); bytes [w, pitch) of every row are not written.  The stand-alone form for callers of the other steps.  Works on a context of several classes (w, h are
+ * the call's own).  BSX_EINVAL, with a bsx_last_error text, for: a NULL pointer; w, h or n not positive; an odd w or h; a pitch below w or not a multiple of 4; a
+ * plane that is not 4-byte aligned.  The planes must not overlap each other or the source (not checked). */
+BSX_API int bsx_bgr_to_nv12(bsx_ctx* ctx, const uint8_t* d_bgr, int w, int h, int n, uint8_t* d_y, int pitch_y, uint8_t* d_uv, int pitch_uv, void* stream);
 
 /* YUYV 4:2:2 (bytes Y0 U Y1 V) [n][h][w][2] -> BGR u8 [n][h][w][3], exactly cv::cvtColor(COLOR_YUV2BGR_YUYV): the conversion
  * cv::VideoCapture applies to raw camera frames for the reference (app/deepseg.cc:553, :725).  Lets a caller upload 2 B/px. */
