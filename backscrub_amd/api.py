@@ -80,6 +80,10 @@ class _VcamOutNv12(C.Structure):            # bsx.h bsx_vcam_out_nv12
     _fields_ = [("item", C.c_int), ("out_w", C.c_int), ("out_h", C.c_int), ("pitch_y", C.c_int), ("pitch_uv", C.c_int), ("d_y", C.c_void_p), ("d_uv", C.c_void_p)]
 
 
+class _SurfaceItem(C.Structure):            # bsx.h bsx_surface_item
+    _fields_ = [("d_y", C.c_void_p), ("d_uv", C.c_void_p), ("pitch_y", C.c_int), ("pitch_uv", C.c_int), ("setting", _StreamSetting)]
+
+
 class StreamSetting:
     """one stream's settings for MaskGen.step_mixed — what one reference process takes as -b <image> (bg), -H / -V (flip_h / flip_v), -p bgblur:<k> (bgblur)
     and toggles at run time with the s / h / v keys (filter_off, flip_h, flip_v; app/deepseg.cc:387-437, 624-673, 777-790).  bg: a cuda uint8 [H,W,3] image
@@ -133,6 +137,7 @@ SYMBOLS = [
     ("bsx_step_batch_vcam_geoms_outs", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(_GeomItem), C.c_int, C.POINTER(_VcamOut), C.c_int, C.c_void_p, C.c_uint]),
     ("bsx_step_batch_vcam_geoms_outs_nv12", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(_GeomItem), C.c_int, C.POINTER(_VcamOutNv12), C.c_int, C.c_void_p,
                                                       C.c_uint]),
+    ("bsx_step_batch_surfaces", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(_SurfaceItem), C.c_int, C.POINTER(_VcamOutNv12), C.c_int, C.c_void_p, C.c_uint]),
     ("bsx_step_batch_mixed", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(_StreamSetting), C.c_void_p, C.c_int, C.c_void_p, C.c_uint]),
     ("bsx_step_batch_vcam_mixed", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.POINTER(_StreamSetting), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                             C.c_uint]),
@@ -140,6 +145,7 @@ SYMBOLS = [
     ("bsx_resize_bgr_batch", C.c_int, [C.c_void_p, C.POINTER(_ResizeItem), C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("bsx_bgr_to_yuyv", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("bsx_bgr_to_nv12", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    ("bsx_nv12_to_bgr", C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     ("bsx_yuyv_to_bgr", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("bsx_background_load", C.c_void_p, [C.c_void_p, C.c_char_p, C.c_int]),
     ("bsx_background_from_frames", C.c_void_p, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int]),
@@ -487,6 +493,12 @@ class MaskGen:
         bytes of the YUYV output of step_vcam_geoms_outs, the chroma averaged (truncating) over each pair of rows; bytes past out_w of a row are not written."""
         outs = list(outs)
         arr, n, items, _ok = self._vcam_outs_items(ids, frames, settings, "step_vcam_geoms_outs_nv12")
+        recs, m = self._nv12_out_records(outs, n)
+        _check(lib().bsx_step_batch_vcam_geoms_outs_nv12(self.h, arr, items, n, recs, m, _stream_ptr(), 0), self.h, "bsx_step_batch_vcam_geoms_outs_nv12")
+        return [(y, uv) for _i, y, uv in outs]
+
+    def _nv12_out_records(self, outs, n):
+        """the NV12 output records of a call of n positions, validated: (ctypes records, m).  outs: a list of (item_index, y, uv)"""
         m = len(outs)
         recs = (_VcamOutNv12 * max(m, 1))()
         named, sizes = {}, []
@@ -506,7 +518,46 @@ class MaskGen:
                     raise BsxError("outs[%d]: %d x %d is distinct output size %d of the call (at most %d)" % (j, ow, oh, len(sizes), BSX_MAX_OUT_SIZES))
             r = recs[j]
             r.item, r.out_w, r.out_h, r.pitch_y, r.pitch_uv, r.d_y, r.d_uv = int(item), ow, oh, py, puv, y.data_ptr(), uv.data_ptr()
-        _check(lib().bsx_step_batch_vcam_geoms_outs_nv12(self.h, arr, items, n, recs, m, _stream_ptr(), 0), self.h, "bsx_step_batch_vcam_geoms_outs_nv12")
+        return recs, m
+
+    def step_surfaces(self, ids, surfaces, settings, outs):
+        """step_vcam_geoms_outs_nv12 whose frames are NV12 surfaces too, as a video decoder leaves them (bsx_step_batch_surfaces): surfaces is a sequence of (y, uv),
+        one per id — y a cuda uint8 view [H, W] with strides (pitch_y, 1), uv [H / 2, W] with strides (pitch_uv, 1), U and V interleaved, at the capture size of the
+        stream's class; pitches multiples of 4, both planes 4-byte aligned; bytes past W of a row are never read.  The BGR frame of a surface is nv12_to_bgr of it.
+        settings: flip_h / flip_v / filter_off and bg (no bgblur, no yuyv_in); outs: as step_vcam_geoms_outs_nv12."""
+        arr, n = _ids(ids)
+        surfaces, settings, outs = list(surfaces), list(settings), list(outs)
+        if len(surfaces) != n or len(settings) != n:
+            raise BsxError("%d ids for %d surfaces and %d settings" % (n, len(surfaces), len(settings)))
+        torch = _torch()
+        items = (_SurfaceItem * max(n, 1))()
+        for i in range(n):
+            g = self._geom_of(int(arr[i]))
+            H, W = g["height"], g["width"]
+            if not isinstance(surfaces[i], (tuple, list)) or len(surfaces[i]) != 2:
+                raise BsxError("surfaces[%d] must be a pair (y, uv)" % i)
+            y, uv = surfaces[i]
+            sw, sh, py, puv = self._nv12_planes("surfaces[%d]" % i, y, uv)
+            if (sw, sh) != (W, H):
+                raise BsxFrameFormatError("surfaces[%d] is %d x %d, stream %d captures %d x %d" % (i, sw, sh, arr[i], W, H))
+            s = settings[i]
+            if not isinstance(s, StreamSetting):
+                raise BsxError("settings[%d] is not a StreamSetting" % i)
+            if s.bgblur:
+                raise BsxError("settings[%d]: bgblur is not taken by step_surfaces" % i)
+            if s.yuyv_in:
+                raise BsxError("settings[%d]: yuyv_in is not taken by step_surfaces (every frame is an NV12 surface)" % i)
+            if not s.filter_off and s.bg is None:
+                raise BsxError("settings[%d]: bg is required unless filter_off is set" % i)
+            if s.bg is not None and not (isinstance(s.bg, torch.Tensor) and s.bg.dtype == torch.uint8 and self._on_device(s.bg) and
+                                         tuple(s.bg.shape) == (H, W, 3) and s.bg.is_contiguous()):
+                raise BsxError("settings[%d].bg must be a contiguous cuda:%d uint8 tensor [%d,%d,3] (stream %d)" % (i, self.device, H, W, arr[i]))
+            it = items[i]
+            it.d_y, it.d_uv, it.pitch_y, it.pitch_uv = y.data_ptr(), uv.data_ptr(), py, puv
+            it.setting.d_bg = s.bg.data_ptr() if s.bg is not None else None
+            it.setting.flags = s.flags()
+        recs, m = self._nv12_out_records(outs, n)
+        _check(lib().bsx_step_batch_surfaces(self.h, arr, items, n, recs, m, _stream_ptr(), 0), self.h, "bsx_step_batch_surfaces")
         return [(y, uv) for _i, y, uv in outs]
 
     # ---- batched device path -----------------------------------------------------------------
@@ -819,6 +870,33 @@ class MaskGen:
         _check(lib().bsx_bgr_to_nv12(self.h, C.c_void_p(bgr.data_ptr()), w, h, n, C.c_void_p(y.data_ptr()), pitch[0], C.c_void_p(uv.data_ptr()), pitch[1],
                                      _stream_ptr()), self.h, "bsx_bgr_to_nv12")
         return y[:, :, :w], uv[:, :, :w]
+
+    def nv12_to_bgr(self, y, uv, w=None, h=None):
+        """NV12 surfaces → [n,h,w,3] u8 device frames (bsx_nv12_to_bgr), the counterpart of bgr_to_nv12 and of its layout: y a cuda uint8 view [n, h, w] (or [h, w])
+        with strides (h * pitch_y, pitch_y, 1), uv [n, h / 2, w] with strides (h / 2 * pitch_uv, pitch_uv, 1), U and V interleaved — the images' planes one behind
+        the other.  w, h: checked against the views where given.  Bytes past w of a row are not read."""
+        torch = _torch()
+        for name, t in (("y", y), ("uv", uv)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() not in (2, 3) or t.numel() == 0:
+                raise BsxFrameFormatError("nv12_to_bgr: %s must be a non-empty uint8 tensor [n,rows,w] or [rows,w]" % name)
+            if not self._on_device(t):
+                raise BsxError("nv12_to_bgr: %s must be on cuda:%d (it is on %s)" % (name, self.device, t.device))
+        if y.dim() != uv.dim():
+            raise BsxFrameFormatError("nv12_to_bgr: y has %d dimensions and uv %d" % (y.dim(), uv.dim()))
+        y3, uv3 = (y, uv) if y.dim() == 3 else (y[None], uv[None])
+        n = int(y3.shape[0])
+        if int(uv3.shape[0]) != n:
+            raise BsxFrameFormatError("nv12_to_bgr: y holds %d images and uv %d" % (n, int(uv3.shape[0])))
+        sw, sh, py, puv = self._nv12_planes("nv12_to_bgr", y3[0], uv3[0])
+        if (w is not None and int(w) != sw) or (h is not None and int(h) != sh):
+            raise BsxFrameFormatError("nv12_to_bgr: the views are %d x %d, not w = %r, h = %r" % (sw, sh, w, h))
+        if n > 1 and (y3.stride(0) != sh * py or uv3.stride(0) != sh // 2 * puv):
+            raise BsxFrameFormatError("nv12_to_bgr: image i's planes must lie at i * h * pitch_y and i * (h / 2) * pitch_uv (strides %d and %d, pitches %d and %d)" % (
+                y3.stride(0), uv3.stride(0), py, puv))
+        out = torch.empty((n, sh, sw, 3), dtype=torch.uint8, device=y.device)
+        _check(lib().bsx_nv12_to_bgr(self.h, C.c_void_p(y3.data_ptr()), py, C.c_void_p(uv3.data_ptr()), puv, sw, sh, n, C.c_void_p(out.data_ptr()), _stream_ptr()),
+               self.h, "bsx_nv12_to_bgr")
+        return out if y.dim() == 3 else out[0]
 
     def flip_bgr(self, bgr, code):
         """cv::flip(bgr, out, code) for [n,h,w,3] u8 device frames (deepseg.cc:667-673): 0 vertical, >0 horizontal, <0 both."""

@@ -29,6 +29,7 @@
 #include "tflite_model.hpp"
 #include "vcam_nv12_plan.hpp"
 #include "vcam_outs_plan.hpp"
+#include "vcam_surface_plan.hpp"
 
 using namespace bsx;
 
@@ -219,8 +220,13 @@ struct bsx_ctx {
   size_t mask_bytes = 0;                    // the whole d_masks allocation
   GeomClass* d_geom_classes = nullptr;      // device copy of the class records (uploaded by bsx_new_geoms; for a one-class context on its first geoms step)
   uint8_t* d_geom_tile_class = nullptr;     // one byte per workgroup of the largest ragged tile grid (every stream of every class) + 4; null: BSX_NO_UNIFORM_TILES
-  GeomDesc* h_geo = nullptr;                // pinned [kIdRing][n_streams]: the descriptors of a geoms step, ordered by class (the ring entries and events of the ids)
+  GeomDesc* h_geo = nullptr;                // pinned [kIdRing][geo_entry_bytes()]: the descriptors of a geoms step, ordered by class (the ring entries and events of the ids)
   GeomDesc* d_geo = nullptr;                // device, likewise
+  // an entry: n_streams GeomDesc, then room for n_streams VgSurfRec — bsx_step_batch_surfaces puts its n surface records right behind its n descriptors, so that
+  // its copy is one too
+  size_t geo_entry_bytes() const { return (size_t)n_streams * (sizeof(GeomDesc) + sizeof(VgSurfRec)); }
+  GeomDesc* geo_entry(GeomDesc* ring, int k) const { return reinterpret_cast<GeomDesc*>(reinterpret_cast<uint8_t*>(ring) + (size_t)k * geo_entry_bytes()); }
+  std::vector<bsx_geom_item> sf_items;      // host scratch of bsx_step_batch_surfaces: its items as geoms_front takes them (d_frame = the Y plane)
   std::vector<int> geo_order, geo_ids;      // host scratch: the call's positions ordered by class, their stream ids in that order
   // bsx_step_batch_vcam_geoms: per output size the device array of one VgClass per class (kernels.hpp) — capture size, capture -> output table, per-tap bit — built
   // and uploaded on the first call at that size.  Class 0's table is the one in vcam_tabs (shared with bsx_step_batch_vcam); the others' memory is owned here.
@@ -309,7 +315,7 @@ int model_type_from_name(const std::string& n) {  // lib/libbackscrub.cc:116-130
 // Idempotent: bsx_new_geoms calls it for a context of several classes, the first geoms step of a one-class context does (like h_mix: allocated on first use).
 int geoms_device_state(bsx_ctx* c) {
   if (c->d_geo) return BSX_OK;
-  const size_t G = c->geoms.size(), N = (size_t)c->n_streams;
+  const size_t G = c->geoms.size();
   std::vector<GeomClass> rec(G), rec_vg(G);
   size_t tiles = 0;
   bool any_edge = false;
@@ -334,8 +340,8 @@ int geoms_device_state(bsx_ctx* c) {
     BSX_HIP(c, hipMalloc(&c->d_geom_tile_class, tiles + 4));        // (+4: the tile kernel reads the aligned word around a byte)
     BSX_HIP(c, hipMemset(c->d_geom_tile_class, 0, tiles + 4));
   }
-  if (!c->h_geo) BSX_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_geo), bsx_ctx::kIdRing * N * sizeof(GeomDesc), hipHostMallocDefault));
-  BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_geo), bsx_ctx::kIdRing * N * sizeof(GeomDesc)));
+  if (!c->h_geo) BSX_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_geo), bsx_ctx::kIdRing * c->geo_entry_bytes(), hipHostMallocDefault));
+  BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_geo), bsx_ctx::kIdRing * c->geo_entry_bytes()));
   return BSX_OK;
 }
 
@@ -1258,7 +1264,10 @@ int geoms_check(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item*
 // edge: some position's class is off the 4-pixel grid (bsx_new_geoms_ex) — the geoms step then takes launch_mask_blend_geoms_edge
 struct GeomsStaged { const GeomDesc* desc = nullptr; GeomSpans tiles{}, outside{}; unsigned xcd_mask = 0; bool fmt = false, edge = false; };      // fmt: some item is YUYV — the *_fmt launchers
 // vg: the tile grid of the vcam step (ROI-anchored tile columns for every class)
-int geoms_front(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item* items, int n, hipStream_t s, int k, GeomsStaged* st, bool vg = false) {
+// surf (bsx_step_batch_surfaces): items[i].d_frame is the Y plane of the NV12 surface surf[i] — the surface records follow the descriptors in the ring entry, a
+// descriptor names its position in pad[0], and the prep launch is launch_prep_geoms_nv12
+int geoms_front(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item* items, int n, hipStream_t s, int k, GeomsStaged* st, bool vg = false,
+                const bsx_surface_item* surf = nullptr) {
   const int G = (int)c->geoms.size();
   // positions ordered by class (a counting sort: stable, so a class keeps the caller's order)
   int count[kMaxGeoms] = {0};
@@ -1282,7 +1291,8 @@ int geoms_front(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item*
   int next[kMaxGeoms];
   for (int g = 0; g < kMaxGeoms; g++) next[g] = tiles.pos[g];
   for (int i = 0; i < n; i++) c->geo_order[(size_t)next[c->geom_of(ids[i])]++] = i;
-  GeomDesc* hd = c->h_geo + (size_t)k * c->n_streams;
+  GeomDesc* hd = c->geo_entry(c->h_geo, k);
+  VgSurfRec* const hs = reinterpret_cast<VgSurfRec*>(hd + n);          // (48 n bytes behind a 16-byte aligned address)
   for (int j = 0; j < n; j++) {
     const int i = c->geo_order[(size_t)j], id = ids[i];
     const bsx_ctx::Geom& q = c->geoms[c->geom_of(id)];
@@ -1291,17 +1301,19 @@ int geoms_front(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item*
     const bool off = (it.setting.flags & BSX_STREAM_FILTER_OFF) != 0;
     hd[j] = GeomDesc{it.d_frame, it.d_out, off ? nullptr : it.setting.d_bg, c->d_masks + q.mask_offset + (size_t)(id - q.first) * q.width * q.height,
                      it.setting.flags & (kMixFlipH | kMixFlipV | kMixFilterOff | kGeomYuyvIn), id, {0, 0}};
+    if (surf) { hd[j].pad[0] = j; hs[j] = VgSurfRec{surf[i].d_uv, surf[i].pitch_y, surf[i].pitch_uv}; }
   }
   st->fmt = geoms_any_yuyv(items, n);
   const int* d_ids = nullptr;
   if (const int rc = ids_copy(c, c->geo_ids.data(), n, s, k, &d_ids)) return rc;
-  GeomDesc* const dd = c->d_geo + (size_t)k * c->n_streams;
-  BSX_HIP(c, hipMemcpyAsync(dd, hd, (size_t)n * sizeof(GeomDesc), hipMemcpyHostToDevice, s));
+  GeomDesc* const dd = c->geo_entry(c->d_geo, k);
+  BSX_HIP(c, hipMemcpyAsync(dd, hd, (size_t)n * (sizeof(GeomDesc) + (surf ? sizeof(VgSurfRec) : 0)), hipMemcpyHostToDevice, s));
   st->desc = dd;
   {
     bsx_roctx::Range range("bsx:prep");
     float* f32 = !c->in_u8 ? c->tensor_ptr(c->plan.input) : nullptr;
-    BSX_HIP(c, (st->fmt ? launch_prep_geoms_fmt : launch_prep_geoms)(c->d_geom_classes, dd, prep, f32, c->in_u8 ? c->d_net_in_u8 : nullptr, c->inW, c->inH, c->bilateral, n, s));
+    if (surf) BSX_HIP(c, launch_prep_geoms_nv12(c->d_geom_classes, dd, reinterpret_cast<const VgSurfRec*>(dd + n), prep, f32, c->in_u8 ? c->d_net_in_u8 : nullptr, c->inW, c->inH, c->bilateral, n, s));
+    else BSX_HIP(c, (st->fmt ? launch_prep_geoms_fmt : launch_prep_geoms)(c->d_geom_classes, dd, prep, f32, c->in_u8 ? c->d_net_in_u8 : nullptr, c->inW, c->inH, c->bilateral, n, s));
   }
   return infer_after_prep(c, n, s, 0, d_ids);
 }
@@ -1491,9 +1503,61 @@ int vcam_nv12_check(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_i
   return BSX_OK;
 }
 
+// ... of bsx_step_batch_surfaces: vcam_nv12_check with the items' frames NV12 surfaces — the item checks and the class admission by vcam_surface_plan.hpp, an input
+// plane's extent pitch * (rows - 1) + W.  Leaves the items as geoms_front takes them in sf_items.
+int vcam_surfaces_check(bsx_ctx* c, const char* fn, const int* ids, const bsx_surface_item* items, int n, const bsx_vcam_out_nv12* outs, int m, unsigned flags,
+                        VcamOutsPlan* plan) {
+  if (!items) return refuse(c, fn, "items is NULL");
+  if (flags) return refuse(c, fn, "flags 0x%x: this step takes no flags (an item's flips belong to items[i].setting.flags)", flags);
+  if (const int rc = refuse_pending(c, fn)) return rc;
+  if (c->onmask) return refuse(c, fn, "needs the fused mask route (no onmask callback)");
+  std::vector<bsx_ctx::Span>& sp = c->rsz_spans;
+  sp.clear();
+  c->vo_class.resize((size_t)n);
+  c->sf_items.resize((size_t)n);
+  SurfaceRefusal why;
+  for (int i = 0; i < n; i++) {
+    const bsx_surface_item& it = items[i];
+    const int g = c->geom_of(ids[i]);
+    const bsx_ctx::Geom& G = c->geoms[g];
+    c->vo_class[(size_t)i] = g;
+    if (!vcam_surface_item(it, i, G.width, G.height, &why)) return refuse(c, fn, "%s", why.text);
+    if (!G.fusable)
+      return refuse(c, fn, "items[%d]: stream %d is of class %d (%d x %d), which is off the fused tile route (width, roi.x, roi.w multiples of 4, a tiled linear mask up-scale)",
+                    i, ids[i], g, G.width, G.height);
+    if (!vcam_surface_class(i, ids[i], g, G.width, G.height, G.tab_down.tab.mode, G.roi.w, G.roi.h, &why)) return refuse(c, fn, "%s", why.text);
+    c->sf_items[(size_t)i] = bsx_geom_item{it.d_y, nullptr, it.setting};
+    // Span::item of an input: 3 i for d_y, 3 i + 1 for d_uv, 3 i + 2 for the background
+    sp.push_back({(uintptr_t)it.d_y, (uintptr_t)it.d_y + vcam_nv12_extent(it.pitch_y, G.height, G.width), 3 * i, false});
+    sp.push_back({(uintptr_t)it.d_uv, (uintptr_t)it.d_uv + vcam_nv12_extent(it.pitch_uv, G.height / 2, G.width), 3 * i + 1, false});
+    if (it.setting.flags & BSX_STREAM_FILTER_OFF) continue;          // reads no background
+    sp.push_back({(uintptr_t)it.setting.d_bg, (uintptr_t)it.setting.d_bg + (size_t)G.width * G.height * 3, 3 * i + 2, false});
+  }
+  const int pr = vcam_nv12_plan(c->vo_class.data(), n, outs, m, plan);
+  if (pr == VcamOutsPlan::kRefused) return refuse(c, fn, "%s", plan->text);
+  if (pr == VcamOutsPlan::kTooLarge) { c->last_error = std::string("error: ") + fn + ": the batch needs more than 2^31 workgroups\n"; return BSX_EDEVICE; }
+  for (int j = 0; j < m; j++) {
+    const bsx_vcam_out_nv12& r = outs[j];
+    sp.push_back({(uintptr_t)r.d_y, (uintptr_t)r.d_y + vcam_nv12_extent(r.pitch_y, r.out_h, r.out_w), 2 * j, true});
+    sp.push_back({(uintptr_t)r.d_uv, (uintptr_t)r.d_uv + vcam_nv12_extent(r.pitch_uv, r.out_h / 2, r.out_w), 2 * j + 1, true});
+  }
+  const bsx_ctx::Span* d = nullptr;
+  const bsx_ctx::Span* o = nullptr;
+  if (spans_overlap(sp, &d, &o)) {
+    const char* const plane = (d->item & 1) ? "d_uv" : "d_y";
+    if (o->dst)
+      return refuse(c, fn, "outs[%d]: %s %p overlaps %s of outs[%d] (%p)", d->item / 2, plane, (const void*)d->begin, (o->item & 1) ? "d_uv" : "d_y", o->item / 2,
+                    (const void*)o->begin);
+    static const char* const kIn[3] = {"d_y", "d_uv", "setting.d_bg"};
+    return refuse(c, fn, "outs[%d]: %s %p overlaps %s of items[%d] (%p)", d->item / 2, plane, (const void*)d->begin, kIn[o->item % 3], o->item / 3, (const void*)o->begin);
+  }
+  return BSX_OK;
+}
+
 // outs: the BGR / YUYV records; nv12 (outs NULL): the NV12 records, whose plane records follow the descriptors in the ring entry
+// surf (with nv12): the items' frames are NV12 surfaces (geoms_front's surf); the resize pass is launch_vcam_geoms_outs_nv12in's
 int vcam_outs_run(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item* items, int n, const bsx_vcam_out* outs, const bsx_vcam_out_nv12* nv12,
-                  const VcamOutsPlan& plan, hipStream_t s, unsigned flags, int k) {
+                  const VcamOutsPlan& plan, hipStream_t s, unsigned flags, int k, const bsx_surface_item* surf = nullptr) {
   const size_t eb = c->vo_entry_bytes(), m = plan.order.size();
   if (!c->h_vo) BSX_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_vo), bsx_ctx::kIdRing * eb, hipHostMallocDefault));
   if (!c->d_vo) BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_vo), bsx_ctx::kIdRing * eb));
@@ -1504,11 +1568,11 @@ int vcam_outs_run(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_ite
     if (const int rc = vg_geoms_records(c, plan.sizes[q][0], plan.sizes[q][1], &dev, &rec[q])) return rc;
   }
   GeomsStaged st;
-  if (const int rc = geoms_front(c, fn, ids, items, n, s, k, &st, true)) return rc;
+  if (const int rc = geoms_front(c, fn, ids, items, n, s, k, &st, true, surf)) return rc;
   // groups and output descriptors into ring entry k: a record's descriptor is its position's (geoms_front left them in the pinned entry) with `out` replaced
   VgOutGroup* const hg = reinterpret_cast<VgOutGroup*>(c->h_vo + (size_t)k * eb);
   GeomDesc* const ho = reinterpret_cast<GeomDesc*>(hg + kMaxOutGroups);
-  const GeomDesc* const hd = c->h_geo + (size_t)k * c->n_streams;
+  const GeomDesc* const hd = c->geo_entry(c->h_geo, k);
   c->vo_pos.resize((size_t)n);
   for (int j = 0; j < n; j++) c->vo_pos[(size_t)c->geo_order[(size_t)j]] = j;
   OutSpans sp{};
@@ -1539,6 +1603,13 @@ int vcam_outs_run(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_ite
   const size_t desc_at = (size_t)kMaxOutGroups * sizeof(VgOutGroup), nrec_at = desc_at + m * sizeof(GeomDesc);
   if (m) BSX_HIP(c, hipMemcpyAsync(dv, hg, nrec_at + (nv12 ? m * sizeof(VgNv12Rec) : 0), hipMemcpyHostToDevice, s));
   bsx_roctx::Range range("bsx:mask+vcam");
+  if (surf) {
+    BSX_HIP(c, launch_vcam_geoms_outs_nv12in(c->d_geom_classes_vg ? c->d_geom_classes_vg : c->d_geom_classes, reinterpret_cast<const VgOutGroup*>(dv),
+                                             reinterpret_cast<const GeomDesc*>(dv + desc_at), reinterpret_cast<const VgNv12Rec*>(dv + nrec_at),
+                                             reinterpret_cast<const VgSurfRec*>(st.desc + n), sp, st.desc, st.tiles, st.xcd_mask, c->d_ofinal, c->outW, c->outH,
+                                             c->d_geom_tile_class, n, s));
+    return BSX_OK;
+  }
   if (nv12) {
     BSX_HIP(c, launch_vcam_geoms_outs_nv12(c->d_geom_classes_vg ? c->d_geom_classes_vg : c->d_geom_classes, reinterpret_cast<const VgOutGroup*>(dv),
                                            reinterpret_cast<const GeomDesc*>(dv + desc_at), reinterpret_cast<const VgNv12Rec*>(dv + nrec_at), sp, st.desc, st.tiles,
@@ -2028,6 +2099,22 @@ int bsx_step_batch_vcam_geoms_outs_nv12(bsx_ctx* c, const int* ids, const bsx_ge
   return ids_release(c, entry, s, vcam_outs_run(c, fn, ids, items, n, nullptr, outs, plan, s, 0, entry));
 }
 
+// bsx_step_batch_vcam_geoms_outs_nv12 with every frame an NV12 surface; see bsx.h
+int bsx_step_batch_surfaces(bsx_ctx* c, const int* ids, const bsx_surface_item* items, int n, const bsx_vcam_out_nv12* outs, int m, void* stream, unsigned flags) {
+  const char* fn = "bsx_step_batch_surfaces";
+  if (!c) return BSX_EINVAL;
+  if (const int rc = ids_check(c, fn, ids, n)) return rc;
+  if (n == 0) return refuse_pending(c, fn);
+  VcamOutsPlan plan;
+  if (const int rc = vcam_surfaces_check(c, fn, ids, items, n, outs, m, flags, &plan)) return rc;
+  DeviceGuard guard(c->device);
+  hipStream_t s = pick(c, stream);
+  if (const int rc = geoms_device_state(c)) return rc;
+  int entry = 0;
+  if (const int rc = ring_acquire(c, &entry)) return rc;
+  return ids_release(c, entry, s, vcam_outs_run(c, fn, ids, c->sf_items.data(), n, nullptr, outs, plan, s, 0, entry, items));
+}
+
 int bsx_reset_streams(bsx_ctx* c, const int* ids, int n, void* stream) {
   if (!c) return BSX_EINVAL;
   if (const int rc = ids_check(c, "bsx_reset_streams", ids, n)) return rc;
@@ -2195,6 +2282,21 @@ int bsx_bgr_to_nv12(bsx_ctx* c, const uint8_t* d_bgr, int w, int h, int n, uint8
   if ((uintptr_t)d_uv & 3) return refuse(c, fn, "d_uv %p is not 4-byte aligned", (const void*)d_uv);
   DeviceGuard guard(c->device);
   BSX_HIP(c, launch_bgr_to_nv12(d_bgr, w, h, n, d_y, pitch_y, d_uv, pitch_uv, pick(c, stream)));
+  return BSX_OK;
+}
+
+int bsx_nv12_to_bgr(bsx_ctx* c, const uint8_t* d_y, int pitch_y, const uint8_t* d_uv, int pitch_uv, int w, int h, int n, uint8_t* d_bgr, void* stream) {
+  const char* fn = "bsx_nv12_to_bgr";
+  if (!c) return BSX_EINVAL;
+  if (!d_y || !d_uv || !d_bgr) return refuse(c, fn, "d_y %p, d_uv %p or d_bgr %p is NULL", (const void*)d_y, (const void*)d_uv, (const void*)d_bgr);
+  if (w <= 0 || h <= 0 || n <= 0) return refuse(c, fn, "w = %d, h = %d and n = %d must be positive", w, h, n);
+  if ((w | h) & 1) return refuse(c, fn, "NV12 needs an even width and height (%d x %d)", w, h);
+  if (pitch_y < w || (pitch_y & 3)) return refuse(c, fn, "pitch_y = %d must be a multiple of 4 and at least w = %d", pitch_y, w);
+  if (pitch_uv < w || (pitch_uv & 3)) return refuse(c, fn, "pitch_uv = %d must be a multiple of 4 and at least w = %d", pitch_uv, w);
+  if ((uintptr_t)d_y & 3) return refuse(c, fn, "d_y %p is not 4-byte aligned", (const void*)d_y);
+  if ((uintptr_t)d_uv & 3) return refuse(c, fn, "d_uv %p is not 4-byte aligned", (const void*)d_uv);
+  DeviceGuard guard(c->device);
+  BSX_HIP(c, launch_nv12_to_bgr(d_y, pitch_y, d_uv, pitch_uv, w, h, n, d_bgr, pick(c, stream)));
   return BSX_OK;
 }
 

@@ -240,6 +240,20 @@ struct alignas(16) VgNv12Rec { uint8_t* uv; int pitch_y, pitch_uv; };
 hipError_t launch_vcam_geoms_outs_nv12(const GeomClass* classes, const VgOutGroup* groups, const GeomDesc* odesc, const VgNv12Rec* nrec, const OutSpans& outs,
                                        const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const uint8_t* ofinal, int outW, int outH, uint8_t* tile_class,
                                        int n, hipStream_t s, bool fmt);
+// bsx_step_batch_surfaces: launch_prep_geoms and launch_vcam_geoms_outs_nv12 for positions whose frames are all NV12 SURFACES — desc[i].frame is position i's Y
+// plane ([H] rows of pitch_y bytes), srec[i] its interleaved UV plane ([H / 2] rows of pitch_uv bytes) and the two pitches (multiples of 4, >= W; both planes 4-byte
+// aligned; W and H even).  srec: a DEVICE array staged behind the call's descriptors, read with one 16-byte uniform load; an OUTPUT record's descriptor names its
+// position (the index into srec) in pad[0].  Pixel (x, y) of the frame is Y[y][x] with the chroma pair UV[y >> 1][x & ~1 ..], converted with cv::COLOR_YUV2BGR_YUYV's
+// integers: the BGR frame is launch_yuyv_to_bgr of the 4:2:2 image whose row y repeats chroma row y >> 1.  No load touches a byte at or past W of a row.  Every class
+// of the call must satisfy prep_nv12_fusable (the proper INTER_LINEAR down-scale table, W and H even, W >= 4); the prep kernel is prep_geoms_nv12_k, the resize pass
+// vg_outs_nv12in_k, tile_class_geoms_k and mask_geoms_k are launch_vcam_geoms_outs_nv12's.
+struct alignas(16) VgSurfRec { const uint8_t* uv; int pitch_y, pitch_uv; };
+bool prep_nv12_fusable(int W, int H, const ResizeTab& tab);
+hipError_t launch_prep_geoms_nv12(const GeomClass* classes, const GeomDesc* desc, const VgSurfRec* srec, const GeomSpans& spans, float* input, uint32_t* input_u8, int inW,
+                                  int inH, BilateralParams bp, int n, hipStream_t s);
+hipError_t launch_vcam_geoms_outs_nv12in(const GeomClass* classes, const VgOutGroup* groups, const GeomDesc* odesc, const VgNv12Rec* nrec, const VgSurfRec* srec,
+                                         const OutSpans& outs, const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const uint8_t* ofinal, int outW, int outH,
+                                         uint8_t* tile_class, int n, hipStream_t s);
 // ---- classes off the 4-pixel grid (bsx_new_geoms_ex with BSX_GEOMS_EDGE_ROI): W % 4 == 0, roi.x and roi.w free ----------------------------------------------------
 // The composite moves in 4-pixel groups of three aligned dwords, so the groups are anchored to the FRAME: with s = roi.x & 3 (geom_edge_shift) tile column tbx of a
 // class starts at ROI-relative column 128 tbx - s, and a class has ceil((s + roi.w) / 128) tile columns (geom_tile_cols: GeomClass::ntx, the spans and the tile-class
@@ -275,6 +289,9 @@ hipError_t launch_bgr_to_yuyv(const uint8_t* bgr, uint8_t* yuyv, int w, int h, i
 // >= w; planes 4-byte aligned.  Y and chroma are launch_bgr_to_yuyv's bytes, the chroma averaged (truncating) over each pair of rows: UV[r][2c] is the mean of byte 1
 // of the 4:2:2 words (2r, c) and (2r + 1, c), UV[r][2c + 1] that of byte 3.  Bytes [w, pitch) of a row are not written.
 hipError_t launch_bgr_to_nv12(const uint8_t* bgr, int w, int h, int n, uint8_t* y, int pitch_y, uint8_t* uv, int pitch_uv, hipStream_t s);
+// NV12 → BGR: launch_bgr_to_nv12's layout read back — n pitched surfaces into tight [h][w][3] images.  The bytes of launch_yuyv_to_bgr applied to the 4:2:2 image
+// Q[y][c] = (Y[y][2c], UV[y / 2][2c], Y[y][2c + 1], UV[y / 2][2c + 1]).  Bytes [w, pitch) of a row are not read.  bgr: any alignment.
+hipError_t launch_nv12_to_bgr(const uint8_t* y, int pitch_y, const uint8_t* uv, int pitch_uv, int w, int h, int n, uint8_t* bgr, hipStream_t s);
 // YUYV → BGR ingest.  deepseg.cc:553 (CAP_PROP_CONVERT_RGB), :725
 hipError_t launch_yuyv_to_bgr(const uint8_t* yuyv, uint8_t* bgr, int w, int h, int n, hipStream_t s);
 // cv::flip of the composited frame (code as cv::flip: 0 vertical, >0 horizontal, <0 both).  deepseg.cc:667-673

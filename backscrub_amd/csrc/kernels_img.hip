@@ -2805,4 +2805,202 @@ hipError_t launch_bgr_to_nv12(const uint8_t* bgr, int w, int h, int n, uint8_t* 
   return hipGetLastError();
 }
 
+// ---- bsx_step_batch_surfaces and bsx_nv12_to_bgr: the frame of a position is an NV12 surface (kernels.hpp: VgSurfRec) ------------------------------------------------
+// A 4:2:0 frame differs from a 4:2:2 one only in where a pixel's U and V bytes lie: pixel (x, y) takes Y[y][x] and the pair UV[y >> 1][x & ~1 ..], and from there the
+// integers are yuv_tap_to_bgr's / yuyv4_to_bgr3's.  prep_geoms_nv12_k is prep_geoms_k with prep_tile.inc's NV12 windows (BSX_PT_NV12), vg_outs_nv12in_k is
+// vg_outs_nv12_k with vcam_tile.inc's frame read through vcam_surf_px / vcam_surf_group (BSX_VT_NV12IN).  A position's second plane and pitches come from a table of
+// 16-byte records beside the descriptors, one uniform load; GeomDesc keeps its layout, an output record's descriptor names its position in pad[0].  Kernels of their
+// own at the end of the file, in a namespace of their own (the reason is given above mask_geoms_k): every earlier kernel's text is what it was.
+static_assert(sizeof(VgSurfRec) == 16, "vg_surf_rec reads a record as one uint4");
+namespace {
+struct VcSurf { const uint8_t* uv; int py, puv; };
+__device__ __forceinline__ VcSurf vg_surf_rec(const VgSurfRec* __restrict__ rec, int n) {
+  const uint4 v = reinterpret_cast<const uint4*>(rec)[n];
+  typedef __attribute__((address_space(1))) uint8_t* gp;
+  return VcSurf{(const uint8_t*)(gp)(((uint64_t)v.y << 32) | v.x), (int)v.z, (int)v.w};
+}
+// the surface's pixel (cx, cy) as B | G << 8 | R << 16: one Y byte and the chroma pair of its column (vcam_frame_px for a surface)
+__device__ __forceinline__ uint32_t vcam_surf_frame_px(const uint8_t* __restrict__ fr, const VcSurf& sf, int cx, int cy) {
+  const uint8_t* const c = sf.uv + (long)(cy >> 1) * sf.puv + (cx & ~1);
+  return yuv_tap_to_bgr((uint32_t)fr[(long)cy * sf.py + cx] | ((uint32_t)c[0] << 8) | ((uint32_t)c[1] << 16));
+}
+// vcam_px<.., SEL = true> with the frame a surface
+template <bool SEL>
+__device__ __forceinline__ uint32_t vcam_surf_px(const uint8_t* __restrict__ fr, const VcSurf& sf, const uint8_t* __restrict__ bgp, const uint8_t* __restrict__ mk, int W,
+                                                 int cx, int cy, bool off) {
+  static_assert(SEL, "the surface step is a per-position form");
+  const long p = (long)cy * W + cx;
+  const uint32_t fw = vcam_surf_frame_px(fr, sf, cx, cy);               // (the frame's loads first, as in vcam_px)
+  if (off) return fw & 0xffffffu;
+  const uint8_t* a = bgp + p * 3;
+  const uint32_t m = (uint32_t)mk[p] * 0x00010001u;
+  return blend_word((uint32_t)a[0] | ((uint32_t)a[1] << 8) | ((uint32_t)a[2] << 16), fw, m, m);
+}
+// vcam_group<.., SEL = true> with the frame a surface.  words (W % 4 == 0, cx % 4 == 0, 4-byte aligned planes and pitches): one Y dword at cy * pitch_y + cx and one
+// UV dword at (cy >> 1) * pitch_uv + cx are the group's two 4:2:2 words (Y0 U0 Y1 V0, Y2 U1 Y3 V1) after two v_perm_b32
+template <bool SEL>
+__device__ __forceinline__ void vcam_surf_group(const uint8_t* __restrict__ fr, const VcSurf& sf, const uint8_t* __restrict__ bgp, const uint8_t* __restrict__ mk, int W,
+                                                int cx, int cy, bool words, uint32_t w[4], bool off) {
+  if (words) {
+    const long p = (long)cy * W + cx;
+    const uint32_t yw = *reinterpret_cast<const uint32_t*>(fr + (long)cy * sf.py + cx), cw = *reinterpret_cast<const uint32_t*>(sf.uv + (long)(cy >> 1) * sf.puv + cx);
+    uint32_t f3[3], o[3];
+    yuyv4_to_bgr3(__builtin_amdgcn_perm(cw, yw, 0x05010400u), __builtin_amdgcn_perm(cw, yw, 0x07030602u), f3);
+    if (off) { vcam_quad_words(f3, w); return; }
+    const u3v av = *reinterpret_cast<const u3v*>(bgp + p * 3);
+    const uint32_t a3[3] = {av.x, av.y, av.z};
+    blend_quad(a3, f3, *reinterpret_cast<const uint32_t*>(mk + p), o);
+    vcam_quad_words(o, w);
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < 4; k++) w[k] = cx + k < W ? vcam_surf_px<SEL>(fr, sf, bgp, mk, W, cx + k, cy, off) : 0u;
+}
+
+// prep_geoms_k for positions that are all NV12 surfaces: every class of the call has the proper INTER_LINEAR table and W >= 4 (the host admits no other), so there
+// is one body.  desc[f].frame is the Y plane, srec[f] the rest of the surface.
+template <int OUT>
+__global__ __launch_bounds__(kThreads) void prep_geoms_nv12_k(const GeomClass* __restrict__ classes, const GeomDesc* __restrict__ desc, const VgSurfRec* __restrict__ srec,
+                                                             GeomSpans sp, float* __restrict__ input, uint32_t* __restrict__ input_u8, int inW, int inH, BilateralParams bp,
+                                                             int TW, int TH, int ntx, int nty, int n_frames) {
+  __shared__ float lut[768];
+  __shared__ uint32_t tile[kPfS * kPfS];
+  const int tid = threadIdx.x;
+  unsigned f_, t_;
+  xcd_frame_tile((unsigned)(ntx * nty), (unsigned)n_frames, &f_, &t_);
+  const int g = geom_class_of_position(sp, (int)f_);
+  const GeomClass c = classes[g];                                     // (uniform index: scalar loads) — independent of the descriptor's and the surface record's
+  const uint8_t* const frames = geom_desc(desc, (int)f_).frame;
+  const VcSurf sf = vg_surf_rec(srec, (int)f_);
+  const uint8_t* const suv = sf.uv;
+  const int pitch_y = sf.py, pitch_uv = sf.puv;
+  const ResizeTab tab = geom_tab(c.down);
+  const int W = c.W;
+  const Rect4 roi = c.roi, q = c.in_roi;
+  const long n = (long)f_;
+  constexpr bool LINEAR = true, YIN = true;
+#define BSX_PT_NV12
+#include "prep_tile.inc"
+#undef BSX_PT_NV12
+}
+
+// vg_outs_nv12_k with every position's frame a surface: odesc[r].frame is the Y plane of record r's position, srec[odesc[r].pad[0]] the rest of it
+template <int = 0>
+__global__ __launch_bounds__(kThreads) void vg_outs_nv12in_k(const VgOutGroup* __restrict__ groups, const GeomDesc* __restrict__ odesc, const VgNv12Rec* __restrict__ nrec,
+                                                             const VgSurfRec* __restrict__ srec, OutSpans sp) {
+  __shared__ uint32_t s_px[kVLdsWords];
+  int g, w0, r0, per;
+  out_span(sp, (int)blockIdx.x, &g, &w0, &r0, &per);
+  const unsigned local = blockIdx.x - (unsigned)w0, rl = local / (unsigned)per, tile_ = local - rl * (unsigned)per;
+  const VgOutGroup G = groups[g];                                     // (uniform index: scalar loads) — independent of the descriptor's and the plane record's
+  const GeomDescRegs d = geom_desc(odesc, r0 + (int)rl);
+  const Nv12Regs nv = vg_nv12_rec(nrec, r0 + (int)rl);
+  const VcSurf surf = vg_surf_rec(srec, (int)reinterpret_cast<const uint4*>(odesc)[3 * (size_t)(r0 + (int)rl) + 2].z);      // pad[0]: the record's position
+  const int W = G.c.W, H = G.c.H, ntx = G.ntx;
+  int opt = 0;
+  const ResizeTab tab = geom_tab(G.c.tab);
+  const uint8_t *const frames = d.frame, *const bg = d.bg, *const masks = d.mask;
+  uint8_t *const out = d.out, *const out_uv = nv.uv;                  // the Y plane, the UV plane of the OUTPUT
+  const int pitch_y = nv.pitch_y, pitch_uv = nv.pitch_uv;
+  if ((W & 3) == 0 && ((((uintptr_t)frames) | ((uintptr_t)masks) | ((uintptr_t)surf.uv) | (uintptr_t)(surf.py | surf.puv)) & 3) == 0) opt |= kVcWords;      // launch_vg_mixed's rule, per position, with the surface's second plane and pitches
+  constexpr bool SEL = true, YIN = false;
+  constexpr long bg_stride = 0;
+  [[maybe_unused]] const int* const slot_of = nullptr;
+#define BSX_VT_NV12
+#define BSX_VT_NV12IN
+#define BSX_VT_OWN_LDS
+#define BSX_VT_TILE tile_
+#define BSX_VT_POS 0l                                                /* the record's own bases: index 0 of each */
+#define BSX_VT_DESC(fl) fl = d.flags
+  if (G.c.direct) {
+    constexpr bool DIRECT = true;
+#include "vcam_tile.inc"
+  } else {
+    constexpr bool DIRECT = false;
+#include "vcam_tile.inc"
+  }
+#undef BSX_VT_TILE
+#undef BSX_VT_POS
+#undef BSX_VT_DESC
+#undef BSX_VT_OWN_LDS
+#undef BSX_VT_NV12IN
+#undef BSX_VT_NV12
+}
+
+// bsx_nv12_to_bgr: one lane per block of 4 x 2 pixels (the 2-pixel block that ends a row of w % 4 == 2 included) — a Y dword per row and one UV dword (16 bits each
+// in the tail block: no byte at or past w of a row is read), per row the two 4:2:2 words of the block and yuyv4_to_bgr3.  WORDS: w % 4 == 0 and a 4-byte aligned
+// destination, three dwords per row; else the 3 cnt bytes of a row one by one.
+template <bool WORDS>
+__global__ __launch_bounds__(kThreads) void nv12_to_bgr_k(const uint8_t* __restrict__ yp, int pitch_y, const uint8_t* __restrict__ uvp, int pitch_uv,
+                                                         uint8_t* __restrict__ bgr, int w, int h) {
+  const unsigned gpr = ((unsigned)w + 3) / 4, i = blockIdx.x * kThreads + threadIdx.x;
+  if (i >= gpr * ((unsigned)h / 2)) return;
+  const int r = (int)(i / gpr), x = 4 * (int)(i - (unsigned)r * gpr), cnt = min(4, w - x);
+  const long n = blockIdx.y;
+  const uint8_t* const y0 = yp + (n * (long)h + 2 * r) * pitch_y + x;
+  const uint8_t* const u0 = uvp + (n * (long)(h / 2) + r) * pitch_uv + x;
+  uint32_t yw[2], cw;
+  if (WORDS || cnt == 4) {
+    yw[0] = *reinterpret_cast<const uint32_t*>(y0); yw[1] = *reinterpret_cast<const uint32_t*>(y0 + pitch_y); cw = *reinterpret_cast<const uint32_t*>(u0);
+  } else {
+    yw[0] = *reinterpret_cast<const uint16_t*>(y0); yw[1] = *reinterpret_cast<const uint16_t*>(y0 + pitch_y); cw = *reinterpret_cast<const uint16_t*>(u0);
+  }
+#pragma unroll
+  for (int j = 0; j < 2; j++) {
+    uint32_t b3[3];
+    yuyv4_to_bgr3(__builtin_amdgcn_perm(cw, yw[j], 0x05010400u), __builtin_amdgcn_perm(cw, yw[j], 0x07030602u), b3);
+    uint8_t* const o = bgr + ((n * (long)h + 2 * r + j) * w + x) * 3;
+    if constexpr (WORDS) {
+      *reinterpret_cast<u3v*>(o) = u3v{b3[0], b3[1], b3[2]};
+    } else {
+#pragma unroll
+      for (int b = 0; b < 12; b++)
+        if (b < 3 * cnt) o[b] = (uint8_t)(b3[b >> 2] >> (8 * (b & 3)));
+    }
+  }
+}
+}  // namespace
+
+bool prep_nv12_fusable(int W, int H, const ResizeTab& tab) { return tab.mode == 0 && ((W | H) & 1) == 0 && W >= 4; }
+
+hipError_t launch_prep_geoms_nv12(const GeomClass* classes, const GeomDesc* desc, const VgSurfRec* srec, const GeomSpans& spans, float* input, uint32_t* input_u8, int inW,
+                                  int inH, BilateralParams bp, int n, hipStream_t s) {
+  if ((!input && !input_u8) || n <= 0 || !srec) return hipErrorInvalidValue;
+  const int ntx = (inW + 31) / 32, nty = (inH + 31) / 32, TW = (inW + ntx - 1) / ntx, TH = (inH + nty - 1) / nty;      // launch_prep_fused's tiles
+  if ((unsigned long long)ntx * nty * (unsigned long long)n >= (1ull << 31)) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)(ntx * nty) * (unsigned)n);
+#define BSX_PG(O) prep_geoms_nv12_k<O><<<grid, kThreads, 0, s>>>(classes, desc, srec, spans, input, input_u8, inW, inH, bp, TW, TH, ntx, nty, xcd_frames(n))
+  if (input && input_u8) BSX_PG(3); else if (input_u8) BSX_PG(2); else BSX_PG(1);
+#undef BSX_PG
+  return hipGetLastError();
+}
+
+hipError_t launch_vcam_geoms_outs_nv12in(const GeomClass* classes, const VgOutGroup* groups, const GeomDesc* odesc, const VgNv12Rec* nrec, const VgSurfRec* srec,
+                                         const OutSpans& outs, const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const uint8_t* ofinal, int outW, int outH,
+                                         uint8_t* tile_class, int n, hipStream_t s) {
+  const int total = outs.wg[kMaxOutGroups];
+  if (!out_spans_ok(outs, groups, odesc, tiles, n) || (total > 0 && (!nrec || !srec))) return hipErrorInvalidValue;
+  if (tile_class) tile_class_geoms_k<<<dim3((unsigned)n), kThreads, 0, s>>>(classes, desc, tiles, ofinal, outW, outH, tile_class);
+  mask_geoms_k<><<<dim3((unsigned)tiles.wg[kMaxGeoms]), kThreads, 0, s>>>(classes, desc, tiles, xcd_mask, ofinal, outW, outH, tile_class);      // (reads no frame)
+  if (total > 0) vg_outs_nv12in_k<><<<dim3((unsigned)total), kThreads, 0, s>>>(groups, odesc, nrec, srec, outs);
+  return hipGetLastError();
+}
+
+hipError_t launch_nv12_to_bgr(const uint8_t* y, int pitch_y, const uint8_t* uv, int pitch_uv, int w, int h, int n, uint8_t* bgr, hipStream_t s) {
+  if (w <= 0 || h <= 0 || n <= 0 || ((w | h) & 1) || pitch_y < w || pitch_uv < w || ((pitch_y | pitch_uv) & 3) || (((uintptr_t)y | (uintptr_t)uv) & 3))
+    return hipErrorInvalidValue;
+  const long blocks = (long)((w + 3) / 4) * (h / 2);
+  if (blocks >= (1l << 31)) return hipErrorInvalidValue;
+  const bool words = (w & 3) == 0 && ((uintptr_t)bgr & 3) == 0;
+  for (int n0 = 0; n0 < n; n0 += kMaxGridY) {
+    const int nn = n - n0 < kMaxGridY ? n - n0 : kMaxGridY;
+    const uint8_t* const yp = y + (size_t)n0 * h * pitch_y;
+    const uint8_t* const up = uv + (size_t)n0 * (h / 2) * pitch_uv;
+    uint8_t* const dst = bgr + (size_t)n0 * w * h * 3;
+    if (words) nv12_to_bgr_k<true><<<dim3(blocks_for(blocks), nn), kThreads, 0, s>>>(yp, pitch_y, up, pitch_uv, dst, w, h);
+    else nv12_to_bgr_k<false><<<dim3(blocks_for(blocks), nn), kThreads, 0, s>>>(yp, pitch_y, up, pitch_uv, dst, w, h);
+  }
+  return hipGetLastError();
+}
+
 }  // namespace bsx

@@ -13,7 +13,17 @@
 // provides out_uv, pitch_y, pitch_uv (`out` is the Y plane; dw and dh even).  A lane's two 4-pixel groups are vertically adjacent — rows 2 (tid / 16) and
 // 2 (tid / 16) + 1 of the tile instead of tid / 16 and tid / 16 + 16 — so it holds both rows of its 2 x 2 chroma blocks: per row one Y dword, per pair one UV dword
 // (16 bits each for the 2-pixel group that ends a row of out_w % 4 == 2), the chroma bytes those of yuyv_pair, averaged over the two rows as it averages two pixels.
+// BSX_VT_NV12IN (vg_outs_nv12in_k, with SEL true and YIN false; undefined, the text is what it was): the position's frame is an NV12 surface — `frames` is its Y
+// plane, the includer also provides `surf` (VcSurf: the UV plane and the two pitches), and the frame's pixels and 4-pixel groups are read by vcam_surf_px /
+// vcam_surf_group.  Background, mask, taps and stores are unchanged.
 // BSX_VT_OWN_LDS (vg_geoms_fmt_k, which includes the body once per frame format): the includer declares s_px itself, one staging area for all of its inclusions.
+#ifdef BSX_VT_NV12IN
+#define BSX_VT_GROUP(...) vcam_surf_group<SEL>(fr, surf, __VA_ARGS__)
+#define BSX_VT_PX(...) vcam_surf_px<SEL>(fr, surf, __VA_ARGS__)
+#else
+#define BSX_VT_GROUP(...) vcam_group<YIN, SEL>(fr, __VA_ARGS__)
+#define BSX_VT_PX(...) vcam_px<YIN, SEL>(fr, __VA_ARGS__)
+#endif
 #ifndef BSX_VT_OWN_LDS
   __shared__ uint32_t s_px[DIRECT ? 1 : kVLdsWords];
 #endif
@@ -51,7 +61,7 @@
     for (int i = tid; i < items; i += kThreads) {                                            \
       const int r = i / ng, g = i - r * ng;                                                  \
       uint32_t w[4];                                                                         \
-      vcam_group<YIN, SEL>(fr, bgp, mk, W, gx0 + 4 * g, cy_lo + r, words, w, OFF);           \
+      BSX_VT_GROUP(bgp, mk, W, gx0 + 4 * g, cy_lo + r, words, w, OFF);                       \
       *reinterpret_cast<uint4*>(s_px + r * rw + 4 * g) = make_uint4(w[0], w[1], w[2], w[3]); \
     }
     if constexpr (SEL) {
@@ -89,8 +99,8 @@
       uint32_t t00, t01, t10, t11;
       if constexpr (DIRECT) {
 #define BSX_VG_TAPS(OFF)                                                                                                 \
-        t00 = vcam_px<YIN, SEL>(fr, bgp, mk, W, x0, y0, OFF); t01 = vcam_px<YIN, SEL>(fr, bgp, mk, W, x1, y0, OFF); \
-        t10 = vcam_px<YIN, SEL>(fr, bgp, mk, W, x0, y1, OFF); t11 = vcam_px<YIN, SEL>(fr, bgp, mk, W, x1, y1, OFF);
+        t00 = BSX_VT_PX(bgp, mk, W, x0, y0, OFF); t01 = BSX_VT_PX(bgp, mk, W, x1, y0, OFF); \
+        t10 = BSX_VT_PX(bgp, mk, W, x0, y1, OFF); t11 = BSX_VT_PX(bgp, mk, W, x1, y1, OFF);
         if constexpr (SEL) {                                         // (once per value of the filter switch, as the staging loop)
           if (off) { BSX_VG_TAPS(true) } else { BSX_VG_TAPS(false) }
         } else {
@@ -145,3 +155,5 @@
     }
 #endif
   }
+#undef BSX_VT_GROUP
+#undef BSX_VT_PX

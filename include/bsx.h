@@ -29,12 +29,14 @@
  *   bsx_step_batch_vcam_geoms  … the same streams, every composite written at the virtual camera's one size  app/deepseg.cc:634-681
  *   bsx_step_batch_vcam_geoms_outs  … the same streams, several outputs per stream, each of its own size (speaker + thumbnails, simulcast layers)
  *   bsx_step_batch_vcam_geoms_outs_nv12  … every output an NV12 surface with row pitches, for a video encoder (bsx_bgr_to_nv12: the stand-alone conversion)
+ *   bsx_step_batch_surfaces  … every frame an NV12 surface too, as a video decoder leaves it: NV12 in, NV12 out (bsx_nv12_to_bgr: the stand-alone conversion)
  *   bsx_reset_streams      bsx_reset for a chosen subset of the streams (a slot reused for a new camera)
  *                          (set_input_frame → mask → alpha_blend), batched
  *   bsx_resize_bgr         grab_background() cv::resize   app/background.cc:178-194
  *   bsx_resize_bgr_batch   … of n images of their own sizes in one launch
  *   bsx_bgr_to_yuyv        convert_rgb_to_yuyv()          app/deepseg.cc:87-106
  *   bsx_yuyv_to_bgr        VideoCapture's YUYV->BGR       app/deepseg.cc:553,725 (cv::COLOR_YUV2BGR_YUYV)
+ *   bsx_nv12_to_bgr        the same integers for a video decoder's NV12 surface (pitched Y and UV planes)
  *   bsx_flip_bgr           cv::flip of the output frame   app/deepseg.cc:667-673 (flipHorizontal / flipVertical)
  *   bsx_gaussian_blur_bgr  cv::GaussianBlur of the background app/deepseg.cc:415-431,652-658 (-p bgblur:<n>: blur the camera frame itself
  *                          (or the background image) and composite over it)
@@ -388,7 +390,7 @@ BSX_API int bsx_step_batch_vcam_geoms_outs(bsx_ctx* ctx, const int* ids, const b
  *     bsx_step_batch_vcam_geoms_outs that still applies; any bit in flags; an odd out_w or out_h; a pitch below out_w or not a multiple of 4; a NULL or not 4-byte
  *     aligned plane; a plane overlapping any frame, background or other plane of the call, its own record's second plane included.  A refused call changes no state;
  *   - overlap is judged on a plane's byte extent pitch * (rows - 1) + out_w: two records that interleave their rows inside one canvas are refused.
- * Out of scope: writing a mosaic (several records into one canvas), I420 / three-plane output, NV12 input, odd sizes. */
+ * Out of scope: writing a mosaic (several records into one canvas), I420 / three-plane output, odd sizes.  (NV12 input: bsx_step_batch_surfaces.) */
 typedef struct bsx_vcam_out_nv12 {
   int item; int out_w, out_h;          /* as bsx_vcam_out; out_w and out_h even */
   int pitch_y, pitch_uv;               /* bytes per row of each plane: multiples of 4, >= out_w */
@@ -397,6 +399,43 @@ typedef struct bsx_vcam_out_nv12 {
 } bsx_vcam_out_nv12;
 BSX_API int bsx_step_batch_vcam_geoms_outs_nv12(bsx_ctx* ctx, const int* ids, const bsx_geom_item* items, int n, const bsx_vcam_out_nv12* outs, int m, void* stream,
                                                 unsigned flags /* 0 */);
+
+/* bsx_step_batch_vcam_geoms_outs_nv12 whose FRAMES are NV12 surfaces as well: what a simulcast forwarder holds after the hardware decoder — a Y plane and an
+ * interleaved UV plane of half the rows, each with a row pitch — stepped straight into encoder surfaces.  The prep kernel and the resize pass read 1.5 B/px from the
+ * decoder's surface; no 3 B/px BGR frame is stored or read back.
+ * The definition.  No reference code reads 4:2:0, so an NV12 frame is defined through the 4:2:2 frame the library already takes.  For a capture of W x H, both even,
+ * with planes Y ([H] rows of pitch_y bytes) and UV ([H / 2] rows of pitch_uv bytes) let Q be the YUYV image [H][W / 2] of words (Y0 U Y1 V) with
+ *     Q[y][c] = ( Y[y][2c],  UV[y / 2][2c],  Y[y][2c + 1],  UV[y / 2][2c + 1] )
+ * The BGR frame of the surface is bsx_yuyv_to_bgr(Q): every pixel takes the chroma pair of its 2 x 2 block, nothing is interpolated, and the integers are those of
+ * cv::COLOR_YUV2BGR_YUYV.  (Believed, not checked: this is also what cv::COLOR_YUV2BGR_NV12 computes, since OpenCV uses the same BT.601 fixed-point constants for
+ * both layouts.  Nothing here depends on it.)  Bytes [W, pitch) of a row mean nothing and are never read.  bsx_nv12_to_bgr is that conversion on its own.
+ *   - everything of bsx_step_batch_vcam_geoms_outs_nv12 but the frame's form: the ids rules and the staging ring (no host synchronisation unless four calls ahead),
+ *     BSX_MAX_OUTS_PER_ITEM, BSX_MAX_OUT_SIZES and the per-size table cache, every refusal of an output record, n == 0 (returns 0, enqueues nothing), m == 0 with
+ *     n > 0 (a masks-only step), every kind of context (bsx_new, bsx_new_geoms, bsx_new_geoms_ex with BSX_GEOMS_EDGE_ROI).  Launches: ONE prep launch, the network, one
+ *     tile-class launch, one masks-only tile launch, ONE resize pass;
+ *   - result: every output plane, every persistent mask and ofinal of every stream of the context are byte-identical to bsx_step_batch_vcam_geoms_outs_nv12 fed the
+ *     BGR frames bsx_nv12_to_bgr makes of the same surfaces.  A filter-off item's output is its converted frame, flipped, resized and packed;
+ *   - admission of a class: the proper INTER_LINEAR down-scale table (the condition of a BSX_STREAM_YUYV_IN item: not the copy, not the 2x2 area mean), an even width
+ *     and height, a width of at least 4.  Chroma is addressed by the FRAME's column and row, (roi.x + sx) >> 1 and (roi.y + sy) >> 1, so an odd roi.x or roi.y — the
+ *     edge classes, segm_lite at 1920 x 1080 — needs no further rule.  There is no conversion fallback: an item of a class that is not admitted is refused with a text
+ *     naming items[i], the stream, the class size and the reason, and the caller converts with bsx_nv12_to_bgr and takes bsx_step_batch_vcam_geoms_outs_nv12;
+ *   - setting.flags: BSX_STEP_FLIP_H | BSX_STEP_FLIP_V | BSX_STREAM_FILTER_OFF; setting.d_bg: BGR at the class's capture size, 4-byte aligned, unread with
+ *     BSX_STREAM_FILTER_OFF; flags: 0;
+ *   - BSX_EINVAL before anything is enqueued, with a bsx_last_error text naming items[i] or outs[j] and the value, for: items NULL; a NULL or not 4-byte aligned
+ *     plane; a pitch below the class's width or not a multiple of 4 (or a plane of 2 GiB or more); a setting bit outside the three above, BSX_STREAM_YUYV_IN and a
+ *     blur size included; any bit in flags; a NULL or unaligned d_bg that is read; a pending pipelined composite, an onmask callback, a class off the fused route; an
+ *     output plane overlapping an input plane, a background or another output plane.  An input plane is judged on its extent pitch * (rows - 1) + W.  A refused
+ *     call changes no state.
+ * Out of scope: NV12 items mixed with BGR or YUYV items in one call; NV12 input for the capture-size steps (bsx_step_batch_geoms) and for the packed-output vcam
+ * calls; P010 and I420; odd sizes; a surface whose two planes share one pitch field. */
+typedef struct bsx_surface_item {
+  const uint8_t* d_y;                  /* [height_g] rows of pitch_y bytes, 4-byte aligned */
+  const uint8_t* d_uv;                 /* [height_g / 2] rows of pitch_uv bytes (U, V interleaved), 4-byte aligned */
+  int pitch_y, pitch_uv;               /* multiples of 4, >= width_g */
+  bsx_stream_setting setting;          /* d_bg: BGR at the class's capture size; BSX_STEP_FLIP_H | BSX_STEP_FLIP_V | BSX_STREAM_FILTER_OFF */
+} bsx_surface_item;
+BSX_API int bsx_step_batch_surfaces(bsx_ctx* ctx, const int* ids, const bsx_surface_item* items, int n, const bsx_vcam_out_nv12* outs, int m, void* stream,
+                                    unsigned flags /* 0 */);
 
 /* Reset the temporal state of the listed streams only (ofinal → 0, persistent mask → 255, as bsx_reset does for all) — a slot reused for a new camera.  The
  * other streams' state is untouched, and a pending pipelined composite is NOT dropped: the call is refused (BSX_EINVAL) while one is pending.  Same ids rules,
@@ -480,6 +519,13 @@ BSX_API int bsx_bgr_to_yuyv(bsx_ctx* ctx, const uint8_t* d_bgr, uint8_t* d_yuyv,
  * the call's own).  BSX_EINVAL, with a bsx_last_error text, for: a NULL pointer; w, h or n not positive; an odd w or h; a pitch below w or not a multiple of 4; a
  * plane that is not 4-byte aligned.  The planes must not overlap each other or the source (not checked). */
 BSX_API int bsx_bgr_to_nv12(bsx_ctx* ctx, const uint8_t* d_bgr, int w, int h, int n, uint8_t* d_y, int pitch_y, uint8_t* d_uv, int pitch_uv, void* stream);
+
+/* NV12 in pitched planes -> BGR u8 [n][h][w][3], by the definition at bsx_step_batch_surfaces: the bytes of bsx_yuyv_to_bgr applied to the 4:2:2 image whose row y
+ * repeats chroma row y / 2.  The counterpart of bsx_bgr_to_nv12 and its layout: image i's planes are at d_y + i * pitch_y * h ([h] rows of pitch_y bytes) and
+ * d_uv + i * pitch_uv * (h / 2) ([h / 2] rows of pitch_uv bytes); bytes [w, pitch) of every row are not read.  d_bgr may lie at any address.  Works on a context of
+ * several classes (w, h are the call's own).  BSX_EINVAL, with a bsx_last_error text, for: a NULL pointer; w, h or n not positive; an odd w or h; a pitch below w or
+ * not a multiple of 4; a plane that is not 4-byte aligned.  d_bgr must not overlap the planes (not checked). */
+BSX_API int bsx_nv12_to_bgr(bsx_ctx* ctx, const uint8_t* d_y, int pitch_y, const uint8_t* d_uv, int pitch_uv, int w, int h, int n, uint8_t* d_bgr, void* stream);
 
 /* YUYV 4:2:2 (bytes Y0 U Y1 V) [n][h][w][2] -> BGR u8 [n][h][w][3], exactly cv::cvtColor(COLOR_YUV2BGR_YUYV): the conversion
  * cv::VideoCapture applies to raw camera frames for the reference (app/deepseg.cc:553, :725).  Lets a caller upload 2 B/px. */
