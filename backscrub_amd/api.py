@@ -306,42 +306,90 @@ class MaskGen:
         _check(lib().bsx_debug_buffer(self.h, 3, C.byref(p), C.byref(b)), self.h, "bsx_debug_buffer")
         return _as_torch(p.value + g["mask_offset"] + (stream - g["first_stream"]) * px, px, "uint8", (g["height"], g["width"]), self.device)
 
+    def _u8(self, t, shape):
+        """is t a contiguous uint8 tensor of that shape on the context's device?"""
+        torch = _torch()
+        return isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and self._on_device(t) and tuple(t.shape) == shape and t.is_contiguous()
+
+    def _geom_setting(self, who, i, s, H, W, stream, item, yuyv_in=True):
+        """settings[i] of a multi-geometry step, validated against its class's size and written into item.setting"""
+        if not isinstance(s, StreamSetting):
+            raise BsxError("settings[%d] is not a StreamSetting" % i)
+        if s.bgblur:
+            raise BsxError("settings[%d]: bgblur is not taken by %s" % (i, who))
+        if s.yuyv_in and not yuyv_in:
+            raise BsxError("settings[%d]: yuyv_in is not taken by %s (every frame is an NV12 surface)" % (i, who))
+        if not s.filter_off and s.bg is None:
+            raise BsxError("settings[%d]: bg is required unless filter_off is set" % i)
+        if s.bg is not None and not self._u8(s.bg, (H, W, 3)):
+            raise BsxError("settings[%d].bg must be a contiguous cuda:%d uint8 tensor [%d,%d,3] (stream %d)" % (i, self.device, H, W, stream))
+        item.setting.d_bg = s.bg.data_ptr() if s.bg is not None else None
+        item.setting.flags = s.flags()
+
+    def _geom_items(self, who, ids, frames, settings, outs=None, ch=3, common=False):
+        """the ids and items of step_geoms / step_vcam_geoms / step_vcam_geoms_outs / _nv12, validated: (ctypes ids, n, ctypes items, out_w, out_h).  outs: one output
+        per item, at the size of the item's class, or (common) all at the size of outs[0], which is returned; None: the items carry no output"""
+        arr, n = _ids(ids)
+        frames, settings = list(frames), list(settings)
+        if outs is None:
+            if len(frames) != n or len(settings) != n:
+                raise BsxError("%d ids for %d frames and %d settings" % (n, len(frames), len(settings)))
+        elif len(frames) != n or len(outs) != n or len(settings) != n:
+            raise BsxError("%d ids for %d frames, %d outs and %d settings" % (n, len(frames), len(outs), len(settings)))
+        items = (_GeomItem * max(n, 1))()
+        out_h = out_w = 0
+        if common and n:
+            if not isinstance(outs[0], _torch().Tensor) or outs[0].dim() != 3 or outs[0].shape[2] != ch:
+                raise BsxError("outs[0] must be a cuda:%d uint8 tensor [out_h,out_w,%d]: it gives the output size" % (self.device, ch))
+            out_h, out_w = int(outs[0].shape[0]), int(outs[0].shape[1])
+            if ch == 2 and (out_w & 1):
+                raise BsxError("YUYV output needs an even width (outs[0] is %d wide)" % out_w)
+        for i in range(n):
+            g = self._geom_of(int(arr[i]))
+            H, W = g["height"], g["width"]
+            s = settings[i]
+            fch = 2 if isinstance(s, StreamSetting) and s.yuyv_in else 3      # the item's own pixel format: YUYV 4:2:2 or BGR
+            if not self._u8(frames[i], (H, W, fch)):
+                raise BsxFrameFormatError("frames[%d] must be a contiguous cuda:%d uint8 tensor [%d,%d,%d] (stream %d%s)" % (
+                    i, self.device, H, W, fch, arr[i], ", a YUYV item" if fch == 2 else ""))
+            if common and not self._u8(outs[i], (out_h, out_w, ch)):
+                raise BsxError("outs[%d] must be a contiguous cuda:%d uint8 tensor [%d,%d,%d] (the size of outs[0])" % (i, self.device, out_h, out_w, ch))
+            if outs is not None and not common and not self._u8(outs[i], (H, W, ch)):
+                raise BsxError("outs[%d] must be a contiguous cuda:%d uint8 tensor [%d,%d,%d] (stream %d)" % (i, self.device, H, W, ch, arr[i]))
+            self._geom_setting(who, i, s, H, W, arr[i], items[i])
+            items[i].d_frame, items[i].d_out = frames[i].data_ptr(), outs[i].data_ptr() if outs is not None else None
+        return arr, n, items, out_w, out_h
+
+    def _out_records(self, outs, n, rec_type, form, fill):
+        """the output records of a call of n positions, validated: (ctypes records, m).  outs: a list of (item_index, ...) of the given form (its words, its length);
+        fill(j, record, ...) checks the rest of outs[j], writes the record's buffers and returns (out_w, out_h)"""
+        m = len(outs)
+        recs = (rec_type * max(m, 1))()
+        named, sizes = {}, []
+        for j, rec in enumerate(outs):
+            if not isinstance(rec, (tuple, list)) or len(rec) != form[1]:
+                raise BsxError("outs[%d] must be a %s" % (j, form[0]))
+            item = rec[0]
+            if isinstance(item, bool) or not isinstance(item, (int, np.integer)) or not 0 <= int(item) < n:
+                raise BsxError("outs[%d]: item %r is not an index into the call's %d positions" % (j, item, n))
+            ow, oh = fill(j, recs[j], *rec[1:])
+            named[int(item)] = named.get(int(item), 0) + 1
+            if named[int(item)] > BSX_MAX_OUTS_PER_ITEM:
+                raise BsxError("outs[%d]: record %d of position %d (at most %d name one position)" % (j, named[int(item)], int(item), BSX_MAX_OUTS_PER_ITEM))
+            if (ow, oh) not in sizes:
+                sizes.append((ow, oh))
+                if len(sizes) > BSX_MAX_OUT_SIZES:
+                    raise BsxError("outs[%d]: %d x %d is distinct output size %d of the call (at most %d)" % (j, ow, oh, len(sizes), BSX_MAX_OUT_SIZES))
+            recs[j].item, recs[j].out_w, recs[j].out_h = int(item), ow, oh
+        return recs, m
+
     def step_geoms(self, ids, frames, outs, settings, yuyv=False, no_mask=False):
         """one main-loop iteration for streams of ANY mix of the context's geometry classes (bsx_step_batch_geoms): ids[i] names the stream of position i, frames[i]
         (cuda uint8 [H_g, W_g, 3] BGR, or the camera's raw YUYV 4:2:2 [H_g, W_g, 2] for an item whose setting has yuyv_in), outs[i] ([H_g, W_g, 3], or [.., 2]
         with yuyv) and settings[i] (a StreamSetting: bg at the class's size, flip_h, flip_v, filter_off, yuyv_in; no bgblur) have the capture size of that
         stream's class.  One prep launch, one network pass, one tile launch whatever the mix of sizes and pixel formats."""
-        torch = _torch()
-        arr, n = _ids(ids)
-        frames, outs, settings = list(frames), list(outs), list(settings)
-        if len(frames) != n or len(outs) != n or len(settings) != n:
-            raise BsxError("%d ids for %d frames, %d outs and %d settings" % (n, len(frames), len(outs), len(settings)))
-        items = (_GeomItem * max(n, 1))()
-        ch = 2 if yuyv else 3
-        for i in range(n):
-            g = self._geom_of(int(arr[i]))
-            H, W = g["height"], g["width"]
-
-            def ok(t, c):
-                return isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and self._on_device(t) and tuple(t.shape) == (H, W, c) and t.is_contiguous()
-            s = settings[i]
-            fch = 2 if isinstance(s, StreamSetting) and s.yuyv_in else 3      # the item's own pixel format: YUYV 4:2:2 or BGR
-            if not ok(frames[i], fch):
-                raise BsxFrameFormatError("frames[%d] must be a contiguous cuda:%d uint8 tensor [%d,%d,%d] (stream %d%s)" % (
-                    i, self.device, H, W, fch, arr[i], ", a YUYV item" if fch == 2 else ""))
-            if not ok(outs[i], ch):
-                raise BsxError("outs[%d] must be a contiguous cuda:%d uint8 tensor [%d,%d,%d] (stream %d)" % (i, self.device, H, W, ch, arr[i]))
-            if not isinstance(s, StreamSetting):
-                raise BsxError("settings[%d] is not a StreamSetting" % i)
-            if s.bgblur:
-                raise BsxError("settings[%d]: bgblur is not taken by step_geoms" % i)
-            if not s.filter_off and s.bg is None:
-                raise BsxError("settings[%d]: bg is required unless filter_off is set" % i)
-            if s.bg is not None and not ok(s.bg, 3):
-                raise BsxError("settings[%d].bg must be a contiguous cuda:%d uint8 tensor [%d,%d,3] (stream %d)" % (i, self.device, H, W, arr[i]))
-            items[i].d_frame, items[i].d_out = frames[i].data_ptr(), outs[i].data_ptr()
-            items[i].setting.d_bg = s.bg.data_ptr() if s.bg is not None else None
-            items[i].setting.flags = s.flags()
+        outs = list(outs)
+        arr, n, items, _w, _h = self._geom_items("step_geoms", ids, frames, settings, outs, 2 if yuyv else 3)
         flags = (1 if yuyv else 0) | (8 if no_mask else 0)
         _check(lib().bsx_step_batch_geoms(self.h, arr, items, n, _stream_ptr(), flags), self.h, "bsx_step_batch_geoms")
         return outs
@@ -351,78 +399,10 @@ class MaskGen:
         capture size of the class of ids[i] (frames[i] is [H_g, W_g, 2] YUYV 4:2:2 where settings[i].yuyv_in); every outs[i] is a cuda uint8 [out_h, out_w, 3]
         (or [.., 2] with yuyv) — the size is taken from outs[0].  Blend ->
         flip -> resize -> [pack] in one pass per position: no capture-size composite is stored."""
-        torch = _torch()
-        arr, n = _ids(ids)
-        frames, outs, settings = list(frames), list(outs), list(settings)
-        if len(frames) != n or len(outs) != n or len(settings) != n:
-            raise BsxError("%d ids for %d frames, %d outs and %d settings" % (n, len(frames), len(outs), len(settings)))
-        items = (_GeomItem * max(n, 1))()
-        ch = 2 if yuyv else 3
-        out_h = out_w = 0
-        if n:
-            if not isinstance(outs[0], torch.Tensor) or outs[0].dim() != 3 or outs[0].shape[2] != ch:
-                raise BsxError("outs[0] must be a cuda:%d uint8 tensor [out_h,out_w,%d]: it gives the output size" % (self.device, ch))
-            out_h, out_w = int(outs[0].shape[0]), int(outs[0].shape[1])
-            if yuyv and (out_w & 1):
-                raise BsxError("YUYV output needs an even width (outs[0] is %d wide)" % out_w)
-        for i in range(n):
-            g = self._geom_of(int(arr[i]))
-            H, W = g["height"], g["width"]
-
-            def ok(t, shape):
-                return isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and self._on_device(t) and tuple(t.shape) == shape and t.is_contiguous()
-            s = settings[i]
-            fch = 2 if isinstance(s, StreamSetting) and s.yuyv_in else 3      # the item's own pixel format: YUYV 4:2:2 or BGR
-            if not ok(frames[i], (H, W, fch)):
-                raise BsxFrameFormatError("frames[%d] must be a contiguous cuda:%d uint8 tensor [%d,%d,%d] (stream %d%s)" % (
-                    i, self.device, H, W, fch, arr[i], ", a YUYV item" if fch == 2 else ""))
-            if not ok(outs[i], (out_h, out_w, ch)):
-                raise BsxError("outs[%d] must be a contiguous cuda:%d uint8 tensor [%d,%d,%d] (the size of outs[0])" % (i, self.device, out_h, out_w, ch))
-            if not isinstance(s, StreamSetting):
-                raise BsxError("settings[%d] is not a StreamSetting" % i)
-            if s.bgblur:
-                raise BsxError("settings[%d]: bgblur is not taken by step_vcam_geoms" % i)
-            if not s.filter_off and s.bg is None:
-                raise BsxError("settings[%d]: bg is required unless filter_off is set" % i)
-            if s.bg is not None and not ok(s.bg, (H, W, 3)):
-                raise BsxError("settings[%d].bg must be a contiguous cuda:%d uint8 tensor [%d,%d,3] (stream %d)" % (i, self.device, H, W, arr[i]))
-            items[i].d_frame, items[i].d_out = frames[i].data_ptr(), outs[i].data_ptr()
-            items[i].setting.d_bg = s.bg.data_ptr() if s.bg is not None else None
-            items[i].setting.flags = s.flags()
+        outs = list(outs)
+        arr, n, items, out_w, out_h = self._geom_items("step_vcam_geoms", ids, frames, settings, outs, 2 if yuyv else 3, common=True)
         _check(lib().bsx_step_batch_vcam_geoms(self.h, arr, items, n, out_w, out_h, _stream_ptr(), 1 if yuyv else 0), self.h, "bsx_step_batch_vcam_geoms")
         return outs
-
-    def _vcam_outs_items(self, ids, frames, settings, who):
-        """the ids and items of step_vcam_geoms_outs / step_vcam_geoms_outs_nv12, validated: (ctypes ids, n, ctypes items, the tensor check both use)"""
-        torch = _torch()
-        arr, n = _ids(ids)
-        frames, settings = list(frames), list(settings)
-        if len(frames) != n or len(settings) != n:
-            raise BsxError("%d ids for %d frames and %d settings" % (n, len(frames), len(settings)))
-        items = (_GeomItem * max(n, 1))()
-
-        def ok(t, shape):
-            return isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and self._on_device(t) and tuple(t.shape) == shape and t.is_contiguous()
-        for i in range(n):
-            g = self._geom_of(int(arr[i]))
-            H, W = g["height"], g["width"]
-            s = settings[i]
-            fch = 2 if isinstance(s, StreamSetting) and s.yuyv_in else 3      # the item's own pixel format: YUYV 4:2:2 or BGR
-            if not ok(frames[i], (H, W, fch)):
-                raise BsxFrameFormatError("frames[%d] must be a contiguous cuda:%d uint8 tensor [%d,%d,%d] (stream %d%s)" % (
-                    i, self.device, H, W, fch, arr[i], ", a YUYV item" if fch == 2 else ""))
-            if not isinstance(s, StreamSetting):
-                raise BsxError("settings[%d] is not a StreamSetting" % i)
-            if s.bgblur:
-                raise BsxError("settings[%d]: bgblur is not taken by %s" % (i, who))
-            if not s.filter_off and s.bg is None:
-                raise BsxError("settings[%d]: bg is required unless filter_off is set" % i)
-            if s.bg is not None and not ok(s.bg, (H, W, 3)):
-                raise BsxError("settings[%d].bg must be a contiguous cuda:%d uint8 tensor [%d,%d,3] (stream %d)" % (i, self.device, H, W, arr[i]))
-            items[i].d_frame, items[i].d_out = frames[i].data_ptr(), None
-            items[i].setting.d_bg = s.bg.data_ptr() if s.bg is not None else None
-            items[i].setting.flags = s.flags()
-        return arr, n, items, ok
 
     def step_vcam_geoms_outs(self, ids, frames, settings, outs, yuyv=False):
         """step_vcam_geoms with several outputs per stream, each of its own size (bsx_step_batch_vcam_geoms_outs): outs is a sequence of (item_index, tensor) —
@@ -430,30 +410,17 @@ class MaskGen:
         records (with none its stream still advances), a call uses at most 4 distinct sizes.  Every stream is filtered once; one resize pass writes every record."""
         torch = _torch()
         outs = list(outs)
-        arr, n, items, ok = self._vcam_outs_items(ids, frames, settings, "step_vcam_geoms_outs")
+        arr, n, items, _w, _h = self._geom_items("step_vcam_geoms_outs", ids, frames, settings)
         ch = 2 if yuyv else 3
-        m = len(outs)
-        recs = (_VcamOut * max(m, 1))()
-        named, sizes = {}, []
-        for j, rec in enumerate(outs):
-            if not isinstance(rec, (tuple, list)) or len(rec) != 2:
-                raise BsxError("outs[%d] must be a pair (item_index, tensor)" % j)
-            item, t = rec
-            if isinstance(item, bool) or not isinstance(item, (int, np.integer)) or not 0 <= int(item) < n:
-                raise BsxError("outs[%d]: item %r is not an index into the call's %d positions" % (j, item, n))
-            if not isinstance(t, torch.Tensor) or t.dim() != 3 or not ok(t, (int(t.shape[0]), int(t.shape[1]), ch)) or t.numel() == 0:
+
+        def fill(j, r, t):
+            if not isinstance(t, torch.Tensor) or t.dim() != 3 or not self._u8(t, (int(t.shape[0]), int(t.shape[1]), ch)) or t.numel() == 0:
                 raise BsxError("outs[%d]: the output must be a contiguous, non-empty cuda:%d uint8 tensor [out_h,out_w,%d]" % (j, self.device, ch))
-            oh, ow = int(t.shape[0]), int(t.shape[1])
-            if yuyv and (ow & 1):
-                raise BsxError("outs[%d]: YUYV output needs an even width (the tensor is %d wide)" % (j, ow))
-            named[int(item)] = named.get(int(item), 0) + 1
-            if named[int(item)] > BSX_MAX_OUTS_PER_ITEM:
-                raise BsxError("outs[%d]: record %d of position %d (at most %d name one position)" % (j, named[int(item)], int(item), BSX_MAX_OUTS_PER_ITEM))
-            if (ow, oh) not in sizes:
-                sizes.append((ow, oh))
-                if len(sizes) > BSX_MAX_OUT_SIZES:
-                    raise BsxError("outs[%d]: %d x %d is distinct output size %d of the call (at most %d)" % (j, ow, oh, len(sizes), BSX_MAX_OUT_SIZES))
-            recs[j].item, recs[j].out_w, recs[j].out_h, recs[j].d_out = int(item), ow, oh, t.data_ptr()
+            if yuyv and (int(t.shape[1]) & 1):
+                raise BsxError("outs[%d]: YUYV output needs an even width (the tensor is %d wide)" % (j, int(t.shape[1])))
+            r.d_out = t.data_ptr()
+            return int(t.shape[1]), int(t.shape[0])
+        recs, m = self._out_records(outs, n, _VcamOut, ("pair (item_index, tensor)", 2), fill)
         _check(lib().bsx_step_batch_vcam_geoms_outs(self.h, arr, items, n, recs, m, _stream_ptr(), 1 if yuyv else 0), self.h, "bsx_step_batch_vcam_geoms_outs")
         return [t for _i, t in outs]
 
@@ -486,39 +453,24 @@ class MaskGen:
             pitch.append(p)
         return ow, oh, pitch[0], pitch[1]
 
+    def _nv12_out_records(self, outs, n):
+        """the NV12 output records of a call of n positions, validated: (ctypes records, m).  outs: a list of (item_index, y, uv)"""
+        def fill(j, r, y, uv):
+            ow, oh, r.pitch_y, r.pitch_uv = self._nv12_planes("outs[%d]" % j, y, uv)
+            r.d_y, r.d_uv = y.data_ptr(), uv.data_ptr()
+            return ow, oh
+        return self._out_records(outs, n, _VcamOutNv12, ("triple (item_index, y, uv)", 3), fill)
+
     def step_vcam_geoms_outs_nv12(self, ids, frames, settings, outs):
         """step_vcam_geoms_outs with every output an NV12 surface with row pitches, as a video encoder takes it (bsx_step_batch_vcam_geoms_outs_nv12): outs is a
         sequence of (item_index, y, uv) — y a cuda uint8 view [out_h, out_w] with strides (pitch_y, 1), uv [out_h / 2, out_w] with strides (pitch_uv, 1), U and V
         interleaved; sizes and pitches are read from the views.  out_w and out_h even, pitches multiples of 4, both planes 4-byte aligned.  Y and chroma are the
         bytes of the YUYV output of step_vcam_geoms_outs, the chroma averaged (truncating) over each pair of rows; bytes past out_w of a row are not written."""
         outs = list(outs)
-        arr, n, items, _ok = self._vcam_outs_items(ids, frames, settings, "step_vcam_geoms_outs_nv12")
+        arr, n, items, _w, _h = self._geom_items("step_vcam_geoms_outs_nv12", ids, frames, settings)
         recs, m = self._nv12_out_records(outs, n)
         _check(lib().bsx_step_batch_vcam_geoms_outs_nv12(self.h, arr, items, n, recs, m, _stream_ptr(), 0), self.h, "bsx_step_batch_vcam_geoms_outs_nv12")
         return [(y, uv) for _i, y, uv in outs]
-
-    def _nv12_out_records(self, outs, n):
-        """the NV12 output records of a call of n positions, validated: (ctypes records, m).  outs: a list of (item_index, y, uv)"""
-        m = len(outs)
-        recs = (_VcamOutNv12 * max(m, 1))()
-        named, sizes = {}, []
-        for j, rec in enumerate(outs):
-            if not isinstance(rec, (tuple, list)) or len(rec) != 3:
-                raise BsxError("outs[%d] must be a triple (item_index, y, uv)" % j)
-            item, y, uv = rec
-            if isinstance(item, bool) or not isinstance(item, (int, np.integer)) or not 0 <= int(item) < n:
-                raise BsxError("outs[%d]: item %r is not an index into the call's %d positions" % (j, item, n))
-            ow, oh, py, puv = self._nv12_planes("outs[%d]" % j, y, uv)
-            named[int(item)] = named.get(int(item), 0) + 1
-            if named[int(item)] > BSX_MAX_OUTS_PER_ITEM:
-                raise BsxError("outs[%d]: record %d of position %d (at most %d name one position)" % (j, named[int(item)], int(item), BSX_MAX_OUTS_PER_ITEM))
-            if (ow, oh) not in sizes:
-                sizes.append((ow, oh))
-                if len(sizes) > BSX_MAX_OUT_SIZES:
-                    raise BsxError("outs[%d]: %d x %d is distinct output size %d of the call (at most %d)" % (j, ow, oh, len(sizes), BSX_MAX_OUT_SIZES))
-            r = recs[j]
-            r.item, r.out_w, r.out_h, r.pitch_y, r.pitch_uv, r.d_y, r.d_uv = int(item), ow, oh, py, puv, y.data_ptr(), uv.data_ptr()
-        return recs, m
 
     def step_surfaces(self, ids, surfaces, settings, outs):
         """step_vcam_geoms_outs_nv12 whose frames are NV12 surfaces too, as a video decoder leaves them (bsx_step_batch_surfaces): surfaces is a sequence of (y, uv),
@@ -529,7 +481,6 @@ class MaskGen:
         surfaces, settings, outs = list(surfaces), list(settings), list(outs)
         if len(surfaces) != n or len(settings) != n:
             raise BsxError("%d ids for %d surfaces and %d settings" % (n, len(surfaces), len(settings)))
-        torch = _torch()
         items = (_SurfaceItem * max(n, 1))()
         for i in range(n):
             g = self._geom_of(int(arr[i]))
@@ -540,22 +491,9 @@ class MaskGen:
             sw, sh, py, puv = self._nv12_planes("surfaces[%d]" % i, y, uv)
             if (sw, sh) != (W, H):
                 raise BsxFrameFormatError("surfaces[%d] is %d x %d, stream %d captures %d x %d" % (i, sw, sh, arr[i], W, H))
-            s = settings[i]
-            if not isinstance(s, StreamSetting):
-                raise BsxError("settings[%d] is not a StreamSetting" % i)
-            if s.bgblur:
-                raise BsxError("settings[%d]: bgblur is not taken by step_surfaces" % i)
-            if s.yuyv_in:
-                raise BsxError("settings[%d]: yuyv_in is not taken by step_surfaces (every frame is an NV12 surface)" % i)
-            if not s.filter_off and s.bg is None:
-                raise BsxError("settings[%d]: bg is required unless filter_off is set" % i)
-            if s.bg is not None and not (isinstance(s.bg, torch.Tensor) and s.bg.dtype == torch.uint8 and self._on_device(s.bg) and
-                                         tuple(s.bg.shape) == (H, W, 3) and s.bg.is_contiguous()):
-                raise BsxError("settings[%d].bg must be a contiguous cuda:%d uint8 tensor [%d,%d,3] (stream %d)" % (i, self.device, H, W, arr[i]))
+            self._geom_setting("step_surfaces", i, settings[i], H, W, arr[i], items[i], yuyv_in=False)
             it = items[i]
             it.d_y, it.d_uv, it.pitch_y, it.pitch_uv = y.data_ptr(), uv.data_ptr(), py, puv
-            it.setting.d_bg = s.bg.data_ptr() if s.bg is not None else None
-            it.setting.flags = s.flags()
         recs, m = self._nv12_out_records(outs, n)
         _check(lib().bsx_step_batch_surfaces(self.h, arr, items, n, recs, m, _stream_ptr(), 0), self.h, "bsx_step_batch_surfaces")
         return [(y, uv) for _i, y, uv in outs]

@@ -27,9 +27,7 @@
 #include "rtc.hpp"
 #include "specialised.hpp"
 #include "tflite_model.hpp"
-#include "vcam_nv12_plan.hpp"
-#include "vcam_outs_plan.hpp"
-#include "vcam_surface_plan.hpp"
+#include "geoms_request.hpp"
 
 using namespace bsx;
 
@@ -196,7 +194,7 @@ struct bsx_ctx {
   BlurDesc* h_blur = nullptr;               // pinned [kIdRing][n_streams]
   BlurDesc* d_blur = nullptr;               // device, likewise
   GaussCoef* d_blur_coef = nullptr;         // device [blur_coef_table_bytes()]
-  struct Span { uintptr_t begin, end; int item; bool dst; };
+  using Span = bsx::Span;
   std::vector<Span> rsz_spans;              // host scratch of the overlap check: the call's sources and destinations, sorted by address
   // Geometry classes (bsx_new_geoms): class 0 IS the context's own geometry — width, height, roi, in_roi, both tables and the first bytes of d_masks above — so every
   // one-geometry path reads what it always read; classes 1.. add their own ROIs and tables and their own slice of the ONE d_masks allocation.  Streams are numbered
@@ -226,7 +224,7 @@ struct bsx_ctx {
   // its copy is one too
   size_t geo_entry_bytes() const { return (size_t)n_streams * (sizeof(GeomDesc) + sizeof(VgSurfRec)); }
   GeomDesc* geo_entry(GeomDesc* ring, int k) const { return reinterpret_cast<GeomDesc*>(reinterpret_cast<uint8_t*>(ring) + (size_t)k * geo_entry_bytes()); }
-  std::vector<bsx_geom_item> sf_items;      // host scratch of bsx_step_batch_surfaces: its items as geoms_front takes them (d_frame = the Y plane)
+  GeomsChecked geo_checked;                 // host scratch of the multi-geometry steps: what geoms_check leaves (geoms_request.hpp)
   std::vector<int> geo_order, geo_ids;      // host scratch: the call's positions ordered by class, their stream ids in that order
   // bsx_step_batch_vcam_geoms: per output size the device array of one VgClass per class (kernels.hpp) — capture size, capture -> output table, per-tap bit — built
   // and uploaded on the first call at that size.  Class 0's table is the one in vcam_tabs (shared with bsx_step_batch_vcam); the others' memory is owned here.
@@ -239,7 +237,7 @@ struct bsx_ctx {
   uint8_t* h_vo = nullptr;                  // pinned [kIdRing][vo_entry_bytes()]
   uint8_t* d_vo = nullptr;                  // device, likewise
   size_t vo_entry_bytes() const { return (size_t)kMaxOutGroups * sizeof(VgOutGroup) + (size_t)BSX_MAX_OUTS_PER_ITEM * (size_t)n_streams * (sizeof(GeomDesc) + sizeof(VgNv12Rec)); }
-  std::vector<int> vo_class, vo_pos;        // host scratch: the class of each item, the position (place in the class-ordered descriptors) of each item
+  std::vector<int> vo_pos;                  // host scratch: the position (place in the class-ordered descriptors) of each item
   int geom_of(int stream) const { int g = 0; while (g + 1 < (int)geoms.size() && stream >= geoms[g + 1].first) g++; return g; }
   bool act16 = false;                  // BSX_ACT16=1: 16-bit activation STORAGE for the segmented Meet / MLKit networks (g1) — opt-in, IoU-gated; needs the specialised middle kernel
 
@@ -638,8 +636,10 @@ int bsx::refuse_call(bsx_ctx* c, const char* fn, const char* fmt, ...) {
 namespace {
 // every entry point that advances the temporal state refuses while the two-deep pipeline holds a composite that reads it
 int refuse_pending(bsx_ctx* c, const char* fn) {
-  return c->pend.active ? refuse(c, fn, "a pipelined composite is pending (flush with bsx_step_batch_pipelined(ctx, NULL, ...) first)") : BSX_OK;
+  return c->pend.active ? refuse(c, fn, "%s", kPendingComposite) : BSX_OK;
 }
+// a grid of 2^31 workgroups or more: nothing has been enqueued
+int too_many_workgroups(bsx_ctx* c, const char* fn) { c->last_error = std::string("error: ") + fn + ": the batch needs more than 2^31 workgroups\n"; return BSX_EDEVICE; }
 
 // every entry point that works at "the" capture size refuses a context of several geometry classes (bsx_new_geoms): only bsx_step_batch_geoms and bsx_step_batch_vcam_geoms step those
 int refuse_geoms(bsx_ctx* c, const char* fn) {
@@ -1059,20 +1059,6 @@ int bg_tab(bsx_ctx* c, int sw, int sh, int dw, int dh, const DevResizeTab** out)
   *out = &it->second;
   return BSX_OK;
 }
-// Does a destination among the spans overlap a source or another destination?  Sorted by address, one sweep; *d = the destination (named first: it is the one the
-// caller placed wrongly), *o = what it overlaps.
-bool spans_overlap(std::vector<bsx_ctx::Span>& sp, const bsx_ctx::Span** d, const bsx_ctx::Span** o) {
-  std::sort(sp.begin(), sp.end(), [](const bsx_ctx::Span& a, const bsx_ctx::Span& b) { return a.begin < b.begin; });
-  const bsx_ctx::Span* far_any = nullptr;   // of the spans that begin at or below the current one: the one that ends last, and the destination that ends last
-  const bsx_ctx::Span* far_dst = nullptr;
-  for (const bsx_ctx::Span& v : sp) {
-    const bsx_ctx::Span* hit = v.dst ? far_any : far_dst;
-    if (hit && hit->end > v.begin) { *d = v.dst ? &v : hit; *o = v.dst ? hit : &v; return true; }
-    if (!far_any || v.end > far_any->end) far_any = &v;
-    if (v.dst && (!far_dst || v.end > far_dst->end)) far_dst = &v;
-  }
-  return false;
-}
 // host-side validation of items[0..n): nothing is enqueued before it passes.  A destination may overlap neither a source picture nor another destination (the
 // launch reads and writes them in no order); sources may overlap each other — two entries may name one picture.  Sorted by address, one sweep.
 int resize_batch_check(bsx_ctx* c, const char* fn, const bsx_resize_item* items, int n, int dw, int dh) {
@@ -1159,7 +1145,7 @@ int blur_batch_check(bsx_ctx* c, const char* fn, const bsx_blur_item* items, int
   *cols = BlurTileCols{};
   for (int g = 0; g < kMaxGeoms; g++) {
     const long per = g < G ? blur_tiles(cw[g], ch[g]) : 0, cnt = g < G ? count[g] : 0;
-    if ((long)spans->wg[g] + cnt * per >= (1l << 31)) { c->last_error = std::string("error: ") + fn + ": the batch needs more than 2^31 workgroups\n"; return BSX_EDEVICE; }
+    if ((long)spans->wg[g] + cnt * per >= (1l << 31)) return too_many_workgroups(c, fn);
     spans->pos[g + 1] = spans->pos[g] + (int)cnt;
     spans->wg[g + 1] = spans->wg[g] + (int)(cnt * per);
     spans->per[g] = (int)per;
@@ -1195,9 +1181,8 @@ int blur_batch_stage(bsx_ctx* c, const bsx_blur_item* items, int n, const GeomSp
 }
 
 // ---- bsx_step_batch_geoms: streams of any mix of geometry classes in ONE prep launch, ONE network pass, ONE tile-class and ONE tile launch ----------------------
-// Checked on the host (ids, then every position against the class of its id, then the overlaps), then: the positions ordered by class, their ids and descriptors
+// Checked on the host (geoms_call: the ids, then geoms_request.hpp's geoms_check), then: the positions ordered by class, their ids and descriptors
 // through the staging ring, the per-class spans of the ragged grids by value in the kernel arguments.
-constexpr unsigned kGeomStreamFlags = BSX_STEP_FLIP_H | BSX_STEP_FLIP_V | BSX_STREAM_FILTER_OFF | BSX_STREAM_YUYV_IN;
 static_assert(BSX_STREAM_YUYV_IN == kGeomYuyvIn, "descriptor flags = the public bits");
 
 // does any item of the call bring a YUYV frame?  Then the call takes the launchers whose kernels read the format per position (kernels.hpp: launch_*_geoms_fmt)
@@ -1205,70 +1190,23 @@ inline bool geoms_any_yuyv(const bsx_geom_item* items, int n) {
   for (int i = 0; i < n; i++) if (items[i].setting.flags & BSX_STREAM_YUYV_IN) return true;
   return false;
 }
-// A YUYV item of class g: BSX_OK where the class has the fused YUYV prep (prep_yuyv_fusable), else the refusal, which names the table that is in the way.  There is
-// no conversion fallback here: the caller converts that stream with bsx_yuyv_to_bgr.
-int geoms_yuyv_item(bsx_ctx* c, const char* fn, int i, int id, int g, const bsx_ctx::Geom& G) {
-  const ResizeTab& t = G.tab_down.tab;
-  if (prep_yuyv_fusable(G.width, G.roi, t)) return BSX_OK;
-  char why[160];
-  if (t.mode == 1) snprintf(why, sizeof why, "its down-scale table is a copy (capture ROI %d x %d = model ROI)", G.roi.w, G.roi.h);
-  else if (t.mode == 2) snprintf(why, sizeof why, "its down-scale table is the 2x2 area mean (capture ROI %d x %d = twice the model ROI)", G.roi.w, G.roi.h);
-  else snprintf(why, sizeof why, "its down-scale table is linear but width %d and roi.x %d must be even and the ROI row at least 4 pixels", G.width, G.roi.x);
-  return refuse(c, fn, "items[%d]: stream %d is of class %d (%d x %d), which has no fused YUYV prep: %s; convert that stream's frames with bsx_yuyv_to_bgr and pass them as BGR",
-                i, id, g, G.width, G.height, why);
-}
-
-int geoms_check(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item* items, int n, unsigned flags) {
-  if (!items) return refuse(c, fn, "items is NULL");
-  if (flags & BSX_STEP_YUYV_IN) return refuse(c, fn, "flags 0x%x: YUYV input frames are not taken by the multi-geometry step as a batch flag (the format belongs to the item: the yuyv-in bit, 0x40, of items[i].setting.flags)", flags);
-  if (flags & ~(BSX_STEP_YUYV | BSX_STEP_NO_MASK)) return refuse(c, fn, "flags 0x%x has bits outside yuyv / no-mask", flags);
-  if (const int rc = refuse_pending(c, fn)) return rc;
-  if (c->onmask) return refuse(c, fn, "needs the fused mask + blend route (no onmask callback)");
-  const bool yuyv = (flags & BSX_STEP_YUYV) != 0;
-  std::vector<bsx_ctx::Span>& sp = c->rsz_spans;
-  sp.clear();
-  for (int i = 0; i < n; i++) {
-    const bsx_geom_item& it = items[i];
-    const int g = c->geom_of(ids[i]);
-    const bsx_ctx::Geom& G = c->geoms[g];
-    const unsigned f = it.setting.flags;
-    if (f & 0xFF00u) return refuse(c, fn, "items[%d]: setting flags 0x%x asks for a background blur, which the multi-geometry step does not take", i, f);
-    if (f & ~kGeomStreamFlags) return refuse(c, fn, "items[%d]: setting flags 0x%x has bits outside flip / filter-off / yuyv-in", i, f);
-    if (!it.d_frame) return refuse(c, fn, "items[%d]: d_frame is NULL", i);
-    if ((uintptr_t)it.d_frame & 3) return refuse(c, fn, "items[%d]: d_frame %p is not 4-byte aligned", i, (const void*)it.d_frame);
-    if (!it.d_out) return refuse(c, fn, "items[%d]: d_out is NULL", i);
-    if ((uintptr_t)it.d_out & 3) return refuse(c, fn, "items[%d]: d_out %p is not 4-byte aligned", i, (const void*)it.d_out);
-    if (yuyv && (G.width & 1)) return refuse(c, fn, "items[%d]: YUYV output needs an even width (stream %d is of class %d, %d x %d)", i, ids[i], g, G.width, G.height);
-    if (!G.fusable)
-      return refuse(c, fn, "items[%d]: stream %d is of class %d (%d x %d), which is off the fused tile route (width, roi.x, roi.w multiples of 4, a tiled linear mask up-scale)",
-                    i, ids[i], g, G.width, G.height);
-    if (f & BSX_STREAM_YUYV_IN) if (const int rc = geoms_yuyv_item(c, fn, i, ids[i], g, G)) return rc;
-    const size_t px = (size_t)G.width * G.height;
-    sp.push_back({(uintptr_t)it.d_frame, (uintptr_t)it.d_frame + px * ((f & BSX_STREAM_YUYV_IN) ? 2 : 3), i, false});      // the frame's real extent
-    sp.push_back({(uintptr_t)it.d_out, (uintptr_t)it.d_out + px * (yuyv ? 2 : 3), i, true});
-    if (f & BSX_STREAM_FILTER_OFF) continue;                          // reads no background
-    if (!it.setting.d_bg) return refuse(c, fn, "items[%d]: setting.d_bg is NULL", i);
-    if ((uintptr_t)it.setting.d_bg & 3) return refuse(c, fn, "items[%d]: setting.d_bg %p is not 4-byte aligned", i, (const void*)it.setting.d_bg);
-    sp.push_back({(uintptr_t)it.setting.d_bg, (uintptr_t)it.setting.d_bg + px * 3, i, false});
-  }
-  const bsx_ctx::Span* d = nullptr;
-  const bsx_ctx::Span* o = nullptr;
-  if (spans_overlap(sp, &d, &o))
-    return refuse(c, fn, "items[%d]: d_out %p overlaps %s of items[%d] (%p)", d->item, (const void*)d->begin, o->dst ? "the output" : "a frame or background", o->item,
-                  (const void*)o->begin);
-  return BSX_OK;
-}
+// the class records of the vcam steps: ROI-anchored tile columns where a class is `edge`
+const GeomClass* vg_classes(const bsx_ctx* c) { return c->d_geom_classes_vg ? c->d_geom_classes_vg : c->d_geom_classes; }
 
 // The front of a checked geoms call on the context's device, ring entry k acquired: the positions ordered by class, ids and descriptors through the ring, ONE prep
 // launch and the network.  Leaves the descriptors' device copy, the ragged grids of the back end and the classes whose tiles keep to one XCD.
 // edge: some position's class is off the 4-pixel grid (bsx_new_geoms_ex) — the geoms step then takes launch_mask_blend_geoms_edge
 struct GeomsStaged { const GeomDesc* desc = nullptr; GeomSpans tiles{}, outside{}; unsigned xcd_mask = 0; bool fmt = false, edge = false; };      // fmt: some item is YUYV — the *_fmt launchers
-// vg: the tile grid of the vcam step (ROI-anchored tile columns for every class)
-// surf (bsx_step_batch_surfaces): items[i].d_frame is the Y plane of the NV12 surface surf[i] — the surface records follow the descriptors in the ring entry, a
-// descriptor names its position in pad[0], and the prep launch is launch_prep_geoms_nv12
-int geoms_front(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item* items, int n, hipStream_t s, int k, GeomsStaged* st, bool vg = false,
-                const bsx_surface_item* surf = nullptr) {
-  const int G = (int)c->geoms.size();
+// Every kind but Geoms: the tile grid of the vcam step (ROI-anchored tile columns for every class).
+// Surfaces: items[i].d_frame is the Y plane of the NV12 surface surf[i] (geoms_check left such items) — the surface records follow the descriptors in the ring entry,
+// a descriptor names its position in pad[0], and the prep launch is launch_prep_geoms_nv12
+int geoms_front(bsx_ctx* c, const GeomsRequest& q, hipStream_t s, int k, GeomsStaged* st) {
+  const char* fn = geoms_kind(q.kind).fn;
+  const bool vg = q.kind != GeomsKind::Geoms;
+  const bsx_surface_item* const surf = q.kind == GeomsKind::Surfaces ? q.surfaces : nullptr;
+  const bsx_geom_item* const items = surf ? c->geo_checked.front_items.data() : q.items;
+  const int* const ids = q.ids;
+  const int n = q.n, G = (int)c->geoms.size();
   // positions ordered by class (a counting sort: stable, so a class keeps the caller's order)
   int count[kMaxGeoms] = {0};
   for (int i = 0; i < n; i++) count[c->geom_of(ids[i])]++;
@@ -1278,8 +1216,8 @@ int geoms_front(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item*
   for (int g = 0; g < kMaxGeoms; g++) {
     const int cnt = g < G ? count[g] : 0;
     const int per_t = g < G ? (int)(vg ? c->geoms[g].vg_tiles_per_frame : c->geoms[g].tiles_per_frame) : 0, per_o = g < G ? c->geoms[g].outside_blocks : 0;
-    if ((long)tiles.wg[g] + (long)cnt * per_t >= (1l << 31) || (long)outside.wg[g] + (long)cnt * per_o >= (1l << 31)) {
-      c->last_error = std::string("error: ") + fn + ": the batch needs more than 2^31 workgroups\n"; return BSX_EDEVICE; }
+    if ((long)tiles.wg[g] + (long)cnt * per_t >= (1l << 31) || (long)outside.wg[g] + (long)cnt * per_o >= (1l << 31))
+      return too_many_workgroups(c, fn);
     prep.pos[g + 1] = tiles.pos[g + 1] = outside.pos[g + 1] = tiles.pos[g] + cnt;
     tiles.wg[g + 1] = tiles.wg[g] + cnt * per_t; tiles.per[g] = per_t;
     outside.wg[g + 1] = outside.wg[g] + cnt * per_o; outside.per[g] = per_o;
@@ -1319,61 +1257,17 @@ int geoms_front(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item*
 }
 
 // the checked call on the context's device, ring entry k acquired
-int geoms_run(bsx_ctx* c, const int* ids, const bsx_geom_item* items, int n, hipStream_t s, unsigned flags, int k) {
+int geoms_run(bsx_ctx* c, const GeomsRequest& q, hipStream_t s, int k) {
   GeomsStaged st;
-  if (const int rc = geoms_front(c, "bsx_step_batch_geoms", ids, items, n, s, k, &st)) return rc;
+  if (const int rc = geoms_front(c, q, s, k, &st)) return rc;
   bsx_roctx::Range range("bsx:mask+blend");
-  BSX_HIP(c, (st.edge ? launch_mask_blend_geoms_edge : st.fmt ? launch_mask_blend_geoms_fmt : launch_mask_blend_geoms)(c->d_geom_classes, st.desc, st.tiles, st.xcd_mask, st.outside, c->d_ofinal, c->outW, c->outH, c->d_geom_tile_class, n, s, (int)flags));
+  BSX_HIP(c, (st.edge ? launch_mask_blend_geoms_edge : st.fmt ? launch_mask_blend_geoms_fmt : launch_mask_blend_geoms)(c->d_geom_classes, st.desc, st.tiles, st.xcd_mask, st.outside, c->d_ofinal, c->outW, c->outH, c->d_geom_tile_class, q.n, s, (int)q.flags));
   return BSX_OK;
 }
 
 // ---- bsx_step_batch_vcam_geoms: the geoms step with every composite written at ONE common size, the virtual camera's ------------------------------------------
 // geoms_run's shape: the same front, then [one tile-class launch,] ONE masks-only tile launch and ONE resize pass over every position's frame, background and mask
 // taps.  Outside a ROI the persistent mask is 255 from reset on, so nothing there needs a launch; no capture-size composite is stored.
-int vcam_geoms_check(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item* items, int n, int out_w, int out_h, unsigned flags) {
-  if (!items) return refuse(c, fn, "items is NULL");
-  if (out_w <= 0 || out_h <= 0) return refuse(c, fn, "output size %d x %d must be positive", out_w, out_h);
-  if (flags & BSX_STEP_NO_MASK) return refuse(c, fn, "unsupported flags 0x%x (the no-mask step has no vcam form)", flags);
-  if (flags & BSX_STEP_YUYV_IN) return refuse(c, fn, "flags 0x%x: YUYV input frames are not taken by the multi-geometry step as a batch flag (the format belongs to the item: the yuyv-in bit, 0x40, of items[i].setting.flags)", flags);
-  if (flags & ~BSX_STEP_YUYV) return refuse(c, fn, "flags 0x%x has bits outside yuyv", flags);
-  if (const int rc = refuse_pending(c, fn)) return rc;
-  if (c->onmask) return refuse(c, fn, "needs the fused mask route (no onmask callback)");
-  const bool yuyv = (flags & BSX_STEP_YUYV) != 0;
-  if (yuyv && (out_w & 1)) return refuse(c, fn, "YUYV output needs an even width (out_w = %d)", out_w);
-  const size_t out_bytes = (size_t)out_w * out_h * (yuyv ? 2 : 3);
-  std::vector<bsx_ctx::Span>& sp = c->rsz_spans;
-  sp.clear();
-  for (int i = 0; i < n; i++) {
-    const bsx_geom_item& it = items[i];
-    const int g = c->geom_of(ids[i]);
-    const bsx_ctx::Geom& G = c->geoms[g];
-    const unsigned f = it.setting.flags;
-    if (f & 0xFF00u) return refuse(c, fn, "items[%d]: setting flags 0x%x asks for a background blur, which the multi-geometry step does not take", i, f);
-    if (f & ~kGeomStreamFlags) return refuse(c, fn, "items[%d]: setting flags 0x%x has bits outside flip / filter-off / yuyv-in", i, f);
-    if (!it.d_frame) return refuse(c, fn, "items[%d]: d_frame is NULL", i);
-    if ((uintptr_t)it.d_frame & 3) return refuse(c, fn, "items[%d]: d_frame %p is not 4-byte aligned", i, (const void*)it.d_frame);
-    if (!it.d_out) return refuse(c, fn, "items[%d]: d_out is NULL", i);
-    if ((uintptr_t)it.d_out & 3) return refuse(c, fn, "items[%d]: d_out %p is not 4-byte aligned", i, (const void*)it.d_out);
-    if (!G.fusable)
-      return refuse(c, fn, "items[%d]: stream %d is of class %d (%d x %d), which is off the fused tile route (width, roi.x, roi.w multiples of 4, a tiled linear mask up-scale); "
-                    "bsx_step_batch_vcam_mixed takes such a context", i, ids[i], g, G.width, G.height);
-    if (f & BSX_STREAM_YUYV_IN) if (const int rc = geoms_yuyv_item(c, fn, i, ids[i], g, G)) return rc;
-    const size_t px = (size_t)G.width * G.height;
-    sp.push_back({(uintptr_t)it.d_frame, (uintptr_t)it.d_frame + px * ((f & BSX_STREAM_YUYV_IN) ? 2 : 3), i, false});      // the frame's real extent
-    sp.push_back({(uintptr_t)it.d_out, (uintptr_t)it.d_out + out_bytes, i, true});
-    if (f & BSX_STREAM_FILTER_OFF) continue;                          // reads no background
-    if (!it.setting.d_bg) return refuse(c, fn, "items[%d]: setting.d_bg is NULL", i);
-    if ((uintptr_t)it.setting.d_bg & 3) return refuse(c, fn, "items[%d]: setting.d_bg %p is not 4-byte aligned", i, (const void*)it.setting.d_bg);
-    sp.push_back({(uintptr_t)it.setting.d_bg, (uintptr_t)it.setting.d_bg + px * 3, i, false});
-  }
-  const bsx_ctx::Span* d = nullptr;
-  const bsx_ctx::Span* o = nullptr;
-  if (spans_overlap(sp, &d, &o))
-    return refuse(c, fn, "items[%d]: d_out %p overlaps %s of items[%d] (%p)", d->item, (const void*)d->begin, o->dst ? "the output" : "a frame or background", o->item,
-                  (const void*)o->begin);
-  return BSX_OK;
-}
-
 // the class records of (out_w, out_h), built and uploaded on the first call at that size
 int vg_geoms_records(bsx_ctx* c, int out_w, int out_h, const VgClass** out, const VgClass** host = nullptr) {
   const auto key = std::make_pair(out_w, out_h);
@@ -1407,157 +1301,27 @@ int vg_geoms_records(bsx_ctx* c, int out_w, int out_h, const VgClass** out, cons
   return BSX_OK;
 }
 
-int vcam_geoms_run(bsx_ctx* c, const int* ids, const bsx_geom_item* items, int n, int out_w, int out_h, hipStream_t s, unsigned flags, int k) {
-  const char* fn = "bsx_step_batch_vcam_geoms";
-  const long out_tiles = (long)((out_w + 63) / 64) * ((out_h + 31) / 32);      // the resize pass's 64 x 32 output tiles (kernels_img.hip)
-  if (out_tiles * n >= (1l << 31)) { c->last_error = std::string("error: ") + fn + ": the batch needs more than 2^31 workgroups\n"; return BSX_EDEVICE; }
+int vcam_geoms_run(bsx_ctx* c, const GeomsRequest& q, hipStream_t s, int k) {
+  const long out_tiles = (long)((q.out_w + 63) / 64) * ((q.out_h + 31) / 32);      // the resize pass's 64 x 32 output tiles (kernels_img.hip)
+  if (out_tiles * q.n >= (1l << 31)) return too_many_workgroups(c, geoms_kind(q.kind).fn);
   const VgClass* vg = nullptr;
-  if (const int rc = vg_geoms_records(c, out_w, out_h, &vg)) return rc;
+  if (const int rc = vg_geoms_records(c, q.out_w, q.out_h, &vg)) return rc;
   GeomsStaged st;
-  if (const int rc = geoms_front(c, fn, ids, items, n, s, k, &st, true)) return rc;
+  if (const int rc = geoms_front(c, q, s, k, &st)) return rc;
   bsx_roctx::Range range("bsx:mask+vcam");
-  BSX_HIP(c, (st.fmt ? launch_vcam_geoms_fmt : launch_vcam_geoms)(c->d_geom_classes_vg ? c->d_geom_classes_vg : c->d_geom_classes, vg, st.desc, st.tiles, st.xcd_mask, c->d_ofinal, c->outW, c->outH, c->d_geom_tile_class, out_w, out_h, n, s, flags & 1u));
+  BSX_HIP(c, (st.fmt ? launch_vcam_geoms_fmt : launch_vcam_geoms)(vg_classes(c), vg, st.desc, st.tiles, st.xcd_mask, c->d_ofinal, c->outW, c->outH, c->d_geom_tile_class, q.out_w, q.out_h, q.n, s, q.flags & 1u));
   return BSX_OK;
 }
 
 // ---- bsx_step_batch_vcam_geoms_outs: the vcam geoms step with several outputs per position, each of its own size -----------------------------------------------
 // vcam_geoms_run's shape: the same front, then [one tile-class launch,] ONE masks-only tile launch and ONE resize pass whose grid ranges over the output records
-// (vcam_outs_plan.hpp orders them into (class, size) groups).  The item checks are vcam_geoms_check's without d_out, which this entry point does not read.
-// the part of the check that both output forms share, after the flags: the context's state and the items.  Leaves the items' frames and backgrounds in rsz_spans
-// and their classes in vo_class.
-int vcam_outs_items(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item* items, int n) {
-  if (const int rc = refuse_pending(c, fn)) return rc;
-  if (c->onmask) return refuse(c, fn, "needs the fused mask route (no onmask callback)");
-  std::vector<bsx_ctx::Span>& sp = c->rsz_spans;
-  sp.clear();
-  c->vo_class.resize((size_t)n);
-  for (int i = 0; i < n; i++) {
-    const bsx_geom_item& it = items[i];
-    const int g = c->geom_of(ids[i]);
-    const bsx_ctx::Geom& G = c->geoms[g];
-    const unsigned f = it.setting.flags;
-    c->vo_class[(size_t)i] = g;
-    if (f & 0xFF00u) return refuse(c, fn, "items[%d]: setting flags 0x%x asks for a background blur, which the multi-geometry step does not take", i, f);
-    if (f & ~kGeomStreamFlags) return refuse(c, fn, "items[%d]: setting flags 0x%x has bits outside flip / filter-off / yuyv-in", i, f);
-    if (!it.d_frame) return refuse(c, fn, "items[%d]: d_frame is NULL", i);
-    if ((uintptr_t)it.d_frame & 3) return refuse(c, fn, "items[%d]: d_frame %p is not 4-byte aligned", i, (const void*)it.d_frame);
-    if (!G.fusable)
-      return refuse(c, fn, "items[%d]: stream %d is of class %d (%d x %d), which is off the fused tile route (width, roi.x, roi.w multiples of 4, a tiled linear mask up-scale)",
-                    i, ids[i], g, G.width, G.height);
-    if (f & BSX_STREAM_YUYV_IN) if (const int rc = geoms_yuyv_item(c, fn, i, ids[i], g, G)) return rc;
-    const size_t px = (size_t)G.width * G.height;
-    sp.push_back({(uintptr_t)it.d_frame, (uintptr_t)it.d_frame + px * ((f & BSX_STREAM_YUYV_IN) ? 2 : 3), i, false});      // the frame's real extent
-    if (f & BSX_STREAM_FILTER_OFF) continue;                          // reads no background
-    if (!it.setting.d_bg) return refuse(c, fn, "items[%d]: setting.d_bg is NULL", i);
-    if ((uintptr_t)it.setting.d_bg & 3) return refuse(c, fn, "items[%d]: setting.d_bg %p is not 4-byte aligned", i, (const void*)it.setting.d_bg);
-    sp.push_back({(uintptr_t)it.setting.d_bg, (uintptr_t)it.setting.d_bg + px * 3, i, false});
-  }
-  return BSX_OK;
-}
-
-int vcam_outs_check(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item* items, int n, const bsx_vcam_out* outs, int m, unsigned flags, VcamOutsPlan* plan) {
-  if (!items) return refuse(c, fn, "items is NULL");
-  if (flags & BSX_STEP_NO_MASK) return refuse(c, fn, "unsupported flags 0x%x (the no-mask step has no vcam form)", flags);
-  if (flags & BSX_STEP_YUYV_IN) return refuse(c, fn, "flags 0x%x: YUYV input frames are not taken by the multi-geometry step as a batch flag (the format belongs to the item: the yuyv-in bit, 0x40, of items[i].setting.flags)", flags);
-  if (flags & ~BSX_STEP_YUYV) return refuse(c, fn, "flags 0x%x has bits outside yuyv", flags);
-  if (const int rc = vcam_outs_items(c, fn, ids, items, n)) return rc;
-  const bool yuyv = (flags & BSX_STEP_YUYV) != 0;
-  std::vector<bsx_ctx::Span>& sp = c->rsz_spans;
-  const int pr = vcam_outs_plan(c->vo_class.data(), n, outs, m, yuyv, plan);
-  if (pr == VcamOutsPlan::kRefused) return refuse(c, fn, "%s", plan->text);
-  if (pr == VcamOutsPlan::kTooLarge) { c->last_error = std::string("error: ") + fn + ": the batch needs more than 2^31 workgroups\n"; return BSX_EDEVICE; }
-  for (int j = 0; j < m; j++)
-    sp.push_back({(uintptr_t)outs[j].d_out, (uintptr_t)outs[j].d_out + (size_t)outs[j].out_w * outs[j].out_h * (yuyv ? 2 : 3), j, true});
-  const bsx_ctx::Span* d = nullptr;
-  const bsx_ctx::Span* o = nullptr;
-  if (spans_overlap(sp, &d, &o))
-    return refuse(c, fn, "outs[%d]: d_out %p overlaps %s[%d] (%p)", d->item, (const void*)d->begin, o->dst ? "the output of outs" : "a frame or background of items", o->item,
-                  (const void*)o->begin);
-  return BSX_OK;
-}
-
-// ... of bsx_step_batch_vcam_geoms_outs_nv12: the same items, the records by vcam_nv12_plan.hpp, a plane's extent pitch * (rows - 1) + out_w.  Span::item of a plane
-// is 2 j for outs[j].d_y and 2 j + 1 for outs[j].d_uv.
-int vcam_nv12_check(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item* items, int n, const bsx_vcam_out_nv12* outs, int m, unsigned flags, VcamOutsPlan* plan) {
-  if (!items) return refuse(c, fn, "items is NULL");
-  if (flags) return refuse(c, fn, "flags 0x%x: this step takes no flags (an item's format and flips belong to items[i].setting.flags)", flags);
-  if (const int rc = vcam_outs_items(c, fn, ids, items, n)) return rc;
-  const int pr = vcam_nv12_plan(c->vo_class.data(), n, outs, m, plan);
-  if (pr == VcamOutsPlan::kRefused) return refuse(c, fn, "%s", plan->text);
-  if (pr == VcamOutsPlan::kTooLarge) { c->last_error = std::string("error: ") + fn + ": the batch needs more than 2^31 workgroups\n"; return BSX_EDEVICE; }
-  std::vector<bsx_ctx::Span>& sp = c->rsz_spans;
-  for (int j = 0; j < m; j++) {
-    const bsx_vcam_out_nv12& r = outs[j];
-    sp.push_back({(uintptr_t)r.d_y, (uintptr_t)r.d_y + vcam_nv12_extent(r.pitch_y, r.out_h, r.out_w), 2 * j, true});
-    sp.push_back({(uintptr_t)r.d_uv, (uintptr_t)r.d_uv + vcam_nv12_extent(r.pitch_uv, r.out_h / 2, r.out_w), 2 * j + 1, true});
-  }
-  const bsx_ctx::Span* d = nullptr;
-  const bsx_ctx::Span* o = nullptr;
-  if (spans_overlap(sp, &d, &o)) {
-    const char* const plane = (d->item & 1) ? "d_uv" : "d_y";
-    if (o->dst)
-      return refuse(c, fn, "outs[%d]: %s %p overlaps %s of outs[%d] (%p)", d->item / 2, plane, (const void*)d->begin, (o->item & 1) ? "d_uv" : "d_y", o->item / 2,
-                    (const void*)o->begin);
-    return refuse(c, fn, "outs[%d]: %s %p overlaps a frame or background of items[%d] (%p)", d->item / 2, plane, (const void*)d->begin, o->item, (const void*)o->begin);
-  }
-  return BSX_OK;
-}
-
-// ... of bsx_step_batch_surfaces: vcam_nv12_check with the items' frames NV12 surfaces — the item checks and the class admission by vcam_surface_plan.hpp, an input
-// plane's extent pitch * (rows - 1) + W.  Leaves the items as geoms_front takes them in sf_items.
-int vcam_surfaces_check(bsx_ctx* c, const char* fn, const int* ids, const bsx_surface_item* items, int n, const bsx_vcam_out_nv12* outs, int m, unsigned flags,
-                        VcamOutsPlan* plan) {
-  if (!items) return refuse(c, fn, "items is NULL");
-  if (flags) return refuse(c, fn, "flags 0x%x: this step takes no flags (an item's flips belong to items[i].setting.flags)", flags);
-  if (const int rc = refuse_pending(c, fn)) return rc;
-  if (c->onmask) return refuse(c, fn, "needs the fused mask route (no onmask callback)");
-  std::vector<bsx_ctx::Span>& sp = c->rsz_spans;
-  sp.clear();
-  c->vo_class.resize((size_t)n);
-  c->sf_items.resize((size_t)n);
-  SurfaceRefusal why;
-  for (int i = 0; i < n; i++) {
-    const bsx_surface_item& it = items[i];
-    const int g = c->geom_of(ids[i]);
-    const bsx_ctx::Geom& G = c->geoms[g];
-    c->vo_class[(size_t)i] = g;
-    if (!vcam_surface_item(it, i, G.width, G.height, &why)) return refuse(c, fn, "%s", why.text);
-    if (!G.fusable)
-      return refuse(c, fn, "items[%d]: stream %d is of class %d (%d x %d), which is off the fused tile route (width, roi.x, roi.w multiples of 4, a tiled linear mask up-scale)",
-                    i, ids[i], g, G.width, G.height);
-    if (!vcam_surface_class(i, ids[i], g, G.width, G.height, G.tab_down.tab.mode, G.roi.w, G.roi.h, &why)) return refuse(c, fn, "%s", why.text);
-    c->sf_items[(size_t)i] = bsx_geom_item{it.d_y, nullptr, it.setting};
-    // Span::item of an input: 3 i for d_y, 3 i + 1 for d_uv, 3 i + 2 for the background
-    sp.push_back({(uintptr_t)it.d_y, (uintptr_t)it.d_y + vcam_nv12_extent(it.pitch_y, G.height, G.width), 3 * i, false});
-    sp.push_back({(uintptr_t)it.d_uv, (uintptr_t)it.d_uv + vcam_nv12_extent(it.pitch_uv, G.height / 2, G.width), 3 * i + 1, false});
-    if (it.setting.flags & BSX_STREAM_FILTER_OFF) continue;          // reads no background
-    sp.push_back({(uintptr_t)it.setting.d_bg, (uintptr_t)it.setting.d_bg + (size_t)G.width * G.height * 3, 3 * i + 2, false});
-  }
-  const int pr = vcam_nv12_plan(c->vo_class.data(), n, outs, m, plan);
-  if (pr == VcamOutsPlan::kRefused) return refuse(c, fn, "%s", plan->text);
-  if (pr == VcamOutsPlan::kTooLarge) { c->last_error = std::string("error: ") + fn + ": the batch needs more than 2^31 workgroups\n"; return BSX_EDEVICE; }
-  for (int j = 0; j < m; j++) {
-    const bsx_vcam_out_nv12& r = outs[j];
-    sp.push_back({(uintptr_t)r.d_y, (uintptr_t)r.d_y + vcam_nv12_extent(r.pitch_y, r.out_h, r.out_w), 2 * j, true});
-    sp.push_back({(uintptr_t)r.d_uv, (uintptr_t)r.d_uv + vcam_nv12_extent(r.pitch_uv, r.out_h / 2, r.out_w), 2 * j + 1, true});
-  }
-  const bsx_ctx::Span* d = nullptr;
-  const bsx_ctx::Span* o = nullptr;
-  if (spans_overlap(sp, &d, &o)) {
-    const char* const plane = (d->item & 1) ? "d_uv" : "d_y";
-    if (o->dst)
-      return refuse(c, fn, "outs[%d]: %s %p overlaps %s of outs[%d] (%p)", d->item / 2, plane, (const void*)d->begin, (o->item & 1) ? "d_uv" : "d_y", o->item / 2,
-                    (const void*)o->begin);
-    static const char* const kIn[3] = {"d_y", "d_uv", "setting.d_bg"};
-    return refuse(c, fn, "outs[%d]: %s %p overlaps %s of items[%d] (%p)", d->item / 2, plane, (const void*)d->begin, kIn[o->item % 3], o->item / 3, (const void*)o->begin);
-  }
-  return BSX_OK;
-}
-
-// outs: the BGR / YUYV records; nv12 (outs NULL): the NV12 records, whose plane records follow the descriptors in the ring entry
-// surf (with nv12): the items' frames are NV12 surfaces (geoms_front's surf); the resize pass is launch_vcam_geoms_outs_nv12in's
-int vcam_outs_run(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_item* items, int n, const bsx_vcam_out* outs, const bsx_vcam_out_nv12* nv12,
-                  const VcamOutsPlan& plan, hipStream_t s, unsigned flags, int k, const bsx_surface_item* surf = nullptr) {
+// (geoms_check left the plan: the records ordered into (class, size) groups).  The three kinds with records — VcamOuts: BGR / YUYV; VcamOutsNv12 and Surfaces: NV12,
+// whose plane records follow the descriptors in the ring entry; Surfaces: the items' frames are NV12 surfaces too (geoms_front) — differ in the resize pass the
+// launcher picks.
+int vcam_outs_run(bsx_ctx* c, const GeomsRequest& q, hipStream_t s, int k) {
+  const VcamOutsPlan& plan = c->geo_checked.plan;
+  const bool nv12 = geoms_kind(q.kind).records == GeomsRecords::Nv12, surf = geoms_kind(q.kind).surface;
+  const int n = q.n;
   const size_t eb = c->vo_entry_bytes(), m = plan.order.size();
   if (!c->h_vo) BSX_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_vo), bsx_ctx::kIdRing * eb, hipHostMallocDefault));
   if (!c->d_vo) BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_vo), bsx_ctx::kIdRing * eb));
@@ -1568,7 +1332,7 @@ int vcam_outs_run(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_ite
     if (const int rc = vg_geoms_records(c, plan.sizes[q][0], plan.sizes[q][1], &dev, &rec[q])) return rc;
   }
   GeomsStaged st;
-  if (const int rc = geoms_front(c, fn, ids, items, n, s, k, &st, true, surf)) return rc;
+  if (const int rc = geoms_front(c, q, s, k, &st)) return rc;
   // groups and output descriptors into ring entry k: a record's descriptor is its position's (geoms_front left them in the pinned entry) with `out` replaced
   VgOutGroup* const hg = reinterpret_cast<VgOutGroup*>(c->h_vo + (size_t)k * eb);
   GeomDesc* const ho = reinterpret_cast<GeomDesc*>(hg + kMaxOutGroups);
@@ -1577,7 +1341,7 @@ int vcam_outs_run(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_ite
   for (int j = 0; j < n; j++) c->vo_pos[(size_t)c->geo_order[(size_t)j]] = j;
   OutSpans sp{};
   sp.ng = (int)plan.groups.size();
-  const unsigned yuyv = flags & 1u;
+  const unsigned yuyv = q.flags & 1u;
   for (int g = 0; g < kMaxOutGroups; g++) {
     sp.wg[g] = (int)plan.total_wg;
     if (g >= sp.ng) { hg[g] = VgOutGroup{}; continue; }
@@ -1587,39 +1351,51 @@ int vcam_outs_run(bsx_ctx* c, const char* fn, const int* ids, const bsx_geom_ite
   }
   sp.wg[kMaxOutGroups] = (int)plan.total_wg;
   VgNv12Rec* const hn = reinterpret_cast<VgNv12Rec*>(ho + m);          // (48 m bytes behind a 16-byte aligned address)
-  for (size_t q = 0; q < m; q++) {
+  for (size_t r = 0; r < m; r++) {
     if (nv12) {
-      const bsx_vcam_out_nv12& o = nv12[plan.order[q]];
-      ho[q] = hd[c->vo_pos[(size_t)o.item]];
-      ho[q].out = o.d_y;
-      hn[q] = VgNv12Rec{o.d_uv, o.pitch_y, o.pitch_uv};
+      const bsx_vcam_out_nv12& o = q.outs_nv12[plan.order[r]];
+      ho[r] = hd[c->vo_pos[(size_t)o.item]];
+      ho[r].out = o.d_y;
+      hn[r] = VgNv12Rec{o.d_uv, o.pitch_y, o.pitch_uv};
     } else {
-      const bsx_vcam_out& o = outs[plan.order[q]];
-      ho[q] = hd[c->vo_pos[(size_t)o.item]];
-      ho[q].out = o.d_out;
+      const bsx_vcam_out& o = q.outs[plan.order[r]];
+      ho[r] = hd[c->vo_pos[(size_t)o.item]];
+      ho[r].out = o.d_out;
     }
   }
   uint8_t* const dv = c->d_vo + (size_t)k * eb;
   const size_t desc_at = (size_t)kMaxOutGroups * sizeof(VgOutGroup), nrec_at = desc_at + m * sizeof(GeomDesc);
   if (m) BSX_HIP(c, hipMemcpyAsync(dv, hg, nrec_at + (nv12 ? m * sizeof(VgNv12Rec) : 0), hipMemcpyHostToDevice, s));
   bsx_roctx::Range range("bsx:mask+vcam");
-  if (surf) {
-    BSX_HIP(c, launch_vcam_geoms_outs_nv12in(c->d_geom_classes_vg ? c->d_geom_classes_vg : c->d_geom_classes, reinterpret_cast<const VgOutGroup*>(dv),
-                                             reinterpret_cast<const GeomDesc*>(dv + desc_at), reinterpret_cast<const VgNv12Rec*>(dv + nrec_at),
-                                             reinterpret_cast<const VgSurfRec*>(st.desc + n), sp, st.desc, st.tiles, st.xcd_mask, c->d_ofinal, c->outW, c->outH,
-                                             c->d_geom_tile_class, n, s));
-    return BSX_OK;
-  }
-  if (nv12) {
-    BSX_HIP(c, launch_vcam_geoms_outs_nv12(c->d_geom_classes_vg ? c->d_geom_classes_vg : c->d_geom_classes, reinterpret_cast<const VgOutGroup*>(dv),
-                                           reinterpret_cast<const GeomDesc*>(dv + desc_at), reinterpret_cast<const VgNv12Rec*>(dv + nrec_at), sp, st.desc, st.tiles,
-                                           st.xcd_mask, c->d_ofinal, c->outW, c->outH, c->d_geom_tile_class, n, s, st.fmt));
-    return BSX_OK;
-  }
-  BSX_HIP(c, launch_vcam_geoms_outs(c->d_geom_classes_vg ? c->d_geom_classes_vg : c->d_geom_classes, reinterpret_cast<const VgOutGroup*>(dv),
-                                    reinterpret_cast<const GeomDesc*>(dv + (size_t)kMaxOutGroups * sizeof(VgOutGroup)), sp, st.desc, st.tiles, st.xcd_mask, c->d_ofinal,
-                                    c->outW, c->outH, c->d_geom_tile_class, n, s, st.fmt));
+  BSX_HIP(c, launch_vcam_geoms_outs(vg_classes(c), reinterpret_cast<const VgOutGroup*>(dv), reinterpret_cast<const GeomDesc*>(dv + desc_at),
+                                    nv12 ? reinterpret_cast<const VgNv12Rec*>(dv + nrec_at) : nullptr, surf ? reinterpret_cast<const VgSurfRec*>(st.desc + n) : nullptr, sp,
+                                    st.desc, st.tiles, st.xcd_mask, c->d_ofinal, c->outW, c->outH, c->d_geom_tile_class, n, s, st.fmt));
   return BSX_OK;
+}
+
+// The one path of the five entry points: the ids, the empty batch, the request's check (geoms_request.hpp: nothing is enqueued before it passes), then on the
+// context's device a ring entry and the run of the request's kind.  The entry points only build the request.
+int geoms_call(bsx_ctx* c, GeomsRequest q, void* stream) {
+  if (!c) return BSX_EINVAL;
+  const char* fn = geoms_kind(q.kind).fn;
+  if (const int rc = ids_check(c, fn, q.ids, q.n)) return rc;
+  if (q.n == 0) return refuse_pending(c, fn);
+  GeomsClass classes[kMaxGeoms];
+  q.classes = classes; q.n_classes = (int)c->geoms.size();
+  for (int g = 0; g < q.n_classes; g++) {
+    const bsx_ctx::Geom& G = c->geoms[(size_t)g];
+    classes[g] = GeomsClass{G.first, G.width, G.height, G.fusable, G.tab_down.tab.mode, G.roi.x, G.roi.w, G.roi.h, prep_yuyv_fusable(G.width, G.roi, G.tab_down.tab)};
+  }
+  q.pending = c->pend.active; q.onmask = c->onmask != nullptr;
+  const int checked = geoms_check(q, &c->geo_checked);
+  if (checked == GeomsChecked::kRefused) return refuse(c, fn, "%s", c->geo_checked.why.text);
+  if (checked == GeomsChecked::kTooLarge) return too_many_workgroups(c, fn);
+  DeviceGuard guard(c->device);
+  hipStream_t s = pick(c, stream);
+  if (const int rc = geoms_device_state(c)) return rc;
+  int entry = 0;
+  if (const int rc = ring_acquire(c, &entry)) return rc;
+  return ids_release(c, entry, s, (q.kind == GeomsKind::Geoms ? geoms_run : q.kind == GeomsKind::VcamGeoms ? vcam_geoms_run : vcam_outs_run)(c, q, s, entry));
 }
 
 // ---- two-deep pipeline: mask pipeline of batch k  ||  composite of batch k - 1 ------------------------------------------------------------------
@@ -2037,82 +1813,35 @@ int bsx_get_geom_info(const bsx_ctx* c, int g, bsx_geom_info* o) {
   return BSX_OK;
 }
 
-// ids (host): position i is stream ids[i], whose class decides the geometry of items[i]; see bsx.h
+// The five multi-geometry steps (bsx.h): each builds its request for geoms_call.  ids (host): position i is stream ids[i], whose class decides the geometry of items[i]
 int bsx_step_batch_geoms(bsx_ctx* c, const int* ids, const bsx_geom_item* items, int n, void* stream, unsigned flags) {
-  const char* fn = "bsx_step_batch_geoms";
-  if (!c) return BSX_EINVAL;
-  if (const int rc = ids_check(c, fn, ids, n)) return rc;
-  if (n == 0) return refuse_pending(c, fn);
-  if (const int rc = geoms_check(c, fn, ids, items, n, flags)) return rc;
-  DeviceGuard guard(c->device);
-  hipStream_t s = pick(c, stream);
-  if (const int rc = geoms_device_state(c)) return rc;
-  int entry = 0;
-  if (const int rc = ring_acquire(c, &entry)) return rc;
-  return ids_release(c, entry, s, geoms_run(c, ids, items, n, s, flags, entry));
+  GeomsRequest q{};
+  q.kind = GeomsKind::Geoms; q.ids = ids; q.n = n; q.items = items; q.flags = flags;
+  return geoms_call(c, q, stream);
 }
-
-// bsx_step_batch_geoms with every d_out at (out_w, out_h); see bsx.h
+// ... with every d_out at (out_w, out_h)
 int bsx_step_batch_vcam_geoms(bsx_ctx* c, const int* ids, const bsx_geom_item* items, int n, int out_w, int out_h, void* stream, unsigned flags) {
-  const char* fn = "bsx_step_batch_vcam_geoms";
-  if (!c) return BSX_EINVAL;
-  if (const int rc = ids_check(c, fn, ids, n)) return rc;
-  if (n == 0) return refuse_pending(c, fn);
-  if (const int rc = vcam_geoms_check(c, fn, ids, items, n, out_w, out_h, flags)) return rc;
-  DeviceGuard guard(c->device);
-  hipStream_t s = pick(c, stream);
-  if (const int rc = geoms_device_state(c)) return rc;
-  int entry = 0;
-  if (const int rc = ring_acquire(c, &entry)) return rc;
-  return ids_release(c, entry, s, vcam_geoms_run(c, ids, items, n, out_w, out_h, s, flags, entry));
+  GeomsRequest q{};
+  q.kind = GeomsKind::VcamGeoms; q.ids = ids; q.n = n; q.items = items; q.out_w = out_w; q.out_h = out_h; q.flags = flags;
+  return geoms_call(c, q, stream);
 }
-
-// bsx_step_batch_vcam_geoms with several outputs per position, each of its own size; see bsx.h
+// ... with several outputs per position, each of its own size
 int bsx_step_batch_vcam_geoms_outs(bsx_ctx* c, const int* ids, const bsx_geom_item* items, int n, const bsx_vcam_out* outs, int m, void* stream, unsigned flags) {
-  const char* fn = "bsx_step_batch_vcam_geoms_outs";
-  if (!c) return BSX_EINVAL;
-  if (const int rc = ids_check(c, fn, ids, n)) return rc;
-  if (n == 0) return refuse_pending(c, fn);
-  VcamOutsPlan plan;
-  if (const int rc = vcam_outs_check(c, fn, ids, items, n, outs, m, flags, &plan)) return rc;
-  DeviceGuard guard(c->device);
-  hipStream_t s = pick(c, stream);
-  if (const int rc = geoms_device_state(c)) return rc;
-  int entry = 0;
-  if (const int rc = ring_acquire(c, &entry)) return rc;
-  return ids_release(c, entry, s, vcam_outs_run(c, fn, ids, items, n, outs, nullptr, plan, s, flags, entry));
+  GeomsRequest q{};
+  q.kind = GeomsKind::VcamOuts; q.ids = ids; q.n = n; q.items = items; q.outs = outs; q.m = m; q.flags = flags;
+  return geoms_call(c, q, stream);
 }
-
-// bsx_step_batch_vcam_geoms_outs with every record an NV12 surface; see bsx.h
+// ... with every record an NV12 surface
 int bsx_step_batch_vcam_geoms_outs_nv12(bsx_ctx* c, const int* ids, const bsx_geom_item* items, int n, const bsx_vcam_out_nv12* outs, int m, void* stream, unsigned flags) {
-  const char* fn = "bsx_step_batch_vcam_geoms_outs_nv12";
-  if (!c) return BSX_EINVAL;
-  if (const int rc = ids_check(c, fn, ids, n)) return rc;
-  if (n == 0) return refuse_pending(c, fn);
-  VcamOutsPlan plan;
-  if (const int rc = vcam_nv12_check(c, fn, ids, items, n, outs, m, flags, &plan)) return rc;
-  DeviceGuard guard(c->device);
-  hipStream_t s = pick(c, stream);
-  if (const int rc = geoms_device_state(c)) return rc;
-  int entry = 0;
-  if (const int rc = ring_acquire(c, &entry)) return rc;
-  return ids_release(c, entry, s, vcam_outs_run(c, fn, ids, items, n, nullptr, outs, plan, s, 0, entry));
+  GeomsRequest q{};
+  q.kind = GeomsKind::VcamOutsNv12; q.ids = ids; q.n = n; q.items = items; q.outs_nv12 = outs; q.m = m; q.flags = flags;
+  return geoms_call(c, q, stream);
 }
-
-// bsx_step_batch_vcam_geoms_outs_nv12 with every frame an NV12 surface; see bsx.h
+// ... with every frame an NV12 surface too
 int bsx_step_batch_surfaces(bsx_ctx* c, const int* ids, const bsx_surface_item* items, int n, const bsx_vcam_out_nv12* outs, int m, void* stream, unsigned flags) {
-  const char* fn = "bsx_step_batch_surfaces";
-  if (!c) return BSX_EINVAL;
-  if (const int rc = ids_check(c, fn, ids, n)) return rc;
-  if (n == 0) return refuse_pending(c, fn);
-  VcamOutsPlan plan;
-  if (const int rc = vcam_surfaces_check(c, fn, ids, items, n, outs, m, flags, &plan)) return rc;
-  DeviceGuard guard(c->device);
-  hipStream_t s = pick(c, stream);
-  if (const int rc = geoms_device_state(c)) return rc;
-  int entry = 0;
-  if (const int rc = ring_acquire(c, &entry)) return rc;
-  return ids_release(c, entry, s, vcam_outs_run(c, fn, ids, c->sf_items.data(), n, nullptr, outs, plan, s, 0, entry, items));
+  GeomsRequest q{};
+  q.kind = GeomsKind::Surfaces; q.ids = ids; q.n = n; q.surfaces = items; q.outs_nv12 = outs; q.m = m; q.flags = flags;
+  return geoms_call(c, q, stream);
 }
 
 int bsx_reset_streams(bsx_ctx* c, const int* ids, int n, void* stream) {

@@ -230,30 +230,28 @@ hipError_t launch_vcam_geoms_fmt(const GeomClass* classes, const VgClass* vg, co
 constexpr int kMaxOutGroups = 32;
 struct alignas(16) VgOutGroup { VgClass c; int ntx, opt, pad[2]; };
 struct OutSpans { int wg[kMaxOutGroups + 1]; int rec[kMaxOutGroups]; int per[kMaxOutGroups]; int ng; };
-hipError_t launch_vcam_geoms_outs(const GeomClass* classes, const VgOutGroup* groups, const GeomDesc* odesc, const OutSpans& outs, const GeomDesc* desc,
-                                  const GeomSpans& tiles, unsigned xcd_mask, const uint8_t* ofinal, int outW, int outH, uint8_t* tile_class, int n, hipStream_t s, bool fmt);
+// ONE launcher for the three forms of the call: nrec NULL — the records are BGR / YUYV; nrec — NV12 records (below); srec with nrec — NV12 frames too (further below).
+struct VgNv12Rec;
+struct VgSurfRec;
+hipError_t launch_vcam_geoms_outs(const GeomClass* classes, const VgOutGroup* groups, const GeomDesc* odesc, const VgNv12Rec* nrec, const VgSurfRec* srec,
+                                  const OutSpans& outs, const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const uint8_t* ofinal, int outW, int outH,
+                                  uint8_t* tile_class, int n, hipStream_t s, bool fmt);
 // bsx_step_batch_vcam_geoms_outs_nv12: launch_vcam_geoms_outs with every record written as NV12 — a Y plane (odesc's `out`) and an interleaved UV plane of half the
 // rows, each with a row pitch in bytes (multiples of 4, >= out_w; out_w and out_h even; both planes 4-byte aligned).  nrec: one VgNv12Rec per output record, in group
 // order like odesc, a DEVICE array staged with it: the kernel reads record r's planes and pitches with the workgroup-uniform index it reads odesc[r] with.  The
 // groups' option bits are not read.  The same three launches; the resize pass is vg_outs_nv12_k (vg_outs_nv12_fmt_k with fmt).
 struct alignas(16) VgNv12Rec { uint8_t* uv; int pitch_y, pitch_uv; };
-hipError_t launch_vcam_geoms_outs_nv12(const GeomClass* classes, const VgOutGroup* groups, const GeomDesc* odesc, const VgNv12Rec* nrec, const OutSpans& outs,
-                                       const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const uint8_t* ofinal, int outW, int outH, uint8_t* tile_class,
-                                       int n, hipStream_t s, bool fmt);
-// bsx_step_batch_surfaces: launch_prep_geoms and launch_vcam_geoms_outs_nv12 for positions whose frames are all NV12 SURFACES — desc[i].frame is position i's Y
+// bsx_step_batch_surfaces: launch_prep_geoms and launch_vcam_geoms_outs with NV12 records for positions whose frames are all NV12 SURFACES — desc[i].frame is position i's Y
 // plane ([H] rows of pitch_y bytes), srec[i] its interleaved UV plane ([H / 2] rows of pitch_uv bytes) and the two pitches (multiples of 4, >= W; both planes 4-byte
 // aligned; W and H even).  srec: a DEVICE array staged behind the call's descriptors, read with one 16-byte uniform load; an OUTPUT record's descriptor names its
 // position (the index into srec) in pad[0].  Pixel (x, y) of the frame is Y[y][x] with the chroma pair UV[y >> 1][x & ~1 ..], converted with cv::COLOR_YUV2BGR_YUYV's
 // integers: the BGR frame is launch_yuyv_to_bgr of the 4:2:2 image whose row y repeats chroma row y >> 1.  No load touches a byte at or past W of a row.  Every class
 // of the call must satisfy prep_nv12_fusable (the proper INTER_LINEAR down-scale table, W and H even, W >= 4); the prep kernel is prep_geoms_nv12_k, the resize pass
-// vg_outs_nv12in_k, tile_class_geoms_k and mask_geoms_k are launch_vcam_geoms_outs_nv12's.
+// vg_outs_nv12in_k, tile_class_geoms_k and mask_geoms_k are those of every other form.
 struct alignas(16) VgSurfRec { const uint8_t* uv; int pitch_y, pitch_uv; };
 bool prep_nv12_fusable(int W, int H, const ResizeTab& tab);
 hipError_t launch_prep_geoms_nv12(const GeomClass* classes, const GeomDesc* desc, const VgSurfRec* srec, const GeomSpans& spans, float* input, uint32_t* input_u8, int inW,
                                   int inH, BilateralParams bp, int n, hipStream_t s);
-hipError_t launch_vcam_geoms_outs_nv12in(const GeomClass* classes, const VgOutGroup* groups, const GeomDesc* odesc, const VgNv12Rec* nrec, const VgSurfRec* srec,
-                                         const OutSpans& outs, const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const uint8_t* ofinal, int outW, int outH,
-                                         uint8_t* tile_class, int n, hipStream_t s);
 // ---- classes off the 4-pixel grid (bsx_new_geoms_ex with BSX_GEOMS_EDGE_ROI): W % 4 == 0, roi.x and roi.w free ----------------------------------------------------
 // The composite moves in 4-pixel groups of three aligned dwords, so the groups are anchored to the FRAME: with s = roi.x & 3 (geom_edge_shift) tile column tbx of a
 // class starts at ROI-relative column 128 tbx - s, and a class has ceil((s + roi.w) / 128) tile columns (geom_tile_cols: GeomClass::ntx, the spans and the tile-class

@@ -1902,13 +1902,19 @@ __global__ __launch_bounds__(kThreads) void vg_geoms_k(const VgClass* __restrict
 }
 }  // namespace
 
+// the front of every vcam geoms back end: [one tile-class launch,] ONE masks-only tile launch over the call's positions (reads no frame)
+static void launch_vcam_masks(const GeomClass* classes, const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const uint8_t* ofinal, int outW, int outH,
+                              uint8_t* tile_class, int n, hipStream_t s) {
+  if (tile_class) tile_class_geoms_k<<<dim3((unsigned)n), kThreads, 0, s>>>(classes, desc, tiles, ofinal, outW, outH, tile_class);
+  mask_geoms_k<><<<dim3((unsigned)tiles.wg[kMaxGeoms]), kThreads, 0, s>>>(classes, desc, tiles, xcd_mask, ofinal, outW, outH, tile_class);
+}
+
 hipError_t launch_vcam_geoms(const GeomClass* classes, const VgClass* vg, const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const uint8_t* ofinal, int outW,
                              int outH, uint8_t* tile_class, int out_w, int out_h, int n, hipStream_t s, unsigned flags) {
   if (n <= 0 || tiles.wg[kMaxGeoms] <= 0 || out_w <= 0 || out_h <= 0 || (flags & ~1u) || ((flags & 1) && (out_w & 1))) return hipErrorInvalidValue;
   const int ntx = (out_w + kVW - 1) / kVW, nty = (out_h + kVH - 1) / kVH;
   if ((unsigned long long)ntx * nty * (unsigned long long)n >= (1ull << 31)) return hipErrorInvalidValue;
-  if (tile_class) tile_class_geoms_k<<<dim3((unsigned)n), kThreads, 0, s>>>(classes, desc, tiles, ofinal, outW, outH, tile_class);
-  mask_geoms_k<><<<dim3((unsigned)tiles.wg[kMaxGeoms]), kThreads, 0, s>>>(classes, desc, tiles, xcd_mask, ofinal, outW, outH, tile_class);
+  launch_vcam_masks(classes, desc, tiles, xcd_mask, ofinal, outW, outH, tile_class, n, s);
   const bool owords = (flags & 1) || out_w % 4 == 0;                   // (every d_out is 4-byte aligned: checked by the caller)
   const int opt = (int)(flags & 1u) | (owords ? kVcOutWords : 0);
   vg_geoms_k<><<<dim3((unsigned)(ntx * nty) * (unsigned)n), kThreads, 0, s>>>(vg, desc, tiles, ntx * nty, ntx, opt);
@@ -2098,8 +2104,7 @@ hipError_t launch_vcam_geoms_fmt(const GeomClass* classes, const VgClass* vg, co
   if (n <= 0 || tiles.wg[kMaxGeoms] <= 0 || out_w <= 0 || out_h <= 0 || (flags & ~1u) || ((flags & 1) && (out_w & 1))) return hipErrorInvalidValue;
   const int ntx = (out_w + kVW - 1) / kVW, nty = (out_h + kVH - 1) / kVH;
   if ((unsigned long long)ntx * nty * (unsigned long long)n >= (1ull << 31)) return hipErrorInvalidValue;
-  if (tile_class) tile_class_geoms_k<<<dim3((unsigned)n), kThreads, 0, s>>>(classes, desc, tiles, ofinal, outW, outH, tile_class);
-  mask_geoms_k<><<<dim3((unsigned)tiles.wg[kMaxGeoms]), kThreads, 0, s>>>(classes, desc, tiles, xcd_mask, ofinal, outW, outH, tile_class);      // (reads no frame)
+  launch_vcam_masks(classes, desc, tiles, xcd_mask, ofinal, outW, outH, tile_class, n, s);
   const bool owords = (flags & 1) || out_w % 4 == 0;                   // (every d_out is 4-byte aligned: checked by the caller)
   const int opt = (int)(flags & 1u) | (owords ? kVcOutWords : 0);
   vg_geoms_fmt_k<><<<dim3((unsigned)(ntx * nty) * (unsigned)n), kThreads, 0, s>>>(vg, desc, tiles, ntx * nty, ntx, opt);
@@ -2621,18 +2626,8 @@ static bool out_spans_ok(const OutSpans& outs, const VgOutGroup* groups, const G
   return true;
 }
 
-hipError_t launch_vcam_geoms_outs(const GeomClass* classes, const VgOutGroup* groups, const GeomDesc* odesc, const OutSpans& outs, const GeomDesc* desc,
-                                  const GeomSpans& tiles, unsigned xcd_mask, const uint8_t* ofinal, int outW, int outH, uint8_t* tile_class, int n, hipStream_t s, bool fmt) {
-  const int total = outs.wg[kMaxOutGroups];
-  if (!out_spans_ok(outs, groups, odesc, tiles, n)) return hipErrorInvalidValue;
-  if (tile_class) tile_class_geoms_k<<<dim3((unsigned)n), kThreads, 0, s>>>(classes, desc, tiles, ofinal, outW, outH, tile_class);
-  mask_geoms_k<><<<dim3((unsigned)tiles.wg[kMaxGeoms]), kThreads, 0, s>>>(classes, desc, tiles, xcd_mask, ofinal, outW, outH, tile_class);      // (reads no frame)
-  if (total > 0) {
-    if (fmt) vg_outs_fmt_k<><<<dim3((unsigned)total), kThreads, 0, s>>>(groups, odesc, outs);
-    else vg_outs_k<><<<dim3((unsigned)total), kThreads, 0, s>>>(groups, odesc, outs);
-  }
-  return hipGetLastError();
-}
+// the resize pass of BGR / YUYV records by `fmt` (named here, in the order fmt, plain: the order of a kernel's first use is its place in the device code)
+static void (*const kVgOuts[2])(const VgOutGroup*, const GeomDesc*, OutSpans) = {vg_outs_fmt_k<>, vg_outs_k<>};
 
 // ---- bsx_step_batch_vcam_geoms_outs_nv12: the same resize pass, every record written as NV12 into two pitched planes (kernels.hpp: VgNv12Rec) ----------------------
 // vg_outs_k / vg_outs_fmt_k with vcam_tile.inc's NV12 form (BSX_VT_NV12: a lane's two groups are a row pair; Y and 2 x 2-subsampled chroma stored from the registers
@@ -2774,19 +2769,8 @@ __global__ __launch_bounds__(kThreads) void bgr_to_nv12_k(const uint8_t* __restr
 }
 }  // namespace
 
-hipError_t launch_vcam_geoms_outs_nv12(const GeomClass* classes, const VgOutGroup* groups, const GeomDesc* odesc, const VgNv12Rec* nrec, const OutSpans& outs,
-                                       const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const uint8_t* ofinal, int outW, int outH, uint8_t* tile_class,
-                                       int n, hipStream_t s, bool fmt) {
-  const int total = outs.wg[kMaxOutGroups];
-  if (!out_spans_ok(outs, groups, odesc, tiles, n) || (total > 0 && !nrec)) return hipErrorInvalidValue;
-  if (tile_class) tile_class_geoms_k<<<dim3((unsigned)n), kThreads, 0, s>>>(classes, desc, tiles, ofinal, outW, outH, tile_class);
-  mask_geoms_k<><<<dim3((unsigned)tiles.wg[kMaxGeoms]), kThreads, 0, s>>>(classes, desc, tiles, xcd_mask, ofinal, outW, outH, tile_class);      // (reads no frame)
-  if (total > 0) {
-    if (fmt) vg_outs_nv12_fmt_k<><<<dim3((unsigned)total), kThreads, 0, s>>>(groups, odesc, nrec, outs);
-    else vg_outs_nv12_k<><<<dim3((unsigned)total), kThreads, 0, s>>>(groups, odesc, nrec, outs);
-  }
-  return hipGetLastError();
-}
+// ... of NV12 records, likewise
+static void (*const kVgOutsNv12[2])(const VgOutGroup*, const GeomDesc*, const VgNv12Rec*, OutSpans) = {vg_outs_nv12_fmt_k<>, vg_outs_nv12_k<>};
 
 hipError_t launch_bgr_to_nv12(const uint8_t* bgr, int w, int h, int n, uint8_t* y, int pitch_y, uint8_t* uv, int pitch_uv, hipStream_t s) {
   if (w <= 0 || h <= 0 || n <= 0 || ((w | h) & 1) || pitch_y < w || pitch_uv < w || ((pitch_y | pitch_uv) & 3) || (((uintptr_t)y | (uintptr_t)uv) & 3))
@@ -2975,14 +2959,19 @@ hipError_t launch_prep_geoms_nv12(const GeomClass* classes, const GeomDesc* desc
   return hipGetLastError();
 }
 
-hipError_t launch_vcam_geoms_outs_nv12in(const GeomClass* classes, const VgOutGroup* groups, const GeomDesc* odesc, const VgNv12Rec* nrec, const VgSurfRec* srec,
-                                         const OutSpans& outs, const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const uint8_t* ofinal, int outW, int outH,
-                                         uint8_t* tile_class, int n, hipStream_t s) {
+// the resize pass by the form of the records and of the frames: nrec NULL — BGR / YUYV records (vg_outs_k); nrec — NV12 records (vg_outs_nv12_k); srec with nrec — the
+// frames are NV12 surfaces too (vg_outs_nv12in_k, which has no fmt form: no position is YUYV).  fmt: some position's frame is YUYV (the *_fmt_k kernels)
+hipError_t launch_vcam_geoms_outs(const GeomClass* classes, const VgOutGroup* groups, const GeomDesc* odesc, const VgNv12Rec* nrec, const VgSurfRec* srec,
+                                  const OutSpans& outs, const GeomDesc* desc, const GeomSpans& tiles, unsigned xcd_mask, const uint8_t* ofinal, int outW, int outH,
+                                  uint8_t* tile_class, int n, hipStream_t s, bool fmt) {
   const int total = outs.wg[kMaxOutGroups];
-  if (!out_spans_ok(outs, groups, odesc, tiles, n) || (total > 0 && (!nrec || !srec))) return hipErrorInvalidValue;
-  if (tile_class) tile_class_geoms_k<<<dim3((unsigned)n), kThreads, 0, s>>>(classes, desc, tiles, ofinal, outW, outH, tile_class);
-  mask_geoms_k<><<<dim3((unsigned)tiles.wg[kMaxGeoms]), kThreads, 0, s>>>(classes, desc, tiles, xcd_mask, ofinal, outW, outH, tile_class);      // (reads no frame)
-  if (total > 0) vg_outs_nv12in_k<><<<dim3((unsigned)total), kThreads, 0, s>>>(groups, odesc, nrec, srec, outs);
+  if (!out_spans_ok(outs, groups, odesc, tiles, n) || (srec && (fmt || (total > 0 && !nrec)))) return hipErrorInvalidValue;
+  launch_vcam_masks(classes, desc, tiles, xcd_mask, ofinal, outW, outH, tile_class, n, s);
+  if (total <= 0) return hipGetLastError();
+  const dim3 grid((unsigned)total);
+  if (srec) vg_outs_nv12in_k<><<<grid, kThreads, 0, s>>>(groups, odesc, nrec, srec, outs);
+  else if (nrec) kVgOutsNv12[fmt ? 0 : 1]<<<grid, kThreads, 0, s>>>(groups, odesc, nrec, outs);
+  else kVgOuts[fmt ? 0 : 1]<<<grid, kThreads, 0, s>>>(groups, odesc, outs);
   return hipGetLastError();
 }
 
