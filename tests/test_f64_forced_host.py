@@ -18,6 +18,7 @@ import os
 import numpy as np
 import pytest
 
+import deeplab_size_cases as D
 from conftest import reference_model_path, synthetic_model_path
 from model_size_cases import BY_NAME, CASES as SIZE_CASES, model_file
 
@@ -27,7 +28,9 @@ import f64_graph as G  # noqa: E402
 
 W, H = 640, 480
 SHIPPED = ["lite", "full", "mlkit", "lite-synthetic", "full-synthetic", "mlkit-synthetic", "deeplab-synthetic"]
-MODELS = SHIPPED + [c.name for c in SIZE_CASES]      # the Meet / MLKit graphs at other input sizes (tests/model_size_cases.py): the bar must be fair there too
+# the Meet / MLKit graphs at other input sizes (tests/model_size_cases.py) and the three smallest DeepLab graphs (tests/deeplab_size_cases.py: 33x33 and 9x9 have
+# dilations that reach past their maps, 65x97 is not square): the bar must be fair there too
+MODELS = SHIPPED + [c.name for c in SIZE_CASES] + D.HOST_PROOF
 INPUTS = ["synthetic", "noise", "black", "white", "dot"]
 _SIZED = {}
 
@@ -40,6 +43,8 @@ def _sized_models(tmp_path_factory):
 def _path(model):
     if model in BY_NAME:
         return model_file(BY_NAME[model], _SIZED["dir"])
+    if model in D.BY_NAME:
+        return D.model_file(D.BY_NAME[model], _SIZED["dir"])
     key, _, syn = model.partition("-")
     return synthetic_model_path(key) if syn else reference_model_path(key)
 
@@ -192,7 +197,7 @@ def _edge_fault(a, what):
     return b
 
 
-@pytest.mark.parametrize("model", ["lite", "mlkit", "deeplab-synthetic", "lite-16x16", "lite-104x168"])
+@pytest.mark.parametrize("model", ["lite", "mlkit", "deeplab-synthetic", "lite-16x16", "lite-104x168", "deeplab-65x97"])
 def test_a_border_row_column_or_corner_taken_from_its_neighbour_fails(model):
     """Edges: what a kernel gets wrong at a SAME-padding edge or a tile edge.  On a noise network input (uniform f32 over the normalised range), in the stem's
     output, in the first stride-2 depthwise output, in the largest tensor of the decoder and in the network output: the last and first row, the last and first

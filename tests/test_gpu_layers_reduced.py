@@ -16,6 +16,10 @@ The segmented paths also store two tensors the file does not have — the 1x1 co
 they are read back and audited as well (f64_graph.moved_convs), against the convolution of the resize's input; without them their rounding shows up as an error of the
 gate and of the network output that nothing explains.
 
+The f16-operand modes also run on three DeepLab graphs of other sizes (tests/deeplab_size_cases.py): 129x129 at 8 streams (8712 rows at its 1/4 level, 2312 at
+its 1/8 level: operand_rounding_rule has to name the fused expands and the GEMMs of one level only), 353x481 at 4 (every level of 8192 rows and more, the stem
+unfused: its K = 16 GEMM too) and the wide graph at 10 (the expands from Cin = 160 run as plain GEMMs, the chain does not exist).
+
 The accumulated error at the network output is printed and recorded, not asserted: these modes are not parity-grade; their gates (tests/test_gpu_parity.py) stay in force."""
 import json
 import os
@@ -25,6 +29,7 @@ import time
 import numpy as np
 import pytest
 
+import deeplab_size_cases as D
 from conftest import reference_model_path, synthetic_model_path
 from test_gpu_layers import H, KNOBS, W, half_by_plan, stored_by_plan
 
@@ -37,23 +42,32 @@ import f64_graph as G  # noqa: E402
 SEGMENTED = [("lite", True), ("full", True), ("mlkit", True), ("lite", False), ("full", False), ("mlkit", False)]
 # (architecture, real weights, environment, streams of the context, streams stepped)
 CASES = ([(a, r, {"BSX_ACT16": "1"}, 8, 5) for a, r in SEGMENTED] + [(a, r, {"BSX_ACT16": "1", "BSX_F32_INPUT": "1"}, 8, 5) for a, r in SEGMENTED] +
-         [("deeplab", False, {"BSX_F16_GEMM": mode}, ns, n) for mode in ("fast", "fast16") for ns, n in ((8, 5), (9, 9))])
+         [("deeplab", False, {"BSX_F16_GEMM": mode}, ns, n) for mode in ("fast", "fast16") for ns, n in ((8, 5), (9, 9))] +
+         [(name, False, {"BSX_F16_GEMM": mode}, ns, n) for name, ns, n in (("deeplab-129x129", 8, 8), ("deeplab-353x481", 8, 4), ("deeplab-wide-193x257", 10, 10))
+          for mode in ("fast", "fast16")])
+
+
+def _mode_id(c):
+    _, _, env, ns, n = c
+    return "%s-%dof%d" % ("-".join(re.sub(r"^bsx_", "", k.lower()) + ("" if v == "1" else "_" + v) for k, v in sorted(env.items())), n, ns)
 
 
 def _case_id(c):
-    arch, real, env, ns, n = c
-    return "%s-%s-%s-%dof%d" % (arch, "real" if real else "synthetic", "-".join(re.sub(r"^bsx_", "", k.lower()) + ("" if v == "1" else "_" + v) for k, v in sorted(env.items())), n, ns)
+    return "%s-%s-%s" % (c[0], "real" if c[1] else "synthetic", _mode_id(c))
 
 
 @pytest.mark.parametrize("case", CASES, ids=_case_id)
-def test_every_stored_tensor_of_a_reduced_precision_mode_against_float64(case, oracle, monkeypatch, debug_switches):
+def test_every_stored_tensor_of_a_reduced_precision_mode_against_float64(case, oracle, monkeypatch, debug_switches, tmp_path):
     from backscrub_amd import tflite_io
     bs = debug_switches
     if not torch.cuda.is_available():
         pytest.fail("GPU tests need a visible MI355X (torch.cuda.is_available() is False)")
     t_start = time.time()
     arch, real, env, n_streams, n_stepped = case
-    path = reference_model_path(arch) if real else synthetic_model_path(arch)
+    if arch in D.BY_NAME:
+        path = D.model_file(D.BY_NAME[arch], tmp_path)
+    else:
+        path = reference_model_path(arch) if real else synthetic_model_path(arch)
     if real and not os.path.exists(path):
         pytest.fail("model fixture %s is missing" % path)
     for k in KNOBS:
@@ -135,7 +149,7 @@ def test_every_stored_tensor_of_a_reduced_precision_mode_against_float64(case, o
             wf = max((r for r in rows if not r["half"]), key=lambda r: r["worst"])
             out = next(r for r in rows if r["t"] == t_out)
             print("%-7s %-9s %-28s stream %d %-9s: %3d tensors audited, %2d stored as halves, %d elements outside, worst |d - v| / (B32 + allowance) of an f32 tensor %5.2f at t%-3d, "
-                  "accumulated error at the output %.3g (scale %.3g)" % (arch, "real" if real else "synthetic", _case_id(case).split("-", 2)[2], i, names[k], len(rows),
+                  "accumulated error at the output %.3g (scale %.3g)" % (arch, "real" if real else "synthetic", _mode_id(case), i, names[k], len(rows),
                                                                         sum(r["half"] for r in rows), outside, wf["worst"], wf["t"], out["acc"], out["scale"]))
             record.append({"stream": i, "input": names[k], "audited": len(rows), "half": sum(r["half"] for r in rows), "outside": outside, "worst_f32": wf["worst"],
                            "worst_f32_tensor": wf["t"], "worst": max(r["worst"] for r in rows), "out_acc": out["acc"], "out_scale": out["scale"]})
@@ -149,7 +163,7 @@ def test_every_stored_tensor_of_a_reduced_precision_mode_against_float64(case, o
         out_path = os.environ.get("BSX_LAYER_AUDIT_OUT")
         if out_path:
             with open(out_path, "a") as f:
-                f.write(json.dumps({"model": arch, "weights": "real" if real else "synthetic", "path": _case_id(case).split("-", 2)[2], "stored": len(expected) + len(synthetic),
+                f.write(json.dumps({"model": arch, "weights": "real" if real else "synthetic", "path": _mode_id(case), "stored": len(expected) + len(synthetic),
                                     "half": len(expected_half | synthetic_half), "rounding_ops": sorted(rounding), "seconds": round(seconds, 1), "streams": record}) + "\n")
         assert not looks_half, "tensors %s are marked f32 by the plan and hold nothing but half-representable values\n%s" % (looks_half, plan)
         assert not problems, "\n".join(problems)

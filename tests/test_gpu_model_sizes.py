@@ -7,15 +7,19 @@
     transpose convolution;
 (b) the four stages and one step per case at two frame sizes, against the oracle: here a 16x16 or 8x8 network output meets the mask up-scaler (40:1, 80:1; the
     shipped models stay below 7:1) and a 97x161 output its linear tables;
-(c) the graph-specialised segment kernels against the ahead-of-time ones, bit for bit, at two of the new geometries."""
+(c) the graph-specialised segment kernels against the ahead-of-time ones, bit for bit, at two of the new geometries;
+(d) the DeepLab graph — the per-launch path of kernels_nn.hip — at twelve other input sizes and once at twice the channel width (tests/deeplab_size_cases.py; "Other model
+    sizes: DeepLab"): (a) on every row of its paths, after the plan of the context has stated the facts of the case's row, and (b), where a 1/8 map that is no 2^k + 1
+    meets the fused align-corners resize + argmax at a scale that is no power of two."""
 import re
 
 import numpy as np
 import pytest
 
+import deeplab_size_cases as D
 from geometry_cases import mask_of_state
 from model_size_cases import BY_NAME, CASES, FORCED, FORCED_KNOBS, model_file
-from test_gpu_layers import KNOBS, _paths, audit_every_stored_tensor
+from test_gpu_layers import KNOBS, NO_FUSION, _paths, audit_every_stored_tensor
 from test_gpu_parity import _dev, bs  # noqa: F401 (bs: the library fixture)
 
 pytestmark = pytest.mark.gpu
@@ -26,7 +30,7 @@ torch = pytest.importorskip("torch")
 @pytest.fixture(scope="module")
 def models(tmp_path_factory):
     d = tmp_path_factory.mktemp("sized_models")
-    return {c.name: model_file(c, d) for c in CASES}
+    return {**{c.name: model_file(c, d) for c in CASES}, **{c.name: D.model_file(c, d) for c in D.CASES}}
 
 
 def _slug(s):
@@ -73,7 +77,7 @@ SIZES = [(640, 480), (322, 242)]
 
 
 @pytest.mark.parametrize("res", SIZES, ids=["%dx%d" % r for r in SIZES])
-@pytest.mark.parametrize("name", [c.name for c in CASES])
+@pytest.mark.parametrize("name", [c.name for c in CASES] + [c.name for c in D.CASES])
 def test_stages_and_one_step_match_the_oracle(bs, oracle, models, name, res):
     """test_stages_match_oracle's body (prep byte-equal, logits within 1e-4 relative, decode + IIR from a random state byte-equal on the oracle's logits, mask
     byte-equal), then one step from that state whose mask and composite are the oracle's up-scale, blur and blend of the temporal state the device itself holds
@@ -82,7 +86,7 @@ def test_stages_and_one_step_match_the_oracle(bs, oracle, models, name, res):
     path = models[name]
     W, H = res
     n = 3
-    if BY_NAME[name].refused:
+    if name in BY_NAME and BY_NAME[name].refused:
         _refused(bs, path, BY_NAME[name], W, H, n)
         return
     mg = bs.MaskGen(path, W, H, n_streams=n)
@@ -136,6 +140,46 @@ def test_stages_and_one_step_match_the_oracle(bs, oracle, models, name, res):
         for c in oc:
             c.close()
         mg.close()
+
+
+# ---- (d) ------------------------------------------------------------------------------------------------------------------------
+def _deeplab_rows(c):
+    """The rows of _paths("deeplab") the case runs.  Without the rewrites every DeepLab step list has a micro-op form, and bsx_new runs it as a frame program where most
+    of its tensors fit the LDS (the 9x9, 17x17, 33x33 and 65x97 graphs): "no graph rewrites" audits whichever of the two bsx_new chooses, and "nothing fused" switches
+    the program off, as it does on the Meet graphs.  9x9 has a micro-op form WITH the rewrites too and runs it on every row: one more row runs the per-launch
+    kernels on its rewritten step list."""
+    rows = [(pname, dict(env, BSX_NO_FRAME_PROGRAM="1") if pname == NO_FUSION else env) for i, (pname, env) in enumerate(_paths(D.FAMILY)) if c.rows is None or i in c.rows]
+    return rows + ([("one launch per step", {"BSX_NO_FRAME_PROGRAM": "1"})] if c.micro_ops else [])
+
+
+DEEPLAB_AUDIT = [(c.name, pname, env) for c in D.CASES for pname, env in _deeplab_rows(c)]
+
+
+@pytest.mark.parametrize("name,pname,env", DEEPLAB_AUDIT, ids=["%s-%s" % (n, _slug(p)) for n, p, _ in DEEPLAB_AUDIT])
+def test_every_stored_tensor_of_a_sized_deeplab_against_float64(name, pname, env, models, oracle, monkeypatch, debug_switches):
+    case = D.BY_NAME[name]
+
+    def about_plan(plan):
+        """the context's own plan still has the geometry the case is in the table for — on the rows that leave the fusions on"""
+        got = D.plan_facts(plan)
+        fp = re.search(r"^frame program: (ON|off), (\d+) micro-ops, .* (\d+) tensors in LDS, (\d+) in HBM$", plan, re.M)
+        assert fp, "no 'frame program:' line of the expected form in the plan\n" + plan
+        program, micro_ops = fp.group(1) == "ON", int(fp.group(2))
+        # bsx_new's rule: a plan that has a program runs it when at least as many of its tensors are in LDS as in HBM
+        assert program == (micro_ops > 0 and int(fp.group(3)) >= int(fp.group(4)) and "BSX_NO_FRAME_PROGRAM" not in env), fp.group(0)
+        if "BSX_NO_REWRITES" not in env:
+            assert micro_ops == case.micro_ops, "%s on %r: %s\n%s" % (name, pname, fp.group(0), plan)
+        if micro_ops:                                                                 # (a plan that has a program, used or not, fuses nothing: plan.cpp)
+            assert not got["head_fused"] and not got["pairs"] and not got["chain"], plan
+            return
+        assert got["chain"] == case.chain, plan
+        if "BSX_NO_IR_FUSE" not in env:                                               # (it switches the fused head off as well)
+            assert got["pairs"] == D.pairs_of(case) and got["unfused"] == case.unfused, (got, plan)
+            if "BSX_NO_HEAD0" not in env:
+                assert got["head_fused"] == case.head_fused, plan
+
+    audit_every_stored_tensor(debug_switches, oracle, monkeypatch, models[name], D.FAMILY, pname, env, model=name, about_plan=about_plan,
+                              n_streams=case.streams, n_stepped=case.stepped)
 
 
 # ---- (c) ------------------------------------------------------------------------------------------------------------------------

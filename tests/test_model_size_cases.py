@@ -9,6 +9,7 @@ import subprocess
 
 import pytest
 
+import deeplab_size_cases as D
 from conftest import ROOT
 from model_size_cases import CASES, FORCED, FORCED_KNOBS, SEGMENTED, STEM_PAD, BY_NAME, model_file
 from test_k3_frame_codegen import FRAME_LINE, HIPCC, LDS_CU, TILES_LINE
@@ -26,7 +27,7 @@ def api():
 @pytest.fixture(scope="module")
 def models(tmp_path_factory):
     d = tmp_path_factory.mktemp("sized_models")
-    return {c.name: model_file(c, d) for c in CASES}
+    return {**{c.name: model_file(c, d) for c in CASES}, **{c.name: D.model_file(c, d) for c in D.CASES}}
 
 
 def plan_facts(d):
@@ -125,6 +126,104 @@ def test_the_forced_tile_variants_plan_in_the_debug_library_only(api, models, na
         assert got["tiles"] == case.tiles and got["k3"][0] == "tiles" and got["k3"][1] == "switched off" and got["k3"][2] == case.k3[1], got
     for k in env:
         assert k.encode() not in open(build.LIB, "rb").read() and k.encode() in open(build.LIB_DBG, "rb").read()
+
+
+# ---- the DeepLab graph at other sizes and widths (tests/deeplab_size_cases.py) ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", D.CASES, ids=[c.name for c in D.CASES])
+def test_every_deeplab_case_plans_and_its_plan_states_the_facts_of_its_row(api, models, case):
+    from backscrub_amd import tflite_io as T
+    from tools import make_synthetic_model as S
+    d = api.model_describe(models[case.name])
+    got = D.plan_facts(d)
+    assert (got["steps"], got["micro_ops"]) == (case.steps, case.micro_ops), (got, d)
+    assert got["head_fused"] == case.head_fused and got["chain"] == case.chain, (got, d)
+    assert got["pairs"] == D.pairs_of(case), (got["pairs"], d)
+    assert got["unfused"] == case.unfused and set(got["pairs"]) | set(got["unfused"]) == set(D.EXPANDS), (got, d)
+    assert "segment" not in d and ("specialised middle kernel: none" in d) == (case.micro_ops > 0), d
+    # the graph is the shipped one in everything but its extents and widths: the same 70 operators, every extent by the operators' own rules
+    m, ref = T.load(models[case.name]), T.load(S.ensure("deeplab"))
+    assert [op.name for op in m.ops] == [op.name for op in ref.ops] and len(m.tensors) == len(ref.tensors)
+    assert m.tensors[m.inputs[0]].shape == [1, case.H, case.W, 3] and m.tensors[m.outputs[0]].shape == [1, case.H, case.W, 21]
+    fh, fw = case.H, case.W
+    for _ in range(3):                                                               # three stride-2 SAME levels: the 1/8 map
+        fh, fw = -(-fh // 2), -(-fw // 2)
+    resizes = [op for op in m.ops if op.name == "RESIZE_BILINEAR"]
+    assert [m.tensors[op.outputs[0]].shape[1:3] for op in resizes] == [[fh, fw], [fh, fw], [case.H, case.W]]
+    assert all(op.opts["align_corners"] == 1 and op.opts["half_pixel_centers"] == 0 for op in resizes)
+    stem = m.tensors[m.ops[0].outputs[0]].shape
+    assert stem[3] == 16 * case.width and m.tensors[next(op for op in m.ops if op.name == "CONCATENATION").outputs[0]].shape == [1, fh, fw, 512]
+
+
+def test_the_deeplab_table_reaches_what_it_claims():
+    """the arithmetic behind the rows (a case edited later must not lose it); the kernels' own thresholds are quoted where they are used"""
+    t = D.BY_NAME
+    names = [c.name for c in D.CASES]
+    assert len(names) == 13 == len(set(names)) == len({c.seed for c in D.CASES}) and all("deeplab" in n for n in names)
+    assert not {c.seed for c in D.CASES} & {c.seed for c in CASES}
+
+    def level(c, k):                                                                  # extents of the 1/2^k map
+        h, w = c.H, c.W
+        for _ in range(k):
+            h, w = -(-h // 2), -(-w // 2)
+        return h, w
+
+    def partial(rows, bh, nb):                                                        # nb bands of bh rows cover `rows` with a shorter last band
+        return (nb - 1) * bh < rows < nb * bh
+
+    # 256x256: even extents at every level (pad_t = pad_l = 0 under SAME, stride 2), a scale that is no power of two, the 64 output rows of the first stride-2 depthwise in 16 bands of 4 exactly
+    assert all(x % 2 == 0 for k in range(3) for x in level(t["deeplab-256x256"], k)) and level(t["deeplab-256x256"], 3) == (32, 32) and 16 * 4 == 64
+    # 129x129: 33 depthwise rows in 4 bands of 9; the M of its 1/8 and 1/4 levels at the five stepped streams against launch_step's 4096 and 8192
+    c = t["deeplab-129x129"]
+    assert D.pairs_of(c)[3] == (16, 9, 4) and partial(33, 9, 4) and level(c, 2) == (33, 33) and level(c, 3) == (17, 17)
+    assert c.stepped * 17 * 17 == 1445 <= 4096 < c.stepped * 33 * 33 == 5445 < 8192
+    assert D.pairs_of(t["deeplab-65x97"])[3][0] == 24 and D.pairs_of(t["deeplab-65x97"])[3][2] == 1 and t["deeplab-65x97"].H != t["deeplab-65x97"].W
+    c = t["deeplab-200x312"]
+    assert [level(c, k) for k in range(4)] == [(200, 312), (100, 156), (50, 78), (25, 39)]       # even, even, even, then odd in both axes
+    # 385x289: the 16-channel chunk in one band on every layer from step 12 on, the dilated ones included; 49 rows in 10 bands of 5; 97 in 11 of 9
+    c = t["deeplab-385x289"]
+    assert all(D.pairs_of(c)[s] == (16, 49, 1) for s in range(12, 49, 3)) and level(c, 3) == (49, 37) and partial(49, 5, 10) and partial(97, 9, 11)
+    # 353x481: the stem is 241 wide behind a 481-wide input: > 339, the widest input whose band fits the LDS of dl_head0_k; banded DILATED pairs with a partial
+    # last band (45 rows in 3 of 15 is exact, in 4 of 12 it is not); the 1/8 level has 8192 rows at the streams it steps
+    c = t["deeplab-353x481"]
+    assert c.W > 339 and not c.head_fused and level(c, 3) == (45, 61)
+    assert all(D.pairs_of(c)[s] == (16, 15, 3) for s in range(21, 40, 3)) and all(D.pairs_of(c)[s] == (16, 12, 4) for s in (42, 45, 48)) and partial(45, 12, 4) and 3 * 15 == 45
+    assert c.stepped * 45 * 61 >= 8192 and D.pairs_of(c)[9][1] == 2 and D.pairs_of(c)[3][1] == 2
+    c = t["deeplab-65x513"]
+    assert c.W > 339 and not c.head_fused and c.unfused == (3,) and level(c, 1) == (33, 257)
+    assert t["deeplab-65x337"].head_fused and 337 <= t["deeplab-65x337"].W <= 339 and not t["deeplab-65x329"].head_fused and t["deeplab-65x329"].W < 340
+    # 33x33 and 17x17: from the level with fewer than 64 pixels on nothing is fused; the dilation reaches (d = 4 on 5x5: 4 * d > H) and passes (3x3) the map's size
+    assert level(t["deeplab-33x33"], 3) == (5, 5) and 5 * 5 < 64 and t["deeplab-33x33"].unfused == tuple(range(12, 49, 3)) and 5 < 4 * 2
+    assert level(t["deeplab-17x17"], 3) == (3, 3) and level(t["deeplab-17x17"], 2) == (5, 5) and t["deeplab-17x17"].unfused == tuple(range(6, 49, 3))
+    c = t["deeplab-9x9"]
+    assert level(c, 3) == (2, 2) and c.micro_ops == 58 and c.steps == 59 and not c.pairs and c.unfused == D.EXPANDS
+    assert [x.name for x in D.CASES if x.micro_ops] == ["deeplab-9x9"]
+    # the wide case: 8192 rows at its 1/8 level need ten streams (nine have 7425); the expands from Cin = 160 (K padded to 160 > 96) are not fused
+    c = t["deeplab-wide-193x257"]
+    assert c.width == 2 and level(c, 3) == (25, 33) and c.stepped * 25 * 33 >= 8192 > (c.stepped - 1) * 25 * 33 and c.streams >= c.stepped
+    assert c.unfused == (42, 45, 48) and not c.chain and not c.head_fused
+    assert [x.name for x in D.CASES if x.rows is not None] == ["deeplab-wide-193x257"] and D.ROWS_DIFFERENT == (0, 1, 4)      # the one case that cannot lose streams
+    assert set(D.HOST_PROOF) <= set(names) and all(t[n].H * t[n].W <= 65 * 97 for n in D.HOST_PROOF)
+
+
+@pytest.mark.parametrize("env,keeps", [({"BSX_NO_HEAD0": "1"}, ("pairs", "chain")), ({"BSX_NO_IR_FUSE": "1"}, ("chain",)), ({"BSX_NO_REWRITES": "1"}, ())],
+                         ids=["no_head0", "no_ir_fuse", "no_rewrites"])
+def test_a_switch_of_the_debug_library_removes_its_own_fusions_from_a_deeplab_plan_only(models, env, keeps, monkeypatch, debug_switches):
+    """what tests/test_gpu_model_sizes.py asserts of a context's plan on the rows that switch one fusion off: the other facts of the case's row stay"""
+    for k in ("BSX_NO_HEAD0", "BSX_NO_IR_FUSE", "BSX_NO_REWRITES"):
+        monkeypatch.delenv(k, raising=False)
+    for name in ("deeplab-129x129", "deeplab-353x481", "deeplab-wide-193x257"):
+        case = D.BY_NAME[name]
+        want = {"head_fused": case.head_fused, "pairs": D.pairs_of(case), "chain": case.chain}
+        assert {k: v for k, v in D.plan_facts(debug_switches.model_describe(models[name])).items() if k in want} == want
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        got = D.plan_facts(debug_switches.model_describe(models[name]))
+        for k in env:
+            monkeypatch.delenv(k)
+        assert {k: got[k] for k in keeps} == {k: want[k] for k in keeps}, (name, env, got)
+        # (BSX_NO_IR_FUSE switches the fused head off as well; without the rewrites the step list has a micro-op form, and a plan with a program fuses nothing: plan.cpp)
+        for gone in {"head_fused", "pairs", "chain"} - set(keeps):
+            assert not got[gone], (name, env, gone, got[gone])
 
 
 # sha256 of the four synthetic models of the shipped sizes, as the generator wrote them before it learnt the transpose convolution's cropped output shape

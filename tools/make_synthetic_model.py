@@ -202,14 +202,18 @@ def _meet_family(H, W, mlkit, seed):
     return g.model(x, out, "synthetic %s %dx%d (seed %d)" % ("mlkit-selfie" if mlkit else "meet", H, W, seed))
 
 
-def _deeplab(seed):
+def _deeplab(seed, H=257, W=257, width=1):
+    """deeplabv3_257_mv_gpu's graph with an H x W network input; `width` multiplies the channel counts of the backbone (1: the shipped file's, 2: MobileNetV2's own
+    32, 16, 24, 32, 64, 96, 160, 320).  The ASPP head keeps its 256 channels and the 21 classes.  Every extent follows from H and W by the operators' own rules: the
+    pooled branch and the first final resize go to the size of the 1/8 map, the last resize to H x W."""
     g = G(seed, f16_weights=False)
-    x = g.tensor([1, 257, 257, 3], "input")
-    t = g.conv(x, 16, 3, 2, SAME, RELU6)
-    t = g.conv(g.dw(t, 3, 1, RELU6), 8, gain=1.0)
+    k = width
+    x = g.tensor([1, H, W, 3], "input")
+    t = g.conv(x, 16 * k, 3, 2, SAME, RELU6)
+    t = g.conv(g.dw(t, 3, 1, RELU6), 8 * k, gain=1.0)
 
     def ir(t, cexp, cout, stride=1, dil=1, residual=False):
-        o = g.conv(g.dw(g.conv(t, cexp, act=RELU6), 3, stride, RELU6, dil=dil), cout, gain=1.0)
+        o = g.conv(g.dw(g.conv(t, cexp * k, act=RELU6), 3, stride, RELU6, dil=dil), cout * k, gain=1.0)
         return g.binary("ADD", o, t) if residual else o
 
     t = ir(t, 48, 12, 2)
@@ -227,25 +231,32 @@ def _deeplab(seed):
     t = ir(t, 480, 80, dil=4, residual=True)
     t = ir(t, 480, 80, dil=4, residual=True)
     t = ir(t, 480, 160, dil=4)
-    pool = g.resize(g.conv(g.gap(t), 256, act=RELU), 33, 33, align=1, half=0)
+    fh, fw = g.shape(t)[1:3]                # the 1/8 map: 33x33 at 257x257
+    pool = g.resize(g.conv(g.gap(t), 256, act=RELU), fh, fw, align=1, half=0)
     br = g.conv(t, 256, act=RELU)
     t = g.conv(g.concat([pool, br], axis=3), 256, act=RELU)
     t = g.conv(t, 21, gain=3.0, bias_add={15: 6.0})  # let "person" win somewhere
-    t = g.resize(t, 33, 33, align=1, half=0)
-    out = g.resize(t, 257, 257, align=1, half=0)
-    return g.model(x, out, "synthetic deeplabv3-mnv2 257 (seed %d)" % seed)
+    t = g.resize(t, fh, fw, align=1, half=0)
+    out = g.resize(t, H, W, align=1, half=0)
+    if (H, W, width) == (257, 257, 1):
+        return g.model(x, out, "synthetic deeplabv3-mnv2 257 (seed %d)" % seed)
+    return g.model(x, out, "synthetic deeplabv3-mnv2 %dx%d width %d (seed %d)" % (H, W, width, seed))
 
 
-def build_sized(family: str, H: int, W: int, seed: int) -> T.Model:
-    """A Meet-family ("lite": the graph of segm_lite / segm_full) or MLKit ("mlkit") model with an H x W network input.  Nothing in the graph is tied to the shipped
-    sizes: every extent follows from H and W by the operators' own rules."""
-    if family not in ("lite", "mlkit"):
+def build_sized(family: str, H: int, W: int, seed: int, width: int = 1) -> T.Model:
+    """A Meet-family ("lite": the graph of segm_lite / segm_full), MLKit ("mlkit") or DeepLab ("deeplab") model with an H x W network input.  Nothing in the graphs is
+    tied to the shipped sizes: every extent follows from H and W by the operators' own rules.  width: DeepLab only, the multiplier of the backbone's channel counts."""
+    if family == "deeplab":
+        return _deeplab(seed, H, W, width)
+    if family not in ("lite", "mlkit") or width != 1:
         raise KeyError(family)
     return _meet_family(H, W, family == "mlkit", seed)
 
 
-def sized_file_name(family: str, H: int, W: int) -> str:
-    """a file name with the substring the model-type sniffing looks for ("segm_" / "selfie")"""
+def sized_file_name(family: str, H: int, W: int, width: int = 1) -> str:
+    """a file name with the substring the model-type sniffing looks for ("segm_" / "selfie" / "deeplab")"""
+    if family == "deeplab":
+        return "synthetic_deeplabv3_%dx%d%s.tflite" % (H, W, "" if width == 1 else "_w%d" % width)
     return ("synthetic_selfie_mlkit_%dx%d.f16.tflite" if family == "mlkit" else "synthetic_segm_lite_%dx%d.tflite") % (H, W)
 
 
