@@ -59,6 +59,11 @@ class _BlurItem(C.Structure):               # bsx.h bsx_blur_item
     _fields_ = [("d_src", C.c_void_p), ("d_dst", C.c_void_p), ("w", C.c_int), ("h", C.c_int), ("ksize", C.c_int), ("flags", C.c_uint)]
 
 
+class _BlurSurfaceItem(C.Structure):        # bsx.h bsx_blur_surface_item
+    _fields_ = [("d_y", C.c_void_p), ("d_uv", C.c_void_p), ("d_dst", C.c_void_p), ("pitch_y", C.c_int), ("pitch_uv", C.c_int), ("w", C.c_int), ("h", C.c_int),
+                ("ksize", C.c_int), ("flags", C.c_uint)]
+
+
 class _Geometry(C.Structure):               # bsx.h bsx_geometry
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("n_streams", C.c_int)]
 
@@ -162,6 +167,7 @@ SYMBOLS = [
     ("bsx_live_timings", C.c_int, [C.c_void_p, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     ("bsx_gaussian_blur_bgr", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("bsx_gaussian_blur_bgr_batch", C.c_int, [C.c_void_p, C.POINTER(_BlurItem), C.c_int, C.c_void_p]),
+    ("bsx_gaussian_blur_surfaces_batch", C.c_int, [C.c_void_p, C.POINTER(_BlurSurfaceItem), C.c_int, C.c_void_p]),
     ("bsx_debug_gauss_coeffs", C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("bsx_flip_bgr", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("bsx_debug_buffer", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
@@ -424,15 +430,16 @@ class MaskGen:
         _check(lib().bsx_step_batch_vcam_geoms_outs(self.h, arr, items, n, recs, m, _stream_ptr(), 1 if yuyv else 0), self.h, "bsx_step_batch_vcam_geoms_outs")
         return [t for _i, t in outs]
 
-    def _nv12_planes(self, who, y, uv):
+    def _nv12_planes(self, who, y, uv, device=True):
         """the two views of an NV12 surface, validated: (out_w, out_h, pitch_y, pitch_uv).  y: uint8 [out_h, out_w] with strides (pitch_y, 1); uv: uint8
-        [out_h / 2, out_w] with strides (pitch_uv, 1) — U, V interleaved; sizes even, pitches multiples of 4, both 4-byte aligned."""
+        [out_h / 2, out_w] with strides (pitch_uv, 1) — U, V interleaved; sizes even, pitches multiples of 4, both 4-byte aligned.  device=False: where the tensors
+        live is the caller's to check."""
         torch = _torch()
         for name, t in (("y", y), ("uv", uv)):
             if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 2 or t.numel() == 0:
                 raise BsxError("%s: %s must be a non-empty uint8 tensor of two dimensions (it is %s)" % (who, name, "a %s" % type(t).__name__ if not isinstance(
                     t, torch.Tensor) else "%s %s" % (t.dtype, tuple(t.shape))))
-            if not self._on_device(t):
+            if device and not self._on_device(t):
                 raise BsxError("%s: %s must be on cuda:%d (it is on %s)" % (who, name, self.device, t.device))
         oh, ow = int(y.shape[0]), int(y.shape[1])
         if (ow | oh) & 1:
@@ -896,6 +903,52 @@ class MaskGen:
             items[i].d_src, items[i].d_dst, items[i].w, items[i].h = t.data_ptr(), o.data_ptr(), int(t.shape[1]), int(t.shape[0])
             items[i].ksize, items[i].flags = ks[i], BSX_STREAM_YUYV_IN if t.shape[2] == 2 else 0
         _check(lib().bsx_gaussian_blur_bgr_batch(self.h, items, n, _stream_ptr()), self.h, "bsx_gaussian_blur_bgr_batch")
+        return out
+
+    def gaussian_blur_surfaces(self, surfaces, ksizes, out=None):
+        """gaussian_blur_batch for NV12 decoder surfaces, in one launch (bsx_gaussian_blur_surfaces_batch; the integers of nv12_to_bgr, then gaussian_blur's — no BGR
+        copy of a frame is made).  surfaces: a sequence of (y, uv) as step_surfaces takes them, each of its own size and pitches — y a cuda uint8 view [h, w] with
+        strides (pitch_y, 1), uv [h / 2, w] with strides (pitch_uv, 1); the surfaces need not be adjacent; ksizes: one odd int of 1..31 for all, or one per surface
+        (1 = the conversion alone); out: None (new tensors) or a sequence of contiguous [h_i,w_i,3] tensors.  Returns the list of outputs — what a StreamSetting's
+        bg takes, so a surfaces tick in blur mode is this call followed by step_surfaces."""
+        torch = _torch()
+        surfaces = list(surfaces)
+        n = len(surfaces)
+        if n > self.n_streams:
+            raise BsxError("%d surfaces for a context of %d streams" % (n, self.n_streams))
+        ks = [int(ksizes)] * n if isinstance(ksizes, (int, np.integer)) else [int(k) for k in ksizes]
+        if len(ks) != n:
+            raise BsxError("%d ksizes for %d surfaces" % (len(ks), n))
+        for i, k in enumerate(ks):
+            if k < 1 or k > 31 or not (k & 1):
+                raise BsxError("ksizes[%d] = %d is not an odd number of 1..31" % (i, k))
+        geo = []
+        for i, sf in enumerate(surfaces):
+            if not isinstance(sf, (tuple, list)) or len(sf) != 2:
+                raise BsxError("surfaces[%d] must be a pair (y, uv)" % i)
+            geo.append(self._nv12_planes("surfaces[%d]" % i, sf[0], sf[1], device=False))
+        if out is not None:
+            out = list(out)
+            if len(out) != n:
+                raise BsxError("%d outputs for %d surfaces" % (len(out), n))
+            for i, (o, (w, h, _py, _puv)) in enumerate(zip(out, geo)):
+                if not (isinstance(o, torch.Tensor) and o.dtype == torch.uint8 and tuple(o.shape) == (h, w, 3) and o.is_contiguous()):
+                    raise BsxError("out[%d] must be a contiguous uint8 tensor [%d,%d,3]" % (i, h, w))
+        for i, (y, uv) in enumerate(surfaces):
+            for name, t in (("y", y), ("uv", uv)):
+                if not self._on_device(t):
+                    raise BsxError("surfaces[%d]: %s is on %s, not on the context's cuda:%d" % (i, name, t.device, self.device))
+        for i, t in enumerate(out or []):
+            if not self._on_device(t):
+                raise BsxError("out[%d] is on %s, not on the context's cuda:%d" % (i, t.device, self.device))
+        if out is None:
+            out = [torch.empty((h, w, 3), dtype=torch.uint8, device="cuda:%d" % self.device) for w, h, _py, _puv in geo]
+        items = (_BlurSurfaceItem * max(n, 1))()
+        for i, ((y, uv), o, (w, h, py, puv)) in enumerate(zip(surfaces, out, geo)):
+            it = items[i]
+            it.d_y, it.d_uv, it.d_dst, it.pitch_y, it.pitch_uv = y.data_ptr(), uv.data_ptr(), o.data_ptr(), py, puv
+            it.w, it.h, it.ksize, it.flags = w, h, ks[i], 0
+        _check(lib().bsx_gaussian_blur_surfaces_batch(self.h, items, n, _stream_ptr()), self.h, "bsx_gaussian_blur_surfaces_batch")
         return out
 
     def yuyv_to_bgr(self, yuyv):

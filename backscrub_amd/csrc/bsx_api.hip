@@ -28,6 +28,7 @@
 #include "specialised.hpp"
 #include "tflite_model.hpp"
 #include "geoms_request.hpp"
+#include "blur_surfaces_plan.hpp"
 
 using namespace bsx;
 
@@ -194,6 +195,10 @@ struct bsx_ctx {
   BlurDesc* h_blur = nullptr;               // pinned [kIdRing][n_streams]
   BlurDesc* d_blur = nullptr;               // device, likewise
   GaussCoef* d_blur_coef = nullptr;         // device [blur_coef_table_bytes()]
+  // bsx_gaussian_blur_surfaces_batch: likewise, the call's n_streams BlurSurfDesc; the coefficient records are d_blur_coef (whichever of the two calls comes first
+  // uploads them).  Allocated on the first call.
+  BlurSurfDesc* h_blur_surf = nullptr;      // pinned [kIdRing][n_streams]
+  BlurSurfDesc* d_blur_surf = nullptr;      // device, likewise
   using Span = bsx::Span;
   std::vector<Span> rsz_spans;              // host scratch of the overlap check: the call's sources and destinations, sorted by address
   // Geometry classes (bsx_new_geoms): class 0 IS the context's own geometry — width, height, roi, in_roi, both tables and the first bytes of d_masks above — so every
@@ -1153,21 +1158,25 @@ int blur_batch_check(bsx_ctx* c, const char* fn, const bsx_blur_item* items, int
   }
   return BSX_OK;
 }
+// the context's ONE device copy of blur_coef_table, made by the first call of either blur batch
+int blur_coef_upload(bsx_ctx* c) {
+  if (c->d_blur_coef) return BSX_OK;
+  std::vector<uint8_t> tab(blur_coef_table_bytes(), 0);
+  blur_coef_table(reinterpret_cast<GaussCoef*>(tab.data()));
+  GaussCoef* dev = nullptr;
+  BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&dev), tab.size()));
+  const hipError_t e = hipMemcpy(dev, tab.data(), tab.size(), hipMemcpyHostToDevice);      // (once per context: complete before the first launch on any stream)
+  if (e != hipSuccess) { (void)hipFree(dev); BSX_HIP(c, e); }
+  c->d_blur_coef = dev;
+  return BSX_OK;
+}
 // items[0..n) as BlurDesc, ordered by size class (a counting sort: stable, so a class keeps the caller's order), into ring entry k (pinned), one copy to the device
 // entry on s; the coefficient table on the first call
 int blur_batch_stage(bsx_ctx* c, const bsx_blur_item* items, int n, const GeomSpans& spans, hipStream_t s, int k, const BlurDesc** d_desc) {
   const size_t N = (size_t)c->n_streams;
   if (!c->h_blur) BSX_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_blur), bsx_ctx::kIdRing * N * sizeof(BlurDesc), hipHostMallocDefault));
   if (!c->d_blur) BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_blur), bsx_ctx::kIdRing * N * sizeof(BlurDesc)));
-  if (!c->d_blur_coef) {
-    std::vector<uint8_t> tab(blur_coef_table_bytes(), 0);
-    blur_coef_table(reinterpret_cast<GaussCoef*>(tab.data()));
-    GaussCoef* dev = nullptr;
-    BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&dev), tab.size()));
-    const hipError_t e = hipMemcpy(dev, tab.data(), tab.size(), hipMemcpyHostToDevice);      // (once per context: complete before the first launch on any stream)
-    if (e != hipSuccess) { (void)hipFree(dev); BSX_HIP(c, e); }
-    c->d_blur_coef = dev;
-  }
+  if (const int rc = blur_coef_upload(c)) return rc;
   int next[kMaxGeoms];
   for (int g = 0; g < kMaxGeoms; g++) next[g] = spans.pos[g];
   BlurDesc* hd = c->h_blur + (size_t)k * N;
@@ -1177,6 +1186,52 @@ int blur_batch_stage(bsx_ctx* c, const bsx_blur_item* items, int n, const GeomSp
   }
   BSX_HIP(c, hipMemcpyAsync(c->d_blur + (size_t)k * N, hd, (size_t)n * sizeof(BlurDesc), hipMemcpyHostToDevice, s));
   *d_desc = c->d_blur + (size_t)k * N;
+  return BSX_OK;
+}
+
+// ---- bsx_gaussian_blur_surfaces_batch: n NV12 surfaces of their own sizes, pitches and blur sizes in ONE launch ------------------------------------------------------
+// Host-side validation of items[0..n): nothing is enqueued before it passes.  The item rules, the size classes and the ragged grid are blur_surfaces_plan.hpp's; the
+// overlap sweep is done here, a plane judged on vcam_nv12_extent (a source span's `item` is 2 i for the Y plane of items[i], 2 i + 1 for its UV plane).
+int blur_surfaces_check(bsx_ctx* c, const char* fn, const bsx_blur_surface_item* items, int n, BlurSurfacesPlan* plan, GeomSpans* spans, BlurTileCols* cols) {
+  const int planned = blur_surfaces_plan(items, n, c->n_streams, plan);
+  if (planned == BlurSurfacesPlan::kRefused) return refuse(c, fn, "%s", plan->text);
+  if (planned == BlurSurfacesPlan::kTooLarge) return too_many_workgroups(c, fn);
+  std::vector<bsx_ctx::Span>& sp = c->rsz_spans;
+  sp.clear();
+  for (int i = 0; i < n; i++) {
+    const bsx_blur_surface_item& it = items[i];
+    sp.push_back({(uintptr_t)it.d_y, (uintptr_t)it.d_y + vcam_nv12_extent(it.pitch_y, it.h, it.w), 2 * i, false});
+    sp.push_back({(uintptr_t)it.d_uv, (uintptr_t)it.d_uv + vcam_nv12_extent(it.pitch_uv, it.h / 2, it.w), 2 * i + 1, false});
+    sp.push_back({(uintptr_t)it.d_dst, (uintptr_t)it.d_dst + (size_t)it.w * (size_t)it.h * 3, i, true});
+  }
+  const bsx_ctx::Span* d = nullptr;
+  const bsx_ctx::Span* o = nullptr;
+  if (spans_overlap(sp, &d, &o))
+    return refuse(c, fn, "items[%d]: d_dst %p overlaps the %s of items[%d] (%p)", d->item, (const void*)d->begin, o->dst ? "destination" : (o->item & 1) ? "UV plane" : "Y plane",
+                  o->dst ? o->item : o->item >> 1, (const void*)o->begin);
+  *spans = GeomSpans{};
+  *cols = BlurTileCols{};
+  static_assert(kBsMaxSizes == kMaxGeoms, "the plan's arrays are GeomSpans' and BlurTileCols'");
+  for (int g = 0; g <= kMaxGeoms; g++) { spans->pos[g] = plan->pos[g]; spans->wg[g] = plan->wg[g]; }
+  for (int g = 0; g < kMaxGeoms; g++) { spans->per[g] = plan->per[g]; cols->ntx[g] = plan->ntx[g]; }
+  return BSX_OK;
+}
+// items[0..n) as BlurSurfDesc, ordered by size class (a counting sort on the plan's classes: stable), into ring entry k (pinned), one copy to the device entry on s;
+// the coefficient table on the first call of either blur batch
+int blur_surfaces_stage(bsx_ctx* c, const bsx_blur_surface_item* items, int n, const BlurSurfacesPlan& plan, hipStream_t s, int k, const BlurSurfDesc** d_desc) {
+  const size_t N = (size_t)c->n_streams;
+  if (!c->h_blur_surf) BSX_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_blur_surf), bsx_ctx::kIdRing * N * sizeof(BlurSurfDesc), hipHostMallocDefault));
+  if (!c->d_blur_surf) BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_blur_surf), bsx_ctx::kIdRing * N * sizeof(BlurSurfDesc)));
+  if (const int rc = blur_coef_upload(c)) return rc;
+  int next[kMaxGeoms];
+  for (int g = 0; g < kMaxGeoms; g++) next[g] = plan.pos[g];
+  BlurSurfDesc* hd = c->h_blur_surf + (size_t)k * N;
+  for (int i = 0; i < n; i++) {
+    const bsx_blur_surface_item& it = items[i];
+    hd[next[plan.cls[(size_t)i]]++] = BlurSurfDesc{it.d_y, it.d_uv, it.d_dst, it.pitch_y, it.pitch_uv, it.w, it.h, it.ksize, 0u};
+  }
+  BSX_HIP(c, hipMemcpyAsync(c->d_blur_surf + (size_t)k * N, hd, (size_t)n * sizeof(BlurSurfDesc), hipMemcpyHostToDevice, s));
+  *d_desc = c->d_blur_surf + (size_t)k * N;
   return BSX_OK;
 }
 
@@ -1681,6 +1736,8 @@ void bsx_delete(bsx_ctx* c) {
   if (c->d_blur) (void)hipFree(c->d_blur);
   if (c->h_blur) (void)hipHostFree(c->h_blur);
   if (c->d_blur_coef) (void)hipFree(c->d_blur_coef);
+  if (c->d_blur_surf) (void)hipFree(c->d_blur_surf);
+  if (c->h_blur_surf) (void)hipHostFree(c->h_blur_surf);
   for (size_t g = 1; g < c->geoms.size(); g++) { if (c->geoms[g].tab_down.mem) (void)hipFree(c->geoms[g].tab_down.mem); if (c->geoms[g].tab_up.mem) (void)hipFree(c->geoms[g].tab_up.mem); }
   if (c->d_geom_classes) (void)hipFree(c->d_geom_classes);
   if (c->d_geom_classes_vg) (void)hipFree(c->d_geom_classes_vg);
@@ -1988,6 +2045,28 @@ int bsx_gaussian_blur_bgr_batch(bsx_ctx* c, const bsx_blur_item* items, int n, v
   if (!rc) {
     const hipError_t e = launch_blur_batch(d_desc, c->d_blur_coef, spans, cols, s);
     if (e != hipSuccess) { report(c, c->ondebug, c->caller_ctx, "error: HIP %s while blurring a batch\n", hipGetErrorString(e)); rc = BSX_EDEVICE; }
+  }
+  return ids_release(c, entry, s, rc);
+}
+
+// n NV12 surfaces, each of its own size, pitches and blur size, blurred into BGR images in ONE launch: planned and checked on the host, the descriptors ordered by size
+// through the staging ring, the ragged grid's spans by value
+int bsx_gaussian_blur_surfaces_batch(bsx_ctx* c, const bsx_blur_surface_item* items, int n, void* stream) {
+  if (!c) return BSX_EINVAL;
+  BlurSurfacesPlan plan;
+  GeomSpans spans{};
+  BlurTileCols cols{};
+  if (const int rc = blur_surfaces_check(c, "bsx_gaussian_blur_surfaces_batch", items, n, &plan, &spans, &cols)) return rc;
+  if (n == 0) return BSX_OK;
+  DeviceGuard guard(c->device);
+  hipStream_t s = pick(c, stream);
+  int entry = 0;
+  if (const int rc = ring_acquire(c, &entry)) return rc;
+  const BlurSurfDesc* d_desc = nullptr;
+  int rc = blur_surfaces_stage(c, items, n, plan, s, entry, &d_desc);
+  if (!rc) {
+    const hipError_t e = launch_blur_surfaces(d_desc, c->d_blur_coef, spans, cols, s);
+    if (e != hipSuccess) { report(c, c->ondebug, c->caller_ctx, "error: HIP %s while blurring a batch of surfaces\n", hipGetErrorString(e)); rc = BSX_EDEVICE; }
   }
   return ids_release(c, entry, s, rc);
 }

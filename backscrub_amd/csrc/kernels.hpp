@@ -315,6 +315,14 @@ inline long blur_tiles(int w, int h) { return (long)((w + 63) / 64) * (long)((h 
 struct BlurTileCols { int ntx[kMaxGeoms]; };                      // by value next to the spans: tiles per image row of class g (blur_tile_cols of its width)
 inline int blur_tile_cols(int w) { return (w + 63) / 64; }
 hipError_t launch_blur_batch(const BlurDesc* desc, const GaussCoef* coef, const GeomSpans& spans, const BlurTileCols& cols, hipStream_t s);
+// launch_blur_batch for NV12 surfaces (bsx_gaussian_blur_surfaces_batch): position i reads desc[i] (a DEVICE array ORDERED BY SURFACE SIZE, three 16-byte uniform loads
+// per workgroup) — its Y plane ([h] rows of pitch_y bytes) and interleaved UV plane ([h / 2] rows of pitch_uv bytes; both planes 4-byte aligned, the pitches multiples
+// of 4 and >= w, w and h even, every plane below 2^31 bytes: offsets into a plane are 32-bit), its destination (w x h BGR, any alignment: a 4-byte aligned one with
+// w % 4 == 0 is stored as dwords) and its blur size (odd, 1 .. 31; 1 = the conversion alone).  spans, cols and coef as above — the same table.  The integers of
+// launch_nv12_to_bgr, then those of launch_gauss_blur; no load touches a byte at or past w of a row.
+struct alignas(16) BlurSurfDesc { const uint8_t* y; const uint8_t* uv; uint8_t* dst; int pitch_y, pitch_uv; int w, h, ksize; unsigned flags; };
+static_assert(sizeof(BlurSurfDesc) == 48, "three 16-byte uniform loads per workgroup");
+hipError_t launch_blur_surfaces(const BlurSurfDesc* desc, const GaussCoef* coef, const GeomSpans& spans, const BlurTileCols& cols, hipStream_t s);
 // composite at the virtual camera's geometry: alpha blend → cv::flip (flags bits 1-2) → cv::resize to (tab.dw, tab.dh) → [YUYV pack (bit 0)] in one pass over
 // frames, background and the persistent masks (deepseg.cc:634-681).  `tab`: a linear table from the capture size (the 2x2 area mode expanded to one);
 // direct = !vcam_tile_fits(tab): every tap blended where it is read instead of the footprint staged in LDS.  yuyv_in: `frames` is YUYV 4:2:2

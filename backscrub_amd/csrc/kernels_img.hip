@@ -2146,7 +2146,9 @@ __device__ __forceinline__ uint32_t blur_src_px(const uint8_t* __restrict__ in, 
   return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
 }
 // gauss_blur_k's passes 2 and 3 for one NT, the coefficient words copied out of the record first (uniform address, constant offsets: scalar loads)
-template <int NT>
+// USER: not read.  Each kernel that takes the passes names its own instances (blur_surfaces_k: 1): an instance inlined at one place only keeps blur_batch_k's code what
+// it was (with two callers of one instance the compiler emitted another, longer blur_batch_k: tools/isa_same.py).
+template <int NT, int USER = 0>
 __device__ __forceinline__ void blur_passes(uint8_t* s_src, uint16_t* s_h, const GaussCoef* __restrict__ gc, int SH, bool owords, uint8_t* __restrict__ out, int W, int H,
                                             int x0, int y0) {
   static_assert(NT >= 2 && NT <= 9, "tap words of the horizontal pass");
@@ -2989,6 +2991,132 @@ hipError_t launch_nv12_to_bgr(const uint8_t* y, int pitch_y, const uint8_t* uv, 
     if (words) nv12_to_bgr_k<true><<<dim3(blocks_for(blocks), nn), kThreads, 0, s>>>(yp, pitch_y, up, pitch_uv, dst, w, h);
     else nv12_to_bgr_k<false><<<dim3(blocks_for(blocks), nn), kThreads, 0, s>>>(yp, pitch_y, up, pitch_uv, dst, w, h);
   }
+  return hipGetLastError();
+}
+
+// ---- bsx_gaussian_blur_surfaces_batch: n NV12 surfaces, each of its own size, pitches and blur size, in ONE launch ------------------------------------------------------
+// blur_batch_k with another staging pass: the ragged grid, the tile (64 x 16, de-interleaved byte planes in LDS), the coefficient table and blur_passes<NT> are its
+// own; a position's BlurSurfDesc comes by three uniform loads and stays in SGPRs.  Pixel (x, y) of a surface takes Y[y][x] and the pair UV[y >> 1][x & ~1 ..], the
+// integers from there are yuv_tap_to_bgr's (vcam_surf_frame_px).  Decided per workgroup, on scalars:
+//   * staging: the word path under blur_batch_k's `xin` rule with rows4 always true (planes and pitches are dword aligned whatever w is) and the bound on the WIDTH,
+//     x0 - r - sh + 4 Gw <= W, never on the pitch: bytes [w, pitch) of a row are not read.  An item is (row, 4-pixel group): one Y dword at gy * pitch_y + xb + 4 grp
+//     and one UV dword (U0 V0 U1 V1) at (gy >> 1) * pitch_uv + xb + 4 grp, gy the row after reflect101_far — xb is a multiple of 4, so the dword holds the group's two
+//     whole chroma pairs — into yuv_luma / yuv_chroma / sat_pk2_shr20 as blur_batch_k's YUYV word path: one dword per LDS plane.  Else the reflecting byte path
+//     (sh = 0, its own coefficient record): pixel (gx, gy) after BOTH reflections, its chroma row (gy >> 1) that of the reflected row;
+//   * NT, the output form (dwords from the packed tile where w % 4 == 0 and dst is 4-byte aligned, else byte stores from the vertical pass) and ksize 1 (the converted
+//     pixels, stored without LDS) as in blur_batch_k.
+// Offsets into the planes and into dst are 32-bit: the host refuses a plane of 2^31 bytes or more and w * h * 3 >= 2^31 (blur_surfaces_plan.hpp).
+// A template of one instance in a namespace of its own at the end of the file, launched by the file's last launcher, for the reason given above mask_geoms_k: every
+// earlier kernel's text is what it was.
+namespace {
+struct BlurSurfRegs { const uint8_t* y; const uint8_t* uv; uint8_t* dst; int py, puv, w, h, ksize; };
+__device__ __forceinline__ BlurSurfRegs blur_surf_desc(const BlurSurfDesc* __restrict__ desc, int n) {
+  const uint4* p = reinterpret_cast<const uint4*>(desc) + 3 * (size_t)n;
+  const uint4 a = p[0], b = p[1], c = p[2];
+  typedef __attribute__((address_space(1))) uint8_t* gp;
+  BlurSurfRegs d;
+  d.y = (const uint8_t*)(gp)(((uint64_t)a.y << 32) | a.x);
+  d.uv = (const uint8_t*)(gp)(((uint64_t)a.w << 32) | a.z);
+  d.dst = (uint8_t*)(gp)(((uint64_t)b.y << 32) | b.x);
+  d.py = (int)b.z; d.puv = (int)b.w;
+  d.w = (int)c.x; d.h = (int)c.y; d.ksize = (int)c.z;
+  return d;
+}
+// pixel (gx, gy) of a position's surface as B | G << 8 | R << 16: vcam_surf_frame_px with 32-bit offsets
+__device__ __forceinline__ uint32_t blur_surf_px(const BlurSurfRegs& d, int gx, int gy) {
+  const uint8_t* const c = d.uv + (unsigned)((gy >> 1) * d.puv + (gx & ~1));
+  return yuv_tap_to_bgr((uint32_t)d.y[(unsigned)(gy * d.py + gx)] | ((uint32_t)c[0] << 8) | ((uint32_t)c[1] << 16));
+}
+
+template <int = 0>
+__global__ __launch_bounds__(kThreads) void blur_surfaces_k(const BlurSurfDesc* __restrict__ desc, const GaussCoef* __restrict__ coef, GeomSpans sp, BlurTileCols cols) {
+  __shared__ __attribute__((aligned(16))) uint8_t s_src[3 * kGSH * kGSrcStride];          // [plane][row][col]; whole-dword output: later the packed tile [row][kGOStride]
+  __shared__ __attribute__((aligned(16))) uint16_t s_h[3 * kGHPlane];                     // [plane][col][row], gh_col()
+  int g, w0, p0, p1, per;
+  geom_span(sp, (int)blockIdx.x, &g, &w0, &p0, &p1, &per);
+  const unsigned local = blockIdx.x - (unsigned)w0, pl = local / (unsigned)per, tile = local - pl * (unsigned)per;
+  const BlurSurfRegs d = blur_surf_desc(desc, p0 + (int)pl);
+  const int W = d.w, H = d.h, r = d.ksize >> 1;
+  uint8_t* __restrict__ const out = d.dst;
+  unsigned ntx = (unsigned)cols.ntx[0];                               // (selected on SGPRs, as in blur_batch_k)
+#pragma unroll
+  for (int k = 1; k < kMaxGeoms; k++) if (g == k) ntx = (unsigned)cols.ntx[k];
+  const unsigned ty = tile / ntx, tx = tile - ty * ntx;
+  const int x0 = (int)tx * kGTW, y0 = (int)ty * kGTH;
+  if (r == 0) {                                                       // ksize 1: the converted pixels themselves
+    for (int i = threadIdx.x; i < kGTW * kGTH; i += kThreads) {
+      const int gx = x0 + (i & (kGTW - 1)), gy = y0 + i / kGTW;
+      if (gx < W && gy < H) {
+        const uint32_t px = blur_surf_px(d, gx, gy);
+        uint8_t* o = out + (unsigned)(gy * W + gx) * 3u;
+        o[0] = (uint8_t)px; o[1] = (uint8_t)(px >> 8); o[2] = (uint8_t)(px >> 16);
+      }
+    }
+    return;
+  }
+  const int SW = kGTW + 2 * r, SH = kGTH + 2 * r;                     // live part of the source tile
+  // 1. stage + convert + de-interleave (reflected at the surface's border)
+  const int shw = (-r) & 3, Gw = (SW + shw + 3) >> 2;
+  const bool xin = x0 - r - shw >= 0 && x0 - r - shw + 4 * Gw <= W;
+  const int sh = xin ? shw : 0;
+  if (xin) {                                                          // item = (row, group of 4 pixels) → one dword per plane
+    const int G = Gw;
+    int row = (int)threadIdx.x / G, grp = (int)threadIdx.x - row * G;
+    const int dr = kThreads / G, dc = kThreads - dr * G;
+    const unsigned xb = (unsigned)(x0 - r - sh);
+    while (row < SH) {
+      const int gy = reflect101_far(y0 - r + row, H);
+      const uint32_t yw = *reinterpret_cast<const uint32_t*>(d.y + ((unsigned)(gy * d.py) + xb + 4u * (unsigned)grp));              // Y0 Y1 Y2 Y3
+      const uint32_t cw = *reinterpret_cast<const uint32_t*>(d.uv + ((unsigned)((gy >> 1) * d.puv) + xb + 4u * (unsigned)grp));     // U0 V0 U1 V1
+      int bu0, gu0, ru0, bu1, gu1, ru1;
+      yuv_chroma((int)(cw & 255u) - 128, (int)((cw >> 8) & 255u) - 128, &bu0, &gu0, &ru0);
+      yuv_chroma((int)((cw >> 16) & 255u) - 128, (int)(cw >> 24) - 128, &bu1, &gu1, &ru1);
+      const int ya = yuv_luma(yw & 255u), yb = yuv_luma((yw >> 8) & 255u), yc = yuv_luma((yw >> 16) & 255u), yd = yuv_luma(yw >> 24);
+      const uint32_t pb = (sat_pk2_shr20(ya + bu0, yb + bu0) & 0xffffu) | (sat_pk2_shr20(yc + bu1, yd + bu1) << 16);
+      const uint32_t pg = (sat_pk2_shr20(ya + gu0, yb + gu0) & 0xffffu) | (sat_pk2_shr20(yc + gu1, yd + gu1) << 16);
+      const uint32_t pr = (sat_pk2_shr20(ya + ru0, yb + ru0) & 0xffffu) | (sat_pk2_shr20(yc + ru1, yd + ru1) << 16);
+      uint32_t* o = reinterpret_cast<uint32_t*>(s_src + row * kGSrcStride) + grp;
+      o[0] = pb; o[kGSH * kGSrcStride / 4] = pg; o[2 * kGSH * kGSrcStride / 4] = pr;
+      grp += dc; row += dr;
+      if (grp >= G) { grp -= G; row++; }
+    }
+  } else {
+    int row = (int)threadIdx.x / SW, col = (int)threadIdx.x - row * SW;
+    const int dr = kThreads / SW, dc = kThreads - dr * SW;
+    while (row < SH) {
+      const int gy = reflect101_far(y0 - r + row, H), gx = reflect101_far(x0 - r + col, W);
+      const uint32_t px = blur_surf_px(d, gx, gy);
+      s_src[(0 * kGSH + row) * kGSrcStride + col] = (uint8_t)px;
+      s_src[(1 * kGSH + row) * kGSrcStride + col] = (uint8_t)(px >> 8);
+      s_src[(2 * kGSH + row) * kGSrcStride + col] = (uint8_t)(px >> 16);
+      col += dc; row += dr;
+      if (col >= SW) { col -= SW; row++; }
+    }
+  }
+  // 2. + 3. blur_batch_k's passes: NT = ceil((ksize + 3 + sh) / 4) (each body copies its coefficient words out first, then the barrier behind the staging)
+  const bool owords = (((W & 3) | (int)((uintptr_t)out & 3)) == 0);
+  const GaussCoef* __restrict__ const gc = coef + blur_coef_index(d.ksize, xin);
+  switch ((d.ksize + sh + 6) >> 2) {
+#define BSX_BS(NT) case NT: blur_passes<NT, 1>(s_src, s_h, gc, SH, owords, out, W, H, x0, y0); break;
+    BSX_BS(2) BSX_BS(3) BSX_BS(4) BSX_BS(5) BSX_BS(6) BSX_BS(7) BSX_BS(8) default: BSX_BS(9)
+#undef BSX_BS
+  }
+  if (owords) {                                                       // this lane's 4-pixel group of the packed tile: three whole dwords
+    __syncthreads();
+    const int orow = threadIdx.x >> 4, ogx = x0 + 4 * (threadIdx.x & 15), ogy = y0 + orow;
+    if (ogx < W && ogy < H) {
+      const uint32_t* bp = reinterpret_cast<const uint32_t*>(s_src + orow * kGOStride + 12 * (threadIdx.x & 15));
+      uint32_t* op = reinterpret_cast<uint32_t*>(out + (unsigned)(ogy * W + ogx) * 3u);
+      op[0] = bp[0]; op[1] = bp[1]; op[2] = bp[2];
+    }
+  }
+}
+}  // namespace
+
+hipError_t launch_blur_surfaces(const BlurSurfDesc* desc, const GaussCoef* coef, const GeomSpans& spans, const BlurTileCols& cols, hipStream_t s) {
+  if (!desc || !coef || spans.wg[kMaxGeoms] <= 0) return hipErrorInvalidValue;
+  for (int g = 0; g < kMaxGeoms; g++) if (spans.per[g] > 0 && (cols.ntx[g] <= 0 || spans.per[g] % cols.ntx[g])) return hipErrorInvalidValue;
+  blur_surfaces_k<><<<dim3((unsigned)spans.wg[kMaxGeoms]), kThreads, 0, s>>>(desc, coef, spans, cols);
   return hipGetLastError();
 }
 

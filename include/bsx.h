@@ -41,6 +41,7 @@
  *   bsx_gaussian_blur_bgr  cv::GaussianBlur of the background app/deepseg.cc:415-431,652-658 (-p bgblur:<n>: blur the camera frame itself
  *                          (or the background image) and composite over it)
  *   bsx_gaussian_blur_bgr_batch  cv::GaussianBlur of every camera's own frame, once per main-loop iteration  app/deepseg.cc:652-658
+ *   bsx_gaussian_blur_surfaces_batch  … of every decoder surface (NV12), the blur mode of bsx_step_batch_surfaces  app/deepseg.cc:415-431, 652-661
  *   bsx_background_*       load_background / grab_background + reader thread   app/background.cc:29-104,126-194
  *   bsx_background_grab_batch  grab_background() of every camera's own source, once per main-loop iteration   app/deepseg.cc:648-651
  *   bsx_live_*             class CalcMask (worker thread, double buffering)     app/deepseg.cc:159-286
@@ -568,6 +569,38 @@ typedef struct bsx_blur_item {
   unsigned flags;         /* 0 | BSX_STREAM_YUYV_IN */
 } bsx_blur_item;
 BSX_API int bsx_gaussian_blur_bgr_batch(bsx_ctx* ctx, const bsx_blur_item* items, int n, void* stream);
+
+/* The same call for NV12 decoder surfaces: n surfaces, each of its own size, pitches and blur size, blurred into capture-size BGR images in ONE kernel launch — the
+ * blur mode of bsx_step_batch_surfaces, whose `setting.d_bg` takes what this call writes.  A surfaces tick in the reference's default mode is this call followed by
+ * bsx_step_batch_surfaces; the decoder's pool stays where it is (no two surfaces need be adjacent) and no 3 B/px copy of a frame is made.
+ *   - d_dst of item i is byte-identical to bsx_nv12_to_bgr(d_y, pitch_y, d_uv, pitch_uv, w, h, 1, tmp) followed by bsx_gaussian_blur_bgr(tmp, d_dst, w, h, 1, ksize).
+ *     The surface's BGR frame is the one bsx_step_batch_surfaces defines: pixel (x, y) takes Y[y][x] and the pair UV[y >> 1][x & ~1 ..], with the integers of
+ *     bsx_yuyv_to_bgr.  The frame is converted as the blur reads it: no BGR copy of the frame exists anywhere.  Bytes [w, pitch) of a row are never read;
+ *   - ksize 1 is the conversion alone, done in the same launch;
+ *   - the whole call is one launch, whatever the mix of sizes, blur sizes and pitches; it takes at most BSX_MAX_GEOMS distinct (w, h) pairs (the grid is ragged: the
+ *     positions are ordered by size on the host, stably, so one 1920x1080 surface among many small ones launches no empty workgroup);
+ *   - items is a HOST array, read before the call returns; the descriptors reach the device through the staging ring of bsx_step_batch_streams (no host
+ *     synchronisation unless the caller runs a ring's length ahead of the GPU); the coefficient words are those bsx_gaussian_blur_bgr_batch uploads, once per context;
+ *   - n <= n_streams of the context; n == 0 returns 0 and enqueues nothing; the same surface may appear in several items (one frame at two blur sizes); works on
+ *     every kind of context, whatever its classes: blurring needs no resize table, so surfaces of classes that bsx_step_batch_surfaces refuses can still be blurred;
+ *   - d_dst takes any alignment (a 4-byte aligned one with w % 4 == 0 is stored as dwords);
+ *   - BSX_EINVAL before anything is enqueued, with a bsx_last_error text naming items[i] and the offending value, for: n < 0 or n > n_streams; items NULL with
+ *     n > 0; a non-positive or odd w or h; a ksize that is even, below 1 or above 31; a NULL d_y, d_uv or d_dst; a plane that is not 4-byte aligned; a pitch below w
+ *     or not a multiple of 4; any bit in flags; w * h * 3 >= 2^31, or a plane of 2 GiB or more; a ninth distinct size; a d_dst (w * h * 3 bytes) that overlaps any
+ *     item's Y or UV plane (its own included; a plane extends from its first byte to byte w of its last row) or another destination.  BSX_EDEVICE for a grid of 2^31
+ *     workgroups or more.  A refused call changes nothing.
+ * Out of scope: NV12 items inside bsx_gaussian_blur_bgr_batch, an NV12 or YUYV destination, blur as a bit of bsx_surface_item.setting, and the formats P010 and
+ * I420 (three planes) as sources. */
+typedef struct bsx_blur_surface_item {
+  const uint8_t* d_y;    /* [h] rows of pitch_y bytes, 4-byte aligned */
+  const uint8_t* d_uv;   /* [h / 2] rows of pitch_uv bytes (U, V interleaved), 4-byte aligned */
+  uint8_t* d_dst;        /* [h][w][3] BGR, any alignment */
+  int pitch_y, pitch_uv; /* multiples of 4, >= w */
+  int w, h;              /* even, positive */
+  int ksize;             /* odd, 1..31 */
+  unsigned flags;        /* 0 */
+} bsx_blur_surface_item;   /* 48 bytes */
+BSX_API int bsx_gaussian_blur_surfaces_batch(bsx_ctx* ctx, const bsx_blur_surface_item* items, int n, void* stream);
 
 /* ---- background source (app/background.cc) ----
  * load_background(): a still image or an animation (GIF87a/89a, 8-bit non-interlaced PNG, binary PPM decoded in this library; other
