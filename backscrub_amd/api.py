@@ -64,6 +64,11 @@ class _BlurSurfaceItem(C.Structure):        # bsx.h bsx_blur_surface_item
                 ("ksize", C.c_int), ("flags", C.c_uint)]
 
 
+class _ResizeSurfaceItem(C.Structure):      # bsx.h bsx_resize_surface_item
+    _fields_ = [("d_y", C.c_void_p), ("d_uv", C.c_void_p), ("d_dst", C.c_void_p), ("pitch_y", C.c_int), ("pitch_uv", C.c_int), ("sw", C.c_int), ("sh", C.c_int),
+                ("dw", C.c_int), ("dh", C.c_int), ("flags", C.c_uint), ("reserved", C.c_int)]
+
+
 class _Geometry(C.Structure):               # bsx.h bsx_geometry
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("n_streams", C.c_int)]
 
@@ -168,6 +173,7 @@ SYMBOLS = [
     ("bsx_gaussian_blur_bgr", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("bsx_gaussian_blur_bgr_batch", C.c_int, [C.c_void_p, C.POINTER(_BlurItem), C.c_int, C.c_void_p]),
     ("bsx_gaussian_blur_surfaces_batch", C.c_int, [C.c_void_p, C.POINTER(_BlurSurfaceItem), C.c_int, C.c_void_p]),
+    ("bsx_resize_surfaces_batch", C.c_int, [C.c_void_p, C.POINTER(_ResizeSurfaceItem), C.c_int, C.c_void_p]),
     ("bsx_debug_gauss_coeffs", C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("bsx_flip_bgr", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     ("bsx_debug_buffer", C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
@@ -949,6 +955,58 @@ class MaskGen:
             it.d_y, it.d_uv, it.d_dst, it.pitch_y, it.pitch_uv = y.data_ptr(), uv.data_ptr(), o.data_ptr(), py, puv
             it.w, it.h, it.ksize, it.flags = w, h, ks[i], 0
         _check(lib().bsx_gaussian_blur_surfaces_batch(self.h, items, n, _stream_ptr()), self.h, "bsx_gaussian_blur_surfaces_batch")
+        return out
+
+    def resize_surfaces(self, surfaces, sizes, out=None):
+        """grab_background() of video backgrounds whose frames a hardware decoder leaves as NV12 surfaces, in one launch (bsx_resize_surfaces_batch; the integers of
+        nv12_to_bgr, then resize_bgr's — no BGR copy of a surface is made).  surfaces: a sequence of (y, uv) as gaussian_blur_surfaces takes them, each of its own
+        size and pitches, not necessarily adjacent, the same one any number of times; sizes: one (w, h) for all, or one per surface — at most 8 distinct ones; out:
+        None (new tensors) or a sequence of contiguous [h_i,w_i,3] tensors.  Returns the list of outputs — what a StreamSetting's bg takes, so a surfaces tick with
+        video backgrounds is this call followed by step_surfaces."""
+        torch = _torch()
+        surfaces = list(surfaces)
+        n = len(surfaces)
+        if n > self.n_streams:
+            raise BsxError("%d surfaces for a context of %d streams" % (n, self.n_streams))
+        sizes = list(sizes)
+        if len(sizes) == 2 and all(isinstance(v, (int, np.integer)) for v in sizes):
+            sizes = [tuple(sizes)] * n
+        if len(sizes) != n:
+            raise BsxError("%d sizes for %d surfaces" % (len(sizes), n))
+        dst = []
+        for i, sz in enumerate(sizes):
+            if not isinstance(sz, (tuple, list)) or len(sz) != 2 or not all(isinstance(v, (int, np.integer)) for v in sz):
+                raise BsxError("sizes[%d] must be a pair (w, h) of integers" % i)
+            if sz[0] <= 0 or sz[1] <= 0:
+                raise BsxError("sizes[%d] = %d x %d is not positive" % (i, sz[0], sz[1]))
+            dst.append((int(sz[0]), int(sz[1])))
+        geo = []
+        for i, sf in enumerate(surfaces):
+            if not isinstance(sf, (tuple, list)) or len(sf) != 2:
+                raise BsxError("surfaces[%d] must be a pair (y, uv)" % i)
+            geo.append(self._nv12_planes("surfaces[%d]" % i, sf[0], sf[1], device=False))
+        if out is not None:
+            out = list(out)
+            if len(out) != n:
+                raise BsxError("%d outputs for %d surfaces" % (len(out), n))
+            for i, (o, (w, h)) in enumerate(zip(out, dst)):
+                if not (isinstance(o, torch.Tensor) and o.dtype == torch.uint8 and tuple(o.shape) == (h, w, 3) and o.is_contiguous()):
+                    raise BsxError("out[%d] must be a contiguous uint8 tensor [%d,%d,3]" % (i, h, w))
+        for i, (y, uv) in enumerate(surfaces):
+            for name, t in (("y", y), ("uv", uv)):
+                if not self._on_device(t):
+                    raise BsxError("surfaces[%d]: %s is on %s, not on the context's cuda:%d" % (i, name, t.device, self.device))
+        for i, t in enumerate(out or []):
+            if not self._on_device(t):
+                raise BsxError("out[%d] is on %s, not on the context's cuda:%d" % (i, t.device, self.device))
+        if out is None:
+            out = [torch.empty((h, w, 3), dtype=torch.uint8, device="cuda:%d" % self.device) for w, h in dst]
+        items = (_ResizeSurfaceItem * max(n, 1))()
+        for i, ((y, uv), o, (sw, sh, py, puv), (dw, dh)) in enumerate(zip(surfaces, out, geo, dst)):
+            it = items[i]
+            it.d_y, it.d_uv, it.d_dst, it.pitch_y, it.pitch_uv = y.data_ptr(), uv.data_ptr(), o.data_ptr(), py, puv
+            it.sw, it.sh, it.dw, it.dh, it.flags, it.reserved = sw, sh, dw, dh, 0, 0
+        _check(lib().bsx_resize_surfaces_batch(self.h, items, n, _stream_ptr()), self.h, "bsx_resize_surfaces_batch")
         return out
 
     def yuyv_to_bgr(self, yuyv):

@@ -29,6 +29,7 @@
 #include "tflite_model.hpp"
 #include "geoms_request.hpp"
 #include "blur_surfaces_plan.hpp"
+#include "resize_surfaces_plan.hpp"
 
 using namespace bsx;
 
@@ -199,6 +200,9 @@ struct bsx_ctx {
   // uploads them).  Allocated on the first call.
   BlurSurfDesc* h_blur_surf = nullptr;      // pinned [kIdRing][n_streams]
   BlurSurfDesc* d_blur_surf = nullptr;      // device, likewise
+  // bsx_resize_surfaces_batch: likewise, the call's n_streams ResizeSurfDesc, ordered by destination size.  Allocated on the first call.
+  ResizeSurfDesc* h_rsz_surf = nullptr;     // pinned [kIdRing][n_streams]
+  ResizeSurfDesc* d_rsz_surf = nullptr;     // device, likewise
   using Span = bsx::Span;
   std::vector<Span> rsz_spans;              // host scratch of the overlap check: the call's sources and destinations, sorted by address
   // Geometry classes (bsx_new_geoms): class 0 IS the context's own geometry — width, height, roi, in_roi, both tables and the first bytes of d_masks above — so every
@@ -1235,6 +1239,38 @@ int blur_surfaces_stage(bsx_ctx* c, const bsx_blur_surface_item* items, int n, c
   return BSX_OK;
 }
 
+// ---- bsx_resize_surfaces_batch: n NV12 surfaces of their own sizes and pitches, each to an output size of its own, in ONE launch -----------------------------------
+// Every rule, the destination-size classes, the stable order and the ragged grid are resize_surfaces_plan.hpp's; here: the plan as the launcher's arguments.
+int resize_surfaces_check(bsx_ctx* c, const char* fn, const bsx_resize_surface_item* items, int n, ResizeSurfacesPlan* plan, GeomSpans* spans, ResizeDstSizes* sizes) {
+  const int planned = resize_surfaces_plan(items, n, c->n_streams, plan);
+  if (planned == ResizeSurfacesPlan::kRefused) return refuse(c, fn, "%s", plan->text);
+  if (planned == ResizeSurfacesPlan::kTooLarge) return too_many_workgroups(c, fn);
+  *spans = GeomSpans{};
+  *sizes = ResizeDstSizes{};
+  static_assert(kRsMaxSizes == kMaxGeoms, "the plan's arrays are GeomSpans' and ResizeDstSizes'");
+  for (int g = 0; g <= kMaxGeoms; g++) { spans->pos[g] = plan->pos[g]; spans->wg[g] = plan->wg[g]; }
+  for (int g = 0; g < kMaxGeoms; g++) { spans->per[g] = plan->per[g]; sizes->dw[g] = plan->sizes[g][0]; sizes->dh[g] = plan->sizes[g][1]; }
+  return BSX_OK;
+}
+// items[0..n) as ResizeSurfDesc in the plan's order into ring entry k (pinned), one copy to the device entry on s; the table of each (sw, sh, dw, dh) from bg_tabs,
+// uploaded on first use
+int resize_surfaces_stage(bsx_ctx* c, const bsx_resize_surface_item* items, int n, const ResizeSurfacesPlan& plan, hipStream_t s, int k, const ResizeSurfDesc** d_desc) {
+  const size_t N = (size_t)c->n_streams;
+  if (!c->h_rsz_surf) BSX_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_rsz_surf), bsx_ctx::kIdRing * N * sizeof(ResizeSurfDesc), hipHostMallocDefault));
+  if (!c->d_rsz_surf) BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_rsz_surf), bsx_ctx::kIdRing * N * sizeof(ResizeSurfDesc)));
+  ResizeSurfDesc* hd = c->h_rsz_surf + (size_t)k * N;
+  const DevResizeTab* t = nullptr;
+  for (int q = 0; q < n; q++) {
+    const bsx_resize_surface_item& it = items[plan.order[(size_t)q]];
+    if (!t || t->tab.sw != it.sw || t->tab.sh != it.sh || t->tab.dw != it.dw || t->tab.dh != it.dh)      // (a run of equal sizes looks its table up once)
+      if (const int rc = bg_tab(c, it.sw, it.sh, it.dw, it.dh, &t)) return rc;
+    hd[q] = ResizeSurfDesc{it.d_y, it.d_uv, it.d_dst, t->tab.xofs, t->tab.xa, t->tab.yofs, t->tab.ya, it.pitch_y, it.pitch_uv, it.sw, it.sh, t->tab.mode, 0};
+  }
+  BSX_HIP(c, hipMemcpyAsync(c->d_rsz_surf + (size_t)k * N, hd, (size_t)n * sizeof(ResizeSurfDesc), hipMemcpyHostToDevice, s));
+  *d_desc = c->d_rsz_surf + (size_t)k * N;
+  return BSX_OK;
+}
+
 // ---- bsx_step_batch_geoms: streams of any mix of geometry classes in ONE prep launch, ONE network pass, ONE tile-class and ONE tile launch ----------------------
 // Checked on the host (geoms_call: the ids, then geoms_request.hpp's geoms_check), then: the positions ordered by class, their ids and descriptors
 // through the staging ring, the per-class spans of the ragged grids by value in the kernel arguments.
@@ -1738,6 +1774,8 @@ void bsx_delete(bsx_ctx* c) {
   if (c->d_blur_coef) (void)hipFree(c->d_blur_coef);
   if (c->d_blur_surf) (void)hipFree(c->d_blur_surf);
   if (c->h_blur_surf) (void)hipHostFree(c->h_blur_surf);
+  if (c->d_rsz_surf) (void)hipFree(c->d_rsz_surf);
+  if (c->h_rsz_surf) (void)hipHostFree(c->h_rsz_surf);
   for (size_t g = 1; g < c->geoms.size(); g++) { if (c->geoms[g].tab_down.mem) (void)hipFree(c->geoms[g].tab_down.mem); if (c->geoms[g].tab_up.mem) (void)hipFree(c->geoms[g].tab_up.mem); }
   if (c->d_geom_classes) (void)hipFree(c->d_geom_classes);
   if (c->d_geom_classes_vg) (void)hipFree(c->d_geom_classes_vg);
@@ -2067,6 +2105,28 @@ int bsx_gaussian_blur_surfaces_batch(bsx_ctx* c, const bsx_blur_surface_item* it
   if (!rc) {
     const hipError_t e = launch_blur_surfaces(d_desc, c->d_blur_coef, spans, cols, s);
     if (e != hipSuccess) { report(c, c->ondebug, c->caller_ctx, "error: HIP %s while blurring a batch of surfaces\n", hipGetErrorString(e)); rc = BSX_EDEVICE; }
+  }
+  return ids_release(c, entry, s, rc);
+}
+
+// n NV12 surfaces, each of its own size and pitches, resized to BGR images of their own sizes in ONE launch: planned and checked on the host, the descriptors ordered by
+// destination size through the staging ring, the ragged grid's spans and the classes' sizes by value
+int bsx_resize_surfaces_batch(bsx_ctx* c, const bsx_resize_surface_item* items, int n, void* stream) {
+  if (!c) return BSX_EINVAL;
+  ResizeSurfacesPlan plan;
+  GeomSpans spans{};
+  ResizeDstSizes sizes{};
+  if (const int rc = resize_surfaces_check(c, "bsx_resize_surfaces_batch", items, n, &plan, &spans, &sizes)) return rc;
+  if (n == 0) return BSX_OK;
+  DeviceGuard guard(c->device);
+  hipStream_t s = pick(c, stream);
+  int entry = 0;
+  if (const int rc = ring_acquire(c, &entry)) return rc;
+  const ResizeSurfDesc* d_desc = nullptr;
+  int rc = resize_surfaces_stage(c, items, n, plan, s, entry, &d_desc);
+  if (!rc) {
+    const hipError_t e = launch_resize_surfaces(d_desc, spans, sizes, s);
+    if (e != hipSuccess) { report(c, c->ondebug, c->caller_ctx, "error: HIP %s while resizing a batch of surfaces\n", hipGetErrorString(e)); rc = BSX_EDEVICE; }
   }
   return ids_release(c, entry, s, rc);
 }

@@ -323,6 +323,24 @@ hipError_t launch_blur_batch(const BlurDesc* desc, const GaussCoef* coef, const 
 struct alignas(16) BlurSurfDesc { const uint8_t* y; const uint8_t* uv; uint8_t* dst; int pitch_y, pitch_uv; int w, h, ksize; unsigned flags; };
 static_assert(sizeof(BlurSurfDesc) == 48, "three 16-byte uniform loads per workgroup");
 hipError_t launch_blur_surfaces(const BlurSurfDesc* desc, const GaussCoef* coef, const GeomSpans& spans, const BlurTileCols& cols, hipStream_t s);
+// launch_resize_bgr_batch for NV12 surfaces, every position with an output size of its own (bsx_resize_surfaces_batch): position i reads desc[i] (a DEVICE array ORDERED
+// BY DESTINATION SIZE, five 16-byte uniform loads per workgroup) — its Y plane ([sh] rows of pitch_y bytes) and interleaved UV plane ([sh / 2] rows of pitch_uv
+// bytes; both planes 4-byte aligned, the pitches multiples of 4 and >= sw, sw and sh even, every plane below 2^31 bytes: offsets into a plane are 32-bit), its
+// destination (dw x dh BGR of its class, dw * dh * 3 < 2^31, any alignment: a 4-byte aligned one with dw % 4 == 0 is stored as dwords) and the table of (sw x sh ->
+// dw x dh), whose mode may differ from one descriptor to the next.  spans: the ragged grid over destination-size classes, per[g] = resize_surf_blocks of the class;
+// sizes: the classes' (dw, dh), by value next to the spans.  The integers of launch_nv12_to_bgr, then those of launch_resize_bgr; no load touches a byte at or past
+// sw of a row.
+struct alignas(16) ResizeSurfDesc {
+  const uint8_t* y; const uint8_t* uv;
+  uint8_t* dst; const int* xofs;
+  const short* xa; const int* yofs;                                       // ResizeTab's tables (null in modes 1 and 2)
+  const short* ya; int pitch_y, pitch_uv;
+  int sw, sh, mode, pad;
+};
+static_assert(sizeof(ResizeSurfDesc) == 80, "five 16-byte uniform loads per workgroup");
+struct ResizeDstSizes { int dw[kMaxGeoms], dh[kMaxGeoms]; };
+inline long resize_surf_blocks(int dw, int dh) { return (((long)dw + 3) / 4 * (long)dh + 255) / 256; }
+hipError_t launch_resize_surfaces(const ResizeSurfDesc* desc, const GeomSpans& spans, const ResizeDstSizes& sizes, hipStream_t s);
 // composite at the virtual camera's geometry: alpha blend → cv::flip (flags bits 1-2) → cv::resize to (tab.dw, tab.dh) → [YUYV pack (bit 0)] in one pass over
 // frames, background and the persistent masks (deepseg.cc:634-681).  `tab`: a linear table from the capture size (the 2x2 area mode expanded to one);
 // direct = !vcam_tile_fits(tab): every tap blended where it is read instead of the footprint staged in LDS.  yuyv_in: `frames` is YUYV 4:2:2

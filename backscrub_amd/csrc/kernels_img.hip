@@ -3120,4 +3120,176 @@ hipError_t launch_blur_surfaces(const BlurSurfDesc* desc, const GaussCoef* coef,
   return hipGetLastError();
 }
 
+// ---- bsx_resize_surfaces_batch: n NV12 surfaces, each of its own size and pitches, resized to BGR images of their OWN sizes in ONE launch -----------------------------
+// resize_bgr_batch_k's form over a ragged grid: the workgroup finds its destination-size class and its position from the spans (geom_span: compares on SGPRs), the
+// class's (dw, dh) from the kernel arguments, the position's ResizeSurfDesc by five uniform loads that stay in SGPRs.  A lane makes FOUR adjacent pixels of one
+// output row with sample_linear<3>'s integers; the copy stores the converted pixels themselves, the 2x2 area mean is the linear form on (2 dx, 2 dy) with
+// coefficients (1024, 1024) — ((b * ((p * a) >> 4)) >> 16 summed over the rows, + 2, >> 2 gives (p00 + p01 + p10 + p11 + 2) >> 2 exactly.  A tap is yuv_tap_to_bgr(Y | U << 8 | V << 16) as vcam_surf_frame_px makes it — the conversion clamps, so it comes before the fixed point.
+// Loads of one output pixel and source row, all bounded by sw and never by the pitch:
+//   * Y: the taps' columns sx and sx1 = sx + 1 are one 16-bit load; where the table clamps sx1 onto sx (the right edge) the 16 bits are those of columns
+//     max(sx - 1, 0) and the next one;
+//   * UV: one 32-bit load at column min(sx & ~1, sw - 4) — an even left column has both taps on one chroma pair, an odd one takes two adjacent pairs, U0 V0 U1 V1
+//     (sx + 2 <= sw - 1 there: sw is even); a surface 2 pixels wide has one pair, 16 bits;
+//   * the lower row's taps are the upper row's where the rows clamp onto one another, and its chroma words are the upper row's where both rows lie in one chroma row
+//     (an even upper row): nothing is loaded twice that the lane already holds.
+// Offsets into the planes and into dst are 32-bit from uniform bases: the host refuses a plane of 2^31 bytes or more and dw * dh * 3 >= 2^31
+// (resize_surfaces_plan.hpp).  No LDS: at a down-scale of 2 or more the taps of neighbouring outputs do not overlap.
+// A template of one instance in a namespace of its own at the end of the file, launched by the file's last launcher, for the reason given above mask_geoms_k: every
+// earlier kernel's text is what it was.
+namespace {
+struct ResizeSurfRegs { const uint8_t* y; const uint8_t* uv; uint8_t* dst; const int* xofs; const short* xa; const int* yofs; const short* ya; int py, puv, sw, sh, mode; };
+__device__ __forceinline__ ResizeSurfRegs resize_surf_desc(const ResizeSurfDesc* __restrict__ desc, int n) {
+  const uint4* p = reinterpret_cast<const uint4*>(desc) + 5 * (size_t)n;
+  const uint4 a = p[0], b = p[1], c = p[2], e = p[3], f = p[4];
+  ResizeSurfRegs d;
+  d.y = as_global((const uint8_t*)(((uint64_t)a.y << 32) | a.x));
+  d.uv = as_global((const uint8_t*)(((uint64_t)a.w << 32) | a.z));
+  d.dst = as_global((uint8_t*)(((uint64_t)b.y << 32) | b.x));
+  d.xofs = as_global((const int*)(((uint64_t)b.w << 32) | b.z));
+  d.xa = as_global((const short*)(((uint64_t)c.y << 32) | c.x));
+  d.yofs = as_global((const int*)(((uint64_t)c.w << 32) | c.z));
+  d.ya = as_global((const short*)(((uint64_t)e.y << 32) | e.x));
+  d.py = (int)e.z; d.puv = (int)e.w;
+  d.sw = (int)f.x; d.sh = (int)f.y; d.mode = (int)f.z;
+  return d;
+}
+struct __attribute__((packed, aligned(1))) RsU16 { uint16_t v; };
+struct __attribute__((packed, aligned(2))) RsU32 { uint32_t v; };
+// Y of the taps at columns sx and (two ? sx + 1 : sx) of the row at byte offset `row`: Y0 | Y1 << 8
+__device__ __forceinline__ uint32_t resize_surf_luma2(const ResizeSurfRegs& d, unsigned row, int sx, bool two) {
+  const int xb = two ? sx : max(sx - 1, 0);
+  const uint32_t w = reinterpret_cast<const RsU16*>(d.y + (row + (unsigned)xb))->v;
+  const uint32_t y0 = sx != xb ? w >> 8 : w & 255u;
+  return y0 | ((two ? w >> 8 : y0) << 8);
+}
+// the chroma pairs of the same two taps, of the chroma row at byte offset `row`: U0 | V0 << 8 | U1 << 16 | V1 << 24
+__device__ __forceinline__ uint32_t resize_surf_chroma2(const ResizeSurfRegs& d, unsigned row, int sx, bool two) {
+  const int e = sx & ~1;
+  if (d.sw < 4) {                                                     // (uniform) sw == 2: the row's one pair
+    const uint32_t c = *reinterpret_cast<const uint16_t*>(d.uv + row);
+    return c | (c << 16);
+  }
+  const int cb = min(e, d.sw - 4);
+  const uint32_t w = reinterpret_cast<const RsU32*>(d.uv + (row + (unsigned)cb))->v;
+  const uint32_t c0 = e != cb ? w >> 16 : w & 0xffffu;
+  return c0 | ((two && (sx & 1) ? w >> 16 : c0) << 16);
+}
+
+// one lane's group of the copy (sw == dw, sh == dh): nothing to interpolate, so one conversion per pixel instead of four — the group's pixels are one Y dword and one
+// UV dword (U0 V0 U1 V1: x is a multiple of 4, rows and planes are dword aligned), converted as yuyv4_to_bgr3 converts two YUYV words; a row's last group where
+// sw % 4 == 2 is two pixels of one chroma pair, 16 bits of each plane
+__device__ __forceinline__ void resize_surf_copy(const ResizeSurfRegs& d, int dw, int x, int dy) {
+  uint8_t* const o = d.dst + (unsigned)(dy * dw + x) * 3u;
+  const unsigned yo = (unsigned)(dy * d.py) + (unsigned)x, co = (unsigned)((dy >> 1) * d.puv) + (unsigned)x;
+  if (x + 4 > dw) {
+    const uint32_t yw = *reinterpret_cast<const uint16_t*>(d.y + yo), cw = *reinterpret_cast<const uint16_t*>(d.uv + co);
+    const uint32_t p0 = yuv_tap_to_bgr((yw & 255u) | (cw << 8)), p1 = yuv_tap_to_bgr((yw >> 8) | (cw << 8));
+    o[0] = (uint8_t)p0; o[1] = (uint8_t)(p0 >> 8); o[2] = (uint8_t)(p0 >> 16);
+    o[3] = (uint8_t)p1; o[4] = (uint8_t)(p1 >> 8); o[5] = (uint8_t)(p1 >> 16);
+    return;
+  }
+  const uint32_t yw = *reinterpret_cast<const uint32_t*>(d.y + yo), cw = *reinterpret_cast<const uint32_t*>(d.uv + co);
+  uint32_t w[3];
+  yuyv4_to_bgr3((yw & 255u) | ((cw & 255u) << 8) | ((yw & 0xff00u) << 8) | ((cw & 0xff00u) << 16),
+                ((yw >> 16) & 255u) | ((cw >> 8) & 0xff00u) | ((yw >> 8) & 0xff0000u) | (cw & 0xff000000u), w);
+  if ((dw & 3) == 0 && ((uintptr_t)d.dst & 3) == 0) {                 // (uniform)
+    uint32_t* const ow = reinterpret_cast<uint32_t*>(o);
+    ow[0] = w[0]; ow[1] = w[1]; ow[2] = w[2];
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < 12; i++) o[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
+}
+// one lane's group: output pixels x .. x + 3 of row dy of a dw-wide destination.  TAB: the table's taps and coefficients (mode 0); else the 2x2 area mean as the
+// linear form described above.  An instance each instead of a mode test per pixel: with the test inside the unrolled loop the compiler (ROCm 7.2, clang 22) left the
+// coefficients of pixels 1 .. 3 of the area mode unset.
+template <bool TAB>
+__device__ __forceinline__ void resize_surf_group(const ResizeSurfRegs& d, int dw, int x, int dy) {
+  int sy0, sy1, b0, b1;
+  if constexpr (TAB) {
+    const int sy = d.yofs[dy];
+    sy0 = min(max(sy, 0), d.sh - 1); sy1 = min(max(sy + 1, 0), d.sh - 1);
+    b0 = d.ya[2 * dy]; b1 = d.ya[2 * dy + 1];
+  } else {
+    sy0 = 2 * dy; sy1 = sy0 + 1;
+    b0 = b1 = 1024;
+  }
+  int sx[4], a0[4], a1[4];
+  bool two[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int dx = min(x + k, dw - 1);                                // (a row's last group repeats its last pixel; the stores below leave the repeats out)
+    if constexpr (TAB) { sx[k] = d.xofs[dx]; two[k] = sx[k] + 1 < d.sw; a0[k] = d.xa[2 * dx]; a1[k] = d.xa[2 * dx + 1]; }
+    else { sx[k] = 2 * dx; two[k] = true; a0[k] = a1[k] = 1024; }
+  }
+  uint32_t yw0[4], cw0[4], yw1[4], cw1[4];
+  const unsigned yr0 = (unsigned)(sy0 * d.py), cr0 = (unsigned)((sy0 >> 1) * d.puv);
+#pragma unroll
+  for (int k = 0; k < 4; k++) { yw0[k] = resize_surf_luma2(d, yr0, sx[k], two[k]); cw0[k] = resize_surf_chroma2(d, cr0, sx[k], two[k]); }
+#pragma unroll
+  for (int k = 0; k < 4; k++) { yw1[k] = yw0[k]; cw1[k] = cw0[k]; }
+  if (sy1 != sy0) {
+    const unsigned yr1 = (unsigned)(sy1 * d.py);
+#pragma unroll
+    for (int k = 0; k < 4; k++) yw1[k] = resize_surf_luma2(d, yr1, sx[k], two[k]);
+    if ((sy1 >> 1) != (sy0 >> 1)) {
+      const unsigned cr1 = (unsigned)((sy1 >> 1) * d.puv);
+#pragma unroll
+      for (int k = 0; k < 4; k++) cw1[k] = resize_surf_chroma2(d, cr1, sx[k], two[k]);
+    }
+  }
+  int v[12];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const uint32_t t00 = yuv_tap_to_bgr((yw0[k] & 255u) | ((cw0[k] & 0xffffu) << 8)), t01 = yuv_tap_to_bgr((yw0[k] >> 8) | ((cw0[k] >> 16) << 8));
+    const uint32_t t10 = yuv_tap_to_bgr((yw1[k] & 255u) | ((cw1[k] & 0xffffu) << 8)), t11 = yuv_tap_to_bgr((yw1[k] >> 8) | ((cw1[k] >> 16) << 8));
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      const int h0 = (int)((t00 >> (8 * c)) & 255u) * a0[k] + (int)((t01 >> (8 * c)) & 255u) * a1[k];
+      const int h1 = (int)((t10 >> (8 * c)) & 255u) * a0[k] + (int)((t11 >> (8 * c)) & 255u) * a1[k];
+      v[3 * k + c] = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
+    }
+  }
+  uint8_t* const o = d.dst + (unsigned)(dy * dw + x) * 3u;
+  if ((dw & 3) == 0 && ((uintptr_t)d.dst & 3) == 0) {                 // (uniform: the class's width, the descriptor's pointer)
+    uint32_t w[3];
+#pragma unroll
+    for (int j = 0; j < 3; j++) w[j] = (uint32_t)v[4 * j] | ((uint32_t)v[4 * j + 1] << 8) | ((uint32_t)v[4 * j + 2] << 16) | ((uint32_t)v[4 * j + 3] << 24);
+    uint32_t* const ow = reinterpret_cast<uint32_t*>(o);
+    ow[0] = w[0]; ow[1] = w[1]; ow[2] = w[2];
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    if (x + k >= dw) break;
+    o[3 * k] = (uint8_t)v[3 * k]; o[3 * k + 1] = (uint8_t)v[3 * k + 1]; o[3 * k + 2] = (uint8_t)v[3 * k + 2];
+  }
+}
+
+template <int = 0>
+__global__ __launch_bounds__(kThreads) void resize_surfaces_k(const ResizeSurfDesc* __restrict__ desc, GeomSpans sp, ResizeDstSizes sz) {
+  int g, w0, p0, p1, per;
+  geom_span(sp, (int)blockIdx.x, &g, &w0, &p0, &p1, &per);
+  const unsigned local = blockIdx.x - (unsigned)w0, pl = local / (unsigned)per, blk = local - pl * (unsigned)per;
+  int dw = sz.dw[0], dh = sz.dh[0];                                   // (selected on SGPRs)
+#pragma unroll
+  for (int k = 1; k < kMaxGeoms; k++) if (g == k) { dw = sz.dw[k]; dh = sz.dh[k]; }
+  const unsigned gpr = ((unsigned)dw + 3u) / 4u, grp = blk * kThreads + threadIdx.x;
+  if (grp >= gpr * (unsigned)dh) return;
+  const ResizeSurfRegs d = resize_surf_desc(desc, p0 + (int)pl);
+  const int dy = (int)(grp / gpr), x = (int)(grp - (unsigned)dy * gpr) * 4;
+  if (d.mode == 0) resize_surf_group<true>(d, dw, x, dy);             // (uniform)
+  else if (d.mode == 1) resize_surf_copy(d, dw, x, dy);
+  else resize_surf_group<false>(d, dw, x, dy);
+}
+}  // namespace
+
+hipError_t launch_resize_surfaces(const ResizeSurfDesc* desc, const GeomSpans& spans, const ResizeDstSizes& sizes, hipStream_t s) {
+  if (!desc || spans.wg[kMaxGeoms] <= 0) return hipErrorInvalidValue;
+  for (int g = 0; g < kMaxGeoms; g++)
+    if (spans.per[g] > 0 && (sizes.dw[g] <= 0 || sizes.dh[g] <= 0 || (long)spans.per[g] != resize_surf_blocks(sizes.dw[g], sizes.dh[g]))) return hipErrorInvalidValue;
+  resize_surfaces_k<><<<dim3((unsigned)spans.wg[kMaxGeoms]), kThreads, 0, s>>>(desc, spans, sizes);
+  return hipGetLastError();
+}
+
 }  // namespace bsx

@@ -34,6 +34,7 @@
  *                          (set_input_frame → mask → alpha_blend), batched
  *   bsx_resize_bgr         grab_background() cv::resize   app/background.cc:178-194
  *   bsx_resize_bgr_batch   … of n images of their own sizes in one launch
+ *   bsx_resize_surfaces_batch  … of n decoder surfaces (NV12), each to its own size: a video background's grab  app/background.cc:181-190
  *   bsx_bgr_to_yuyv        convert_rgb_to_yuyv()          app/deepseg.cc:87-106
  *   bsx_yuyv_to_bgr        VideoCapture's YUYV->BGR       app/deepseg.cc:553,725 (cv::COLOR_YUV2BGR_YUYV)
  *   bsx_nv12_to_bgr        the same integers for a video decoder's NV12 surface (pitched Y and UV planes)
@@ -510,6 +511,42 @@ BSX_API int bsx_resize_bgr(bsx_ctx* ctx, const uint8_t* d_src, int sw, int sh, u
  *     non-positive size; a NULL d_src or d_dst; a d_dst that overlaps a source picture or another destination. */
 typedef struct bsx_resize_item { const uint8_t* d_src; int sw, sh; uint8_t* d_dst; } bsx_resize_item;
 BSX_API int bsx_resize_bgr_batch(bsx_ctx* ctx, const bsx_resize_item* items, int n, int dw, int dh, void* stream);
+
+/* Video backgrounds from a decoder: n NV12 surfaces, each of its own size and pitches, resized to BGR images that each have their OWN size, in ONE kernel launch —
+ * grab_background() of a video source (app/background.cc:181-190: cv::resize(raw, out, Size(width, height)) on every grab) where the frames of the background video
+ * come from a hardware decoder.  What the call writes is what a `setting.d_bg` takes: a tick with video backgrounds is this call followed by
+ * bsx_step_batch_surfaces (or a _geoms step).  The decoder's pool stays where it is (no two surfaces need be adjacent).
+ *   - d_dst of item i is byte-identical to bsx_nv12_to_bgr(d_y, pitch_y, d_uv, pitch_uv, sw, sh, 1, tmp) followed by bsx_resize_bgr(tmp, sw, sh, d_dst, dw, dh, 1), in
+ *     all three modes of the resize: proper INTER_LINEAR; the copy, where sw == dw && sh == dh; the 2x2 area mean, where both scales are exactly 2.  The surface's
+ *     BGR frame is the one bsx_step_batch_surfaces defines: pixel (x, y) takes Y[y][x] and the pair UV[y >> 1][x & ~1 ..], with the integers of bsx_yuyv_to_bgr.
+ *     The conversion clamps, so every tap is converted first and the resize's fixed point runs on BGR taps.  No BGR copy of the surface exists anywhere.  Bytes
+ *     [sw, pitch) of a row are never read, and nothing is read beyond the last row;
+ *   - the whole call is one launch, whatever the mix of source sizes, pitches and destination sizes; it takes at most BSX_MAX_GEOMS distinct (dw, dh) pairs (the
+ *     grid is ragged over destination sizes: the positions are ordered by destination size on the host, stably) and any number of distinct source sizes: the table
+ *     of each (sw, sh, dw, dh) comes from the cache bsx_resize_bgr fills, uploaded when it is first used;
+ *   - items is a HOST array, read before the call returns; the descriptors reach the device through the staging ring of bsx_step_batch_streams (no host
+ *     synchronisation unless the caller runs a ring's length ahead of the GPU);
+ *   - n <= n_streams of the context; n == 0 returns 0 and enqueues nothing; the same surface may appear in several items (one video serves cameras of two sizes);
+ *     works on every kind of context and asks nothing of its classes;
+ *   - d_dst takes any alignment (a 4-byte aligned one with dw % 4 == 0 is stored as dwords; the bytes are the same);
+ *   - BSX_EINVAL before anything is enqueued, with a bsx_last_error text naming items[i] and the offending value, for: n < 0 or n > n_streams; items NULL with
+ *     n > 0; a NULL d_y, d_uv or d_dst; a plane that is not 4-byte aligned; a pitch below sw or not a multiple of 4; a non-positive or odd sw or sh; a non-positive
+ *     dw or dh; any bit in flags, or a non-zero reserved; a plane of 2 GiB or more, or dw * dh * 3 >= 2^31; a ninth distinct destination size; a d_dst (dw * dh * 3
+ *     bytes) that overlaps any item's Y or UV plane (its own included; a plane extends from its first byte to byte sw of its last row) or another destination.
+ *     BSX_EDEVICE for a grid of 2^31 workgroups or more.  A refused call changes nothing.
+ * Out of scope: BGR sources in this call (bsx_resize_bgr_batch serves them), an NV12 or YUYV destination, a bsx_background object that holds surfaces, reading an
+ * NV12 background inside the step's own resize pass, and the formats P010 and I420. */
+typedef struct bsx_resize_surface_item {
+  const uint8_t* d_y;    /* [sh] rows of pitch_y bytes, 4-byte aligned */
+  const uint8_t* d_uv;   /* [sh / 2] rows of pitch_uv bytes (U, V interleaved), 4-byte aligned */
+  uint8_t* d_dst;        /* [dh][dw][3] BGR, any alignment */
+  int pitch_y, pitch_uv; /* multiples of 4, >= sw */
+  int sw, sh;            /* the surface: even, positive */
+  int dw, dh;            /* this item's own output size: positive, any parity */
+  unsigned flags;        /* 0 */
+  int reserved;          /* 0 */
+} bsx_resize_surface_item;   /* 56 bytes */
+BSX_API int bsx_resize_surfaces_batch(bsx_ctx* ctx, const bsx_resize_surface_item* items, int n, void* stream);
 
 /* BGR u8 [n][h][w][3] -> YUYV 4:2:2 [n][h][w][2] exactly as convert_rgb_to_yuyv (byte order Y0 V Y1 U). */
 BSX_API int bsx_bgr_to_yuyv(bsx_ctx* ctx, const uint8_t* d_bgr, uint8_t* d_yuyv, int w, int h, int n, void* stream);
