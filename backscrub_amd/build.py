@@ -21,7 +21,7 @@ LIB = os.path.join(HERE, "libbsx.so")
 OBJ_DBG = os.path.join(CSRC, "build_dbg")
 LIB_DBG = os.path.join(HERE, "libbsx_dbg.so")
 SOURCES = ["tflite_model.cpp", "plan.cpp", "gen_mid.cpp", "gen_seg.cpp", "rtc.cpp", "specialised.cpp", "media.cpp", "jpeg.cpp", "live.cpp", "kernels_nn.hip", "kernels_img.hip", "kernels_frame.hip", "kernels_seg.hip", "bsx_api.hip"]
-HEADERS = ["mid_prelude.hip", "vcam_tile.inc", "prep_tile.inc", "tile_class.inc", "mask_tile.inc", "seg_gate.inc", "seg_gated_row.inc", "seg_k3_rows.inc", "debug_switches.hpp", "gen_mid.hpp", "gen_seg.hpp", "rtc.hpp", "specialised.hpp", "media.hpp", "refusal.hpp", "vcam_outs_plan.hpp", "vcam_nv12_plan.hpp", "geoms_request.hpp", "vcam_surface_plan.hpp", "blur_surfaces_plan.hpp", "resize_surfaces_plan.hpp", "tflite_model.hpp", "plan.hpp", "kernels.hpp", "frame_program.hpp", "segments.hpp", "mfma_tile.hpp", "roctx_ranges.hpp", os.path.join("..", "..", "include", "bsx.h")]
+HEADERS = ["mid_prelude.hip", "vcam_tile.inc", "prep_tile.inc", "tile_class.inc", "mask_tile.inc", "seg_gate.inc", "seg_gated_row.inc", "seg_k3_rows.inc", "debug_switches.hpp", "gen_mid.hpp", "gen_seg.hpp", "rtc.hpp", "specialised.hpp", "media.hpp", "refusal.hpp", "vcam_outs_plan.hpp", "vcam_nv12_plan.hpp", "span_overlap.hpp", "geoms_request.hpp", "vcam_surface_plan.hpp", "picture_batch_plan.hpp", "tflite_model.hpp", "plan.hpp", "kernels.hpp", "frame_program.hpp", "segments.hpp", "mfma_tile.hpp", "roctx_ranges.hpp", os.path.join("..", "..", "include", "bsx.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
          "-Wno-unused-result", "-fvisibility=hidden", "-fvisibility-inlines-hidden"]      # only the BSX_API entry points of include/bsx.h are exported

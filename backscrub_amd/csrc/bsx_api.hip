@@ -28,8 +28,7 @@
 #include "specialised.hpp"
 #include "tflite_model.hpp"
 #include "geoms_request.hpp"
-#include "blur_surfaces_plan.hpp"
-#include "resize_surfaces_plan.hpp"
+#include "picture_batch_plan.hpp"
 
 using namespace bsx;
 
@@ -187,24 +186,13 @@ struct bsx_ctx {
   struct MixBlur { int ksize, off, count; };
   std::vector<MixBlur> mix_blur;            // the staged call's blur groups: ksize, first index into the position list, count
   size_t mix_entry_bytes() const { return (size_t)n_streams * (sizeof(MixDesc) + sizeof(int)); }
-  // bsx_resize_bgr_batch: per ring entry (the same entries and events again) the call's n_streams ResizeBatchDesc (kernels.hpp), built in the pinned entry, copied
-  // to the device entry in one hipMemcpyAsync.  Allocated on the first batch call.
-  ResizeBatchDesc* h_rsz = nullptr;         // pinned [kIdRing][n_streams]
-  ResizeBatchDesc* d_rsz = nullptr;         // device, likewise
-  // bsx_gaussian_blur_bgr_batch: per ring entry (the same entries and events again) the call's n_streams BlurDesc (kernels.hpp), ordered by image size, built in the
-  // pinned entry, copied to the device entry in one hipMemcpyAsync; d_blur_coef: the coefficient records of every (ksize, staging path), uploaded by the first call.
-  BlurDesc* h_blur = nullptr;               // pinned [kIdRing][n_streams]
-  BlurDesc* d_blur = nullptr;               // device, likewise
-  GaussCoef* d_blur_coef = nullptr;         // device [blur_coef_table_bytes()]
-  // bsx_gaussian_blur_surfaces_batch: likewise, the call's n_streams BlurSurfDesc; the coefficient records are d_blur_coef (whichever of the two calls comes first
-  // uploads them).  Allocated on the first call.
-  BlurSurfDesc* h_blur_surf = nullptr;      // pinned [kIdRing][n_streams]
-  BlurSurfDesc* d_blur_surf = nullptr;      // device, likewise
-  // bsx_resize_surfaces_batch: likewise, the call's n_streams ResizeSurfDesc, ordered by destination size.  Allocated on the first call.
-  ResizeSurfDesc* h_rsz_surf = nullptr;     // pinned [kIdRing][n_streams]
-  ResizeSurfDesc* d_rsz_surf = nullptr;     // device, likewise
-  using Span = bsx::Span;
-  std::vector<Span> rsz_spans;              // host scratch of the overlap check: the call's sources and destinations, sorted by address
+  // The n-picture image batches (bsx_resize_bgr_batch, bsx_gaussian_blur_bgr_batch, bsx_gaussian_blur_surfaces_batch, bsx_resize_surfaces_batch): per ring entry
+  // (the same entries and events again) the call's n_streams descriptors (kernels.hpp: ResizeBatchDesc, BlurDesc, BlurSurfDesc, ResizeSurfDesc) in the plan's order,
+  // built in the pinned entry, copied to the device entry in one hipMemcpyAsync.  A ring is allocated on its call's first use (picture_batch_run).
+  struct DescRing { void* h = nullptr; void* d = nullptr; };      // pinned [kIdRing][n_streams] descriptors of the call's type; device, likewise
+  DescRing rsz_ring, blur_ring, blur_surf_ring, rsz_surf_ring;
+  GaussCoef* d_blur_coef = nullptr;         // device [blur_coef_table_bytes()]: the coefficient records of every (ksize, staging path), uploaded by the first call of either blur batch
+  PictureBatchPlan pic_plan;                // host scratch: the plan of the call (picture_batch_plan.hpp)
   // Geometry classes (bsx_new_geoms): class 0 IS the context's own geometry — width, height, roi, in_roi, both tables and the first bytes of d_masks above — so every
   // one-geometry path reads what it always read; classes 1.. add their own ROIs and tables and their own slice of the ONE d_masks allocation.  Streams are numbered
   // class after class.  Model-side state (ofinal by slot, arena, network buffers, weights, kernels) exists once.  bsx_step_batch_geoms advances streams of any mix of
@@ -1057,6 +1045,7 @@ int step_call(bsx_ctx* c, const char* fn, Entry kind, StepReq r, const int* host
 
 // ---- bsx_resize_bgr / bsx_resize_bgr_batch: the resize tables of the backgrounds, one per distinct (sw, sh, dw, dh), uploaded on first use ---------------------
 int bg_tab(bsx_ctx* c, int sw, int sh, int dw, int dh, const DevResizeTab** out) {
+  if (const DevResizeTab* t = *out) { if (t->tab.sw == sw && t->tab.sh == sh && t->tab.dw == dw && t->tab.dh == dh) return BSX_OK; }      // (a run of equal sizes looks its table up once)
   auto key = std::make_pair(std::make_pair(sw, sh), std::make_pair(dw, dh));
   auto it = c->bg_tabs.find(key);
   if (it == c->bg_tabs.end()) {
@@ -1068,100 +1057,8 @@ int bg_tab(bsx_ctx* c, int sw, int sh, int dw, int dh, const DevResizeTab** out)
   *out = &it->second;
   return BSX_OK;
 }
-// host-side validation of items[0..n): nothing is enqueued before it passes.  A destination may overlap neither a source picture nor another destination (the
-// launch reads and writes them in no order); sources may overlap each other — two entries may name one picture.  Sorted by address, one sweep.
-int resize_batch_check(bsx_ctx* c, const char* fn, const bsx_resize_item* items, int n, int dw, int dh) {
-  if (n < 0) return refuse(c, fn, "n = %d is negative", n);
-  if (n > c->n_streams) return refuse(c, fn, "n = %d exceeds the context's %d streams", n, c->n_streams);
-  if (n == 0) return BSX_OK;
-  if (!items) return refuse(c, fn, "items is NULL");
-  if (dw <= 0 || dh <= 0) return refuse(c, fn, "output size %d x %d is not positive", dw, dh);
-  const size_t out_bytes = (size_t)dw * dh * 3;
-  std::vector<bsx_ctx::Span>& sp = c->rsz_spans;
-  sp.clear();
-  for (int i = 0; i < n; i++) {
-    const bsx_resize_item& it = items[i];
-    if (!it.d_src) return refuse(c, fn, "items[%d]: d_src is NULL", i);
-    if (!it.d_dst) return refuse(c, fn, "items[%d]: d_dst is NULL", i);
-    if (it.sw <= 0 || it.sh <= 0) return refuse(c, fn, "items[%d]: source size %d x %d is not positive", i, it.sw, it.sh);
-    sp.push_back({(uintptr_t)it.d_src, (uintptr_t)it.d_src + (size_t)it.sw * it.sh * 3, i, false});
-    sp.push_back({(uintptr_t)it.d_dst, (uintptr_t)it.d_dst + out_bytes, i, true});
-  }
-  const bsx_ctx::Span* d = nullptr;
-  const bsx_ctx::Span* o = nullptr;
-  if (spans_overlap(sp, &d, &o))
-    return refuse(c, fn, "items[%d]: d_dst %p overlaps the %s of items[%d] (%p)", d->item, (const void*)d->begin, o->dst ? "destination" : "source picture", o->item,
-                  (const void*)o->begin);
-  return BSX_OK;
-}
-// items[0..n) as ResizeBatchDesc into ring entry k (pinned), one copy to the device entry on s
-int resize_batch_stage(bsx_ctx* c, const bsx_resize_item* items, int n, int dw, int dh, hipStream_t s, int k, const ResizeBatchDesc** d_desc) {
-  const size_t N = (size_t)c->n_streams;
-  if (!c->h_rsz) BSX_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_rsz), bsx_ctx::kIdRing * N * sizeof(ResizeBatchDesc), hipHostMallocDefault));
-  if (!c->d_rsz) BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_rsz), bsx_ctx::kIdRing * N * sizeof(ResizeBatchDesc)));
-  ResizeBatchDesc* hd = c->h_rsz + (size_t)k * N;
-  const DevResizeTab* t = nullptr;
-  for (int i = 0; i < n; i++) {
-    if (!t || t->tab.sw != items[i].sw || t->tab.sh != items[i].sh)           // (a run of equal sizes looks its table up once)
-      if (const int rc = bg_tab(c, items[i].sw, items[i].sh, dw, dh, &t)) return rc;
-    hd[i] = ResizeBatchDesc{items[i].d_src, items[i].d_dst, t->tab.xofs, t->tab.xa, t->tab.yofs, t->tab.ya, t->tab.sw, t->tab.sh, t->tab.mode, 0};
-  }
-  BSX_HIP(c, hipMemcpyAsync(c->d_rsz + (size_t)k * N, hd, (size_t)n * sizeof(ResizeBatchDesc), hipMemcpyHostToDevice, s));
-  *d_desc = c->d_rsz + (size_t)k * N;
-  return BSX_OK;
-}
 
-// ---- bsx_gaussian_blur_bgr_batch: n images of their own sizes, blur sizes and pixel formats in ONE launch -----------------------------------------------------------
-// Host-side validation of items[0..n): nothing is enqueued before it passes.  Leaves the size class of every item in c->geo_ids (the distinct (w, h) pairs numbered
-// in the order of their first item) and the ragged grid in *spans: per class its positions and its 64 x 16 tiles.
-int blur_batch_check(bsx_ctx* c, const char* fn, const bsx_blur_item* items, int n, GeomSpans* spans, BlurTileCols* cols) {
-  if (n < 0) return refuse(c, fn, "n = %d is negative", n);
-  if (n > c->n_streams) return refuse(c, fn, "n = %d exceeds the context's %d streams", n, c->n_streams);
-  if (n == 0) return BSX_OK;
-  if (!items) return refuse(c, fn, "items is NULL");
-  std::vector<bsx_ctx::Span>& sp = c->rsz_spans;
-  sp.clear();
-  c->geo_ids.resize((size_t)n);
-  int cw[kMaxGeoms], ch[kMaxGeoms], count[kMaxGeoms] = {0}, G = 0;
-  for (int i = 0; i < n; i++) {
-    const bsx_blur_item& it = items[i];
-    if (it.w <= 0 || it.h <= 0) return refuse(c, fn, "items[%d]: size %d x %d is not positive", i, it.w, it.h);
-    if (it.ksize < 1 || it.ksize > 31 || !(it.ksize & 1)) return refuse(c, fn, "items[%d]: ksize %d is not an odd number of 1 .. 31", i, it.ksize);
-    if (!it.d_src) return refuse(c, fn, "items[%d]: d_src is NULL", i);
-    if (!it.d_dst) return refuse(c, fn, "items[%d]: d_dst is NULL", i);
-    if (it.flags & ~BSX_STREAM_YUYV_IN) return refuse(c, fn, "items[%d]: flags 0x%x has bits outside yuyv-in (0x%x)", i, it.flags, BSX_STREAM_YUYV_IN);
-    const bool yin = (it.flags & BSX_STREAM_YUYV_IN) != 0;
-    if (yin && (it.w & 1)) return refuse(c, fn, "items[%d]: a YUYV source needs an even width (w = %d)", i, it.w);
-    if (yin && ((uintptr_t)it.d_src & 3)) return refuse(c, fn, "items[%d]: YUYV d_src %p is not 4-byte aligned", i, (const void*)it.d_src);
-    const size_t px = (size_t)it.w * (size_t)it.h;
-    if (px * 3 > 0x7fffffffu) return refuse(c, fn, "items[%d]: size %d x %d is beyond the kernel's 32-bit offsets (w * h * 3 < 2^31)", i, it.w, it.h);
-    int g = 0;
-    while (g < G && (cw[g] != it.w || ch[g] != it.h)) g++;
-    if (g == G) {
-      if (G == kMaxGeoms) return refuse(c, fn, "items[%d]: %d x %d is distinct size %d of the call (at most %d)", i, it.w, it.h, G + 1, BSX_MAX_GEOMS);
-      cw[G] = it.w; ch[G] = it.h; G++;
-    }
-    c->geo_ids[(size_t)i] = g; count[g]++;
-    sp.push_back({(uintptr_t)it.d_src, (uintptr_t)it.d_src + px * (yin ? 2 : 3), i, false});      // the source's real extent
-    sp.push_back({(uintptr_t)it.d_dst, (uintptr_t)it.d_dst + px * 3, i, true});
-  }
-  const bsx_ctx::Span* d = nullptr;
-  const bsx_ctx::Span* o = nullptr;
-  if (spans_overlap(sp, &d, &o))
-    return refuse(c, fn, "items[%d]: d_dst %p overlaps the %s of items[%d] (%p)", d->item, (const void*)d->begin, o->dst ? "destination" : "source", o->item,
-                  (const void*)o->begin);
-  *spans = GeomSpans{};
-  *cols = BlurTileCols{};
-  for (int g = 0; g < kMaxGeoms; g++) {
-    const long per = g < G ? blur_tiles(cw[g], ch[g]) : 0, cnt = g < G ? count[g] : 0;
-    if ((long)spans->wg[g] + cnt * per >= (1l << 31)) return too_many_workgroups(c, fn);
-    spans->pos[g + 1] = spans->pos[g] + (int)cnt;
-    spans->wg[g + 1] = spans->wg[g] + (int)(cnt * per);
-    spans->per[g] = (int)per;
-    cols->ntx[g] = g < G ? blur_tile_cols(cw[g]) : 0;
-  }
-  return BSX_OK;
-}
+// ---- the n-picture image batches: n pictures of their own sizes in ONE launch ----------------------------------------------------------------------------------------
 // the context's ONE device copy of blur_coef_table, made by the first call of either blur batch
 int blur_coef_upload(bsx_ctx* c) {
   if (c->d_blur_coef) return BSX_OK;
@@ -1174,101 +1071,44 @@ int blur_coef_upload(bsx_ctx* c) {
   c->d_blur_coef = dev;
   return BSX_OK;
 }
-// items[0..n) as BlurDesc, ordered by size class (a counting sort: stable, so a class keeps the caller's order), into ring entry k (pinned), one copy to the device
-// entry on s; the coefficient table on the first call
-int blur_batch_stage(bsx_ctx* c, const bsx_blur_item* items, int n, const GeomSpans& spans, hipStream_t s, int k, const BlurDesc** d_desc) {
+// a plan's ragged grid as the launchers take it by value
+struct PictureGrid { GeomSpans spans{}; BlurTileCols cols{}; ResizeDstSizes sizes{}; };
+PictureGrid picture_grid(const PictureBatchPlan& p) {
+  static_assert(kPbMaxSizes == kMaxGeoms, "the plan's arrays are GeomSpans', BlurTileCols' and ResizeDstSizes'");
+  PictureGrid g;
+  for (int k = 0; k <= kMaxGeoms; k++) { g.spans.pos[k] = p.pos[k]; g.spans.wg[k] = p.wg[k]; }
+  for (int k = 0; k < kMaxGeoms; k++) { g.spans.per[k] = p.per[k]; g.cols.ntx[k] = p.ntx[k]; g.sizes.dw[k] = p.sizes[k][0]; g.sizes.dh[k] = p.sizes[k][1]; }
+  return g;
+}
+// Ring entry k of a planned call: the ring and, with `coef`, the blur coefficients on first use; fill(i, &desc) for the items in the plan's order into the pinned
+// entry (a resize uploads a table it meets for the first time); ONE copy to the device entry on s; launch(descriptors, grid, s)
+template <class Desc, class Fill, class Launch>
+int picture_batch_run(bsx_ctx* c, bsx_ctx::DescRing* ring, bool coef, const char* doing, hipStream_t s, int k, Fill fill, Launch launch) {
   const size_t N = (size_t)c->n_streams;
-  if (!c->h_blur) BSX_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_blur), bsx_ctx::kIdRing * N * sizeof(BlurDesc), hipHostMallocDefault));
-  if (!c->d_blur) BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_blur), bsx_ctx::kIdRing * N * sizeof(BlurDesc)));
-  if (const int rc = blur_coef_upload(c)) return rc;
-  int next[kMaxGeoms];
-  for (int g = 0; g < kMaxGeoms; g++) next[g] = spans.pos[g];
-  BlurDesc* hd = c->h_blur + (size_t)k * N;
-  for (int i = 0; i < n; i++) {
-    const bsx_blur_item& it = items[i];
-    hd[next[c->geo_ids[(size_t)i]]++] = BlurDesc{it.d_src, it.d_dst, it.w, it.h, it.ksize, it.flags & kGeomYuyvIn};
-  }
-  BSX_HIP(c, hipMemcpyAsync(c->d_blur + (size_t)k * N, hd, (size_t)n * sizeof(BlurDesc), hipMemcpyHostToDevice, s));
-  *d_desc = c->d_blur + (size_t)k * N;
+  if (!ring->h) BSX_HIP(c, hipHostMalloc(&ring->h, bsx_ctx::kIdRing * N * sizeof(Desc), hipHostMallocDefault));
+  if (!ring->d) BSX_HIP(c, hipMalloc(&ring->d, bsx_ctx::kIdRing * N * sizeof(Desc)));
+  if (coef) { if (const int rc = blur_coef_upload(c)) return rc; }
+  Desc* const hd = static_cast<Desc*>(ring->h) + (size_t)k * N;
+  Desc* const dd = static_cast<Desc*>(ring->d) + (size_t)k * N;
+  const std::vector<int>& order = c->pic_plan.order;
+  for (size_t q = 0; q < order.size(); q++) { if (const int rc = fill(order[q], &hd[q])) return rc; }
+  BSX_HIP(c, hipMemcpyAsync(dd, hd, order.size() * sizeof(Desc), hipMemcpyHostToDevice, s));
+  const hipError_t e = launch(dd, picture_grid(c->pic_plan), s);
+  if (e != hipSuccess) { report(c, c->ondebug, c->caller_ctx, "error: HIP %s while %s\n", hipGetErrorString(e), doing); return BSX_EDEVICE; }
   return BSX_OK;
 }
-
-// ---- bsx_gaussian_blur_surfaces_batch: n NV12 surfaces of their own sizes, pitches and blur sizes in ONE launch ------------------------------------------------------
-// Host-side validation of items[0..n): nothing is enqueued before it passes.  The item rules, the size classes and the ragged grid are blur_surfaces_plan.hpp's; the
-// overlap sweep is done here, a plane judged on vcam_nv12_extent (a source span's `item` is 2 i for the Y plane of items[i], 2 i + 1 for its UV plane).
-int blur_surfaces_check(bsx_ctx* c, const char* fn, const bsx_blur_surface_item* items, int n, BlurSurfacesPlan* plan, GeomSpans* spans, BlurTileCols* cols) {
-  const int planned = blur_surfaces_plan(items, n, c->n_streams, plan);
-  if (planned == BlurSurfacesPlan::kRefused) return refuse(c, fn, "%s", plan->text);
-  if (planned == BlurSurfacesPlan::kTooLarge) return too_many_workgroups(c, fn);
-  std::vector<bsx_ctx::Span>& sp = c->rsz_spans;
-  sp.clear();
-  for (int i = 0; i < n; i++) {
-    const bsx_blur_surface_item& it = items[i];
-    sp.push_back({(uintptr_t)it.d_y, (uintptr_t)it.d_y + vcam_nv12_extent(it.pitch_y, it.h, it.w), 2 * i, false});
-    sp.push_back({(uintptr_t)it.d_uv, (uintptr_t)it.d_uv + vcam_nv12_extent(it.pitch_uv, it.h / 2, it.w), 2 * i + 1, false});
-    sp.push_back({(uintptr_t)it.d_dst, (uintptr_t)it.d_dst + (size_t)it.w * (size_t)it.h * 3, i, true});
-  }
-  const bsx_ctx::Span* d = nullptr;
-  const bsx_ctx::Span* o = nullptr;
-  if (spans_overlap(sp, &d, &o))
-    return refuse(c, fn, "items[%d]: d_dst %p overlaps the %s of items[%d] (%p)", d->item, (const void*)d->begin, o->dst ? "destination" : (o->item & 1) ? "UV plane" : "Y plane",
-                  o->dst ? o->item : o->item >> 1, (const void*)o->begin);
-  *spans = GeomSpans{};
-  *cols = BlurTileCols{};
-  static_assert(kBsMaxSizes == kMaxGeoms, "the plan's arrays are GeomSpans' and BlurTileCols'");
-  for (int g = 0; g <= kMaxGeoms; g++) { spans->pos[g] = plan->pos[g]; spans->wg[g] = plan->wg[g]; }
-  for (int g = 0; g < kMaxGeoms; g++) { spans->per[g] = plan->per[g]; cols->ntx[g] = plan->ntx[g]; }
-  return BSX_OK;
-}
-// items[0..n) as BlurSurfDesc, ordered by size class (a counting sort on the plan's classes: stable), into ring entry k (pinned), one copy to the device entry on s;
-// the coefficient table on the first call of either blur batch
-int blur_surfaces_stage(bsx_ctx* c, const bsx_blur_surface_item* items, int n, const BlurSurfacesPlan& plan, hipStream_t s, int k, const BlurSurfDesc** d_desc) {
-  const size_t N = (size_t)c->n_streams;
-  if (!c->h_blur_surf) BSX_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_blur_surf), bsx_ctx::kIdRing * N * sizeof(BlurSurfDesc), hipHostMallocDefault));
-  if (!c->d_blur_surf) BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_blur_surf), bsx_ctx::kIdRing * N * sizeof(BlurSurfDesc)));
-  if (const int rc = blur_coef_upload(c)) return rc;
-  int next[kMaxGeoms];
-  for (int g = 0; g < kMaxGeoms; g++) next[g] = plan.pos[g];
-  BlurSurfDesc* hd = c->h_blur_surf + (size_t)k * N;
-  for (int i = 0; i < n; i++) {
-    const bsx_blur_surface_item& it = items[i];
-    hd[next[plan.cls[(size_t)i]]++] = BlurSurfDesc{it.d_y, it.d_uv, it.d_dst, it.pitch_y, it.pitch_uv, it.w, it.h, it.ksize, 0u};
-  }
-  BSX_HIP(c, hipMemcpyAsync(c->d_blur_surf + (size_t)k * N, hd, (size_t)n * sizeof(BlurSurfDesc), hipMemcpyHostToDevice, s));
-  *d_desc = c->d_blur_surf + (size_t)k * N;
-  return BSX_OK;
-}
-
-// ---- bsx_resize_surfaces_batch: n NV12 surfaces of their own sizes and pitches, each to an output size of its own, in ONE launch -----------------------------------
-// Every rule, the destination-size classes, the stable order and the ragged grid are resize_surfaces_plan.hpp's; here: the plan as the launcher's arguments.
-int resize_surfaces_check(bsx_ctx* c, const char* fn, const bsx_resize_surface_item* items, int n, ResizeSurfacesPlan* plan, GeomSpans* spans, ResizeDstSizes* sizes) {
-  const int planned = resize_surfaces_plan(items, n, c->n_streams, plan);
-  if (planned == ResizeSurfacesPlan::kRefused) return refuse(c, fn, "%s", plan->text);
-  if (planned == ResizeSurfacesPlan::kTooLarge) return too_many_workgroups(c, fn);
-  *spans = GeomSpans{};
-  *sizes = ResizeDstSizes{};
-  static_assert(kRsMaxSizes == kMaxGeoms, "the plan's arrays are GeomSpans' and ResizeDstSizes'");
-  for (int g = 0; g <= kMaxGeoms; g++) { spans->pos[g] = plan->pos[g]; spans->wg[g] = plan->wg[g]; }
-  for (int g = 0; g < kMaxGeoms; g++) { spans->per[g] = plan->per[g]; sizes->dw[g] = plan->sizes[g][0]; sizes->dh[g] = plan->sizes[g][1]; }
-  return BSX_OK;
-}
-// items[0..n) as ResizeSurfDesc in the plan's order into ring entry k (pinned), one copy to the device entry on s; the table of each (sw, sh, dw, dh) from bg_tabs,
-// uploaded on first use
-int resize_surfaces_stage(bsx_ctx* c, const bsx_resize_surface_item* items, int n, const ResizeSurfacesPlan& plan, hipStream_t s, int k, const ResizeSurfDesc** d_desc) {
-  const size_t N = (size_t)c->n_streams;
-  if (!c->h_rsz_surf) BSX_HIP(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_rsz_surf), bsx_ctx::kIdRing * N * sizeof(ResizeSurfDesc), hipHostMallocDefault));
-  if (!c->d_rsz_surf) BSX_HIP(c, hipMalloc(reinterpret_cast<void**>(&c->d_rsz_surf), bsx_ctx::kIdRing * N * sizeof(ResizeSurfDesc)));
-  ResizeSurfDesc* hd = c->h_rsz_surf + (size_t)k * N;
-  const DevResizeTab* t = nullptr;
-  for (int q = 0; q < n; q++) {
-    const bsx_resize_surface_item& it = items[plan.order[(size_t)q]];
-    if (!t || t->tab.sw != it.sw || t->tab.sh != it.sh || t->tab.dw != it.dw || t->tab.dh != it.dh)      // (a run of equal sizes looks its table up once)
-      if (const int rc = bg_tab(c, it.sw, it.sh, it.dw, it.dh, &t)) return rc;
-    hd[q] = ResizeSurfDesc{it.d_y, it.d_uv, it.d_dst, t->tab.xofs, t->tab.xa, t->tab.yofs, t->tab.ya, it.pitch_y, it.pitch_uv, it.sw, it.sh, t->tab.mode, 0};
-  }
-  BSX_HIP(c, hipMemcpyAsync(c->d_rsz_surf + (size_t)k * N, hd, (size_t)n * sizeof(ResizeSurfDesc), hipMemcpyHostToDevice, s));
-  *d_desc = c->d_rsz_surf + (size_t)k * N;
-  return BSX_OK;
+// The one path of the four entry points, their items planned into c->pic_plan (picture_batch_plan.hpp: nothing is enqueued before the plan passes): the plan's
+// result, the empty batch, then on the context's device a ring entry and the run.  The entry points only plan and name their ring, fill and launch.
+template <class Desc, class Fill, class Launch>
+int picture_batch_call(bsx_ctx* c, const char* fn, int planned, bsx_ctx::DescRing* ring, bool coef, const char* doing, void* stream, Fill fill, Launch launch) {
+  if (planned == PictureBatchPlan::kRefused) return refuse(c, fn, "%s", c->pic_plan.text);
+  if (planned == PictureBatchPlan::kTooLarge) return too_many_workgroups(c, fn);
+  if (c->pic_plan.order.empty()) return BSX_OK;
+  DeviceGuard guard(c->device);
+  hipStream_t s = pick(c, stream);
+  int entry = 0;
+  if (const int rc = ring_acquire(c, &entry)) return rc;
+  return ids_release(c, entry, s, picture_batch_run<Desc>(c, ring, coef, doing, s, entry, fill, launch));
 }
 
 // ---- bsx_step_batch_geoms: streams of any mix of geometry classes in ONE prep launch, ONE network pass, ONE tile-class and ONE tile launch ----------------------
@@ -1767,15 +1607,11 @@ void bsx_delete(bsx_ctx* c) {
   if (c->h_ids) (void)hipHostFree(c->h_ids);
   if (c->d_mix) (void)hipFree(c->d_mix);
   if (c->h_mix) (void)hipHostFree(c->h_mix);
-  if (c->d_rsz) (void)hipFree(c->d_rsz);
-  if (c->h_rsz) (void)hipHostFree(c->h_rsz);
-  if (c->d_blur) (void)hipFree(c->d_blur);
-  if (c->h_blur) (void)hipHostFree(c->h_blur);
+  for (bsx_ctx::DescRing* r : {&c->rsz_ring, &c->blur_ring, &c->blur_surf_ring, &c->rsz_surf_ring}) {
+    if (r->d) (void)hipFree(r->d);
+    if (r->h) (void)hipHostFree(r->h);
+  }
   if (c->d_blur_coef) (void)hipFree(c->d_blur_coef);
-  if (c->d_blur_surf) (void)hipFree(c->d_blur_surf);
-  if (c->h_blur_surf) (void)hipHostFree(c->h_blur_surf);
-  if (c->d_rsz_surf) (void)hipFree(c->d_rsz_surf);
-  if (c->h_rsz_surf) (void)hipHostFree(c->h_rsz_surf);
   for (size_t g = 1; g < c->geoms.size(); g++) { if (c->geoms[g].tab_down.mem) (void)hipFree(c->geoms[g].tab_down.mem); if (c->geoms[g].tab_up.mem) (void)hipFree(c->geoms[g].tab_up.mem); }
   if (c->d_geom_classes) (void)hipFree(c->d_geom_classes);
   if (c->d_geom_classes_vg) (void)hipFree(c->d_geom_classes_vg);
@@ -2037,19 +1873,16 @@ int bsx_resize_bgr(bsx_ctx* c, const uint8_t* d_src, int sw, int sh, uint8_t* d_
 // n images, each of its own size, to dw x dh in ONE launch: checked on the host, the descriptors through the staging ring, the tables from bg_tabs
 int bsx_resize_bgr_batch(bsx_ctx* c, const bsx_resize_item* items, int n, int dw, int dh, void* stream) {
   if (!c) return BSX_EINVAL;
-  if (const int rc = resize_batch_check(c, "bsx_resize_bgr_batch", items, n, dw, dh)) return rc;
-  if (n == 0) return BSX_OK;
-  DeviceGuard guard(c->device);
-  hipStream_t s = pick(c, stream);
-  int entry = 0;
-  if (const int rc = ring_acquire(c, &entry)) return rc;
-  const ResizeBatchDesc* d_desc = nullptr;
-  int rc = resize_batch_stage(c, items, n, dw, dh, s, entry, &d_desc);
-  if (!rc) {
-    const hipError_t e = launch_resize_bgr_batch(d_desc, n, dw, dh, s);
-    if (e != hipSuccess) { report(c, c->ondebug, c->caller_ctx, "error: HIP %s while resizing a batch\n", hipGetErrorString(e)); rc = BSX_EDEVICE; }
-  }
-  return ids_release(c, entry, s, rc);
+  const int planned = resize_bgr_batch_plan(items, n, c->n_streams, dw, dh, &c->pic_plan);
+  const DevResizeTab* t = nullptr;
+  return picture_batch_call<ResizeBatchDesc>(c, "bsx_resize_bgr_batch", planned, &c->rsz_ring, false, "resizing a batch", stream,
+    [&](int i, ResizeBatchDesc* d) {
+      const bsx_resize_item& it = items[i];
+      if (const int rc = bg_tab(c, it.sw, it.sh, dw, dh, &t)) return rc;
+      *d = ResizeBatchDesc{it.d_src, it.d_dst, t->tab.xofs, t->tab.xa, t->tab.yofs, t->tab.ya, t->tab.sw, t->tab.sh, t->tab.mode, 0};
+      return (int)BSX_OK;
+    },
+    [&](const ResizeBatchDesc* d, const PictureGrid&, hipStream_t s) { return launch_resize_bgr_batch(d, n, dw, dh, s); });
 }
 
 int bsx_flip_bgr(bsx_ctx* c, const uint8_t* d_src, uint8_t* d_dst, int w, int h, int n, int code, void* stream) {
@@ -2070,65 +1903,44 @@ int bsx_gaussian_blur_bgr(bsx_ctx* c, const uint8_t* d_src, uint8_t* d_dst, int 
 // the ragged grid's spans by value
 int bsx_gaussian_blur_bgr_batch(bsx_ctx* c, const bsx_blur_item* items, int n, void* stream) {
   if (!c) return BSX_EINVAL;
-  GeomSpans spans{};
-  BlurTileCols cols{};
-  if (const int rc = blur_batch_check(c, "bsx_gaussian_blur_bgr_batch", items, n, &spans, &cols)) return rc;
-  if (n == 0) return BSX_OK;
-  DeviceGuard guard(c->device);
-  hipStream_t s = pick(c, stream);
-  int entry = 0;
-  if (const int rc = ring_acquire(c, &entry)) return rc;
-  const BlurDesc* d_desc = nullptr;
-  int rc = blur_batch_stage(c, items, n, spans, s, entry, &d_desc);
-  if (!rc) {
-    const hipError_t e = launch_blur_batch(d_desc, c->d_blur_coef, spans, cols, s);
-    if (e != hipSuccess) { report(c, c->ondebug, c->caller_ctx, "error: HIP %s while blurring a batch\n", hipGetErrorString(e)); rc = BSX_EDEVICE; }
-  }
-  return ids_release(c, entry, s, rc);
+  const int planned = blur_bgr_batch_plan(items, n, c->n_streams, &c->pic_plan);
+  return picture_batch_call<BlurDesc>(c, "bsx_gaussian_blur_bgr_batch", planned, &c->blur_ring, true, "blurring a batch", stream,
+    [&](int i, BlurDesc* d) {
+      const bsx_blur_item& it = items[i];
+      *d = BlurDesc{it.d_src, it.d_dst, it.w, it.h, it.ksize, it.flags & kGeomYuyvIn};
+      return (int)BSX_OK;
+    },
+    [&](const BlurDesc* d, const PictureGrid& g, hipStream_t s) { return launch_blur_batch(d, c->d_blur_coef, g.spans, g.cols, s); });
 }
 
 // n NV12 surfaces, each of its own size, pitches and blur size, blurred into BGR images in ONE launch: planned and checked on the host, the descriptors ordered by size
 // through the staging ring, the ragged grid's spans by value
 int bsx_gaussian_blur_surfaces_batch(bsx_ctx* c, const bsx_blur_surface_item* items, int n, void* stream) {
   if (!c) return BSX_EINVAL;
-  BlurSurfacesPlan plan;
-  GeomSpans spans{};
-  BlurTileCols cols{};
-  if (const int rc = blur_surfaces_check(c, "bsx_gaussian_blur_surfaces_batch", items, n, &plan, &spans, &cols)) return rc;
-  if (n == 0) return BSX_OK;
-  DeviceGuard guard(c->device);
-  hipStream_t s = pick(c, stream);
-  int entry = 0;
-  if (const int rc = ring_acquire(c, &entry)) return rc;
-  const BlurSurfDesc* d_desc = nullptr;
-  int rc = blur_surfaces_stage(c, items, n, plan, s, entry, &d_desc);
-  if (!rc) {
-    const hipError_t e = launch_blur_surfaces(d_desc, c->d_blur_coef, spans, cols, s);
-    if (e != hipSuccess) { report(c, c->ondebug, c->caller_ctx, "error: HIP %s while blurring a batch of surfaces\n", hipGetErrorString(e)); rc = BSX_EDEVICE; }
-  }
-  return ids_release(c, entry, s, rc);
+  const int planned = blur_surfaces_plan(items, n, c->n_streams, &c->pic_plan);
+  return picture_batch_call<BlurSurfDesc>(c, "bsx_gaussian_blur_surfaces_batch", planned, &c->blur_surf_ring, true, "blurring a batch of surfaces", stream,
+    [&](int i, BlurSurfDesc* d) {
+      const bsx_blur_surface_item& it = items[i];
+      *d = BlurSurfDesc{it.d_y, it.d_uv, it.d_dst, it.pitch_y, it.pitch_uv, it.w, it.h, it.ksize, 0u};
+      return (int)BSX_OK;
+    },
+    [&](const BlurSurfDesc* d, const PictureGrid& g, hipStream_t s) { return launch_blur_surfaces(d, c->d_blur_coef, g.spans, g.cols, s); });
 }
 
 // n NV12 surfaces, each of its own size and pitches, resized to BGR images of their own sizes in ONE launch: planned and checked on the host, the descriptors ordered by
 // destination size through the staging ring, the ragged grid's spans and the classes' sizes by value
 int bsx_resize_surfaces_batch(bsx_ctx* c, const bsx_resize_surface_item* items, int n, void* stream) {
   if (!c) return BSX_EINVAL;
-  ResizeSurfacesPlan plan;
-  GeomSpans spans{};
-  ResizeDstSizes sizes{};
-  if (const int rc = resize_surfaces_check(c, "bsx_resize_surfaces_batch", items, n, &plan, &spans, &sizes)) return rc;
-  if (n == 0) return BSX_OK;
-  DeviceGuard guard(c->device);
-  hipStream_t s = pick(c, stream);
-  int entry = 0;
-  if (const int rc = ring_acquire(c, &entry)) return rc;
-  const ResizeSurfDesc* d_desc = nullptr;
-  int rc = resize_surfaces_stage(c, items, n, plan, s, entry, &d_desc);
-  if (!rc) {
-    const hipError_t e = launch_resize_surfaces(d_desc, spans, sizes, s);
-    if (e != hipSuccess) { report(c, c->ondebug, c->caller_ctx, "error: HIP %s while resizing a batch of surfaces\n", hipGetErrorString(e)); rc = BSX_EDEVICE; }
-  }
-  return ids_release(c, entry, s, rc);
+  const int planned = resize_surfaces_plan(items, n, c->n_streams, &c->pic_plan);
+  const DevResizeTab* t = nullptr;
+  return picture_batch_call<ResizeSurfDesc>(c, "bsx_resize_surfaces_batch", planned, &c->rsz_surf_ring, false, "resizing a batch of surfaces", stream,
+    [&](int i, ResizeSurfDesc* d) {
+      const bsx_resize_surface_item& it = items[i];
+      if (const int rc = bg_tab(c, it.sw, it.sh, it.dw, it.dh, &t)) return rc;
+      *d = ResizeSurfDesc{it.d_y, it.d_uv, it.d_dst, t->tab.xofs, t->tab.xa, t->tab.yofs, t->tab.ya, it.pitch_y, it.pitch_uv, it.sw, it.sh, t->tab.mode, 0};
+      return (int)BSX_OK;
+    },
+    [&](const ResizeSurfDesc* d, const PictureGrid& g, hipStream_t s) { return launch_resize_surfaces(d, g.spans, g.sizes, s); });
 }
 
 int bsx_bgr_to_yuyv(bsx_ctx* c, const uint8_t* d_bgr, uint8_t* d_yuyv, int w, int h, int n, void* stream) {

@@ -5,31 +5,14 @@
 //   GeomsRequest              the call as its entry point received it, plus the two facts of the context's state the rules ask for;
 //   geoms_check               every rule, in one order (below); leaves the spans, the class of every item, the plan of the output records and, for surfaces, the
 //                             items in the form the front end reads in a GeomsChecked;
-//   Span / spans_overlap      the overlap sweep, also used by the resize and blur batches (bsx_api.hip).
+// The overlap sweep is span_overlap.hpp's.
 // The order of the rules decides which refusal a caller sees when several are broken: items NULL; the vcam step's output size; the batch flags; a pending pipelined
 // composite; an onmask callback; the vcam step's odd YUYV width; the items in index order; the plan of the records; the overlaps.
 #pragma once
-#include <algorithm>
-
+#include "span_overlap.hpp"
 #include "vcam_nv12_plan.hpp"
 
 namespace bsx {
-struct Span { uintptr_t begin, end; int item; bool dst; };
-// Does a destination among the spans overlap a source or another destination?  Sorted by address, one sweep; *d = the destination (named first: it is the one the
-// caller placed wrongly), *o = what it overlaps.
-inline bool spans_overlap(std::vector<Span>& sp, const Span** d, const Span** o) {
-  std::sort(sp.begin(), sp.end(), [](const Span& a, const Span& b) { return a.begin < b.begin; });
-  const Span* far_any = nullptr;   // of the spans that begin at or below the current one: the one that ends last, and the destination that ends last
-  const Span* far_dst = nullptr;
-  for (const Span& v : sp) {
-    const Span* hit = v.dst ? far_any : far_dst;
-    if (hit && hit->end > v.begin) { *d = v.dst ? &v : hit; *o = v.dst ? hit : &v; return true; }
-    if (!far_any || v.end > far_any->end) far_any = &v;
-    if (v.dst && (!far_dst || v.end > far_dst->end)) far_dst = &v;
-  }
-  return false;
-}
-
 // every entry point that advances the temporal state refuses while the two-deep pipeline holds a composite that reads it
 constexpr char kPendingComposite[] = "a pipelined composite is pending (flush with bsx_step_batch_pipelined(ctx, NULL, ...) first)";
 

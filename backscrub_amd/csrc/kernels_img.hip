@@ -3005,7 +3005,7 @@ hipError_t launch_nv12_to_bgr(const uint8_t* y, int pitch_y, const uint8_t* uv, 
 //     (sh = 0, its own coefficient record): pixel (gx, gy) after BOTH reflections, its chroma row (gy >> 1) that of the reflected row;
 //   * NT, the output form (dwords from the packed tile where w % 4 == 0 and dst is 4-byte aligned, else byte stores from the vertical pass) and ksize 1 (the converted
 //     pixels, stored without LDS) as in blur_batch_k.
-// Offsets into the planes and into dst are 32-bit: the host refuses a plane of 2^31 bytes or more and w * h * 3 >= 2^31 (blur_surfaces_plan.hpp).
+// Offsets into the planes and into dst are 32-bit: the host refuses a plane of 2^31 bytes or more and w * h * 3 >= 2^31 (picture_batch_plan.hpp).
 // A template of one instance in a namespace of its own at the end of the file, launched by the file's last launcher, for the reason given above mask_geoms_k: every
 // earlier kernel's text is what it was.
 namespace {
@@ -3133,7 +3133,7 @@ hipError_t launch_blur_surfaces(const BlurSurfDesc* desc, const GaussCoef* coef,
 //   * the lower row's taps are the upper row's where the rows clamp onto one another, and its chroma words are the upper row's where both rows lie in one chroma row
 //     (an even upper row): nothing is loaded twice that the lane already holds.
 // Offsets into the planes and into dst are 32-bit from uniform bases: the host refuses a plane of 2^31 bytes or more and dw * dh * 3 >= 2^31
-// (resize_surfaces_plan.hpp).  No LDS: at a down-scale of 2 or more the taps of neighbouring outputs do not overlap.
+// (picture_batch_plan.hpp).  No LDS: at a down-scale of 2 or more the taps of neighbouring outputs do not overlap.
 // A template of one instance in a namespace of its own at the end of the file, launched by the file's last launcher, for the reason given above mask_geoms_k: every
 // earlier kernel's text is what it was.
 namespace {

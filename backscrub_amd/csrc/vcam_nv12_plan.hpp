@@ -7,12 +7,10 @@
 // What belongs to the surface is checked here, for every record, before the rules the two entry points share (the fifth record of an item, the fifth size): item,
 // a positive and even size, the pitches, the planes.  Overlaps are not judged here (bsx_api.hip), but the extent they are judged on is: vcam_nv12_extent.
 #pragma once
+#include "span_overlap.hpp"
 #include "vcam_outs_plan.hpp"
 
 namespace bsx {
-// the bytes from a plane's first to one past its last written byte: `rows` rows of `w` bytes, `pitch` apart
-inline size_t vcam_nv12_extent(int pitch, int rows, int w) { return (size_t)pitch * (size_t)(rows - 1) + (size_t)w; }
-
 inline int vcam_nv12_plan(const int* item_class, int n, const bsx_vcam_out_nv12* outs, int m, VcamOutsPlan* plan) {
   VcamOutsPlan& p = *plan;
   p = VcamOutsPlan{};

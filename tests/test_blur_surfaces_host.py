@@ -1,4 +1,4 @@
-"""bsx_gaussian_blur_surfaces_batch's planner (csrc/blur_surfaces_plan.hpp) on a box without a GPU, driven by a stand-alone program built with the host sanitizers and run
+"""bsx_gaussian_blur_surfaces_batch's planner (csrc/picture_batch_plan.hpp; its overlap rule: test_picture_batch_host.py) on a box without a GPU, driven by a stand-alone program built with the host sanitizers and run
 directly: every refusal with its text and index, the size classes of accepted calls whose sizes are interleaved, the ragged grid (GeomSpans) and the tiles per row
 (BlurTileCols) against a restatement in Python, eight sizes accepted and a ninth refused."""
 import os
@@ -17,7 +17,7 @@ MAIN = r"""
 // answer as one line of integers "rc bad n_sizes n_cls | cls.. | sizes.. | pos[9] | wg[9] | per[8] | ntx[8]" and the refusal text on the next line
 #include <cstdio>
 #include <vector>
-#include "blur_surfaces_plan.hpp"
+#include "picture_batch_plan.hpp"
 int main() {
   static_assert(sizeof(bsx_blur_surface_item) == 48, "the item of the header");
   int n, n_streams, null_items;
@@ -30,8 +30,8 @@ int main() {
       it.d_uv = reinterpret_cast<const uint8_t*>((uintptr_t)uv);
       it.d_dst = reinterpret_cast<uint8_t*>((uintptr_t)dst);
     }
-    bsx::BlurSurfacesPlan plan;
-    const int rc = bsx::blur_surfaces_plan(null_items ? nullptr : items.data(), n, n_streams, &plan);
+    bsx::PictureBatchPlan plan;      // (blur_surfaces_grid: the call's plan without its last rule, the overlaps — the surfaces of these cases share addresses)
+    const int rc = bsx::blur_surfaces_grid(null_items ? nullptr : items.data(), n, n_streams, &plan);
     printf("%d %d %d %zu |", rc, plan.bad, plan.n_sizes, plan.cls.size());
     for (int c : plan.cls) printf(" %d", c);
     printf(" |");

@@ -1,4 +1,4 @@
-"""bsx_resize_surfaces_batch's planner (csrc/resize_surfaces_plan.hpp) on a box without a GPU, driven by a stand-alone program built with the host sanitizers and run
+"""bsx_resize_surfaces_batch's planner (csrc/picture_batch_plan.hpp) on a box without a GPU, driven by a stand-alone program built with the host sanitizers and run
 directly: the destination-size classes numbered in the order of their first item, the stable order of interleaved classes, the ragged grid (GeomSpans) against a
 restatement in Python, every refusal with its text and index, eight output sizes accepted and a ninth refused, a grid of 2^31 workgroups, and the overlaps — judged on
 a plane's extent to byte sw of its last row."""
@@ -18,7 +18,7 @@ MAIN = r"""
 // planner's answer as one line of integers "rc bad n_sizes n_cls | cls.. | order.. | sizes.. | pos[9] | wg[9] | per[8]" and the refusal text on the next line
 #include <cstdio>
 #include <vector>
-#include "resize_surfaces_plan.hpp"
+#include "picture_batch_plan.hpp"
 int main() {
   static_assert(sizeof(bsx_resize_surface_item) == 56, "the item of the header");
   int n, n_streams, null_items;
@@ -31,7 +31,7 @@ int main() {
       it.d_uv = reinterpret_cast<const uint8_t*>((uintptr_t)uv);
       it.d_dst = reinterpret_cast<uint8_t*>((uintptr_t)dst);
     }
-    bsx::ResizeSurfacesPlan plan;
+    bsx::PictureBatchPlan plan;
     const int rc = bsx::resize_surfaces_plan(null_items ? nullptr : items.data(), n, n_streams, &plan);
     printf("%d %d %d %zu |", rc, plan.bad, plan.n_sizes, plan.cls.size());
     for (int c : plan.cls) printf(" %d", c);
